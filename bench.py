@@ -3,6 +3,7 @@
 roofline, on synthetic IQ already resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2|cfg4|cfg5|cfg1] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
 
 Default workload = BASELINE configs[2] ("cfg3", the configuration the metric is quoted on): 8 buoys
 (28 pairs), 10 MS/s, 4096-sample windows, 4096 windows batched per GPU.  The other BASELINE shapes
@@ -12,14 +13,26 @@ A step = one pass of the hot path (IQ windows -> per-pair lags) over one batch o
 Windows shard across ranks with no data-path collective -- `--scaling weak` (default): every rank owns a full
 batch; `--scaling strong`: the config's windows are block-sharded over the ranks (radio_mapper_amd.shard.window_shard,
 as BASELINE.json words cfg3/cfg4/cfg5) -- and rank 0 gathers the per-pair lag scalars once after the timed region.
-One JSON line is printed by rank 0.  Headline figures (`ms_per_step`, `value`, `roofline`) come from the region that
-follows EXACTLY `--warmup` steps of the headline shape; the same K steps after an untimed pre-warm are reported beside
-them as `ms_per_step_sustained` (+ `prewarm_steps`).  At N = 1 the default run also times the other four BASELINE
-shapes in the same process (`other_configs`, a bounded number of steps each, with per-kernel-family times;
-`--no-other-configs` skips them) and a one-GPU projection of the 1 -> 8 GPU strong-scaling curve
-(`strong_scaling_projection`) -- both run BEFORE the headline region (`region_order` says so) -- and reports the ingest
-rate, the real-time factor, and the host-pointer path for complex64 and raw uint8 input.  The line names the binary
-that ran (`build.binary_digest`) beside the digest of the sources it sees and the run refuses to start on a mismatch.
+One JSON line is printed by rank 0.  Headline figures (`ms_per_step`, `value`) come from the region of EXACTLY K timed
+steps that follows EXACTLY `--warmup` steps of the headline shape.
+
+A plain run does only what the headline needs: set-up, a short settle of the device on the headline step (SETTLE_S
+seconds, so that the warm-up starts on a device at its working clock, as it did when the other shapes ran first), the
+warm-up, the timed steps, the outputs (`--dump-outputs`) and the line.  `--full` adds everything else, as the default
+run did before: the rocprofv3 counter passes (HBM traffic, SQ counters), the same K steps after an untimed pre-warm
+(`ms_per_step_sustained` + `prewarm_steps`), per-kernel times and the `roofline` block, parity against the CPU oracle and
+the CPU baseline, and at N = 1 the other four BASELINE shapes in the same process (`other_configs`, a bounded number of
+steps each, with per-kernel-family times; `--no-other-configs` skips them) and a one-GPU projection of the 1 -> 8 GPU
+strong-scaling curve (`strong_scaling_projection`) -- both run BEFORE the headline region (`region_order` says so) --
+plus the host-pointer path for complex64 and raw uint8 input.  Every line reports the ingest rate and the real-time
+factor of the headline (arithmetic on `ms_per_step`, no run of their own).  The line names
+the binary that ran (`build.binary_digest`) beside the digest of the sources it sees and the run refuses to start on a
+mismatch.
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step (rank 0 after the gather): DIR/lag_int.npy
+(float64), DIR/lag_frac.npy and DIR/peak.npy (float32), DIR/dop_idx.npy (float64, Doppler shapes only), each
+[windows][pairs]; above 64 MB in all a fixed seeded sample of windows is written, with DIR/window_index.npy naming them.
+The inputs are generated from the config's seed, so two builds run with the same arguments see the same windows.
 
 Multi-GPU: `python bench.py --gpus N` with WORLD_SIZE unset starts its own N ranks
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`) as a CHILD process
@@ -499,6 +512,47 @@ def timed_steps(torch, sh, steps, sync_all):
     return time.perf_counter() - t0, ev0.elapsed_time(ev1)
 
 
+# A plain run's settle in front of the warm-up: a device that has just been idle needs 0.1 ... 0.3 s of load to reach its
+# working clock (LABNOTES R5.2).  Before --full existed the other shapes ran first and gave it that load.  Measured on cfg3,
+# --steps 20 --warmup 5, three runs each: 1.73-1.75 ms per step without the settle, 1.69-1.70 with it, 1.69-1.70 for the
+# default run that had the other shapes in front; at --steps 200 --warmup 30 all three read 1.69.
+SETTLE_S = 0.5
+
+
+def settle(torch, sh, seconds):
+    """untimed headline steps until `seconds` have passed, synchronised every few steps -> steps run"""
+    n, t0 = 0, time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(4):
+            sh.step()
+        n += 4
+        torch.cuda.synchronize()
+    return n
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6          # all .npy files of one --dump-outputs together, headers included
+
+
+def dump_outputs(path, outs, seed=0):
+    """outs: {name: [windows][pairs] array} -> path/<name>.npy; integer arrays as float64 (exact), the rest as float32.
+    Above DUMP_MAX_BYTES in all, the same fixed seeded sample of windows is taken from every array (window_index.npy)."""
+    import numpy as np
+    conv = {k: np.asarray(v, np.float64 if np.issubdtype(np.asarray(v).dtype, np.integer) else np.float32)
+            for k, v in outs.items()}
+    n = next(iter(conv.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in conv.values())
+    budget = DUMP_MAX_BYTES - 256 * (len(conv) + 1)        # .npy headers
+    if n * row_bytes > budget:
+        keep = max(1, (budget - 8 * n) // row_bytes)
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        conv = {k: a[idx] for k, a in conv.items()}
+        conv["window_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(conv)
+
+
 def other_config(torch, xcorr, name, dev, dev_index, sync_all, cpu_thr):
     """One of the other BASELINE shapes in the same process (N = 1): a bounded number of steps after the shape's own
     warm-up, the same bracket, parity of the timed outputs on a short subset.  Returns the dict for `other_configs`."""
@@ -617,16 +671,22 @@ def main():
                          "the figures recorded under profiles/ are used instead when their source digest matches")
     ap.add_argument("--no-host-path", action="store_true", help="skip the host-pointer legs (profiling runs)")
     ap.add_argument("--profile", action="store_true",
-                    help="the timed path and its parity only: --no-other-configs --no-projection --no-single-group --no-host-path --no-cpu-baseline")
+                    help="--full with the timed path and its parity only: --no-other-configs --no-projection --no-single-group --no-host-path --no-cpu-baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU work for cpu_baseline")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous + shard + gather only (no compute, no metric): tests the N-rank launcher")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline (counters, sustained region, per-kernel times, roofline, parity, "
+                         "CPU baseline, other shapes, projection, host-pointer legs); the --no-* options prune it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last timed step as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
     if args.profile:
         args.no_other_configs = args.no_projection = args.no_single_group = args.no_host_path = args.no_cpu_baseline = True
         args.no_pmc = True
+        args.full = True
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and env_world is None:
@@ -641,7 +701,7 @@ def main():
 
     # counters of the headline kernel, measured by child processes BEFORE this process touches the GPU (N = 1, cfg3 only)
     live_pmc = None
-    if (world == 1 and rank == 0 and args.config == "cfg3" and not args.no_pmc and not args.launch_check
+    if (args.full and world == 1 and rank == 0 and args.config == "cfg3" and not args.no_pmc and not args.launch_check
             and os.environ.get("RMX_BENCH_CHILD") != "1" and args.buoys is None and args.windows is None):
         import __graft_entry__ as ge0
         ge0.build()                       # the children must not each compile the library
@@ -747,7 +807,7 @@ def main():
     # They run BEFORE the headline region: whatever state they leave the device in is the state a service that handles
     # several shapes is in, and the headline region below is then still exactly W warm-up + K timed steps.
     others = None
-    if rank == 0 and n_gpus == 1 and args.config == "cfg3" and not args.no_other_configs:
+    if args.full and rank == 0 and n_gpus == 1 and args.config == "cfg3" and not args.no_other_configs:
         others = {}
         for name in ("cfg1", "cfg2", "cfg4", "cfg5"):
             try:
@@ -756,7 +816,7 @@ def main():
                 others[name] = {"error": f"{type(e).__name__}: {e}"}
         region_order.append("other_configs (cfg1, cfg2, cfg4, cfg5: warm-up, timed steps, parity each)")
     capture = None
-    if rank == 0 and n_gpus == 1 and args.config == "cfg3" and not args.no_other_configs:
+    if args.full and rank == 0 and n_gpus == 1 and args.config == "cfg3" and not args.no_other_configs:
         capture = {}
         for name in CAPTURE_SHAPES:
             try:
@@ -767,10 +827,14 @@ def main():
     # one-GPU projection of the 1 -> 8 GPU strong-scaling curve: the path has no collective, so G GPUs on
     # the config's job = one GPU on 1/G of its windows; timed on the resident windows of the headline shape
     projection = None
-    if rank == 0 and n_gpus == 1 and args.config == "cfg3" and not args.no_projection and not caf:
+    if args.full and rank == 0 and n_gpus == 1 and args.config == "cfg3" and not args.no_projection and not caf:
         projection = strong_scaling_projection(torch, sh, sync_all)
         region_order.append("strong_scaling_projection (cfg3 on W/G windows, G = 1, 2, 4, 8)")
 
+    settle_steps = 0
+    if not args.full:
+        settle_steps = settle(torch, sh, SETTLE_S)
+        region_order.append(f"settle ({settle_steps} untimed steps, {SETTLE_S} s)")
     for _ in range(warm):
         step()
     # (a) HEADLINE: the driver's contract and nothing else -- W warm-up steps of this shape, then exactly K timed steps
@@ -780,32 +844,44 @@ def main():
     elapsed = max_over_ranks(elapsed)
     ms_per_step = elapsed * 1e3 / steps
     region_order += [f"warmup ({warm} steps)", f"timed HEADLINE region ({steps} steps)"]
-    # (b) untimed pre-warm, then the same K steps again: a device that has just been idle needs some hundred
-    # milliseconds of load to settle on its sustained clock; "prewarm_steps" counts everything that ran between the
-    # headline region and the sustained one
+    # what the timed path returned in its last step, for --dump-outputs (read back outside the timed region)
+    timed_out = None
+    if args.dump_outputs:
+        timed_out = {"lag_int": lag.cpu().numpy(), "lag_frac": frac.cpu().numpy(), "peak": peak.cpu().numpy()}
+        if caf:
+            timed_out["dop_idx"] = sh.dop.cpu().numpy()
+        if world > 1:
+            bucket = [None] * world if rank == 0 else None
+            dist.gather_object(timed_out, bucket, dst=0)
+            timed_out = {k: np.concatenate([b[k] for b in bucket], axis=0) for k in timed_out} if rank == 0 else None
+    ms_per_step_sustained = None
     prewarm = 0
-    if args.config == "cfg3":
-        prewarm = max(0, int(os.environ.get("RMX_BENCH_PREWARM", "300")) - warm - steps)
-    for _ in range(prewarm):
-        step()
-    sus_elapsed, sus_region_ms = timed_steps(torch, sh, steps, sync_all)
-    ms_per_step_sustained = max_over_ranks(sus_elapsed) * 1e3 / steps
-    region_order += [f"prewarm ({prewarm} steps)", f"timed sustained region ({steps} steps)"]
-    # kernel durations from HIP events bracketing every launch on the launch stream: a few more steps with option
-    # "timing" on, a read-back after each (OUTSIDE the timed regions: two event records per launch are a tenth of a
-    # cfg1 step, which is five launches of 6-22 us)
     fwd_ms = pair_ms = 0.0
     fwd_n = pair_n = 0
     n_meas = max(min(steps, 10 if not caf else 1), 1)
     by_kernel = None
-    eng.set_option("timing", 1)
-    for k in range(n_meas):
-        step()
-        tm = eng.last_timing()
-        fwd_ms += tm["fwd_ms"]; fwd_n += tm["fwd_launches"]
-        pair_ms += tm["pair_ms"]; pair_n += tm["pair_launches"]
-        by_kernel = eng.last_timing_by_kernel()
-    eng.set_option("timing", 0)
+    if args.full:
+        # (b) untimed pre-warm, then the same K steps again: a device that has just been idle needs some hundred
+        # milliseconds of load to settle on its sustained clock; "prewarm_steps" counts everything that ran between the
+        # headline region and the sustained one
+        if args.config == "cfg3":
+            prewarm = max(0, int(os.environ.get("RMX_BENCH_PREWARM", "300")) - warm - steps)
+        for _ in range(prewarm):
+            step()
+        sus_elapsed, sus_region_ms = timed_steps(torch, sh, steps, sync_all)
+        ms_per_step_sustained = max_over_ranks(sus_elapsed) * 1e3 / steps
+        region_order += [f"prewarm ({prewarm} steps)", f"timed sustained region ({steps} steps)"]
+        # kernel durations from HIP events bracketing every launch on the launch stream: a few more steps with option
+        # "timing" on, a read-back after each (OUTSIDE the timed regions: two event records per launch are a tenth of a
+        # cfg1 step, which is five launches of 6-22 us)
+        eng.set_option("timing", 1)
+        for k in range(n_meas):
+            step()
+            tm = eng.last_timing()
+            fwd_ms += tm["fwd_ms"]; fwd_n += tm["fwd_launches"]
+            pair_ms += tm["pair_ms"]; pair_n += tm["pair_launches"]
+            by_kernel = eng.last_timing_by_kernel()
+        eng.set_option("timing", 0)
     seen = ranks_seen()
 
     # PCIe-inclusive rate of the same step through the host-pointer entry of the C ABI (reported, never `value`):
@@ -813,7 +889,7 @@ def main():
     # I/Q (2 B/sample; the synthetic windows sit on the rtl_sdr grid, so raw = x + 127.5 exactly and the lags must agree)
     host_ms = host_u8_ms = dev_u8_ms = None
     host_u8_same = None
-    if rank == 0 and n_gpus == 1 and args.config == "cfg3" and not args.no_host_path:
+    if args.full and rank == 0 and n_gpus == 1 and args.config == "cfg3" and not args.no_host_path:
         xh = x.cpu().numpy().view(np.complex64).reshape(W, B, N)
         eng.correlate(xh[:64])
         th = time.perf_counter()
@@ -863,7 +939,7 @@ def main():
     parity = None
     cpu = None
     single = None
-    if rank == 0:
+    if args.full and rank == 0:
         parity = sh.parity(cpu_threads())
         if n_gpus == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(sh.host_windows, W, B, N, args.cpu_budget, doppler=sh.grid)
@@ -889,39 +965,11 @@ def main():
     if rank == 0:
         units_per_step = W_total * P * N * D                  # IQ samples cross-correlated per step
         value = units_per_step / (ms_per_step * 1e-3)
-        if fused:
-            launches_per_step = max(pair_n / n_meas, 1.0)
-            kernel = "k_win (fused forward + pair kernel), one launch per step"
-            launch_ms = region_ms / (steps * launches_per_step)
-            launch_ms_sustained = sus_region_ms / (steps * launches_per_step)
-            isolated_launch_ms = pair_ms / max(pair_n, 1)
-        else:
-            # multi-kernel paths: the figure is for the whole kernel sequence of one step (HIP events on the
-            # launch stream around the timed region); per-kernel durations are in profiles/r04_<cfg>_*
-            launches_per_step = 1.0
-            kernel = ("rmx_caf_batch kernel sequence (un-rotated spectra once; per Doppler bin: de-rotated forward "
-                      "g_cols_fwd + g_rows, g_rows_anchor(product, inverse), g_cols_inv, g_final, k_caf_select)" if caf else
-                      ("four-step sequence g_cols_fwd + g_rows_fused (forward rows, products, inverse rows) + g_cols_inv "
-                       "+ g_final" if B <= 4 and W >= 4 else
-                       "four-step sequence g_cols_fwd + g_rows + g_rows(product, inverse) + g_cols_inv + g_final"))
-            launch_ms = region_ms / steps
-            launch_ms_sustained = sus_region_ms / steps
-            isolated_launch_ms = None
-        alg_bytes_per_launch = alg_bytes_per_step_gpu / launches_per_step
-        achieved = alg_bytes_per_launch / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
-        traffic, traffic_src = recorded_traffic(args.config)
-        if live_pmc and live_pmc.get("hbm_bytes_per_launch"):
-            traffic = live_pmc["hbm_bytes_per_launch"]
-            traffic_src = (f"measured in this run: {live_pmc['method']}; {'; '.join(live_pmc['passes'])}; {live_pmc['note']} "
-                           f"({live_pmc['seconds']:.0f} s)")
-        elif live_pmc:
-            traffic_src = (traffic_src or "no recorded figure") + f" [in-run measurement failed: {live_pmc.get('error') or live_pmc.get('passes')}]"
         ingest = W_total * B * N / (ms_per_step * 1e-3)       # input samples taken in per second, all ranks
         line = {
             "metric": "IQ samples cross-correlated per second" + (" (pair-window-Doppler-bin samples)" if caf else ""),
             "value": value, "unit": "samples/s", "n_gpus": n_gpus, "ranks_seen": seen, "steps": steps,
             "warmup": warm, "engine_calls": calls_headline, "ms_per_step": ms_per_step,
-            "ms_per_step_sustained": ms_per_step_sustained, "prewarm_steps": prewarm,
             "region_order": region_order,
             "build": {"binary_digest": build_info.get("source_digest"), "source_digest": src_digest,
                       "library": os.path.relpath(xcorr.library_path(), ROOT), "info": build_info.get("text")},
@@ -931,37 +979,70 @@ def main():
                        "n_buoys": B, "n_pairs": P, "n_samples": N, "windows_per_gpu": W, "channels": C,
                        "doppler_bins": D if caf else None,
                        "windows_total": W_total, "parallelism": f"windows sharded x{n_gpus}, no collective"},
-            # `bound` is the roofline north_star declares for the path and the one `frac` is taken against; `limiter` is the
-            # resource the counters say the dominant kernel actually waits on
-            "roofline": {"bound": "hbm", "limiter": "fp32-valu-issue" if fused else "hbm (two passes per transform) + CU-side issue",
-                         "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "alg_bytes_per_launch": alg_bytes_per_launch,
-                         "launch_ms": launch_ms, "launch_ms_sustained": launch_ms_sustained,
-                         "frac_sustained": alg_bytes_per_launch / (launch_ms_sustained * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "isolated_launch_ms": isolated_launch_ms,
-                         "kernel_ms_per_step": by_kernel,
-                         "fwd_kernel_ms_per_step": fwd_ms / n_meas,
-                         "pair_kernel_ms_per_step": pair_ms / n_meas,
-                         "whole_path_frac": alg_bytes_per_step_gpu / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "whole_path_frac_sustained": alg_bytes_per_step_gpu / (ms_per_step_sustained * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "valu": recorded_valu(launch_ms, live_pmc) if fused else None,
-                         "counters": recorded_counters(launch_ms, live_pmc) if fused else None,
-                         "fp32_valu_and_lds": "DESIGN.md section 7: the fused kernel is bound by fp32 VALU issue (70 % of the launch "
-                                              "with DPP / compare forms weighted), not by HBM"},
             "ingest_samples_per_s": ingest,
             "realtime_factor": ingest / (B * fs),               # seconds of every buoy's signal processed per second
-            "host_path_ms_per_step": host_ms,
-            "host_path_u8_ms_per_step": host_u8_ms,
-            "host_path_u8_identical": host_u8_same,
-            "device_u8_ms_per_step": dev_u8_ms,                 # raw uint8 I/Q resident in HBM (RMX_IN_U8 | RMX_IN_DEVICE)
-            "single_group": single,
-            "strong_scaling_projection": projection,
-            "other_configs": others,
-            "reference_capture_lengths": capture,
-            "cpu_baseline": cpu,
-            "parity": parity,
         }
+        if args.full:
+            if fused:
+                launches_per_step = max(pair_n / n_meas, 1.0)
+                kernel = "k_win (fused forward + pair kernel), one launch per step"
+                launch_ms = region_ms / (steps * launches_per_step)
+                launch_ms_sustained = sus_region_ms / (steps * launches_per_step)
+                isolated_launch_ms = pair_ms / max(pair_n, 1)
+            else:
+                # multi-kernel paths: the figure is for the whole kernel sequence of one step (HIP events on the
+                # launch stream around the timed region); per-kernel durations are in profiles/r04_<cfg>_*
+                launches_per_step = 1.0
+                kernel = ("rmx_caf_batch kernel sequence (un-rotated spectra once; per Doppler bin: de-rotated forward "
+                          "g_cols_fwd + g_rows, g_rows_anchor(product, inverse), g_cols_inv, g_final, k_caf_select)" if caf else
+                          ("four-step sequence g_cols_fwd + g_rows_fused (forward rows, products, inverse rows) + g_cols_inv "
+                           "+ g_final" if B <= 4 and W >= 4 else
+                           "four-step sequence g_cols_fwd + g_rows + g_rows(product, inverse) + g_cols_inv + g_final"))
+                launch_ms = region_ms / steps
+                launch_ms_sustained = sus_region_ms / steps
+                isolated_launch_ms = None
+            alg_bytes_per_launch = alg_bytes_per_step_gpu / launches_per_step
+            achieved = alg_bytes_per_launch / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
+            traffic, traffic_src = recorded_traffic(args.config)
+            if live_pmc and live_pmc.get("hbm_bytes_per_launch"):
+                traffic = live_pmc["hbm_bytes_per_launch"]
+                traffic_src = (f"measured in this run: {live_pmc['method']}; {'; '.join(live_pmc['passes'])}; {live_pmc['note']} "
+                               f"({live_pmc['seconds']:.0f} s)")
+            elif live_pmc:
+                traffic_src = (traffic_src or "no recorded figure") + f" [in-run measurement failed: {live_pmc.get('error') or live_pmc.get('passes')}]"
+            line.update({
+                "ms_per_step_sustained": ms_per_step_sustained, "prewarm_steps": prewarm,
+                # `bound` is the roofline north_star declares for the path and the one `frac` is taken against; `limiter` is the
+                # resource the counters say the dominant kernel actually waits on
+                "roofline": {"bound": "hbm", "limiter": "fp32-valu-issue" if fused else "hbm (two passes per transform) + CU-side issue",
+                             "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                             "alg_bytes_per_launch": alg_bytes_per_launch,
+                             "launch_ms": launch_ms, "launch_ms_sustained": launch_ms_sustained,
+                             "frac_sustained": alg_bytes_per_launch / (launch_ms_sustained * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "isolated_launch_ms": isolated_launch_ms,
+                             "kernel_ms_per_step": by_kernel,
+                             "fwd_kernel_ms_per_step": fwd_ms / n_meas,
+                             "pair_kernel_ms_per_step": pair_ms / n_meas,
+                             "whole_path_frac": alg_bytes_per_step_gpu / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "whole_path_frac_sustained": alg_bytes_per_step_gpu / (ms_per_step_sustained * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "valu": recorded_valu(launch_ms, live_pmc) if fused else None,
+                             "counters": recorded_counters(launch_ms, live_pmc) if fused else None,
+                             "fp32_valu_and_lds": "DESIGN.md section 7: the fused kernel is bound by fp32 VALU issue (70 % of the launch "
+                                                  "with DPP / compare forms weighted), not by HBM"},
+                "host_path_ms_per_step": host_ms,
+                "host_path_u8_ms_per_step": host_u8_ms,
+                "host_path_u8_identical": host_u8_same,
+                "device_u8_ms_per_step": dev_u8_ms,                 # raw uint8 I/Q resident in HBM (RMX_IN_U8 | RMX_IN_DEVICE)
+                "single_group": single,
+                "strong_scaling_projection": projection,
+                "other_configs": others,
+                "reference_capture_lengths": capture,
+                "cpu_baseline": cpu,
+                "parity": parity,
+            })
+        if args.dump_outputs:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, timed_out)}
         print(json.dumps(line), flush=True)
     if world > 1:
         barrier()

@@ -173,3 +173,32 @@ def test_reference_capture_shapes_are_complete_bench_shapes():
         assert c["W"] * c["B"] * c["N"] * 8 < 2 ** 30
     # the BASELINE shapes are untouched by the addition
     assert [k for k in bench.CONFIGS if k.startswith("cfg")] == ["cfg1", "cfg2", "cfg3", "cfg4", "cfg5"]
+
+
+def test_dump_outputs_float_arrays_and_seeded_sample_under_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: integer outputs as float64, float outputs as float32, values unchanged; above the cap the same
+    seeded sample of windows from every array, named by window_index.npy, and the files together stay under the cap."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    outs = {"lag_int": rng.integers(-4095, 4096, (300, 28)).astype(np.int32),
+            "lag_frac": rng.uniform(-0.5, 0.5, (300, 28)).astype(np.float32),
+            "peak": rng.uniform(0, 1e6, (300, 28)).astype(np.float32)}
+    names = bench.dump_outputs(str(tmp_path / "all"), outs)
+    assert names == ["lag_frac", "lag_int", "peak"]
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in names}
+    assert got["lag_int"].dtype == np.float64 and got["lag_frac"].dtype == np.float32 and got["peak"].dtype == np.float32
+    assert all(np.array_equal(got[k], outs[k]) for k in names)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20000)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), outs) == ["lag_frac", "lag_int", "peak", "window_index"]
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 20000
+    idx = np.load(tmp_path / "s1" / "window_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "window_index.npy")) and 0 < len(idx) < 300
+    assert np.array_equal(np.load(tmp_path / "s1" / "lag_int.npy"), outs["lag_int"][idx.astype(int)])
+
+
+def test_plain_run_options():
+    """a plain run times the headline only; --full brings back everything else, --dump-outputs names a directory"""
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

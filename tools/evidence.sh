@@ -7,8 +7,8 @@ cd $GRAFT_REPO_ROOT
 part=${EVIDENCE_PART:-all}      # a: tests, bench lines, profiles and counters of the BASELINE shapes; b: the N = 8192 / 16384 tables; all: both
 if [ "$part" != b ]; then
 python -m pytest tests -m gpu -x -q > gpurun_out/${tag}_final_pytest.log 2>&1; echo "pytest rc=$?"; tail -2 gpurun_out/${tag}_final_pytest.log
-# (the default line = cfg3 with the other four shapes inside it; the per-shape lines below are each shape's own full line)
-for c in cfg3 cfg2 cfg4 cfg5 cfg1; do python bench.py --config $c > gpurun_out/${tag}_bench_$c.log 2>&1; echo "$c rc=$?"; tail -1 gpurun_out/${tag}_bench_$c.log | cut -c1-200; tail -1 gpurun_out/${tag}_bench_$c.log > profiles/${tag}_bench_$c.json; done
+# (the --full line of cfg3 has the other four shapes inside it; the per-shape lines are each shape's own --full line)
+for c in cfg3 cfg2 cfg4 cfg5 cfg1; do log=$(mktemp); python bench.py --full --config $c > $log 2>&1; echo "$c rc=$?"; tail -1 $log | cut -c1-200; tail -1 $log > profiles/${tag}_bench_$c.json; done
 tools/profile.sh $tag > gpurun_out/profile_$tag.log 2>&1; python tools/summarize_prof.py gpurun_out/prof_$tag $tag | tail -2
 for c in cfg2 cfg4 cfg5 cfg1; do tools/profile.sh ${tag}_$c $c > gpurun_out/profile_${tag}_$c.log 2>&1; python tools/summarize_prof.py gpurun_out/prof_${tag}_$c ${tag}_$c $c | tail -2; done
 # cfg1 (one window per call, five launches): durations and gaps between consecutive kernels of a step from the kernel trace
