@@ -136,6 +136,27 @@ void rmx_clear_default_options(void);
 int rmx_xcorr_batch(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                     int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
 
+/* rmx_xcorr_batch with the peak search restricted to a caller-given lag window per (window, pair): the physical
+ * interval |lag| <= baseline / c + timing uncertainty of a TDoA pair, outside which every peak is false (an echo, a
+ * co-channel transmitter, a periodic component, the wrap-around of a short window).
+ *   lag_bounds  host int32 [lo, hi] in lag units (lag = k - (N-1)): [n_windows][n_pairs][2] when bounds_per_window is
+ *               non-zero, else [n_pairs][2] shared by every window.  -(N-1) <= lo <= hi <= N-1, else RMX_E_INVAL (the
+ *               window, pair and values in rmx_last_error).  The library copies the array through its own staging: the
+ *               caller may reuse it as soon as the call returns, with RMX_OUT_DEVICE too.
+ * Contract: S4-S6 above applied to the SLICE m[lo+N-1 .. hi+N-1] of the 'full' magnitude vector:
+ *         k    = argmax over the slice (ties -> lowest k)   lag_int = k - (N-1), always in [lo, hi]
+ *         lag_frac = the same parabola on m[k-1], m[k], m[k+1] when lo < lag_int < hi, and 0 when lag_int is lo or hi
+ *         peak = m[k]
+ *   with the same parity rules, computed on the slice (bit-exact lag_int wherever the oracle's top-two margin WITHIN the
+ *   slice exceeds 1e-5; lowest index on exact ties; lag_frac within 1e-5 or the flat-peak bound).  The full interval
+ *   [-(N-1), N-1] gives outputs bit-identical to rmx_xcorr_batch (a call whose every interval is the full one IS that
+ *   call; a bounded call otherwise avoids the whole-window kernels g_win_* for N != 4096, 8192, 16384 -- batches of
+ *   such N then run the per-transform kernels, whose float rounding of lag_frac may differ in the last bits).  Every other argument and flag means what it means
+ *   there (RMX_IN_DEVICE, RMX_OUT_DEVICE, RMX_IN_U8, custom pair lists, chunking, the pipelined host-pointer path). */
+int rmx_xcorr_batch_bounded(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                            const int32_t* lag_bounds, int bounds_per_window,
+                            int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
+
 /* Cross-ambiguity variant of the hot path (BASELINE configs[4]): for
  * every window and pair (i, j) the later buoy's window is de-rotated by each Doppler hypothesis,
  *     c_d = correlate(x[w][j] * exp(-2*pi*i*doppler_cps[d]*n), x[w][i], 'full', 'fft'),

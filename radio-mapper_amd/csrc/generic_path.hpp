@@ -486,12 +486,15 @@ struct GPair {
     int i, j;
 };
 
+template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation, lag_bounds.hpp)
 __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ spec, const float2* __restrict__ spec_j,
                                                           const float2* __restrict__ tw,
                                                           const GPair* __restrict__ pairs, int n_pairs,
                                                           int n_buoys, int N, int logL, long first_window,
                                                           float out_scale, int* __restrict__ lag_int,
-                                                          float* __restrict__ lag_frac, float* __restrict__ peak) {
+                                                          float* __restrict__ lag_frac, float* __restrict__ peak,
+                                                          LB... lb_pack) {
+    constexpr bool BOUNDED = sizeof...(LB) > 0;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     float2* x = reinterpret_cast<float2*>(gsm);
     const int L = 1 << logL, tid = threadIdx.x, nthr = blockDim.x;
@@ -507,9 +510,14 @@ __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ 
     lds_dit_inv(x, logL, tw, tid, nthr);
     float best = -1.0f;
     int bk = 0x7fffffff;
+    [[maybe_unused]] int klo = 0, khi = 0;
+    if constexpr (BOUNDED) lag_window(lag_bounds_of(lb_pack...), first_window + wl, q, N - 1, klo, khi);
     for (int m = tid; m < L; m += nthr) {
         const int k = full_index(m, N);
         if (k < 0) continue;
+        if constexpr (BOUNDED) {
+            if ((unsigned)(k - klo) > (unsigned)(khi - klo)) continue;   // outside the lag window
+        }
         const float2 e = x[lp(m)];
         const float v = e.x * e.x + e.y * e.y;
         if (v > best || (v == best && k < bk)) { best = v; bk = k; }
@@ -518,10 +526,18 @@ __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ 
     if (tid == 0) {
         const float b = sqrtf(best) * out_scale;
         float frac = 0.0f;
+        if constexpr (BOUNDED) {   // frac = 0 at the lag window's edges
+            if (bk > klo && bk < khi) {
+                const float2 ra = x[lp(circ_index(bk - 1, N))], rc = x[lp(circ_index(bk + 1, N))];
+                frac = parabola(sqrtf(ra.x * ra.x + ra.y * ra.y) * out_scale, b,
+                                sqrtf(rc.x * rc.x + rc.y * rc.y) * out_scale);
+            }
+        } else {
         if (bk > 0 && bk < 2 * N - 2) {
             const float2 ra = x[lp(circ_index(bk - 1, N))], rc = x[lp(circ_index(bk + 1, N))];
             frac = parabola(sqrtf(ra.x * ra.x + ra.y * ra.y) * out_scale, b,
                             sqrtf(rc.x * rc.x + rc.y * rc.y) * out_scale);
+        }
         }
         const long o = (first_window + wl) * (long)n_pairs + q;
         lag_int[o] = bk - (N - 1);
@@ -1709,9 +1725,12 @@ struct GTile {
     int k;          // its lowest 'full' index
     float tm, tp;   // |r|^2 at k-1, k+1, or -1 where that lag lives in another tile (or does not exist)
 };
-template <int kColLogT, int L1C = 0>
+// LB: empty, or one LagBounds (the bounded instantiation: candidates outside the slot's lag window are skipped; the LDS
+// image keeps every |r|^2, so the taps and the halo are those of the unbounded kernel)
+template <int kColLogT, int L1C = 0, class... LB>
 __global__ __launch_bounds__(1024) void g_cols_inv(const float2* __restrict__ in, const float2* __restrict__ tw, int l1_arg,
-                                                   int l2, GTile* __restrict__ rec, float* __restrict__ halo) {
+                                                   int l2, GTile* __restrict__ rec, float* __restrict__ halo, LB... lb_pack) {
+    constexpr bool BOUNDED = sizeof...(LB) > 0;
     constexpr int kColT = 1 << kColLogT;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     float2* x = reinterpret_cast<float2*>(gsm);
@@ -1727,6 +1746,8 @@ __global__ __launch_bounds__(1024) void g_cols_inv(const float2* __restrict__ in
     const float2* src = in + (long)blockIdx.y * L;
     float best = -1.0f;
     int bk = 0x7fffffff;
+    int klo = 0, khi = 0;
+    if constexpr (BOUNDED) lag_window_slot(lag_bounds_of(lb_pack...), blockIdx.y, N - 1, klo, khi);
     // first pass straight from HBM (a thread's 2^M inputs are neighbouring rows of one column; consecutive
     // threads take consecutive columns: the same row segments a tile load would fetch); the last pass never
     // stores r: every output goes into the thread's running (max |r|^2, lowest 'full' index) and leaves only its
@@ -1756,7 +1777,9 @@ __global__ __launch_bounds__(1024) void g_cols_inv(const float2* __restrict__ in
             if (v >= best) {                      // (rare after the first few elements: the index arithmetic stays off the common path)
                 const int m = ((E >> kColLogT) << l2) + c0 + (E & (kColT - 1));
                 const int k = full_index(m, N);
-                if (k >= 0 && (v > best || k < bk)) { best = v; bk = k; }
+                bool inside = k >= 0;
+                if constexpr (BOUNDED) inside = (unsigned)(k - klo) <= (unsigned)(khi - klo);   // (klo >= 0)
+                if (inside && (v > best || k < bk)) { best = v; bk = k; }
             }
             x[TileInv::pos(E0) + TileInv::pos(off)].x = v;        // (4-byte store: only .x is read back, by the halo and the taps)
         }));
@@ -1787,10 +1810,11 @@ __global__ __launch_bounds__(1024) void g_cols_inv(const float2* __restrict__ in
 
 // final reduction over a slot's tile records (one wave per slot), neighbour taps from the winning record or
 // from the halo columns of the adjacent tile, parabola
+template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation: frac = 0 at the lag window's edges)
 __global__ __launch_bounds__(64) void g_final(int N, int l1, int l2, int col_log_t, const GTile* __restrict__ rec,
                                               const float* __restrict__ halo, int parts, int n_slots, long out_base,
                                               float out_scale, int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                              float* __restrict__ peak) {
+                                              float* __restrict__ peak, LB... lb_pack) {
     const int slot = blockIdx.x, lane = threadIdx.x;
     if (slot >= n_slots) return;
     float best = -1.0f;
@@ -1811,7 +1835,9 @@ __global__ __launch_bounds__(64) void g_final(int N, int l1, int l2, int col_log
     const long L = (long)L1 << l2;
     const float b = sqrtf(best) * out_scale;
     float frac = 0.0f;
-    if (bk > 0 && bk < 2 * N - 2) {
+    int klo = 0, khi = 2 * N - 2;
+    if constexpr (sizeof...(LB) > 0) lag_window_slot(lag_bounds_of(lb_pack...), slot, N - 1, klo, khi);
+    if (bk > klo && bk < khi) {
         const long m = circ_index(bk, N);
         auto tap = [&](float inside, long mm) -> float {
             if (inside >= 0.0f) return inside;

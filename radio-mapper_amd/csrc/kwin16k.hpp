@@ -74,9 +74,11 @@ __device__ __forceinline__ void k_to_owner16(int kk, int& tt, int& sg) {
 }
 
 // one pending pair: lane r < 16 looks at record r = 2 wave + phase
+// (BOUNDED: frac = 0 at the edges of the pair's lag window, lag_bounds.hpp; output index out = window * P + pair)
+template <bool BOUNDED = false>
 __device__ __forceinline__ void resolve16(int lane, const float4* red, const float* halo, const long long* oidx, int slot,
                                           float out_scale, int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                          float* __restrict__ peak) {
+                                          float* __restrict__ peak, LagBounds lb = {}) {
     const int r = lane & 15;
     const bool act = lane < 16;
     const float* rf = reinterpret_cast<const float*>(red) + 4 * (slot * 16 + r);
@@ -111,7 +113,13 @@ __device__ __forceinline__ void resolve16(int lane, const float4* red, const flo
     const float c = sqrtf(tp >= 0.0f ? tp : hp) * out_scale;
     const double den = (double)a - 2.0 * (double)b + (double)c;
     float frac = 0.0f;
+    if constexpr (BOUNDED) {
+        int klo = 0, khi = 0;
+        if (act) lag_window(lb, (long)(out / lb.n_pairs), (int)(out % lb.n_pairs), kN16 - 1, klo, khi);
+        if (kc > klo && kc < khi && den != 0.0) frac = (float)(0.5 * ((double)a - (double)c) / den);
+    } else {
     if (kc > 0 && kc < 2 * kN16 - 2 && den != 0.0) frac = (float)(0.5 * ((double)a - (double)c) / den);
+    }
     if (win) {
         lag_int[out] = kc - (kN16 - 1);
         lag_frac[out] = frac;
@@ -287,6 +295,7 @@ __global__ __launch_bounds__(kThreads, 2) void k16_fwd(const void* __restrict__ 
 }
 
 // ---- pairs --------------------------------------------------------------------------------------------------------------
+template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation; lb.w0 = the launch's window 0, lb.n_pairs = P)
 __global__ __launch_bounds__(kThreads, 2) void k16_pairs(const float4* __restrict__ spec,     // [window][buoy][4][8][512]
                                                         const float4* __restrict__ tw1_g, const float2* __restrict__ gq_g,
                                                         const float2* __restrict__ tw2_g, const float2* __restrict__ tws_g,
@@ -295,7 +304,8 @@ __global__ __launch_bounds__(kThreads, 2) void k16_pairs(const float4* __restric
                                                         long out_first,       // output index of (window 0, pair 0)
                                                         int n_win, int flat,  // flat: items b, b + grid, ... of [(window 0, pair 0 .. P-1), (window 1, ...)]
                                                         float out_scale, int* __restrict__ lag_int,
-                                                        float* __restrict__ lag_frac, float* __restrict__ peak) {
+                                                        float* __restrict__ lag_frac, float* __restrict__ peak, LB... lb_pack) {
+    constexpr bool BOUNDED = sizeof...(LB) > 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* img0 = reinterpret_cast<float2*>(smem);
     float4* park = reinterpret_cast<float4*>(smem + kLdsPark);
@@ -429,7 +439,13 @@ __global__ __launch_bounds__(kThreads, 2) void k16_pairs(const float4* __restric
         __syncthreads();
         if (npend) {
             if (wave == (seq & 7))
+            {
+                if constexpr (BOUNDED)
+                    resolve16<true>(lane, red, halo, oidx, (npair - 1) & (kRing - 1), out_scale, lag_int, lag_frac, peak,
+                                    lag_bounds_of(lb_pack...));
+                else
                 resolve16(lane, red, halo, oidx, (npair - 1) & (kRing - 1), out_scale, lag_int, lag_frac, peak);
+            }
             npend = 0;
         }
     };
@@ -571,6 +587,16 @@ __global__ __launch_bounds__(kThreads, 2) void k16_pairs(const float4* __restric
                     m1[q] = fmaf(ax, ax, ay * ay);
                     m3[q] = fmaf(bx, bx, by * by);
                 }
+                if constexpr (BOUNDED) {         // lag window: |r|^2 outside it -> the -1 sentinel (lag_bounds.hpp)
+                    const LagBounds lb = lag_bounds_of(lb_pack...);
+                    int klo, khi;
+                    lag_window(lb, lb.w0 + wl, pq, kN16 - 1, klo, khi);
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {   // value arrays rho = 1, 3: 'full' index kbase + 256 q + 8192 rho
+                        m1[q] = lag_mask(m1[q], kbase + 256 * q + 8192, klo, khi);
+                        m3[q] = lag_mask(m3[q], kbase + 256 * q + 3 * 8192, klo, khi);
+                    }
+                }
                 search32(m1, m3, std::integral_constant<int, 1>{}, std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{});
             }
             {
@@ -588,6 +614,16 @@ __global__ __launch_bounds__(kThreads, 2) void k16_pairs(const float4* __restric
                     }
                 }
                 if (p == 0 && u == 0) m0[0] = -1.0f;     // m = 0 of s = 2: lag -N is not part of the 'full' output
+                if constexpr (BOUNDED) {
+                    const LagBounds lb = lag_bounds_of(lb_pack...);
+                    int klo, khi;
+                    lag_window(lb, lb.w0 + wl, pq, kN16 - 1, klo, khi);
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {   // rho = 0, 2
+                        m0[q] = lag_mask(m0[q], kbase + 256 * q, klo, khi);
+                        m2[q] = lag_mask(m2[q], kbase + 256 * q + 2 * 8192, klo, khi);
+                    }
+                }
                 search32(m0, m2, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 1>{});
             }
             ++npend;

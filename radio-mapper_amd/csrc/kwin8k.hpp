@@ -86,9 +86,12 @@ __device__ __forceinline__ void k_to_owner8(int kk, int& tt, int& sg) {
 }
 
 // resolve_batch of kwin.hpp for this kernel's records: lane = 8 g + r looks at wave r's record of the g-th pending pair
+// BOUNDED: frac = 0 at the edges of the pair's lag window (lag_bounds.hpp), window w (global index)
+template <bool BOUNDED = false>
 __device__ __forceinline__ void resolve_batch8(int lane, const float4* red, const float* halo, const int* oidx, int first,
                                                int cnt, long obase, float out_scale, int* __restrict__ lag_int,
-                                               float* __restrict__ lag_frac, float* __restrict__ peak) {
+                                               float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb = {},
+                                               long w = 0) {
     const int g = lane >> 3, r = lane & 7;
     const bool act = g < cnt;
     const int slot = (first + (act ? g : 0)) & (kSlots8 - 1);
@@ -122,7 +125,13 @@ __device__ __forceinline__ void resolve_batch8(int lane, const float4* red, cons
     const float c = sqrtf(tp >= 0.0f ? tp : hp) * out_scale;
     const double den = (double)a - 2.0 * (double)b + (double)c;
     float frac = 0.0f;
-    if (kc > 0 && kc < 2 * kN8 - 2 && den != 0.0) frac = (float)(0.5 * ((double)a - (double)c) / den);
+    if constexpr (BOUNDED) {
+        int klo = 0, khi = 0;
+        if (act) lag_window(lb, w, out, kN8 - 1, klo, khi);
+        if (kc > klo && kc < khi && den != 0.0) frac = (float)(0.5 * ((double)a - (double)c) / den);
+    } else {
+        if (kc > 0 && kc < 2 * kN8 - 2 && den != 0.0) frac = (float)(0.5 * ((double)a - (double)c) / den);
+    }
     if (win) {
         lag_int[obase + out] = kc - (kN8 - 1);
         lag_frac[obase + out] = frac;
@@ -156,14 +165,16 @@ constexpr int kLdsLPairs = kLdsLTw2 + kLdsTw2;
 constexpr int kLdsLBytes = kLdsLPairs + kMaxPairs8 * 8;
 static_assert(kLdsLBytes <= 160 * 1024, "k_win8kl LDS");
 
-template <bool U8>
+template <bool U8, class... LB>   // LB: empty, or one LagBounds (the bounded instantiation, lag_bounds.hpp)
 __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__ iq_v, float4* __restrict__ spec,
                                                        const float4* __restrict__ tw1_g,     // [2 halves][8][512]
                                                        const float2* __restrict__ tw2_g, int n_buoys,
                                                        const Pair2* __restrict__ pairs, int n_pairs, long first_window,
                                                        float out_scale, int* __restrict__ lag_int,
                                                        float* __restrict__ lag_frac, float* __restrict__ peak, int n_win,
-                                                       int stag) {   // (stag: unused here -- one exchange image, no half-order staggering; kept so the launch sites of the three N = 8192 kernels match)
+                                                       int stag,     // (stag: unused here -- one exchange image, no half-order staggering; kept so the launch sites of the three N = 8192 kernels match)
+                                                       LB... lb_pack) {
+    constexpr bool BOUNDED = sizeof...(LB) > 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* img0 = reinterpret_cast<float2*>(smem);                      // the ONE exchange image
     float4* anc = reinterpret_cast<float4*>(smem + kLdsLAnc);            // anchor half 1: [8][512] float4, thread-private columns
@@ -215,9 +226,15 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
     auto barrier_hook = [&](bool flush) __attribute__((always_inline)) {
         __syncthreads();
         if (npend == kBatch8 || (flush && npend > 0)) {
+            if constexpr (BOUNDED) {
+                if (wave == (seq & 7))
+                    resolve_batch8<true>(lane, red, halo, oidx, (npair - npend) & (kSlots8 - 1), npend, obase, out_scale,
+                                         lag_int, lag_frac, peak, lag_bounds_of(lb_pack...), first_window + wl);
+            } else {
             if (wave == (seq & 7))
                 resolve_batch8(lane, red, halo, oidx, (npair - npend) & (kSlots8 - 1), npend, obase, out_scale, lag_int,
                                lag_frac, peak);
+            }
             npend = 0;
         }
     };
@@ -378,6 +395,15 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
             m1[q] = fmaf(bx, bx, by * by);
         }
         if (p == 0 && u == 0) m1[0] = -1.0f;     // m = 8192: lag -N is not part of the 'full' output
+        if constexpr (BOUNDED) {                 // lag window: |r|^2 outside it -> the same sentinel (lag_bounds.hpp)
+            int klo, khi;
+            lag_window(lag_bounds_of(lb_pack...), first_window + wl, out_idx, kN8 - 1, klo, khi);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {       // m1[q]: 'full' index kbase + 256 q; m0[q]: 8192 above it
+                m1[q] = lag_mask(m1[q], kbase + 256 * q, klo, khi);
+                m0[q] = lag_mask(m0[q], kbase + 256 * q + 8192, klo, khi);
+            }
+        }
         const int rb = npair & (kSlots8 - 1);
         if (is_halo) {
             float4* hp = reinterpret_cast<float4*>(halo + ((rb * 8 + wave) * 4 + hl) * 32);

@@ -25,6 +25,7 @@
 
 #include "../../include/rmx.h"
 #include "host_plan.hpp"
+#include "lag_bounds.hpp"
 #include "fft_r16.hpp"
 #include "kwin.hpp"
 #include "fft_r8.hpp"
@@ -114,13 +115,14 @@ __global__ __launch_bounds__(kThreads, 4) void k_fwd(const void* __restrict__ iq
 //   out arrays are indexed [(first_window + wl) * n_pairs + item.out].
 // Streaming variant (k_pair_str, option "resident" = 0): two workgroups per CU (<= 128 VGPRs); TW1,
 // X_i and X_j are re-read every pair.  The resident variant is k_pair_res below.
+template <bool BOUNDED>
 __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const float4* __restrict__ spec_j,
                                           const float4* __restrict__ tw1_g,
                                           const float2* __restrict__ tw2_g, const PairItem* __restrict__ items,
                                           const int* __restrict__ part_begin, int n_parts, int n_buoys,
                                           int n_pairs, int xcd_map, long first_window, float out_scale,
                                           int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                          float* __restrict__ peak, int i_wrap) {
+                                          float* __restrict__ peak, int i_wrap, LagBounds lb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* xl = reinterpret_cast<float2*>(smem);
     float2* tw2_lds = reinterpret_cast<float2*>(smem + kLdsXchg);
@@ -225,6 +227,13 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
         // 'full' order index of slot q: even lanes lag tau = n >= 0 -> k = n + M - 1;
         // odd lanes tau = n - M -> k = n - 1 (n = 0, i.e. tau = -M, is not part of 'full').
         if (p && u == 0) mag[0] = -1.0f;
+        int klo = 0, khi = 2 * kM - 2;
+        if constexpr (BOUNDED) {   // lag window: |r|^2 outside it -> the same sentinel (lag_bounds.hpp)
+            lag_window(lb, first_window + wl, out_idx, kM - 1, klo, khi);
+            const int kb = p ? (u - 1) : (u + kM - 1);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) mag[q] = lag_mask(mag[q], kb + q * 256, klo, khi);
+        }
         float tmax = mag[0];
 #pragma unroll
         for (int q = 1; q < 16; ++q) tmax = fmaxf(tmax, mag[q]);
@@ -268,7 +277,7 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
         if (t == 0) {
             const double b = (double)red_tap[1];
             double frac = 0.0;
-            if (kstar > 0 && kstar < 2 * kM - 2) {
+            if (kstar > klo && kstar < khi) {   // (klo = 0, khi = 2M - 2 unbounded)
                 const double a = (double)red_tap[0], c = (double)red_tap[2];
                 const double den = a - 2.0 * b + c;
                 if (den != 0.0) frac = 0.5 * (a - c) / den;
@@ -294,9 +303,10 @@ constexpr int kLdsMag = kL * 4;                         // one |.|^2 image: [q4]
 constexpr int kLdsResOff = kLdsXchg + kLdsTw2;
 constexpr int kLdsResBytes = kLdsXchg + kLdsTw2 + 2 * kLdsMag + 256;
 
+template <bool BOUNDED>
 __device__ __forceinline__ void resolve_pair(const float* magbuf, const float2* red, long out_pos, float out_scale,
                                              int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                             float* __restrict__ peak) {
+                                             float* __restrict__ peak, LagBounds lb, long w, int q_out) {
     // red[w] = (wave max of |r|^2 as float bits, lowest 'full' index attaining it), w = 0..7
     float gmax = -2.0f;
     int kstar = 0x7fffffff;
@@ -316,7 +326,9 @@ __device__ __forceinline__ void resolve_pair(const float* magbuf, const float2* 
     };
     const float b = sqrtf(gmax) * out_scale;
     float frac = 0.0f;
-    if (kstar > 0 && kstar < 2 * kM - 2) {
+    int klo = 0, khi = 2 * kM - 2;
+    if constexpr (BOUNDED) lag_window(lb, w, q_out, kM - 1, klo, khi);
+    if (kstar > klo && kstar < khi) {
         const float a = tap(kstar - 1), c = tap(kstar + 1);
         const double den = (double)a - 2.0 * (double)b + (double)c;
         if (den != 0.0) frac = (float)(0.5 * ((double)a - (double)c) / den);
@@ -326,11 +338,14 @@ __device__ __forceinline__ void resolve_pair(const float* magbuf, const float2* 
     peak[out_pos] = b;
 }
 
+template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation)
 __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     const float4* __restrict__ spec, const float4* __restrict__ spec_j, const float4* __restrict__ tw1_g, const float2* __restrict__ tw2_g,
     const PairItem* __restrict__ items, const int* __restrict__ part_begin, int n_parts, int n_buoys, int n_pairs,
     int xcd_map, long first_window, float out_scale, int* __restrict__ lag_int, float* __restrict__ lag_frac,
-    float* __restrict__ peak, int dbg_rt, int i_wrap) {
+    float* __restrict__ peak, int dbg_rt, int i_wrap, LB... lb_pack) {
+    constexpr bool BOUNDED = sizeof...(LB) > 0;
+    const LagBounds lb = lag_bounds_of(lb_pack...);
 #ifdef RMX_ABLATE
     const int dbg = dbg_rt;   // timing-only ablation build (wrong results), as in k_win
 #else
@@ -418,8 +433,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
         if (!(dbg & 8)) xchg_b_write(xl, v, t);       // into this half wave's own region
         if (!(dbg & 1)) __syncthreads();              // the pair's only barrier; also publishes pair it-1's winners
         if (!(dbg & 2) && prev_out >= 0 && t == ((it - it_begin) & 7) * 64)
-            resolve_pair(reinterpret_cast<const float*>(magbuf + (buf ^ 1) * (4 * kThreads)), red + (buf ^ 1) * 8,
-                         obase + prev_out, out_scale, lag_int, lag_frac, peak);
+            resolve_pair<BOUNDED>(reinterpret_cast<const float*>(magbuf + (buf ^ 1) * (4 * kThreads)), red + (buf ^ 1) * 8,
+                                  obase + prev_out, out_scale, lag_int, lag_frac, peak, lb, first_window + wl, prev_out);
         if (!(dbg & 8)) xchg_a_read(xl, v, t);
         mul_tw1(v, tw1);              // W_M^(u*k0) [* W_L^u on odd lanes]
         dft16(v);                     // k0 -> n2   (role A): e[n] (even lanes) / o[n]*W_L^u (odd lanes)
@@ -435,6 +450,12 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
             mag[q] = rx * rx + ry * ry;
         }
         if (p && u == 0) mag[0] = -1.0f;   // lag -M is not part of the 'full' output
+        if constexpr (BOUNDED) {           // lag window: |r|^2 outside it -> the same sentinel (lag_bounds.hpp)
+            int klo, khi;
+            lag_window(lb, first_window + wl, out_idx, kM - 1, klo, khi);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) mag[q] = lag_mask(mag[q], kbase + q * 256, klo, khi);
+        }
         if (dbg & 2) { float s = 0; 
 #pragma unroll
             for (int q = 0; q < 16; ++q) s += mag[q];
@@ -458,8 +479,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     __syncthreads();
     if (t == 0) {
         const int buf = (it_end - 1 - it_begin) & 1;
-        resolve_pair(reinterpret_cast<const float*>(magbuf + buf * (4 * kThreads)), red + buf * 8, obase + prev_out,
-                     out_scale, lag_int, lag_frac, peak);
+        resolve_pair<BOUNDED>(reinterpret_cast<const float*>(magbuf + buf * (4 * kThreads)), red + buf * 8, obase + prev_out,
+                              out_scale, lag_int, lag_frac, peak, lb, first_window + wl, prev_out);
     }
 }
 
@@ -490,7 +511,10 @@ __global__ __launch_bounds__(kThreads, 2) void k_winp(const void* __restrict__ i
     spec, spec_j, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,      \
         lag_int, lag_frac, peak, i_wrap
 
-__global__ __launch_bounds__(kThreads, 4) void k_pair_str(RMX_PAIR_ARGS) { pair_body(RMX_PAIR_PASS); }
+template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation)
+__global__ __launch_bounds__(kThreads, 4) void k_pair_str(RMX_PAIR_ARGS, LB... lb) {
+    pair_body<(sizeof...(LB) > 0)>(RMX_PAIR_PASS, lag_bounds_of(lb...));
+}
 
 
 // ---- CAF helper: running best hypothesis per pair-window -------------------------------------------
@@ -690,6 +714,7 @@ struct rmx_ctx {
     float4* g_k16_tw1 = nullptr;           // slot factors of TW1
     float2 *g_k16_gq = nullptr, *g_k16_tw2 = nullptr, *g_k16_tws = nullptr;   // per-quarter thread factors, k_win's TW2, W_128 rows
     const void* g_cols_inv_fn = nullptr;
+    const void* g_cols_inv_lb_fn = nullptr;   // its bounded instantiation (rmx_xcorr_batch_bounded)
     const void* g_cols_fwd_fn[2] = {nullptr, nullptr};   // [u8]
     const void* g_rows_inv_fn = nullptr;
     const void* g_rows_anchor_fn = nullptr;   // inverse rows with a resident anchor (default pair list), or null
@@ -718,6 +743,11 @@ struct rmx_ctx {
     int* caf_lag = nullptr;  float* caf_frac = nullptr;  float* caf_peak = nullptr;  int* caf_dop = nullptr;
     size_t caf_out_elems = 0;
     std::vector<double> caf_grid;
+    // rmx_xcorr_batch_bounded: the caller's lag windows, staged in pinned memory and copied to a ctx-owned device buffer
+    rmx::LagBounds lb{nullptr, 0, 0, 0};   // lb.b != nullptr while a bounded call dispatches: the bounded kernels run
+    int* d_lb = nullptr;  size_t d_lb_elems = 0;
+    int32_t* h_lb = nullptr;  size_t h_lb_elems = 0;
+    hipEvent_t lb_ev = nullptr;   // the last copy out of h_lb: the next bounded call waits for it before it rewrites h_lb
     // cached pair plan
     std::vector<int32_t> plan_pairs;
     int plan_n_pairs = -1, plan_n_parts = 0, plan_ppb = 0;
@@ -891,23 +921,25 @@ static size_t gen_rows_lds(const rmx_ctx* c, int R) {   // rows + per-row twiddl
     return ((size_t)(gen::kGThreads / tpr) * ((size_t)gen::lp(R) + (1 << a) + (R >> a)) + (size_t)(R >> 1) + (R < 4096 ? 240 : 0)) * 8;   // + W_R table + the q = 16 pass's own
 }
 // column kernels with the column length compiled in (16-column tiles, the default thread count), else the run-time ones
+// (LB: empty, or LagBounds for the bounded instantiations of the same set)
+template <class... LB>
 static const void* cols_inv_fn(int l1, int lt, int thr) {
     using namespace gen;
-    if (lt == 3) return (const void*)g_cols_inv<3>;
+    if (lt == 3) return (const void*)g_cols_inv<3, 0, LB...>;
     if (lt == 5) {          // 32-column tiles (256-byte row segments): option col_logt = 5, an A/B switch (VERDICT r04 #3a)
-        if (thr == cols_threads(l1, 5) && l1 == 8) return (const void*)g_cols_inv<5, 8>;
-        if (thr == cols_threads(l1, 5) && l1 == 9) return (const void*)g_cols_inv<5, 9>;
-        return (const void*)g_cols_inv<5>;
+        if (thr == cols_threads(l1, 5) && l1 == 8) return (const void*)g_cols_inv<5, 8, LB...>;
+        if (thr == cols_threads(l1, 5) && l1 == 9) return (const void*)g_cols_inv<5, 9, LB...>;
+        return (const void*)g_cols_inv<5, 0, LB...>;
     }
     if (thr == cols_threads(l1, 4)) switch (l1) {
-        case 5: return (const void*)g_cols_inv<4, 5>;
-        case 6: return (const void*)g_cols_inv<4, 6>;
-        case 7: return (const void*)g_cols_inv<4, 7>;
-        case 8: return (const void*)g_cols_inv<4, 8>;
-        case 9: return (const void*)g_cols_inv<4, 9>;
+        case 5: return (const void*)g_cols_inv<4, 5, LB...>;
+        case 6: return (const void*)g_cols_inv<4, 6, LB...>;
+        case 7: return (const void*)g_cols_inv<4, 7, LB...>;
+        case 8: return (const void*)g_cols_inv<4, 8, LB...>;
+        case 9: return (const void*)g_cols_inv<4, 9, LB...>;
         default: break;
     }
-    return (const void*)g_cols_inv<4>;
+    return (const void*)g_cols_inv<4, 0, LB...>;
 }
 template <bool U8>
 static const void* cols_fwd_fn(int l1, int lt, int thr) {
@@ -1034,7 +1066,8 @@ static int generic_init(rmx_ctx* c) {
         int rc = upload(c, &c->g_tw, t);
         if (rc) return rc;
         const int slds = (int)(gen::lp(L) * 8 + 1024 * 8);
-        RMX_HIP(c, hipFuncSetAttribute((const void*)g_pair_small, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)g_pair_small<>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)g_pair_small<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<false>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<true>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         // at most four buoys, 512 <= L <= 4096: whole windows in one kernel, spectra in registers (RMX_WFUSED=0: the two
@@ -1078,7 +1111,9 @@ static int generic_init(rmx_ctx* c) {
         const int cols_lds = (int)gen_cols_lds(c, c->g_logL1), rows_lds = (int)gen_rows_lds(c, 1 << c->g_logL2);
         {
             const int lt = host_col_log_t(c, c->g_logL1), thr = gen_cols_threads(c, c->g_logL1);
-            c->g_cols_inv_fn = cols_inv_fn(c->g_logL1, lt, thr);
+            c->g_cols_inv_fn = cols_inv_fn<>(c->g_logL1, lt, thr);
+            c->g_cols_inv_lb_fn = cols_inv_fn<LagBounds>(c->g_logL1, lt, thr);
+            RMX_HIP(c, hipFuncSetAttribute(c->g_cols_inv_lb_fn, hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
             c->g_cols_fwd_fn[0] = cols_fwd_fn<false>(c->g_logL1, lt, thr);
             c->g_cols_fwd_fn[1] = cols_fwd_fn<true>(c->g_logL1, lt, thr);
             RMX_HIP(c, hipFuncSetAttribute(c->g_cols_inv_fn, hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
@@ -1183,6 +1218,8 @@ static int generic_init(rmx_ctx* c) {
             c->scratch_bytes += t1.size() * sizeof(float4) + t2.size() * sizeof(float2);
             RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8kl<false>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLdsLBytes));
             RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8kl<true>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLdsLBytes));
+            RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8kl<false, LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLdsLBytes));
+            RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8kl<true, LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLdsLBytes));
             c->g_k8 = c->g_ws_upw == 1 && grid <= c->n_cus;      // (its grid is the scratch's: one window slot per workgroup)
             c->g_k8_kind = (int)c->knobs.get_or("kwin8k", 1);
 #ifdef RMX_EXPERIMENTS
@@ -1211,7 +1248,8 @@ static int generic_init(rmx_ctx* c) {
             c->scratch_bytes += t1.size() * sizeof(float4);
             RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsFwdBytes));
             RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsFwdBytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsPairBytes));
+            RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_pairs<>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsPairBytes));
+            RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_pairs<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsPairBytes));
             c->g_k16 = (int)c->knobs.get_or("kwin16k", 1);
         }
     }
@@ -1365,7 +1403,12 @@ static int generic_pairs(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, fl
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
         RMX_TM_BEGIN(c);
-        hipLaunchKernelGGL(g_pair_small, dim3(slots), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st, c->g_spec,
+        if (c->lb.b)   // bounded call (rmx_xcorr_batch_bounded)
+            hipLaunchKernelGGL(g_pair_small<LagBounds>, dim3(slots), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st,
+                               c->g_spec, spec_j, c->g_tw, c->g_pairs, n_pairs, B, N, logL, (long)w0, out_scale, d_lag, d_frac,
+                               d_peak, c->lb);
+        else
+        hipLaunchKernelGGL(g_pair_small<>, dim3(slots), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st, c->g_spec,
                            spec_j, c->g_tw, c->g_pairs, n_pairs, B, N, logL, (long)w0, out_scale, d_lag, d_frac, d_peak);
         RMX_HIP(c, hipGetLastError());
         RMX_TM_END(c, kTkPairSmall);
@@ -1430,13 +1473,23 @@ static int generic_pairs(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, fl
         int a_l1 = l1, a_l2 = l2;
         GTile* a_rec = c->g_rec;
         float* a_halo = c->g_halo;
-        void* args[] = {&a_in, &a_tw, &a_l1, &a_l2, &a_rec, &a_halo};
+        LagBounds a_lb = c->lb;   // (bounded call: slot -> window w0 + slot / P, pair slot % P)
+        a_lb.w0 = w0;
+        a_lb.n_pairs = n_pairs;
+        void* args[] = {&a_in, &a_tw, &a_l1, &a_l2, &a_rec, &a_halo, &a_lb};
         RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_cols_inv_fn, dim3(ntiles, slots), dim3(cthr), args, clds, st));
+        RMX_HIP(c, hipLaunchKernel(c->lb.b ? c->g_cols_inv_lb_fn : c->g_cols_inv_fn, dim3(ntiles, slots), dim3(cthr), args, clds, st));
         RMX_TM_END(c, kTkColsInv);
     }
     RMX_TM_BEGIN(c);
-    hipLaunchKernelGGL(g_final, dim3(slots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, slots,
+    if (c->lb.b) {
+        LagBounds a_lb = c->lb;
+        a_lb.w0 = w0;
+        a_lb.n_pairs = n_pairs;
+        hipLaunchKernelGGL(g_final<LagBounds>, dim3(slots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, slots,
+                           (long)w0 * n_pairs, out_scale, d_lag, d_frac, d_peak, a_lb);
+    } else
+    hipLaunchKernelGGL(g_final<>, dim3(slots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, slots,
                        (long)w0 * n_pairs, out_scale, d_lag, d_frac, d_peak);
     RMX_HIP(c, hipGetLastError());
     RMX_TM_END(c, kTkFinal);
@@ -1491,7 +1544,15 @@ static int k16_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pairs, i
         long pgrid = 8 * S;
         if (flat) pgrid = (long)wc * n_pairs < c->n_cus ? (long)wc * n_pairs : c->n_cus;
         RMX_TM_BEGIN(c);
-        hipLaunchKernelGGL(k16::k16_pairs, dim3((unsigned)pgrid), dim3(kThreads), k16::kLdsPairBytes, c->stream, c->g_ws_scratch,
+        if (c->lb.b) {   // bounded call: the same kernel with the lag windows (lb.w0: window 0 of this launch)
+            LagBounds a_lb = c->lb;
+            a_lb.w0 = w0;
+            a_lb.n_pairs = n_pairs;
+            hipLaunchKernelGGL(k16::k16_pairs<LagBounds>, dim3((unsigned)pgrid), dim3(kThreads), k16::kLdsPairBytes, c->stream,
+                               c->g_ws_scratch, c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, B, prs, n_pairs,
+                               (long)w0 * n_pairs, wc, flat, out_scale, d_lag, d_frac, d_peak, a_lb);
+        } else
+        hipLaunchKernelGGL(k16::k16_pairs<>, dim3((unsigned)pgrid), dim3(kThreads), k16::kLdsPairBytes, c->stream, c->g_ws_scratch,
                            c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, B, prs, n_pairs, (long)w0 * n_pairs, wc, flat,
                            out_scale, d_lag, d_frac, d_peak);
         RMX_HIP(c, hipGetLastError());
@@ -1521,8 +1582,17 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
     // at 256 windows, 0.85-0.94 x at 192, 0.9-1.25 x at 128: profiles/r03_weo_sweep.log)
     // (L = 16384 through k_win8kl: 242 us for anything up to one window per CU at 8 buoys, 50 us at 3, against 194 / 50 us at
     // 64 windows and 290 / 64 us at 96 through the per-transform kernels -- tools/exp_k8_small.py: from 5/16 of a workgroup per CU)
-    const bool use_wscr = c->g_wscr && (c->g_wscr_always || ws_blocks >= (c->g_logL == 14 ? (c->g_k8 ? 5L : 7L) : 11L) * c->n_cus / 16);
-    const bool whole_window = c->g_wfused || use_wscr;   // those kernels keep no per-window state in HBM
+    const bool def_list_b = c->plan_all_pairs && n_pairs == c->n_buoys * (c->n_buoys - 1) / 2;
+    // Bounded calls (rmx_xcorr_batch_bounded): of the whole-window kernels only k_win8kl has a bounded instantiation.
+    // g_win_fused, g_win_scr, g_win_scr14 and g_win_eo15 have none: a bounded call that would take one of them takes the
+    // per-transform kernels instead (g_fwd_small + g_pair_small up to L = small_maxl, the four-step kernels above), whose
+    // peak searches are bounded.  At the BASELINE shapes the fused kernels run either way (k_win, k_win8kl, k16_pairs).
+    const bool bounded = c->lb.b != nullptr;
+    const bool k8_route = c->g_k8 && (def_list_b || n_pairs <= k8::kMaxPairs8);
+    const bool use_wscr = c->g_wscr && (!bounded || k8_route) &&
+                          (c->g_wscr_always || ws_blocks >= (c->g_logL == 14 ? (c->g_k8 ? 5L : 7L) : 11L) * c->n_cus / 16);
+    const bool use_wfused = c->g_wfused && !bounded;
+    const bool whole_window = use_wfused || use_wscr;   // those kernels keep no per-window state in HBM
     int rc = generic_ensure(c, n_pairs, !whole_window, !whole_window);
     if (rc) return rc;
     if (use_wscr) {
@@ -1568,7 +1638,15 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
                                        d_frac, d_peak, n_windows, stag);
             } else
 #endif
-            if (u8)
+            if (bounded && u8)
+                hipLaunchKernelGGL((k8::k_win8kl<true, LagBounds>), dim3((unsigned)grid), dim3(kThreads), k8::kLdsLBytes, c->stream,
+                                   d_iq, c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale,
+                                   d_lag, d_frac, d_peak, n_windows, stag, c->lb);
+            else if (bounded)
+                hipLaunchKernelGGL((k8::k_win8kl<false, LagBounds>), dim3((unsigned)grid), dim3(kThreads), k8::kLdsLBytes, c->stream,
+                                   d_iq, c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale,
+                                   d_lag, d_frac, d_peak, n_windows, stag, c->lb);
+            else if (u8)
                 hipLaunchKernelGGL(k8::k_win8kl<true>, dim3((unsigned)grid), dim3(kThreads), k8::kLdsLBytes, c->stream, d_iq,
                                    c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag,
                                    d_frac, d_peak, n_windows, stag);
@@ -1607,7 +1685,7 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
         RMX_TM_END(c, kTkWindow);
         return RMX_OK;
     }
-    if (c->g_wfused) {
+    if (use_wfused) {
         using namespace gen;
         const int logL = c->g_logL, B = c->n_buoys, hs = logL / 2;
         const bool def_plan = c->plan_all_pairs && n_pairs == B * (B - 1) / 2;
@@ -1746,10 +1824,15 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
 #endif
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_res, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsResBytes));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_res<>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsResBytes));
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_win<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_win<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_str, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_str<>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
+        // the bounded instantiations (rmx_xcorr_batch_bounded)
+        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_res<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsResBytes));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)k_win_lb<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)k_win_lb<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_str<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
         return RMX_OK;
     };
     rc = init();
@@ -1788,6 +1871,9 @@ void rmx_destroy(rmx_ctx* c) {
     if (c->d_in) (void)hipFree(c->d_in);
     if (c->d_lag) (void)hipFree(c->d_lag);            // (d_frac / d_peak point into the same block)
     if (c->h_out) (void)hipHostFree(c->h_out);
+    if (c->d_lb) (void)hipFree(c->d_lb);
+    if (c->h_lb) (void)hipHostFree(c->h_lb);
+    if (c->lb_ev) (void)hipEventDestroy(c->lb_ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1923,12 +2009,20 @@ static int pairs4096(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, float*
     const int xcd_map = (wc % 8 == 0) ? 1 : 0;
     const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
     RMX_TM_BEGIN(c);
-    if (c->resident)
-        hipLaunchKernelGGL(k_pair_res, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream, (const float4*)c->d_spec,
+    if (c->lb.b && c->resident)   // bounded call (rmx_xcorr_batch_bounded)
+        hipLaunchKernelGGL(k_pair_res<LagBounds>, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream,
+                           (const float4*)c->d_spec, spec_j, c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys,
+                           n_pairs, xcd_map, (long)w0, out_scale, d_lag, d_frac, d_peak, c->dbg, i_wrap, c->lb);
+    else if (c->lb.b)
+        hipLaunchKernelGGL(k_pair_str<LagBounds>, dim3(wc * n_parts), dim3(kThreads), kLdsBytes, c->stream,
+                           (const float4*)c->d_spec, spec_j, c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys,
+                           n_pairs, xcd_map, (long)w0, out_scale, d_lag, d_frac, d_peak, i_wrap, c->lb);
+    else if (c->resident)
+        hipLaunchKernelGGL(k_pair_res<>, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream, (const float4*)c->d_spec,
                            spec_j, c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map,
                            (long)w0, out_scale, d_lag, d_frac, d_peak, c->dbg, i_wrap);
     else
-        hipLaunchKernelGGL(k_pair_str, dim3(wc * n_parts), dim3(kThreads), kLdsBytes, c->stream, (const float4*)c->d_spec, spec_j,
+        hipLaunchKernelGGL(k_pair_str<>, dim3(wc * n_parts), dim3(kThreads), kLdsBytes, c->stream, (const float4*)c->d_spec, spec_j,
                            c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, (long)w0,
                            out_scale, d_lag, d_frac, d_peak, i_wrap);
     RMX_HIP(c, hipGetLastError());
@@ -2170,7 +2264,15 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
                                            c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc);
                 } else
 #endif
-                if (u8)
+                if (c->lb.b && u8)   // bounded call (rmx_xcorr_batch_bounded): k_win's bounded instantiation
+                    hipLaunchKernelGGL(k_win_lb<true>, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec,
+                                       c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac,
+                                       d_peak, sc, c->dbg, c->stag, c->lb);
+                else if (c->lb.b)
+                    hipLaunchKernelGGL(k_win_lb<false>, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec,
+                                       c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac,
+                                       d_peak, sc, c->dbg, c->stag, c->lb);
+                else if (u8)
                     hipLaunchKernelGGL(k_win<true>, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec,
                                        c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac,
                                        d_peak, sc, c->dbg, c->stag);
@@ -2196,6 +2298,68 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     }
     if (!out_dev) return fetch_out(c, out_elems, lag_int, lag_frac, peak);
     return RMX_OK;
+}
+
+// rmx_xcorr_batch with a lag window per (window, pair): the bounds are validated here, copied through the ctx's own pinned
+// staging into a ctx-owned device buffer (the caller may reuse its array as soon as the call returns, RMX_OUT_DEVICE
+// included), and rmx_xcorr_batch then dispatches with c->lb set: every route launches the bounded instantiation of its
+// peak-searching kernel (lag_bounds.hpp), or -- the whole-window generic kernels, which have none -- is steered to the
+// per-transform kernels (generic_batch).
+int rmx_xcorr_batch_bounded(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                            const int32_t* lag_bounds, int bounds_per_window, int32_t* lag_int, float* lag_frac, float* peak,
+                            unsigned flags) {
+    if (!c) return RMX_E_INVAL;
+    if (!iq || !lag_int || !lag_frac || !peak || !lag_bounds) return fail(c, RMX_E_INVAL, "NULL buffer");
+    if (n_windows < 0 || n_windows > c->max_windows)
+        return fail(c, RMX_E_INVAL, "n_windows %d not in 0..max_windows=%d", n_windows, c->max_windows);
+    const int all_pairs = c->n_buoys * (c->n_buoys - 1) / 2;
+    if (!pairs) {
+        if (n_pairs != 0 && n_pairs != all_pairs)
+            return fail(c, RMX_E_INVAL, "pairs == NULL needs n_pairs == 0 or %d, got %d", all_pairs, n_pairs);
+        n_pairs = all_pairs;
+    }
+    if (n_pairs < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
+    if (n_windows == 0 || n_pairs == 0) return RMX_OK;
+    const int nm1 = c->n_samples - 1;
+    const long rows = bounds_per_window ? (long)n_windows * n_pairs : (long)n_pairs;
+    bool all_full = true;
+    for (long r = 0; r < rows; ++r) {
+        const int lo = lag_bounds[2 * r], hi = lag_bounds[2 * r + 1];
+        if (lo < -nm1 || hi > nm1 || lo > hi)
+            return fail(c, RMX_E_INVAL, "lag_bounds of window %ld, pair %ld: [%d, %d] is not an interval inside [%d, %d]",
+                        bounds_per_window ? r / n_pairs : -1L, r % n_pairs, lo, hi, -nm1, nm1);
+        all_full = all_full && lo == -nm1 && hi == nm1;
+    }
+    // every interval the full one: that is rmx_xcorr_batch, whatever route it takes (the whole-window generic kernels,
+    // which a bounded call avoids, included)
+    if (all_full) return rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+    RMX_HIP(c, hipSetDevice(c->device));
+    const size_t elems = (size_t)(2 * rows);
+    if (!c->lb_ev) RMX_HIP(c, hipEventCreateWithFlags(&c->lb_ev, hipEventDisableTiming));
+    RMX_HIP(c, hipEventSynchronize(c->lb_ev));   // the previous bounded call's copy out of the staging has finished
+    if (c->h_lb_elems < elems) {
+        if (c->h_lb) (void)hipHostFree(c->h_lb);
+        c->h_lb = nullptr; c->h_lb_elems = 0;
+        RMX_HIP(c, hipHostMalloc((void**)&c->h_lb, elems * sizeof(int32_t), hipHostMallocDefault));
+        c->h_lb_elems = elems;
+    }
+    if (c->d_lb_elems < elems) {
+        RMX_HIP(c, hipStreamSynchronize(c->stream));   // earlier kernels of this ctx may still read the old buffer
+        if (c->d_lb) (void)hipFree(c->d_lb);
+        c->scratch_bytes -= c->d_lb_elems * sizeof(int32_t);
+        c->d_lb = nullptr; c->d_lb_elems = 0;
+        RMX_HIP(c, hipMalloc((void**)&c->d_lb, elems * sizeof(int32_t)));
+        c->d_lb_elems = elems;
+        c->scratch_bytes += elems * sizeof(int32_t);
+    }
+    std::memcpy(c->h_lb, lag_bounds, elems * sizeof(int32_t));
+    // on the ctx stream: behind every earlier kernel that reads d_lb, in front of this call's kernels
+    RMX_HIP(c, hipMemcpyAsync(c->d_lb, c->h_lb, elems * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    RMX_HIP(c, hipEventRecord(c->lb_ev, c->stream));
+    c->lb = LagBounds{c->d_lb, bounds_per_window ? 2L * n_pairs : 0L, 0L, n_pairs};
+    const int rc = rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+    c->lb = LagBounds{nullptr, 0, 0, 0};
+    return rc;
 }
 
 int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,

@@ -141,16 +141,22 @@ class TDoACalculator:
     SPEED_OF_LIGHT = _C  # tdoa_processor.py:141
     MAX_ENGINES = 4      # engines kept alive (one rmx_ctx each: device scratch), least recently used evicted
 
-    def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, min_cut_samples: int = 128):
+    LAG_GUARD_SAMPLES = 2   # bound_lags: samples added on either side of the physical lag interval
+
+    def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, min_cut_samples: int = 128,
+                 bound_lags: bool = False):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
         shortest window a group may be CUT to when its windows differ in length (see _group_windows); 128 is the
-        shortest cut the reference's own clipping can produce."""
+        shortest cut the reference's own clipping can produce.  bound_lags: search each pair's peak only over the lags
+        a geometry can produce (lag_bounds below: |dt| <= baseline / c + rss of the two timing accuracies, plus a guard
+        of LAG_GUARD_SAMPLES); a plain attribute, so `TDoAProcessor().tdoa_calculator.bound_lags = True` works too."""
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
         self.devices = devices
         self.min_cut_samples = int(min_cut_samples)
+        self.bound_lags = bool(bound_lags)
         self._engines: Dict[Tuple[int, int], Any] = {}   # insertion order = recency
         self._tconf: Dict[Tuple[int, int], float] = {}
 
@@ -190,11 +196,12 @@ class TDoACalculator:
             eng.close()
         self._engines.clear()
 
-    def measure_lags(self, iq, pairs=None):
+    def measure_lags(self, iq, pairs=None, lag_bounds=None):
         """Batched hot path.  iq: complex64 [W][B][N] (or uint8 [W][B][2N]) ->
         (lag_int [W][P], lag_frac [W][P], peak [W][P]); lag = delay(j) - delay(i) in samples.
         A leading channel axis is a batch axis: [C][W][B][N] -> three [C][W][P] arrays (channels and
-        windows are independent units, tdoa_processor.py:363)."""
+        windows are independent units, tdoa_processor.py:363).  lag_bounds: None, or int [P][2] / [W][P][2] (with a
+        channel axis: [C][W][P][2]) = the lag window [lo, hi] each pair's peak is searched in."""
         iq = np.asarray(iq)
         lead = None
         if iq.ndim == 4:
@@ -203,7 +210,14 @@ class TDoACalculator:
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N] or [C][W][B][N], got shape {iq.shape}")
         n = iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2]
-        out = self._engine(iq.shape[1], n, iq.shape[0]).correlate(iq, pairs)
+        eng = self._engine(iq.shape[1], n, iq.shape[0])
+        if lag_bounds is None:
+            out = eng.correlate(iq, pairs)
+        else:
+            lb = np.asarray(lag_bounds)
+            if lead is not None and lb.ndim == 4:
+                lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
+            out = eng.correlate(iq, pairs, lag_bounds=lb)
         if lead is not None:
             out = tuple(a.reshape(lead + a.shape[1:]) for a in out)
         return out
@@ -268,11 +282,55 @@ class TDoACalculator:
             iqs = [a[:n * per] for a in iqs]
         return (len(iqs), iqs[0].dtype.str, iqs[0].shape, next(iter(rates))), np.stack(iqs)
 
-    def _measure_groups(self, stacked: np.ndarray):
+    def lag_bounds(self, detections: Sequence[SignalDetection], buoy_positions: Dict[str, BuoyPosition], n: int,
+                   fs: float):
+        """bound_lags: the lag window of every pair (i < j, nested-loop order) of one group of windows of n samples at
+        fs.  A lag is physical when dt = (d_j.gps_timestamp_ns - d_i.gps_timestamp_ns) / 1e9 + lag / fs satisfies
+        |dt| <= D / c + u, D the 3-D distance of the two buoys, u the rss of their timing accuracies (the quantity the
+        reference's confidence uses, tdoa_processor.py:200-210); hence
+            lo = ceil(fs (-D/c - u - ds)) - g,   hi = floor(fs (D/c + u - ds)) + g,   g = LAG_GUARD_SAMPLES,
+        clipped to +-(n - 1).  Returns (bounds int32 [P][2], empty bool [P]): an empty pair (no lag of the window is
+        physical) gets the full interval and is flagged; a pair with an unknown buoy position gets the full interval."""
+        nd = len(detections)
+        nm1 = n - 1
+        bounds, empty = [], []
+        xyz = {}
+        g = self.LAG_GUARD_SAMPLES
+        for i in range(nd):
+            for j in range(i + 1, nd):
+                d1, d2 = detections[i], detections[j]
+                p1, p2 = buoy_positions.get(d1.buoy_id), buoy_positions.get(d2.buoy_id)
+                if not p1 or not p2:
+                    bounds.append((-nm1, nm1))
+                    empty.append(False)
+                    continue
+                for p in (p1, p2):
+                    if p.buoy_id not in xyz:
+                        xyz[p.buoy_id] = GeodeticCalculator.lat_lng_to_xyz(p.lat, p.lng, p.altitude)
+                a, b = xyz[p1.buoy_id], xyz[p2.buoy_id]
+                dist = math.sqrt((a[0] - b[0]) ** 2 + (a[1] - b[1]) ** 2 + (a[2] - b[2]) ** 2)
+                reach = dist / self.SPEED_OF_LIGHT + math.hypot(p1.timing_accuracy_ns, p2.timing_accuracy_ns) * 1e-9
+                ds = (d2.gps_timestamp_ns - d1.gps_timestamp_ns) * 1e-9
+                lo = math.ceil(fs * (-reach - ds)) - g
+                hi = math.floor(fs * (reach - ds)) + g
+                lo, hi = max(lo, -nm1), min(hi, nm1)
+                if lo > hi:
+                    bounds.append((-nm1, nm1))
+                    empty.append(True)
+                else:
+                    bounds.append((lo, hi))
+                    empty.append(False)
+        return np.asarray(bounds, np.int32).reshape(-1, 2), np.asarray(empty, bool)
+
+    def _measure_groups(self, stacked: np.ndarray, lag_bounds=None):
         """[G][B][N] -> lag [G][P] float64, or None after logging: the reference's seam never raises
-        (tdoa_processor.py:151-153) and there is no fallback to time tags once IQ was supplied."""
+        (tdoa_processor.py:151-153) and there is no fallback to time tags once IQ was supplied.  lag_bounds: None, or
+        int [G][P][2] (bound_lags)."""
         try:
-            li, lf, _ = self.measure_lags(stacked)
+            if lag_bounds is None:
+                li, lf, _ = self.measure_lags(stacked)
+            else:
+                li, lf, _ = self.measure_lags(stacked, lag_bounds=lag_bounds)
             return li.astype(np.float64) + lf.astype(np.float64)
         except (ImportError, OSError) as e:   # library not built / not loadable
             self.logger.error(f"Cross-correlation engine failed: {e}")
@@ -312,19 +370,26 @@ class TDoACalculator:
             return out
         lag = None
         fs = None
+        empty = None   # bound_lags: pairs whose lag window is empty (skipped below)
         if _lag is self._NO_LAG:
             key, stacked = self._iq_batch_key(detections)
             if key is False:
                 return out
             if key:
-                res = self._measure_groups(stacked[None])
+                lb = None
+                if self.bound_lags:
+                    per = 2 if stacked.dtype == np.uint8 else 1
+                    lb, empty = self.lag_bounds(detections, buoy_positions, stacked.shape[-1] // per, key[3])
+                    lb = lb[None]
+                res = self._measure_groups(stacked[None], lb)
                 if res is None:
                     return out
                 lag, fs = res[0], key[3]
         elif _lag is None:
             return out
         elif _lag is not self._TIME_TAGS:
-            lag, fs = _lag
+            lag, fs = _lag[0], _lag[1]
+            empty = _lag[2] if len(_lag) > 2 else None
         q = -1
         if lag is not None:
             # the same float64 arithmetic as `round(lag[q] / fs * 1e9)` per pair, done once for the group (numpy scalars make
@@ -340,6 +405,10 @@ class TDoACalculator:
                 q += 1
                 d1, d2 = detections[i], detections[j]
                 if abs(d1.frequency_mhz - d2.frequency_mhz) > 0.01:
+                    continue
+                if empty is not None and empty[q]:
+                    self.logger.warning("TDoA %s-%s skipped: no lag of the window is physical for this baseline and "
+                                        "window-start difference", d1.buoy_id, d2.buoy_id)
                     continue
                 dt_ns = d2.gps_timestamp_ns - d1.gps_timestamp_ns
                 if lag is not None:
@@ -487,8 +556,17 @@ class TDoAProcessor:
         for n, item in enumerate(work):
             if item[2]:
                 batches.setdefault(item[2], []).append(n)
+        calc = self.tdoa_calculator
         for key, members in batches.items():
-            lags = self.tdoa_calculator._measure_groups(np.stack([work[n][3] for n in members]))
+            stacked = np.stack([work[n][3] for n in members])
+            if calc.bound_lags:   # per-window bounds [G][P][2]: each group has its own buoys and window starts
+                n_samp = stacked.shape[-1] // (2 if stacked.dtype == np.uint8 else 1)
+                per = [calc.lag_bounds(work[n][1], self.buoy_positions, n_samp, key[3]) for n in members]
+                lags = calc._measure_groups(stacked, np.stack([b for b, _ in per]))
+                for k, n in enumerate(members):
+                    work[n][4] = None if lags is None else (lags[k], key[3], per[k][1])
+                continue
+            lags = calc._measure_groups(stacked)
             for k, n in enumerate(members):
                 work[n][4] = None if lags is None else (lags[k], key[3])
         results: List[TriangulationResult] = []

@@ -67,6 +67,8 @@ def load_library():
     lib.rmx_clear_default_options.restype = None
     lib.rmx_xcorr_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, cu]
     lib.rmx_xcorr_batch.restype = ci
+    lib.rmx_xcorr_batch_bounded.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, cu]
+    lib.rmx_xcorr_batch_bounded.restype = ci
     lib.rmx_caf_batch.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, cu]
     lib.rmx_caf_batch.restype = ci
     lib.rmx_solve_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, ci, ci, vp, vp, vp, cu]
@@ -88,8 +90,29 @@ def load_library():
     return lib
 
 
+def check_lag_bounds(lag_bounds, n_windows: int, n_pairs: int):
+    """lag_bounds as correlate() takes it -> (contiguous int32 array or None, per_window).  Shape [P][2] (shared by every
+    window) or [W][P][2]; an integer dtype.  Raises ValueError before any call into the library; the values themselves
+    (-(N-1) <= lo <= hi <= N-1) are checked by the library (RmxError, RMX_E_INVAL)."""
+    if lag_bounds is None:
+        return None, False
+    a = np.asarray(lag_bounds)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"lag_bounds must be an integer array, got dtype {a.dtype}")
+    if a.ndim == 2 and a.shape == (n_pairs, 2):
+        per_window = False
+    elif a.ndim == 3 and a.shape == (n_windows, n_pairs, 2):
+        per_window = True
+    else:
+        raise ValueError(f"lag_bounds must be [P][2] = [{n_pairs}][2] or [W][P][2] = [{n_windows}][{n_pairs}][2], "
+                         f"got shape {a.shape}")
+    if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+        raise ValueError("lag_bounds values do not fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32), per_window
+
+
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -233,11 +256,13 @@ class XcorrEngine:
         return np.ascontiguousarray(iq), flags
 
     # -- the hot path ----------------------------------------------------------------------------
-    def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None
+    def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None
                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Host arrays in, host arrays out.  iq: complex64 [W][B][N] (or uint8 [W][B][2N] raw
         rtl_sdr I,Q).  Returns (lag_int int32 [W][P], lag_frac float32 [W][P], peak float32 [W][P]);
-        lag = lag_int + lag_frac = delay(j) - delay(i) in samples."""
+        lag = lag_int + lag_frac = delay(j) - delay(i) in samples.
+        lag_bounds: None (every lag of 'full'), or int [P][2] / [W][P][2] = [lo, hi] per pair (per window): the peak
+        is searched over lags lo..hi only (rmx_xcorr_batch_bounded)."""
         iq, flags = self._check_iq(iq)
         W = iq.shape[0]
         if pairs is not None:
@@ -247,15 +272,22 @@ class XcorrEngine:
         else:
             P = self.n_buoys * (self.n_buoys - 1) // 2
             pp = None
+        lb, per_window = check_lag_bounds(lag_bounds, W, P)
         lag_int = np.zeros((W, P), np.int32)
         lag_frac = np.zeros((W, P), np.float32)
         peak = np.zeros((W, P), np.float32)
         if W == 0 or P == 0:
             return lag_int, lag_frac, peak
-        self._check(self._lib.rmx_xcorr_batch(
-            self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P,
-            lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
-            peak.ctypes.data_as(C.c_void_p), flags))
+        if lb is None:
+            self._check(self._lib.rmx_xcorr_batch(
+                self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P,
+                lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
+                peak.ctypes.data_as(C.c_void_p), flags))
+        else:
+            self._check(self._lib.rmx_xcorr_batch_bounded(
+                self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P, lb.ctypes.data_as(C.c_void_p), int(per_window),
+                lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
+                peak.ctypes.data_as(C.c_void_p), flags))
         return lag_int, lag_frac, peak
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None):
@@ -363,9 +395,9 @@ class XcorrEngine:
                                             flags))
 
     def correlate_device(self, iq_ptr: int, n_windows: int, lag_int_ptr: int, lag_frac_ptr: int,
-                         peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False):
+                         peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None):
         """Device pointers in and out (inputs already resident in HBM); asynchronous on the ctx
-        stream."""
+        stream.  lag_bounds: as for correlate() (a host array; the library keeps its own copy)."""
         if pairs is not None:
             pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
             P = pairs.shape[0]
@@ -374,6 +406,13 @@ class XcorrEngine:
             P = self.n_buoys * (self.n_buoys - 1) // 2
             pp = None
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
-        self._check(self._lib.rmx_xcorr_batch(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
-                                              C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
-                                              C.c_void_p(peak_ptr), flags))
+        lb, per_window = check_lag_bounds(lag_bounds, n_windows, P)
+        if lb is None:
+            self._check(self._lib.rmx_xcorr_batch(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
+                                                  C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
+                                                  C.c_void_p(peak_ptr), flags))
+        else:
+            self._check(self._lib.rmx_xcorr_batch_bounded(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
+                                                          lb.ctypes.data_as(C.c_void_p), int(per_window),
+                                                          C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
+                                                          C.c_void_p(peak_ptr), flags))
