@@ -198,12 +198,17 @@ int rmx_solve_batch(rmx_ctx* ctx, const double* buoy_xyz, int n_buoys, const int
  * (power of two, 16..16384; independent of the ctx's n_samples) complex samples:
  *     P[k] = 20 log10(|FFT_N(iq)[k]| + 1e-12)                            (float32, unpadded, unwindowed)
  *     peaks = scipy.signal.find_peaks(P, height=threshold_db, distance=distance)   (buoy_node.py:411-415)
+ *             (local maxima, a plateau at its midpoint (the lower middle bin), none at bin 0 or n_samples-1; kept
+ *             when P >= (float)threshold_db; then highest-first removal of every peak closer than distance bins to
+ *             a kept one.  Exact ties in P rank the higher bin first: scipy's own order on exact ties comes from
+ *             numpy's unstable argsort and is unspecified.  Any distance >= n_samples acts as n_samples: only the
+ *             highest candidate is kept.)
  *     floor = median(P); snr = P[peak] - floor; confidence = min(max(snr/20, 0), 1) (buoy_node.py:425-427)
  *     a peak is reported unless |signed FFT bin| < dc_exclude_bins (the +-10 kHz of buoy_node.py:419,
  *     i.e. 10e3 * n_samples / sample_rate) or confidence < min_confidence (0.3, buoy_node.py:430)
  *   iq          complex64 [n_windows][n_samples] (or uint8 I,Q pairs with RMX_IN_U8); device with RMX_IN_DEVICE
  *   count       int32 [n_windows]   peaks found (may exceed max_peaks; the arrays hold the first max_peaks,
- *               in ascending bin order as find_peaks returns them)
+ *               in ascending bin order as find_peaks returns them; entries past min(count, max_peaks) are undefined)
  *   bin / power_db / snr_db / confidence   [n_windows][max_peaks];  noise_floor_db float [n_windows]
  *   (device pointers with RMX_OUT_DEVICE).  Frequency of a bin: fftfreq, f_centre + (bin < N/2 ? bin : bin - N) * fs / N. */
 int rmx_detect_batch(rmx_ctx* ctx, const void* iq, int n_windows, int n_samples, float threshold_db, int distance,

@@ -15,8 +15,9 @@
 // median at 256 threads).  The greedy highest-first filter of scipy is evaluated in
 // parallel rounds: an undecided candidate that outranks every undecided candidate within d-1 bins is
 // kept, its neighbours are removed, repeat -- the same set as the sequential sweep.  Ties in height
-// rank the higher bin first (what scipy's argsort-from-the-end does on the short peak lists it
-// insertion-sorts; exact ties between neighbouring float32 dB values do not occur in practice).
+// rank the higher bin first: a rule of this kernel, since scipy's order on exact ties follows numpy's
+// unstable argsort and is unspecified (tests/detect_select_ref.py restates the rule; the host clamps
+// the distance to N, which keeps the same set as any larger distance).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -2644,7 +2644,10 @@ int rmx_detect_batch(rmx_ctx* c, const void* iq, int n_windows, int n_samples, f
     RMX_HIP(c, hipGetLastError());
     const int pthr = N >= 4096 ? 1024 : 256;
     const size_t plds = (size_t)N * 4 + N + (size_t)N + 256 * 4 + 8 * 4 + (size_t)pthr * 4;
-    hipLaunchKernelGGL(rmx::det::d_peaks, dim3(n_windows), dim3(pthr), plds, c->stream, c->dt_pdb, logn, threshold_db, distance,
+    // a distance >= N keeps the single highest candidate, as N does: clamped, so that the kernel's neighbour span
+    // 2 (distance - 1) + 1 stays in int range and each candidate scans at most 2 N - 1 bins
+    const int dist = distance < N ? distance : N;
+    hipLaunchKernelGGL(rmx::det::d_peaks, dim3(n_windows), dim3(pthr), plds, c->stream, c->dt_pdb, logn, threshold_db, dist,
                        dc_exclude_bins, min_confidence, max_peaks, d_count, d_bin, d_pw, d_snr, d_conf, d_floor);
     RMX_HIP(c, hipGetLastError());
     if (!out_dev) {

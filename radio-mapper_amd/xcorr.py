@@ -6,6 +6,7 @@ constructor raises.  (The CPU oracle lives in ``oracle/`` and is test infrastruc
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Tuple
 
@@ -348,7 +349,11 @@ class XcorrEngine:
                min_confidence: float = 0.3, max_peaks: int = 2048):
         """Spectral detection (rmx_detect_batch), host arrays in and out.  iq: complex64 [W][N] (or uint8
         [W][2N]).  Returns a list of W tuples (bins int32, power_db, snr_db, confidence float32 arrays,
-        noise_floor_db float)."""
+        noise_floor_db float).  distance is rounded up, as scipy.signal.find_peaks does, and must be >= 1."""
+        if not distance >= 1:
+            raise ValueError(f"distance must be >= 1, got {distance}")
+        # (any distance >= n_samples acts as n_samples; beyond the int range of the ABI the value is capped there)
+        dist = math.ceil(distance) if distance < 2**31 - 1 else 2**31 - 1
         iq = np.asarray(iq)
         flags = 0
         if iq.dtype == np.uint8:
@@ -367,7 +372,7 @@ class XcorrEngine:
         if W == 0:
             return []
         vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-        self._check(self._lib.rmx_detect_batch(self._ctx, vp(iq), W, N, float(threshold_db), int(distance),
+        self._check(self._lib.rmx_detect_batch(self._ctx, vp(iq), W, N, float(threshold_db), dist,
                                                float(dc_exclude_bins), float(min_confidence), int(max_peaks), vp(cnt),
                                                vp(bins), vp(pw), vp(snr), vp(conf), vp(floor), flags))
         out = []
