@@ -157,6 +157,39 @@ int rmx_xcorr_batch_bounded(rmx_ctx* ctx, const void* iq, int n_windows, const i
                             const int32_t* lag_bounds, int bounds_per_window,
                             int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
 
+/* weightings of rmx_xcorr_batch_weighted() */
+enum { RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1 };
+
+/* Generalized cross-correlation: rmx_xcorr_batch (or rmx_xcorr_batch_bounded) on a band-limited and / or PHAT-whitened
+ * cross-spectrum.  A band keeps one emitter of a wideband capture (two transmitters heard together otherwise share the
+ * stronger one's lag); PHAT sets every bin to unit magnitude, so no single strong line -- the receivers' common DC offset
+ * or LO leakage, which correlates at lag 0 -- dominates the peak.
+ *   band_cps    NULL (every bin), or host double [lo, hi] in cycles per sample (f / fs): [n_windows][2] when
+ *               band_per_window is non-zero (a window is one frequency group: its pairs share a band), else [2] shared
+ *               by every window.  Finite, -0.5 <= lo <= hi <= 0.5; a band that wraps across +-fs/2 is not supported.
+ *               Kept: the signed bins s in [-N, N-1] of the L = 2N point transform with lo <= s / L <= hi, i.e.
+ *               s in [ceil(lo L), floor(hi L)] (exact: L is a power of two).  A band that keeps no bin (e.g. [0.5, 0.5])
+ *               is RMX_E_INVAL, as is any other bad value; rmx_last_error names the window.
+ *   weighting   RMX_WEIGHT_NONE or RMX_WEIGHT_PHAT; anything else is RMX_E_INVAL.
+ *   lag_bounds  NULL, or exactly what rmx_xcorr_batch_bounded takes (the same sliced peak rule).
+ * Definition: X_b = FFT_L(x_b zero padded) as in rmx_xcorr_batch;  Y_b[k] = M_w[k] X_b[k] (NONE) or
+ *   M_w[k] X_b[k] / |X_b[k]| (PHAT; 0 where X_b[k] == 0: a dead receiver gives zeros, never NaN), M_w the 0/1 mask of
+ *   window w's band;  r = IFFT_L(Y_j conj(Y_i)) with numpy's 1/L;  m[k] = |r[(k - (N-1)) mod L]|, k = 0 .. 2N-2;  then
+ *   S4-S6 of rmx_xcorr_batch, or the sliced rule with lag_bounds.  peak = |r| at the integer peak.
+ * Parity against a float32 restatement (tests/weighted_ref.py), with that helper's top-two margin inside the searched
+ *   slice: lag_int bit-exact wherever the margin exceeds 1e-5; lag_frac within 1e-5 * max(|lag|, 1) or the flat-peak
+ *   bound; peak within 1e-5 relative + 1e-6 of the vector's maximum.
+ * No band (or the full one) with RMX_WEIGHT_NONE IS rmx_xcorr_batch / rmx_xcorr_batch_bounded: bit-identical outputs.
+ * Otherwise the weight is applied where each forward spectrum is stored (it factors per buoy), so a weighted call runs the
+ * per-transform kernels at every batch size -- k_fwd + k_pair at N = 4096, g_fwd_small + g_pair_small up to
+ * L = small_maxl, the four-step kernels beyond -- never the whole-window ones (k_win, k_win8kl, k16_*, g_win_*,
+ * g_rows_fused).  Every flag and the custom pair lists mean what they mean there.  The library copies the bands through
+ * its own staging: the caller may reuse its arrays as soon as the call returns, with RMX_OUT_DEVICE too. */
+int rmx_xcorr_batch_weighted(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                             const double* band_cps, int band_per_window, unsigned weighting,
+                             const int32_t* lag_bounds, int bounds_per_window,
+                             int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
+
 /* Cross-ambiguity variant of the hot path (BASELINE configs[4]): for
  * every window and pair (i, j) the later buoy's window is de-rotated by each Doppler hypothesis,
  *     c_d = correlate(x[w][j] * exp(-2*pi*i*doppler_cps[d]*n), x[w][i], 'full', 'fft'),

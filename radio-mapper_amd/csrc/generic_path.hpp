@@ -453,11 +453,11 @@ __device__ __forceinline__ float parabola(float a, float b, float c) {
 
 // ---- small path -------------------------------------------------------------------------------
 // spectrum layout: [item][L] complex, bit-reversed order, scaled by `scale`
-template <bool U8>
+template <bool U8, class... WT>   // WT: empty, or one XWeight (the weighted instantiation, xspec_weight.hpp)
 __global__ __launch_bounds__(1024) void g_fwd_small(const void* __restrict__ iq, float2* __restrict__ spec,
                                                          const float2* __restrict__ tw, int N, int logL,
                                                          long first_item, float scale,
-                                                         const float2* __restrict__ rot = nullptr) {
+                                                         const float2* __restrict__ rot = nullptr, WT... wt_pack) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     float2* x = reinterpret_cast<float2*>(gsm);
     const int L = 1 << logL, tid = threadIdx.x, nthr = blockDim.x;
@@ -476,6 +476,16 @@ __global__ __launch_bounds__(1024) void g_fwd_small(const void* __restrict__ iq,
     __syncthreads();
     lds_dif(x, logL, tw, tid, nthr);
     float2* out = spec + (long)blockIdx.x * L;
+    if constexpr (sizeof...(WT) > 0) {   // rmx_xcorr_batch_weighted: position n holds natural bin bitrev(n)
+        const XWeight wt = xweight_of(wt_pack...);
+        const XBand bd = xband_of(wt, item / wt.n_buoys);
+        for (int n = tid; n < L; n += nthr) {
+            const float2 e = x[lp(n)];
+            const int k = (int)(__brev((unsigned)n) >> (32 - logL));
+            out[n] = xweight_apply(wt, bd, k, L - 1, make_float2(e.x * scale, e.y * scale));
+        }
+        return;
+    }
     for (int n = tid; n < L; n += nthr) {
         const float2 e = x[lp(n)];
         out[n] = make_float2(e.x * scale, e.y * scale);
@@ -563,7 +573,8 @@ __device__ __forceinline__ float2 big_tw(long m, int lo_bits, const float2* __re
 //        X_j[row] conj(X_i[row]) from the spectra (slot = window-in-chunk * n_pairs + pair), which
 //        saves the product's own pass through HBM; the result is written to `data`.
 // LOGR > 0: the row length as a compile-time constant (pass loops unrolled, strides and LDS offsets immediates)
-template <bool FWD, bool TW, bool PROD = false, int LOGR = 0>
+// WT (forward only): empty, or one XWeight (the weighted instantiation, xspec_weight.hpp)
+template <bool FWD, bool TW, bool PROD = false, int LOGR = 0, class... WT>
 __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, const float2* __restrict__ tw, int logR_arg,
                                                     int n_rows, int row_bits, long Ltot, int lo_bits,
                                                     const float2* __restrict__ thi,
@@ -571,7 +582,7 @@ __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, c
                                                     const float2* __restrict__ spec = nullptr,
                                                     const float2* __restrict__ spec_j = nullptr,
                                                     const GPair* __restrict__ pairs = nullptr, int n_pairs = 0,
-                                                    int n_buoys = 0, int tpr_arg = 0) {
+                                                    int n_buoys = 0, int tpr_arg = 0, WT... wt_pack) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     const int logR = LOGR > 0 ? LOGR : logR_arg;
     const int R = 1 << logR;
@@ -604,6 +615,20 @@ __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, c
         // consecutive threads read consecutive elements), the last leaves the spectrum in LDS for the store loop
         fft_dif<0>(x, logR, twl, tid, tpr, make_src([&](int E) -> float2 { return live ? row[E] : make_float2(0.f, 0.f); }), lds);
         __syncthreads();
+        if constexpr (sizeof...(WT) > 0) {   // rmx_xcorr_batch_weighted: [k1'][k2'] holds natural bin k1 + L1 k2,
+            // k1 = bitrev(row index), k2 = bitrev(position) (the column pass's and this pass's DIF orders)
+            static_assert(FWD, "the weight rides on the forward rows");
+            const XWeight wt = xweight_of(wt_pack...);
+            if (live) {
+                const XBand bd = xband_of(wt, wt.w0 + (ridx >> row_bits) / wt.n_buoys);
+                const int k1 = brev(rib, row_bits), lmask = (int)(Ltot - 1);
+                batched<8>(tid, R, tpr, [&](int n) -> float2 { return x[lp(n)]; },
+                           [&](int n, float2 e) {
+                               row[n] = xweight_apply(wt, bd, k1 + (brev(n, logR) << row_bits), lmask,
+                                                      make_float2(e.x * scale, e.y * scale));
+                           });
+            }
+        } else
         if (live)
             batched<8>(tid, R, tpr, [&](int n) -> float2 { return x[lp(n)]; },
                        [&](int n, float2 e) { row[n] = make_float2(e.x * scale, e.y * scale); });

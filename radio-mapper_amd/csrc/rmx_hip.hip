@@ -26,6 +26,7 @@
 #include "../../include/rmx.h"
 #include "host_plan.hpp"
 #include "lag_bounds.hpp"
+#include "xspec_weight.hpp"
 #include "fft_r16.hpp"
 #include "kwin.hpp"
 #include "fft_r8.hpp"
@@ -51,11 +52,12 @@ namespace rmx {
 // Forward spectra.  grid = n_items workgroups of 512; item = wl * B + b inside the chunk.
 //   spec layout: [item][j = 0..7][t = 0..511] float4 = bins of slots (2j, 2j+1) of thread t,
 //   scaled by `scale` (a power of two; the pair kernel's product then carries 1/L exactly).
-template <bool U8>
+template <bool U8, class... WT>   // WT: empty, or one XWeight (the weighted instantiation, xspec_weight.hpp)
 __global__ __launch_bounds__(kThreads, 4) void k_fwd(const void* __restrict__ iq_v, float4* __restrict__ spec,
                                                      const float4* __restrict__ tw1_g,
                                                      const float2* __restrict__ tw2_g, long first_item,
-                                                     float scale, const float2* __restrict__ rot, int wrap_items) {
+                                                     float scale, const float2* __restrict__ rot, int wrap_items,
+                                                     WT... wt_pack) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* xl = reinterpret_cast<float2*>(smem);
     float2* tw2_lds = reinterpret_cast<float2*>(smem + kLdsXchg);
@@ -103,6 +105,14 @@ __global__ __launch_bounds__(kThreads, 4) void k_fwd(const void* __restrict__ iq
     wave_lds_fence();
     xchg_bc_read_c(xl, v, t);
     dft16(v);                         // n0 -> k2
+    if constexpr (sizeof...(WT) > 0) {   // rmx_xcorr_batch_weighted (wrap_items == 0: item is the global item)
+        const XWeight wt = xweight_of(wt_pack...);
+        const XBand bd = xband_of(wt, item / wt.n_buoys);
+        // role C (fft_r16.hpp): u = 16 k0 + k1, slot s = k2 -> natural bin 2 (k0 + 16 k1 + 256 s) + p
+        const int kb = 2 * ((u >> 4) + 16 * (u & 15)) + p;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) v[s] = xweight_apply(wt, bd, kb + 512 * s, kL - 1, v[s]);
+    }
     float4* out = spec + (long)blockIdx.x * (8 * kThreads);
 #pragma unroll
     for (int j = 0; j < 8; ++j)
@@ -748,6 +758,12 @@ struct rmx_ctx {
     int* d_lb = nullptr;  size_t d_lb_elems = 0;
     int32_t* h_lb = nullptr;  size_t h_lb_elems = 0;
     hipEvent_t lb_ev = nullptr;   // the last copy out of h_lb: the next bounded call waits for it before it rewrites h_lb
+    // rmx_xcorr_batch_weighted: the bands as signed bins, staged the same way
+    rmx::XWeight wt{nullptr, 0, 0, 0, 0, 0.0f};   // wt.band != nullptr while a weighted call dispatches
+    int* d_band = nullptr;  size_t d_band_elems = 0;
+    int32_t* h_band = nullptr;  size_t h_band_elems = 0;
+    hipEvent_t band_ev = nullptr;
+    const void* g_rows_fwd_wt_fn = nullptr;   // the weighted instantiation of g_rows_fwd_fn
     // cached pair plan
     std::vector<int32_t> plan_pairs;
     int plan_n_pairs = -1, plan_n_parts = 0, plan_ppb = 0;
@@ -960,16 +976,17 @@ static const void* cols_fwd_fn(int l1, int lt, int thr) {
     }
     return (const void*)g_cols_fwd<U8, 4>;
 }
+template <class... WT>   // WT: empty, or XWeight for the weighted instantiations of the same set
 static const void* rows_fwd_fn(int logR, int tpr) {
     using namespace gen;
-    if (tpr != rows_tpr(1 << logR)) return (const void*)g_rows<true, false, false>;
+    if (tpr != rows_tpr(1 << logR)) return (const void*)g_rows<true, false, false, 0, WT...>;
     switch (logR) {
-        case 9: return (const void*)g_rows<true, false, false, 9>;
-        case 10: return (const void*)g_rows<true, false, false, 10>;
-        case 11: return (const void*)g_rows<true, false, false, 11>;
-        case 12: return (const void*)g_rows<true, false, false, 12>;
-        case 13: return (const void*)g_rows<true, false, false, 13>;
-        default: return (const void*)g_rows<true, false, false>;
+        case 9: return (const void*)g_rows<true, false, false, 9, WT...>;
+        case 10: return (const void*)g_rows<true, false, false, 10, WT...>;
+        case 11: return (const void*)g_rows<true, false, false, 11, WT...>;
+        case 12: return (const void*)g_rows<true, false, false, 12, WT...>;
+        case 13: return (const void*)g_rows<true, false, false, 13, WT...>;
+        default: return (const void*)g_rows<true, false, false, 0, WT...>;
     }
 }
 static const void* rows_inv_fn(int logR, int tpr) {       // the inverse row kernel, row length compiled in where we have it
@@ -1070,6 +1087,8 @@ static int generic_init(rmx_ctx* c) {
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_pair_small<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<false>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<true>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<false, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<true, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         // at most four buoys, 512 <= L <= 4096: whole windows in one kernel, spectra in registers (RMX_WFUSED=0: the two
         // kernels above, as for custom Doppler searches)
         c->g_wfused = c->n_buoys >= 2 && c->n_buoys <= 4 && c->g_logL >= 9 && c->g_logL <= 12;
@@ -1123,8 +1142,10 @@ static int generic_init(rmx_ctx* c) {
         RMX_HIP(c, hipFuncSetAttribute((const void*)(g_rows<true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)(g_rows<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
         c->g_rows_inv_fn = rows_inv_fn(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));
-        c->g_rows_fwd_fn = rows_fwd_fn(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));
+        c->g_rows_fwd_fn = rows_fwd_fn<>(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));
         RMX_HIP(c, hipFuncSetAttribute(c->g_rows_fwd_fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
+        c->g_rows_fwd_wt_fn = rows_fwd_fn<XWeight>(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));   // (weighted calls)
+        RMX_HIP(c, hipFuncSetAttribute(c->g_rows_fwd_wt_fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
         RMX_HIP(c, hipFuncSetAttribute(c->g_rows_inv_fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
         c->g_rows_anchor_fn = rows_anchor_fn(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));
         { long v; if (c->knobs.get("rows_anchor", &v)) { if (v == 0) c->g_rows_anchor_fn = nullptr; else if (v >= 2) c->g_rows_anchor_min_b = (int)v; } }
@@ -1339,7 +1360,16 @@ static int generic_forward(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
         RMX_TM_BEGIN(c);
-        if (u8)
+        if (c->wt.band) {   // weighted call (rmx_xcorr_batch_weighted; never with rot): the stored bins carry fwd_scale
+            XWeight a_wt = c->wt;
+            a_wt.unit = fwd_scale;
+            if (u8)
+                hipLaunchKernelGGL((g_fwd_small<true, XWeight>), dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst,
+                                   c->g_tw, N, logL, first_item, fwd_scale, (const float2*)nullptr, a_wt);
+            else
+                hipLaunchKernelGGL((g_fwd_small<false, XWeight>), dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst,
+                                   c->g_tw, N, logL, first_item, fwd_scale, (const float2*)nullptr, a_wt);
+        } else if (u8)
             hipLaunchKernelGGL(g_fwd_small<true>, dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst, c->g_tw, N, logL,
                                first_item, fwd_scale, rot);
         else
@@ -1378,10 +1408,15 @@ static int generic_forward(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8
         int a_l2 = l2, a_L1 = L1, a_l1 = l1, a_lo = c->g_lo_bits, a_zero = 0, a_tpr = tpr;
         long a_L = L, a_rows = rows;
         float a_scale = fwd_scale;
+        // weighted call (rmx_xcorr_batch_weighted): the same arguments plus the weight, whose chunk starts at window w0
+        XWeight a_wt = c->wt;
+        a_wt.w0 = w0;
+        a_wt.unit = fwd_scale;
         void* args[] = {&a_data, &a_tw, &a_l2, &a_L1, &a_l1, &a_L, &a_lo, &a_thi, &a_tlo, &a_scale, &a_rows, &a_null, &a_null,
-                        &a_pairs, &a_zero, &a_zero, &a_tpr};
+                        &a_pairs, &a_zero, &a_zero, &a_tpr, &a_wt};
         RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_rows_fwd_fn, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), args, rlds, st));
+        RMX_HIP(c, hipLaunchKernel(c->wt.band ? c->g_rows_fwd_wt_fn : c->g_rows_fwd_fn, dim3((unsigned)((rows + rpw - 1) / rpw)),
+                                   dim3(kGThreads), args, rlds, st));
         RMX_TM_END(c, kTkRowsFwd);
     }
     RMX_HIP(c, hipGetLastError());
@@ -1567,7 +1602,11 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
     // two launches cost about 40 us whatever the size, the four-step kernels 26 us for one window: from about 100 transforms
     // (windows x (buoys + pairs)) on it wins (tools/exp_k16_sweep.py: 3 buoys from 16 windows, 5 from 8, 8 from 1).  wscr = 2
     // (tests: "the whole-window kernel, whatever the batch") keeps g_win_eo15, as do pair lists beyond the kernel's LDS copy
-    if (c->g_k16 && c->g_logL == 15 && n_pairs <= k16::kMaxPairs16 &&
+    // Weighted calls (rmx_xcorr_batch_weighted) weight the spectra where the per-transform forward kernels store them:
+    // g_fwd_small up to L = small_maxl, g_cols_fwd + the forward g_rows above.  The whole-window kernels (g_win_*,
+    // k_win8kl), k16_fwd and g_rows_fused keep their spectra to themselves and are never taken.
+    const bool weighted = c->wt.band != nullptr;
+    if (!weighted && c->g_k16 && c->g_logL == 15 && n_pairs <= k16::kMaxPairs16 &&
         (c->g_k16 == 2 || (!c->g_wscr_always &&
                            n_windows >= (int)c->knobs.get_or("k16_min_windows", (100 + c->n_buoys + n_pairs - 1) / (c->n_buoys + n_pairs))))) {
         const int rc16 = generic_ensure(c, n_pairs, false, false);
@@ -1589,9 +1628,9 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
     // peak searches are bounded.  At the BASELINE shapes the fused kernels run either way (k_win, k_win8kl, k16_pairs).
     const bool bounded = c->lb.b != nullptr;
     const bool k8_route = c->g_k8 && (def_list_b || n_pairs <= k8::kMaxPairs8);
-    const bool use_wscr = c->g_wscr && (!bounded || k8_route) &&
+    const bool use_wscr = !weighted && c->g_wscr && (!bounded || k8_route) &&
                           (c->g_wscr_always || ws_blocks >= (c->g_logL == 14 ? (c->g_k8 ? 5L : 7L) : 11L) * c->n_cus / 16);
-    const bool use_wfused = c->g_wfused && !bounded;
+    const bool use_wfused = !weighted && c->g_wfused && !bounded;
     const bool whole_window = use_wfused || use_wscr;   // those kernels keep no per-window state in HBM
     int rc = generic_ensure(c, n_pairs, !whole_window, !whole_window);
     if (rc) return rc;
@@ -1708,7 +1747,8 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
         // the fused row kernel when its (window, row block) units fill the chip at least twice: below that (cfg1's single
         // window: 128 workgroups) its long serial chain per unit loses to the two-kernel passes' wider grids (57 vs 47 us)
         const long fused_blocks = c->g_fused ? (long)wc * (1L << c->g_logL1) / (gen::kGThreads / ((1 << c->g_logL2) >> 4)) : 0;
-        const bool fused = c->g_fused && (1L << c->g_logL) > kGenSmallMaxL && (fused_blocks >= 2L * c->n_cus || c->g_fused_always);
+        const bool fused = !weighted && c->g_fused && (1L << c->g_logL) > kGenSmallMaxL &&
+                           (fused_blocks >= 2L * c->n_cus || c->g_fused_always);
         rc = generic_forward(c, d_iq, w0, wc, u8, nullptr, fused);
         if (rc) return rc;
         rc = generic_pairs(c, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
@@ -1824,6 +1864,9 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
 #endif
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
+        // the weighted instantiations (rmx_xcorr_batch_weighted)
+        RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<false, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<true, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_res<>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsResBytes));
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_win<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
         RMX_HIP(c, hipFuncSetAttribute((const void*)k_win<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
@@ -1874,6 +1917,9 @@ void rmx_destroy(rmx_ctx* c) {
     if (c->d_lb) (void)hipFree(c->d_lb);
     if (c->h_lb) (void)hipHostFree(c->h_lb);
     if (c->lb_ev) (void)hipEventDestroy(c->lb_ev);
+    if (c->d_band) (void)hipFree(c->d_band);
+    if (c->h_band) (void)hipHostFree(c->h_band);
+    if (c->band_ev) (void)hipEventDestroy(c->band_ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1991,7 +2037,16 @@ static int fwd4096(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8, const 
     }
     float4* dst = rot ? c->d_spec_r : c->d_spec;
     RMX_TM_BEGIN(c);
-    if (u8)
+    if (c->wt.band) {   // weighted call (rmx_xcorr_batch_weighted; never with rot): the stored bins carry the TW1 scale
+        XWeight a_wt = c->wt;
+        a_wt.unit = (float)kTw1Scale;
+        if (u8)
+            hipLaunchKernelGGL((k_fwd<true, XWeight>), dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1,
+                               c->d_tw2, first_item, 1.0f, (const float2*)nullptr, 0, a_wt);
+        else
+            hipLaunchKernelGGL((k_fwd<false, XWeight>), dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1,
+                               c->d_tw2, first_item, 1.0f, (const float2*)nullptr, 0, a_wt);
+    } else if (u8)
         hipLaunchKernelGGL(k_fwd<true>, dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1, c->d_tw2,
                            first_item, 1.0f, rot, wrap);
     else
@@ -2116,6 +2171,12 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     int ppb_small = 7;
     if (!c->generic && c->fused && c->small_batch && c->n_buoys >= 3 && n_pairs == all_pairs) {
         small = split_cost4096(c, n_windows, n_pairs, &ppb_small) < host::fused_cost4096(c->n_cus, c->n_buoys, n_pairs, n_windows);
+    }
+    // a weighted call (rmx_xcorr_batch_weighted) weights the spectra where k_fwd stores them: the per-transform kernels
+    // at every batch size, never k_win (whose spectra stay inside the workgroup)
+    if (c->wt.band && !c->generic) {
+        (void)split_cost4096(c, n_windows, n_pairs, &ppb_small);
+        small = true;
     }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
     // The same arithmetic for the LAST round of a larger batch: W = k CUs + r windows cost the fused kernel k + 1 rounds
@@ -2359,6 +2420,84 @@ int rmx_xcorr_batch_bounded(rmx_ctx* c, const void* iq, int n_windows, const int
     c->lb = LagBounds{c->d_lb, bounds_per_window ? 2L * n_pairs : 0L, 0L, n_pairs};
     const int rc = rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
     c->lb = LagBounds{nullptr, 0, 0, 0};
+    return rc;
+}
+
+// rmx_xcorr_batch(_bounded) on band-masked and / or PHAT-whitened spectra: the bands are validated and converted to signed
+// bins here, copied through the ctx's own pinned staging into a ctx-owned device buffer (as the lag bounds are), and the
+// call then dispatches with c->wt set: every route launches the weighted instantiation of its per-transform forward
+// kernel (xspec_weight.hpp) and the pair kernels as they are.  No band (or the full one) and no weighting IS the plain
+// call.
+int rmx_xcorr_batch_weighted(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                             const double* band_cps, int band_per_window, unsigned weighting,
+                             const int32_t* lag_bounds, int bounds_per_window,
+                             int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    if (!c) return RMX_E_INVAL;
+    if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
+    if (weighting != RMX_WEIGHT_NONE && weighting != RMX_WEIGHT_PHAT)
+        return fail(c, RMX_E_INVAL, "unknown weighting %u (RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1)", weighting);
+    if (n_windows < 0 || n_windows > c->max_windows)
+        return fail(c, RMX_E_INVAL, "n_windows %d not in 0..max_windows=%d", n_windows, c->max_windows);
+    const int N = c->n_samples;
+    const long L = 2L * N;
+    const long rows = band_cps ? (band_per_window ? (long)n_windows : 1L) : 1L;
+    std::vector<int32_t> bins((size_t)(2 * rows));
+    bool all_full = true;
+    for (long r = 0; r < rows; ++r) {
+        double lo = -0.5, hi = 0.5;
+        if (band_cps) { lo = band_cps[2 * r]; hi = band_cps[2 * r + 1]; }
+        const char* shared = band_per_window ? "" : " (one band shared by every window)";
+        if (!std::isfinite(lo) || !std::isfinite(hi) || lo < -0.5 || hi > 0.5 || lo > hi)
+            return fail(c, RMX_E_INVAL, "band of window %ld%s: [%g, %g] is not an interval inside [-0.5, 0.5] cycles per sample",
+                        r, shared, lo, hi);
+        // signed bins s in [-N, N-1] with lo <= s / L <= hi (exact: L is a power of two)
+        const long s_lo = (long)std::ceil(lo * (double)L);
+        long s_hi = (long)std::floor(hi * (double)L);
+        if (s_hi > N - 1) s_hi = N - 1;
+        if (s_lo > s_hi)
+            return fail(c, RMX_E_INVAL, "band of window %ld%s: [%g, %g] keeps no bin of the %ld-point transform", r, shared, lo,
+                        hi, L);
+        bins[2 * r] = (int32_t)s_lo;
+        bins[2 * r + 1] = (int32_t)s_hi;
+        all_full = all_full && s_lo == -N && s_hi == N - 1;
+    }
+    // no band and no weighting: that is the plain call, whatever route it takes
+    if (all_full && weighting == RMX_WEIGHT_NONE) {
+        if (lag_bounds)
+            return rmx_xcorr_batch_bounded(c, iq, n_windows, pairs, n_pairs, lag_bounds, bounds_per_window, lag_int, lag_frac,
+                                           peak, flags);
+        return rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+    }
+    if (n_windows == 0) return RMX_OK;
+    RMX_HIP(c, hipSetDevice(c->device));
+    const size_t elems = bins.size();
+    if (!c->band_ev) RMX_HIP(c, hipEventCreateWithFlags(&c->band_ev, hipEventDisableTiming));
+    RMX_HIP(c, hipEventSynchronize(c->band_ev));   // the previous weighted call's copy out of the staging has finished
+    if (c->h_band_elems < elems) {
+        if (c->h_band) (void)hipHostFree(c->h_band);
+        c->h_band = nullptr; c->h_band_elems = 0;
+        RMX_HIP(c, hipHostMalloc((void**)&c->h_band, elems * sizeof(int32_t), hipHostMallocDefault));
+        c->h_band_elems = elems;
+    }
+    if (c->d_band_elems < elems) {
+        RMX_HIP(c, hipStreamSynchronize(c->stream));   // earlier kernels of this ctx may still read the old buffer
+        if (c->d_band) (void)hipFree(c->d_band);
+        c->scratch_bytes -= c->d_band_elems * sizeof(int32_t);
+        c->d_band = nullptr; c->d_band_elems = 0;
+        RMX_HIP(c, hipMalloc((void**)&c->d_band, elems * sizeof(int32_t)));
+        c->d_band_elems = elems;
+        c->scratch_bytes += elems * sizeof(int32_t);
+    }
+    std::memcpy(c->h_band, bins.data(), elems * sizeof(int32_t));
+    // on the ctx stream: behind every earlier kernel that reads d_band, in front of this call's kernels
+    RMX_HIP(c, hipMemcpyAsync(c->d_band, c->h_band, elems * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    RMX_HIP(c, hipEventRecord(c->band_ev, c->stream));
+    c->wt = XWeight{c->d_band, (band_cps && band_per_window) ? 2L : 0L, 0L, c->n_buoys,
+                    weighting == RMX_WEIGHT_PHAT ? 1 : 0, 1.0f};
+    const int rc = lag_bounds ? rmx_xcorr_batch_bounded(c, iq, n_windows, pairs, n_pairs, lag_bounds, bounds_per_window,
+                                                        lag_int, lag_frac, peak, flags)
+                              : rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+    c->wt = XWeight{nullptr, 0, 0, 0, 0, 0.0f};
     return rc;
 }
 

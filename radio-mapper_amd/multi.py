@@ -21,7 +21,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .shard import window_shard
-from .xcorr import check_lag_bounds
+from .xcorr import check_band, check_lag_bounds
 
 
 class MultiXcorrEngine:
@@ -116,20 +116,30 @@ class MultiXcorrEngine:
         return tuple(outs)
 
     # -- the hot path --------------------------------------------------------------------------------
-    def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None):
+    def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
+                  whiten: bool = False):
         """iq: complex64 [W][B][N] or uint8 [W][B][2N] -> (lag_int [W][P], lag_frac [W][P], peak [W][P]).
-        lag_bounds: None, [P][2] (every block gets it whole) or [W][P][2] (each block gets its own windows' rows)."""
+        lag_bounds: None, [P][2] (every block gets it whole) or [W][P][2] (each block gets its own windows' rows).
+        band: None, [2] (every block gets it whole) or [W][2] (each block its own windows' rows); whiten: PHAT."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
         lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
 
+        bd, band_pw = check_band(band, iq.shape[0])
+
         def block_bounds(s, c):
             return lb[s:s + c] if per_window else lb
-        return self._run(iq.shape[0], lambda eng, s, c: eng.correlate(iq[s:s + c], pairs, block_bounds(s, c))
-                         if lb is not None else eng.correlate(iq[s:s + c], pairs), 3,
-                         (np.int32, np.float32, np.float32), P)
+
+        def block_call(eng, s, c):
+            if bd is not None or whiten:
+                return eng.correlate(iq[s:s + c], pairs, None if lb is None else block_bounds(s, c),
+                                     band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten)
+            if lb is not None:
+                return eng.correlate(iq[s:s + c], pairs, block_bounds(s, c))
+            return eng.correlate(iq[s:s + c], pairs)
+        return self._run(iq.shape[0], block_call, 3, (np.int32, np.float32, np.float32), P)
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None):
         """Cross-ambiguity search -> (doppler_idx, lag_int, lag_frac, peak), each [W][P]."""

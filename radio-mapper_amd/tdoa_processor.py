@@ -8,7 +8,8 @@ Same public names, argument meaning and error behaviour as the reference module 
   -----------------------------------------------------  ------------------------------------------
   BuoyPosition / SignalDetection / TDoAMeasurement /      same field names and order (:24-69);
   TriangulationResult dataclasses                          SignalDetection gains two OPTIONAL trailing
-                                                           fields (iq_samples, sample_rate_hz)
+                                                           fields (iq_samples, sample_rate_hz,
+                                                           center_freq_hz, bandwidth_hz)
   GeodeticCalculator (:71-136)                             same statics (spherical ECEF, R=6378137)
   TDoACalculator.calculate_tdoa_measurements (:146-198)    same pair order / skips / confidence;
                                                            ``time_diff_ns`` (:166) becomes
@@ -67,6 +68,10 @@ class SignalDetection:
     # gps_timestamp_ns is then the time tag of the window's first sample.
     iq_samples: Optional[Any] = None          # np.ndarray complex64 [N] or raw uint8 [2N]
     sample_rate_hz: Optional[float] = None
+    # the capture's tuning (its centre frequency) and the emitter's bandwidth (the reference's wire records carry
+    # bandwidth_hz, iq_stream_client.py:46-60): what TDoACalculator(band_limit=True) derives a group's band from
+    center_freq_hz: Optional[float] = None
+    bandwidth_hz: Optional[float] = None
 
 
 @dataclass
@@ -142,21 +147,28 @@ class TDoACalculator:
     MAX_ENGINES = 4      # engines kept alive (one rmx_ctx each: device scratch), least recently used evicted
 
     LAG_GUARD_SAMPLES = 2   # bound_lags: samples added on either side of the physical lag interval
+    DEFAULT_BANDWIDTH_HZ = 10e3   # band_limit: a detection without bandwidth_hz (the reference's default, central_processor.py:52)
 
     def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, min_cut_samples: int = 128,
-                 bound_lags: bool = False):
+                 bound_lags: bool = False, band_limit: bool = False, whiten: bool = False):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
         shortest window a group may be CUT to when its windows differ in length (see _group_windows); 128 is the
         shortest cut the reference's own clipping can produce.  bound_lags: search each pair's peak only over the lags
         a geometry can produce (lag_bounds below: |dt| <= baseline / c + rss of the two timing accuracies, plus a guard
-        of LAG_GUARD_SAMPLES); a plain attribute, so `TDoAProcessor().tdoa_calculator.bound_lags = True` works too."""
+        of LAG_GUARD_SAMPLES); a plain attribute, so `TDoAProcessor().tdoa_calculator.bound_lags = True` works too.
+        band_limit: correlate each group over its emitter's band only (band() below: the detections' frequencies and
+        bandwidths around the capture's centre frequency), so that two transmitters heard in one capture each get their
+        own lags.  whiten: PHAT weighting of every group with IQ (no strong spectral line -- the receivers' DC offset, LO
+        leakage -- dominates the peak).  Both plain attributes, off by default."""
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
         self.devices = devices
         self.min_cut_samples = int(min_cut_samples)
         self.bound_lags = bool(bound_lags)
+        self.band_limit = bool(band_limit)
+        self.whiten = bool(whiten)
         self._engines: Dict[Tuple[int, int], Any] = {}   # insertion order = recency
         self._tconf: Dict[Tuple[int, int], float] = {}
 
@@ -196,12 +208,14 @@ class TDoACalculator:
             eng.close()
         self._engines.clear()
 
-    def measure_lags(self, iq, pairs=None, lag_bounds=None):
+    def measure_lags(self, iq, pairs=None, lag_bounds=None, band=None, whiten=False):
         """Batched hot path.  iq: complex64 [W][B][N] (or uint8 [W][B][2N]) ->
         (lag_int [W][P], lag_frac [W][P], peak [W][P]); lag = delay(j) - delay(i) in samples.
         A leading channel axis is a batch axis: [C][W][B][N] -> three [C][W][P] arrays (channels and
         windows are independent units, tdoa_processor.py:363).  lag_bounds: None, or int [P][2] / [W][P][2] (with a
-        channel axis: [C][W][P][2]) = the lag window [lo, hi] each pair's peak is searched in."""
+        channel axis: [C][W][P][2]) = the lag window [lo, hi] each pair's peak is searched in.  band: None, or float [2] /
+        [W][2] (with a channel axis: [C][W][2]) = the band [lo, hi] in cycles per sample kept of the cross-spectrum;
+        whiten: PHAT weighting (rmx_xcorr_batch_weighted)."""
         iq = np.asarray(iq)
         lead = None
         if iq.ndim == 4:
@@ -211,12 +225,21 @@ class TDoACalculator:
             raise ValueError(f"iq must be [W][B][N] or [C][W][B][N], got shape {iq.shape}")
         n = iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2]
         eng = self._engine(iq.shape[1], n, iq.shape[0])
-        if lag_bounds is None:
-            out = eng.correlate(iq, pairs)
-        else:
+        lb = None
+        if lag_bounds is not None:
             lb = np.asarray(lag_bounds)
             if lead is not None and lb.ndim == 4:
                 lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
+        if band is not None or whiten:
+            bd = None
+            if band is not None:
+                bd = np.asarray(band)
+                if lead is not None and bd.ndim == 3:
+                    bd = bd.reshape((lead[0] * lead[1],) + bd.shape[2:])
+            out = eng.correlate(iq, pairs, lag_bounds=lb, band=bd, whiten=bool(whiten))
+        elif lb is None:
+            out = eng.correlate(iq, pairs)
+        else:
             out = eng.correlate(iq, pairs, lag_bounds=lb)
         if lead is not None:
             out = tuple(a.reshape(lead + a.shape[1:]) for a in out)
@@ -322,15 +345,48 @@ class TDoACalculator:
                     empty.append(False)
         return np.asarray(bounds, np.int32).reshape(-1, 2), np.asarray(empty, bool)
 
-    def _measure_groups(self, stacked: np.ndarray, lag_bounds=None):
+    def band(self, detections: Sequence[SignalDetection], n: int, fs: float):
+        """band_limit: the band of one group of windows of n samples at fs, as (band float [2] in cycles per sample or
+        None, reason or None).  With every detection's centre frequency fc known:
+            [(min(f - bw/2) - fc) / fs, (max(f + bw/2) - fc) / fs]   clipped to +-0.5,
+        f = frequency_mhz * 1e6, bw = bandwidth_hz or DEFAULT_BANDWIDTH_HZ (for one bandwidth: f_min - bw/2 .. f_max + bw/2).
+        (None, None) when no detection carries a centre frequency (the full band, as without band_limit); (None, reason)
+        when the group cannot be band limited: only some detections carry a centre frequency, they disagree, the band
+        misses the capture, or it keeps no bin of the 2n-point transform."""
+        fcs = [d.center_freq_hz for d in detections]
+        if all(f is None for f in fcs):
+            return None, None
+        if any(f is None for f in fcs):
+            return None, "only some detections of the group carry a centre frequency"
+        fcs = [float(f) for f in fcs]
+        if max(fcs) - min(fcs) > 1.0:
+            return None, f"the group's centre frequencies disagree ({min(fcs):.0f} .. {max(fcs):.0f} Hz)"
+        fc = fcs[0]
+        bws = [self.DEFAULT_BANDWIDTH_HZ if d.bandwidth_hz is None else float(d.bandwidth_hz) for d in detections]
+        lo = (min(d.frequency_mhz * 1e6 - bw / 2 for d, bw in zip(detections, bws)) - fc) / fs
+        hi = (max(d.frequency_mhz * 1e6 + bw / 2 for d, bw in zip(detections, bws)) - fc) / fs
+        if not (math.isfinite(lo) and math.isfinite(hi)) or hi < -0.5 or lo > 0.5 or lo > hi:
+            return None, (f"the group's band [{lo:.4f}, {hi:.4f}] cycles per sample misses the capture "
+                          f"(centre {fc:.0f} Hz, {fs:.0f} samples/s)")
+        lo, hi = max(lo, -0.5), min(hi, 0.5)
+        L = 2 * n
+        if math.ceil(lo * L) > min(math.floor(hi * L), n - 1):
+            return None, f"the group's band [{lo:.6f}, {hi:.6f}] cycles per sample keeps no bin of a {L}-point transform"
+        return np.array([lo, hi], np.float64), None
+
+    def _measure_groups(self, stacked: np.ndarray, lag_bounds=None, band=None):
         """[G][B][N] -> lag [G][P] float64, or None after logging: the reference's seam never raises
         (tdoa_processor.py:151-153) and there is no fallback to time tags once IQ was supplied.  lag_bounds: None, or
-        int [G][P][2] (bound_lags)."""
+        int [G][P][2] (bound_lags); band: None, or float [G][2] (band_limit); whiten applies to every group."""
+        kw = {}
+        if lag_bounds is not None:
+            kw["lag_bounds"] = lag_bounds
+        if band is not None:
+            kw["band"] = band
+        if self.whiten:
+            kw["whiten"] = True
         try:
-            if lag_bounds is None:
-                li, lf, _ = self.measure_lags(stacked)
-            else:
-                li, lf, _ = self.measure_lags(stacked, lag_bounds=lag_bounds)
+            li, lf, _ = self.measure_lags(stacked, **kw)
             return li.astype(np.float64) + lf.astype(np.float64)
         except (ImportError, OSError) as e:   # library not built / not loadable
             self.logger.error(f"Cross-correlation engine failed: {e}")
@@ -377,11 +433,17 @@ class TDoACalculator:
                 return out
             if key:
                 lb = None
+                per = 2 if stacked.dtype == np.uint8 else 1
                 if self.bound_lags:
-                    per = 2 if stacked.dtype == np.uint8 else 1
                     lb, empty = self.lag_bounds(detections, buoy_positions, stacked.shape[-1] // per, key[3])
                     lb = lb[None]
-                res = self._measure_groups(stacked[None], lb)
+                band = None
+                if self.band_limit:
+                    band, why = self.band(detections, stacked.shape[-1] // per, key[3])
+                    if why:
+                        self.logger.error(f"Cannot band limit the group: {why}; no TDoA measurements for it")
+                        return out
+                res = self._measure_groups(stacked[None], lb, None if band is None else band[None])
                 if res is None:
                     return out
                 lag, fs = res[0], key[3]
@@ -503,9 +565,10 @@ class HyperbolicPositioning:
 # orchestrator (tdoa_processor.py:330-465)
 # --------------------------------------------------------------------------------------------------
 class TDoAProcessor:
-    def __init__(self):
+    def __init__(self, band_limit: bool = False, whiten: bool = False):
+        """band_limit, whiten: the TDoACalculator settings of the same names (off by default)."""
         self.logger = logging.getLogger(__name__ + ".TDoAProcessor")
-        self.tdoa_calculator = TDoACalculator()
+        self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten)
         self.hyperbolic_positioner = HyperbolicPositioning()
         self.buoy_positions: Dict[str, BuoyPosition] = {}
         self.correlation_window_s = 10.0
@@ -558,15 +621,30 @@ class TDoAProcessor:
                 batches.setdefault(item[2], []).append(n)
         calc = self.tdoa_calculator
         for key, members in batches.items():
+            n_samp = work[members[0]][3].shape[-1] // (2 if work[members[0]][3].dtype == np.uint8 else 1)
+            band = None
+            if calc.band_limit:   # one band per group: [G][2]; a group that cannot be band limited gets no measurements
+                bands = {}
+                for n in list(members):
+                    b, why = calc.band(work[n][1], n_samp, key[3])
+                    if why:
+                        calc.logger.error(f"Cannot band limit the group at {work[n][0]} MHz: {why}; no TDoA measurements for it")
+                        work[n][4] = None
+                        members.remove(n)
+                    else:
+                        bands[n] = b
+                if not members:
+                    continue
+                if any(bands[n] is not None for n in members):
+                    band = np.stack([np.array([-0.5, 0.5]) if bands[n] is None else bands[n] for n in members])
             stacked = np.stack([work[n][3] for n in members])
             if calc.bound_lags:   # per-window bounds [G][P][2]: each group has its own buoys and window starts
-                n_samp = stacked.shape[-1] // (2 if stacked.dtype == np.uint8 else 1)
                 per = [calc.lag_bounds(work[n][1], self.buoy_positions, n_samp, key[3]) for n in members]
-                lags = calc._measure_groups(stacked, np.stack([b for b, _ in per]))
+                lags = calc._measure_groups(stacked, np.stack([b for b, _ in per]), band)
                 for k, n in enumerate(members):
                     work[n][4] = None if lags is None else (lags[k], key[3], per[k][1])
                 continue
-            lags = calc._measure_groups(stacked)
+            lags = calc._measure_groups(stacked, None, band)
             for k, n in enumerate(members):
                 work[n][4] = None if lags is None else (lags[k], key[3])
         results: List[TriangulationResult] = []

@@ -20,6 +20,9 @@ RMX_IN_DEVICE = 1
 RMX_OUT_DEVICE = 2
 RMX_IN_U8 = 4
 
+RMX_WEIGHT_NONE = 0
+RMX_WEIGHT_PHAT = 1
+
 _lib = None
 
 
@@ -70,6 +73,8 @@ def load_library():
     lib.rmx_xcorr_batch.restype = ci
     lib.rmx_xcorr_batch_bounded.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, cu]
     lib.rmx_xcorr_batch_bounded.restype = ci
+    lib.rmx_xcorr_batch_weighted.argtypes = [vp, vp, ci, vp, ci, vp, ci, cu, vp, ci, vp, vp, vp, cu]
+    lib.rmx_xcorr_batch_weighted.restype = ci
     lib.rmx_caf_batch.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, cu]
     lib.rmx_caf_batch.restype = ci
     lib.rmx_solve_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, ci, ci, vp, vp, vp, cu]
@@ -112,8 +117,33 @@ def check_lag_bounds(lag_bounds, n_windows: int, n_pairs: int):
     return np.ascontiguousarray(a, dtype=np.int32), per_window
 
 
+def check_band(band, n_windows: int):
+    """band as correlate() takes it -> (contiguous float64 array or None, per_window).  Shape [2] (one [lo, hi] shared by
+    every window) or [W][2], in cycles per sample; finite, -0.5 <= lo <= hi <= 0.5.  Raises ValueError before any call
+    into the library.  Whether a band keeps a bin at all depends on the window length: the library checks that
+    (RmxError, RMX_E_INVAL)."""
+    if band is None:
+        return None, False
+    a = np.asarray(band)
+    if a.dtype.kind not in "iuf":
+        raise ValueError(f"band must be a real array, got dtype {a.dtype}")
+    if a.shape == (2,):
+        per_window = False
+    elif a.ndim == 2 and a.shape == (n_windows, 2):
+        per_window = True
+    else:
+        raise ValueError(f"band must be [2] or [W][2] = [{n_windows}][2], got shape {a.shape}")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if not np.all(np.isfinite(a)):
+        raise ValueError("band values must be finite")
+    lo, hi = a[..., 0], a[..., 1]
+    if np.any(lo < -0.5) or np.any(hi > 0.5) or np.any(lo > hi):
+        raise ValueError("band must satisfy -0.5 <= lo <= hi <= 0.5 (cycles per sample; no wrap across +-fs/2)")
+    return a, per_window
+
+
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -257,13 +287,15 @@ class XcorrEngine:
         return np.ascontiguousarray(iq), flags
 
     # -- the hot path ----------------------------------------------------------------------------
-    def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None
-                  ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
+                  whiten: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Host arrays in, host arrays out.  iq: complex64 [W][B][N] (or uint8 [W][B][2N] raw
         rtl_sdr I,Q).  Returns (lag_int int32 [W][P], lag_frac float32 [W][P], peak float32 [W][P]);
         lag = lag_int + lag_frac = delay(j) - delay(i) in samples.
         lag_bounds: None (every lag of 'full'), or int [P][2] / [W][P][2] = [lo, hi] per pair (per window): the peak
-        is searched over lags lo..hi only (rmx_xcorr_batch_bounded)."""
+        is searched over lags lo..hi only (rmx_xcorr_batch_bounded).
+        band: None (every bin), or float [2] / [W][2] = [lo, hi] in cycles per sample (f / fs) kept of the
+        cross-spectrum; whiten: PHAT, every bin at unit magnitude (rmx_xcorr_batch_weighted)."""
         iq, flags = self._check_iq(iq)
         W = iq.shape[0]
         if pairs is not None:
@@ -274,12 +306,21 @@ class XcorrEngine:
             P = self.n_buoys * (self.n_buoys - 1) // 2
             pp = None
         lb, per_window = check_lag_bounds(lag_bounds, W, P)
+        bd, band_pw = check_band(band, W)
         lag_int = np.zeros((W, P), np.int32)
         lag_frac = np.zeros((W, P), np.float32)
         peak = np.zeros((W, P), np.float32)
         if W == 0 or P == 0:
             return lag_int, lag_frac, peak
-        if lb is None:
+        if bd is not None or whiten:
+            self._check(self._lib.rmx_xcorr_batch_weighted(
+                self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P,
+                None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
+                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
+                None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window),
+                lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
+                peak.ctypes.data_as(C.c_void_p), flags))
+        elif lb is None:
             self._check(self._lib.rmx_xcorr_batch(
                 self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P,
                 lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
@@ -400,9 +441,10 @@ class XcorrEngine:
                                             flags))
 
     def correlate_device(self, iq_ptr: int, n_windows: int, lag_int_ptr: int, lag_frac_ptr: int,
-                         peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None):
+                         peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
+                         band=None, whiten: bool = False):
         """Device pointers in and out (inputs already resident in HBM); asynchronous on the ctx
-        stream.  lag_bounds: as for correlate() (a host array; the library keeps its own copy)."""
+        stream.  lag_bounds, band, whiten: as for correlate() (host arrays; the library keeps its own copies)."""
         if pairs is not None:
             pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
             P = pairs.shape[0]
@@ -412,7 +454,14 @@ class XcorrEngine:
             pp = None
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
         lb, per_window = check_lag_bounds(lag_bounds, n_windows, P)
-        if lb is None:
+        bd, band_pw = check_band(band, n_windows)
+        if bd is not None or whiten:
+            self._check(self._lib.rmx_xcorr_batch_weighted(
+                self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P, None if bd is None else bd.ctypes.data_as(C.c_void_p),
+                int(band_pw), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
+                None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window),
+                C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags))
+        elif lb is None:
             self._check(self._lib.rmx_xcorr_batch(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
                                                   C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
                                                   C.c_void_p(peak_ptr), flags))
