@@ -190,6 +190,40 @@ int rmx_xcorr_batch_weighted(rmx_ctx* ctx, const void* iq, int n_windows, const 
                              const int32_t* lag_bounds, int bounds_per_window,
                              int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
 
+/* Noncoherent integration: rmx_xcorr_batch_weighted with ONE peak search per group of `integrate` consecutive windows,
+ * on the lag-by-lag sum of the windows' squared correlation magnitudes.  Two receivers with free-running oscillators stay
+ * phase-coherent over a short segment only (a frequency offset rotates the cross-spectrum and the coherent peak of a long
+ * window collapses), and a weak emitter's single-window peak may lie below the largest noise lag; cutting the capture
+ * into K short windows and summing |c|^2 over them repairs both, without a Doppler search.
+ *   integrate   K >= 1 windows per group.  n_windows must be a positive multiple of K; windows g K .. g K + K - 1 form
+ *               group g, G = n_windows / K groups.  Anything else is RMX_E_INVAL (the values in rmx_last_error).
+ *   band_cps, band_per_window, weighting   exactly as in rmx_xcorr_batch_weighted: bands stay per WINDOW ([n_windows][2] or [2]).
+ *   lag_bounds  NULL, or host int32 [lo, hi]: [G][n_pairs][2] when bounds_per_group is non-zero, else [n_pairs][2] shared
+ *               by every group; the sliced rule of rmx_xcorr_batch_bounded, applied to m below.
+ *   lag_int / lag_frac / peak   [G][n_pairs] (not [n_windows][n_pairs]).
+ * Definition, for group g and pair (i, j): c_w = the correlation of window w exactly as rmx_xcorr_batch_weighted defines
+ *   it (band mask and PHAT where given);  s[k] = sum over the group's windows, in window order, of |c_w[k]|^2 in float32;
+ *   m[k] = sqrt(s[k]) (scipy scaling: the root-sum-square of the per-window magnitudes);  then S4-S6 of rmx_xcorr_batch on
+ *   m -- argmax with the lowest index on ties, the parabola on m[k-1], m[k], m[k+1], peak = m[k] -- or the sliced rule
+ *   with lag_bounds.  The kernels search the maximum of s and take the square root of the three taps only; the note on
+ *   that at rmx_xcorr_batch applies unchanged.  The additions of a lag's K terms are made by one thread in window order:
+ *   two identical calls give bit-identical outputs.
+ * Parity against a float32 restatement (tests/integrated_ref.py) is that of rmx_xcorr_batch_weighted, computed on m; the
+ *   in-order float32 sum of K positive terms adds at most (K - 1) 2^-24 relative (4e-6 at K = 64).
+ * integrate == 1 IS rmx_xcorr_batch_weighted with the same arguments: bit-identical outputs.
+ * Otherwise the call runs the per-transform kernels at every batch size, like a weighted call -- k_fwd + k_pair (the
+ * streaming variant) at N = 4096, g_fwd_small + g_pair_small up to L = small_maxl, the four-step kernels beyond, for every
+ * N rmx_create accepts -- never the whole-window ones.  The forward kernels run on all windows; the pair / peak kernels
+ * run one work item per (group, pair) that walks the group's windows (radio-mapper_amd/csrc/integrate.hpp).  Flags,
+ * custom pair lists and chunking mean what they mean for the weighted entry.  A chunk always holds whole groups: K larger
+ * than the largest chunk the ctx can hold (option "chunk_windows" at N = 4096, the scratch budget elsewhere) is
+ * RMX_E_INVAL with a text that says so, never a silent split. */
+int rmx_xcorr_batch_integrated(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                               int integrate,
+                               const double* band_cps, int band_per_window, unsigned weighting,
+                               const int32_t* lag_bounds, int bounds_per_group,
+                               int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
+
 /* Cross-ambiguity variant of the hot path (BASELINE configs[4]): for
  * every window and pair (i, j) the later buoy's window is de-rotated by each Doppler hypothesis,
  *     c_d = correlate(x[w][j] * exp(-2*pi*i*doppler_cps[d]*n), x[w][i], 'full', 'fft'),

@@ -496,7 +496,84 @@ struct GPair {
     int i, j;
 };
 
-template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation, lag_bounds.hpp)
+// The integrating instantiation of g_pair_small (integrate.hpp): workgroup = (group, pair).  Thread tid owns the circular
+// lags m = tid + e nthr, e < 16 (L <= 16 nthr for every L this kernel runs), in every window of the group; their |r|^2
+// are added in window order into acc[e], and the scan, the workgroup argmax and the parabola run once on the sums.
+// The three taps live in their owners' registers: the owners publish them (as the N = 4096 pair kernel does).
+__device__ __forceinline__ void pair_small_integ(const float2* __restrict__ spec, const float2* __restrict__ tw,
+                                                 const GPair* __restrict__ pairs, int n_pairs, int n_buoys, int N, int logL,
+                                                 long first_group, float out_scale, int* __restrict__ lag_int,
+                                                 float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K) {
+    extern __shared__ __attribute__((aligned(16))) char gsm[];
+    float2* x = reinterpret_cast<float2*>(gsm);
+    const int L = 1 << logL, tid = threadIdx.x, nthr = blockDim.x;
+    float* sv = reinterpret_cast<float*>(gsm + (size_t)lp(L) * 8);
+    int* sk = reinterpret_cast<int*>(sv + nthr);
+    const int gl = blockIdx.x / n_pairs, q = blockIdx.x % n_pairs;
+    const GPair pr = pairs[q];
+    float acc[kIntegMaxPerThread];
+#pragma unroll
+    for (int e = 0; e < kIntegMaxPerThread; ++e) acc[e] = 0.0f;
+    for (int kw = 0; kw < K; ++kw) {
+        const long wl = (long)gl * K + kw;
+        const float2* xi = spec + (wl * n_buoys + pr.i) * L;
+        const float2* xj = spec + (wl * n_buoys + pr.j) * L;
+        batched<4>(tid, L, nthr, [&](int n) -> float4 { const float2 a = xj[n], b = xi[n]; return make_float4(a.x, a.y, b.x, b.y); },
+                   [&](int n, float4 v) { x[lp(n)] = g_cmulc(make_float2(v.x, v.y), make_float2(v.z, v.w)); });   // X_j conj(X_i)
+        __syncthreads();
+        lds_dit_inv(x, logL, tw, tid, nthr);
+#pragma unroll
+        for (int e = 0; e < kIntegMaxPerThread; ++e) {
+            const int m = tid + e * nthr;
+            if (m < L) {
+                const float2 r = x[lp(m)];
+                acc[e] += r.x * r.x + r.y * r.y;
+            }
+        }
+        __syncthreads();   // the next window's product overwrites x
+    }
+    float best = -1.0f;
+    int bk = 0x7fffffff;
+    int klo, khi;
+    lag_window(lb, first_group + gl, q, N - 1, klo, khi);
+#pragma unroll
+    for (int e = 0; e < kIntegMaxPerThread; ++e) {
+        const int m = tid + e * nthr;
+        const int k = full_index(m, N);
+        if (m < L && k >= 0 && (unsigned)(k - klo) <= (unsigned)(khi - klo)) {
+            const float v = acc[e];
+            if (v > best || (v == best && k < bk)) { best = v; bk = k; }
+        }
+    }
+    block_argmax(best, bk, sv, sk, tid, nthr);
+#pragma unroll
+    for (int d = -1; d <= 1; ++d) {
+        const int kk = bk + d;
+        if (kk >= 0 && kk <= 2 * N - 2) {
+            const int m = circ_index(kk, N);
+            if ((m & (nthr - 1)) == tid) {
+                const int eo = m / nthr;
+                float val = 0.0f;
+#pragma unroll
+                for (int e = 0; e < kIntegMaxPerThread; ++e)
+                    if (e == eo) val = acc[e];
+                sv[d + 1] = sqrtf(val) * out_scale;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const float b = sv[1];
+        const float frac = (bk > klo && bk < khi) ? parabola(sv[0], b, sv[2]) : 0.0f;   // 0 at the lag window's edges
+        const long o = (first_group + gl) * (long)n_pairs + q;
+        lag_int[o] = bk - (N - 1);
+        lag_frac[o] = frac;
+        peak[o] = b;
+    }
+}
+
+// LB: empty, one LagBounds (the bounded instantiation, lag_bounds.hpp), or <LagBounds, Integrate> (integrate.hpp)
+template <class... LB>
 __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ spec, const float2* __restrict__ spec_j,
                                                           const float2* __restrict__ tw,
                                                           const GPair* __restrict__ pairs, int n_pairs,
@@ -504,6 +581,11 @@ __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ 
                                                           float out_scale, int* __restrict__ lag_int,
                                                           float* __restrict__ lag_frac, float* __restrict__ peak,
                                                           LB... lb_pack) {
+    if constexpr (kIntegrating<LB...>) {   // (first_window: the chunk's first GROUP; spec_j == spec)
+        pair_small_integ(spec, tw, pairs, n_pairs, n_buoys, N, logL, first_window, out_scale, lag_int, lag_frac, peak,
+                         integ_bounds(lb_pack...), integ_windows(lb_pack...));
+        return;
+    }
     constexpr bool BOUNDED = sizeof...(LB) > 0;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     float2* x = reinterpret_cast<float2*>(gsm);
@@ -1750,11 +1832,95 @@ struct GTile {
     int k;          // its lowest 'full' index
     float tm, tp;   // |r|^2 at k-1, k+1, or -1 where that lag lives in another tile (or does not exist)
 };
+// The integrating instantiation of g_cols_inv (integrate.hpp): blockIdx.y is a (group, pair) slot gs = g P + q; the
+// workgroup walks the K product slots ((g K + w) P + q) of its group.  A tile holds whole columns and this is the last
+// pass, so the sum stays inside the tile: every window's |r|^2 lands in the tile image as in the plain kernel, thread tid
+// adds the elements tid + e nthr (e < 16: a tile has at most 16 elements per thread at the thread counts the host
+// launches this instantiation with) into acc[e], and after the last window the sums go back into the image.  The
+// candidate scan, the halo, the tile record and g_final then see the summed |r|^2 where the plain kernel sees one
+// window's.
+template <int kColLogT, int L1C>
+__device__ __forceinline__ void cols_inv_integ(const float2* __restrict__ in, const float2* __restrict__ tw, int l1_arg, int l2,
+                                               GTile* __restrict__ rec, float* __restrict__ halo, LagBounds lb, int K) {
+    constexpr int kColT = 1 << kColLogT;
+    extern __shared__ __attribute__((aligned(16))) char gsm[];
+    float2* x = reinterpret_cast<float2*>(gsm);
+    const int l1 = L1C > 0 ? L1C : l1_arg;
+    const int L1 = 1 << l1, L2 = 1 << l2, tid = threadIdx.x, nthr = L1C > 0 ? cols_threads(L1C, kColLogT) : (int)blockDim.x;
+    const long L = (long)L1 << l2;
+    const int N = (int)(L >> 1);
+    const int tile = xcd_tile(blockIdx.x, gridDim.x), c0 = tile * kColT;
+    float2* twl = x + lp((long)L1 << kColLogT) + (long)kColT * ((1 << (l1 >> 1)) + (L1 >> (l1 >> 1)) + 1);
+    float* sv = reinterpret_cast<float*>(x + lp((long)L1 << kColLogT));
+    int* sk = reinterpret_cast<int*>(sv + 16);
+    for (int k = tid; k < (L1 >> 1); k += nthr) twl[k] = tw[k];
+    __syncthreads();
+    const int elems = L1 << kColLogT;
+    const long gs = blockIdx.y;
+    const long slot0 = (gs / lb.n_pairs) * K * lb.n_pairs + gs % lb.n_pairs;   // the group's first window, this pair
+    float acc[kIntegMaxPerThread];
+#pragma unroll
+    for (int e = 0; e < kIntegMaxPerThread; ++e) acc[e] = 0.0f;
+    for (int kw = 0; kw < K; ++kw) {
+        const float2* src = in + (slot0 + (long)kw * lb.n_pairs) * L;
+        fft_dit_inv<kColLogT>(
+            x, l1, twl, tid, nthr,
+            make_src([&](int E) -> float2 { return src[((E >> kColLogT) << l2) + c0 + (E & (kColT - 1))]; }),
+            make_dst([&](int E0, int off, float2 e) { x[TileInv::pos(E0) + TileInv::pos(off)].x = e.x * e.x + e.y * e.y; }));
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < kIntegMaxPerThread; ++e) {
+            const int E = tid + e * nthr;
+            if (E < elems) acc[e] += x[TileInv::pos(E)].x;
+        }
+        __syncthreads();   // the next window's first pass overwrites the image
+    }
+    float best = -1.0f;
+    int bk = 0x7fffffff;
+    int klo, khi;
+    lag_window_slot(lb, gs, N - 1, klo, khi);
+#pragma unroll
+    for (int e = 0; e < kIntegMaxPerThread; ++e) {
+        const int E = tid + e * nthr;
+        if (E < elems) {
+            const float v = acc[e];
+            x[TileInv::pos(E)].x = v;
+            const int m = ((E >> kColLogT) << l2) + c0 + (E & (kColT - 1));
+            const int k = full_index(m, N);
+            if ((unsigned)(k - klo) <= (unsigned)(khi - klo) && (v > best || (v == best && k < bk))) { best = v; bk = k; }   // (klo >= 0)
+        }
+    }
+    __syncthreads();
+    float* hb = halo + ((long)blockIdx.y * gridDim.x + tile) * 2L * L1;
+    for (int n1 = tid; n1 < 2 * L1; n1 += nthr) {
+        const int row = n1 & (L1 - 1), col = n1 < L1 ? 0 : kColT - 1;
+        hb[n1] = x[TileInv::pos((row << kColLogT) + col)].x;
+    }
+    block_argmax_w(best, bk, sv, sk, tid, nthr);
+    if (tid == 0) {
+        GTile t;
+        t.v = best;
+        t.k = bk;
+        t.tm = t.tp = -1.0f;
+        if (bk > 0 && bk < 2 * N - 2) {
+            const long m = circ_index(bk, N);
+            const int c = (int)(m & (L2 - 1)) - c0, row = (int)(m >> l2);
+            if (c > 0) t.tm = x[TileInv::pos((row << kColLogT) + c - 1)].x;
+            if (c < kColT - 1) t.tp = x[TileInv::pos((row << kColLogT) + c + 1)].x;
+        }
+        rec[(long)blockIdx.y * gridDim.x + tile] = t;
+    }
+}
+
 // LB: empty, or one LagBounds (the bounded instantiation: candidates outside the slot's lag window are skipped; the LDS
-// image keeps every |r|^2, so the taps and the halo are those of the unbounded kernel)
+// image keeps every |r|^2, so the taps and the halo are those of the unbounded kernel), or <LagBounds, Integrate>
 template <int kColLogT, int L1C = 0, class... LB>
 __global__ __launch_bounds__(1024) void g_cols_inv(const float2* __restrict__ in, const float2* __restrict__ tw, int l1_arg,
                                                    int l2, GTile* __restrict__ rec, float* __restrict__ halo, LB... lb_pack) {
+    if constexpr (kIntegrating<LB...>) {
+        cols_inv_integ<kColLogT, L1C>(in, tw, l1_arg, l2, rec, halo, integ_bounds(lb_pack...), integ_windows(lb_pack...));
+        return;
+    }
     constexpr bool BOUNDED = sizeof...(LB) > 0;
     constexpr int kColT = 1 << kColLogT;
     extern __shared__ __attribute__((aligned(16))) char gsm[];

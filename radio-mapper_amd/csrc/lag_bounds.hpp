@@ -22,14 +22,10 @@ struct LagBounds {
     int n_pairs;     // ... and the pairs per window
 };
 
-template <class... LB>
-__device__ __forceinline__ LagBounds lag_bounds_of(LB... lb) {
-    if constexpr (sizeof...(LB) > 0) {
-        return LagBounds(lb...);
-    } else {
-        return LagBounds{nullptr, 0, 0, 0};
-    }
-}
+// the LagBounds of a kernel's trailing pack: its first member (integrate.hpp adds a second), or none
+__device__ __forceinline__ LagBounds lag_bounds_of() { return LagBounds{nullptr, 0, 0, 0}; }
+template <class... More>
+__device__ __forceinline__ LagBounds lag_bounds_of(LagBounds lb, More...) { return lb; }
 
 // 'full' index interval of window w (global index), pair q (output index); nm1 = N - 1
 __device__ __forceinline__ void lag_window(const LagBounds& lb, long w, int q, int nm1, int& klo, int& khi) {

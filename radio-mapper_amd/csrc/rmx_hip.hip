@@ -27,6 +27,7 @@
 #include "host_plan.hpp"
 #include "lag_bounds.hpp"
 #include "xspec_weight.hpp"
+#include "integrate.hpp"
 #include "fft_r16.hpp"
 #include "kwin.hpp"
 #include "fft_r8.hpp"
@@ -301,6 +302,167 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// The integrating instantiation of k_pair_str (integrate.hpp).  grid = groups_in_chunk * n_parts; a work item is
+// (group, pair): the workgroup walks the group's K windows -- product, the three radix-16 passes, |.|^2 as in pair_body --
+// and adds each window's mag[16] into acc[16], in window order; masking, argmax, tap publication and parabola then run
+// once, on acc.  The next window's spectra (or the next pair's first window's) are requested where pair_body requests
+// the next pair's.  With the 16 sums on top of pair_body's registers the kernel does not fit 128 VGPRs (pair_body itself
+// spills there), so this instantiation is built for two waves per SIMD, one workgroup per CU, like k_pair_res, and keeps
+// TW1 in registers as that kernel does.  One more barrier per window than pair_body has per pair: the A<->B image of window w is read across
+// waves, and window w + 1 writes the exchange buffer again without the argmax's barriers in between.
+//   out arrays and lag windows are indexed [(first_group + gl) * n_pairs + item.out].
+__device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec, const float4* __restrict__ tw1_g,
+                                                const float2* __restrict__ tw2_g, const PairItem* __restrict__ items,
+                                                const int* __restrict__ part_begin, int n_parts, int n_buoys, int n_pairs,
+                                                int xcd_map, long first_group, float out_scale, int* __restrict__ lag_int,
+                                                float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K) {
+    extern __shared__ __attribute__((aligned(16))) char smem_ig[];   // (pair_body's carve)
+    float2* xl = reinterpret_cast<float2*>(smem_ig);
+    float2* tw2_lds = reinterpret_cast<float2*>(smem_ig + kLdsXchg);
+    float* red_max = reinterpret_cast<float*>(smem_ig + kLdsXchg + kLdsTw2);      // [8]
+    int* red_k = reinterpret_cast<int*>(smem_ig + kLdsXchg + kLdsTw2 + 32);       // [1]
+    float* red_tap = reinterpret_cast<float*>(smem_ig + kLdsXchg + kLdsTw2 + 48); // [3]
+
+    const int t = threadIdx.x;
+    const int p = t & 1, u = t >> 1;
+    const int lane = t & 63, wave = t >> 6;
+    int gl, part;   // (the placement of pair_body, with groups for windows)
+    {
+        const int b = blockIdx.x;
+        if (xcd_map) {
+            const int xcd = b & 7, s = b >> 3;
+            gl = (s / n_parts) * 8 + xcd;
+            part = s % n_parts;
+        } else {
+            gl = b / n_parts;
+            part = b % n_parts;
+        }
+    }
+    if (t < 256) tw2_lds[(t >> 4) * kTw2RowF2 + (t & 15)] = tw2_g[t];   // (load_tw2_to_lds)
+    float2 tw1[16];   // resident over all windows and pairs (this instantiation has the registers: two waves per SIMD)
+    load_tw1(tw1, tw1_g, t);
+    __syncthreads();
+
+    const float sgn = p ? -1.0f : 1.0f;
+    const int kbase = p ? (u - 1) : (u + kM - 1);
+    const int it_begin = part_begin[part];
+    const int it_end = part_begin[part + 1];
+    const long gbase = (long)gl * K * n_buoys;   // item of the group's first window, buoy 0 (chunk-local)
+    float4 sa[8], sb[8];   // X_i and X_j of the window about to be processed
+    PairItem pi = items[it_begin < it_end ? it_begin : 0];
+    auto request = [&](const PairItem& pr, int kw) {
+        const float4* xi = spec + (gbase + (long)kw * n_buoys + pr.i) * (8 * kThreads);
+        const float4* xj = spec + (gbase + (long)kw * n_buoys + pr.j) * (8 * kThreads);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            sa[j] = xi[j * kThreads + t];
+            sb[j] = xj[j * kThreads + t];
+        }
+    };
+    if (it_begin < it_end) request(pi, 0);
+    for (int it = it_begin; it < it_end; ++it) {
+        const int out_idx = pi.out;
+        float acc[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
+        for (int kw = 0; kw < K; ++kw) {
+            float2 v[16];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {   // R = X_j * conj(X_i), (im, re)-swapped (pair_body)
+                const float4 a = sa[j];
+                const float4 b = sb[j];
+                v[2 * j] = make_float2(b.y * a.x - b.x * a.y, b.x * a.x + b.y * a.y);
+                v[2 * j + 1] = make_float2(b.w * a.z - b.z * a.w, b.z * a.z + b.w * a.w);
+            }
+            dft16(v);                     // k2 -> n0   (role C)
+            mul_tw2(v, tw2_lds, u & 15);  // W_256^(k1*n0)
+            xchg_bc_write_c(xl, v, t);
+            wave_lds_fence();
+            xchg_bc_read_b(xl, v, t);
+            dft16(v);                     // k1 -> n1   (role B)
+            xchg_b_write(xl, v, t);
+            __syncthreads();
+            xchg_a_read(xl, v, t);
+            mul_tw1(v, tw1);              // W_M^(u*k0) [* W_L^u odd]
+            dft16(v);                     // k0 -> n2   (role A)
+            if (p) {
+#pragma unroll
+                for (int q = 1; q < 16; ++q) v[q] = cmul(v[q], w32(q));
+            }
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {   // last radix-2 stage across the lane pair, |.|^2, the running sum
+                const float rx = sgn * v[q].x + dpp_xor1(v[q].x);
+                const float ry = sgn * v[q].y + dpp_xor1(v[q].y);
+                acc[q] += rx * rx + ry * ry;
+            }
+            if (kw + 1 < K) {
+                request(pi, kw + 1);
+            } else if (it + 1 < it_end) {
+                pi = items[it + 1];
+                request(pi, 0);
+            }
+            __syncthreads();   // every wave has read the A<->B image: the next window may write the exchange buffer
+        }
+        if (p && u == 0) acc[0] = -1.0f;   // lag -M is not part of 'full'
+        int klo, khi;
+        lag_window(lb, first_group + gl, out_idx, kM - 1, klo, khi);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[q] = lag_mask(acc[q], kbase + q * 256, klo, khi);
+        float tmax = acc[0];
+#pragma unroll
+        for (int q = 1; q < 16; ++q) tmax = fmaxf(tmax, acc[q]);
+        float wmax = tmax;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, off, 64));
+        if (lane == 0) red_max[wave] = wmax;
+        if (t == 0) *red_k = 0x7fffffff;
+        __syncthreads();
+        float gmax = red_max[0];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) gmax = fmaxf(gmax, red_max[w]);
+        if (tmax == gmax) {
+            int kmin = 0x7fffffff;
+#pragma unroll
+            for (int q = 15; q >= 0; --q)
+                if (acc[q] == gmax) kmin = kbase + q * 256;
+            atomicMin(red_k, kmin);
+        }
+        __syncthreads();
+        const int kstar = *red_k;
+#pragma unroll
+        for (int d = -1; d <= 1; ++d) {   // owners of taps k*-1, k*, k*+1 publish sqrt(sum) (scipy scaling)
+            const int kk = kstar + d;
+            if (kk >= 0 && kk <= 2 * kM - 2) {
+                const int par = (kk >= kM - 1) ? 0 : 1;
+                const int n = par ? (kk + 1) : (kk - (kM - 1));
+                if (p == par && u == (n & 255)) {
+                    const int qo = n >> 8;
+                    float val = 0.0f;
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if (q == qo) val = acc[q];
+                    red_tap[d + 1] = sqrtf(val) * out_scale;
+                }
+            }
+        }
+        __syncthreads();
+        if (t == 0) {
+            const double b = (double)red_tap[1];
+            double frac = 0.0;
+            if (kstar > klo && kstar < khi) {
+                const double a = (double)red_tap[0], c = (double)red_tap[2];
+                const double den = a - 2.0 * b + c;
+                if (den != 0.0) frac = 0.5 * (a - c) / den;
+            }
+            const long o = (first_group + gl) * (long)n_pairs + out_idx;
+            lag_int[o] = kstar - (kM - 1);
+            lag_frac[o] = (float)frac;
+            peak[o] = (float)b;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Resident pair kernel (one workgroup per CU, <= 256 VGPRs).  One workgroup barrier per pair:
 //   pair n:  product -> [request X_j of pair n+1] -> DFT16 -> TW2 -> wave-local exchange -> DFT16 ->
 //            write A<->B image -> BARRIER -> [resolve pair n-1] -> read image -> TW1 -> DFT16 -> W32 ->
@@ -521,9 +683,16 @@ __global__ __launch_bounds__(kThreads, 2) void k_winp(const void* __restrict__ i
     spec, spec_j, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,      \
         lag_int, lag_frac, peak, i_wrap
 
-template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation)
-__global__ __launch_bounds__(kThreads, 4) void k_pair_str(RMX_PAIR_ARGS, LB... lb) {
-    pair_body<(sizeof...(LB) > 0)>(RMX_PAIR_PASS, lag_bounds_of(lb...));
+// LB: empty, one LagBounds (the bounded instantiation), or <LagBounds, Integrate> (the integrating one, integrate.hpp:
+// first_window is then the chunk's first GROUP; spec_j and i_wrap are not used)
+template <class... LB>
+__global__ __launch_bounds__(kThreads, kIntegrating<LB...> ? 2 : 4) void k_pair_str(RMX_PAIR_ARGS, LB... lb) {
+    if constexpr (kIntegrating<LB...>) {
+        pair_body_integ(spec, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
+                        lag_int, lag_frac, peak, integ_bounds(lb...), integ_windows(lb...));
+    } else {
+        pair_body<(sizeof...(LB) > 0)>(RMX_PAIR_PASS, lag_bounds_of(lb...));
+    }
 }
 
 
@@ -764,6 +933,10 @@ struct rmx_ctx {
     int32_t* h_band = nullptr;  size_t h_band_elems = 0;
     hipEvent_t band_ev = nullptr;
     const void* g_rows_fwd_wt_fn = nullptr;   // the weighted instantiation of g_rows_fwd_fn
+    // rmx_xcorr_batch_integrated: windows per group while an integrated call dispatches (1 otherwise); with it the bounds
+    // above are per GROUP and every chunk holds whole groups
+    int integ = 1;
+    const void* g_cols_inv_int_fn = nullptr;   // the integrating instantiation of g_cols_inv_fn (integrate.hpp)
     // cached pair plan
     std::vector<int32_t> plan_pairs;
     int plan_n_pairs = -1, plan_n_parts = 0, plan_ppb = 0;
@@ -1085,6 +1258,7 @@ static int generic_init(rmx_ctx* c) {
         const int slds = (int)(gen::lp(L) * 8 + 1024 * 8);
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_pair_small<>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_pair_small<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
+        RMX_HIP(c, hipFuncSetAttribute((const void*)(g_pair_small<LagBounds, Integrate>), hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<false>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<true>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
         RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<false, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
@@ -1133,6 +1307,8 @@ static int generic_init(rmx_ctx* c) {
             c->g_cols_inv_fn = cols_inv_fn<>(c->g_logL1, lt, thr);
             c->g_cols_inv_lb_fn = cols_inv_fn<LagBounds>(c->g_logL1, lt, thr);
             RMX_HIP(c, hipFuncSetAttribute(c->g_cols_inv_lb_fn, hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
+            c->g_cols_inv_int_fn = cols_inv_fn<LagBounds, Integrate>(c->g_logL1, lt, thr);   // (integrated calls)
+            RMX_HIP(c, hipFuncSetAttribute(c->g_cols_inv_int_fn, hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
             c->g_cols_fwd_fn[0] = cols_fwd_fn<false>(c->g_logL1, lt, thr);
             c->g_cols_fwd_fn[1] = cols_fwd_fn<true>(c->g_logL1, lt, thr);
             RMX_HIP(c, hipFuncSetAttribute(c->g_cols_inv_fn, hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
@@ -1438,7 +1614,11 @@ static int generic_pairs(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, fl
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
         RMX_TM_BEGIN(c);
-        if (c->lb.b)   // bounded call (rmx_xcorr_batch_bounded)
+        if (c->integ > 1)   // integrated call: one workgroup per (group, pair); w0 and wc are whole groups, the bounds per group
+            hipLaunchKernelGGL((g_pair_small<LagBounds, Integrate>), dim3(slots / c->integ), dim3(sthr),
+                               (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st, c->g_spec, spec_j, c->g_tw, c->g_pairs, n_pairs, B, N,
+                               logL, (long)(w0 / c->integ), out_scale, d_lag, d_frac, d_peak, c->lb, Integrate{c->integ});
+        else if (c->lb.b)   // bounded call (rmx_xcorr_batch_bounded)
             hipLaunchKernelGGL(g_pair_small<LagBounds>, dim3(slots), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st,
                                c->g_spec, spec_j, c->g_tw, c->g_pairs, n_pairs, B, N, logL, (long)w0, out_scale, d_lag, d_frac,
                                d_peak, c->lb);
@@ -1502,6 +1682,30 @@ static int generic_pairs(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, fl
         RMX_TM_BEGIN(c);
         RMX_HIP(c, hipLaunchKernel(c->g_rows_inv_fn, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), args, rlds, st));
         RMX_TM_END(c, kTkRowsInv);
+    }
+    if (c->integ > 1) {
+        // integrated call: the column pass sums the |r|^2 of a group's K product slots tile by tile and leaves one tile
+        // record and halo per (group, pair) slot; g_final then reduces those slots as it reduces a window's (the bounds are
+        // per group: slot -> group w0 / K + slot / P)
+        const int gslots = slots / c->integ;
+        const float2 *a_in = c->g_prod, *a_tw = c->g_tw1;
+        int a_l1 = l1, a_l2 = l2;
+        GTile* a_rec = c->g_rec;
+        float* a_halo = c->g_halo;
+        LagBounds a_lb = c->lb;
+        a_lb.w0 = w0 / c->integ;
+        a_lb.n_pairs = n_pairs;
+        Integrate a_ig{c->integ};
+        void* args[] = {&a_in, &a_tw, &a_l1, &a_l2, &a_rec, &a_halo, &a_lb, &a_ig};
+        RMX_TM_BEGIN(c);
+        RMX_HIP(c, hipLaunchKernel(c->g_cols_inv_int_fn, dim3(ntiles, gslots), dim3(cthr), args, clds, st));
+        RMX_TM_END(c, kTkColsInv);
+        RMX_TM_BEGIN(c);
+        hipLaunchKernelGGL(g_final<LagBounds>, dim3(gslots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, gslots,
+                           (long)(w0 / c->integ) * n_pairs, out_scale, d_lag, d_frac, d_peak, a_lb);
+        RMX_HIP(c, hipGetLastError());
+        RMX_TM_END(c, kTkFinal);
+        return RMX_OK;
     }
     {
         const float2 *a_in = c->g_prod, *a_tw = c->g_tw1;
@@ -1605,7 +1809,8 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
     // Weighted calls (rmx_xcorr_batch_weighted) weight the spectra where the per-transform forward kernels store them:
     // g_fwd_small up to L = small_maxl, g_cols_fwd + the forward g_rows above.  The whole-window kernels (g_win_*,
     // k_win8kl), k16_fwd and g_rows_fused keep their spectra to themselves and are never taken.
-    const bool weighted = c->wt.band != nullptr;
+    // Integrated calls (rmx_xcorr_batch_integrated) sum over windows inside the per-transform pair kernels: the same routes.
+    const bool weighted = c->wt.band != nullptr || c->integ > 1;
     if (!weighted && c->g_k16 && c->g_logL == 15 && n_pairs <= k16::kMaxPairs16 &&
         (c->g_k16 == 2 || (!c->g_wscr_always &&
                            n_windows >= (int)c->knobs.get_or("k16_min_windows", (100 + c->n_buoys + n_pairs - 1) / (c->n_buoys + n_pairs))))) {
@@ -1742,8 +1947,17 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
         RMX_TM_END(c, kTkWindow);
         return RMX_OK;
     }
-    for (int w0 = 0; w0 < n_windows; w0 += c->g_chunk) {
-        const int wc = n_windows - w0 < c->g_chunk ? n_windows - w0 : c->g_chunk;
+    // (integrated call: a chunk holds whole groups -- never a silent split of a group)
+    const int chunk = c->g_chunk / c->integ * c->integ;
+    if (chunk == 0)
+        return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
+                    c->integ, c->g_chunk);
+    if (c->integ > 1 && (1L << c->g_logL) > kGenSmallMaxL &&
+        ((1L << c->g_logL1) << host_col_log_t(c, c->g_logL1)) > (long)kIntegMaxPerThread * gen_cols_threads(c, c->g_logL1))
+        return fail(c, RMX_E_UNSUPPORTED, "integrated call: a column tile of %ld elements on %d threads is more than %d per thread",
+                    (1L << c->g_logL1) << host_col_log_t(c, c->g_logL1), gen_cols_threads(c, c->g_logL1), kIntegMaxPerThread);
+    for (int w0 = 0; w0 < n_windows; w0 += chunk) {
+        const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
         // the fused row kernel when its (window, row block) units fill the chip at least twice: below that (cfg1's single
         // window: 128 workgroups) its long serial chain per unit loses to the two-kernel passes' wider grids (57 vs 47 us)
         const long fused_blocks = c->g_fused ? (long)wc * (1L << c->g_logL1) / (gen::kGThreads / ((1 << c->g_logL2) >> 4)) : 0;
@@ -2063,6 +2277,19 @@ static int pairs4096(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, float*
     wc *= n_bins;
     const int xcd_map = (wc % 8 == 0) ? 1 : 0;
     const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
+    if (c->integ > 1) {
+        // integrated call: always the streaming kernel's integrating instantiation, one work item per (group, pair);
+        // w0 and wc are whole groups, the bounds per group
+        const int gc = wc / c->integ;
+        RMX_TM_BEGIN(c);
+        hipLaunchKernelGGL((k_pair_str<LagBounds, Integrate>), dim3(gc * n_parts), dim3(kThreads), kLdsBytes, c->stream,
+                           (const float4*)c->d_spec, spec_j, c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys,
+                           n_pairs, (gc % 8 == 0) ? 1 : 0, (long)(w0 / c->integ), out_scale, d_lag, d_frac, d_peak, 0, c->lb,
+                           Integrate{c->integ});
+        RMX_HIP(c, hipGetLastError());
+        RMX_TM_END(c, kTkPair4096);
+        return RMX_OK;
+    }
     RMX_TM_BEGIN(c);
     if (c->lb.b && c->resident)   // bounded call (rmx_xcorr_batch_bounded)
         hipLaunchKernelGGL(k_pair_res<LagBounds>, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream,
@@ -2174,8 +2401,9 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     }
     // a weighted call (rmx_xcorr_batch_weighted) weights the spectra where k_fwd stores them: the per-transform kernels
     // at every batch size, never k_win (whose spectra stay inside the workgroup)
-    if (c->wt.band && !c->generic) {
-        (void)split_cost4096(c, n_windows, n_pairs, &ppb_small);
+    // (an integrated call sums over windows inside k_pair_str: the same kernels, with one work item per (group, pair))
+    if ((c->wt.band || c->integ > 1) && !c->generic) {
+        (void)split_cost4096(c, n_windows / c->integ, n_pairs, &ppb_small);
         small = true;
     }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
@@ -2253,7 +2481,7 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     int* d_lag = lag_int;
     float* d_frac = lag_frac;
     float* d_peak = peak;
-    const size_t out_elems = (size_t)n_windows * n_pairs;
+    const size_t out_elems = (size_t)(n_windows / c->integ) * n_pairs;   // (integrated call: one row per group)
     if (!out_dev) {
         {
             const int rc_out = ensure_out(c, out_elems);
@@ -2277,8 +2505,13 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
         if (rc != RMX_OK) return rc;
     }
     int n_sub = 0;
-    for (int w0 = 0; w0 < n_windows; w0 += c->chunk_windows) {
-        const int wc = (n_windows - w0 < c->chunk_windows) ? n_windows - w0 : c->chunk_windows;
+    // (integrated call: a chunk holds whole groups -- never a silent split of a group)
+    const int chunk_windows = c->chunk_windows / c->integ * c->integ;
+    if (chunk_windows == 0)
+        return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
+                    c->integ, c->chunk_windows);
+    for (int w0 = 0; w0 < n_windows; w0 += chunk_windows) {
+        const int wc = (n_windows - w0 < chunk_windows) ? n_windows - w0 : chunk_windows;
         if (fused_now) {
             // this chunk's partial round (see above): only behind at least one full round of this call, and only when the
             // model says so for ITS size -- with the default chunk (a multiple of the CU count) that is the batch's last
@@ -2382,18 +2615,20 @@ int rmx_xcorr_batch_bounded(rmx_ctx* c, const void* iq, int n_windows, const int
     if (n_pairs < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
     if (n_windows == 0 || n_pairs == 0) return RMX_OK;
     const int nm1 = c->n_samples - 1;
-    const long rows = bounds_per_window ? (long)n_windows * n_pairs : (long)n_pairs;
+    // (inside an integrated call the intervals are per GROUP of c->integ windows, and the integrating kernels always run:
+    // they carry the bounds whatever their values)
+    const long rows = bounds_per_window ? (long)(n_windows / c->integ) * n_pairs : (long)n_pairs;
     bool all_full = true;
     for (long r = 0; r < rows; ++r) {
         const int lo = lag_bounds[2 * r], hi = lag_bounds[2 * r + 1];
         if (lo < -nm1 || hi > nm1 || lo > hi)
-            return fail(c, RMX_E_INVAL, "lag_bounds of window %ld, pair %ld: [%d, %d] is not an interval inside [%d, %d]",
-                        bounds_per_window ? r / n_pairs : -1L, r % n_pairs, lo, hi, -nm1, nm1);
+            return fail(c, RMX_E_INVAL, "lag_bounds of %s %ld, pair %ld: [%d, %d] is not an interval inside [%d, %d]",
+                        c->integ > 1 ? "group" : "window", bounds_per_window ? r / n_pairs : -1L, r % n_pairs, lo, hi, -nm1, nm1);
         all_full = all_full && lo == -nm1 && hi == nm1;
     }
     // every interval the full one: that is rmx_xcorr_batch, whatever route it takes (the whole-window generic kernels,
     // which a bounded call avoids, included)
-    if (all_full) return rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+    if (all_full && c->integ == 1) return rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
     RMX_HIP(c, hipSetDevice(c->device));
     const size_t elems = (size_t)(2 * rows);
     if (!c->lb_ev) RMX_HIP(c, hipEventCreateWithFlags(&c->lb_ev, hipEventDisableTiming));
@@ -2498,6 +2733,43 @@ int rmx_xcorr_batch_weighted(rmx_ctx* c, const void* iq, int n_windows, const in
                                                         lag_int, lag_frac, peak, flags)
                               : rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
     c->wt = XWeight{nullptr, 0, 0, 0, 0, 0.0f};
+    return rc;
+}
+
+// rmx_xcorr_batch_weighted with one peak search per group of `integrate` consecutive windows, on the lag-by-lag sum of the
+// windows' |c|^2 (integrate.hpp).  The arguments are checked here; the call then dispatches through the weighted and the
+// bounded entries with c->integ set: the bands stay per window, the bounds and the outputs are per group, every chunk
+// holds whole groups and the pair / peak kernels of the per-transform routes run their integrating instantiations, which
+// always carry bounds (an unbounded call passes the full interval).
+int rmx_xcorr_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
+                               const double* band_cps, int band_per_window, unsigned weighting,
+                               const int32_t* lag_bounds, int bounds_per_group,
+                               int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    if (!c) return RMX_E_INVAL;
+    if (integrate < 1) return fail(c, RMX_E_INVAL, "integrate = %d: at least one window per group", integrate);
+    if (n_windows <= 0 || n_windows % integrate != 0)
+        return fail(c, RMX_E_INVAL, "n_windows = %d is not a positive multiple of integrate = %d", n_windows, integrate);
+    if (integrate == 1)
+        return rmx_xcorr_batch_weighted(c, iq, n_windows, pairs, n_pairs, band_cps, band_per_window, weighting, lag_bounds,
+                                        bounds_per_group, lag_int, lag_frac, peak, flags);
+    std::vector<int32_t> full;
+    if (!lag_bounds) {
+        int np = n_pairs;
+        if (!pairs) np = c->n_buoys * (c->n_buoys - 1) / 2;
+        if (np < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
+        full.resize((size_t)(2 * np));
+        for (int q = 0; q < np; ++q) {
+            full[2 * q] = -(c->n_samples - 1);
+            full[2 * q + 1] = c->n_samples - 1;
+        }
+        if (np == 0) full.resize(2);   // (never read: a call without pairs returns before the bounds)
+        lag_bounds = full.data();
+        bounds_per_group = 0;
+    }
+    c->integ = integrate;
+    const int rc = rmx_xcorr_batch_weighted(c, iq, n_windows, pairs, n_pairs, band_cps, band_per_window, weighting, lag_bounds,
+                                            bounds_per_group, lag_int, lag_frac, peak, flags);
+    c->integ = 1;
     return rc;
 }
 

@@ -21,7 +21,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .shard import window_shard
-from .xcorr import check_band, check_lag_bounds
+from .xcorr import check_band, check_integrate, check_lag_bounds
 
 
 class MultiXcorrEngine:
@@ -94,9 +94,12 @@ class MultiXcorrEngine:
         """(start, count) of every device's block, in device order (empty blocks included)."""
         return [window_shard(n_windows, r, len(self.devices)) for r in range(len(self.devices))]
 
-    def _run(self, n_windows: int, call: Callable, n_out: int, dtypes, n_pairs: int):
+    def _run(self, n_windows: int, call: Callable, n_out: int, dtypes, n_pairs: int, n_rows: Optional[int] = None):
+        """n_rows: the items that are sharded and the rows of the results (the groups of an integrated call); default: the
+        windows"""
         if n_windows > self.max_windows:
             raise ValueError(f"n_windows {n_windows} > max_windows {self.max_windows}")
+        n_windows = n_windows if n_rows is None else n_rows
         outs = [np.zeros((n_windows, n_pairs), dt) for dt in dtypes]
         with self._lock:
             futs = []
@@ -117,14 +120,19 @@ class MultiXcorrEngine:
 
     # -- the hot path --------------------------------------------------------------------------------
     def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
-                  whiten: bool = False):
+                  whiten: bool = False, integrate: int = 1):
         """iq: complex64 [W][B][N] or uint8 [W][B][2N] -> (lag_int [W][P], lag_frac [W][P], peak [W][P]).
         lag_bounds: None, [P][2] (every block gets it whole) or [W][P][2] (each block gets its own windows' rows).
-        band: None, [2] (every block gets it whole) or [W][2] (each block its own windows' rows); whiten: PHAT."""
+        band: None, [2] (every block gets it whole) or [W][2] (each block its own windows' rows); whiten: PHAT.
+        integrate: K windows per group (XcorrEngine.correlate): whole groups are sharded over the devices, the results and
+        per-group lag_bounds are [W // K][.]; a block larger than its engine holds runs as several calls of whole groups."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
+        K = check_integrate(integrate, iq.shape[0])
+        if K > 1:
+            return self._correlate_integrated(iq, pairs, lag_bounds, band, whiten, K, P)
         lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
 
         bd, band_pw = check_band(band, iq.shape[0])
@@ -140,6 +148,28 @@ class MultiXcorrEngine:
                 return eng.correlate(iq[s:s + c], pairs, block_bounds(s, c))
             return eng.correlate(iq[s:s + c], pairs)
         return self._run(iq.shape[0], block_call, 3, (np.int32, np.float32, np.float32), P)
+
+    def _correlate_integrated(self, iq, pairs, lag_bounds, band, whiten, K, P):
+        W = iq.shape[0]
+        G = W // K
+        lb, per_group = check_lag_bounds(lag_bounds, G, P)
+        bd, band_pw = check_band(band, W)
+
+        def block_call(eng, gs, gc):
+            # the engines are sized for an even split of the WINDOWS; a block of whole groups may be a little larger
+            step = getattr(eng, "max_windows", gc * K) // K
+            if step < 1:
+                raise ValueError(f"integrate = {K} windows per group is more than one device's engine holds "
+                                 f"({eng.max_windows} windows)")
+            parts = []
+            for g0 in range(gs, gs + gc, step):
+                g1 = min(g0 + step, gs + gc)
+                parts.append(eng.correlate(iq[g0 * K:g1 * K], pairs,
+                                           None if lb is None else (lb[g0:g1] if per_group else lb),
+                                           band=None if bd is None else (bd[g0 * K:g1 * K] if band_pw else bd),
+                                           whiten=whiten, integrate=K))
+            return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
+        return self._run(W, block_call, 3, (np.int32, np.float32, np.float32), P, n_rows=G)
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None):
         """Cross-ambiguity search -> (doppler_idx, lag_int, lag_frac, peak), each [W][P]."""

@@ -150,7 +150,7 @@ class TDoACalculator:
     DEFAULT_BANDWIDTH_HZ = 10e3   # band_limit: a detection without bandwidth_hz (the reference's default, central_processor.py:52)
 
     def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, min_cut_samples: int = 128,
-                 bound_lags: bool = False, band_limit: bool = False, whiten: bool = False):
+                 bound_lags: bool = False, band_limit: bool = False, whiten: bool = False, integrate: int = 1):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
@@ -161,7 +161,13 @@ class TDoACalculator:
         band_limit: correlate each group over its emitter's band only (band() below: the detections' frequencies and
         bandwidths around the capture's centre frequency), so that two transmitters heard in one capture each get their
         own lags.  whiten: PHAT weighting of every group with IQ (no strong spectral line -- the receivers' DC offset, LO
-        leakage -- dominates the peak).  Both plain attributes, off by default."""
+        leakage -- dominates the peak).  Both plain attributes, off by default.
+        integrate: K > 1 cuts every group's [B][N] windows into K consecutive segments of N // K samples and measures ONE
+        lag per pair on the sum of the segments' squared correlation magnitudes (noncoherent integration,
+        rmx_xcorr_batch_integrated): receivers with free-running oscillators stay coherent over a short segment only.
+        The segments of one capture share its start tag, so they share the lag; bound_lags and band_limit derive their
+        values for N // K.  A group whose segments cannot be formed (segment_length below) yields no measurements.  A
+        plain attribute, 1 (off) by default."""
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
         self.devices = devices
@@ -169,6 +175,7 @@ class TDoACalculator:
         self.bound_lags = bool(bound_lags)
         self.band_limit = bool(band_limit)
         self.whiten = bool(whiten)
+        self.integrate = int(integrate)
         self._engines: Dict[Tuple[int, int], Any] = {}   # insertion order = recency
         self._tconf: Dict[Tuple[int, int], float] = {}
 
@@ -208,19 +215,26 @@ class TDoACalculator:
             eng.close()
         self._engines.clear()
 
-    def measure_lags(self, iq, pairs=None, lag_bounds=None, band=None, whiten=False):
+    def measure_lags(self, iq, pairs=None, lag_bounds=None, band=None, whiten=False, integrate=1):
         """Batched hot path.  iq: complex64 [W][B][N] (or uint8 [W][B][2N]) ->
         (lag_int [W][P], lag_frac [W][P], peak [W][P]); lag = delay(j) - delay(i) in samples.
         A leading channel axis is a batch axis: [C][W][B][N] -> three [C][W][P] arrays (channels and
         windows are independent units, tdoa_processor.py:363).  lag_bounds: None, or int [P][2] / [W][P][2] (with a
         channel axis: [C][W][P][2]) = the lag window [lo, hi] each pair's peak is searched in.  band: None, or float [2] /
         [W][2] (with a channel axis: [C][W][2]) = the band [lo, hi] in cycles per sample kept of the cross-spectrum;
-        whiten: PHAT weighting (rmx_xcorr_batch_weighted)."""
+        whiten: PHAT weighting (rmx_xcorr_batch_weighted).  integrate: K >= 1 consecutive windows per group, one lag
+        per pair and group (rmx_xcorr_batch_integrated): W must be a multiple of K, the results and per-window lag_bounds
+        have W // K rows where they have W otherwise; band stays per window."""
+        from .xcorr import check_integrate
         iq = np.asarray(iq)
         lead = None
         if iq.ndim == 4:
             lead = iq.shape[:2]
             iq = iq.reshape((lead[0] * lead[1],) + iq.shape[2:])
+            integrate = check_integrate(integrate, lead[1])
+            lead = (lead[0], lead[1] // integrate)
+        elif iq.ndim == 3:
+            integrate = check_integrate(integrate, iq.shape[0])
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N] or [C][W][B][N], got shape {iq.shape}")
         n = iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2]
@@ -230,13 +244,14 @@ class TDoACalculator:
             lb = np.asarray(lag_bounds)
             if lead is not None and lb.ndim == 4:
                 lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
-        if band is not None or whiten:
+        if band is not None or whiten or integrate > 1:
             bd = None
             if band is not None:
                 bd = np.asarray(band)
                 if lead is not None and bd.ndim == 3:
-                    bd = bd.reshape((lead[0] * lead[1],) + bd.shape[2:])
-            out = eng.correlate(iq, pairs, lag_bounds=lb, band=bd, whiten=bool(whiten))
+                    bd = bd.reshape((-1,) + bd.shape[2:])
+            kw = {"integrate": integrate} if integrate > 1 else {}
+            out = eng.correlate(iq, pairs, lag_bounds=lb, band=bd, whiten=bool(whiten), **kw)
         elif lb is None:
             out = eng.correlate(iq, pairs)
         else:
@@ -374,6 +389,20 @@ class TDoACalculator:
             return None, f"the group's band [{lo:.6f}, {hi:.6f}] cycles per sample keeps no bin of a {L}-point transform"
         return np.array([lo, hi], np.float64), None
 
+    def segment_length(self, n: int):
+        """integrate: the segment length of windows of n samples, as (n // K, None), or (None, reason) when the segments
+        cannot be formed: K is not a power of two, does not divide n, or leaves fewer than max(min_cut_samples, 16)
+        samples (a segment is a cut of the window, and the engine's shortest window is 16)."""
+        k = self.integrate
+        if k < 1 or k & (k - 1):
+            return None, f"integrate = {k} is not a power of two"
+        if n % k:
+            return None, f"integrate = {k} does not divide the window length {n}"
+        if n // k < max(self.min_cut_samples, 16):
+            return None, (f"integrate = {k} leaves segments of {n // k} samples out of {n}, below "
+                          f"{max(self.min_cut_samples, 16)}")
+        return n // k, None
+
     def _measure_groups(self, stacked: np.ndarray, lag_bounds=None, band=None):
         """[G][B][N] -> lag [G][P] float64, or None after logging: the reference's seam never raises
         (tdoa_processor.py:151-153) and there is no fallback to time tags once IQ was supplied.  lag_bounds: None, or
@@ -381,6 +410,15 @@ class TDoACalculator:
         kw = {}
         if lag_bounds is not None:
             kw["lag_bounds"] = lag_bounds
+        if self.integrate > 1:
+            # [G][B][N] -> [G K][B][N // K]: window g K + s is segment s of group g (the callers checked segment_length and
+            # derived lag_bounds and band for N // K); one lag per pair and group comes back, as without integration
+            k = self.integrate
+            g, b, nn = stacked.shape
+            stacked = np.ascontiguousarray(stacked.reshape(g, b, k, nn // k).transpose(0, 2, 1, 3)).reshape(g * k, b, nn // k)
+            if band is not None:
+                band = np.repeat(np.asarray(band), k, axis=0)
+            kw["integrate"] = k
         if band is not None:
             kw["band"] = band
         if self.whiten:
@@ -434,12 +472,18 @@ class TDoACalculator:
             if key:
                 lb = None
                 per = 2 if stacked.dtype == np.uint8 else 1
+                n_samp = stacked.shape[-1] // per
+                if self.integrate != 1:   # the engine sees segments of n_samp // K samples
+                    n_samp, why = self.segment_length(n_samp)
+                    if why:
+                        self.logger.error(f"Cannot integrate the group: {why}; no TDoA measurements for it")
+                        return out
                 if self.bound_lags:
-                    lb, empty = self.lag_bounds(detections, buoy_positions, stacked.shape[-1] // per, key[3])
+                    lb, empty = self.lag_bounds(detections, buoy_positions, n_samp, key[3])
                     lb = lb[None]
                 band = None
                 if self.band_limit:
-                    band, why = self.band(detections, stacked.shape[-1] // per, key[3])
+                    band, why = self.band(detections, n_samp, key[3])
                     if why:
                         self.logger.error(f"Cannot band limit the group: {why}; no TDoA measurements for it")
                         return out
@@ -565,10 +609,10 @@ class HyperbolicPositioning:
 # orchestrator (tdoa_processor.py:330-465)
 # --------------------------------------------------------------------------------------------------
 class TDoAProcessor:
-    def __init__(self, band_limit: bool = False, whiten: bool = False):
-        """band_limit, whiten: the TDoACalculator settings of the same names (off by default)."""
+    def __init__(self, band_limit: bool = False, whiten: bool = False, integrate: int = 1):
+        """band_limit, whiten, integrate: the TDoACalculator settings of the same names (off by default)."""
         self.logger = logging.getLogger(__name__ + ".TDoAProcessor")
-        self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten)
+        self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten, integrate=integrate)
         self.hyperbolic_positioner = HyperbolicPositioning()
         self.buoy_positions: Dict[str, BuoyPosition] = {}
         self.correlation_window_s = 10.0
@@ -622,6 +666,13 @@ class TDoAProcessor:
         calc = self.tdoa_calculator
         for key, members in batches.items():
             n_samp = work[members[0]][3].shape[-1] // (2 if work[members[0]][3].dtype == np.uint8 else 1)
+            if calc.integrate != 1:   # the engine sees segments of n_samp // K samples; a batch shares one window length
+                n_samp, why = calc.segment_length(n_samp)
+                if why:
+                    for n in members:
+                        calc.logger.error(f"Cannot integrate the group at {work[n][0]} MHz: {why}; no TDoA measurements for it")
+                        work[n][4] = None
+                    continue
             band = None
             if calc.band_limit:   # one band per group: [G][2]; a group that cannot be band limited gets no measurements
                 bands = {}

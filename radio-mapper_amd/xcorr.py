@@ -75,6 +75,8 @@ def load_library():
     lib.rmx_xcorr_batch_bounded.restype = ci
     lib.rmx_xcorr_batch_weighted.argtypes = [vp, vp, ci, vp, ci, vp, ci, cu, vp, ci, vp, vp, vp, cu]
     lib.rmx_xcorr_batch_weighted.restype = ci
+    lib.rmx_xcorr_batch_integrated.argtypes = [vp, vp, ci, vp, ci, ci, vp, ci, cu, vp, ci, vp, vp, vp, cu]
+    lib.rmx_xcorr_batch_integrated.restype = ci
     lib.rmx_caf_batch.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, cu]
     lib.rmx_caf_batch.restype = ci
     lib.rmx_solve_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, ci, ci, vp, vp, vp, cu]
@@ -142,8 +144,21 @@ def check_band(band, n_windows: int):
     return a, per_window
 
 
+def check_integrate(integrate, n_windows: int) -> int:
+    """integrate as correlate() takes it -> K, the windows per group (noncoherent integration, rmx_xcorr_batch_integrated).
+    An integer >= 1 that divides n_windows; raises ValueError before any call into the library."""
+    if isinstance(integrate, bool) or not isinstance(integrate, (int, np.integer)):
+        raise ValueError(f"integrate must be an integer, got {integrate!r}")
+    k = int(integrate)
+    if k < 1:
+        raise ValueError(f"integrate must be >= 1, got {k}")
+    if n_windows % k != 0:
+        raise ValueError(f"the number of windows, {n_windows}, is not a multiple of integrate = {k}")
+    return k
+
+
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_integrated", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -288,16 +303,20 @@ class XcorrEngine:
 
     # -- the hot path ----------------------------------------------------------------------------
     def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
-                  whiten: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  whiten: bool = False, integrate: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Host arrays in, host arrays out.  iq: complex64 [W][B][N] (or uint8 [W][B][2N] raw
         rtl_sdr I,Q).  Returns (lag_int int32 [W][P], lag_frac float32 [W][P], peak float32 [W][P]);
         lag = lag_int + lag_frac = delay(j) - delay(i) in samples.
         lag_bounds: None (every lag of 'full'), or int [P][2] / [W][P][2] = [lo, hi] per pair (per window): the peak
         is searched over lags lo..hi only (rmx_xcorr_batch_bounded).
         band: None (every bin), or float [2] / [W][2] = [lo, hi] in cycles per sample (f / fs) kept of the
-        cross-spectrum; whiten: PHAT, every bin at unit magnitude (rmx_xcorr_batch_weighted)."""
+        cross-spectrum; whiten: PHAT, every bin at unit magnitude (rmx_xcorr_batch_weighted).
+        integrate: K >= 1; every K consecutive windows form a group with ONE peak search on the sum of the windows'
+        squared magnitudes (rmx_xcorr_batch_integrated).  W must be a multiple of K; the results are [W // K][P],
+        lag_bounds [P][2] or [W // K][P][2]; band stays per window."""
         iq, flags = self._check_iq(iq)
         W = iq.shape[0]
+        K = check_integrate(integrate, W)
         if pairs is not None:
             pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
             P = pairs.shape[0]
@@ -305,14 +324,22 @@ class XcorrEngine:
         else:
             P = self.n_buoys * (self.n_buoys - 1) // 2
             pp = None
-        lb, per_window = check_lag_bounds(lag_bounds, W, P)
+        lb, per_window = check_lag_bounds(lag_bounds, W // K, P)
         bd, band_pw = check_band(band, W)
-        lag_int = np.zeros((W, P), np.int32)
-        lag_frac = np.zeros((W, P), np.float32)
-        peak = np.zeros((W, P), np.float32)
+        lag_int = np.zeros((W // K, P), np.int32)
+        lag_frac = np.zeros((W // K, P), np.float32)
+        peak = np.zeros((W // K, P), np.float32)
         if W == 0 or P == 0:
             return lag_int, lag_frac, peak
-        if bd is not None or whiten:
+        if K > 1:
+            self._check(self._lib.rmx_xcorr_batch_integrated(
+                self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P, K,
+                None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
+                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
+                None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window),
+                lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
+                peak.ctypes.data_as(C.c_void_p), flags))
+        elif bd is not None or whiten:
             self._check(self._lib.rmx_xcorr_batch_weighted(
                 self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P,
                 None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
@@ -442,9 +469,11 @@ class XcorrEngine:
 
     def correlate_device(self, iq_ptr: int, n_windows: int, lag_int_ptr: int, lag_frac_ptr: int,
                          peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
-                         band=None, whiten: bool = False):
+                         band=None, whiten: bool = False, integrate: int = 1):
         """Device pointers in and out (inputs already resident in HBM); asynchronous on the ctx
-        stream.  lag_bounds, band, whiten: as for correlate() (host arrays; the library keeps its own copies)."""
+        stream.  lag_bounds, band, whiten, integrate: as for correlate() (host arrays; the library keeps its own copies;
+        with integrate = K the three outputs are [n_windows // K][P])."""
+        K = check_integrate(integrate, n_windows)
         if pairs is not None:
             pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
             P = pairs.shape[0]
@@ -453,9 +482,15 @@ class XcorrEngine:
             P = self.n_buoys * (self.n_buoys - 1) // 2
             pp = None
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
-        lb, per_window = check_lag_bounds(lag_bounds, n_windows, P)
+        lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
         bd, band_pw = check_band(band, n_windows)
-        if bd is not None or whiten:
+        if K > 1:
+            self._check(self._lib.rmx_xcorr_batch_integrated(
+                self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P, K, None if bd is None else bd.ctypes.data_as(C.c_void_p),
+                int(band_pw), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
+                None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window),
+                C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags))
+        elif bd is not None or whiten:
             self._check(self._lib.rmx_xcorr_batch_weighted(
                 self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P, None if bd is None else bd.ctypes.data_as(C.c_void_p),
                 int(band_pw), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
