@@ -118,6 +118,29 @@ inline int check_create_args(int n_buoys, int n_samples, int max_windows, std::s
     return 0;
 }
 
+// one [lo, hi] row of a lag_bounds array (rmx_xcorr_batch_bounded): an interval inside [-(N-1), N-1]?  *full: all of it
+inline bool lag_interval_ok(int lo, int hi, int n_samples, bool* full) {
+    const int nm1 = n_samples - 1;
+    if (lo < -nm1 || hi > nm1 || lo > hi) return false;
+    *full = lo == -nm1 && hi == nm1;
+    return true;
+}
+
+// one band [lo, hi] in cycles per sample (rmx_xcorr_batch_weighted) -> the signed bins s in [-N, N-1] of the 2N-point
+// transform with lo <= s / 2N <= hi (exact: 2N is a power of two); hi = 0.5 is bin N, which -N stands for: clamped to N-1
+enum BandCheck { kBandOk = 0, kBandNoInterval = 1, kBandNoBin = 2 };   // not an interval inside [-0.5, 0.5] / keeps no bin
+inline BandCheck band_to_bins(double lo, double hi, int n_samples, int32_t* s_lo, int32_t* s_hi) {
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo < -0.5 || hi > 0.5 || lo > hi) return kBandNoInterval;
+    const long N = n_samples, L = 2L * N;
+    const long a = (long)std::ceil(lo * (double)L);
+    long b = (long)std::floor(hi * (double)L);
+    if (b > N - 1) b = N - 1;
+    if (a > b) return kBandNoBin;
+    *s_lo = (int32_t)a;
+    *s_hi = (int32_t)b;
+    return kBandOk;
+}
+
 // ---- the pair plan ------------------------------------------------------------------------------------------------
 struct PairPlan {
     std::vector<int32_t> pairs;     // [P][2]

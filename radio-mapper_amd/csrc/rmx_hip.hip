@@ -832,6 +832,32 @@ __global__ __launch_bounds__(64) void k_solve(const double* __restrict__ buoy_xy
 // ================================================================================================
 static thread_local std::string g_create_error;
 
+// What ONE correlation call asks of the launch code beyond the plain call: built by the entry (xcorr_request), handed
+// down by const reference to every function that launches a kernel, never stored.  The default is the plain call;
+// rmx_caf_batch passes exactly that.
+struct XcorrCall {
+    LagBounds lb{nullptr, 0, 0, 0};          // lag intervals on the device (rmx_xcorr_batch_bounded), or none
+    XWeight wt{nullptr, 0, 0, 0, 0, 0.0f};   // bands as signed bins on the device + weighting (rmx_xcorr_batch_weighted)
+    int integ = 1;                           // windows per group (rmx_xcorr_batch_integrated): the bounds and the outputs
+                                             // are then per GROUP, the bands stay per window, a chunk holds whole groups
+    bool bounded() const { return lb.b != nullptr; }         // the bounded instantiations of the peak-searching kernels
+    bool integrated() const { return integ > 1; }            // the integrating instantiations of the pair kernels
+    bool weighted() const { return wt.band != nullptr || integ > 1; }   // only the per-transform routes can serve it
+};
+
+// a small host array that kernels read: staged through pinned memory into a ctx-owned device buffer (stage_to_device)
+struct DevStage {
+    int32_t* h = nullptr;  size_t h_elems = 0;
+    int* d = nullptr;      size_t d_elems = 0;
+    hipEvent_t ev = nullptr;   // the last copy out of h: the next call waits for it before it rewrites h
+};
+
+// U8 as a compile-time constant: f(std::true_type) or f(std::false_type)
+template <class F>
+static void with_u8(bool u8, F&& f) {
+    if (u8) f(std::true_type{}); else f(std::false_type{});
+}
+
 }  // namespace rmx
 
 struct rmx_ctx {
@@ -922,20 +948,10 @@ struct rmx_ctx {
     int* caf_lag = nullptr;  float* caf_frac = nullptr;  float* caf_peak = nullptr;  int* caf_dop = nullptr;
     size_t caf_out_elems = 0;
     std::vector<double> caf_grid;
-    // rmx_xcorr_batch_bounded: the caller's lag windows, staged in pinned memory and copied to a ctx-owned device buffer
-    rmx::LagBounds lb{nullptr, 0, 0, 0};   // lb.b != nullptr while a bounded call dispatches: the bounded kernels run
-    int* d_lb = nullptr;  size_t d_lb_elems = 0;
-    int32_t* h_lb = nullptr;  size_t h_lb_elems = 0;
-    hipEvent_t lb_ev = nullptr;   // the last copy out of h_lb: the next bounded call waits for it before it rewrites h_lb
-    // rmx_xcorr_batch_weighted: the bands as signed bins, staged the same way
-    rmx::XWeight wt{nullptr, 0, 0, 0, 0, 0.0f};   // wt.band != nullptr while a weighted call dispatches
-    int* d_band = nullptr;  size_t d_band_elems = 0;
-    int32_t* h_band = nullptr;  size_t h_band_elems = 0;
-    hipEvent_t band_ev = nullptr;
+    // the caller's lag windows (rmx_xcorr_batch_bounded) and its bands as signed bins (rmx_xcorr_batch_weighted): the
+    // device copies that a call's XcorrCall points into
+    rmx::DevStage lb_stage, band_stage;
     const void* g_rows_fwd_wt_fn = nullptr;   // the weighted instantiation of g_rows_fwd_fn
-    // rmx_xcorr_batch_integrated: windows per group while an integrated call dispatches (1 otherwise); with it the bounds
-    // above are per GROUP and every chunk holds whole groups
-    int integ = 1;
     const void* g_cols_inv_int_fn = nullptr;   // the integrating instantiation of g_cols_inv_fn (integrate.hpp)
     // cached pair plan
     std::vector<int32_t> plan_pairs;
@@ -1518,7 +1534,7 @@ static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool n
 
 // forward spectra of windows [w0, w0 + wc) of d_iq into g_spec (rot == nullptr) or, de-rotated by the phasor
 // table rot[N], into g_spec_r (rmx_caf_batch)
-static int generic_forward(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8, const float2* rot,
+static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot,
                            bool cols_only = false) {
     using namespace gen;
     const int N = c->n_samples, logL = c->g_logL, B = c->n_buoys;
@@ -1536,21 +1552,19 @@ static int generic_forward(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
         RMX_TM_BEGIN(c);
-        if (c->wt.band) {   // weighted call (rmx_xcorr_batch_weighted; never with rot): the stored bins carry fwd_scale
-            XWeight a_wt = c->wt;
-            a_wt.unit = fwd_scale;
-            if (u8)
-                hipLaunchKernelGGL((g_fwd_small<true, XWeight>), dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst,
-                                   c->g_tw, N, logL, first_item, fwd_scale, (const float2*)nullptr, a_wt);
-            else
-                hipLaunchKernelGGL((g_fwd_small<false, XWeight>), dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst,
-                                   c->g_tw, N, logL, first_item, fwd_scale, (const float2*)nullptr, a_wt);
-        } else if (u8)
-            hipLaunchKernelGGL(g_fwd_small<true>, dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst, c->g_tw, N, logL,
-                               first_item, fwd_scale, rot);
-        else
-            hipLaunchKernelGGL(g_fwd_small<false>, dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst, c->g_tw, N, logL,
-                               first_item, fwd_scale, rot);
+        auto launch = [&](auto kern, const float2* a_rot, auto... wt) {
+            hipLaunchKernelGGL(kern, dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst, c->g_tw, N, logL, first_item,
+                               fwd_scale, a_rot, wt...);
+        };
+        with_u8(u8, [&](auto U) {
+            constexpr bool U8 = decltype(U)::value;
+            if (call.wt.band) {   // weighted call (never with rot): the stored bins carry fwd_scale
+                XWeight a_wt = call.wt;
+                a_wt.unit = fwd_scale;
+                launch(g_fwd_small<U8, XWeight>, nullptr, a_wt);
+            } else
+                launch(g_fwd_small<U8>, rot);
+        });
         RMX_HIP(c, hipGetLastError());
         RMX_TM_END(c, kTkFwdSmall);
         return RMX_OK;
@@ -1584,14 +1598,14 @@ static int generic_forward(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8
         int a_l2 = l2, a_L1 = L1, a_l1 = l1, a_lo = c->g_lo_bits, a_zero = 0, a_tpr = tpr;
         long a_L = L, a_rows = rows;
         float a_scale = fwd_scale;
-        // weighted call (rmx_xcorr_batch_weighted): the same arguments plus the weight, whose chunk starts at window w0
-        XWeight a_wt = c->wt;
+        // weighted call: the same arguments plus the weight, whose chunk starts at window w0
+        XWeight a_wt = call.wt;
         a_wt.w0 = w0;
         a_wt.unit = fwd_scale;
         void* args[] = {&a_data, &a_tw, &a_l2, &a_L1, &a_l1, &a_L, &a_lo, &a_thi, &a_tlo, &a_scale, &a_rows, &a_null, &a_null,
                         &a_pairs, &a_zero, &a_zero, &a_tpr, &a_wt};
         RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->wt.band ? c->g_rows_fwd_wt_fn : c->g_rows_fwd_fn, dim3((unsigned)((rows + rpw - 1) / rpw)),
+        RMX_HIP(c, hipLaunchKernel(call.wt.band ? c->g_rows_fwd_wt_fn : c->g_rows_fwd_fn, dim3((unsigned)((rows + rpw - 1) / rpw)),
                                    dim3(kGThreads), args, rlds, st));
         RMX_TM_END(c, kTkRowsFwd);
     }
@@ -1601,7 +1615,7 @@ static int generic_forward(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8
 
 // pair kernels of that chunk: X_i from g_spec, X_j from g_spec (use_rot false) or g_spec_r; results at
 // [(w0 + wl) * n_pairs + q] of the three output arrays
-static int generic_pairs(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak,
+static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak,
                          bool use_rot, bool fused = false) {
     using namespace gen;
     const int N = c->n_samples, logL = c->g_logL, B = c->n_buoys;
@@ -1614,17 +1628,16 @@ static int generic_pairs(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, fl
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
         RMX_TM_BEGIN(c);
-        if (c->integ > 1)   // integrated call: one workgroup per (group, pair); w0 and wc are whole groups, the bounds per group
-            hipLaunchKernelGGL((g_pair_small<LagBounds, Integrate>), dim3(slots / c->integ), dim3(sthr),
-                               (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st, c->g_spec, spec_j, c->g_tw, c->g_pairs, n_pairs, B, N,
-                               logL, (long)(w0 / c->integ), out_scale, d_lag, d_frac, d_peak, c->lb, Integrate{c->integ});
-        else if (c->lb.b)   // bounded call (rmx_xcorr_batch_bounded)
-            hipLaunchKernelGGL(g_pair_small<LagBounds>, dim3(slots), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st,
-                               c->g_spec, spec_j, c->g_tw, c->g_pairs, n_pairs, B, N, logL, (long)w0, out_scale, d_lag, d_frac,
-                               d_peak, c->lb);
+        auto launch = [&](auto kern, int grid, long first, auto... tail) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st, c->g_spec, spec_j, c->g_tw,
+                               c->g_pairs, n_pairs, B, N, logL, first, out_scale, d_lag, d_frac, d_peak, tail...);
+        };
+        if (call.integrated())   // one workgroup per (group, pair); w0 and wc are whole groups, the bounds per group
+            launch(g_pair_small<LagBounds, Integrate>, slots / call.integ, (long)(w0 / call.integ), call.lb, Integrate{call.integ});
+        else if (call.bounded())
+            launch(g_pair_small<LagBounds>, slots, (long)w0, call.lb);
         else
-        hipLaunchKernelGGL(g_pair_small<>, dim3(slots), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st, c->g_spec,
-                           spec_j, c->g_tw, c->g_pairs, n_pairs, B, N, logL, (long)w0, out_scale, d_lag, d_frac, d_peak);
+            launch(g_pair_small<>, slots, (long)w0);
         RMX_HIP(c, hipGetLastError());
         RMX_TM_END(c, kTkPairSmall);
         return RMX_OK;
@@ -1683,53 +1696,31 @@ static int generic_pairs(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, fl
         RMX_HIP(c, hipLaunchKernel(c->g_rows_inv_fn, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), args, rlds, st));
         RMX_TM_END(c, kTkRowsInv);
     }
-    if (c->integ > 1) {
-        // integrated call: the column pass sums the |r|^2 of a group's K product slots tile by tile and leaves one tile
-        // record and halo per (group, pair) slot; g_final then reduces those slots as it reduces a window's (the bounds are
-        // per group: slot -> group w0 / K + slot / P)
-        const int gslots = slots / c->integ;
-        const float2 *a_in = c->g_prod, *a_tw = c->g_tw1;
-        int a_l1 = l1, a_l2 = l2;
-        GTile* a_rec = c->g_rec;
-        float* a_halo = c->g_halo;
-        LagBounds a_lb = c->lb;
-        a_lb.w0 = w0 / c->integ;
-        a_lb.n_pairs = n_pairs;
-        Integrate a_ig{c->integ};
-        void* args[] = {&a_in, &a_tw, &a_l1, &a_l2, &a_rec, &a_halo, &a_lb, &a_ig};
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_cols_inv_int_fn, dim3(ntiles, gslots), dim3(cthr), args, clds, st));
-        RMX_TM_END(c, kTkColsInv);
-        RMX_TM_BEGIN(c);
-        hipLaunchKernelGGL(g_final<LagBounds>, dim3(gslots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, gslots,
-                           (long)(w0 / c->integ) * n_pairs, out_scale, d_lag, d_frac, d_peak, a_lb);
-        RMX_HIP(c, hipGetLastError());
-        RMX_TM_END(c, kTkFinal);
-        return RMX_OK;
-    }
+    // integrated call: the column pass sums the |r|^2 of a group's K product slots tile by tile and leaves one tile record
+    // and halo per (group, pair) slot; g_final then reduces those slots as it reduces a window's (the bounds are per group:
+    // slot -> group w0 / K + slot / P).  Otherwise K = 1: slot -> window w0 + slot / P, pair slot % P.
+    const int oslots = slots / call.integ;
+    LagBounds a_lb = call.lb;
+    a_lb.w0 = w0 / call.integ;
+    a_lb.n_pairs = n_pairs;
     {
         const float2 *a_in = c->g_prod, *a_tw = c->g_tw1;
         int a_l1 = l1, a_l2 = l2;
         GTile* a_rec = c->g_rec;
         float* a_halo = c->g_halo;
-        LagBounds a_lb = c->lb;   // (bounded call: slot -> window w0 + slot / P, pair slot % P)
-        a_lb.w0 = w0;
-        a_lb.n_pairs = n_pairs;
-        void* args[] = {&a_in, &a_tw, &a_l1, &a_l2, &a_rec, &a_halo, &a_lb};
+        Integrate a_ig{call.integ};
+        void* args[] = {&a_in, &a_tw, &a_l1, &a_l2, &a_rec, &a_halo, &a_lb, &a_ig};   // (each kernel reads its own leading part)
+        const void* fn = call.integrated() ? c->g_cols_inv_int_fn : call.bounded() ? c->g_cols_inv_lb_fn : c->g_cols_inv_fn;
         RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->lb.b ? c->g_cols_inv_lb_fn : c->g_cols_inv_fn, dim3(ntiles, slots), dim3(cthr), args, clds, st));
+        RMX_HIP(c, hipLaunchKernel(fn, dim3(ntiles, oslots), dim3(cthr), args, clds, st));
         RMX_TM_END(c, kTkColsInv);
     }
     RMX_TM_BEGIN(c);
-    if (c->lb.b) {
-        LagBounds a_lb = c->lb;
-        a_lb.w0 = w0;
-        a_lb.n_pairs = n_pairs;
-        hipLaunchKernelGGL(g_final<LagBounds>, dim3(slots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, slots,
-                           (long)w0 * n_pairs, out_scale, d_lag, d_frac, d_peak, a_lb);
-    } else
-    hipLaunchKernelGGL(g_final<>, dim3(slots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, slots,
-                       (long)w0 * n_pairs, out_scale, d_lag, d_frac, d_peak);
+    auto reduce = [&](auto kern, auto... lb) {
+        hipLaunchKernelGGL(kern, dim3(oslots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, oslots,
+                           a_lb.w0 * n_pairs, out_scale, d_lag, d_frac, d_peak, lb...);
+    };
+    if (call.bounded()) reduce(g_final<LagBounds>, a_lb); else reduce(g_final<>);   // (an integrated call always carries bounds)
     RMX_HIP(c, hipGetLastError());
     RMX_TM_END(c, kTkFinal);
     return RMX_OK;
@@ -1737,7 +1728,7 @@ static int generic_pairs(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, fl
 
 // windows [w0, w0 + n) of a batch through the four-step kernels (the partial last round behind a whole-window kernel's full
 // rounds, same stream): buffers on first need, chunks as in generic_batch's own loop
-static int four_step_windows(rmx_ctx* c, const void* d_iq, int w_first, int n, int n_pairs, int* d_lag, float* d_frac,
+static int four_step_windows(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w_first, int n, int n_pairs, int* d_lag, float* d_frac,
                              float* d_peak, bool u8) {
     int rc = generic_ensure(c, n_pairs, true, true);
     if (rc) return rc;
@@ -1745,9 +1736,9 @@ static int four_step_windows(rmx_ctx* c, const void* d_iq, int w_first, int n, i
         const int wc = w_first + n - w0 < c->g_chunk ? w_first + n - w0 : c->g_chunk;
         const long fused_blocks = c->g_fused ? (long)wc * (1L << c->g_logL1) / (gen::kGThreads / ((1 << c->g_logL2) >> 4)) : 0;
         const bool fused = c->g_fused && (fused_blocks >= 2L * c->n_cus || c->g_fused_always);
-        rc = generic_forward(c, d_iq, w0, wc, u8, nullptr, fused);
+        rc = generic_forward(c, call, d_iq, w0, wc, u8, nullptr, fused);
         if (rc) return rc;
-        rc = generic_pairs(c, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
+        rc = generic_pairs(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
         if (rc) return rc;
     }
     return RMX_OK;
@@ -1756,7 +1747,8 @@ static int four_step_windows(rmx_ctx* c, const void* d_iq, int w_first, int n, i
 // N = 16384 through k16_fwd / k16_pairs (kwin16k.hpp): per chunk of g_ws_grid windows (the spectrum scratch holds that many)
 // one forward launch -- (window, buoy) items over at most one workgroup per CU -- and one pair launch of 8 S workgroups,
 // S = workgroups per XCD.  No per-window state survives the chunk.
-static int k16_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pairs, int* d_lag, float* d_frac, float* d_peak, bool u8) {
+static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_windows, int n_pairs, int* d_lag, float* d_frac, float* d_peak,
+                     bool u8) {
     const int B = c->n_buoys;
     const float out_scale = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 15);
     const int chunk = c->g_ws_grid;
@@ -1766,12 +1758,10 @@ static int k16_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pairs, i
         const int items = wc * B;
         const unsigned fgrid = (unsigned)(items < c->n_cus ? items : c->n_cus);
         RMX_TM_BEGIN(c);
-        if (u8)
-            hipLaunchKernelGGL(k16::k16_fwd<true>, dim3(fgrid), dim3(kThreads), k16::kLdsFwdBytes, c->stream, d_iq, c->g_ws_scratch,
-                               c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, (long)w0 * B, items);
-        else
-            hipLaunchKernelGGL(k16::k16_fwd<false>, dim3(fgrid), dim3(kThreads), k16::kLdsFwdBytes, c->stream, d_iq, c->g_ws_scratch,
-                               c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, (long)w0 * B, items);
+        with_u8(u8, [&](auto U) {
+            hipLaunchKernelGGL(k16::k16_fwd<decltype(U)::value>, dim3(fgrid), dim3(kThreads), k16::kLdsFwdBytes, c->stream, d_iq,
+                               c->g_ws_scratch, c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, (long)w0 * B, items);
+        });
         RMX_HIP(c, hipGetLastError());
         RMX_TM_END(c, kTkFwd16k);
         // XCD-aware item order (the pairs of a window on one XCD) unless the windows do not spread evenly over eight XCDs
@@ -1783,24 +1773,25 @@ static int k16_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pairs, i
         long pgrid = 8 * S;
         if (flat) pgrid = (long)wc * n_pairs < c->n_cus ? (long)wc * n_pairs : c->n_cus;
         RMX_TM_BEGIN(c);
-        if (c->lb.b) {   // bounded call: the same kernel with the lag windows (lb.w0: window 0 of this launch)
-            LagBounds a_lb = c->lb;
+        auto pairs = [&](auto kern, auto... lb) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)pgrid), dim3(kThreads), k16::kLdsPairBytes, c->stream, c->g_ws_scratch,
+                               c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, B, prs, n_pairs, (long)w0 * n_pairs, wc, flat,
+                               out_scale, d_lag, d_frac, d_peak, lb...);
+        };
+        if (call.bounded()) {   // the same kernel with the lag windows (lb.w0: window 0 of this launch)
+            LagBounds a_lb = call.lb;
             a_lb.w0 = w0;
             a_lb.n_pairs = n_pairs;
-            hipLaunchKernelGGL(k16::k16_pairs<LagBounds>, dim3((unsigned)pgrid), dim3(kThreads), k16::kLdsPairBytes, c->stream,
-                               c->g_ws_scratch, c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, B, prs, n_pairs,
-                               (long)w0 * n_pairs, wc, flat, out_scale, d_lag, d_frac, d_peak, a_lb);
+            pairs(k16::k16_pairs<LagBounds>, a_lb);
         } else
-        hipLaunchKernelGGL(k16::k16_pairs<>, dim3((unsigned)pgrid), dim3(kThreads), k16::kLdsPairBytes, c->stream, c->g_ws_scratch,
-                           c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, B, prs, n_pairs, (long)w0 * n_pairs, wc, flat,
-                           out_scale, d_lag, d_frac, d_peak);
+            pairs(k16::k16_pairs<>);
         RMX_HIP(c, hipGetLastError());
         RMX_TM_END(c, kTkPairs16k);
     }
     return RMX_OK;
 }
 
-static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pairs, int* d_lag, float* d_frac,
+static int generic_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_windows, int n_pairs, int* d_lag, float* d_frac,
                          float* d_peak, bool u8) {
     // N = 16384 on k_win's network (kwin16k.hpp): fine-grained items, so no partial last round and a low minimum batch -- its
     // two launches cost about 40 us whatever the size, the four-step kernels 26 us for one window: from about 100 transforms
@@ -1810,13 +1801,13 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
     // g_fwd_small up to L = small_maxl, g_cols_fwd + the forward g_rows above.  The whole-window kernels (g_win_*,
     // k_win8kl), k16_fwd and g_rows_fused keep their spectra to themselves and are never taken.
     // Integrated calls (rmx_xcorr_batch_integrated) sum over windows inside the per-transform pair kernels: the same routes.
-    const bool weighted = c->wt.band != nullptr || c->integ > 1;
+    const bool weighted = call.weighted();
     if (!weighted && c->g_k16 && c->g_logL == 15 && n_pairs <= k16::kMaxPairs16 &&
         (c->g_k16 == 2 || (!c->g_wscr_always &&
                            n_windows >= (int)c->knobs.get_or("k16_min_windows", (100 + c->n_buoys + n_pairs - 1) / (c->n_buoys + n_pairs))))) {
         const int rc16 = generic_ensure(c, n_pairs, false, false);
         if (rc16) return rc16;
-        return k16_batch(c, d_iq, n_windows, n_pairs, d_lag, d_frac, d_peak, u8);
+        return k16_batch(c, call, d_iq, n_windows, n_pairs, d_lag, d_frac, d_peak, u8);
     }
     // g_win_scr runs a window's B + P transforms one after the other in one workgroup: batches that leave most of the chip
     // without a workgroup are better off in the per-transform kernels below (8 buoys x 8 windows of 8192: 0.32 vs 0.05 ms).
@@ -1831,7 +1822,7 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
     // g_win_fused, g_win_scr, g_win_scr14 and g_win_eo15 have none: a bounded call that would take one of them takes the
     // per-transform kernels instead (g_fwd_small + g_pair_small up to L = small_maxl, the four-step kernels above), whose
     // peak searches are bounded.  At the BASELINE shapes the fused kernels run either way (k_win, k_win8kl, k16_pairs).
-    const bool bounded = c->lb.b != nullptr;
+    const bool bounded = call.bounded();
     const bool k8_route = c->g_k8 && (def_list_b || n_pairs <= k8::kMaxPairs8);
     const bool use_wscr = !weighted && c->g_wscr && (!bounded || k8_route) &&
                           (c->g_wscr_always || ws_blocks >= (c->g_logL == 14 ? (c->g_k8 ? 5L : 7L) : 11L) * c->n_cus / 16);
@@ -1870,37 +1861,21 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
             const int n_head = n_windows - n_tail;
             n_windows = n_head;                 // (the launches below take the full rounds)
             RMX_TM_BEGIN(c);
+            auto launch = [&](auto kern, size_t lds, auto... lb) {
+                hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, c->stream, d_iq, c->g_ws_scratch, c->g_k8_tw1,
+                                   c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag, d_frac, d_peak, n_windows, stag, lb...);
+            };
+            with_u8(u8, [&](auto U) {
+                constexpr bool U8 = decltype(U)::value;
 #ifdef RMX_EXPERIMENTS
-            if (c->g_k8_kind == 2) {
-                if (u8)
-                    hipLaunchKernelGGL(k8::k_win8k<true>, dim3((unsigned)grid), dim3(kThreads), k8::kLds8Bytes, c->stream, d_iq,
-                                       c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag,
-                                       d_frac, d_peak, n_windows, stag);
+                if (c->g_k8_kind == 2) launch(k8::k_win8k<U8>, k8::kLds8Bytes);
                 else
-                    hipLaunchKernelGGL(k8::k_win8k<false>, dim3((unsigned)grid), dim3(kThreads), k8::kLds8Bytes, c->stream, d_iq,
-                                       c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag,
-                                       d_frac, d_peak, n_windows, stag);
-            } else
 #endif
-            if (bounded && u8)
-                hipLaunchKernelGGL((k8::k_win8kl<true, LagBounds>), dim3((unsigned)grid), dim3(kThreads), k8::kLdsLBytes, c->stream,
-                                   d_iq, c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale,
-                                   d_lag, d_frac, d_peak, n_windows, stag, c->lb);
-            else if (bounded)
-                hipLaunchKernelGGL((k8::k_win8kl<false, LagBounds>), dim3((unsigned)grid), dim3(kThreads), k8::kLdsLBytes, c->stream,
-                                   d_iq, c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale,
-                                   d_lag, d_frac, d_peak, n_windows, stag, c->lb);
-            else if (u8)
-                hipLaunchKernelGGL(k8::k_win8kl<true>, dim3((unsigned)grid), dim3(kThreads), k8::kLdsLBytes, c->stream, d_iq,
-                                   c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag,
-                                   d_frac, d_peak, n_windows, stag);
-            else
-                hipLaunchKernelGGL(k8::k_win8kl<false>, dim3((unsigned)grid), dim3(kThreads), k8::kLdsLBytes, c->stream, d_iq,
-                                   c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag,
-                                   d_frac, d_peak, n_windows, stag);
+                if (bounded) launch(k8::k_win8kl<U8, LagBounds>, k8::kLdsLBytes, call.lb); else launch(k8::k_win8kl<U8>, k8::kLdsLBytes);
+            });
             RMX_HIP(c, hipGetLastError());
             RMX_TM_END(c, kTkWindow);
-            if (n_tail) return four_step_windows(c, d_iq, n_head, n_tail, n_pairs, d_lag, d_frac, d_peak, u8);
+            if (n_tail) return four_step_windows(c, call, d_iq, n_head, n_tail, n_pairs, d_lag, d_frac, d_peak, u8);
             return RMX_OK;
         }
         if (logL == 15) {                          // g_win_eo15: one more table
@@ -1920,7 +1895,7 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
             RMX_TM_BEGIN(c);
             RMX_HIP(c, hipLaunchKernel(c->g_ws_fn[u8 ? 1 : 0], dim3((unsigned)grid), dim3(c->g_ws_thr), args, c->g_ws_lds, c->stream));
             RMX_TM_END(c, kTkWindow);
-            if (n_tail) return four_step_windows(c, d_iq, n_head, n_tail, n_pairs, d_lag, d_frac, d_peak, u8);
+            if (n_tail) return four_step_windows(c, call, d_iq, n_head, n_tail, n_pairs, d_lag, d_frac, d_peak, u8);
             return RMX_OK;
         }
         void* args[] = {&a_iq, &a_scr, &a_tw, &a_nb, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
@@ -1948,11 +1923,11 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
         return RMX_OK;
     }
     // (integrated call: a chunk holds whole groups -- never a silent split of a group)
-    const int chunk = c->g_chunk / c->integ * c->integ;
+    const int chunk = c->g_chunk / call.integ * call.integ;
     if (chunk == 0)
         return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
-                    c->integ, c->g_chunk);
-    if (c->integ > 1 && (1L << c->g_logL) > kGenSmallMaxL &&
+                    call.integ, c->g_chunk);
+    if (call.integrated() && (1L << c->g_logL) > kGenSmallMaxL &&
         ((1L << c->g_logL1) << host_col_log_t(c, c->g_logL1)) > (long)kIntegMaxPerThread * gen_cols_threads(c, c->g_logL1))
         return fail(c, RMX_E_UNSUPPORTED, "integrated call: a column tile of %ld elements on %d threads is more than %d per thread",
                     (1L << c->g_logL1) << host_col_log_t(c, c->g_logL1), gen_cols_threads(c, c->g_logL1), kIntegMaxPerThread);
@@ -1963,9 +1938,9 @@ static int generic_batch(rmx_ctx* c, const void* d_iq, int n_windows, int n_pair
         const long fused_blocks = c->g_fused ? (long)wc * (1L << c->g_logL1) / (gen::kGThreads / ((1 << c->g_logL2) >> 4)) : 0;
         const bool fused = !weighted && c->g_fused && (1L << c->g_logL) > kGenSmallMaxL &&
                            (fused_blocks >= 2L * c->n_cus || c->g_fused_always);
-        rc = generic_forward(c, d_iq, w0, wc, u8, nullptr, fused);
+        rc = generic_forward(c, call, d_iq, w0, wc, u8, nullptr, fused);
         if (rc) return rc;
-        rc = generic_pairs(c, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
+        rc = generic_pairs(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
         if (rc) return rc;
     }
     return RMX_OK;
@@ -2128,12 +2103,11 @@ void rmx_destroy(rmx_ctx* c) {
     if (c->d_in) (void)hipFree(c->d_in);
     if (c->d_lag) (void)hipFree(c->d_lag);            // (d_frac / d_peak point into the same block)
     if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->d_lb) (void)hipFree(c->d_lb);
-    if (c->h_lb) (void)hipHostFree(c->h_lb);
-    if (c->lb_ev) (void)hipEventDestroy(c->lb_ev);
-    if (c->d_band) (void)hipFree(c->d_band);
-    if (c->h_band) (void)hipHostFree(c->h_band);
-    if (c->band_ev) (void)hipEventDestroy(c->band_ev);
+    for (rmx::DevStage* s : {&c->lb_stage, &c->band_stage}) {
+        if (s->d) (void)hipFree(s->d);
+        if (s->h) (void)hipHostFree(s->h);
+        if (s->ev) (void)hipEventDestroy(s->ev);
+    }
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2233,7 +2207,7 @@ static int ensure_spec(rmx_ctx* c, long windows) {
 
 // N = 4096, unfused path: forward spectra of windows [w0, w0 + wc) into d_spec (rot == nullptr) or, de-rotated by
 // the phasor table rot[N], into d_spec_r (rmx_caf_batch); then the pair kernels over the plan's pair list
-static int fwd4096(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8, const float2* rot, int n_bins = 1) {
+static int fwd4096(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot, int n_bins = 1) {
     const long first_item = (long)w0 * c->n_buoys;
     const int wrap = n_bins > 1 ? wc * c->n_buoys : 0;
     const int n_items = wc * c->n_buoys * n_bins;
@@ -2251,62 +2225,53 @@ static int fwd4096(rmx_ctx* c, const void* d_iq, int w0, int wc, bool u8, const 
     }
     float4* dst = rot ? c->d_spec_r : c->d_spec;
     RMX_TM_BEGIN(c);
-    if (c->wt.band) {   // weighted call (rmx_xcorr_batch_weighted; never with rot): the stored bins carry the TW1 scale
-        XWeight a_wt = c->wt;
-        a_wt.unit = (float)kTw1Scale;
-        if (u8)
-            hipLaunchKernelGGL((k_fwd<true, XWeight>), dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1,
-                               c->d_tw2, first_item, 1.0f, (const float2*)nullptr, 0, a_wt);
-        else
-            hipLaunchKernelGGL((k_fwd<false, XWeight>), dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1,
-                               c->d_tw2, first_item, 1.0f, (const float2*)nullptr, 0, a_wt);
-    } else if (u8)
-        hipLaunchKernelGGL(k_fwd<true>, dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1, c->d_tw2,
-                           first_item, 1.0f, rot, wrap);
-    else
-        hipLaunchKernelGGL(k_fwd<false>, dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1, c->d_tw2,
-                           first_item, 1.0f, rot, wrap);
+    auto launch = [&](auto kern, const float2* a_rot, int a_wrap, auto... wt) {
+        hipLaunchKernelGGL(kern, dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1, c->d_tw2, first_item,
+                           1.0f, a_rot, a_wrap, wt...);
+    };
+    with_u8(u8, [&](auto U) {
+        constexpr bool U8 = decltype(U)::value;
+        if (call.wt.band) {   // weighted call (never with rot): the stored bins carry the TW1 scale
+            XWeight a_wt = call.wt;
+            a_wt.unit = (float)kTw1Scale;
+            launch(k_fwd<U8, XWeight>, nullptr, 0, a_wt);
+        } else
+            launch(k_fwd<U8>, rot, wrap);
+    });
     RMX_HIP(c, hipGetLastError());
     RMX_TM_END(c, kTkFwd4096);
     return RMX_OK;
 }
-static int pairs4096(rmx_ctx* c, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, float out_scale,
+static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, float out_scale,
                      bool use_rot, int n_bins = 1) {
     const int n_parts = c->plan_n_parts;
     const int i_wrap = n_bins > 1 ? wc : 0;     // (all hypotheses in one launch: virtual window = hypothesis * wc + window)
     wc *= n_bins;
     const int xcd_map = (wc % 8 == 0) ? 1 : 0;
     const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
-    if (c->integ > 1) {
-        // integrated call: always the streaming kernel's integrating instantiation, one work item per (group, pair);
-        // w0 and wc are whole groups, the bounds per group
-        const int gc = wc / c->integ;
-        RMX_TM_BEGIN(c);
-        hipLaunchKernelGGL((k_pair_str<LagBounds, Integrate>), dim3(gc * n_parts), dim3(kThreads), kLdsBytes, c->stream,
-                           (const float4*)c->d_spec, spec_j, c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys,
-                           n_pairs, (gc % 8 == 0) ? 1 : 0, (long)(w0 / c->integ), out_scale, d_lag, d_frac, d_peak, 0, c->lb,
-                           Integrate{c->integ});
-        RMX_HIP(c, hipGetLastError());
-        RMX_TM_END(c, kTkPair4096);
-        return RMX_OK;
-    }
-    RMX_TM_BEGIN(c);
-    if (c->lb.b && c->resident)   // bounded call (rmx_xcorr_batch_bounded)
-        hipLaunchKernelGGL(k_pair_res<LagBounds>, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream,
-                           (const float4*)c->d_spec, spec_j, c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys,
-                           n_pairs, xcd_map, (long)w0, out_scale, d_lag, d_frac, d_peak, c->dbg, i_wrap, c->lb);
-    else if (c->lb.b)
-        hipLaunchKernelGGL(k_pair_str<LagBounds>, dim3(wc * n_parts), dim3(kThreads), kLdsBytes, c->stream,
-                           (const float4*)c->d_spec, spec_j, c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys,
-                           n_pairs, xcd_map, (long)w0, out_scale, d_lag, d_frac, d_peak, i_wrap, c->lb);
-    else if (c->resident)
-        hipLaunchKernelGGL(k_pair_res<>, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream, (const float4*)c->d_spec,
-                           spec_j, c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map,
-                           (long)w0, out_scale, d_lag, d_frac, d_peak, c->dbg, i_wrap);
-    else
-        hipLaunchKernelGGL(k_pair_str<>, dim3(wc * n_parts), dim3(kThreads), kLdsBytes, c->stream, (const float4*)c->d_spec, spec_j,
+    // the streaming and the resident kernel (which takes c->dbg as well), each with or without its trailing structs
+    auto str = [&](auto kern, int windows, int xmap, long first, int wrap, auto... tail) {
+        hipLaunchKernelGGL(kern, dim3(windows * n_parts), dim3(kThreads), kLdsBytes, c->stream, (const float4*)c->d_spec, spec_j,
+                           c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xmap, first, out_scale,
+                           d_lag, d_frac, d_peak, wrap, tail...);
+    };
+    auto res = [&](auto kern, auto... lb) {
+        hipLaunchKernelGGL(kern, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream, (const float4*)c->d_spec, spec_j,
                            c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, (long)w0,
-                           out_scale, d_lag, d_frac, d_peak, i_wrap);
+                           out_scale, d_lag, d_frac, d_peak, c->dbg, i_wrap, lb...);
+    };
+    RMX_TM_BEGIN(c);
+    if (call.integrated()) {
+        // always the streaming kernel's integrating instantiation, one work item per (group, pair); w0 and wc are whole
+        // groups, the bounds per group
+        const int gc = wc / call.integ;
+        str(k_pair_str<LagBounds, Integrate>, gc, (gc % 8 == 0) ? 1 : 0, (long)(w0 / call.integ), 0, call.lb, Integrate{call.integ});
+    } else if (c->resident) {
+        if (call.bounded()) res(k_pair_res<LagBounds>, call.lb); else res(k_pair_res<>);
+    } else {
+        if (call.bounded()) str(k_pair_str<LagBounds>, wc, xcd_map, (long)w0, i_wrap, call.lb);
+        else str(k_pair_str<>, wc, xcd_map, (long)w0, i_wrap);
+    }
     RMX_HIP(c, hipGetLastError());
     RMX_TM_END(c, kTkPair4096);
     return RMX_OK;
@@ -2368,21 +2333,71 @@ static double split_cost4096(const rmx_ctx* c, int n_windows, int n_pairs, int* 
     return host::split_cost4096(c->n_cus, c->n_buoys, n_pairs, n_windows, c->ppb_user ? c->pairs_per_block : 0, ppb);
 }
 
-int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
-                    int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    if (!c) return RMX_E_INVAL;
-    if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
+// ---- what the correlation entries share ----------------------------------------------------------------------------
+static int check_n_windows(rmx_ctx* c, int n_windows) {
     if (n_windows < 0 || n_windows > c->max_windows)
         return fail(c, RMX_E_INVAL, "n_windows %d not in 0..max_windows=%d", n_windows, c->max_windows);
+    return RMX_OK;
+}
+// the shape of a batch: n_windows in range; pairs == NULL is the default list, and *n_pairs becomes its length
+static int check_batch(rmx_ctx* c, int n_windows, const int32_t* pairs, int* n_pairs) {
+    const int rc = check_n_windows(c, n_windows);
+    if (rc != RMX_OK) return rc;
     const int all_pairs = c->n_buoys * (c->n_buoys - 1) / 2;
     if (!pairs) {
-        if (n_pairs != 0 && n_pairs != all_pairs)
-            return fail(c, RMX_E_INVAL, "pairs == NULL needs n_pairs == 0 or %d, got %d", all_pairs, n_pairs);
-        n_pairs = all_pairs;
+        if (*n_pairs != 0 && *n_pairs != all_pairs)
+            return fail(c, RMX_E_INVAL, "pairs == NULL needs n_pairs == 0 or %d, got %d", all_pairs, *n_pairs);
+        *n_pairs = all_pairs;
     }
-    if (n_pairs < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
-    if (n_windows == 0 || n_pairs == 0) return RMX_OK;
-    RMX_HIP(c, hipSetDevice(c->device));
+    if (*n_pairs < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", *n_pairs);
+    return RMX_OK;
+}
+
+// host windows: the ctx-owned device copy they go to
+static int ensure_in(rmx_ctx* c, size_t in_bytes) {
+    if (c->d_in_bytes >= in_bytes) return RMX_OK;
+    if (c->d_in) (void)hipFree(c->d_in);
+    c->d_in = nullptr;
+    c->d_in_bytes = 0;
+    RMX_HIP(c, hipMalloc(&c->d_in, in_bytes));
+    c->d_in_bytes = in_bytes;
+    return RMX_OK;
+}
+
+// `elems` int32 of src into s->d through the pinned s->h: the caller may reuse src as soon as the call returns (with
+// RMX_OUT_DEVICE too), and the copy runs on the ctx stream -- behind every earlier kernel that reads s->d, in front of
+// this call's kernels
+static int stage_to_device(rmx_ctx* c, DevStage* s, const int32_t* src, size_t elems) {
+    if (!s->ev) RMX_HIP(c, hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
+    RMX_HIP(c, hipEventSynchronize(s->ev));   // the previous call's copy out of the pinned buffer has finished
+    if (s->h_elems < elems) {
+        if (s->h) (void)hipHostFree(s->h);
+        s->h = nullptr; s->h_elems = 0;
+        RMX_HIP(c, hipHostMalloc((void**)&s->h, elems * sizeof(int32_t), hipHostMallocDefault));
+        s->h_elems = elems;
+    }
+    if (s->d_elems < elems) {
+        RMX_HIP(c, hipStreamSynchronize(c->stream));   // earlier kernels of this ctx may still read the old buffer
+        if (s->d) (void)hipFree(s->d);
+        c->scratch_bytes -= s->d_elems * sizeof(int32_t);
+        s->d = nullptr; s->d_elems = 0;
+        RMX_HIP(c, hipMalloc((void**)&s->d, elems * sizeof(int32_t)));
+        s->d_elems = elems;
+        c->scratch_bytes += elems * sizeof(int32_t);
+    }
+    std::memcpy(s->h, src, elems * sizeof(int32_t));
+    RMX_HIP(c, hipMemcpyAsync(s->d, s->h, elems * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    RMX_HIP(c, hipEventRecord(s->ev, c->stream));
+    return RMX_OK;
+}
+
+// One correlation call as `call` describes it -- plain, bounded, weighted, integrated or any mix: every route launches the
+// instantiations the request names (the bounded one of its peak-searching kernel, lag_bounds.hpp; the weighted one of its
+// per-transform forward kernel, xspec_weight.hpp; the integrating one of its pair kernel, integrate.hpp) or, where a
+// route has none, is steered to the per-transform kernels.  The arguments have been checked (xcorr_request).
+static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& call, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                          int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    const int all_pairs = c->n_buoys * (c->n_buoys - 1) / 2;
     tm_reset(c);
     // Few windows of N = 4096: the fused kernel is one workgroup per WINDOW -- (B + P) transforms in sequence, 92 us for
     // one window of 8 buoys, 344 us for 16 buoys, whatever the rest of the chip does -- while the per-transform kernels
@@ -2402,8 +2417,8 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     // a weighted call (rmx_xcorr_batch_weighted) weights the spectra where k_fwd stores them: the per-transform kernels
     // at every batch size, never k_win (whose spectra stay inside the workgroup)
     // (an integrated call sums over windows inside k_pair_str: the same kernels, with one work item per (group, pair))
-    if ((c->wt.band || c->integ > 1) && !c->generic) {
-        (void)split_cost4096(c, n_windows / c->integ, n_pairs, &ppb_small);
+    if (call.weighted() && !c->generic) {
+        (void)split_cost4096(c, n_windows / call.integ, n_pairs, &ppb_small);
         small = true;
     }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
@@ -2456,13 +2471,8 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     const void* d_iq = iq;
     bool pipelined = false;
     if (!in_dev) {
-        if (c->d_in_bytes < in_bytes) {
-            if (c->d_in) (void)hipFree(c->d_in);
-            c->d_in = nullptr;
-            c->d_in_bytes = 0;
-            RMX_HIP(c, hipMalloc(&c->d_in, in_bytes));
-            c->d_in_bytes = in_bytes;
-        }
+        rc = ensure_in(c, in_bytes);
+        if (rc != RMX_OK) return rc;
         // fused path: the copy is cut into sub-chunks issued on a second stream, each followed by its
         // kernel launch, so that copy k+1 travels while kernel k runs (below); otherwise one copy up front
         pipelined = !c->generic && fused_now && n_windows > kHostSubChunk;
@@ -2481,7 +2491,7 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     int* d_lag = lag_int;
     float* d_frac = lag_frac;
     float* d_peak = peak;
-    const size_t out_elems = (size_t)(n_windows / c->integ) * n_pairs;   // (integrated call: one row per group)
+    const size_t out_elems = (size_t)(n_windows / call.integ) * n_pairs;   // (integrated call: one row per group)
     if (!out_dev) {
         {
             const int rc_out = ensure_out(c, out_elems);
@@ -2491,7 +2501,7 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     }
 
     if (c->generic) {
-        rc = rmx::generic_batch(c, d_iq, n_windows, n_pairs, d_lag, d_frac, d_peak, u8);
+        rc = rmx::generic_batch(c, call, d_iq, n_windows, n_pairs, d_lag, d_frac, d_peak, u8);
         if (rc != RMX_OK) return rc;
         if (!out_dev) return fetch_out(c, out_elems, lag_int, lag_frac, peak);
         return RMX_OK;
@@ -2506,10 +2516,10 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
     }
     int n_sub = 0;
     // (integrated call: a chunk holds whole groups -- never a silent split of a group)
-    const int chunk_windows = c->chunk_windows / c->integ * c->integ;
+    const int chunk_windows = c->chunk_windows / call.integ * call.integ;
     if (chunk_windows == 0)
         return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
-                    c->integ, c->chunk_windows);
+                    call.integ, c->chunk_windows);
     for (int w0 = 0; w0 < n_windows; w0 += chunk_windows) {
         const int wc = (n_windows - w0 < chunk_windows) ? n_windows - w0 : chunk_windows;
         if (fused_now) {
@@ -2539,238 +2549,198 @@ int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pa
                 // one persistent workgroup per CU (the kernel's LDS footprint allows exactly one)
                 const int wgrid = sc < c->n_cus ? sc : c->n_cus;
                 RMX_TM_BEGIN(c);
+                with_u8(u8, [&](auto U) {
+                    constexpr bool U8 = decltype(U)::value;
+                    auto launch = [&](auto kern, auto... lb) {
+                        hipLaunchKernelGGL(kern, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec, c->d_tw1,
+                                           c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, c->dbg, c->stag, lb...);
+                    };
 #ifdef RMX_EXPERIMENTS
-                if (c->win8) {
-                    if (u8)
-                        hipLaunchKernelGGL(w8::k_win8<true>, dim3(wgrid), dim3(w8::kT8), w8::kLdsWin8Bytes, c->stream, d_iq,
-                                           c->d_spec, c->d_tw1_8, c->d_tb8, c->d_tc8, c->n_buoys, wfirst, out_scale, d_lag,
-                                           d_frac, d_peak, sc, c->stag);
-                    else
-                        hipLaunchKernelGGL(w8::k_win8<false>, dim3(wgrid), dim3(w8::kT8), w8::kLdsWin8Bytes, c->stream, d_iq,
-                                           c->d_spec, c->d_tw1_8, c->d_tb8, c->d_tc8, c->n_buoys, wfirst, out_scale, d_lag,
-                                           d_frac, d_peak, sc, c->stag);
-                } else if (c->pk) {
-                    if (u8)
-                        hipLaunchKernelGGL(k_winp<true>, dim3(wgrid), dim3(kThreads), pk::kLdsWinpBytes, c->stream, d_iq, c->d_spec,
+                    if (c->win8)
+                        hipLaunchKernelGGL(w8::k_win8<U8>, dim3(wgrid), dim3(w8::kT8), w8::kLdsWin8Bytes, c->stream, d_iq, c->d_spec,
+                                           c->d_tw1_8, c->d_tb8, c->d_tc8, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc,
+                                           c->stag);
+                    else if (c->pk)
+                        hipLaunchKernelGGL(k_winp<U8>, dim3(wgrid), dim3(kThreads), pk::kLdsWinpBytes, c->stream, d_iq, c->d_spec,
                                            c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc);
                     else
-                        hipLaunchKernelGGL(k_winp<false>, dim3(wgrid), dim3(kThreads), pk::kLdsWinpBytes, c->stream, d_iq, c->d_spec,
-                                           c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc);
-                } else
 #endif
-                if (c->lb.b && u8)   // bounded call (rmx_xcorr_batch_bounded): k_win's bounded instantiation
-                    hipLaunchKernelGGL(k_win_lb<true>, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec,
-                                       c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac,
-                                       d_peak, sc, c->dbg, c->stag, c->lb);
-                else if (c->lb.b)
-                    hipLaunchKernelGGL(k_win_lb<false>, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec,
-                                       c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac,
-                                       d_peak, sc, c->dbg, c->stag, c->lb);
-                else if (u8)
-                    hipLaunchKernelGGL(k_win<true>, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec,
-                                       c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac,
-                                       d_peak, sc, c->dbg, c->stag);
-                else
-                    hipLaunchKernelGGL(k_win<false>, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec,
-                                       c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac,
-                                       d_peak, sc, c->dbg, c->stag);
+                    if (call.bounded()) launch(k_win_lb<U8>, call.lb);   // k_win's bounded instantiation
+                    else launch(k_win<U8>);
+                });
                 RMX_HIP(c, hipGetLastError());
                 RMX_TM_END(c, kTkPair4096);
             }
             if (wtail) {
-                rc = fwd4096(c, d_iq, w0 + wf, wtail, u8, nullptr);
+                rc = fwd4096(c, call, d_iq, w0 + wf, wtail, u8, nullptr);
                 if (rc != RMX_OK) return rc;
-                rc = pairs4096(c, w0 + wf, wtail, n_pairs, d_lag, d_frac, d_peak, out_scale, false);
+                rc = pairs4096(c, call, w0 + wf, wtail, n_pairs, d_lag, d_frac, d_peak, out_scale, false);
                 if (rc != RMX_OK) return rc;
             }
             continue;
         }
-        rc = fwd4096(c, d_iq, w0, wc, u8, nullptr);
+        rc = fwd4096(c, call, d_iq, w0, wc, u8, nullptr);
         if (rc != RMX_OK) return rc;
-        rc = pairs4096(c, w0, wc, n_pairs, d_lag, d_frac, d_peak, out_scale, false);
+        rc = pairs4096(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, out_scale, false);
         if (rc != RMX_OK) return rc;
     }
     if (!out_dev) return fetch_out(c, out_elems, lag_int, lag_frac, peak);
     return RMX_OK;
 }
 
-// rmx_xcorr_batch with a lag window per (window, pair): the bounds are validated here, copied through the ctx's own pinned
-// staging into a ctx-owned device buffer (the caller may reuse its array as soon as the call returns, RMX_OUT_DEVICE
-// included), and rmx_xcorr_batch then dispatches with c->lb set: every route launches the bounded instantiation of its
-// peak-searching kernel (lag_bounds.hpp), or -- the whole-window generic kernels, which have none -- is steered to the
-// per-transform kernels (generic_batch).
+// ---- the three validators, one per feature --------------------------------------------------------------------------
+// rmx_xcorr_batch_integrated: K and the group count; an unbounded call with K > 1 gets the full interval per pair in
+// *full (the integrating kernels always carry bounds)
+static int check_integrated(rmx_ctx* c, int n_windows, const int32_t* pairs, int n_pairs, int integrate, bool bounds_given,
+                            std::vector<int32_t>* full) {
+    if (integrate < 1) return fail(c, RMX_E_INVAL, "integrate = %d: at least one window per group", integrate);
+    if (n_windows <= 0 || n_windows % integrate != 0)
+        return fail(c, RMX_E_INVAL, "n_windows = %d is not a positive multiple of integrate = %d", n_windows, integrate);
+    if (integrate == 1 || bounds_given) return RMX_OK;
+    const int np = pairs ? n_pairs : c->n_buoys * (c->n_buoys - 1) / 2;
+    if (np < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
+    full->resize((size_t)(2 * (np > 0 ? np : 1)));   // (np == 0 is never read: a call without pairs returns before the bounds)
+    for (int q = 0; q < np; ++q) {
+        (*full)[2 * q] = -(c->n_samples - 1);
+        (*full)[2 * q + 1] = c->n_samples - 1;
+    }
+    return RMX_OK;
+}
+
+// rmx_xcorr_batch_weighted: the weighting, the window count and the bands, one per window or one for all, converted to
+// signed bins in *bins.  *weighted stays false when there is no band (or the full one) and no weighting: the plain call.
+static int check_weighted(rmx_ctx* c, int n_windows, const double* band_cps, int band_per_window, unsigned weighting,
+                          std::vector<int32_t>* bins, bool* weighted) {
+    if (weighting != RMX_WEIGHT_NONE && weighting != RMX_WEIGHT_PHAT)
+        return fail(c, RMX_E_INVAL, "unknown weighting %u (RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1)", weighting);
+    const int rc = check_n_windows(c, n_windows);
+    if (rc != RMX_OK) return rc;
+    const int N = c->n_samples;
+    const long rows = band_cps ? (band_per_window ? (long)n_windows : 1L) : 1L;
+    bins->resize((size_t)(2 * rows));
+    bool all_full = true;
+    for (long r = 0; r < rows; ++r) {
+        const double lo = band_cps ? band_cps[2 * r] : -0.5, hi = band_cps ? band_cps[2 * r + 1] : 0.5;
+        const char* shared = band_per_window ? "" : " (one band shared by every window)";
+        int32_t* s = bins->data() + 2 * r;
+        const host::BandCheck bc = host::band_to_bins(lo, hi, N, &s[0], &s[1]);
+        if (bc == host::kBandNoInterval)
+            return fail(c, RMX_E_INVAL, "band of window %ld%s: [%g, %g] is not an interval inside [-0.5, 0.5] cycles per sample",
+                        r, shared, lo, hi);
+        if (bc == host::kBandNoBin)
+            return fail(c, RMX_E_INVAL, "band of window %ld%s: [%g, %g] keeps no bin of the %ld-point transform", r, shared, lo,
+                        hi, 2L * N);
+        all_full = all_full && s[0] == -N && s[1] == N - 1;
+    }
+    *weighted = !(all_full && weighting == RMX_WEIGHT_NONE);
+    return RMX_OK;
+}
+
+// rmx_xcorr_batch_bounded: one interval per pair, shared or per window -- per GROUP of `integrate` windows in an
+// integrated call.  *bounded stays false when every interval is the full one and nothing is integrated: that is the
+// unbounded call, whatever route it takes (the whole-window generic kernels, which a bounded call avoids, included).
+static int check_bounded(rmx_ctx* c, int n_windows, int n_pairs, int integrate, const int32_t* lag_bounds,
+                         int bounds_per_window, long* rows, bool* bounded) {
+    const int nm1 = c->n_samples - 1;
+    *rows = bounds_per_window ? (long)(n_windows / integrate) * n_pairs : (long)n_pairs;
+    bool all_full = true;
+    for (long r = 0; r < *rows; ++r) {
+        const int lo = lag_bounds[2 * r], hi = lag_bounds[2 * r + 1];
+        bool full = false;
+        if (!host::lag_interval_ok(lo, hi, c->n_samples, &full))
+            return fail(c, RMX_E_INVAL, "lag_bounds of %s %ld, pair %ld: [%d, %d] is not an interval inside [%d, %d]",
+                        integrate > 1 ? "group" : "window", bounds_per_window ? r / n_pairs : -1L, r % n_pairs, lo, hi, -nm1, nm1);
+        all_full = all_full && full;
+    }
+    *bounded = !(all_full && integrate == 1);
+    return RMX_OK;
+}
+
+// What the four correlation entries do: check the arguments -- the integrated entry's own checks have run; here the
+// weighted entry's, then the bounded entry's, so an input with several bad arguments is refused for the same one whichever
+// entry it came through --, copy the bands (as signed bins) and the lag intervals into ctx-owned device buffers, describe
+// the call in an XcorrCall and dispatch it.  The plain call is integrate = 1, no band, no weighting, no bounds.
+static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
+                         const double* band_cps, int band_per_window, unsigned weighting, const int32_t* lag_bounds,
+                         int bounds_per_window, int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
+    std::vector<int32_t> bins;
+    bool weighted = false, bounded = false;
+    long bound_rows = 0;
+    int rc;
+    if (band_cps || weighting != RMX_WEIGHT_NONE) {
+        rc = check_weighted(c, n_windows, band_cps, band_per_window, weighting, &bins, &weighted);
+        if (rc != RMX_OK) return rc;
+        if (weighted && n_windows == 0) return RMX_OK;   // (the weighted entry does not look at the pairs of an empty batch)
+    }
+    rc = check_batch(c, n_windows, pairs, &n_pairs);
+    if (rc != RMX_OK) return rc;
+    if (n_windows == 0 || n_pairs == 0) return RMX_OK;
+    if (lag_bounds) {
+        rc = check_bounded(c, n_windows, n_pairs, integrate, lag_bounds, bounds_per_window, &bound_rows, &bounded);
+        if (rc != RMX_OK) return rc;
+    }
+    RMX_HIP(c, hipSetDevice(c->device));
+    XcorrCall call;
+    call.integ = integrate;
+    if (weighted) {
+        rc = stage_to_device(c, &c->band_stage, bins.data(), bins.size());
+        if (rc != RMX_OK) return rc;
+        call.wt = XWeight{c->band_stage.d, (band_cps && band_per_window) ? 2L : 0L, 0L, c->n_buoys,
+                          weighting == RMX_WEIGHT_PHAT ? 1 : 0, 1.0f};
+    }
+    if (bounded) {
+        rc = stage_to_device(c, &c->lb_stage, lag_bounds, (size_t)(2 * bound_rows));
+        if (rc != RMX_OK) return rc;
+        call.lb = LagBounds{c->lb_stage.d, bounds_per_window ? 2L * n_pairs : 0L, 0L, n_pairs};
+    }
+    return xcorr_dispatch(c, call, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+}
+
+int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                    int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    if (!c) return RMX_E_INVAL;
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0, lag_int, lag_frac, peak, flags);
+}
+
+// rmx_xcorr_batch with a lag interval per (window, pair).  Every interval the full one IS the plain call.
 int rmx_xcorr_batch_bounded(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                             const int32_t* lag_bounds, int bounds_per_window, int32_t* lag_int, float* lag_frac, float* peak,
                             unsigned flags) {
     if (!c) return RMX_E_INVAL;
-    if (!iq || !lag_int || !lag_frac || !peak || !lag_bounds) return fail(c, RMX_E_INVAL, "NULL buffer");
-    if (n_windows < 0 || n_windows > c->max_windows)
-        return fail(c, RMX_E_INVAL, "n_windows %d not in 0..max_windows=%d", n_windows, c->max_windows);
-    const int all_pairs = c->n_buoys * (c->n_buoys - 1) / 2;
-    if (!pairs) {
-        if (n_pairs != 0 && n_pairs != all_pairs)
-            return fail(c, RMX_E_INVAL, "pairs == NULL needs n_pairs == 0 or %d, got %d", all_pairs, n_pairs);
-        n_pairs = all_pairs;
-    }
-    if (n_pairs < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
-    if (n_windows == 0 || n_pairs == 0) return RMX_OK;
-    const int nm1 = c->n_samples - 1;
-    // (inside an integrated call the intervals are per GROUP of c->integ windows, and the integrating kernels always run:
-    // they carry the bounds whatever their values)
-    const long rows = bounds_per_window ? (long)(n_windows / c->integ) * n_pairs : (long)n_pairs;
-    bool all_full = true;
-    for (long r = 0; r < rows; ++r) {
-        const int lo = lag_bounds[2 * r], hi = lag_bounds[2 * r + 1];
-        if (lo < -nm1 || hi > nm1 || lo > hi)
-            return fail(c, RMX_E_INVAL, "lag_bounds of %s %ld, pair %ld: [%d, %d] is not an interval inside [%d, %d]",
-                        c->integ > 1 ? "group" : "window", bounds_per_window ? r / n_pairs : -1L, r % n_pairs, lo, hi, -nm1, nm1);
-        all_full = all_full && lo == -nm1 && hi == nm1;
-    }
-    // every interval the full one: that is rmx_xcorr_batch, whatever route it takes (the whole-window generic kernels,
-    // which a bounded call avoids, included)
-    if (all_full && c->integ == 1) return rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
-    RMX_HIP(c, hipSetDevice(c->device));
-    const size_t elems = (size_t)(2 * rows);
-    if (!c->lb_ev) RMX_HIP(c, hipEventCreateWithFlags(&c->lb_ev, hipEventDisableTiming));
-    RMX_HIP(c, hipEventSynchronize(c->lb_ev));   // the previous bounded call's copy out of the staging has finished
-    if (c->h_lb_elems < elems) {
-        if (c->h_lb) (void)hipHostFree(c->h_lb);
-        c->h_lb = nullptr; c->h_lb_elems = 0;
-        RMX_HIP(c, hipHostMalloc((void**)&c->h_lb, elems * sizeof(int32_t), hipHostMallocDefault));
-        c->h_lb_elems = elems;
-    }
-    if (c->d_lb_elems < elems) {
-        RMX_HIP(c, hipStreamSynchronize(c->stream));   // earlier kernels of this ctx may still read the old buffer
-        if (c->d_lb) (void)hipFree(c->d_lb);
-        c->scratch_bytes -= c->d_lb_elems * sizeof(int32_t);
-        c->d_lb = nullptr; c->d_lb_elems = 0;
-        RMX_HIP(c, hipMalloc((void**)&c->d_lb, elems * sizeof(int32_t)));
-        c->d_lb_elems = elems;
-        c->scratch_bytes += elems * sizeof(int32_t);
-    }
-    std::memcpy(c->h_lb, lag_bounds, elems * sizeof(int32_t));
-    // on the ctx stream: behind every earlier kernel that reads d_lb, in front of this call's kernels
-    RMX_HIP(c, hipMemcpyAsync(c->d_lb, c->h_lb, elems * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    RMX_HIP(c, hipEventRecord(c->lb_ev, c->stream));
-    c->lb = LagBounds{c->d_lb, bounds_per_window ? 2L * n_pairs : 0L, 0L, n_pairs};
-    const int rc = rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
-    c->lb = LagBounds{nullptr, 0, 0, 0};
-    return rc;
+    if (!lag_bounds) return fail(c, RMX_E_INVAL, "NULL buffer");
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, lag_bounds, bounds_per_window, lag_int,
+                         lag_frac, peak, flags);
 }
 
-// rmx_xcorr_batch(_bounded) on band-masked and / or PHAT-whitened spectra: the bands are validated and converted to signed
-// bins here, copied through the ctx's own pinned staging into a ctx-owned device buffer (as the lag bounds are), and the
-// call then dispatches with c->wt set: every route launches the weighted instantiation of its per-transform forward
-// kernel (xspec_weight.hpp) and the pair kernels as they are.  No band (or the full one) and no weighting IS the plain
-// call.
+// rmx_xcorr_batch(_bounded) on band-masked and / or PHAT-whitened spectra.  No band (or the full one) and no weighting IS
+// the bounded or the plain call.
 int rmx_xcorr_batch_weighted(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                              const double* band_cps, int band_per_window, unsigned weighting,
                              const int32_t* lag_bounds, int bounds_per_window,
                              int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
-    if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
-    if (weighting != RMX_WEIGHT_NONE && weighting != RMX_WEIGHT_PHAT)
-        return fail(c, RMX_E_INVAL, "unknown weighting %u (RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1)", weighting);
-    if (n_windows < 0 || n_windows > c->max_windows)
-        return fail(c, RMX_E_INVAL, "n_windows %d not in 0..max_windows=%d", n_windows, c->max_windows);
-    const int N = c->n_samples;
-    const long L = 2L * N;
-    const long rows = band_cps ? (band_per_window ? (long)n_windows : 1L) : 1L;
-    std::vector<int32_t> bins((size_t)(2 * rows));
-    bool all_full = true;
-    for (long r = 0; r < rows; ++r) {
-        double lo = -0.5, hi = 0.5;
-        if (band_cps) { lo = band_cps[2 * r]; hi = band_cps[2 * r + 1]; }
-        const char* shared = band_per_window ? "" : " (one band shared by every window)";
-        if (!std::isfinite(lo) || !std::isfinite(hi) || lo < -0.5 || hi > 0.5 || lo > hi)
-            return fail(c, RMX_E_INVAL, "band of window %ld%s: [%g, %g] is not an interval inside [-0.5, 0.5] cycles per sample",
-                        r, shared, lo, hi);
-        // signed bins s in [-N, N-1] with lo <= s / L <= hi (exact: L is a power of two)
-        const long s_lo = (long)std::ceil(lo * (double)L);
-        long s_hi = (long)std::floor(hi * (double)L);
-        if (s_hi > N - 1) s_hi = N - 1;
-        if (s_lo > s_hi)
-            return fail(c, RMX_E_INVAL, "band of window %ld%s: [%g, %g] keeps no bin of the %ld-point transform", r, shared, lo,
-                        hi, L);
-        bins[2 * r] = (int32_t)s_lo;
-        bins[2 * r + 1] = (int32_t)s_hi;
-        all_full = all_full && s_lo == -N && s_hi == N - 1;
-    }
-    // no band and no weighting: that is the plain call, whatever route it takes
-    if (all_full && weighting == RMX_WEIGHT_NONE) {
-        if (lag_bounds)
-            return rmx_xcorr_batch_bounded(c, iq, n_windows, pairs, n_pairs, lag_bounds, bounds_per_window, lag_int, lag_frac,
-                                           peak, flags);
-        return rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
-    }
-    if (n_windows == 0) return RMX_OK;
-    RMX_HIP(c, hipSetDevice(c->device));
-    const size_t elems = bins.size();
-    if (!c->band_ev) RMX_HIP(c, hipEventCreateWithFlags(&c->band_ev, hipEventDisableTiming));
-    RMX_HIP(c, hipEventSynchronize(c->band_ev));   // the previous weighted call's copy out of the staging has finished
-    if (c->h_band_elems < elems) {
-        if (c->h_band) (void)hipHostFree(c->h_band);
-        c->h_band = nullptr; c->h_band_elems = 0;
-        RMX_HIP(c, hipHostMalloc((void**)&c->h_band, elems * sizeof(int32_t), hipHostMallocDefault));
-        c->h_band_elems = elems;
-    }
-    if (c->d_band_elems < elems) {
-        RMX_HIP(c, hipStreamSynchronize(c->stream));   // earlier kernels of this ctx may still read the old buffer
-        if (c->d_band) (void)hipFree(c->d_band);
-        c->scratch_bytes -= c->d_band_elems * sizeof(int32_t);
-        c->d_band = nullptr; c->d_band_elems = 0;
-        RMX_HIP(c, hipMalloc((void**)&c->d_band, elems * sizeof(int32_t)));
-        c->d_band_elems = elems;
-        c->scratch_bytes += elems * sizeof(int32_t);
-    }
-    std::memcpy(c->h_band, bins.data(), elems * sizeof(int32_t));
-    // on the ctx stream: behind every earlier kernel that reads d_band, in front of this call's kernels
-    RMX_HIP(c, hipMemcpyAsync(c->d_band, c->h_band, elems * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    RMX_HIP(c, hipEventRecord(c->band_ev, c->stream));
-    c->wt = XWeight{c->d_band, (band_cps && band_per_window) ? 2L : 0L, 0L, c->n_buoys,
-                    weighting == RMX_WEIGHT_PHAT ? 1 : 0, 1.0f};
-    const int rc = lag_bounds ? rmx_xcorr_batch_bounded(c, iq, n_windows, pairs, n_pairs, lag_bounds, bounds_per_window,
-                                                        lag_int, lag_frac, peak, flags)
-                              : rmx_xcorr_batch(c, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
-    c->wt = XWeight{nullptr, 0, 0, 0, 0, 0.0f};
-    return rc;
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, band_cps, band_per_window, weighting, lag_bounds, bounds_per_window,
+                         lag_int, lag_frac, peak, flags);
 }
 
 // rmx_xcorr_batch_weighted with one peak search per group of `integrate` consecutive windows, on the lag-by-lag sum of the
-// windows' |c|^2 (integrate.hpp).  The arguments are checked here; the call then dispatches through the weighted and the
-// bounded entries with c->integ set: the bands stay per window, the bounds and the outputs are per group, every chunk
-// holds whole groups and the pair / peak kernels of the per-transform routes run their integrating instantiations, which
-// always carry bounds (an unbounded call passes the full interval).
+// windows' |c|^2 (integrate.hpp): the bands stay per window, the bounds and the outputs are per group.  integrate = 1 IS
+// the weighted call.
 int rmx_xcorr_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
                                const double* band_cps, int band_per_window, unsigned weighting,
                                const int32_t* lag_bounds, int bounds_per_group,
                                int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
-    if (integrate < 1) return fail(c, RMX_E_INVAL, "integrate = %d: at least one window per group", integrate);
-    if (n_windows <= 0 || n_windows % integrate != 0)
-        return fail(c, RMX_E_INVAL, "n_windows = %d is not a positive multiple of integrate = %d", n_windows, integrate);
-    if (integrate == 1)
-        return rmx_xcorr_batch_weighted(c, iq, n_windows, pairs, n_pairs, band_cps, band_per_window, weighting, lag_bounds,
-                                        bounds_per_group, lag_int, lag_frac, peak, flags);
     std::vector<int32_t> full;
-    if (!lag_bounds) {
-        int np = n_pairs;
-        if (!pairs) np = c->n_buoys * (c->n_buoys - 1) / 2;
-        if (np < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
-        full.resize((size_t)(2 * np));
-        for (int q = 0; q < np; ++q) {
-            full[2 * q] = -(c->n_samples - 1);
-            full[2 * q + 1] = c->n_samples - 1;
-        }
-        if (np == 0) full.resize(2);   // (never read: a call without pairs returns before the bounds)
+    const int rc = check_integrated(c, n_windows, pairs, n_pairs, integrate, lag_bounds != nullptr, &full);
+    if (rc != RMX_OK) return rc;
+    if (!full.empty()) {
         lag_bounds = full.data();
         bounds_per_group = 0;
     }
-    c->integ = integrate;
-    const int rc = rmx_xcorr_batch_weighted(c, iq, n_windows, pairs, n_pairs, band_cps, band_per_window, weighting, lag_bounds,
-                                            bounds_per_group, lag_int, lag_frac, peak, flags);
-    c->integ = 1;
-    return rc;
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, integrate, band_cps, band_per_window, weighting, lag_bounds,
+                         bounds_per_group, lag_int, lag_frac, peak, flags);
 }
 
 int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
@@ -2779,17 +2749,11 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
     if (!c) return RMX_E_INVAL;
     if (!iq || !dop_idx || !lag_int || !lag_frac || !peak || !doppler_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
     if (n_dopplers < 1 || n_dopplers > 4096) return fail(c, RMX_E_INVAL, "n_dopplers %d not in 1..4096", n_dopplers);
-    if (n_windows < 0 || n_windows > c->max_windows)
-        return fail(c, RMX_E_INVAL, "n_windows %d not in 0..max_windows=%d", n_windows, c->max_windows);
-    const int B = c->n_buoys, N = c->n_samples;
-    const int all_pairs = B * (B - 1) / 2;
-    if (!pairs) {
-        if (n_pairs != 0 && n_pairs != all_pairs)
-            return fail(c, RMX_E_INVAL, "pairs == NULL needs n_pairs == 0 or %d, got %d", all_pairs, n_pairs);
-        n_pairs = all_pairs;
-    }
-    if (n_pairs < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
+    int rc = check_batch(c, n_windows, pairs, &n_pairs);
+    if (rc != RMX_OK) return rc;
     if (n_windows == 0 || n_pairs == 0) return RMX_OK;
+    const int B = c->n_buoys, N = c->n_samples;
+    const XcorrCall call;   // the plain request: no bounds, no weighting, nothing integrated, whatever ran before
     RMX_HIP(c, hipSetDevice(c->device));
     // N = 4096, one chunk: all hypotheses in ONE forward launch and ONE pair launch (virtual window = hypothesis x
     // window) instead of three launches per hypothesis -- 21 hypotheses on one frequency group: 431 -> ~60 us
@@ -2801,18 +2765,14 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
         (void)split_cost4096(c, batch_bins ? n_windows * n_dopplers : n_windows, n_pairs, &q);
         c->pairs_per_block = q;
     }
-    int rc = build_plan(c, pairs, n_pairs);          // validates the pair list
+    rc = build_plan(c, pairs, n_pairs);              // validates the pair list
     if (rc != RMX_OK) return rc;
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
     const size_t in_bytes = (size_t)n_windows * B * N * (u8 ? 2 : 8);
     const void* d_iq = iq;
     if (!in_dev) {
-        if (c->d_in_bytes < in_bytes) {
-            if (c->d_in) (void)hipFree(c->d_in);
-            c->d_in = nullptr; c->d_in_bytes = 0;
-            RMX_HIP(c, hipMalloc(&c->d_in, in_bytes));
-            c->d_in_bytes = in_bytes;
-        }
+        rc = ensure_in(c, in_bytes);
+        if (rc != RMX_OK) return rc;
         RMX_HIP(c, hipMemcpyAsync(c->d_in, iq, in_bytes, hipMemcpyHostToDevice, c->stream));
         d_iq = c->d_in;
     }
@@ -2869,9 +2829,9 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
     }
     const float osc = out_scale4096();
     if (batch_bins) {
-        rc = fwd4096(c, d_iq, 0, n_windows, u8, nullptr);
-        if (rc == RMX_OK) rc = fwd4096(c, d_iq, 0, n_windows, u8, c->caf_rot, n_dopplers);
-        if (rc == RMX_OK) rc = pairs4096(c, 0, n_windows, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, osc, true, n_dopplers);
+        rc = fwd4096(c, call, d_iq, 0, n_windows, u8, nullptr);
+        if (rc == RMX_OK) rc = fwd4096(c, call, d_iq, 0, n_windows, u8, c->caf_rot, n_dopplers);
+        if (rc == RMX_OK) rc = pairs4096(c, call, 0, n_windows, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, osc, true, n_dopplers);
         if (rc == RMX_OK) rc = tm_begin(c);
         if (rc == RMX_OK) {
             hipLaunchKernelGGL(k_caf_select_all, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, c->stream, n_dopplers,
@@ -2882,13 +2842,13 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
     }
     for (int w0 = 0; !batch_bins && w0 < n_windows && rc == RMX_OK; w0 += chunk) {
         const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
-        rc = c->generic ? rmx::generic_forward(c, d_iq, w0, wc, u8, nullptr) : fwd4096(c, d_iq, w0, wc, u8, nullptr);
+        rc = c->generic ? rmx::generic_forward(c, call, d_iq, w0, wc, u8, nullptr) : fwd4096(c, call, d_iq, w0, wc, u8, nullptr);
         for (int d = 0; d < n_dopplers && rc == RMX_OK; ++d) {
             const float2* rot = c->caf_rot + (size_t)d * N;
-            rc = c->generic ? rmx::generic_forward(c, d_iq, w0, wc, u8, rot) : fwd4096(c, d_iq, w0, wc, u8, rot);
+            rc = c->generic ? rmx::generic_forward(c, call, d_iq, w0, wc, u8, rot) : fwd4096(c, call, d_iq, w0, wc, u8, rot);
             if (rc != RMX_OK) break;
-            rc = c->generic ? rmx::generic_pairs(c, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true)
-                            : pairs4096(c, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, osc, true);
+            rc = c->generic ? rmx::generic_pairs(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true)
+                            : pairs4096(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, osc, true);
             if (rc != RMX_OK) break;
             const long first = (long)w0 * n_pairs, cnt = (long)wc * n_pairs;
             rc = tm_begin(c);

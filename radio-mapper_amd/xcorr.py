@@ -302,6 +302,25 @@ class XcorrEngine:
         return np.ascontiguousarray(iq), flags
 
     # -- the hot path ----------------------------------------------------------------------------
+    def _xcorr(self, iq_p, W: int, pp, P: int, K: int, bd, band_pw: bool, whiten: bool, lb, per_window: bool,
+               lag_int_p, lag_frac_p, peak_p, flags: int):
+        """One correlation call through the C entry its arguments name: the integrated one for K > 1, else the weighted
+        one for a band or whitening, else the plain one without lag bounds and the bounded one with them.  iq and the
+        outputs are pointers (host or device, as `flags` says); bd and lb are checked host arrays or None."""
+        lib, head, out = self._lib, (self._ctx, iq_p, W, pp, P), (lag_int_p, lag_frac_p, peak_p, flags)
+        bounds = (None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window))
+        weight = (None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
+                  RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE)
+        if K > 1:
+            rc = lib.rmx_xcorr_batch_integrated(*head, K, *weight, *bounds, *out)
+        elif bd is not None or whiten:
+            rc = lib.rmx_xcorr_batch_weighted(*head, *weight, *bounds, *out)
+        elif lb is None:
+            rc = lib.rmx_xcorr_batch(*head, *out)
+        else:
+            rc = lib.rmx_xcorr_batch_bounded(*head, *bounds, *out)
+        self._check(rc)
+
     def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
                   whiten: bool = False, integrate: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Host arrays in, host arrays out.  iq: complex64 [W][B][N] (or uint8 [W][B][2N] raw
@@ -331,32 +350,8 @@ class XcorrEngine:
         peak = np.zeros((W // K, P), np.float32)
         if W == 0 or P == 0:
             return lag_int, lag_frac, peak
-        if K > 1:
-            self._check(self._lib.rmx_xcorr_batch_integrated(
-                self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P, K,
-                None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
-                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
-                None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window),
-                lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
-                peak.ctypes.data_as(C.c_void_p), flags))
-        elif bd is not None or whiten:
-            self._check(self._lib.rmx_xcorr_batch_weighted(
-                self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P,
-                None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
-                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
-                None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window),
-                lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
-                peak.ctypes.data_as(C.c_void_p), flags))
-        elif lb is None:
-            self._check(self._lib.rmx_xcorr_batch(
-                self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P,
-                lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
-                peak.ctypes.data_as(C.c_void_p), flags))
-        else:
-            self._check(self._lib.rmx_xcorr_batch_bounded(
-                self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P, lb.ctypes.data_as(C.c_void_p), int(per_window),
-                lag_int.ctypes.data_as(C.c_void_p), lag_frac.ctypes.data_as(C.c_void_p),
-                peak.ctypes.data_as(C.c_void_p), flags))
+        vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self._xcorr(vp(iq), W, pp, P, K, bd, band_pw, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags)
         return lag_int, lag_frac, peak
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None):
@@ -484,24 +479,5 @@ class XcorrEngine:
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
         lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
         bd, band_pw = check_band(band, n_windows)
-        if K > 1:
-            self._check(self._lib.rmx_xcorr_batch_integrated(
-                self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P, K, None if bd is None else bd.ctypes.data_as(C.c_void_p),
-                int(band_pw), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
-                None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window),
-                C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags))
-        elif bd is not None or whiten:
-            self._check(self._lib.rmx_xcorr_batch_weighted(
-                self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P, None if bd is None else bd.ctypes.data_as(C.c_void_p),
-                int(band_pw), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
-                None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window),
-                C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags))
-        elif lb is None:
-            self._check(self._lib.rmx_xcorr_batch(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
-                                                  C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
-                                                  C.c_void_p(peak_ptr), flags))
-        else:
-            self._check(self._lib.rmx_xcorr_batch_bounded(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
-                                                          lb.ctypes.data_as(C.c_void_p), int(per_window),
-                                                          C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
-                                                          C.c_void_p(peak_ptr), flags))
+        self._xcorr(C.c_void_p(iq_ptr), n_windows, pp, P, K, bd, band_pw, whiten, lb, per_window, C.c_void_p(lag_int_ptr),
+                    C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags)

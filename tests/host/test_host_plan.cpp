@@ -134,9 +134,41 @@ static void test_chunks() {
     CHECK(generic_chunk_windows(2, 32, 1, 32L << 30, 4096) == 1);
 }
 
+static void test_request_conversions() {
+    int32_t a = 77, b = 77;
+    for (int N : {16, 4096, 1 << 22}) {
+        const double L = 2.0 * N;
+        CHECK(band_to_bins(-0.5, 0.5, N, &a, &b) == kBandOk && a == -N && b == N - 1);            // the full band
+        CHECK(band_to_bins(0.25, 0.5, N, &a, &b) == kBandOk && a == N / 2 && b == N - 1);         // hi = 0.5 is bin N: clamped
+        CHECK(band_to_bins(0.5, 0.5, N, &a, &b) == kBandNoBin);                                   // ... and on its own keeps nothing
+        CHECK(band_to_bins(-0.5, -0.5, N, &a, &b) == kBandOk && a == -N && b == -N);
+        CHECK(band_to_bins(0.0, 0.0, N, &a, &b) == kBandOk && a == 0 && b == 0);                  // one bin, both ends included
+        CHECK(band_to_bins(3.0 / L, 5.0 / L, N, &a, &b) == kBandOk && a == 3 && b == 5);
+        CHECK(band_to_bins(-4.75 / L, 4.75 / L, N, &a, &b) == kBandOk && a == -4 && b == 4);      // inwards on both sides
+        a = b = 77;
+        CHECK(band_to_bins(1.25 / L, 1.75 / L, N, &a, &b) == kBandNoBin && a == 77 && b == 77);   // between two adjacent bins
+        CHECK(band_to_bins(-1.75 / L, -1.25 / L, N, &a, &b) == kBandNoBin);
+        CHECK(band_to_bins(0.1, 0.05, N, &a, &b) == kBandNoInterval);                             // lo > hi
+        CHECK(band_to_bins(-0.5000001, 0.0, N, &a, &b) == kBandNoInterval && band_to_bins(0.0, 0.5000001, N, &a, &b) == kBandNoInterval);
+        CHECK(band_to_bins(NAN, 0.1, N, &a, &b) == kBandNoInterval && band_to_bins(0.0, INFINITY, N, &a, &b) == kBandNoInterval);
+        CHECK(band_to_bins(-INFINITY, 0.0, N, &a, &b) == kBandNoInterval && a == 77 && b == 77);
+    }
+    bool full = false;
+    for (int N : {16, 4096, 1 << 22}) {
+        const int nm1 = N - 1;
+        CHECK(lag_interval_ok(-nm1, nm1, N, &full) && full);
+        CHECK(lag_interval_ok(-nm1 + 1, nm1, N, &full) && !full && lag_interval_ok(-nm1, nm1 - 1, N, &full) && !full);
+        CHECK(lag_interval_ok(5, 5, N, &full) && !full && lag_interval_ok(-nm1, -nm1, N, &full) && lag_interval_ok(nm1, nm1, N, &full));
+        CHECK(!lag_interval_ok(-nm1 - 1, 0, N, &full) && !lag_interval_ok(-N, nm1, N, &full));   // lo < -(N-1)
+        CHECK(!lag_interval_ok(0, N, N, &full) && !lag_interval_ok(3, 2, N, &full));
+        CHECK(!lag_interval_ok(INT_MIN, INT_MAX, N, &full) && !lag_interval_ok(INT_MAX, INT_MIN, N, &full));
+    }
+}
+
 int main() {
     test_options();
     test_create_args();
+    test_request_conversions();
     test_pair_plan();
     test_chunks();
     std::puts("host_plan: all checks passed");

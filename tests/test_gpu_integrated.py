@@ -327,3 +327,44 @@ def test_argument_errors_through_the_raw_abi(xc, opts):
     with xc.XcorrEngine(3, 256, 8) as eng:
         with pytest.raises(xc.RmxError):
             eng.correlate(np.zeros((8, 3, 256), np.complex64), integrate=4, lag_bounds=np.full((3, 2), 256, np.int32))
+
+
+@pytest.mark.parametrize("N", [256, 4096, 8192])
+def test_no_call_leaves_anything_behind_for_the_next(xc, N):
+    """A call's bounds, weighting and K are arguments of that call alone: after two refused calls (an integrated one whose
+    band and K are fine and whose lag interval is not; a weighted one whose second band is not) and a successful band + PHAT +
+    bounds + K = 2 call, the plain call and the Doppler search of the same engine return, bit for bit, what a fresh engine
+    returns that never saw the others.  N = 256: the small generic kernels; 4096: the per-transform kernels; 8192: four-step."""
+    B, W, P, K = 3, 4, 3, 2
+    lib = xc.load_library()
+    rng = np.random.default_rng(N)
+    iq, _ = rm.synth.make_windows(W, B, N, 10e6, seed=N)
+    dops = np.array([0.0, 1.0 / N])
+    band = np.array([-0.2, 0.3])
+    lb = _random_bounds(rng, (P,), N)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+
+    def raw(eng, entry, *args):
+        out = [np.zeros((W, P), t) for t in (np.int32, np.float32, np.float32)]
+        rc = entry(eng._ctx, vp(iq), W, None, P, *args, *[vp(o) for o in out], 0)
+        return rc, lib.rmx_last_error(eng._ctx).decode()
+
+    with xc.XcorrEngine(B, N, W) as fresh:
+        want_plain = fresh.correlate(iq)
+    with xc.XcorrEngine(B, N, W) as fresh:
+        want_caf = fresh.caf(iq, dops)
+    with xc.XcorrEngine(B, N, W) as eng:
+        bad_lb = lb.copy()
+        bad_lb[1] = (7, 6)
+        rc, msg = raw(eng, lib.rmx_xcorr_batch_integrated, K, vp(band), 0, 1, vp(bad_lb), 0)
+        assert rc == -1 and "lag_bounds of group" in msg and "pair 1" in msg, (rc, msg)   # RMX_E_INVAL; band and K accepted
+        bad_band = np.tile(band, (W, 1))
+        bad_band[1] = (0.2, 0.1)
+        rc, msg = raw(eng, lib.rmx_xcorr_batch_weighted, vp(bad_band), 1, 1, None, 0)
+        assert rc == -1 and "band of window 1" in msg, (rc, msg)
+        li, lf, pk = eng.correlate(iq, band=band, whiten=True, lag_bounds=lb, integrate=K)
+        _assert_parity(li, lf, pk, _ref(iq, K, band, True, lb), "band + PHAT + bounds + K = 2")
+        got_plain = eng.correlate(iq)
+        got_caf = eng.caf(iq, dops)
+    assert all(np.array_equal(u, v) for u, v in zip(got_plain, want_plain))
+    assert all(np.array_equal(u, v) for u, v in zip(got_caf, want_caf))
