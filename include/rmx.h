@@ -224,6 +224,48 @@ int rmx_xcorr_batch_integrated(rmx_ctx* ctx, const void* iq, int n_windows, cons
                                const int32_t* lag_bounds, int bounds_per_group,
                                int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
 
+/* Fine lag search: rmx_xcorr_batch_integrated with the sub-sample estimate taken from the band-limited interpolant of the
+ * SAME correlation on a grid of 1 / U samples around the integer peak, instead of a parabola through three integer lags.
+ * The peak of a band-limited correlation is a sinc (a Dirichlet kernel under PHAT), not a parabola: the three-point fit
+ * carries a deterministic bias of up to 0.15 samples (0.06 rms at bandwidth 0.8 fs, 0.25 on a white source) that neither
+ * averaging nor a longer window removes.  On the fine grid the same parabola spans 2 / U samples and the bias falls to
+ * 0.002 ... 0.015 samples rms at 10 dB.  A narrow band (0.2 fs or less) is noise-limited:
+ * refinement gains nothing there.
+ *   refine      U, one of 0, 2, 4, 8, 16; anything else is RMX_E_INVAL with the value in rmx_last_error (refused after the
+ *               integrate, weighting / band and lag_bounds checks, before anything is copied).
+ *   every other argument means exactly what it means for rmx_xcorr_batch_integrated.
+ * Definition, for one (window, pair) -- or one (group, pair) of an integrated call: lag0 is the integer lag the existing
+ *   rule finds, unchanged, searched in [lo, hi] (the full interval [-(N-1), N-1] without lag_bounds).  With Y_b the
+ *   (weighted) L = 2N point spectra exactly as rmx_xcorr_batch_weighted defines them:
+ *     P[s]  = Y_j[s mod L] * conj(Y_i[s mod L])         signed bins s = -N .. N-1
+ *     r(t)  = (1/L) * sum_s P[s] * exp(+2*pi*i*s*t/L)   real t; r at integer t is the existing r[t mod L]
+ *     f[u]  = |r(lag0 + u/U)|                           integer u in [-U, U] with lo <= lag0 + u/U <= hi
+ *             integrated call: f[u] = sqrt( sum over the group's windows, in window order, of |r_w(lag0 + u/U)|^2 )
+ *     u*    = the admitted u with the largest f; equal values: the smallest |u|, then the negative one
+ *             (so an all-zero window gives u* = 0)
+ *     d     = the S5 parabola on f[u*-1], f[u*], f[u*+1], in double from the float32 taps;
+ *             0 when a neighbour is not admitted, or when the denominator is 0
+ *     delta = (u* + d) / U
+ *     n     = +1 if delta > 0.5, -1 if delta < -0.5, else 0
+ *     lag_int  = lag0 + n        (inside [lo, hi] by construction)
+ *     lag_frac = (float)(delta - n)   in [-0.5, 0.5]
+ *     peak     = f[u*]
+ *   The fine rule never changes which integer peak was chosen; it relocates the estimate within +-1 sample of it.
+ * Parity against a float64 restatement (tests/refined_ref.py), where that restatement's coarse top-two margin exceeds
+ *   1e-5: lag_int + lag_frac within 1e-5 * max(|lag|, 1) or the flat-peak bound of the fine taps divided by U (the two
+ *   parts may split differently near delta = +-0.5); peak within 1e-5 relative + 1e-6 of the vector's maximum.
+ * refine == 0 IS rmx_xcorr_batch_integrated with the same arguments: bit-identical outputs, the same kernels.
+ * Otherwise both spectra of a pair must be in HBM, so the call runs the per-transform kernels at every batch size, exactly
+ *   as a weighted call does (a full band and no whitening when the caller gave none), and one more kernel, k_refine
+ *   (radio-mapper_amd/csrc/refine.hpp), runs behind each chunk's pair kernels: it reads lag0 from the outputs, sums the
+ *   cross-spectrum in storage order with exact rational phases, reduces in a fixed tree (two identical calls give
+ *   bit-identical outputs) and overwrites the three outputs in place.  rmx_caf_batch is not refined. */
+int rmx_xcorr_batch_refined(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                            int integrate,
+                            const double* band_cps, int band_per_window, unsigned weighting,
+                            const int32_t* lag_bounds, int bounds_per_group, int refine,
+                            int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
+
 /* Cross-ambiguity variant of the hot path (BASELINE configs[4]): for
  * every window and pair (i, j) the later buoy's window is de-rotated by each Doppler hypothesis,
  *     c_d = correlate(x[w][j] * exp(-2*pi*i*doppler_cps[d]*n), x[w][i], 'full', 'fft'),

@@ -481,8 +481,7 @@ __global__ __launch_bounds__(1024) void g_fwd_small(const void* __restrict__ iq,
         const XBand bd = xband_of(wt, item / wt.n_buoys);
         for (int n = tid; n < L; n += nthr) {
             const float2 e = x[lp(n)];
-            const int k = (int)(__brev((unsigned)n) >> (32 - logL));
-            out[n] = xweight_apply(wt, bd, k, L - 1, make_float2(e.x * scale, e.y * scale));
+            out[n] = xweight_apply(wt, bd, xbin_small(n, logL), L - 1, make_float2(e.x * scale, e.y * scale));
         }
         return;
     }
@@ -703,10 +702,10 @@ __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, c
             const XWeight wt = xweight_of(wt_pack...);
             if (live) {
                 const XBand bd = xband_of(wt, wt.w0 + (ridx >> row_bits) / wt.n_buoys);
-                const int k1 = brev(rib, row_bits), lmask = (int)(Ltot - 1);
+                const int k1 = xbin_rows_k1(rib, row_bits), lmask = (int)(Ltot - 1);
                 batched<8>(tid, R, tpr, [&](int n) -> float2 { return x[lp(n)]; },
                            [&](int n, float2 e) {
-                               row[n] = xweight_apply(wt, bd, k1 + (brev(n, logR) << row_bits), lmask,
+                               row[n] = xweight_apply(wt, bd, xbin_rows(k1, n, row_bits, logR), lmask,
                                                       make_float2(e.x * scale, e.y * scale));
                            });
             }

@@ -1,0 +1,172 @@
+// refine.hpp -- the fine lag search of rmx_xcorr_batch_refined (include/rmx.h): the band-limited interpolant of the
+// correlation on a grid of 1 / U samples around the integer peak, evaluated straight from the cross-spectrum.
+//
+// A refined call runs the per-transform kernels (its spectra are in HBM when the pair kernels have finished).  Per chunk
+// one k_refine launch follows the pair / final kernels, on the same stream, before the next chunk's forward kernels
+// overwrite the spectra.  Its work item is one output slot -- (window, pair), or (group, pair) of an integrated call,
+// walking the group's K windows in order -- on one workgroup of kRefThreads threads:
+//   - lag0 is read from lag_int[slot], which the pair kernels just wrote; the coarse rule is not touched;
+//   - the two stored spectra are walked in STORAGE order with 16-byte loads at the same positions; every stored
+//     position is mapped to its natural bin k by the map of the forward kernel that wrote it (xspec_weight.hpp), and
+//     P = X_j conj(X_i) is rotated to the 2 U + 1 lags lag0 + u / U: with s the signed index of k,
+//         base = ((k lag0) mod L) / L turns     (k = s mod L and lag0 is an integer)
+//         step = s / (U L) turns                (|s| <= N: exact in float32)
+//     both exact rationals with power-of-two denominators, reduced in integers and handed to sincospif as multiples of
+//     pi -- 2 pi s t / L is never formed in float.  P base is rotated outward from u = 0 by the step, U complex
+//     multiplies each way, and added into 2 U + 1 complex partial sums in registers (U is a template argument);
+//   - the partial sums are reduced in a fixed tree (xor shuffles within a wave, LDS across the waves, no atomics), so
+//     two identical calls give bit-identical outputs; thread u then adds |r_w(lag0 + u / U)|^2 into its float32 sum,
+//     window after window in window order;
+//   - thread 0 resolves u*, the parabola and the carry into lag_int in double and overwrites the three outputs.
+// The stored spectra carry the forward kernels' power-of-two scale; `scale` = (1 / L) / unit^2 is exact.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "lag_bounds.hpp"
+#include "xspec_weight.hpp"
+
+namespace rmx {
+
+constexpr int kRefThreads = 256;
+constexpr int kRefWaves = kRefThreads / 64;
+
+// which forward kernel stored the spectra
+enum RefLayout { kRefKfwd = 0, kRefSmall = 1, kRefRows = 2 };
+
+struct RefPair {
+    int i, j;
+};
+
+struct RefineArgs {
+    const float2* spec;     // the chunk's spectra, [item = window-in-chunk * n_buoys + buoy][L] in the layout's order
+    const RefPair* pairs;   // [n_pairs] in output order
+    LagBounds lb;           // b == nullptr: the full interval; else the call's intervals (w is the global window / group)
+    long first_out;         // global index of the chunk's first output row (window, or group of an integrated call)
+    int n_buoys, n_pairs;
+    int logL;               // L = 2 N
+    int row_bits;           // kRefRows: log2 of the rows per spectrum (L1); the row length is L >> row_bits
+    int k;                  // windows per output row (1, or K of an integrated call)
+    float scale;            // |sum| -> |r|: (1 / L) / (forward scale)^2, a power of two
+};
+
+// natural bin of stored complex position pos (0 .. L-1) of one spectrum
+template <int LAYOUT>
+__device__ __forceinline__ int ref_bin(int pos, int logL, int row_bits) {
+    if constexpr (LAYOUT == kRefKfwd) {
+        const int f = pos >> 1;   // float4 index j * kThreads + t: slots 2 j, 2 j + 1 of thread t
+        return xbin_kfwd(f & 1, (f & 511) >> 1) + kXbinKfwdSlot * (2 * (f >> 9) + (pos & 1));
+    } else if constexpr (LAYOUT == kRefSmall) {
+        return xbin_small(pos, logL);
+    } else {
+        const int logR = logL - row_bits;
+        return xbin_rows(xbin_rows_k1(pos >> logR, row_bits), pos & ((1 << logR) - 1), row_bits, logR);
+    }
+}
+
+template <int U, int LAYOUT>
+__global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __restrict__ lag_int, float* __restrict__ lag_frac,
+                                                        float* __restrict__ peak) {
+    constexpr int T = 2 * U + 1;
+    __shared__ float red[kRefWaves][2 * T];
+    __shared__ float taps[T];
+    const int tid = threadIdx.x;
+    const int gl = blockIdx.x / a.n_pairs, q = blockIdx.x % a.n_pairs;   // output row inside the chunk, pair
+    const long o = (a.first_out + gl) * (long)a.n_pairs + q;
+    const int L = 1 << a.logL, N = L >> 1;
+    const int lag0 = lag_int[o];
+    const RefPair pr = a.pairs[q];
+    const float inv_n = 1.0f / (float)N, inv_un = 1.0f / ((float)N * (float)U);   // powers of two
+    float fsum = 0.0f;   // thread u < T: sum over the windows of |r_w(lag0 + (u - U) / U)|^2, unscaled
+    for (int w = 0; w < a.k; ++w) {
+        const long wl = (long)gl * a.k + w;
+        const float4* xi = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.i) * L);
+        const float4* xj = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.j) * L);
+        float2 acc[T];
+#pragma unroll
+        for (int u = 0; u < T; ++u) acc[u] = make_float2(0.0f, 0.0f);
+        for (int f = tid; f < (L >> 1); f += kRefThreads) {
+            const float4 vi = xi[f], vj = xj[f];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const float2 bi = e ? make_float2(vi.z, vi.w) : make_float2(vi.x, vi.y);
+                const float2 bj = e ? make_float2(vj.z, vj.w) : make_float2(vj.x, vj.y);
+                const int k = ref_bin<LAYOUT>(2 * f + e, a.logL, a.row_bits);
+                const int s = k < N ? k : k - L;
+                const unsigned m = ((unsigned)k * (unsigned)lag0) & (unsigned)(L - 1);   // (k lag0) mod L: L divides 2^32
+                float bs, bc, ss, sc;
+                sincospif((float)m * inv_n, &bs, &bc);      // base: 2 m / L half turns
+                sincospif((float)s * inv_un, &ss, &sc);     // step: 2 s / (U L) half turns
+                const float2 p = make_float2(bj.x * bi.x + bj.y * bi.y, bj.y * bi.x - bj.x * bi.y);   // X_j conj(X_i)
+                const float2 c0 = make_float2(p.x * bc - p.y * bs, p.x * bs + p.y * bc);
+                acc[U].x += c0.x;
+                acc[U].y += c0.y;
+                float2 up = c0, dn = c0;
+#pragma unroll
+                for (int u = 1; u <= U; ++u) {
+                    up = make_float2(up.x * sc - up.y * ss, up.x * ss + up.y * sc);
+                    dn = make_float2(dn.x * sc + dn.y * ss, dn.y * sc - dn.x * ss);
+                    acc[U + u].x += up.x;
+                    acc[U + u].y += up.y;
+                    acc[U - u].x += dn.x;
+                    acc[U - u].y += dn.y;
+                }
+            }
+        }
+        // fixed tree: xor butterflies inside each wave, then the waves in order
+#pragma unroll
+        for (int u = 0; u < T; ++u) {
+            float re = acc[u].x, im = acc[u].y;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                re += __shfl_xor(re, d, 64);
+                im += __shfl_xor(im, d, 64);
+            }
+            if ((tid & 63) == 0) {
+                red[tid >> 6][2 * u] = re;
+                red[tid >> 6][2 * u + 1] = im;
+            }
+        }
+        __syncthreads();
+        if (tid < T) {
+            float re = red[0][2 * tid], im = red[0][2 * tid + 1];
+#pragma unroll
+            for (int v = 1; v < kRefWaves; ++v) {
+                re += red[v][2 * tid];
+                im += red[v][2 * tid + 1];
+            }
+            fsum += re * re + im * im;   // in window order
+        }
+        __syncthreads();
+    }
+    if (tid < T) taps[tid] = sqrtf(fsum) * a.scale;
+    __syncthreads();
+    if (tid != 0) return;
+    int lo = -(N - 1), hi = N - 1;
+    if (a.lb.b) {
+        const int* p = a.lb.b + (a.first_out + gl) * a.lb.wstride + 2 * q;
+        lo = p[0];
+        hi = p[1];
+    }
+    // admitted: lo <= lag0 + u / U <= hi, i.e. every u >= 0 (<= 0) unless lag0 sits on hi (lo)
+    const int umin = lag0 > lo ? -U : 0, umax = lag0 < hi ? U : 0;
+    int best = 0;
+    float fb = taps[U];
+    for (int d = 1; d <= U; ++d) {   // equal values: the smallest |u|, then the negative one
+        if (-d >= umin && taps[U - d] > fb) { fb = taps[U - d]; best = -d; }
+        if (d <= umax && taps[U + d] > fb) { fb = taps[U + d]; best = d; }
+    }
+    double dd = 0.0;
+    if (best - 1 >= umin && best + 1 <= umax) {
+        const double ta = (double)taps[U + best - 1], tb = (double)fb, tc = (double)taps[U + best + 1];
+        const double den = ta - 2.0 * tb + tc;
+        dd = den == 0.0 ? 0.0 : 0.5 * (ta - tc) / den;
+    }
+    const double delta = ((double)best + dd) / (double)U;
+    const int n = delta > 0.5 ? 1 : (delta < -0.5 ? -1 : 0);
+    lag_int[o] = lag0 + n;
+    lag_frac[o] = (float)(delta - (double)n);
+    peak[o] = fb;
+}
+
+}  // namespace rmx

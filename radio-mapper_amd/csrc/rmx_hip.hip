@@ -28,6 +28,7 @@
 #include "lag_bounds.hpp"
 #include "xspec_weight.hpp"
 #include "integrate.hpp"
+#include "refine.hpp"
 #include "fft_r16.hpp"
 #include "kwin.hpp"
 #include "fft_r8.hpp"
@@ -110,9 +111,9 @@ __global__ __launch_bounds__(kThreads, 4) void k_fwd(const void* __restrict__ iq
         const XWeight wt = xweight_of(wt_pack...);
         const XBand bd = xband_of(wt, item / wt.n_buoys);
         // role C (fft_r16.hpp): u = 16 k0 + k1, slot s = k2 -> natural bin 2 (k0 + 16 k1 + 256 s) + p
-        const int kb = 2 * ((u >> 4) + 16 * (u & 15)) + p;
+        const int kb = RMX_XBIN_KFWD(p, u);   // (xspec_weight.hpp: the map k_refine reads the spectra back with)
 #pragma unroll
-        for (int s = 0; s < 16; ++s) v[s] = xweight_apply(wt, bd, kb + 512 * s, kL - 1, v[s]);
+        for (int s = 0; s < 16; ++s) v[s] = xweight_apply(wt, bd, kb + kXbinKfwdSlot * s, kL - 1, v[s]);
     }
     float4* out = spec + (long)blockIdx.x * (8 * kThreads);
 #pragma unroll
@@ -833,16 +834,18 @@ __global__ __launch_bounds__(64) void k_solve(const double* __restrict__ buoy_xy
 static thread_local std::string g_create_error;
 
 // What ONE correlation call asks of the launch code beyond the plain call: built by the entry (xcorr_request), handed
-// down by const reference to every function that launches a kernel, never stored.  The default is the plain call;
-// rmx_caf_batch passes exactly that.
+// down by const reference to every function that launches a kernel, never stored.  The default is the plain, unrefined
+// call; rmx_caf_batch passes exactly that.
 struct XcorrCall {
     LagBounds lb{nullptr, 0, 0, 0};          // lag intervals on the device (rmx_xcorr_batch_bounded), or none
     XWeight wt{nullptr, 0, 0, 0, 0, 0.0f};   // bands as signed bins on the device + weighting (rmx_xcorr_batch_weighted)
     int integ = 1;                           // windows per group (rmx_xcorr_batch_integrated): the bounds and the outputs
                                              // are then per GROUP, the bands stay per window, a chunk holds whole groups
+    int refine = 0;                          // U of rmx_xcorr_batch_refined: k_refine behind every chunk's pair kernels, or 0
     bool bounded() const { return lb.b != nullptr; }         // the bounded instantiations of the peak-searching kernels
     bool integrated() const { return integ > 1; }            // the integrating instantiations of the pair kernels
-    bool weighted() const { return wt.band != nullptr || integ > 1; }   // only the per-transform routes can serve it
+    bool refined() const { return refine > 0; }              // k_refine reads both spectra of a pair from HBM
+    bool weighted() const { return wt.band != nullptr || integ > 1 || refine > 0; }   // only the per-transform routes can serve it
 };
 
 // a small host array that kernels read: staged through pinned memory into a ctx-owned device buffer (stage_to_device)
@@ -953,6 +956,8 @@ struct rmx_ctx {
     rmx::DevStage lb_stage, band_stage;
     const void* g_rows_fwd_wt_fn = nullptr;   // the weighted instantiation of g_rows_fwd_fn
     const void* g_cols_inv_int_fn = nullptr;   // the integrating instantiation of g_cols_inv_fn (integrate.hpp)
+    rmx::RefPair* rf_pairs = nullptr;          // k_refine's pair list (refine.hpp): the plan's pairs in output order
+    std::vector<int32_t> rf_pairs_plan;
     // cached pair plan
     std::vector<int32_t> plan_pairs;
     int plan_n_pairs = -1, plan_n_parts = 0, plan_ppb = 0;
@@ -1048,11 +1053,12 @@ enum TimeKind {
     kTkCafSelect = 12,   // k_caf_select / k_caf_select_all
     kTkFwd16k = 13,      // k16_fwd
     kTkPairs16k = 14,    // k16_pairs
-    kTkCount = 15
+    kTkRefine = 15,      // k_refine
+    kTkCount = 16
 };
 static const char* const kTimeKindName[kTkCount] = {
     "k_fwd", "k_win|k_pair", "g_cols_fwd", "g_rows_fwd", "g_rows_fused", "g_rows_anchor", "g_rows_inv", "g_cols_inv",
-    "g_final", "g_win_*", "g_fwd_small", "g_pair_small", "k_caf_select", "k16_fwd", "k16_pairs"};
+    "g_final", "g_win_*", "g_fwd_small", "g_pair_small", "k_caf_select", "k16_fwd", "k16_pairs", "k_refine"};
 static int tm_begin(rmx_ctx* c) {
     if (!c->timing) return RMX_OK;
     const int rc = ensure_events(c, c->ev_used + 2);
@@ -1091,6 +1097,50 @@ static int build_plan(rmx_ctx* c, const int32_t* pairs, int n_pairs) {
     c->plan_n_pairs = n_pairs;
     c->plan_n_parts = pp.n_parts;
     c->plan_ppb = c->pairs_per_block;
+    return RMX_OK;
+}
+
+// The fine lag search of a refined call (refine.hpp) on the chunk the pair kernels have just finished: windows
+// [w0, w0 + wc), whose spectra `spec` still holds in the order `layout` names.  One workgroup per output slot of the
+// chunk; lag_int is read (the coarse lag0) and all three outputs are overwritten in place.
+static int refine_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const void* spec, int logL, int row_bits, int unit_log2,
+                        int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak) {
+    if (c->rf_pairs_plan != c->plan_pairs || !c->rf_pairs) {
+        RMX_HIP(c, hipStreamSynchronize(c->stream));   // an earlier call's k_refine may still read the old list
+        if (c->rf_pairs) { (void)hipFree(c->rf_pairs); c->rf_pairs = nullptr; }
+        c->rf_pairs_plan.clear();
+        RMX_HIP(c, hipMalloc((void**)&c->rf_pairs, sizeof(RefPair) * (size_t)n_pairs));
+        RMX_HIP(c, hipMemcpy(c->rf_pairs, c->plan_pairs.data(), sizeof(RefPair) * (size_t)n_pairs, hipMemcpyHostToDevice));
+        c->rf_pairs_plan = c->plan_pairs;
+    }
+    RefineArgs a;
+    a.spec = static_cast<const float2*>(spec);
+    a.pairs = c->rf_pairs;
+    a.lb = call.lb;
+    a.first_out = w0 / call.integ;
+    a.n_buoys = c->n_buoys;
+    a.n_pairs = n_pairs;
+    a.logL = logL;
+    a.row_bits = row_bits;
+    a.k = call.integ;
+    a.scale = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the two stored forward scales 2^unit_log2
+    const unsigned grid = (unsigned)(wc / call.integ * n_pairs);
+    RMX_TM_BEGIN(c);
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefThreads), 0, c->stream, a, d_lag, d_frac, d_peak); };
+    auto with_u = [&](auto lay) {
+        constexpr int LAY = decltype(lay)::value;
+        switch (call.refine) {
+            case 2: launch(k_refine<2, LAY>); break;
+            case 4: launch(k_refine<4, LAY>); break;
+            case 8: launch(k_refine<8, LAY>); break;
+            default: launch(k_refine<16, LAY>); break;
+        }
+    };
+    if (layout == kRefKfwd) with_u(std::integral_constant<int, kRefKfwd>{});
+    else if (layout == kRefSmall) with_u(std::integral_constant<int, kRefSmall>{});
+    else with_u(std::integral_constant<int, kRefRows>{});
+    RMX_HIP(c, hipGetLastError());
+    RMX_TM_END(c, kTkRefine);
     return RMX_OK;
 }
 
@@ -1942,6 +1992,12 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, in
         if (rc) return rc;
         rc = generic_pairs(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
         if (rc) return rc;
+        if (call.refined()) {   // (a refined call is weighted(): never fused, g_spec holds this chunk's spectra, scaled 2^-(logL / 2))
+            const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
+            rc = refine_chunk(c, call, small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1,
+                              -(c->g_logL / 2), w0, wc, n_pairs, d_lag, d_frac, d_peak);
+            if (rc) return rc;
+        }
     }
     return RMX_OK;
 }
@@ -2103,6 +2159,7 @@ void rmx_destroy(rmx_ctx* c) {
     if (c->d_in) (void)hipFree(c->d_in);
     if (c->d_lag) (void)hipFree(c->d_lag);            // (d_frac / d_peak point into the same block)
     if (c->h_out) (void)hipHostFree(c->h_out);
+    if (c->rf_pairs) (void)hipFree(c->rf_pairs);
     for (rmx::DevStage* s : {&c->lb_stage, &c->band_stage}) {
         if (s->d) (void)hipFree(s->d);
         if (s->h) (void)hipHostFree(s->h);
@@ -2276,6 +2333,7 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
     RMX_TM_END(c, kTkPair4096);
     return RMX_OK;
 }
+static_assert(kL == 1 << 13, "refine_chunk is handed log2 kL");
 static float out_scale4096() {
     // power-of-two scaling: the TW1 table carries 2^-6, so the spectra carry 2^-6, the product 2^-12 and
     // the inverse transform (which uses the table once more) 2^-18; the taps get the remaining factor
@@ -2583,6 +2641,10 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& call, const void* iq, int
         if (rc != RMX_OK) return rc;
         rc = pairs4096(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, out_scale, false);
         if (rc != RMX_OK) return rc;
+        if (call.refined()) {   // (a refined call is weighted(): this branch, d_spec holds the chunk's spectra, scaled 2^-6)
+            rc = refine_chunk(c, call, kRefKfwd, c->d_spec, 13 /* log2 kL */, 0, -kTw1ScaleLog2, w0, wc, n_pairs, d_lag, d_frac, d_peak);
+            if (rc != RMX_OK) return rc;
+        }
     }
     if (!out_dev) return fetch_out(c, out_elems, lag_int, lag_frac, peak);
     return RMX_OK;
@@ -2662,7 +2724,7 @@ static int check_bounded(rmx_ctx* c, int n_windows, int n_pairs, int integrate, 
 // the call in an XcorrCall and dispatch it.  The plain call is integrate = 1, no band, no weighting, no bounds.
 static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
                          const double* band_cps, int band_per_window, unsigned weighting, const int32_t* lag_bounds,
-                         int bounds_per_window, int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+                         int bounds_per_window, int refine, int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
     std::vector<int32_t> bins;
     bool weighted = false, bounded = false;
@@ -2680,9 +2742,13 @@ static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_
         rc = check_bounded(c, n_windows, n_pairs, integrate, lag_bounds, bounds_per_window, &bound_rows, &bounded);
         if (rc != RMX_OK) return rc;
     }
+    // rmx_xcorr_batch_refined: U, refused after the other three and before anything is staged
+    if (refine != 0 && refine != 2 && refine != 4 && refine != 8 && refine != 16)
+        return fail(c, RMX_E_INVAL, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", refine);
     RMX_HIP(c, hipSetDevice(c->device));
     XcorrCall call;
     call.integ = integrate;
+    call.refine = refine;
     if (weighted) {
         rc = stage_to_device(c, &c->band_stage, bins.data(), bins.size());
         if (rc != RMX_OK) return rc;
@@ -2700,7 +2766,7 @@ static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_
 int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                     int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0, lag_int, lag_frac, peak, flags);
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0, 0, lag_int, lag_frac, peak, flags);
 }
 
 // rmx_xcorr_batch with a lag interval per (window, pair).  Every interval the full one IS the plain call.
@@ -2709,7 +2775,7 @@ int rmx_xcorr_batch_bounded(rmx_ctx* c, const void* iq, int n_windows, const int
                             unsigned flags) {
     if (!c) return RMX_E_INVAL;
     if (!lag_bounds) return fail(c, RMX_E_INVAL, "NULL buffer");
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, lag_bounds, bounds_per_window, lag_int,
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, lag_bounds, bounds_per_window, 0, lag_int,
                          lag_frac, peak, flags);
 }
 
@@ -2721,7 +2787,7 @@ int rmx_xcorr_batch_weighted(rmx_ctx* c, const void* iq, int n_windows, const in
                              int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
     return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, band_cps, band_per_window, weighting, lag_bounds, bounds_per_window,
-                         lag_int, lag_frac, peak, flags);
+                         0, lag_int, lag_frac, peak, flags);
 }
 
 // rmx_xcorr_batch_weighted with one peak search per group of `integrate` consecutive windows, on the lag-by-lag sum of the
@@ -2731,6 +2797,16 @@ int rmx_xcorr_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const 
                                const double* band_cps, int band_per_window, unsigned weighting,
                                const int32_t* lag_bounds, int bounds_per_group,
                                int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    return rmx_xcorr_batch_refined(c, iq, n_windows, pairs, n_pairs, integrate, band_cps, band_per_window, weighting, lag_bounds,
+                                   bounds_per_group, 0, lag_int, lag_frac, peak, flags);
+}
+
+// rmx_xcorr_batch_integrated with the fine lag search of refine.hpp behind the coarse one: refine = U in {2, 4, 8, 16}
+// relocates each estimate within +-1 sample of the integer peak the coarse rule chose.  refine = 0 IS the integrated call.
+int rmx_xcorr_batch_refined(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
+                            const double* band_cps, int band_per_window, unsigned weighting,
+                            const int32_t* lag_bounds, int bounds_per_group, int refine,
+                            int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
     std::vector<int32_t> full;
     const int rc = check_integrated(c, n_windows, pairs, n_pairs, integrate, lag_bounds != nullptr, &full);
@@ -2740,7 +2816,7 @@ int rmx_xcorr_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const 
         bounds_per_group = 0;
     }
     return xcorr_request(c, iq, n_windows, pairs, n_pairs, integrate, band_cps, band_per_window, weighting, lag_bounds,
-                         bounds_per_group, lag_int, lag_frac, peak, flags);
+                         bounds_per_group, refine, lag_int, lag_frac, peak, flags);
 }
 
 int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,

@@ -34,6 +34,25 @@ __device__ __forceinline__ XWeight xweight_of(WT... wt) {
     }
 }
 
+// ---- where each per-transform forward kernel stores natural bin k of its L-point spectrum ---------------------------
+// (the weighted store epilogues and k_refine, refine.hpp, which walks the stored spectra in storage order, share these)
+// k_fwd, role C (fft_r16.hpp): spec[item][j][t] float4 = slots (2 j, 2 j + 1) of thread t; with p = t & 1 and
+// u = t >> 1 = 16 k0 + k1, slot s = k2 holds natural bin 2 (k0 + 16 k1 + 256 s) + p = xbin_kfwd(p, u) + kXbinKfwdSlot * s
+// (k_fwd expands the expression in place: through an inlined function hipcc allocated the weighted k_fwd's registers and
+// ordered its address arithmetic differently -- the same instructions otherwise --, and tools/isa_diff.py holds the existing
+// kernels to their bodies; xbin_kfwd is the same expansion for every other caller)
+constexpr int kXbinKfwdSlot = 512;
+#define RMX_XBIN_KFWD(p, u) (2 * (((u) >> 4) + 16 * ((u) & 15)) + (p))
+__device__ __forceinline__ int xbin_kfwd(int p, int u) { return RMX_XBIN_KFWD(p, u); }
+// g_fwd_small: spec[item][n], position n holds natural bin bitrev(n) (the DIF order of the LDS transform)
+__device__ __forceinline__ int xbin_small(int n, int logL) { return (int)(__brev((unsigned)n) >> (32 - logL)); }
+// forward g_rows (four-step): spec[item][row][n] holds natural bin k1 + L1 k2, k1 = bitrev(row index) over row_bits,
+// k2 = bitrev(n) over logR (the column pass's and the row pass's DIF orders)
+__device__ __forceinline__ int xbin_rows_k1(int row, int row_bits) { return (int)(__brev((unsigned)row) >> (32 - row_bits)); }
+__device__ __forceinline__ int xbin_rows(int k1, int n, int row_bits, int logR) {
+    return k1 + ((int)(__brev((unsigned)n) >> (32 - logR)) << row_bits);
+}
+
 // the kept set of one window as a test on the natural bin k: (k - s_lo) mod L <= s_hi - s_lo
 struct XBand {
     int lo;         // s_lo

@@ -21,7 +21,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .shard import window_shard
-from .xcorr import check_band, check_integrate, check_lag_bounds
+from .xcorr import check_band, check_integrate, check_lag_bounds, check_refine
 
 
 class MultiXcorrEngine:
@@ -120,19 +120,21 @@ class MultiXcorrEngine:
 
     # -- the hot path --------------------------------------------------------------------------------
     def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
-                  whiten: bool = False, integrate: int = 1):
+                  whiten: bool = False, integrate: int = 1, refine: int = 0):
         """iq: complex64 [W][B][N] or uint8 [W][B][2N] -> (lag_int [W][P], lag_frac [W][P], peak [W][P]).
         lag_bounds: None, [P][2] (every block gets it whole) or [W][P][2] (each block gets its own windows' rows).
         band: None, [2] (every block gets it whole) or [W][2] (each block its own windows' rows); whiten: PHAT.
         integrate: K windows per group (XcorrEngine.correlate): whole groups are sharded over the devices, the results and
-        per-group lag_bounds are [W // K][.]; a block larger than its engine holds runs as several calls of whole groups."""
+        per-group lag_bounds are [W // K][.]; a block larger than its engine holds runs as several calls of whole groups.
+        refine: U of the fine lag search (XcorrEngine.correlate), handed to every block's call."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
         K = check_integrate(integrate, iq.shape[0])
+        U = check_refine(refine)
         if K > 1:
-            return self._correlate_integrated(iq, pairs, lag_bounds, band, whiten, K, P)
+            return self._correlate_integrated(iq, pairs, lag_bounds, band, whiten, K, P, U)
         lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
 
         bd, band_pw = check_band(band, iq.shape[0])
@@ -141,6 +143,9 @@ class MultiXcorrEngine:
             return lb[s:s + c] if per_window else lb
 
         def block_call(eng, s, c):
+            if U > 0:
+                return eng.correlate(iq[s:s + c], pairs, None if lb is None else block_bounds(s, c),
+                                     band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, refine=U)
             if bd is not None or whiten:
                 return eng.correlate(iq[s:s + c], pairs, None if lb is None else block_bounds(s, c),
                                      band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten)
@@ -149,11 +154,13 @@ class MultiXcorrEngine:
             return eng.correlate(iq[s:s + c], pairs)
         return self._run(iq.shape[0], block_call, 3, (np.int32, np.float32, np.float32), P)
 
-    def _correlate_integrated(self, iq, pairs, lag_bounds, band, whiten, K, P):
+    def _correlate_integrated(self, iq, pairs, lag_bounds, band, whiten, K, P, U=0):
         W = iq.shape[0]
         G = W // K
         lb, per_group = check_lag_bounds(lag_bounds, G, P)
         bd, band_pw = check_band(band, W)
+
+        kw = {"refine": U} if U > 0 else {}
 
         def block_call(eng, gs, gc):
             # the engines are sized for an even split of the WINDOWS; a block of whole groups may be a little larger
@@ -167,7 +174,7 @@ class MultiXcorrEngine:
                 parts.append(eng.correlate(iq[g0 * K:g1 * K], pairs,
                                            None if lb is None else (lb[g0:g1] if per_group else lb),
                                            band=None if bd is None else (bd[g0 * K:g1 * K] if band_pw else bd),
-                                           whiten=whiten, integrate=K))
+                                           whiten=whiten, integrate=K, **kw))
             return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
         return self._run(W, block_call, 3, (np.int32, np.float32, np.float32), P, n_rows=G)
 

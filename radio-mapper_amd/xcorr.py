@@ -77,6 +77,8 @@ def load_library():
     lib.rmx_xcorr_batch_weighted.restype = ci
     lib.rmx_xcorr_batch_integrated.argtypes = [vp, vp, ci, vp, ci, ci, vp, ci, cu, vp, ci, vp, vp, vp, cu]
     lib.rmx_xcorr_batch_integrated.restype = ci
+    lib.rmx_xcorr_batch_refined.argtypes = [vp, vp, ci, vp, ci, ci, vp, ci, cu, vp, ci, ci, vp, vp, vp, cu]
+    lib.rmx_xcorr_batch_refined.restype = ci
     lib.rmx_caf_batch.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, cu]
     lib.rmx_caf_batch.restype = ci
     lib.rmx_solve_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, ci, ci, vp, vp, vp, cu]
@@ -157,8 +159,22 @@ def check_integrate(integrate, n_windows: int) -> int:
     return k
 
 
+REFINE_VALUES = (0, 2, 4, 8, 16)
+
+
+def check_refine(refine) -> int:
+    """refine as correlate() takes it -> U, the fine lag grid of 1 / U samples around the integer peak
+    (rmx_xcorr_batch_refined): one of 0 (none), 2, 4, 8, 16; raises ValueError before any call into the library."""
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)):
+        raise ValueError(f"refine must be an integer, got {refine!r}")
+    u = int(refine)
+    if u not in REFINE_VALUES:
+        raise ValueError(f"refine must be one of {REFINE_VALUES}, got {u}")
+    return u
+
+
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_integrated", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -303,15 +319,18 @@ class XcorrEngine:
 
     # -- the hot path ----------------------------------------------------------------------------
     def _xcorr(self, iq_p, W: int, pp, P: int, K: int, bd, band_pw: bool, whiten: bool, lb, per_window: bool,
-               lag_int_p, lag_frac_p, peak_p, flags: int):
-        """One correlation call through the C entry its arguments name: the integrated one for K > 1, else the weighted
+               lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0):
+        """One correlation call through the C entry its arguments name: the refined one for U > 0, else the integrated
+        one for K > 1, else the weighted
         one for a band or whitening, else the plain one without lag bounds and the bounded one with them.  iq and the
         outputs are pointers (host or device, as `flags` says); bd and lb are checked host arrays or None."""
         lib, head, out = self._lib, (self._ctx, iq_p, W, pp, P), (lag_int_p, lag_frac_p, peak_p, flags)
         bounds = (None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window))
         weight = (None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
                   RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE)
-        if K > 1:
+        if U > 0:
+            rc = lib.rmx_xcorr_batch_refined(*head, K, *weight, *bounds, U, *out)
+        elif K > 1:
             rc = lib.rmx_xcorr_batch_integrated(*head, K, *weight, *bounds, *out)
         elif bd is not None or whiten:
             rc = lib.rmx_xcorr_batch_weighted(*head, *weight, *bounds, *out)
@@ -322,7 +341,7 @@ class XcorrEngine:
         self._check(rc)
 
     def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
-                  whiten: bool = False, integrate: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                  whiten: bool = False, integrate: int = 1, refine: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Host arrays in, host arrays out.  iq: complex64 [W][B][N] (or uint8 [W][B][2N] raw
         rtl_sdr I,Q).  Returns (lag_int int32 [W][P], lag_frac float32 [W][P], peak float32 [W][P]);
         lag = lag_int + lag_frac = delay(j) - delay(i) in samples.
@@ -332,10 +351,14 @@ class XcorrEngine:
         cross-spectrum; whiten: PHAT, every bin at unit magnitude (rmx_xcorr_batch_weighted).
         integrate: K >= 1; every K consecutive windows form a group with ONE peak search on the sum of the windows'
         squared magnitudes (rmx_xcorr_batch_integrated).  W must be a multiple of K; the results are [W // K][P],
-        lag_bounds [P][2] or [W // K][P][2]; band stays per window."""
+        lag_bounds [P][2] or [W // K][P][2]; band stays per window.
+        refine: U in (0, 2, 4, 8, 16); U > 0 takes the sub-sample estimate from the band-limited interpolant of the
+        correlation on a grid of 1 / U samples around the integer peak instead of the three-point parabola
+        (rmx_xcorr_batch_refined): the same integer peak, the estimate relocated within +-1 sample of it."""
         iq, flags = self._check_iq(iq)
         W = iq.shape[0]
         K = check_integrate(integrate, W)
+        U = check_refine(refine)
         if pairs is not None:
             pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
             P = pairs.shape[0]
@@ -351,7 +374,7 @@ class XcorrEngine:
         if W == 0 or P == 0:
             return lag_int, lag_frac, peak
         vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
-        self._xcorr(vp(iq), W, pp, P, K, bd, band_pw, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags)
+        self._xcorr(vp(iq), W, pp, P, K, bd, band_pw, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags, U)
         return lag_int, lag_frac, peak
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None):
@@ -464,11 +487,12 @@ class XcorrEngine:
 
     def correlate_device(self, iq_ptr: int, n_windows: int, lag_int_ptr: int, lag_frac_ptr: int,
                          peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
-                         band=None, whiten: bool = False, integrate: int = 1):
+                         band=None, whiten: bool = False, integrate: int = 1, refine: int = 0):
         """Device pointers in and out (inputs already resident in HBM); asynchronous on the ctx
-        stream.  lag_bounds, band, whiten, integrate: as for correlate() (host arrays; the library keeps its own copies;
-        with integrate = K the three outputs are [n_windows // K][P])."""
+        stream.  lag_bounds, band, whiten, integrate, refine: as for correlate() (host arrays; the library keeps its own
+        copies; with integrate = K the three outputs are [n_windows // K][P])."""
         K = check_integrate(integrate, n_windows)
+        U = check_refine(refine)
         if pairs is not None:
             pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
             P = pairs.shape[0]
@@ -480,4 +504,4 @@ class XcorrEngine:
         lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
         bd, band_pw = check_band(band, n_windows)
         self._xcorr(C.c_void_p(iq_ptr), n_windows, pp, P, K, bd, band_pw, whiten, lb, per_window, C.c_void_p(lag_int_ptr),
-                    C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags)
+                    C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags, U)
