@@ -266,6 +266,61 @@ int rmx_xcorr_batch_refined(rmx_ctx* ctx, const void* iq, int n_windows, const i
                             const int32_t* lag_bounds, int bounds_per_group, int refine,
                             int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
 
+/* the four values of one output slot of rmx_xcorr_batch_quality(): quality[slot][RMX_Q_...] */
+enum { RMX_Q_COHERENCE = 0, RMX_Q_PSR = 1, RMX_Q_RMS_BW = 2, RMX_Q_NEFF = 3 };
+
+/* Qualified lags: rmx_xcorr_batch_refined with four figures per output slot that say whether its lag can be trusted.
+ * `peak` is in scipy's scaling -- it grows with the window length and the input power, so it cannot be thresholded, and
+ * a noise-only window yields a lag exactly as a 20 dB emitter does.  The figures below are normalised.
+ *   quality     float32 [rows][n_pairs][4], rows = n_windows, or the G groups of an integrated call; a device pointer
+ *               with RMX_OUT_DEVICE, like the other three outputs.  NULL: the call IS rmx_xcorr_batch_refined.  It must
+ *               not overlap lag_int, lag_frac or peak (RMX_E_INVAL naming the array; refused after the integrate,
+ *               weighting / band, lag_bounds and refine checks, before anything is copied).
+ *   every other argument means exactly what it means for rmx_xcorr_batch_refined.
+ * Definition, for one output slot -- (window, pair), or (group g, pair) of an integrated call with its K windows w in
+ *   window order -- and pair (i, j); Y_b,w the (weighted) L = 2N point spectra exactly as rmx_xcorr_batch_weighted
+ *   defines them, s the signed bin of k (s = k, or k - L for k >= N):
+ *     A_w = sum_k |Y_i,w[k]|^2            B_w = sum_k |Y_j,w[k]|^2
+ *     C_w = sum_k |Y_i,w[k]|^2 |Y_j,w[k]|^2          (= sum |P|^2,  P = Y_j conj(Y_i))
+ *     D_w = sum_k |Y_i,w[k]| |Y_j,w[k]|              (= sum |P|)
+ *     F_w = sum_k (s / L)^2 |Y_i,w[k]| |Y_j,w[k]|
+ *     EE  = sum_w (A_w / L) (B_w / L)     the energy product of the two windows (time domain, by Parseval)
+ *     Et  = sum_w C_w / L                 = sum_w sum over ALL L circular lags of |r_w|^2 (Parseval on r = IFFT_L(P))
+ *     p0  = the COARSE rule's peak of this slot (m[k*]; sqrt(s[k*]) when integrated), before any refinement
+ *   quality[RMX_Q_COHERENCE] = min(p0 / sqrt(EE), 1); 0 when EE = 0.  The normalised correlation coefficient in [0, 1]
+ *       (Cauchy-Schwarz per window); 1 for identical windows; under PHAT p0 L / (kept bins).
+ *   quality[RMX_Q_PSR]       = p0^2 (L - 1) / (Et - p0^2); +inf when the denominator <= 0 < p0; 0 when p0 = 0.  The peak
+ *       power over the mean power of all OTHER circular lags.  For a white noise-only pair each |r[k]|^2 / floor is
+ *       Exp(1) -- Gamma(K) / K when K windows are integrated --, but the zero-padded linear correlation has a triangular
+ *       variance, up to 2 x the mean floor near lag 0: a threshold for a false-alarm rate must allow for that factor
+ *       (xcorr.psr_threshold does).
+ *   quality[RMX_Q_RMS_BW]    = sqrt(sum_w F_w / sum_w D_w) cycles per sample; 0 when sum D = 0.  The rms bandwidth of the
+ *       cross-spectrum, which sets the peak's curvature.
+ *   quality[RMX_Q_NEFF]      = (sum_w D_w)^2 / sum_w C_w; 0 when sum C = 0.  The participation count of bins (a
+ *       time-bandwidth product): L under full-band PHAT, K L when K windows are integrated.
+ *   A dead receiver (all zeros) gives four zeros, never NaN.
+ * The sums run over the stored float32 spectra in storage order, five float32 partial sums per thread and window,
+ *   reduced in a fixed tree and added over the windows in window order: two identical calls give bit-identical outputs.
+ * Parity against a float64 restatement (tests/quality_ref.py): coherence, rms_bw and n_eff within 1e-4 relative;
+ *   psr compared as Et / p0^2 = (L - 1) / psr + 1 within 1e-4 relative (the difference Et - p0^2 cancels on a clean
+ *   signal).
+ * quality == NULL IS rmx_xcorr_batch_refined with the same arguments: bit-identical outputs, the same kernels.
+ * lag_int, lag_frac and peak of a quality call are bit-identical to the same call without quality, whatever route that
+ *   call takes; k_quality (radio-mapper_amd/csrc/quality.hpp) writes nothing but quality.  Both spectra of a pair must be
+ *   in HBM for it, so:
+ *   - a call with a band, a weighting, integration or refinement runs the per-transform kernels at every batch size
+ *     anyway, and k_quality runs behind each chunk's pair kernels and in front of k_refine, which overwrites peak;
+ *   - a call with none of those first runs exactly what the call without quality runs (the whole-window kernels k_win,
+ *     k_win8kl, k16_*, g_win_*, g_rows_fused included, which keep their spectra to themselves and round lag_frac and
+ *     peak differently in the last bits than the per-transform kernels), then, chunk by chunk, the per-transform
+ *     forward kernels and k_quality: one more forward pass, and the outputs stay those of the call without quality.
+ *   rmx_caf_batch reports no quality. */
+int rmx_xcorr_batch_quality(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                            int integrate,
+                            const double* band_cps, int band_per_window, unsigned weighting,
+                            const int32_t* lag_bounds, int bounds_per_group, int refine,
+                            int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
+
 /* Cross-ambiguity variant of the hot path (BASELINE configs[4]): for
  * every window and pair (i, j) the later buoy's window is de-rotated by each Doppler hypothesis,
  *     c_d = correlate(x[w][j] * exp(-2*pi*i*doppler_cps[d]*n), x[w][i], 'full', 'fft'),

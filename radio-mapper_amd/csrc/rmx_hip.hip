@@ -29,6 +29,7 @@
 #include "xspec_weight.hpp"
 #include "integrate.hpp"
 #include "refine.hpp"
+#include "quality.hpp"
 #include "fft_r16.hpp"
 #include "kwin.hpp"
 #include "fft_r8.hpp"
@@ -844,8 +845,12 @@ struct XcorrCall {
     int refine = 0;                          // U of rmx_xcorr_batch_refined: k_refine behind every chunk's pair kernels, or 0
     bool bounded() const { return lb.b != nullptr; }         // the bounded instantiations of the peak-searching kernels
     bool integrated() const { return integ > 1; }            // the integrating instantiations of the pair kernels
+    float* quality = nullptr;                // rmx_xcorr_batch_quality: [rows][n_pairs][4] on the device (k_quality behind every
+                                             // chunk's pair kernels, in front of k_refine), or none
     bool refined() const { return refine > 0; }              // k_refine reads both spectra of a pair from HBM
-    bool weighted() const { return wt.band != nullptr || integ > 1 || refine > 0; }   // only the per-transform routes can serve it
+    bool qualified() const { return quality != nullptr; }    // k_quality does too
+    // only the per-transform routes can serve it
+    bool weighted() const { return wt.band != nullptr || integ > 1 || refine > 0 || quality != nullptr; }
 };
 
 // a small host array that kernels read: staged through pinned memory into a ctx-owned device buffer (stage_to_device)
@@ -893,6 +898,7 @@ struct rmx_ctx {
     void* d_in = nullptr;      size_t d_in_bytes = 0;
     int* d_lag = nullptr;      float* d_frac = nullptr;  float* d_peak = nullptr;  size_t d_out_elems = 0;   // ONE block: lag | frac | peak
     int* d_dop = nullptr;
+    float* d_quality = nullptr;  size_t d_quality_elems = 0;   // rmx_xcorr_batch_quality's fourth output of a host-pointer call
     void* h_out = nullptr;     size_t h_out_bytes = 0;   // pinned staging of small host-pointer results (fetch_out)
     size_t spec_bytes = 0, scratch_bytes = 0;
     // generic path (n_samples != 4096): see generic_path.hpp
@@ -956,7 +962,7 @@ struct rmx_ctx {
     rmx::DevStage lb_stage, band_stage;
     const void* g_rows_fwd_wt_fn = nullptr;   // the weighted instantiation of g_rows_fwd_fn
     const void* g_cols_inv_int_fn = nullptr;   // the integrating instantiation of g_cols_inv_fn (integrate.hpp)
-    rmx::RefPair* rf_pairs = nullptr;          // k_refine's pair list (refine.hpp): the plan's pairs in output order
+    rmx::RefPair* rf_pairs = nullptr;          // k_refine's and k_quality's pair list (refine.hpp): the plan's pairs in output order
     std::vector<int32_t> rf_pairs_plan;
     // cached pair plan
     std::vector<int32_t> plan_pairs;
@@ -1054,11 +1060,13 @@ enum TimeKind {
     kTkFwd16k = 13,      // k16_fwd
     kTkPairs16k = 14,    // k16_pairs
     kTkRefine = 15,      // k_refine
-    kTkCount = 16
+    kTkQuality = 16,     // k_quality
+    kTkCount = 17
 };
 static const char* const kTimeKindName[kTkCount] = {
     "k_fwd", "k_win|k_pair", "g_cols_fwd", "g_rows_fwd", "g_rows_fused", "g_rows_anchor", "g_rows_inv", "g_cols_inv",
-    "g_final", "g_win_*", "g_fwd_small", "g_pair_small", "k_caf_select", "k16_fwd", "k16_pairs", "k_refine"};
+    "g_final", "g_win_*", "g_fwd_small", "g_pair_small", "k_caf_select", "k16_fwd", "k16_pairs", "k_refine",
+    "k_quality"};
 static int tm_begin(rmx_ctx* c) {
     if (!c->timing) return RMX_OK;
     const int rc = ensure_events(c, c->ev_used + 2);
@@ -1103,15 +1111,24 @@ static int build_plan(rmx_ctx* c, const int32_t* pairs, int n_pairs) {
 // The fine lag search of a refined call (refine.hpp) on the chunk the pair kernels have just finished: windows
 // [w0, w0 + wc), whose spectra `spec` still holds in the order `layout` names.  One workgroup per output slot of the
 // chunk; lag_int is read (the coarse lag0) and all three outputs are overwritten in place.
-static int refine_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const void* spec, int logL, int row_bits, int unit_log2,
-                        int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak) {
+// the plan's pairs in output order on the device, for the kernels that take one output slot per workgroup
+static int ensure_ref_pairs(rmx_ctx* c, int n_pairs) {
     if (c->rf_pairs_plan != c->plan_pairs || !c->rf_pairs) {
-        RMX_HIP(c, hipStreamSynchronize(c->stream));   // an earlier call's k_refine may still read the old list
+        RMX_HIP(c, hipStreamSynchronize(c->stream));   // an earlier call's k_refine / k_quality may still read the old list
         if (c->rf_pairs) { (void)hipFree(c->rf_pairs); c->rf_pairs = nullptr; }
         c->rf_pairs_plan.clear();
         RMX_HIP(c, hipMalloc((void**)&c->rf_pairs, sizeof(RefPair) * (size_t)n_pairs));
         RMX_HIP(c, hipMemcpy(c->rf_pairs, c->plan_pairs.data(), sizeof(RefPair) * (size_t)n_pairs, hipMemcpyHostToDevice));
         c->rf_pairs_plan = c->plan_pairs;
+    }
+    return RMX_OK;
+}
+
+static int refine_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const void* spec, int logL, int row_bits, int unit_log2,
+                        int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak) {
+    {
+        const int rc_p = ensure_ref_pairs(c, n_pairs);
+        if (rc_p != RMX_OK) return rc_p;
     }
     RefineArgs a;
     a.spec = static_cast<const float2*>(spec);
@@ -1141,6 +1158,37 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const voi
     else with_u(std::integral_constant<int, kRefRows>{});
     RMX_HIP(c, hipGetLastError());
     RMX_TM_END(c, kTkRefine);
+    return RMX_OK;
+}
+
+// The quality figures of a quality call (quality.hpp) on the chunk the pair kernels have just finished, in front of
+// refine_chunk: d_peak still holds the coarse peaks.  One workgroup per output slot of the chunk; nothing but
+// call.quality is written.
+static int quality_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const void* spec, int logL, int row_bits, int unit_log2,
+                         int w0, int wc, int n_pairs, const float* d_peak) {
+    {
+        const int rc_p = ensure_ref_pairs(c, n_pairs);
+        if (rc_p != RMX_OK) return rc_p;
+    }
+    QualityArgs a;
+    a.spec = static_cast<const float2*>(spec);
+    a.pairs = c->rf_pairs;
+    a.first_out = w0 / call.integ;
+    a.n_buoys = c->n_buoys;
+    a.n_pairs = n_pairs;
+    a.logL = logL;
+    a.row_bits = row_bits;
+    a.k = call.integ;
+    a.sa = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the stored forward scale 2^unit_log2, squared
+    a.sc = std::ldexp(1.0f, -logL - 4 * unit_log2);   // ... to the fourth power
+    const unsigned grid = (unsigned)(wc / call.integ * n_pairs);
+    RMX_TM_BEGIN(c);
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefThreads), 0, c->stream, a, d_peak, call.quality); };
+    if (layout == kRefKfwd) launch(k_quality<kRefKfwd>);
+    else if (layout == kRefSmall) launch(k_quality<kRefSmall>);
+    else launch(k_quality<kRefRows>);
+    RMX_HIP(c, hipGetLastError());
+    RMX_TM_END(c, kTkQuality);
     return RMX_OK;
 }
 
@@ -1992,6 +2040,12 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, in
         if (rc) return rc;
         rc = generic_pairs(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
         if (rc) return rc;
+        if (call.qualified()) {   // (weighted() like a refined call; in front of k_refine, which overwrites the coarse peak)
+            const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
+            rc = quality_chunk(c, call, small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1,
+                               -(c->g_logL / 2), w0, wc, n_pairs, d_peak);
+            if (rc) return rc;
+        }
         if (call.refined()) {   // (a refined call is weighted(): never fused, g_spec holds this chunk's spectra, scaled 2^-(logL / 2))
             const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
             rc = refine_chunk(c, call, small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1,
@@ -2160,6 +2214,7 @@ void rmx_destroy(rmx_ctx* c) {
     if (c->d_lag) (void)hipFree(c->d_lag);            // (d_frac / d_peak point into the same block)
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->rf_pairs) (void)hipFree(c->rf_pairs);
+    if (c->d_quality) (void)hipFree(c->d_quality);
     for (rmx::DevStage* s : {&c->lb_stage, &c->band_stage}) {
         if (s->d) (void)hipFree(s->d);
         if (s->h) (void)hipHostFree(s->h);
@@ -2386,6 +2441,16 @@ static int fetch_out(rmx_ctx* c, size_t out_elems, int32_t* lag_int, float* lag_
     return RMX_OK;
 }
 
+// the device block a host-pointer quality call writes its fourth output to (rmx_xcorr_batch_quality)
+static int ensure_quality(rmx_ctx* c, size_t elems) {
+    if (c->d_quality_elems >= elems) return RMX_OK;
+    if (c->d_quality) (void)hipFree(c->d_quality);
+    c->d_quality = nullptr; c->d_quality_elems = 0;
+    RMX_HIP(c, hipMalloc((void**)&c->d_quality, elems * sizeof(float)));
+    c->d_quality_elems = elems;
+    return RMX_OK;
+}
+
 // N = 4096: the model of host_plan.hpp with this ctx's numbers
 static double split_cost4096(const rmx_ctx* c, int n_windows, int n_pairs, int* ppb) {
     return host::split_cost4096(c->n_cus, c->n_buoys, n_pairs, n_windows, c->ppb_user ? c->pairs_per_block : 0, ppb);
@@ -2449,12 +2514,70 @@ static int stage_to_device(rmx_ctx* c, DevStage* s, const int32_t* src, size_t e
     return RMX_OK;
 }
 
+// The second pass of a quality call that asks for nothing else that needs the spectra in HBM (no band, no weighting, no
+// integration, no refinement).  Its three lag outputs have just been written by the routes of the SAME call without
+// quality -- the whole-window kernels included, which keep their spectra to themselves --, so they are that call's
+// outputs bit for bit; here the per-transform forward kernels store the spectra chunk by chunk and k_quality reads them
+// and the peaks.  The input is on the device (the caller's, or the ctx's copy the first pass made).
+static int quality_pass(rmx_ctx* c, const XcorrCall& req, const void* iq, int n_windows, int n_pairs, const float* peak,
+                        unsigned flags) {
+    const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
+    const void* d_iq = in_dev ? iq : c->d_in;
+    const float* d_peak = out_dev ? peak : c->d_peak;
+    const size_t out_elems = (size_t)n_windows * n_pairs;
+    XcorrCall call = req;
+    if (!out_dev) {
+        const int rc_q = ensure_quality(c, 4 * out_elems);
+        if (rc_q != RMX_OK) return rc_q;
+        call.quality = c->d_quality;
+    }
+    int rc;
+    if (c->generic) {
+        rc = rmx::generic_ensure(c, n_pairs, true, true);
+        if (rc != RMX_OK) return rc;
+        const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
+        for (int w0 = 0; w0 < n_windows; w0 += c->g_chunk) {
+            const int wc = n_windows - w0 < c->g_chunk ? n_windows - w0 : c->g_chunk;
+            rc = rmx::generic_forward(c, call, d_iq, w0, wc, u8, nullptr);
+            if (rc != RMX_OK) return rc;
+            rc = quality_chunk(c, call, small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1,
+                               -(c->g_logL / 2), w0, wc, n_pairs, d_peak);
+            if (rc != RMX_OK) return rc;
+        }
+    } else {
+        rc = ensure_spec(c, n_windows < c->chunk_windows ? n_windows : c->chunk_windows);
+        if (rc != RMX_OK) return rc;
+        for (int w0 = 0; w0 < n_windows; w0 += c->chunk_windows) {
+            const int wc = n_windows - w0 < c->chunk_windows ? n_windows - w0 : c->chunk_windows;
+            rc = fwd4096(c, call, d_iq, w0, wc, u8, nullptr);
+            if (rc != RMX_OK) return rc;
+            rc = quality_chunk(c, call, kRefKfwd, c->d_spec, 13 /* log2 kL */, 0, -kTw1ScaleLog2, w0, wc, n_pairs, d_peak);
+            if (rc != RMX_OK) return rc;
+        }
+    }
+    if (!out_dev) {
+        RMX_HIP(c, hipMemcpyAsync(req.quality, c->d_quality, 4 * out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        RMX_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return RMX_OK;
+}
+
 // One correlation call as `call` describes it -- plain, bounded, weighted, integrated or any mix: every route launches the
 // instantiations the request names (the bounded one of its peak-searching kernel, lag_bounds.hpp; the weighted one of its
 // per-transform forward kernel, xspec_weight.hpp; the integrating one of its pair kernel, integrate.hpp) or, where a
 // route has none, is steered to the per-transform kernels.  The arguments have been checked (xcorr_request).
-static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& call, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                           int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    // Quality and nothing else that needs the spectra in HBM: the three lag outputs come from the routes of the same call
+    // without quality, so they are that call's bit for bit whatever kernel it takes; the figures follow in a second pass.
+    if (req.qualified() && !req.wt.band && !req.integrated() && !req.refined()) {
+        XcorrCall lags = req;
+        lags.quality = nullptr;
+        const int rc_l = xcorr_dispatch(c, lags, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+        if (rc_l != RMX_OK) return rc_l;
+        return quality_pass(c, req, iq, n_windows, n_pairs, peak, flags);
+    }
+    XcorrCall call = req;   // (req.quality is the caller's pointer; a host-pointer call gets the ctx's device block below)
     const int all_pairs = c->n_buoys * (c->n_buoys - 1) / 2;
     tm_reset(c);
     // Few windows of N = 4096: the fused kernel is one workgroup per WINDOW -- (B + P) transforms in sequence, 92 us for
@@ -2556,12 +2679,23 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& call, const void* iq, int
             if (rc_out != RMX_OK) return rc_out;
         }
         d_lag = c->d_lag; d_frac = c->d_frac; d_peak = c->d_peak;
+        if (call.qualified()) {
+            const int rc_q = ensure_quality(c, 4 * out_elems);
+            if (rc_q != RMX_OK) return rc_q;
+            call.quality = c->d_quality;
+        }
     }
+    // host-pointer results: the fourth array is queued in front of fetch_out, which waits for the stream
+    auto fetch_all = [&]() -> int {
+        if (call.qualified())
+            RMX_HIP(c, hipMemcpyAsync(req.quality, c->d_quality, 4 * out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        return fetch_out(c, out_elems, lag_int, lag_frac, peak);
+    };
 
     if (c->generic) {
         rc = rmx::generic_batch(c, call, d_iq, n_windows, n_pairs, d_lag, d_frac, d_peak, u8);
         if (rc != RMX_OK) return rc;
-        if (!out_dev) return fetch_out(c, out_elems, lag_int, lag_frac, peak);
+        if (!out_dev) return fetch_all();
         return RMX_OK;
     }
     const float out_scale = out_scale4096();   // (the forward scale 2^-6 rides on the TW1 table)
@@ -2641,12 +2775,16 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& call, const void* iq, int
         if (rc != RMX_OK) return rc;
         rc = pairs4096(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, out_scale, false);
         if (rc != RMX_OK) return rc;
+        if (call.qualified()) {   // (weighted() like a refined call: this branch; in front of k_refine, which overwrites the coarse peak)
+            rc = quality_chunk(c, call, kRefKfwd, c->d_spec, 13 /* log2 kL */, 0, -kTw1ScaleLog2, w0, wc, n_pairs, d_peak);
+            if (rc != RMX_OK) return rc;
+        }
         if (call.refined()) {   // (a refined call is weighted(): this branch, d_spec holds the chunk's spectra, scaled 2^-6)
             rc = refine_chunk(c, call, kRefKfwd, c->d_spec, 13 /* log2 kL */, 0, -kTw1ScaleLog2, w0, wc, n_pairs, d_lag, d_frac, d_peak);
             if (rc != RMX_OK) return rc;
         }
     }
-    if (!out_dev) return fetch_out(c, out_elems, lag_int, lag_frac, peak);
+    if (!out_dev) return fetch_all();
     return RMX_OK;
 }
 
@@ -2724,7 +2862,8 @@ static int check_bounded(rmx_ctx* c, int n_windows, int n_pairs, int integrate, 
 // the call in an XcorrCall and dispatch it.  The plain call is integrate = 1, no band, no weighting, no bounds.
 static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
                          const double* band_cps, int band_per_window, unsigned weighting, const int32_t* lag_bounds,
-                         int bounds_per_window, int refine, int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+                         int bounds_per_window, int refine, int32_t* lag_int, float* lag_frac, float* peak, float* quality,
+                         unsigned flags) {
     if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
     std::vector<int32_t> bins;
     bool weighted = false, bounded = false;
@@ -2745,10 +2884,23 @@ static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_
     // rmx_xcorr_batch_refined: U, refused after the other three and before anything is staged
     if (refine != 0 && refine != 2 && refine != 4 && refine != 8 && refine != 16)
         return fail(c, RMX_E_INVAL, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", refine);
+    // rmx_xcorr_batch_quality: the fourth output must not lie over one of the other three (k_quality reads peak while it
+    // writes quality); refused after the other four and before anything is staged
+    if (quality) {
+        const size_t rows = (size_t)(n_windows / integrate) * n_pairs;
+        const char *q0 = reinterpret_cast<const char*>(quality), *q1 = q0 + 4 * rows * sizeof(float);
+        const struct { const char* name; const void* p; } outs[3] = {{"lag_int", lag_int}, {"lag_frac", lag_frac}, {"peak", peak}};
+        for (const auto& o : outs) {
+            const char* p0 = static_cast<const char*>(o.p);
+            if (p0 < q1 && q0 < p0 + rows * sizeof(float))
+                return fail(c, RMX_E_INVAL, "quality overlaps %s: the %zu x 4 floats of quality need a buffer of their own", o.name, rows);
+        }
+    }
     RMX_HIP(c, hipSetDevice(c->device));
     XcorrCall call;
     call.integ = integrate;
     call.refine = refine;
+    call.quality = quality;
     if (weighted) {
         rc = stage_to_device(c, &c->band_stage, bins.data(), bins.size());
         if (rc != RMX_OK) return rc;
@@ -2766,7 +2918,8 @@ static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_
 int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                     int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0, 0, lag_int, lag_frac, peak, flags);
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0, 0, lag_int, lag_frac, peak, nullptr,
+                         flags);
 }
 
 // rmx_xcorr_batch with a lag interval per (window, pair).  Every interval the full one IS the plain call.
@@ -2776,7 +2929,7 @@ int rmx_xcorr_batch_bounded(rmx_ctx* c, const void* iq, int n_windows, const int
     if (!c) return RMX_E_INVAL;
     if (!lag_bounds) return fail(c, RMX_E_INVAL, "NULL buffer");
     return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, lag_bounds, bounds_per_window, 0, lag_int,
-                         lag_frac, peak, flags);
+                         lag_frac, peak, nullptr, flags);
 }
 
 // rmx_xcorr_batch(_bounded) on band-masked and / or PHAT-whitened spectra.  No band (or the full one) and no weighting IS
@@ -2787,7 +2940,7 @@ int rmx_xcorr_batch_weighted(rmx_ctx* c, const void* iq, int n_windows, const in
                              int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
     return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, band_cps, band_per_window, weighting, lag_bounds, bounds_per_window,
-                         0, lag_int, lag_frac, peak, flags);
+                         0, lag_int, lag_frac, peak, nullptr, flags);
 }
 
 // rmx_xcorr_batch_weighted with one peak search per group of `integrate` consecutive windows, on the lag-by-lag sum of the
@@ -2807,6 +2960,16 @@ int rmx_xcorr_batch_refined(rmx_ctx* c, const void* iq, int n_windows, const int
                             const double* band_cps, int band_per_window, unsigned weighting,
                             const int32_t* lag_bounds, int bounds_per_group, int refine,
                             int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    return rmx_xcorr_batch_quality(c, iq, n_windows, pairs, n_pairs, integrate, band_cps, band_per_window, weighting, lag_bounds,
+                                   bounds_per_group, refine, lag_int, lag_frac, peak, nullptr, flags);
+}
+
+// rmx_xcorr_batch_refined with four quality figures per output slot (quality.hpp) as a fourth output, computed from the
+// pair's two stored spectra and the coarse peak.  quality == NULL IS the refined call.
+int rmx_xcorr_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
+                            const double* band_cps, int band_per_window, unsigned weighting,
+                            const int32_t* lag_bounds, int bounds_per_group, int refine,
+                            int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
     if (!c) return RMX_E_INVAL;
     std::vector<int32_t> full;
     const int rc = check_integrated(c, n_windows, pairs, n_pairs, integrate, lag_bounds != nullptr, &full);
@@ -2816,7 +2979,7 @@ int rmx_xcorr_batch_refined(rmx_ctx* c, const void* iq, int n_windows, const int
         bounds_per_group = 0;
     }
     return xcorr_request(c, iq, n_windows, pairs, n_pairs, integrate, band_cps, band_per_window, weighting, lag_bounds,
-                         bounds_per_group, refine, lag_int, lag_frac, peak, flags);
+                         bounds_per_group, refine, lag_int, lag_frac, peak, quality, flags);
 }
 
 int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,

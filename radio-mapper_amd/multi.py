@@ -94,13 +94,15 @@ class MultiXcorrEngine:
         """(start, count) of every device's block, in device order (empty blocks included)."""
         return [window_shard(n_windows, r, len(self.devices)) for r in range(len(self.devices))]
 
-    def _run(self, n_windows: int, call: Callable, n_out: int, dtypes, n_pairs: int, n_rows: Optional[int] = None):
+    def _run(self, n_windows: int, call: Callable, n_out: int, dtypes, n_pairs: int, n_rows: Optional[int] = None,
+             tails=None):
         """n_rows: the items that are sharded and the rows of the results (the groups of an integrated call); default: the
-        windows"""
+        windows.  tails: per output, the trailing shape behind [rows][P] (the 4 of the quality array); default: none"""
         if n_windows > self.max_windows:
             raise ValueError(f"n_windows {n_windows} > max_windows {self.max_windows}")
         n_windows = n_windows if n_rows is None else n_rows
-        outs = [np.zeros((n_windows, n_pairs), dt) for dt in dtypes]
+        tails = tails or [()] * len(dtypes)
+        outs = [np.zeros((n_windows, n_pairs) + tuple(t), dt) for dt, t in zip(dtypes, tails)]
         with self._lock:
             futs = []
             for r, (s, c) in enumerate(self.blocks(n_windows)):
@@ -120,21 +122,25 @@ class MultiXcorrEngine:
 
     # -- the hot path --------------------------------------------------------------------------------
     def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
-                  whiten: bool = False, integrate: int = 1, refine: int = 0):
+                  whiten: bool = False, integrate: int = 1, refine: int = 0, quality: bool = False):
         """iq: complex64 [W][B][N] or uint8 [W][B][2N] -> (lag_int [W][P], lag_frac [W][P], peak [W][P]).
         lag_bounds: None, [P][2] (every block gets it whole) or [W][P][2] (each block gets its own windows' rows).
         band: None, [2] (every block gets it whole) or [W][2] (each block its own windows' rows); whiten: PHAT.
         integrate: K windows per group (XcorrEngine.correlate): whole groups are sharded over the devices, the results and
         per-group lag_bounds are [W // K][.]; a block larger than its engine holds runs as several calls of whole groups.
-        refine: U of the fine lag search (XcorrEngine.correlate), handed to every block's call."""
+        refine: U of the fine lag search (XcorrEngine.correlate), handed to every block's call.
+        quality: True gathers a fourth array, the blocks' quality figures [W // K][P][4] (XcorrEngine.correlate)."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
         K = check_integrate(integrate, iq.shape[0])
         U = check_refine(refine)
+        n_out = 4 if quality else 3
+        dtypes = (np.int32, np.float32, np.float32, np.float32)[:n_out]
+        tails = [(), (), (), (4,)][:n_out]
         if K > 1:
-            return self._correlate_integrated(iq, pairs, lag_bounds, band, whiten, K, P, U)
+            return self._correlate_integrated(iq, pairs, lag_bounds, band, whiten, K, P, U, bool(quality))
         lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
 
         bd, band_pw = check_band(band, iq.shape[0])
@@ -143,6 +149,10 @@ class MultiXcorrEngine:
             return lb[s:s + c] if per_window else lb
 
         def block_call(eng, s, c):
+            if quality:
+                return eng.correlate(iq[s:s + c], pairs, None if lb is None else block_bounds(s, c),
+                                     band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, refine=U,
+                                     quality=True)
             if U > 0:
                 return eng.correlate(iq[s:s + c], pairs, None if lb is None else block_bounds(s, c),
                                      band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, refine=U)
@@ -152,15 +162,18 @@ class MultiXcorrEngine:
             if lb is not None:
                 return eng.correlate(iq[s:s + c], pairs, block_bounds(s, c))
             return eng.correlate(iq[s:s + c], pairs)
-        return self._run(iq.shape[0], block_call, 3, (np.int32, np.float32, np.float32), P)
+        return self._run(iq.shape[0], block_call, n_out, dtypes, P, tails=tails)
 
-    def _correlate_integrated(self, iq, pairs, lag_bounds, band, whiten, K, P, U=0):
+    def _correlate_integrated(self, iq, pairs, lag_bounds, band, whiten, K, P, U=0, quality=False):
         W = iq.shape[0]
         G = W // K
         lb, per_group = check_lag_bounds(lag_bounds, G, P)
         bd, band_pw = check_band(band, W)
 
         kw = {"refine": U} if U > 0 else {}
+        if quality:
+            kw["quality"] = True
+        n_out = 4 if quality else 3
 
         def block_call(eng, gs, gc):
             # the engines are sized for an even split of the WINDOWS; a block of whole groups may be a little larger
@@ -175,8 +188,9 @@ class MultiXcorrEngine:
                                            None if lb is None else (lb[g0:g1] if per_group else lb),
                                            band=None if bd is None else (bd[g0 * K:g1 * K] if band_pw else bd),
                                            whiten=whiten, integrate=K, **kw))
-            return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
-        return self._run(W, block_call, 3, (np.int32, np.float32, np.float32), P, n_rows=G)
+            return tuple(np.concatenate([p[k] for p in parts]) for k in range(n_out))
+        return self._run(W, block_call, n_out, (np.int32, np.float32, np.float32, np.float32)[:n_out], P, n_rows=G,
+                         tails=[(), (), (), (4,)][:n_out])
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None):
         """Cross-ambiguity search -> (doppler_idx, lag_int, lag_frac, peak), each [W][P]."""

@@ -151,7 +151,7 @@ class TDoACalculator:
 
     def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, min_cut_samples: int = 128,
                  bound_lags: bool = False, band_limit: bool = False, whiten: bool = False, integrate: int = 1,
-                 refine: int = 0):
+                 refine: int = 0, min_psr: Optional[float] = None, correlation_confidence: bool = False):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
@@ -172,7 +172,13 @@ class TDoACalculator:
         refine: U in (0, 2, 4, 8, 16); U > 0 takes every lag's sub-sample part from the band-limited interpolant of the
         correlation on a grid of 1 / U samples around the integer peak (rmx_xcorr_batch_refined) instead of the
         three-point parabola, whose bias on a band-limited peak is up to 0.15 samples.  The refined lag flows into
-        time_difference_ns unchanged in meaning.  A plain attribute, 0 (off) by default."""
+        time_difference_ns unchanged in meaning.  A plain attribute, 0 (off) by default.
+        min_psr, correlation_confidence: qualify every measured lag by the correlation itself (rmx_xcorr_batch_quality).
+        min_psr: a pair whose peak-to-floor ratio lies below it is dropped and logged -- a dead or drowned receiver's lag
+        is noise (xcorr.psr_threshold gives the value for a false-alarm rate).  correlation_confidence: the measurement's
+        confidence, built from the detector's confidence and a timing term only, is additionally multiplied by the pair's
+        coherence in [0, 1].  Plain attributes; None and False (off) by default: the engine is then called exactly as
+        before.  Neither applies to groups without IQ (the time-tag arithmetic has no correlation)."""
         from .xcorr import check_refine
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
@@ -183,6 +189,8 @@ class TDoACalculator:
         self.whiten = bool(whiten)
         self.integrate = int(integrate)
         self.refine = check_refine(refine)
+        self.min_psr = None if min_psr is None else float(min_psr)
+        self.correlation_confidence = bool(correlation_confidence)
         self._engines: Dict[Tuple[int, int], Any] = {}   # insertion order = recency
         self._tconf: Dict[Tuple[int, int], float] = {}
 
@@ -222,7 +230,10 @@ class TDoACalculator:
             eng.close()
         self._engines.clear()
 
-    def measure_lags(self, iq, pairs=None, lag_bounds=None, band=None, whiten=False, integrate=1, refine=0):
+    def _wants_quality(self) -> bool:
+        return self.min_psr is not None or self.correlation_confidence
+
+    def measure_lags(self, iq, pairs=None, lag_bounds=None, band=None, whiten=False, integrate=1, refine=0, quality=False):
         """Batched hot path.  iq: complex64 [W][B][N] (or uint8 [W][B][2N]) ->
         (lag_int [W][P], lag_frac [W][P], peak [W][P]); lag = delay(j) - delay(i) in samples.
         A leading channel axis is a batch axis: [C][W][B][N] -> three [C][W][P] arrays (channels and
@@ -232,7 +243,8 @@ class TDoACalculator:
         whiten: PHAT weighting (rmx_xcorr_batch_weighted).  integrate: K >= 1 consecutive windows per group, one lag
         per pair and group (rmx_xcorr_batch_integrated): W must be a multiple of K, the results and per-window lag_bounds
         have W // K rows where they have W otherwise; band stays per window.  refine: U of the fine lag search
-        (rmx_xcorr_batch_refined), 0 for none."""
+        (rmx_xcorr_batch_refined), 0 for none.  quality: True returns a fourth array [W][P][4] (with a channel axis:
+        [C][W][P][4]), the quality figures of every lag (rmx_xcorr_batch_quality)."""
         from .xcorr import check_integrate, check_refine
         refine = check_refine(refine)
         iq = np.asarray(iq)
@@ -253,7 +265,7 @@ class TDoACalculator:
             lb = np.asarray(lag_bounds)
             if lead is not None and lb.ndim == 4:
                 lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
-        if band is not None or whiten or integrate > 1 or refine > 0:
+        if band is not None or whiten or integrate > 1 or refine > 0 or quality:
             bd = None
             if band is not None:
                 bd = np.asarray(band)
@@ -262,6 +274,8 @@ class TDoACalculator:
             kw = {"integrate": integrate} if integrate > 1 else {}
             if refine > 0:
                 kw["refine"] = refine
+            if quality:
+                kw["quality"] = True
             out = eng.correlate(iq, pairs, lag_bounds=lb, band=bd, whiten=bool(whiten), **kw)
         elif lb is None:
             out = eng.correlate(iq, pairs)
@@ -414,10 +428,11 @@ class TDoACalculator:
                           f"{max(self.min_cut_samples, 16)}")
         return n // k, None
 
-    def _measure_groups(self, stacked: np.ndarray, lag_bounds=None, band=None):
+    def _measure_groups(self, stacked: np.ndarray, lag_bounds=None, band=None, with_quality: bool = False):
         """[G][B][N] -> lag [G][P] float64, or None after logging: the reference's seam never raises
         (tdoa_processor.py:151-153) and there is no fallback to time tags once IQ was supplied.  lag_bounds: None, or
-        int [G][P][2] (bound_lags); band: None, or float [G][2] (band_limit); whiten applies to every group."""
+        int [G][P][2] (bound_lags); band: None, or float [G][2] (band_limit); whiten applies to every group.
+        with_quality: -> (lag [G][P], quality [G][P][4]) instead (min_psr / correlation_confidence), None all the same."""
         kw = {}
         if lag_bounds is not None:
             kw["lag_bounds"] = lag_bounds
@@ -437,6 +452,9 @@ class TDoACalculator:
         if self.refine > 0:
             kw["refine"] = self.refine
         try:
+            if with_quality:
+                li, lf, _, qual = self.measure_lags(stacked, quality=True, **kw)
+                return li.astype(np.float64) + lf.astype(np.float64), np.asarray(qual)
             li, lf, _ = self.measure_lags(stacked, **kw)
             return li.astype(np.float64) + lf.astype(np.float64)
         except (ImportError, OSError) as e:   # library not built / not loadable
@@ -469,7 +487,8 @@ class TDoACalculator:
                                     _lag=_NO_LAG) -> List[TDoAMeasurement]:
         """The reference's pair loop (tdoa_processor.py:146-198).  `_lag` (private): (lags [P], sample rate) of this
         group, already measured in a batch with other groups by TDoAProcessor; None when that batch failed or the
-        group's IQ could not be batched; `_TIME_TAGS` when TDoAProcessor found no IQ on the group."""
+        group's IQ could not be batched; `_TIME_TAGS` when TDoAProcessor found no IQ on the group.  The tuple may go on
+        with the empty-interval flags [P] (or None) and the quality figures [P][4] of the group."""
         out: List[TDoAMeasurement] = []
         nd = len(detections)
         if nd < 2:
@@ -478,6 +497,7 @@ class TDoACalculator:
         lag = None
         fs = None
         empty = None   # bound_lags: pairs whose lag window is empty (skipped below)
+        qual = None    # min_psr / correlation_confidence: the quality figures [P][4] of the group's lags
         if _lag is self._NO_LAG:
             key, stacked = self._iq_batch_key(detections)
             if key is False:
@@ -500,15 +520,22 @@ class TDoACalculator:
                     if why:
                         self.logger.error(f"Cannot band limit the group: {why}; no TDoA measurements for it")
                         return out
-                res = self._measure_groups(stacked[None], lb, None if band is None else band[None])
-                if res is None:
-                    return out
+                if self._wants_quality():
+                    res = self._measure_groups(stacked[None], lb, None if band is None else band[None], with_quality=True)
+                    if res is None:
+                        return out
+                    res, qual = res[0], res[1][0]
+                else:
+                    res = self._measure_groups(stacked[None], lb, None if band is None else band[None])
+                    if res is None:
+                        return out
                 lag, fs = res[0], key[3]
         elif _lag is None:
             return out
         elif _lag is not self._TIME_TAGS:
             lag, fs = _lag[0], _lag[1]
             empty = _lag[2] if len(_lag) > 2 else None
+            qual = _lag[3] if len(_lag) > 3 else None
         q = -1
         if lag is not None:
             # the same float64 arithmetic as `round(lag[q] / fs * 1e9)` per pair, done once for the group (numpy scalars make
@@ -537,6 +564,13 @@ class TDoACalculator:
                 if not p1 or not p2:
                     continue
                 conf = min(d1.confidence, d2.confidence) * self._timing_confidence(p1, p2)
+                if qual is not None:
+                    if self.min_psr is not None and not float(qual[q][1]) >= self.min_psr:   # (RMX_Q_PSR)
+                        self.logger.warning("TDoA %s-%s dropped: peak-to-floor ratio %.1f below min_psr %.1f", d1.buoy_id,
+                                            d2.buoy_id, float(qual[q][1]), self.min_psr)
+                        continue
+                    if self.correlation_confidence:
+                        conf *= float(qual[q][0])   # (RMX_Q_COHERENCE)
                 out.append(TDoAMeasurement(d1.buoy_id, d2.buoy_id, dt_ns, dist_m, conf, d1.frequency_mhz))
                 if debug:
                     self.logger.debug("TDoA %s-%s dT=%.1f us dD=%.1f m", d1.buoy_id, d2.buoy_id, dt_ns / 1000, dist_m)
@@ -622,10 +656,13 @@ class HyperbolicPositioning:
 # orchestrator (tdoa_processor.py:330-465)
 # --------------------------------------------------------------------------------------------------
 class TDoAProcessor:
-    def __init__(self, band_limit: bool = False, whiten: bool = False, integrate: int = 1, refine: int = 0):
-        """band_limit, whiten, integrate, refine: the TDoACalculator settings of the same names (off by default)."""
+    def __init__(self, band_limit: bool = False, whiten: bool = False, integrate: int = 1, refine: int = 0,
+                 min_psr: Optional[float] = None, correlation_confidence: bool = False):
+        """band_limit, whiten, integrate, refine, min_psr, correlation_confidence: the TDoACalculator settings of the same
+        names (off by default)."""
         self.logger = logging.getLogger(__name__ + ".TDoAProcessor")
-        self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten, integrate=integrate, refine=refine)
+        self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten, integrate=integrate, refine=refine,
+                                              min_psr=min_psr, correlation_confidence=correlation_confidence)
         self.hyperbolic_positioner = HyperbolicPositioning()
         self.buoy_positions: Dict[str, BuoyPosition] = {}
         self.correlation_window_s = 10.0
@@ -702,15 +739,23 @@ class TDoAProcessor:
                 if any(bands[n] is not None for n in members):
                     band = np.stack([np.array([-0.5, 0.5]) if bands[n] is None else bands[n] for n in members])
             stacked = np.stack([work[n][3] for n in members])
+            # (min_psr / correlation_confidence: the quality figures ride along as the tuple's fourth entry)
+            more = {"with_quality": True} if calc._wants_quality() else {}
             if calc.bound_lags:   # per-window bounds [G][P][2]: each group has its own buoys and window starts
                 per = [calc.lag_bounds(work[n][1], self.buoy_positions, n_samp, key[3]) for n in members]
-                lags = calc._measure_groups(stacked, np.stack([b for b, _ in per]), band)
+                lags = calc._measure_groups(stacked, np.stack([b for b, _ in per]), band, **more)
+                qual = None
+                if more and lags is not None:
+                    lags, qual = lags
                 for k, n in enumerate(members):
-                    work[n][4] = None if lags is None else (lags[k], key[3], per[k][1])
+                    work[n][4] = None if lags is None else ((lags[k], key[3], per[k][1]) + (() if qual is None else (qual[k],)))
                 continue
-            lags = calc._measure_groups(stacked, None, band)
+            lags = calc._measure_groups(stacked, None, band, **more)
+            qual = None
+            if more and lags is not None:
+                lags, qual = lags
             for k, n in enumerate(members):
-                work[n][4] = None if lags is None else (lags[k], key[3])
+                work[n][4] = None if lags is None else ((lags[k], key[3]) + (() if qual is None else (None, qual[k])))
         results: List[TriangulationResult] = []
         for freq, recent, key, _, lag in work:
             meas = self.tdoa_calculator.calculate_tdoa_measurements(recent, self.buoy_positions, _lag=lag)
