@@ -150,6 +150,16 @@ struct PairPlan {
     bool all_pairs = false;         // the default list: all i < j in nested-loop order (tdoa_processor.py:156-157)
 };
 
+// is this the default list (pairs == nullptr: n_pairs alone says)?  Reads nothing when the count is not B(B-1)/2.
+inline bool is_default_list(int n_buoys, const int32_t* pairs, int n_pairs) {
+    if (n_pairs != (long)n_buoys * (n_buoys - 1) / 2) return false;
+    int q = 0;
+    for (int i = 0; pairs && i < n_buoys; ++i)
+        for (int j = i + 1; j < n_buoys; ++j, ++q)
+            if (pairs[2 * q] != i || pairs[2 * q + 1] != j) return false;
+    return true;
+}
+
 // pairs == nullptr: the default list (n_pairs must then be P = B(B-1)/2).  0, or -1 with *err.
 inline int make_pair_plan(int n_buoys, const int32_t* pairs, int n_pairs, int pairs_per_block, PairPlan* out, std::string* err) {
     char b[200];
@@ -181,12 +191,7 @@ inline int make_pair_plan(int n_buoys, const int32_t* pairs, int n_pairs, int pa
     out->part_begin.assign(n_parts + 1, 0);
     for (int k = 0; k <= n_parts && n_parts > 0; ++k) out->part_begin[k] = (int)((long)k * n_pairs / n_parts);
     out->n_parts = n_parts;
-    bool def = n_pairs == all;
-    int q = 0;
-    for (int i = 0; def && i < n_buoys; ++i)
-        for (int j = i + 1; j < n_buoys; ++j, ++q)
-            if (pl[2 * q] != i || pl[2 * q + 1] != j) { def = false; break; }
-    out->all_pairs = def;
+    out->all_pairs = is_default_list(n_buoys, pl.data(), n_pairs);
     out->pairs.swap(pl);
     return 0;
 }
@@ -232,6 +237,186 @@ inline double split_cost4096(int n_cus, int n_buoys, int n_pairs, long n_windows
         if (fixed_ppb > 0) break;
     }
     return best;
+}
+
+// ---- the route of one correlation call ---------------------------------------------------------------------------------
+// plan_route is the ONE place where a call's kernels are chosen; the launch code executes the plan.
+enum Route {
+    kRouteKWin,        // N = 4096: k_win, forward + pairs in one workgroup per window (a chunk's partial round: route_wtail4096)
+    kRoutePer4096,     // N = 4096: k_fwd + k_pair_res / k_pair_str per chunk
+    kRouteK16,         // N = 16384: k16_fwd + k16_pairs per chunk of ws_grid windows
+    kRouteKWin8,       // N = 8192: k_win8kl (k_win8k in an experiments build), the batch's partial round through the per-transform kernels
+    kRouteWinScr,      // g_win_scr / g_win_scr14: whole windows, spectra in a cache-resident scratch
+    kRouteWinEo15,     // N = 16384: g_win_eo15, the partial round as for k_win8kl
+    kRouteWinFused,    // <= 4 buoys, L <= 4096: g_win_fused, spectra in registers
+    kRouteSmallL,      // L <= small_maxl: g_fwd_small + g_pair_small per chunk
+    kRouteFourStep     // longer: the column and row passes per chunk (route_rows_fused: g_rows_fused does both row passes)
+};
+enum RouteRefusal { kRouteOk = 0, kRefuseIntegChunk, kRefuseIntegTile };   // integrate > a chunk / column tile too large per thread
+
+// what rmx_create / generic_init (and rmx_set_option) fixed for the ctx
+struct RouteCaps {
+    int n_cus = 1, n_buoys = 2, logL = 13, logL1 = 0, logL2 = 0;
+    bool generic = false;
+    long small_maxl = 8192;
+    bool fused = true, small_batch = true;   // N = 4096 ...
+    int chunk_windows = 8, ppb_user = 0;     // ... ppb_user: the caller's pairs per workgroup, or 0
+    int g_chunk = 1, ws_upw = 0, ws_grid = 0, k16 = 0;   // generic ...
+    bool wfused = false, wscr = false, wscr_always = false, k8 = false, g_fused = false, g_fused_always = false;
+    long k16_min_windows = 0;                // option k16_min_windows, or 0: 100 / (buoys + pairs), rounded up
+    int max_pairs8 = 640, max_pairs16 = 640;                               // k8::kMaxPairs8, k16::kMaxPairs16
+    long col_tile = 0;  int cols_threads = 1, integ_max_per_thread = 16;   // four-step column tile, its threads, kIntegMaxPerThread
+};
+// what the call asks
+struct RouteCall {
+    int n_windows = 0, n_pairs = 0;
+    bool all_pairs = true, pairs_given = false;   // PairPlan::all_pairs; the caller passed a list (which may still be the default one)
+    bool bounded = false, weighted = false;       // XcorrCall::bounded(), XcorrCall::weighted()
+    int integ = 1;
+    bool in_dev = true;
+};
+struct RoutePlan {
+    Route route = kRoutePer4096;
+    int ppb = 7;                 // pairs per workgroup of the N = 4096 pair kernels (unused elsewhere)
+    int chunk = 0;               // windows per chunk of the per-transform routes and of k16, a multiple of integ
+    int n_head = 0, n_tail = 0;  // k_win8kl / g_win_eo15: windows of the full rounds / of the partial round behind them
+    int tail = 0;                // k_win: the largest partial round of any chunk that pays (the gate of route_wtail4096), or 0
+    bool pipelined = false;      // k_win, host windows: the copy is cut into sub-chunks on a second stream
+    RouteRefusal refused = kRouteOk;
+};
+
+constexpr int kHostSubChunk = 512;   // windows per copy/kernel step of the pipelined host-pointer path
+
+// N = 4096, k_win: r windows through the per-transform kernels are cheaper than one more round of the fused kernel
+inline bool tail_pays4096(const RouteCaps& k, int n_pairs, int r, int* q) {
+    return split_cost4096(k.n_cus, k.n_buoys, n_pairs, r, k.ppb_user, q) < 0.9 * fused_cost4096(k.n_cus, k.n_buoys, n_pairs, 1);
+}
+// This chunk's partial round (windows [w0, w0 + wc) of the call): only behind at least one full round of this call, and
+// only when the model says so for ITS size -- with the default chunk (a multiple of the CU count) that is the batch's last
+// partial round; 0 <= wtail < CUs and wtail <= wc by construction
+inline int route_wtail4096(const RouteCaps& k, const RoutePlan& p, int n_pairs, int w0, int wc) {
+    if (!p.tail || !(w0 > 0 || wc > k.n_cus) || wc % k.n_cus == 0) return 0;
+    int q_unused = 7;
+    return tail_pays4096(k, n_pairs, wc % k.n_cus, &q_unused) ? wc % k.n_cus : 0;
+}
+// Four-step: the fused row kernel when its (window, row block) units fill the chip at least twice: below that (cfg1's single
+// window: 128 workgroups) its long serial chain per unit loses to the two-kernel passes' wider grids (57 vs 47 us).  Never for
+// a weighted() call: g_rows_fused keeps its spectra to itself.
+inline bool route_rows_fused(const RouteCaps& k, bool weighted, int wc) {
+    if (weighted || !k.generic || !k.g_fused || (1L << k.logL) <= k.small_maxl) return false;
+    const long fused_blocks = (long)wc * (1L << k.logL1) / (256 / ((1 << k.logL2) >> 4));   // (256: gen::kGThreads)
+    return fused_blocks >= 2L * k.n_cus || k.g_fused_always;
+}
+
+inline RoutePlan plan_route4096(const RouteCaps& k, const RouteCall& a) {
+    RoutePlan p;
+    const int all_pairs = k.n_buoys * (k.n_buoys - 1) / 2, W = a.n_windows;
+    auto split = [&](long w, int* q) { return split_cost4096(k.n_cus, k.n_buoys, a.n_pairs, w, k.ppb_user, q); };
+    // Few windows of N = 4096: the fused kernel is one workgroup per WINDOW -- (B + P) transforms in sequence, 92 us for
+    // one window of 8 buoys, 344 us for 16 buoys, whatever the rest of the chip does -- while the per-transform kernels
+    // spread a window's spectra and pairs over the CUs: 13-15 us for the same single windows (tools/exp_small4096.py;
+    // the crossover sits at 64 / 110 / 140 windows for 3 / 8 / 16 buoys).  This is the shape of the reference's seam:
+    // one frequency group per call (tdoa_processor.py:363-377).  Both paths are costed with the model above and the
+    // cheaper one runs; the same model picks the pairs per workgroup (1 ... 7) unless the caller set them.
+    const bool modelled = k.fused && k.small_batch && k.n_buoys >= 3 && a.n_pairs == all_pairs;
+    bool small = false;  int ppb_small = 7;
+    if (modelled) small = split(W, &ppb_small) < fused_cost4096(k.n_cus, k.n_buoys, a.n_pairs, W);
+    // a weighted call weights the spectra where k_fwd stores them: the per-transform kernels at every batch size, never
+    // k_win (whose spectra stay inside the workgroup); an integrated call sums over windows inside k_pair_str: the same
+    // kernels, with one work item per (group, pair)
+    if (a.weighted) { (void)split(W / a.integ, &ppb_small); small = true; }
+    // The same arithmetic for the LAST round of a larger batch: W = k CUs + r windows cost the fused kernel k + 1 rounds
+    // (300 windows of 8 buoys: two rounds, 184 us); when the model says the r windows are cheaper through the
+    // per-transform kernels than a round of the fused one, they go there (after the k full rounds, on the same stream).
+    // The decision is taken per CHUNK of windows (a batch-wide tail larger than the last chunk ran past the
+    // chunk and past the spectrum scratch): route_wtail4096 decides for a chunk's own partial round, wc mod CUs, so it
+    // never exceeds the chunk, and the scratch of min(chunk, CUs) window slots covers it.  `tail` is the gate -- the
+    // largest remainder of ANY chunk that pays (every chunk but the last has chunk_windows windows; ADVICE r04: it used
+    // to look at the last chunk only) -- and sizes the pair workgroups (one plan per call) for that largest partial round.
+    const bool tail_ok = !small && modelled && k.n_cus > 0 && (a.in_dev || W <= kHostSubChunk);
+    if (tail_ok && W > k.n_cus) {
+        const long cw = k.chunk_windows;
+        const int last_wc = (int)(W - ((long)(W - 1) / cw) * cw);   // windows of the last chunk
+        const int r_last = last_wc % k.n_cus;
+        const int r_full = (W > cw) ? (int)(cw % k.n_cus) : 0;      // every earlier chunk's remainder
+        for (int r : {r_full > r_last ? r_full : r_last, r_full > r_last ? r_last : r_full}) {
+            int q = 7;
+            if (r != 0 && tail_pays4096(k, a.n_pairs, r, &q)) { p.tail = r; ppb_small = q; break; }
+        }
+    }
+    if (k.ppb_user) p.ppb = k.ppb_user;
+    else if (!small && !p.tail && (a.pairs_given || !k.fused)) (void)split(W, &p.ppb);   // a custom pair list (or fused = 0): the per-transform kernels anyway
+    else p.ppb = (small || p.tail) ? ppb_small : 7;
+    const bool fused_now = k.fused && a.all_pairs && !small;
+    if (!fused_now) p.tail = 0;
+    p.route = fused_now ? kRouteKWin : kRoutePer4096;
+    // fused path: the host copy is cut into sub-chunks issued on a second stream, each followed by its kernel launch, so
+    // that copy k+1 travels while kernel k runs; otherwise one copy up front
+    p.pipelined = !a.in_dev && fused_now && W > kHostSubChunk;
+    p.chunk = k.chunk_windows / a.integ * a.integ;   // (integrated call: a chunk holds whole groups -- never a silent split of a group)
+    if (p.chunk == 0) p.refused = kRefuseIntegChunk;
+    return p;
+}
+
+inline RoutePlan plan_route(const RouteCaps& k, const RouteCall& a) {
+    if (!k.generic) return plan_route4096(k, a);
+    RoutePlan p;
+    const int W = a.n_windows;
+    p.n_head = W;
+    // N = 16384 on k_win's network (kwin16k.hpp): fine-grained items, so no partial last round and a low minimum batch -- its
+    // two launches cost about 40 us whatever the size, the four-step kernels 26 us for one window: from about 100 transforms
+    // (windows x (buoys + pairs)) on it wins (tools/exp_k16_sweep.py: 3 buoys from 16 windows, 5 from 8, 8 from 1).  wscr = 2
+    // (tests: "the whole-window kernel, whatever the batch") keeps g_win_eo15, as do pair lists beyond the kernel's LDS copy.
+    // Weighted calls weight the spectra where the per-transform forward kernels store them: g_fwd_small up to
+    // L = small_maxl, g_cols_fwd + the forward g_rows above.  The whole-window kernels (g_win_*, k_win8kl), k16_fwd and
+    // g_rows_fused keep their spectra to themselves and are never taken.  Integrated calls sum over windows inside the
+    // per-transform pair kernels: the same routes.
+    const long k16_min = k.k16_min_windows > 0 ? k.k16_min_windows : (100 + k.n_buoys + a.n_pairs - 1) / (k.n_buoys + a.n_pairs);
+    if (!a.weighted && k.k16 && k.logL == 15 && a.n_pairs <= k.max_pairs16 &&
+        (k.k16 == 2 || (!k.wscr_always && W >= (int)k16_min))) { p.route = kRouteK16; p.chunk = k.ws_grid; return p; }
+    // g_win_scr runs a window's B + P transforms one after the other in one workgroup: batches that leave most of the chip
+    // without a workgroup are better off in the per-transform kernels (8 buoys x 8 windows of 8192: 0.32 vs 0.05 ms).
+    // Measured crossovers (tools/smallw.sh): 0.43 workgroups per CU at L = 16384 (8 buoys; 0.63 with 3), 0.66 .. 0.68 below
+    // (L = 32768, g_win_eo15: it wins from about 0.7 workgroups per CU on for 2 ... 16 buoys -- 0.67-0.79 x the four-step's time
+    // at 256 windows, 0.85-0.94 x at 192, 0.9-1.25 x at 128: profiles/r03_weo_sweep.log)
+    // (L = 16384 through k_win8kl: 242 us for anything up to one window per CU at 8 buoys, 50 us at 3, against 194 / 50 us at
+    // 64 windows and 290 / 64 us at 96 through the per-transform kernels -- tools/exp_k8_small.py: from 5/16 of a workgroup per CU)
+    const int upw = k.ws_upw > 0 ? k.ws_upw : 1;
+    const long ws_blocks = ((long)W + upw - 1) / upw;
+    // Bounded calls: of the whole-window kernels only k_win8kl has a bounded instantiation.  g_win_fused, g_win_scr,
+    // g_win_scr14 and g_win_eo15 have none: a bounded call that would take one of them takes the per-transform kernels
+    // instead, whose peak searches are bounded.  At the BASELINE shapes the fused kernels run either way (k_win, k_win8kl, k16_pairs).
+    const bool k8_route = k.k8 && (a.all_pairs || a.n_pairs <= k.max_pairs8);
+    const bool use_wscr = !a.weighted && k.wscr && (!a.bounded || k8_route) &&
+                          (k.wscr_always || ws_blocks >= (k.logL == 14 ? (k.k8 ? 5L : 7L) : 11L) * k.n_cus / 16);
+    if (use_wscr) {
+        // k_win8kl, g_win_eo15: the batch's last, partial round (W mod grid windows behind at least one full round) costs the
+        // kernel a whole round whatever its size -- k_win8kl 3.5 us per half transform: 245 us at 8 buoys, 50 at 3; g_win_eo15
+        // 12.6 us: 907 us at 8 buoys --, the four-step kernels about 30 us + 0.07 us per window and spectrum-or-pair (0.14 at
+        // L = 32768; tools/exp_k8_small.py: 8 buoys 104 us for 32 windows, 140 for 48; 3 buoys 43 / 47) plus four more launches.
+        // The cheaper one runs, on the same stream behind the full rounds: 8 buoys x 300 windows 507 -> 444 us, x 560
+        // 762 -> 710; 3 buoys never split.  Not with wscr = 2 (tests force the kernel).
+        auto partial_round = [&](double us_half, double base_us, double us_item, long wg16, double margin) {
+            if (k.wscr_always || k.ws_grid <= 0 || W <= k.ws_grid) return;
+            const int r = W % k.ws_grid;
+            const double round_us = us_half * (2.0 * k.n_buoys + 2.0 * a.n_pairs);
+            const double four_us = base_us + us_item * r * (double)(k.n_buoys + a.n_pairs);
+            if (r > 0 && (long)r * 16 < wg16 * k.n_cus && four_us < margin * round_us) p.n_tail = r;
+        };
+        p.route = k8_route ? kRouteKWin8 : k.logL == 15 ? kRouteWinEo15 : kRouteWinScr;
+        if (p.route == kRouteKWin8) partial_round(3.5, 40.0, 0.07, 5, 0.7);   // (5 buoys x 300: 234 split, 228 whole)
+        if (p.route == kRouteWinEo15 && k.ws_upw == 1) partial_round(12.6, 60.0, 0.14, 11, 0.85);
+        p.n_head = W - p.n_tail;
+        p.chunk = k.g_chunk;   // (of the partial round: plain or bounded calls only, integ = 1)
+        return p;
+    }
+    if (!a.weighted && k.wfused && !a.bounded) { p.route = kRouteWinFused; return p; }
+    p.route = (1L << k.logL) <= k.small_maxl ? kRouteSmallL : kRouteFourStep;
+    p.chunk = k.g_chunk / a.integ * a.integ;   // (integrated call: a chunk holds whole groups -- never a silent split of a group)
+    if (p.chunk == 0) p.refused = kRefuseIntegChunk;
+    else if (a.integ > 1 && p.route == kRouteFourStep && k.col_tile > (long)k.integ_max_per_thread * k.cols_threads)
+        p.refused = kRefuseIntegTile;
+    return p;
 }
 
 }  // namespace host

@@ -853,6 +853,17 @@ struct XcorrCall {
     bool weighted() const { return wt.band != nullptr || integ > 1 || refine > 0 || quality != nullptr; }
 };
 
+// Where a ctx's per-transform spectra lie once a chunk's forward kernels have run, and the launchers that write and read
+// them (N = 4096: k_fwd / k_pair_*; generic: g_fwd_small / g_pair_small or the four-step passes).  Filled by spec_view().
+struct SpecView {
+    int layout;  const void* base;          // RefLayout (refine.hpp); d_spec / g_spec
+    int logL, row_bits, unit_log2;          // log2 of the transform length; kRefRows: log2 of the rows per spectrum; the stored bins carry 2^unit_log2
+    // rows_fused: four-step, g_rows_fused does both row passes (forward: the column pass only)
+    int (*forward)(rmx_ctx*, const XcorrCall&, const void* d_iq, int w0, int wc, bool u8, const float2* rot, bool rows_fused);
+    int (*pairs)(rmx_ctx*, const XcorrCall&, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, bool use_rot,
+                 bool rows_fused);
+};
+
 // a small host array that kernels read: staged through pinned memory into a ctx-owned device buffer (stage_to_device)
 struct DevStage {
     int32_t* h = nullptr;  size_t h_elems = 0;
@@ -1124,21 +1135,19 @@ static int ensure_ref_pairs(rmx_ctx* c, int n_pairs) {
     return RMX_OK;
 }
 
-static int refine_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const void* spec, int logL, int row_bits, int unit_log2,
-                        int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak) {
-    {
-        const int rc_p = ensure_ref_pairs(c, n_pairs);
-        if (rc_p != RMX_OK) return rc_p;
-    }
+static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, int w0, int wc, int n_pairs, int* d_lag, float* d_frac,
+                        float* d_peak) {
+    const int rc_p = ensure_ref_pairs(c, n_pairs), logL = sv.logL, unit_log2 = sv.unit_log2;
+    if (rc_p != RMX_OK) return rc_p;
     RefineArgs a;
-    a.spec = static_cast<const float2*>(spec);
+    a.spec = static_cast<const float2*>(sv.base);
     a.pairs = c->rf_pairs;
     a.lb = call.lb;
     a.first_out = w0 / call.integ;
     a.n_buoys = c->n_buoys;
     a.n_pairs = n_pairs;
     a.logL = logL;
-    a.row_bits = row_bits;
+    a.row_bits = sv.row_bits;
     a.k = call.integ;
     a.scale = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the two stored forward scales 2^unit_log2
     const unsigned grid = (unsigned)(wc / call.integ * n_pairs);
@@ -1153,8 +1162,8 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const voi
             default: launch(k_refine<16, LAY>); break;
         }
     };
-    if (layout == kRefKfwd) with_u(std::integral_constant<int, kRefKfwd>{});
-    else if (layout == kRefSmall) with_u(std::integral_constant<int, kRefSmall>{});
+    if (sv.layout == kRefKfwd) with_u(std::integral_constant<int, kRefKfwd>{});
+    else if (sv.layout == kRefSmall) with_u(std::integral_constant<int, kRefSmall>{});
     else with_u(std::integral_constant<int, kRefRows>{});
     RMX_HIP(c, hipGetLastError());
     RMX_TM_END(c, kTkRefine);
@@ -1164,28 +1173,25 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const voi
 // The quality figures of a quality call (quality.hpp) on the chunk the pair kernels have just finished, in front of
 // refine_chunk: d_peak still holds the coarse peaks.  One workgroup per output slot of the chunk; nothing but
 // call.quality is written.
-static int quality_chunk(rmx_ctx* c, const XcorrCall& call, int layout, const void* spec, int logL, int row_bits, int unit_log2,
-                         int w0, int wc, int n_pairs, const float* d_peak) {
-    {
-        const int rc_p = ensure_ref_pairs(c, n_pairs);
-        if (rc_p != RMX_OK) return rc_p;
-    }
+static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, int w0, int wc, int n_pairs, const float* d_peak) {
+    const int rc_p = ensure_ref_pairs(c, n_pairs), logL = sv.logL, unit_log2 = sv.unit_log2;
+    if (rc_p != RMX_OK) return rc_p;
     QualityArgs a;
-    a.spec = static_cast<const float2*>(spec);
+    a.spec = static_cast<const float2*>(sv.base);
     a.pairs = c->rf_pairs;
     a.first_out = w0 / call.integ;
     a.n_buoys = c->n_buoys;
     a.n_pairs = n_pairs;
     a.logL = logL;
-    a.row_bits = row_bits;
+    a.row_bits = sv.row_bits;
     a.k = call.integ;
     a.sa = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the stored forward scale 2^unit_log2, squared
     a.sc = std::ldexp(1.0f, -logL - 4 * unit_log2);   // ... to the fourth power
     const unsigned grid = (unsigned)(wc / call.integ * n_pairs);
     RMX_TM_BEGIN(c);
     auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefThreads), 0, c->stream, a, d_peak, call.quality); };
-    if (layout == kRefKfwd) launch(k_quality<kRefKfwd>);
-    else if (layout == kRefSmall) launch(k_quality<kRefSmall>);
+    if (sv.layout == kRefKfwd) launch(k_quality<kRefKfwd>);
+    else if (sv.layout == kRefSmall) launch(k_quality<kRefSmall>);
     else launch(k_quality<kRefRows>);
     RMX_HIP(c, hipGetLastError());
     RMX_TM_END(c, kTkQuality);
@@ -1633,7 +1639,7 @@ static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool n
 // forward spectra of windows [w0, w0 + wc) of d_iq into g_spec (rot == nullptr) or, de-rotated by the phasor
 // table rot[N], into g_spec_r (rmx_caf_batch)
 static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot,
-                           bool cols_only = false) {
+                           bool cols_only) {
     using namespace gen;
     const int N = c->n_samples, logL = c->g_logL, B = c->n_buoys;
     const long L = 1L << logL;
@@ -1714,7 +1720,7 @@ static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, 
 // pair kernels of that chunk: X_i from g_spec, X_j from g_spec (use_rot false) or g_spec_r; results at
 // [(w0 + wl) * n_pairs + q] of the three output arrays
 static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak,
-                         bool use_rot, bool fused = false) {
+                         bool use_rot, bool fused) {
     using namespace gen;
     const int N = c->n_samples, logL = c->g_logL, B = c->n_buoys;
     const long L = 1L << logL;
@@ -1824,20 +1830,130 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     return RMX_OK;
 }
 
-// windows [w0, w0 + n) of a batch through the four-step kernels (the partial last round behind a whole-window kernel's full
-// rounds, same stream): buffers on first need, chunks as in generic_batch's own loop
-static int four_step_windows(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w_first, int n, int n_pairs, int* d_lag, float* d_frac,
-                             float* d_peak, bool u8) {
-    int rc = generic_ensure(c, n_pairs, true, true);
-    if (rc) return rc;
-    for (int w0 = w_first; w0 < w_first + n; w0 += c->g_chunk) {
-        const int wc = w_first + n - w0 < c->g_chunk ? w_first + n - w0 : c->g_chunk;
-        const long fused_blocks = c->g_fused ? (long)wc * (1L << c->g_logL1) / (gen::kGThreads / ((1 << c->g_logL2) >> 4)) : 0;
-        const bool fused = c->g_fused && (fused_blocks >= 2L * c->n_cus || c->g_fused_always);
-        rc = generic_forward(c, call, d_iq, w0, wc, u8, nullptr, fused);
-        if (rc) return rc;
-        rc = generic_pairs(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
-        if (rc) return rc;
+// N = 4096, unfused path: forward spectra of windows [w0, w0 + wc) into d_spec (rot == nullptr) or, de-rotated by
+// the phasor table rot[N], into d_spec_r (rmx_caf_batch); then the pair kernels over the plan's pair list
+static int fwd4096(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot, int n_bins = 1) {
+    const long first_item = (long)w0 * c->n_buoys;
+    const int wrap = n_bins > 1 ? wc * c->n_buoys : 0;
+    const int n_items = wc * c->n_buoys * n_bins;
+    if (rot) {
+        const size_t nb = n_bins > 1 ? (size_t)n_items * (8 * kThreads) * sizeof(float4)
+                                     : (size_t)(wc < c->chunk_windows ? c->chunk_windows : wc) * c->n_buoys * (8 * kThreads) * sizeof(float4);
+        if (c->spec_r_bytes < nb) {
+            RMX_HIP(c, hipStreamSynchronize(c->stream));
+            if (c->d_spec_r) (void)hipFree(c->d_spec_r);
+            c->d_spec_r = nullptr;
+            c->spec_r_bytes = 0;
+            RMX_HIP(c, hipMalloc((void**)&c->d_spec_r, nb));
+            c->spec_r_bytes = nb;
+        }
+    }
+    float4* dst = rot ? c->d_spec_r : c->d_spec;
+    RMX_TM_BEGIN(c);
+    auto launch = [&](auto kern, const float2* a_rot, int a_wrap, auto... wt) {
+        hipLaunchKernelGGL(kern, dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1, c->d_tw2, first_item,
+                           1.0f, a_rot, a_wrap, wt...);
+    };
+    with_u8(u8, [&](auto U) {
+        constexpr bool U8 = decltype(U)::value;
+        if (call.wt.band) {   // weighted call (never with rot): the stored bins carry the TW1 scale
+            XWeight a_wt = call.wt;
+            a_wt.unit = (float)kTw1Scale;
+            launch(k_fwd<U8, XWeight>, nullptr, 0, a_wt);
+        } else
+            launch(k_fwd<U8>, rot, wrap);
+    });
+    RMX_HIP(c, hipGetLastError());
+    RMX_TM_END(c, kTkFwd4096);
+    return RMX_OK;
+}
+static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, float out_scale,
+                     bool use_rot, int n_bins = 1) {
+    const int n_parts = c->plan_n_parts;
+    const int i_wrap = n_bins > 1 ? wc : 0;     // (all hypotheses in one launch: virtual window = hypothesis * wc + window)
+    wc *= n_bins;
+    const int xcd_map = (wc % 8 == 0) ? 1 : 0;
+    const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
+    // the streaming and the resident kernel (which takes c->dbg as well), each with or without its trailing structs
+    auto str = [&](auto kern, int windows, int xmap, long first, int wrap, auto... tail) {
+        hipLaunchKernelGGL(kern, dim3(windows * n_parts), dim3(kThreads), kLdsBytes, c->stream, (const float4*)c->d_spec, spec_j,
+                           c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xmap, first, out_scale,
+                           d_lag, d_frac, d_peak, wrap, tail...);
+    };
+    auto res = [&](auto kern, auto... lb) {
+        hipLaunchKernelGGL(kern, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream, (const float4*)c->d_spec, spec_j,
+                           c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, (long)w0,
+                           out_scale, d_lag, d_frac, d_peak, c->dbg, i_wrap, lb...);
+    };
+    RMX_TM_BEGIN(c);
+    if (call.integrated()) {
+        // always the streaming kernel's integrating instantiation, one work item per (group, pair); w0 and wc are whole
+        // groups, the bounds per group
+        const int gc = wc / call.integ;
+        str(k_pair_str<LagBounds, Integrate>, gc, (gc % 8 == 0) ? 1 : 0, (long)(w0 / call.integ), 0, call.lb, Integrate{call.integ});
+    } else if (c->resident) {
+        if (call.bounded()) res(k_pair_res<LagBounds>, call.lb); else res(k_pair_res<>);
+    } else {
+        if (call.bounded()) str(k_pair_str<LagBounds>, wc, xcd_map, (long)w0, i_wrap, call.lb);
+        else str(k_pair_str<>, wc, xcd_map, (long)w0, i_wrap);
+    }
+    RMX_HIP(c, hipGetLastError());
+    RMX_TM_END(c, kTkPair4096);
+    return RMX_OK;
+}
+static_assert(kL == 1 << 13, "spec_view and out_scale4096 say log2 kL = 13");
+static float out_scale4096() {
+    // power-of-two scaling: the TW1 table carries 2^-6, so the spectra carry 2^-6, the product 2^-12 and
+    // the inverse transform (which uses the table once more) 2^-18; the taps get the remaining factor
+    return std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 13);
+}
+
+static SpecView spec_view(const rmx_ctx* c) {
+    if (!c->generic)   // (the forward scale 2^-6 rides on the TW1 table)
+        return {kRefKfwd, c->d_spec, 13 /* log2 kL */, 0, -kTw1ScaleLog2,
+                [](rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot, bool) {
+                    return fwd4096(c, call, d_iq, w0, wc, u8, rot);
+                },
+                [](rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, bool use_rot, bool) {
+                    return pairs4096(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, out_scale4096(), use_rot);
+                }};
+    const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
+    return {small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1, -(c->g_logL / 2), generic_forward, generic_pairs};
+}
+
+// what the planner (host_plan.hpp: plan_route) needs to know of this ctx
+static_assert(gen::kGThreads == 256, "host::route_rows_fused counts g_rows_fused's units per workgroup of 256 threads");
+static host::RouteCaps route_caps(const rmx_ctx* c) {
+    host::RouteCaps k;
+    k.n_cus = c->n_cus;  k.n_buoys = c->n_buoys;  k.generic = c->generic;
+    k.fused = c->fused;  k.small_batch = c->small_batch;  k.chunk_windows = c->chunk_windows;
+    k.ppb_user = c->ppb_user ? c->pairs_per_block : 0;
+    if (!c->generic) return k;
+    k.logL = c->g_logL;  k.logL1 = c->g_logL1;  k.logL2 = c->g_logL2;  k.small_maxl = kGenSmallMaxL;
+    k.g_chunk = c->g_chunk;  k.wfused = c->g_wfused;  k.wscr = c->g_wscr;  k.wscr_always = c->g_wscr_always;
+    k.ws_upw = c->g_ws_upw;  k.ws_grid = c->g_ws_grid;  k.k8 = c->g_k8;  k.k16 = c->g_k16;
+    if (c->g_k16 == 1) k.k16_min_windows = c->knobs.get_or("k16_min_windows", 0);
+    k.g_fused = c->g_fused;  k.g_fused_always = c->g_fused_always;
+    k.max_pairs8 = k8::kMaxPairs8;  k.max_pairs16 = k16::kMaxPairs16;  k.integ_max_per_thread = kIntegMaxPerThread;
+    k.col_tile = (1L << c->g_logL1) << host_col_log_t(c, c->g_logL1);  k.cols_threads = gen_cols_threads(c, c->g_logL1);   // (four-step)
+    return k;
+}
+
+// Windows [w_first, w_first + n) through the per-transform kernels, `chunk` windows at a time (the buffers are there): the
+// forward spectra, the pair kernels (with_pairs false: quality_pass, whose lags are there already), then k_quality on the
+// spectra and the coarse peaks, then k_refine, which overwrites them.  A qualified or refined call is weighted(): its
+// chunks never take g_rows_fused, so the view holds every spectrum of the chunk.
+static int run_chunks(rmx_ctx* c, const XcorrCall& call, const host::RouteCaps& caps, const void* d_iq, int w_first, int n, int chunk,
+                      int n_pairs, int* d_lag, float* d_frac, float* d_peak, bool u8, bool with_pairs = true) {
+    const SpecView sv = spec_view(c);
+    for (int w0 = w_first; w0 < w_first + n; w0 += chunk) {
+        const int wc = w_first + n - w0 < chunk ? w_first + n - w0 : chunk;
+        const bool rows_fused = with_pairs && host::route_rows_fused(caps, call.weighted(), wc);
+        int rc = sv.forward(c, call, d_iq, w0, wc, u8, nullptr, rows_fused);
+        if (rc == RMX_OK && with_pairs) rc = sv.pairs(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, rows_fused);
+        if (rc == RMX_OK && call.qualified()) rc = quality_chunk(c, call, sv, w0, wc, n_pairs, d_peak);
+        if (rc == RMX_OK && call.refined()) rc = refine_chunk(c, call, sv, w0, wc, n_pairs, d_lag, d_frac, d_peak);
+        if (rc != RMX_OK) return rc;
     }
     return RMX_OK;
 }
@@ -1845,11 +1961,10 @@ static int four_step_windows(rmx_ctx* c, const XcorrCall& call, const void* d_iq
 // N = 16384 through k16_fwd / k16_pairs (kwin16k.hpp): per chunk of g_ws_grid windows (the spectrum scratch holds that many)
 // one forward launch -- (window, buoy) items over at most one workgroup per CU -- and one pair launch of 8 S workgroups,
 // S = workgroups per XCD.  No per-window state survives the chunk.
-static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_windows, int n_pairs, int* d_lag, float* d_frac, float* d_peak,
-                     bool u8) {
+static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_windows, int chunk, int n_pairs, int* d_lag, float* d_frac,
+                     float* d_peak, bool u8) {
     const int B = c->n_buoys;
     const float out_scale = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 15);
-    const int chunk = c->g_ws_grid;
     const k16::Pair2* prs = reinterpret_cast<const k16::Pair2*>(c->g_pairs);
     for (int w0 = 0; w0 < n_windows; w0 += chunk) {
         const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
@@ -1889,178 +2004,91 @@ static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_
     return RMX_OK;
 }
 
-static int generic_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_windows, int n_pairs, int* d_lag, float* d_frac,
-                         float* d_peak, bool u8) {
-    // N = 16384 on k_win's network (kwin16k.hpp): fine-grained items, so no partial last round and a low minimum batch -- its
-    // two launches cost about 40 us whatever the size, the four-step kernels 26 us for one window: from about 100 transforms
-    // (windows x (buoys + pairs)) on it wins (tools/exp_k16_sweep.py: 3 buoys from 16 windows, 5 from 8, 8 from 1).  wscr = 2
-    // (tests: "the whole-window kernel, whatever the batch") keeps g_win_eo15, as do pair lists beyond the kernel's LDS copy
-    // Weighted calls (rmx_xcorr_batch_weighted) weight the spectra where the per-transform forward kernels store them:
-    // g_fwd_small up to L = small_maxl, g_cols_fwd + the forward g_rows above.  The whole-window kernels (g_win_*,
-    // k_win8kl), k16_fwd and g_rows_fused keep their spectra to themselves and are never taken.
-    // Integrated calls (rmx_xcorr_batch_integrated) sum over windows inside the per-transform pair kernels: the same routes.
-    const bool weighted = call.weighted();
-    if (!weighted && c->g_k16 && c->g_logL == 15 && n_pairs <= k16::kMaxPairs16 &&
-        (c->g_k16 == 2 || (!c->g_wscr_always &&
-                           n_windows >= (int)c->knobs.get_or("k16_min_windows", (100 + c->n_buoys + n_pairs - 1) / (c->n_buoys + n_pairs))))) {
-        const int rc16 = generic_ensure(c, n_pairs, false, false);
-        if (rc16) return rc16;
-        return k16_batch(c, call, d_iq, n_windows, n_pairs, d_lag, d_frac, d_peak, u8);
-    }
-    // g_win_scr runs a window's B + P transforms one after the other in one workgroup: batches that leave most of the chip
-    // without a workgroup are better off in the per-transform kernels below (8 buoys x 8 windows of 8192: 0.32 vs 0.05 ms).
-    // Measured crossovers (tools/smallw.sh): 0.43 workgroups per CU at L = 16384 (8 buoys; 0.63 with 3), 0.66 .. 0.68 below
-    const long ws_blocks = ((long)n_windows + (c->g_ws_upw > 0 ? c->g_ws_upw : 1) - 1) / (c->g_ws_upw > 0 ? c->g_ws_upw : 1);
-    // (L = 32768, g_win_eo15: it wins from about 0.7 workgroups per CU on for 2 ... 16 buoys -- 0.67-0.79 x the four-step's time
-    // at 256 windows, 0.85-0.94 x at 192, 0.9-1.25 x at 128: profiles/r03_weo_sweep.log)
-    // (L = 16384 through k_win8kl: 242 us for anything up to one window per CU at 8 buoys, 50 us at 3, against 194 / 50 us at
-    // 64 windows and 290 / 64 us at 96 through the per-transform kernels -- tools/exp_k8_small.py: from 5/16 of a workgroup per CU)
-    const bool def_list_b = c->plan_all_pairs && n_pairs == c->n_buoys * (c->n_buoys - 1) / 2;
-    // Bounded calls (rmx_xcorr_batch_bounded): of the whole-window kernels only k_win8kl has a bounded instantiation.
-    // g_win_fused, g_win_scr, g_win_scr14 and g_win_eo15 have none: a bounded call that would take one of them takes the
-    // per-transform kernels instead (g_fwd_small + g_pair_small up to L = small_maxl, the four-step kernels above), whose
-    // peak searches are bounded.  At the BASELINE shapes the fused kernels run either way (k_win, k_win8kl, k16_pairs).
-    const bool bounded = call.bounded();
-    const bool k8_route = c->g_k8 && (def_list_b || n_pairs <= k8::kMaxPairs8);
-    const bool use_wscr = !weighted && c->g_wscr && (!bounded || k8_route) &&
-                          (c->g_wscr_always || ws_blocks >= (c->g_logL == 14 ? (c->g_k8 ? 5L : 7L) : 11L) * c->n_cus / 16);
-    const bool use_wfused = !weighted && c->g_wfused && !bounded;
-    const bool whole_window = use_wfused || use_wscr;   // those kernels keep no per-window state in HBM
-    int rc = generic_ensure(c, n_pairs, !whole_window, !whole_window);
-    if (rc) return rc;
-    if (use_wscr) {
-        const int logL = c->g_logL, hs = logL / 2;
-        const void* a_iq = d_iq;
-        float4* a_scr = c->g_ws_scratch;
-        const float2* a_tw = c->g_tw_win;
-        int a_nb = c->n_buoys, a_np = n_pairs;
-        long a_nw = n_windows, a_first = 0;
-        float a_fs = std::ldexp(1.0f, -hs), a_os = std::ldexp(1.0f, -(logL - 2 * hs));
-        const gen::GPair* a_pairs = c->g_pairs;
-        long grid = ((long)n_windows + c->g_ws_upw - 1) / c->g_ws_upw;
-        if (grid > c->g_ws_grid) grid = c->g_ws_grid;
-        const bool def_list = c->plan_all_pairs && n_pairs == c->n_buoys * (c->n_buoys - 1) / 2;
-        if (c->g_k8 && (def_list || n_pairs <= k8::kMaxPairs8)) {   // N = 8192 on k_win's network (kwin8k.hpp)
-            const float out_scale = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 14);
-            const k8::Pair2* prs = def_list ? nullptr : reinterpret_cast<const k8::Pair2*>(c->g_pairs);
-            const int stag = (int)c->knobs.get_or("stag", 1);
-            // The batch's last, partial round (W mod CUs windows behind at least one full round) costs this kernel a whole
-            // round whatever its size -- 3.5 us per half transform: 245 us at 8 buoys, 50 at 3 --, the four-step kernels about
-            // 30 us + 0.07 us per window and spectrum-or-pair (tools/exp_k8_small.py: 8 buoys 104 us for 32 windows, 140 for 48;
-            // 3 buoys 43 / 47) plus four more launches.  The cheaper one runs, on the same stream behind the full rounds:
-            // 8 buoys x 300 windows 507 -> 444 us, x 560 762 -> 710; 3 buoys never split.  Not with wscr = 2 (tests force the kernel).
-            int n_tail = 0;
-            if (!c->g_wscr_always && n_windows > c->g_ws_grid) {
-                const int r = n_windows % c->g_ws_grid;
-                const double round_us = 3.5 * (2.0 * c->n_buoys + 2.0 * n_pairs);
-                const double four_us = 40.0 + 0.07 * r * (double)(c->n_buoys + n_pairs);
-                if (r > 0 && (long)r * 16 < 5L * c->n_cus && four_us < 0.7 * round_us) n_tail = r;   // (5 buoys x 300: 234 split, 228 whole)
-            }
-            const int n_head = n_windows - n_tail;
-            n_windows = n_head;                 // (the launches below take the full rounds)
-            RMX_TM_BEGIN(c);
-            auto launch = [&](auto kern, size_t lds, auto... lb) {
-                hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, c->stream, d_iq, c->g_ws_scratch, c->g_k8_tw1,
-                                   c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag, d_frac, d_peak, n_windows, stag, lb...);
-            };
-            with_u8(u8, [&](auto U) {
-                constexpr bool U8 = decltype(U)::value;
-#ifdef RMX_EXPERIMENTS
-                if (c->g_k8_kind == 2) launch(k8::k_win8k<U8>, k8::kLds8Bytes);
-                else
-#endif
-                if (bounded) launch(k8::k_win8kl<U8, LagBounds>, k8::kLdsLBytes, call.lb); else launch(k8::k_win8kl<U8>, k8::kLdsLBytes);
-            });
-            RMX_HIP(c, hipGetLastError());
-            RMX_TM_END(c, kTkWindow);
-            if (n_tail) return four_step_windows(c, call, d_iq, n_head, n_tail, n_pairs, d_lag, d_frac, d_peak, u8);
-            return RMX_OK;
-        }
-        if (logL == 15) {                          // g_win_eo15: one more table
-            // (the partial last round as above: a round costs this kernel 12.6 us per half transform -- 907 us at 8 buoys --, the
-            // four-step kernels about 0.14 us per window and spectrum-or-pair at this length)
-            int n_tail = 0;
-            if (!c->g_wscr_always && n_windows > c->g_ws_grid && c->g_ws_upw == 1) {
-                const int r = n_windows % c->g_ws_grid;
-                const double round_us = 12.6 * (2.0 * c->n_buoys + 2.0 * n_pairs);
-                const double four_us = 60.0 + 0.14 * r * (double)(c->n_buoys + n_pairs);
-                if (r > 0 && (long)r * 16 < 11L * c->n_cus && four_us < 0.85 * round_us) n_tail = r;
-            }
-            const int n_head = n_windows - n_tail;
-            a_nw = n_head;
-            const float2* a_twl = c->g_tw_l;
-            void* args[] = {&a_iq, &a_scr, &a_tw, &a_twl, &a_nb, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
-            RMX_TM_BEGIN(c);
-            RMX_HIP(c, hipLaunchKernel(c->g_ws_fn[u8 ? 1 : 0], dim3((unsigned)grid), dim3(c->g_ws_thr), args, c->g_ws_lds, c->stream));
-            RMX_TM_END(c, kTkWindow);
-            if (n_tail) return four_step_windows(c, call, d_iq, n_head, n_tail, n_pairs, d_lag, d_frac, d_peak, u8);
-            return RMX_OK;
-        }
-        void* args[] = {&a_iq, &a_scr, &a_tw, &a_nb, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_ws_fn[u8 ? 1 : 0], dim3((unsigned)grid), dim3(c->g_ws_thr), args, c->g_ws_lds, c->stream));
-        RMX_TM_END(c, kTkWindow);
-        return RMX_OK;
-    }
-    if (use_wfused) {
-        using namespace gen;
-        const int logL = c->g_logL, B = c->n_buoys, hs = logL / 2;
-        const bool def_plan = c->plan_all_pairs && n_pairs == B * (B - 1) / 2;
-        const int upw = kGThreads / ((1 << logL) >> 4);
-        const void* a_iq = d_iq;
+// a refusal of the planner as the caller reads it
+static int route_refusal(rmx_ctx* c, const host::RoutePlan& plan, const host::RouteCaps& k, int integ) {
+    if (plan.refused == host::kRouteOk) return RMX_OK;
+    if (plan.refused == host::kRefuseIntegChunk)
+        return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
+                    integ, k.generic ? k.g_chunk : k.chunk_windows);
+    return fail(c, RMX_E_UNSUPPORTED, "integrated call: a column tile of %ld elements on %d threads is more than %d per thread",
+                k.col_tile, k.cols_threads, k.integ_max_per_thread);
+}
+
+// The generic lengths: executes the route that host::plan_route chose for the call `rq` describes (host_plan.hpp has the
+// rules and the measurements behind them).
+static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps, const host::RouteCall& rq, host::RoutePlan plan,
+                         const void* d_iq, int* d_lag, float* d_frac, float* d_peak, bool u8) {
+    using namespace host;
+    const int n_pairs = rq.n_pairs, logL = c->g_logL, hs = logL / 2;
+    // device buffers on first need; a failed allocation halves g_chunk, and the plan follows (the route does not depend on it)
+    auto ensure = [&](bool need_spec, bool need_pairbufs) -> int {
+        const int rc_e = generic_ensure(c, n_pairs, need_spec, need_pairbufs);
+        if (rc_e == RMX_OK && c->g_chunk != caps.g_chunk) { caps.g_chunk = c->g_chunk; plan = plan_route(caps, rq); }
+        return rc_e;
+    };
+    // the whole-window kernels and k16 keep no per-window state in HBM
+    const bool per_transform = plan.route == kRouteSmallL || plan.route == kRouteFourStep;
+    int rc = ensure(per_transform, per_transform);
+    if (rc == RMX_OK) rc = route_refusal(c, plan, caps, call.integ);
+    if (rc != RMX_OK) return rc;
+    if (per_transform) return run_chunks(c, call, caps, d_iq, 0, rq.n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
+    if (plan.route == kRouteK16) return k16_batch(c, call, d_iq, rq.n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
+    const void* a_iq = d_iq;
+    long a_nw = plan.n_head, a_first = 0;
+    float a_fs = std::ldexp(1.0f, -hs), a_os = std::ldexp(1.0f, -(logL - 2 * hs));
+    const gen::GPair* a_pairs = c->g_pairs;
+    int a_nb = c->n_buoys, a_np = n_pairs;
+    if (plan.route == kRouteWinFused) {
+        const int upw = gen::kGThreads / ((1 << logL) >> 4), def = rq.all_pairs ? 1 : 0;
         const float2* a_tw = c->g_tw;
-        long a_nw = n_windows, a_first = 0;
-        float a_fs = std::ldexp(1.0f, -hs), a_os = std::ldexp(1.0f, -(logL - 2 * hs));
-        const GPair* a_pairs = c->g_pairs;
-        int a_np = n_pairs;
         void* args[] = {&a_iq, &a_tw, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
         RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_wf_fn[def_plan ? 1 : 0][u8 ? 1 : 0], dim3((unsigned)((n_windows + upw - 1) / upw)),
-                                   dim3(kGThreads), args, c->g_wf_lds[def_plan ? 1 : 0], c->stream));
+        RMX_HIP(c, hipLaunchKernel(c->g_wf_fn[def][u8 ? 1 : 0], dim3((unsigned)((rq.n_windows + upw - 1) / upw)), dim3(gen::kGThreads), args,
+                                   c->g_wf_lds[def], c->stream));
         RMX_TM_END(c, kTkWindow);
         return RMX_OK;
     }
-    // (integrated call: a chunk holds whole groups -- never a silent split of a group)
-    const int chunk = c->g_chunk / call.integ * call.integ;
-    if (chunk == 0)
-        return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
-                    call.integ, c->g_chunk);
-    if (call.integrated() && (1L << c->g_logL) > kGenSmallMaxL &&
-        ((1L << c->g_logL1) << host_col_log_t(c, c->g_logL1)) > (long)kIntegMaxPerThread * gen_cols_threads(c, c->g_logL1))
-        return fail(c, RMX_E_UNSUPPORTED, "integrated call: a column tile of %ld elements on %d threads is more than %d per thread",
-                    (1L << c->g_logL1) << host_col_log_t(c, c->g_logL1), gen_cols_threads(c, c->g_logL1), kIntegMaxPerThread);
-    for (int w0 = 0; w0 < n_windows; w0 += chunk) {
-        const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
-        // the fused row kernel when its (window, row block) units fill the chip at least twice: below that (cfg1's single
-        // window: 128 workgroups) its long serial chain per unit loses to the two-kernel passes' wider grids (57 vs 47 us)
-        const long fused_blocks = c->g_fused ? (long)wc * (1L << c->g_logL1) / (gen::kGThreads / ((1 << c->g_logL2) >> 4)) : 0;
-        const bool fused = !weighted && c->g_fused && (1L << c->g_logL) > kGenSmallMaxL &&
-                           (fused_blocks >= 2L * c->n_cus || c->g_fused_always);
-        rc = generic_forward(c, call, d_iq, w0, wc, u8, nullptr, fused);
-        if (rc) return rc;
-        rc = generic_pairs(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, false, fused);
-        if (rc) return rc;
-        if (call.qualified()) {   // (weighted() like a refined call; in front of k_refine, which overwrites the coarse peak)
-            const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
-            rc = quality_chunk(c, call, small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1,
-                               -(c->g_logL / 2), w0, wc, n_pairs, d_peak);
-            if (rc) return rc;
-        }
-        if (call.refined()) {   // (a refined call is weighted(): never fused, g_spec holds this chunk's spectra, scaled 2^-(logL / 2))
-            const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
-            rc = refine_chunk(c, call, small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1,
-                              -(c->g_logL / 2), w0, wc, n_pairs, d_lag, d_frac, d_peak);
-            if (rc) return rc;
-        }
+    // g_win_scr*, g_win_eo15, k_win8kl: persistent workgroups over the ctx's scratch; the full rounds here, the planned
+    // partial round behind them through the per-transform kernels on the same stream
+    float4* a_scr = c->g_ws_scratch;
+    const float2 *a_tw = c->g_tw_win, *a_twl = c->g_tw_l;
+    long grid = ((long)rq.n_windows + c->g_ws_upw - 1) / c->g_ws_upw;
+    if (grid > c->g_ws_grid) grid = c->g_ws_grid;
+    RMX_TM_BEGIN(c);
+    if (plan.route == kRouteKWin8) {            // N = 8192 on k_win's network (kwin8k.hpp)
+        const float out_scale = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 14);
+        const k8::Pair2* prs = rq.all_pairs ? nullptr : reinterpret_cast<const k8::Pair2*>(c->g_pairs);
+        const int stag = (int)c->knobs.get_or("stag", 1);
+        auto launch = [&](auto kern, size_t lds, auto... lb) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, c->stream, d_iq, c->g_ws_scratch, c->g_k8_tw1,
+                               c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag, d_frac, d_peak, plan.n_head, stag, lb...);
+        };
+        with_u8(u8, [&](auto U) {
+            constexpr bool U8 = decltype(U)::value;
+#ifdef RMX_EXPERIMENTS
+            if (c->g_k8_kind == 2) launch(k8::k_win8k<U8>, k8::kLds8Bytes);
+            else
+#endif
+            if (call.bounded()) launch(k8::k_win8kl<U8, LagBounds>, k8::kLdsLBytes, call.lb); else launch(k8::k_win8kl<U8>, k8::kLdsLBytes);
+        });
+        RMX_HIP(c, hipGetLastError());
+    } else {                                    // (g_win_eo15: one more table)
+        void* args15[] = {&a_iq, &a_scr, &a_tw, &a_twl, &a_nb, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
+        void* args[] = {&a_iq, &a_scr, &a_tw, &a_nb, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
+        RMX_HIP(c, hipLaunchKernel(c->g_ws_fn[u8 ? 1 : 0], dim3((unsigned)grid), dim3(c->g_ws_thr), plan.route == kRouteWinEo15 ? args15 : args,
+                                   c->g_ws_lds, c->stream));
     }
-    return RMX_OK;
+    RMX_TM_END(c, kTkWindow);
+    if (!plan.n_tail) return RMX_OK;
+    rc = ensure(true, true);
+    return rc != RMX_OK ? rc : run_chunks(c, call, caps, d_iq, plan.n_head, plan.n_tail, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
 }
 
 }  // namespace rmx
 
 using namespace rmx;
 
-static constexpr int kHostSubChunk = 512;   // windows per copy/kernel step of the pipelined host-pointer path
+using host::kHostSubChunk;
 
 extern "C" {
 
@@ -2317,86 +2345,6 @@ static int ensure_spec(rmx_ctx* c, long windows) {
     return RMX_OK;
 }
 
-// N = 4096, unfused path: forward spectra of windows [w0, w0 + wc) into d_spec (rot == nullptr) or, de-rotated by
-// the phasor table rot[N], into d_spec_r (rmx_caf_batch); then the pair kernels over the plan's pair list
-static int fwd4096(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot, int n_bins = 1) {
-    const long first_item = (long)w0 * c->n_buoys;
-    const int wrap = n_bins > 1 ? wc * c->n_buoys : 0;
-    const int n_items = wc * c->n_buoys * n_bins;
-    if (rot) {
-        const size_t nb = n_bins > 1 ? (size_t)n_items * (8 * kThreads) * sizeof(float4)
-                                     : (size_t)(wc < c->chunk_windows ? c->chunk_windows : wc) * c->n_buoys * (8 * kThreads) * sizeof(float4);
-        if (c->spec_r_bytes < nb) {
-            RMX_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->d_spec_r) (void)hipFree(c->d_spec_r);
-            c->d_spec_r = nullptr;
-            c->spec_r_bytes = 0;
-            RMX_HIP(c, hipMalloc((void**)&c->d_spec_r, nb));
-            c->spec_r_bytes = nb;
-        }
-    }
-    float4* dst = rot ? c->d_spec_r : c->d_spec;
-    RMX_TM_BEGIN(c);
-    auto launch = [&](auto kern, const float2* a_rot, int a_wrap, auto... wt) {
-        hipLaunchKernelGGL(kern, dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1, c->d_tw2, first_item,
-                           1.0f, a_rot, a_wrap, wt...);
-    };
-    with_u8(u8, [&](auto U) {
-        constexpr bool U8 = decltype(U)::value;
-        if (call.wt.band) {   // weighted call (never with rot): the stored bins carry the TW1 scale
-            XWeight a_wt = call.wt;
-            a_wt.unit = (float)kTw1Scale;
-            launch(k_fwd<U8, XWeight>, nullptr, 0, a_wt);
-        } else
-            launch(k_fwd<U8>, rot, wrap);
-    });
-    RMX_HIP(c, hipGetLastError());
-    RMX_TM_END(c, kTkFwd4096);
-    return RMX_OK;
-}
-static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, float out_scale,
-                     bool use_rot, int n_bins = 1) {
-    const int n_parts = c->plan_n_parts;
-    const int i_wrap = n_bins > 1 ? wc : 0;     // (all hypotheses in one launch: virtual window = hypothesis * wc + window)
-    wc *= n_bins;
-    const int xcd_map = (wc % 8 == 0) ? 1 : 0;
-    const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
-    // the streaming and the resident kernel (which takes c->dbg as well), each with or without its trailing structs
-    auto str = [&](auto kern, int windows, int xmap, long first, int wrap, auto... tail) {
-        hipLaunchKernelGGL(kern, dim3(windows * n_parts), dim3(kThreads), kLdsBytes, c->stream, (const float4*)c->d_spec, spec_j,
-                           c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xmap, first, out_scale,
-                           d_lag, d_frac, d_peak, wrap, tail...);
-    };
-    auto res = [&](auto kern, auto... lb) {
-        hipLaunchKernelGGL(kern, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream, (const float4*)c->d_spec, spec_j,
-                           c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, (long)w0,
-                           out_scale, d_lag, d_frac, d_peak, c->dbg, i_wrap, lb...);
-    };
-    RMX_TM_BEGIN(c);
-    if (call.integrated()) {
-        // always the streaming kernel's integrating instantiation, one work item per (group, pair); w0 and wc are whole
-        // groups, the bounds per group
-        const int gc = wc / call.integ;
-        str(k_pair_str<LagBounds, Integrate>, gc, (gc % 8 == 0) ? 1 : 0, (long)(w0 / call.integ), 0, call.lb, Integrate{call.integ});
-    } else if (c->resident) {
-        if (call.bounded()) res(k_pair_res<LagBounds>, call.lb); else res(k_pair_res<>);
-    } else {
-        if (call.bounded()) str(k_pair_str<LagBounds>, wc, xcd_map, (long)w0, i_wrap, call.lb);
-        else str(k_pair_str<>, wc, xcd_map, (long)w0, i_wrap);
-    }
-    RMX_HIP(c, hipGetLastError());
-    RMX_TM_END(c, kTkPair4096);
-    return RMX_OK;
-}
-static_assert(kL == 1 << 13, "refine_chunk is handed log2 kL");
-static float out_scale4096() {
-    // power-of-two scaling: the TW1 table carries 2^-6, so the spectra carry 2^-6, the product 2^-12 and
-    // the inverse transform (which uses the table once more) 2^-18; the taps get the remaining factor
-    int logl = 0;
-    while ((1 << logl) < kL) ++logl;
-    return std::ldexp(1.0f, 3 * kTw1ScaleLog2 - logl);
-}
-
 // host-pointer results: the three arrays live in ONE device block.  Small batches (the seam's one frequency group per
 // call) come back as ONE copy into pinned memory + three memcpys instead of three pageable copies (each of which the
 // runtime stages and synchronises on its own); large ones keep the three direct copies.
@@ -2449,11 +2397,6 @@ static int ensure_quality(rmx_ctx* c, size_t elems) {
     RMX_HIP(c, hipMalloc((void**)&c->d_quality, elems * sizeof(float)));
     c->d_quality_elems = elems;
     return RMX_OK;
-}
-
-// N = 4096: the model of host_plan.hpp with this ctx's numbers
-static double split_cost4096(const rmx_ctx* c, int n_windows, int n_pairs, int* ppb) {
-    return host::split_cost4096(c->n_cus, c->n_buoys, n_pairs, n_windows, c->ppb_user ? c->pairs_per_block : 0, ppb);
 }
 
 // ---- what the correlation entries share ----------------------------------------------------------------------------
@@ -2519,11 +2462,10 @@ static int stage_to_device(rmx_ctx* c, DevStage* s, const int32_t* src, size_t e
 // quality -- the whole-window kernels included, which keep their spectra to themselves --, so they are that call's
 // outputs bit for bit; here the per-transform forward kernels store the spectra chunk by chunk and k_quality reads them
 // and the peaks.  The input is on the device (the caller's, or the ctx's copy the first pass made).
-static int quality_pass(rmx_ctx* c, const XcorrCall& req, const void* iq, int n_windows, int n_pairs, const float* peak,
-                        unsigned flags) {
+static int quality_pass(rmx_ctx* c, const XcorrCall& req, const void* iq, int n_windows, int n_pairs, float* peak, unsigned flags) {
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
     const void* d_iq = in_dev ? iq : c->d_in;
-    const float* d_peak = out_dev ? peak : c->d_peak;
+    float* d_peak = out_dev ? peak : c->d_peak;
     const size_t out_elems = (size_t)n_windows * n_pairs;
     XcorrCall call = req;
     if (!out_dev) {
@@ -2531,30 +2473,12 @@ static int quality_pass(rmx_ctx* c, const XcorrCall& req, const void* iq, int n_
         if (rc_q != RMX_OK) return rc_q;
         call.quality = c->d_quality;
     }
-    int rc;
-    if (c->generic) {
-        rc = rmx::generic_ensure(c, n_pairs, true, true);
-        if (rc != RMX_OK) return rc;
-        const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
-        for (int w0 = 0; w0 < n_windows; w0 += c->g_chunk) {
-            const int wc = n_windows - w0 < c->g_chunk ? n_windows - w0 : c->g_chunk;
-            rc = rmx::generic_forward(c, call, d_iq, w0, wc, u8, nullptr);
-            if (rc != RMX_OK) return rc;
-            rc = quality_chunk(c, call, small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1,
-                               -(c->g_logL / 2), w0, wc, n_pairs, d_peak);
-            if (rc != RMX_OK) return rc;
-        }
-    } else {
-        rc = ensure_spec(c, n_windows < c->chunk_windows ? n_windows : c->chunk_windows);
-        if (rc != RMX_OK) return rc;
-        for (int w0 = 0; w0 < n_windows; w0 += c->chunk_windows) {
-            const int wc = n_windows - w0 < c->chunk_windows ? n_windows - w0 : c->chunk_windows;
-            rc = fwd4096(c, call, d_iq, w0, wc, u8, nullptr);
-            if (rc != RMX_OK) return rc;
-            rc = quality_chunk(c, call, kRefKfwd, c->d_spec, 13 /* log2 kL */, 0, -kTw1ScaleLog2, w0, wc, n_pairs, d_peak);
-            if (rc != RMX_OK) return rc;
-        }
-    }
+    int rc = c->generic ? rmx::generic_ensure(c, n_pairs, true, true)
+                        : ensure_spec(c, n_windows < c->chunk_windows ? n_windows : c->chunk_windows);
+    if (rc == RMX_OK)
+        rc = run_chunks(c, call, route_caps(c), d_iq, 0, n_windows, c->generic ? c->g_chunk : c->chunk_windows, n_pairs, nullptr, nullptr,
+                        d_peak, u8, false);
+    if (rc != RMX_OK) return rc;
     if (!out_dev) {
         RMX_HIP(c, hipMemcpyAsync(req.quality, c->d_quality, 4 * out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         RMX_HIP(c, hipStreamSynchronize(c->stream));
@@ -2578,86 +2502,27 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
         return quality_pass(c, req, iq, n_windows, n_pairs, peak, flags);
     }
     XcorrCall call = req;   // (req.quality is the caller's pointer; a host-pointer call gets the ctx's device block below)
-    const int all_pairs = c->n_buoys * (c->n_buoys - 1) / 2;
     tm_reset(c);
-    // Few windows of N = 4096: the fused kernel is one workgroup per WINDOW -- (B + P) transforms in sequence, 92 us for
-    // one window of 8 buoys, 344 us for 16 buoys, whatever the rest of the chip does -- while the per-transform kernels
-    // spread a window's spectra and pairs over the CUs: 13-15 us for the same single windows (tools/exp_small4096.py;
-    // the crossover sits at 64 / 110 / 140 windows for 3 / 8 / 16 buoys).  This is the shape of the reference's seam:
-    // one frequency group per call (tdoa_processor.py:363-377).
-    // Both paths are costed with a small model read off that table (us: 2.6 per transform of the fused kernel; 3.5 per
-    // round of forward workgroups, two per CU; 4.0 per pair workgroup + 3.3 per pair in it, one workgroup per CU; a
-    // round that fills the chip runs up to 45 % slower than a lone workgroup, less so when many rounds follow each other
-    // out of step) and the cheaper one runs; the same model picks the pairs per workgroup (1 ... 7) unless the caller
-    // set them.  Against the measured table it is within 10 % on every row and picks the faster path on all of them.
-    bool small = false;
-    int ppb_small = 7;
-    if (!c->generic && c->fused && c->small_batch && c->n_buoys >= 3 && n_pairs == all_pairs) {
-        small = split_cost4096(c, n_windows, n_pairs, &ppb_small) < host::fused_cost4096(c->n_cus, c->n_buoys, n_pairs, n_windows);
-    }
-    // a weighted call (rmx_xcorr_batch_weighted) weights the spectra where k_fwd stores them: the per-transform kernels
-    // at every batch size, never k_win (whose spectra stay inside the workgroup)
-    // (an integrated call sums over windows inside k_pair_str: the same kernels, with one work item per (group, pair))
-    if (call.weighted() && !c->generic) {
-        (void)split_cost4096(c, n_windows / call.integ, n_pairs, &ppb_small);
-        small = true;
-    }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
-    // The same arithmetic for the LAST round of a larger batch: W = k CUs + r windows cost the fused kernel k + 1 rounds
-    // (300 windows of 8 buoys: two rounds, 184 us); when the model says the r windows are cheaper through the
-    // per-transform kernels than a round of the fused one, they go there (after the k full rounds, on the same stream).
-    // The decision is taken per CHUNK of windows (a batch-wide tail larger than the last chunk ran past the
-    // chunk and past the spectrum scratch): in the chunk loop below a chunk's own partial round, wc mod CUs, takes that
-    // route when the model says so for ITS size, so it never exceeds the chunk, and the scratch of min(chunk, CUs) window
-    // slots covers it.  `tail` here is the gate -- the largest remainder of ANY chunk that pays (every chunk but the last
-    // has chunk_windows windows; ADVICE r04: it used to look at the last chunk only) -- and sizes the pair workgroups
-    // (one plan per call) for that largest partial round.
-    int tail = 0;
-    const bool tail_ok = !small && !c->generic && c->fused && c->small_batch && c->n_buoys >= 3 && n_pairs == all_pairs &&
-                         c->n_cus > 0 && (in_dev || n_windows <= kHostSubChunk);
-    auto tail_pays = [&](int r, int* q) -> bool {
-        return split_cost4096(c, r, n_pairs, q) < 0.9 * host::fused_cost4096(c->n_cus, c->n_buoys, n_pairs, 1);
-    };
-    if (tail_ok && n_windows > c->n_cus) {
-        const long cw = c->chunk_windows;
-        const int last_wc = (int)(n_windows - ((long)(n_windows - 1) / cw) * cw);   // windows of the last chunk
-        const int r_last = last_wc % c->n_cus;
-        const int r_full = (n_windows > cw) ? (int)(cw % c->n_cus) : 0;             // every earlier chunk's remainder
-        for (int r : {r_full > r_last ? r_full : r_last, r_full > r_last ? r_last : r_full}) {
-            int q = 7;
-            if (r != 0 && tail_pays(r, &q)) {
-                tail = r;
-                ppb_small = q;
-                break;
-            }
-        }
-    }
-    if (!c->generic && !c->ppb_user) {
-        if (!small && !tail && (pairs != nullptr || !c->fused)) {   // a custom pair list (or fused = 0): the per-transform kernels anyway
-            int q = 7;
-            (void)split_cost4096(c, n_windows, n_pairs, &q);
-            ppb_small = q;
-            c->pairs_per_block = q;
-        } else {
-            c->pairs_per_block = (small || tail) ? ppb_small : 7;
-        }
-    }
+    // the route (host_plan.hpp: plan_route), and the pair plan with the pairs per workgroup it chose
+    const host::RouteCall rq{n_windows, n_pairs, host::is_default_list(c->n_buoys, pairs, n_pairs), pairs != nullptr, call.bounded(),
+                             call.weighted(), call.integ, in_dev};
+    const host::RouteCaps caps = route_caps(c);
+    const host::RoutePlan plan = host::plan_route(caps, rq);
+    if (!c->generic) c->pairs_per_block = plan.ppb;
     int rc = build_plan(c, pairs, n_pairs);
+    if (rc == RMX_OK && !c->generic) rc = route_refusal(c, plan, caps, call.integ);
     if (rc != RMX_OK) return rc;
-    const bool fused_now = c->fused && c->plan_all_pairs && !small;
-    if (!fused_now) tail = 0;
 
     const size_t samp_bytes = u8 ? 2 : 8;
     const size_t in_bytes = (size_t)n_windows * c->n_buoys * c->n_samples * samp_bytes;
     const void* d_iq = iq;
-    bool pipelined = false;
     if (!in_dev) {
         rc = ensure_in(c, in_bytes);
         if (rc != RMX_OK) return rc;
-        // fused path: the copy is cut into sub-chunks issued on a second stream, each followed by its
+        // k_win: the copy is cut into sub-chunks issued on a second stream, each followed by its
         // kernel launch, so that copy k+1 travels while kernel k runs (below); otherwise one copy up front
-        pipelined = !c->generic && fused_now && n_windows > kHostSubChunk;
-        if (pipelined) {
+        if (plan.pipelined) {
             if (!c->copy_stream) RMX_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
             for (hipEvent_t& e : c->copy_ev)
                 if (!e) RMX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -2670,143 +2535,82 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
         d_iq = c->d_in;
     }
     int* d_lag = lag_int;
-    float* d_frac = lag_frac;
-    float* d_peak = peak;
+    float *d_frac = lag_frac, *d_peak = peak;
     const size_t out_elems = (size_t)(n_windows / call.integ) * n_pairs;   // (integrated call: one row per group)
     if (!out_dev) {
-        {
-            const int rc_out = ensure_out(c, out_elems);
-            if (rc_out != RMX_OK) return rc_out;
-        }
+        rc = ensure_out(c, out_elems);
+        if (rc == RMX_OK && call.qualified()) rc = ensure_quality(c, 4 * out_elems);
+        if (rc != RMX_OK) return rc;
         d_lag = c->d_lag; d_frac = c->d_frac; d_peak = c->d_peak;
-        if (call.qualified()) {
-            const int rc_q = ensure_quality(c, 4 * out_elems);
-            if (rc_q != RMX_OK) return rc_q;
-            call.quality = c->d_quality;
-        }
+        if (call.qualified()) call.quality = c->d_quality;
     }
     // host-pointer results: the fourth array is queued in front of fetch_out, which waits for the stream
-    auto fetch_all = [&]() -> int {
+    auto done = [&](int rc_k) -> int {
+        if (rc_k != RMX_OK || out_dev) return rc_k;
         if (call.qualified())
             RMX_HIP(c, hipMemcpyAsync(req.quality, c->d_quality, 4 * out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         return fetch_out(c, out_elems, lag_int, lag_frac, peak);
     };
-
-    if (c->generic) {
-        rc = rmx::generic_batch(c, call, d_iq, n_windows, n_pairs, d_lag, d_frac, d_peak, u8);
-        if (rc != RMX_OK) return rc;
-        if (!out_dev) return fetch_all();
-        return RMX_OK;
-    }
+    if (c->generic) return done(rmx::generic_batch(c, call, caps, rq, plan, d_iq, d_lag, d_frac, d_peak, u8));
+    const bool k_win_route = plan.route == host::kRouteKWin;
+    const long chunk_w = n_windows < c->chunk_windows ? n_windows : c->chunk_windows;
+    rc = ensure_spec(c, k_win_route ? (chunk_w < c->n_cus ? chunk_w : c->n_cus) : chunk_w);   // per workgroup for k_win, per window of a chunk otherwise
+    if (rc != RMX_OK) return rc;
+    if (!k_win_route) return done(run_chunks(c, call, caps, d_iq, 0, n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8));
     const float out_scale = out_scale4096();   // (the forward scale 2^-6 rides on the TW1 table)
-
-    {   // scratch: per workgroup for the fused kernel, per window of a chunk otherwise
-        const bool fused_path = fused_now;
-        const long chunk_w = n_windows < c->chunk_windows ? n_windows : c->chunk_windows;
-        rc = ensure_spec(c, fused_path ? (chunk_w < c->n_cus ? chunk_w : c->n_cus) : chunk_w);
-        if (rc != RMX_OK) return rc;
-    }
     int n_sub = 0;
-    // (integrated call: a chunk holds whole groups -- never a silent split of a group)
-    const int chunk_windows = c->chunk_windows / call.integ * call.integ;
-    if (chunk_windows == 0)
-        return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
-                    call.integ, c->chunk_windows);
-    for (int w0 = 0; w0 < n_windows; w0 += chunk_windows) {
-        const int wc = (n_windows - w0 < chunk_windows) ? n_windows - w0 : chunk_windows;
-        if (fused_now) {
-            // this chunk's partial round (see above): only behind at least one full round of this call, and only when the
-            // model says so for ITS size -- with the default chunk (a multiple of the CU count) that is the batch's last
-            // partial round; 0 <= wtail < CUs and wtail <= wc by construction
-            int wtail = 0;
-            if (tail && (w0 > 0 || wc > c->n_cus) && wc % c->n_cus != 0) {
-                int q_unused = 7;
-                if (tail_pays(wc % c->n_cus, &q_unused)) wtail = wc % c->n_cus;
+    for (int w0 = 0; w0 < n_windows; w0 += plan.chunk) {
+        const int wc = (n_windows - w0 < plan.chunk) ? n_windows - w0 : plan.chunk;
+        const int wtail = host::route_wtail4096(caps, plan, n_pairs, w0, wc);   // this chunk's partial round
+        const int wf = wc - wtail;
+        const int sub = plan.pipelined ? kHostSubChunk : (wf > 0 ? wf : 1);
+        for (int s0 = 0; s0 < wf; s0 += sub) {
+            const int sc = wf - s0 < sub ? wf - s0 : sub;
+            const long wfirst = (long)w0 + s0;
+            if (plan.pipelined) {
+                const size_t off = (size_t)wfirst * c->n_buoys * c->n_samples * samp_bytes;
+                const size_t nb = (size_t)sc * c->n_buoys * c->n_samples * samp_bytes;
+                hipEvent_t ev = c->copy_ev[n_sub % 3];
+                ++n_sub;
+                RMX_HIP(c, hipMemcpyAsync((char*)c->d_in + off, (const char*)iq + off, nb, hipMemcpyHostToDevice,
+                                          c->copy_stream));
+                RMX_HIP(c, hipEventRecord(ev, c->copy_stream));
+                RMX_HIP(c, hipStreamWaitEvent(c->stream, ev, 0));
             }
-            const int wf = wc - wtail;
-            const int sub = pipelined ? kHostSubChunk : (wf > 0 ? wf : 1);
-            for (int s0 = 0; s0 < wf; s0 += sub) {
-                const int sc = wf - s0 < sub ? wf - s0 : sub;
-                const long wfirst = (long)w0 + s0;
-                if (pipelined) {
-                    const size_t off = (size_t)wfirst * c->n_buoys * c->n_samples * samp_bytes;
-                    const size_t nb = (size_t)sc * c->n_buoys * c->n_samples * samp_bytes;
-                    hipEvent_t ev = c->copy_ev[n_sub % 3];
-                    ++n_sub;
-                    RMX_HIP(c, hipMemcpyAsync((char*)c->d_in + off, (const char*)iq + off, nb, hipMemcpyHostToDevice,
-                                              c->copy_stream));
-                    RMX_HIP(c, hipEventRecord(ev, c->copy_stream));
-                    RMX_HIP(c, hipStreamWaitEvent(c->stream, ev, 0));
-                }
-                // one persistent workgroup per CU (the kernel's LDS footprint allows exactly one)
-                const int wgrid = sc < c->n_cus ? sc : c->n_cus;
-                RMX_TM_BEGIN(c);
-                with_u8(u8, [&](auto U) {
-                    constexpr bool U8 = decltype(U)::value;
-                    auto launch = [&](auto kern, auto... lb) {
-                        hipLaunchKernelGGL(kern, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec, c->d_tw1,
-                                           c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, c->dbg, c->stag, lb...);
-                    };
+            // one persistent workgroup per CU (the kernel's LDS footprint allows exactly one)
+            const int wgrid = sc < c->n_cus ? sc : c->n_cus;
+            RMX_TM_BEGIN(c);
+            with_u8(u8, [&](auto U) {
+                constexpr bool U8 = decltype(U)::value;
+                auto launch = [&](auto kern, auto... lb) {
+                    hipLaunchKernelGGL(kern, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec, c->d_tw1,
+                                       c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, c->dbg, c->stag, lb...);
+                };
 #ifdef RMX_EXPERIMENTS
-                    if (c->win8)
-                        hipLaunchKernelGGL(w8::k_win8<U8>, dim3(wgrid), dim3(w8::kT8), w8::kLdsWin8Bytes, c->stream, d_iq, c->d_spec,
-                                           c->d_tw1_8, c->d_tb8, c->d_tc8, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc,
-                                           c->stag);
-                    else if (c->pk)
-                        hipLaunchKernelGGL(k_winp<U8>, dim3(wgrid), dim3(kThreads), pk::kLdsWinpBytes, c->stream, d_iq, c->d_spec,
-                                           c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc);
-                    else
+                if (c->win8)
+                    hipLaunchKernelGGL(w8::k_win8<U8>, dim3(wgrid), dim3(w8::kT8), w8::kLdsWin8Bytes, c->stream, d_iq, c->d_spec,
+                                       c->d_tw1_8, c->d_tb8, c->d_tc8, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc,
+                                       c->stag);
+                else if (c->pk)
+                    hipLaunchKernelGGL(k_winp<U8>, dim3(wgrid), dim3(kThreads), pk::kLdsWinpBytes, c->stream, d_iq, c->d_spec,
+                                       c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc);
+                else
 #endif
-                    if (call.bounded()) launch(k_win_lb<U8>, call.lb);   // k_win's bounded instantiation
-                    else launch(k_win<U8>);
-                });
-                RMX_HIP(c, hipGetLastError());
-                RMX_TM_END(c, kTkPair4096);
-            }
-            if (wtail) {
-                rc = fwd4096(c, call, d_iq, w0 + wf, wtail, u8, nullptr);
-                if (rc != RMX_OK) return rc;
-                rc = pairs4096(c, call, w0 + wf, wtail, n_pairs, d_lag, d_frac, d_peak, out_scale, false);
-                if (rc != RMX_OK) return rc;
-            }
-            continue;
+                if (call.bounded()) launch(k_win_lb<U8>, call.lb);   // k_win's bounded instantiation
+                else launch(k_win<U8>);
+            });
+            RMX_HIP(c, hipGetLastError());
+            RMX_TM_END(c, kTkPair4096);
         }
-        rc = fwd4096(c, call, d_iq, w0, wc, u8, nullptr);
-        if (rc != RMX_OK) return rc;
-        rc = pairs4096(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, out_scale, false);
-        if (rc != RMX_OK) return rc;
-        if (call.qualified()) {   // (weighted() like a refined call: this branch; in front of k_refine, which overwrites the coarse peak)
-            rc = quality_chunk(c, call, kRefKfwd, c->d_spec, 13 /* log2 kL */, 0, -kTw1ScaleLog2, w0, wc, n_pairs, d_peak);
-            if (rc != RMX_OK) return rc;
-        }
-        if (call.refined()) {   // (a refined call is weighted(): this branch, d_spec holds the chunk's spectra, scaled 2^-6)
-            rc = refine_chunk(c, call, kRefKfwd, c->d_spec, 13 /* log2 kL */, 0, -kTw1ScaleLog2, w0, wc, n_pairs, d_lag, d_frac, d_peak);
+        if (wtail) {
+            rc = run_chunks(c, call, caps, d_iq, w0 + wf, wtail, wtail, n_pairs, d_lag, d_frac, d_peak, u8);
             if (rc != RMX_OK) return rc;
         }
     }
-    if (!out_dev) return fetch_all();
-    return RMX_OK;
+    return done(RMX_OK);
 }
 
-// ---- the three validators, one per feature --------------------------------------------------------------------------
-// rmx_xcorr_batch_integrated: K and the group count; an unbounded call with K > 1 gets the full interval per pair in
-// *full (the integrating kernels always carry bounds)
-static int check_integrated(rmx_ctx* c, int n_windows, const int32_t* pairs, int n_pairs, int integrate, bool bounds_given,
-                            std::vector<int32_t>* full) {
-    if (integrate < 1) return fail(c, RMX_E_INVAL, "integrate = %d: at least one window per group", integrate);
-    if (n_windows <= 0 || n_windows % integrate != 0)
-        return fail(c, RMX_E_INVAL, "n_windows = %d is not a positive multiple of integrate = %d", n_windows, integrate);
-    if (integrate == 1 || bounds_given) return RMX_OK;
-    const int np = pairs ? n_pairs : c->n_buoys * (c->n_buoys - 1) / 2;
-    if (np < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
-    full->resize((size_t)(2 * (np > 0 ? np : 1)));   // (np == 0 is never read: a call without pairs returns before the bounds)
-    for (int q = 0; q < np; ++q) {
-        (*full)[2 * q] = -(c->n_samples - 1);
-        (*full)[2 * q + 1] = c->n_samples - 1;
-    }
-    return RMX_OK;
-}
-
+// ---- the validators, one per feature ---------------------------------------------------------------------------------
 // rmx_xcorr_batch_weighted: the weighting, the window count and the bands, one per window or one for all, converted to
 // signed bins in *bins.  *weighted stays false when there is no band (or the full one) and no weighting: the plain call.
 static int check_weighted(rmx_ctx* c, int n_windows, const double* band_cps, int band_per_window, unsigned weighting,
@@ -2856,19 +2660,37 @@ static int check_bounded(rmx_ctx* c, int n_windows, int n_pairs, int integrate, 
     return RMX_OK;
 }
 
-// What the four correlation entries do: check the arguments -- the integrated entry's own checks have run; here the
-// weighted entry's, then the bounded entry's, so an input with several bad arguments is refused for the same one whichever
-// entry it came through --, copy the bands (as signed bins) and the lag intervals into ctx-owned device buffers, describe
-// the call in an XcorrCall and dispatch it.  The plain call is integrate = 1, no band, no weighting, no bounds.
-static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
+// What all six correlation entries do, and none of them through another: check the arguments -- the checks of the entries
+// that take `integrate` (grouped), then the weighted entry's, then the bounded entry's, so an input with several bad
+// arguments is refused for the same one whichever entry it came through --, copy the bands (as signed bins) and the lag
+// intervals into ctx-owned device buffers, describe the call in an XcorrCall and dispatch it.  The plain call is
+// integrate = 1, no band, no weighting, no bounds.
+static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, bool grouped, int integrate,
                          const double* band_cps, int band_per_window, unsigned weighting, const int32_t* lag_bounds,
                          int bounds_per_window, int refine, int32_t* lag_int, float* lag_frac, float* peak, float* quality,
                          unsigned flags) {
-    if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
-    std::vector<int32_t> bins;
+    if (!c) return RMX_E_INVAL;
+    std::vector<int32_t> bins, full;
     bool weighted = false, bounded = false;
     long bound_rows = 0;
     int rc;
+    if (grouped) {   // K and the group count
+        if (integrate < 1) return fail(c, RMX_E_INVAL, "integrate = %d: at least one window per group", integrate);
+        if (n_windows <= 0 || n_windows % integrate != 0)
+            return fail(c, RMX_E_INVAL, "n_windows = %d is not a positive multiple of integrate = %d", n_windows, integrate);
+        if (integrate > 1 && !lag_bounds) {   // the integrating kernels always carry bounds: the full interval per pair
+            const int np = pairs ? n_pairs : c->n_buoys * (c->n_buoys - 1) / 2;
+            if (np < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
+            full.resize((size_t)(2 * (np > 0 ? np : 1)));   // (np == 0 is never read: a call without pairs returns before the bounds)
+            for (int q = 0; q < np; ++q) {
+                full[2 * q] = -(c->n_samples - 1);
+                full[2 * q + 1] = c->n_samples - 1;
+            }
+            lag_bounds = full.data();
+            bounds_per_window = 0;
+        }
+    }
+    if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
     if (band_cps || weighting != RMX_WEIGHT_NONE) {
         rc = check_weighted(c, n_windows, band_cps, band_per_window, weighting, &bins, &weighted);
         if (rc != RMX_OK) return rc;
@@ -2917,9 +2739,8 @@ static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_
 
 int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                     int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    if (!c) return RMX_E_INVAL;
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0, 0, lag_int, lag_frac, peak, nullptr,
-                         flags);
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0, 0, lag_int, lag_frac, peak,
+                         nullptr, flags);
 }
 
 // rmx_xcorr_batch with a lag interval per (window, pair).  Every interval the full one IS the plain call.
@@ -2928,7 +2749,7 @@ int rmx_xcorr_batch_bounded(rmx_ctx* c, const void* iq, int n_windows, const int
                             unsigned flags) {
     if (!c) return RMX_E_INVAL;
     if (!lag_bounds) return fail(c, RMX_E_INVAL, "NULL buffer");
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, nullptr, 0, RMX_WEIGHT_NONE, lag_bounds, bounds_per_window, 0, lag_int,
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, nullptr, 0, RMX_WEIGHT_NONE, lag_bounds, bounds_per_window, 0, lag_int,
                          lag_frac, peak, nullptr, flags);
 }
 
@@ -2938,9 +2759,8 @@ int rmx_xcorr_batch_weighted(rmx_ctx* c, const void* iq, int n_windows, const in
                              const double* band_cps, int band_per_window, unsigned weighting,
                              const int32_t* lag_bounds, int bounds_per_window,
                              int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    if (!c) return RMX_E_INVAL;
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, 1, band_cps, band_per_window, weighting, lag_bounds, bounds_per_window,
-                         0, lag_int, lag_frac, peak, nullptr, flags);
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, band_cps, band_per_window, weighting, lag_bounds,
+                         bounds_per_window, 0, lag_int, lag_frac, peak, nullptr, flags);
 }
 
 // rmx_xcorr_batch_weighted with one peak search per group of `integrate` consecutive windows, on the lag-by-lag sum of the
@@ -2950,8 +2770,8 @@ int rmx_xcorr_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const 
                                const double* band_cps, int band_per_window, unsigned weighting,
                                const int32_t* lag_bounds, int bounds_per_group,
                                int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    return rmx_xcorr_batch_refined(c, iq, n_windows, pairs, n_pairs, integrate, band_cps, band_per_window, weighting, lag_bounds,
-                                   bounds_per_group, 0, lag_int, lag_frac, peak, flags);
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, true, integrate, band_cps, band_per_window, weighting, lag_bounds,
+                         bounds_per_group, 0, lag_int, lag_frac, peak, nullptr, flags);
 }
 
 // rmx_xcorr_batch_integrated with the fine lag search of refine.hpp behind the coarse one: refine = U in {2, 4, 8, 16}
@@ -2960,8 +2780,8 @@ int rmx_xcorr_batch_refined(rmx_ctx* c, const void* iq, int n_windows, const int
                             const double* band_cps, int band_per_window, unsigned weighting,
                             const int32_t* lag_bounds, int bounds_per_group, int refine,
                             int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    return rmx_xcorr_batch_quality(c, iq, n_windows, pairs, n_pairs, integrate, band_cps, band_per_window, weighting, lag_bounds,
-                                   bounds_per_group, refine, lag_int, lag_frac, peak, nullptr, flags);
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, true, integrate, band_cps, band_per_window, weighting, lag_bounds,
+                         bounds_per_group, refine, lag_int, lag_frac, peak, nullptr, flags);
 }
 
 // rmx_xcorr_batch_refined with four quality figures per output slot (quality.hpp) as a fourth output, computed from the
@@ -2970,15 +2790,7 @@ int rmx_xcorr_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int
                             const double* band_cps, int band_per_window, unsigned weighting,
                             const int32_t* lag_bounds, int bounds_per_group, int refine,
                             int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
-    if (!c) return RMX_E_INVAL;
-    std::vector<int32_t> full;
-    const int rc = check_integrated(c, n_windows, pairs, n_pairs, integrate, lag_bounds != nullptr, &full);
-    if (rc != RMX_OK) return rc;
-    if (!full.empty()) {
-        lag_bounds = full.data();
-        bounds_per_group = 0;
-    }
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, integrate, band_cps, band_per_window, weighting, lag_bounds,
+    return xcorr_request(c, iq, n_windows, pairs, n_pairs, true, integrate, band_cps, band_per_window, weighting, lag_bounds,
                          bounds_per_group, refine, lag_int, lag_frac, peak, quality, flags);
 }
 
@@ -3001,7 +2813,7 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
                             (long)n_dopplers * n_windows < (1L << 20);
     if (!c->generic && !c->ppb_user) {               // (N = 4096: blocks sized to this batch, not to the previous call's)
         int q = 7;
-        (void)split_cost4096(c, batch_bins ? n_windows * n_dopplers : n_windows, n_pairs, &q);
+        (void)host::split_cost4096(c->n_cus, c->n_buoys, n_pairs, batch_bins ? n_windows * n_dopplers : n_windows, 0, &q);
         c->pairs_per_block = q;
     }
     rc = build_plan(c, pairs, n_pairs);              // validates the pair list
@@ -3067,6 +2879,7 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
         if (rc != RMX_OK) return rc;
     }
     const float osc = out_scale4096();
+    const SpecView sv = spec_view(c);
     if (batch_bins) {
         rc = fwd4096(c, call, d_iq, 0, n_windows, u8, nullptr);
         if (rc == RMX_OK) rc = fwd4096(c, call, d_iq, 0, n_windows, u8, c->caf_rot, n_dopplers);
@@ -3081,13 +2894,12 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
     }
     for (int w0 = 0; !batch_bins && w0 < n_windows && rc == RMX_OK; w0 += chunk) {
         const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
-        rc = c->generic ? rmx::generic_forward(c, call, d_iq, w0, wc, u8, nullptr) : fwd4096(c, call, d_iq, w0, wc, u8, nullptr);
+        rc = sv.forward(c, call, d_iq, w0, wc, u8, nullptr, false);
         for (int d = 0; d < n_dopplers && rc == RMX_OK; ++d) {
             const float2* rot = c->caf_rot + (size_t)d * N;
-            rc = c->generic ? rmx::generic_forward(c, call, d_iq, w0, wc, u8, rot) : fwd4096(c, call, d_iq, w0, wc, u8, rot);
+            rc = sv.forward(c, call, d_iq, w0, wc, u8, rot, false);
             if (rc != RMX_OK) break;
-            rc = c->generic ? rmx::generic_pairs(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true)
-                            : pairs4096(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, osc, true);
+            rc = sv.pairs(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true, false);
             if (rc != RMX_OK) break;
             const long first = (long)w0 * n_pairs, cnt = (long)wc * n_pairs;
             rc = tm_begin(c);

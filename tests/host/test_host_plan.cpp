@@ -165,7 +165,264 @@ static void test_request_conversions() {
     }
 }
 
+// ---- the route planner -------------------------------------------------------------------------------------------------
+// the caps rmx_create gives an N = 4096 ctx: every one follows from (buoys, max_windows, ncus, options) without a device
+static RouteCaps caps4096(int n_buoys, int max_windows, int n_cus, int chunk_opt = 4096) {
+    RouteCaps k;
+    k.n_cus = n_cus;
+    k.n_buoys = n_buoys;
+    int chunk = chunk_opt < 8 ? 8 : chunk_opt;
+    chunk = (chunk + 7) & ~7;
+    if (chunk > max_windows) chunk = max_windows;
+    k.chunk_windows = chunk;
+    return k;
+}
+static RouteCall call4096(int n_buoys, int n_windows) {
+    RouteCall a;
+    a.n_windows = n_windows;
+    a.n_pairs = n_buoys * (n_buoys - 1) / 2;
+    a.in_dev = false;
+    return a;
+}
+// the launches of families "k_fwd" and "k_win|k_pair" a plan implies for a plain N = 4096 call
+static void launches4096(const RouteCaps& k, const RouteCall& a, int* n_fwd, int* n_pair, RoutePlan* out = nullptr) {
+    const RoutePlan p = plan_route(k, a);
+    CHECK(p.refused == kRouteOk && p.chunk > 0);
+    *n_fwd = *n_pair = 0;
+    for (int w0 = 0; w0 < a.n_windows; w0 += p.chunk) {
+        const int wc = a.n_windows - w0 < p.chunk ? a.n_windows - w0 : p.chunk;
+        if (p.route == kRoutePer4096) { ++*n_fwd; ++*n_pair; continue; }
+        CHECK(p.route == kRouteKWin);
+        const int wtail = route_wtail4096(k, p, a.n_pairs, w0, wc), wf = wc - wtail;
+        if (wf > 0) *n_pair += p.pipelined ? (wf + kHostSubChunk - 1) / kHostSubChunk : 1;
+        if (wtail) { ++*n_fwd; ++*n_pair; }
+    }
+    if (out) *out = p;
+}
+
+// The N = 4096 rows of tests/golden/route_table.json, transcribed: the launch counts are the RECORDING's (the library of the
+// commit before the planner, on an MI355X), the plan must imply exactly them.  pairs: 0 the default list (NULL), 1 the default
+// list passed explicitly, 2 the default list reversed, 3 the default list without its last pair.  quality_only: the two-pass
+// route (the plain call, then one k_fwd per chunk in front of k_quality).
+struct RecordedRow {
+    const char* name;
+    int B, W, max_windows, ncus, chunk_opt;
+    bool fused, small4096;
+    int ppb_user, pairs;
+    bool bounded, weighted;
+    int integ;
+    bool in_dev, quality_only;
+    int k_fwd, k_pair;   // launches of the families "k_fwd" and "k_win|k_pair"
+};
+static const RecordedRow kRecorded[] = {
+    {"n4096_b3_w1", 3, 1, 1, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 1},
+    {"n4096_b3_w2", 3, 2, 2, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 1},
+    {"n4096_b3_w4", 3, 4, 4, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w8", 3, 8, 8, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w12", 3, 12, 12, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w9_tail", 3, 9, 9, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 2},
+    {"n4096_b3_w15_tail", 3, 15, 15, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w17_tail", 3, 17, 17, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 2},
+    {"n4096_b3_w23_tail", 3, 23, 23, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w15_chunk8_cu6", 3, 15, 15, 6, 8, true, true, 0, 0, false, false, 1, false, false, 1, 3},
+    {"n4096_b3_w14_chunk8_cu6", 3, 14, 14, 6, 8, true, true, 0, 0, false, false, 1, false, false, 0, 2},
+    {"n4096_b3_w17_rev", 3, 17, 17, 8, 4096, true, true, 0, 2, false, false, 1, false, false, 1, 1},
+    {"n4096_b3_w17_explicit_default", 3, 17, 17, 8, 4096, true, true, 0, 1, false, false, 1, false, false, 1, 2},
+    {"n4096_b3_w4_sub", 3, 4, 4, 8, 4096, true, true, 0, 3, false, false, 1, false, false, 1, 1},
+    {"n4096_b3_w17_unfused", 3, 17, 17, 8, 4096, false, true, 0, 0, false, false, 1, false, false, 1, 1},
+    {"n4096_b3_w17_ppb3", 3, 17, 17, 8, 4096, true, true, 3, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w2_ppb3", 3, 2, 2, 8, 4096, true, true, 3, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w17_small0", 3, 17, 17, 8, 4096, true, false, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w2_small0", 3, 2, 2, 8, 4096, true, false, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w17_u8", 3, 17, 17, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 2},
+    {"n4096_b3_w17_bounded", 3, 17, 17, 8, 4096, true, true, 0, 0, true, false, 1, false, false, 1, 2},
+    {"n4096_b8_w1", 8, 1, 1, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 1},
+    {"n4096_b8_w2", 8, 2, 2, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 1},
+    {"n4096_b8_w4", 8, 4, 4, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 1},
+    {"n4096_b8_w8", 8, 8, 8, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b8_w12", 8, 12, 12, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 2},
+    {"n4096_b8_w9_tail", 8, 9, 9, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 2},
+    {"n4096_b8_w15_tail", 8, 15, 15, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b8_w17_tail", 8, 17, 17, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 2},
+    {"n4096_b8_w23_tail", 8, 23, 23, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b8_w15_chunk8_cu6", 8, 15, 15, 6, 8, true, true, 0, 0, false, false, 1, false, false, 2, 4},
+    {"n4096_b8_w14_chunk8_cu6", 8, 14, 14, 6, 8, true, true, 0, 0, false, false, 1, false, false, 1, 3},
+    {"n4096_b8_w17_rev", 8, 17, 17, 8, 4096, true, true, 0, 2, false, false, 1, false, false, 1, 1},
+    {"n4096_b8_w17_explicit_default", 8, 17, 17, 8, 4096, true, true, 0, 1, false, false, 1, false, false, 1, 2},
+    {"n4096_b8_w4_sub", 8, 4, 4, 8, 4096, true, true, 0, 3, false, false, 1, false, false, 1, 1},
+    {"n4096_b8_w17_unfused", 8, 17, 17, 8, 4096, false, true, 0, 0, false, false, 1, false, false, 1, 1},
+    {"n4096_b8_w17_ppb3", 8, 17, 17, 8, 4096, true, true, 3, 0, false, false, 1, false, false, 1, 2},
+    {"n4096_b8_w2_ppb3", 8, 2, 2, 8, 4096, true, true, 3, 0, false, false, 1, false, false, 1, 1},
+    {"n4096_b8_w17_small0", 8, 17, 17, 8, 4096, true, false, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b8_w2_small0", 8, 2, 2, 8, 4096, true, false, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b8_w17_u8", 8, 17, 17, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 1, 2},
+    {"n4096_b8_w17_bounded", 8, 17, 17, 8, 4096, true, true, 0, 0, true, false, 1, false, false, 1, 2},
+    {"n4096_b2_w3", 2, 3, 3, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 1},
+    {"n4096_b3_w521_host", 3, 521, 521, 8, 4096, true, true, 0, 0, false, false, 1, false, false, 0, 2},
+    {"n4096_b3_w521_device", 3, 521, 521, 8, 4096, true, true, 0, 0, false, false, 1, true, false, 1, 2},
+    {"n4096_bounded", 3, 6, 6, 8, 4096, true, true, 0, 0, true, false, 1, false, false, 0, 1},
+    {"n4096_band_phat", 3, 6, 6, 8, 4096, true, true, 0, 0, false, true, 1, false, false, 1, 1},
+    {"n4096_integ2", 3, 6, 6, 8, 4096, true, true, 0, 0, true, true, 2, false, false, 1, 1},
+    {"n4096_refine4", 3, 6, 6, 8, 4096, true, true, 0, 0, false, true, 1, false, false, 1, 1},
+    {"n4096_quality", 3, 6, 6, 8, 4096, true, true, 0, 0, false, false, 1, false, true, 1, 1},
+    {"n4096_quality_band", 3, 6, 6, 8, 4096, true, true, 0, 0, false, true, 1, false, false, 1, 1},
+    {"n4096_all", 3, 6, 6, 8, 4096, true, true, 0, 0, true, true, 2, false, false, 1, 1},
+    {"n4096_all_two_chunks", 3, 16, 16, 8, 8, true, true, 0, 0, true, true, 2, false, false, 2, 2},
+    {"n4096_quality_two_chunks", 3, 16, 16, 8, 8, true, true, 0, 0, false, false, 1, false, true, 2, 2},
+    {"n4096_plain_two_chunks", 3, 16, 16, 8, 8, true, true, 0, 0, false, false, 1, false, false, 0, 2},
+};
+
+static void test_recorded_rows() {
+    int n = 0;
+    for (const RecordedRow& r : kRecorded) {
+        RouteCaps k = caps4096(r.B, r.max_windows, r.ncus, r.chunk_opt);
+        k.fused = r.fused;
+        k.small_batch = r.small4096;
+        k.ppb_user = r.ppb_user;
+        RouteCall a = call4096(r.B, r.W);
+        if (r.pairs == 3) --a.n_pairs;
+        a.all_pairs = r.pairs < 2;
+        a.pairs_given = r.pairs != 0;
+        a.bounded = r.bounded;
+        a.weighted = r.weighted;
+        a.integ = r.integ;
+        a.in_dev = r.in_dev;
+        int n_fwd = 0, n_pair = 0;
+        RoutePlan p;
+        launches4096(k, a, &n_fwd, &n_pair, &p);
+        if (r.quality_only) n_fwd += (r.W + k.chunk_windows - 1) / k.chunk_windows;
+        if (n_fwd != r.k_fwd || n_pair != r.k_pair) {
+            std::fprintf(stderr, "%s: the plan implies %d k_fwd + %d k_win|k_pair launches, recorded %d + %d\n", r.name, n_fwd, n_pair,
+                         r.k_fwd, r.k_pair);
+            std::exit(1);
+        }
+        if (r.ppb_user) CHECK(p.ppb == r.ppb_user);
+        ++n;
+    }
+    CHECK(n >= 40);
+}
+
+
+static bool same_plan(const RoutePlan& a, const RoutePlan& b) {
+    return a.route == b.route && a.ppb == b.ppb && a.chunk == b.chunk && a.n_head == b.n_head && a.n_tail == b.n_tail && a.tail == b.tail &&
+           a.pipelined == b.pipelined && a.refused == b.refused;
+}
+
+static void test_route_invariants() {
+    long n_plans = 0;
+    for (int B = 2; B <= 16; ++B)
+        for (int logL = 5; logL <= 23; ++logL)
+            for (int n_cus : {1, 8, 37})
+                for (int variant = 0; variant < 4; ++variant) {
+                    RouteCaps k;
+                    k.n_cus = n_cus;
+                    k.n_buoys = B;
+                    k.generic = !(logL == 13 && variant < 2);                     // (logL 13: N = 4096 itself, and generic4096)
+                    k.logL = logL;
+                    k.small_maxl = 8192;
+                    k.fused = variant != 1;
+                    k.chunk_windows = variant == 0 ? 4096 : 8;
+                    k.ppb_user = variant == 1 ? 9 : 0;
+                    if (k.generic) {                                                // as generic_init derives them
+                        const bool four_step = (1L << logL) > k.small_maxl;
+                        if (four_step) {
+                            k.logL1 = (logL - 3) / 2;
+                            if (k.logL1 < logL - 13) k.logL1 = logL - 13;
+                            if (k.logL1 > 10) k.logL1 = 10;
+                            k.logL2 = logL - k.logL1;
+                            k.g_fused = B <= 4 && k.logL2 >= 9 && k.logL2 <= 12 && variant != 3;
+                            k.g_fused_always = k.g_fused && variant == 2;
+                            k.col_tile = (1L << k.logL1) << (k.logL1 >= 10 ? 3 : 4);
+                            k.cols_threads = variant == 3 ? 64 : (int)(k.col_tile / 16 >= 1024 ? 1024 : k.col_tile / 16 < 64 ? 64 : k.col_tile / 16);
+                        }
+                        k.wfused = !four_step && B <= 4 && logL >= 9 && logL <= 12 && variant != 3;
+                        k.wscr = !k.wfused && logL >= 9 && logL <= 15 && variant != 3;
+                        k.wscr_always = k.wscr && variant == 2;
+                        k.ws_upw = logL >= 13 ? 1 : 2;
+                        k.ws_grid = n_cus;
+                        k.k8 = k.wscr && logL == 14 && variant != 1;
+                        k.k16 = k.wscr && logL == 15 ? (variant == 1 ? 2 : 1) : 0;
+                        k.g_chunk = variant == 3 ? 3 : 64;
+                    }
+                    const int P = B * (B - 1) / 2;
+                    for (int W = 1; W <= 3 * n_cus + 1; ++W)
+                        for (int flags = 0; flags < 8; ++flags)
+                            for (int integ : {1, 2, 5}) {
+                                RouteCall a;
+                                a.n_windows = W;
+                                a.all_pairs = !(flags & 4);
+                                a.pairs_given = flags & 4;
+                                const int custom[3] = {640, 641, 700};               // at, just beyond and far beyond kMaxPairs8 / kMaxPairs16
+                                a.n_pairs = a.all_pairs ? P : custom[(W + integ) % 3];
+                                a.bounded = (flags & 1) || integ > 1;               // (an integrated call always carries bounds)
+                                a.weighted = (flags & 2) || integ > 1;
+                                a.integ = integ;
+                                a.in_dev = W & 1;
+                                if (W % integ != 0) continue;                       // (refused by the entry)
+                                const RoutePlan p = plan_route(k, a);
+                                ++n_plans;
+                                if (a.n_pairs > 640) CHECK(p.route != kRouteKWin8 && p.route != kRouteK16);
+                                CHECK(same_plan(p, plan_route(k, a)));              // a pure function
+                                const bool whole = p.route == kRouteKWin || p.route == kRouteKWin8 || p.route == kRouteWinScr ||
+                                                   p.route == kRouteWinEo15 || p.route == kRouteWinFused;
+                                CHECK(k.generic == !(p.route == kRouteKWin || p.route == kRoutePer4096));
+                                if (a.weighted) {
+                                    CHECK(!whole && p.route != kRouteK16);
+                                    for (int wc = 1; wc <= W; ++wc) CHECK(!route_rows_fused(k, true, wc));
+                                }
+                                // only k_win, k_win8kl, k16_pairs and the per-transform kernels have a bounded instantiation
+                                if (a.bounded) CHECK(p.route != kRouteWinScr && p.route != kRouteWinEo15 && p.route != kRouteWinFused);
+                                if (k.generic) {
+                                    CHECK(p.n_head + p.n_tail == W && p.n_tail >= 0);
+                                    if (p.n_tail) CHECK(p.n_head > 0 && p.n_head % k.ws_grid == 0 && (p.route == kRouteKWin8 || p.route == kRouteWinEo15));
+                                }
+                                const bool chunked = p.route == kRoutePer4096 || p.route == kRouteKWin || p.route == kRouteSmallL ||
+                                                     p.route == kRouteFourStep;
+                                if (chunked) CHECK(p.refused != kRouteOk || (p.chunk > 0 && p.chunk % integ == 0));
+                                if (p.refused != kRouteOk) CHECK(integ > 1 && !whole);
+                                if (p.refused == kRefuseIntegChunk) CHECK(integ > (k.generic ? k.g_chunk : k.chunk_windows));
+                                if (!k.generic) CHECK(k.ppb_user ? p.ppb == k.ppb_user : (p.ppb >= 1 && p.ppb <= 7));
+                                if (p.route != kRouteKWin) CHECK(p.tail == 0 && !p.pipelined);
+                                if (p.route == kRouteKWin && p.refused == kRouteOk)
+                                    for (int w0 = 0; w0 < W; w0 += p.chunk) {
+                                        const int wc = W - w0 < p.chunk ? W - w0 : p.chunk;
+                                        const int wtail = route_wtail4096(k, p, a.n_pairs, w0, wc);
+                                        CHECK(0 <= wtail && wtail < k.n_cus && wtail <= wc);
+                                        if (!p.tail) CHECK(wtail == 0);
+                                    }
+                            }
+                }
+    CHECK(n_plans > 100000);
+    // the pipelined host copy: only k_win, only host windows beyond one sub-chunk; the tail gate is then closed
+    RouteCaps k = caps4096(3, 4096, 8);
+    RouteCall a = call4096(3, kHostSubChunk + 9);
+    CHECK(plan_route(k, a).pipelined && plan_route(k, a).tail == 0);
+    a.in_dev = true;
+    CHECK(!plan_route(k, a).pipelined && plan_route(k, a).tail == 1);
+    a.n_windows = kHostSubChunk;
+    a.in_dev = false;
+    CHECK(!plan_route(k, a).pipelined);
+    // a custom list of exactly kMaxPairs8 / kMaxPairs16 pairs still takes k_win8kl / k16, one more does not
+    for (int logL : {14, 15}) {
+        RouteCaps g;
+        g.generic = true;  g.n_cus = 8;  g.n_buoys = 8;  g.logL = logL;  g.logL1 = logL - 10;  g.logL2 = 10;  g.g_chunk = 64;
+        g.wscr = true;  g.ws_upw = 1;  g.ws_grid = 8;  g.k8 = logL == 14;  g.k16 = logL == 15;
+        RouteCall b;
+        b.n_windows = 8;  b.all_pairs = false;  b.pairs_given = true;
+        b.n_pairs = 640;
+        CHECK(plan_route(g, b).route == (logL == 14 ? kRouteKWin8 : kRouteK16));
+        b.n_pairs = 641;
+        CHECK(plan_route(g, b).route == (logL == 14 ? kRouteWinScr : kRouteWinEo15));
+    }
+    // the default list is recognised with and without a pointer, and nothing is read when the count is off
+    const int32_t d3[] = {0, 1, 0, 2, 1, 2}, s3[] = {0, 2, 0, 1, 1, 2};
+    CHECK(is_default_list(3, nullptr, 3) && is_default_list(3, d3, 3) && !is_default_list(3, s3, 3) && !is_default_list(3, nullptr, 2) &&
+          !is_default_list(3, d3, 2));
+}
+
 int main() {
+    test_route_invariants();
+    test_recorded_rows();
     test_options();
     test_create_args();
     test_request_conversions();
