@@ -351,7 +351,21 @@ int rmx_caf_batch(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pa
  *   weight     float [n_windows][n_pairs] = 1/(confidence+0.1) (tdoa_processor.py:267), or NULL = 1
  *   pos        double [n_windows][3]  ECEF metres        cost    double [n_windows]  f at pos
  *   iters      int32  [n_windows]     iterations used    (device pointers with RMX_OUT_DEVICE)
- * accuracy_meters of the reference = sqrt(cost / n_pairs) (tdoa_processor.py:300). */
+ * accuracy_meters of the reference = sqrt(cost / n_pairs) (tdoa_processor.py:300).
+ * Parity: pos, cost and iters are bit-identical, for every window, to tests/solve_kernel_ref.py, the float64 restatement
+ *   of k_solve that keeps the kernel's order of sums and products with one rounding per operation (no contraction into
+ *   fma; f64 divide and square root are correctly rounded).  The pair list is used as given: repeats, reversed pairs
+ *   and (i, i) are legal; swapping every pair to (j, i) while negating lag_int and lag_frac gives the same bits.
+ *   weight == NULL gives the bits of a weight array of ones.  oracle/solve_ref.py states the same rule with other sums
+ *   (numpy @, LU) and agrees to 1e-6 relative in the cost on the windows that reach the global minimum.
+ * Degenerate input gives finite outputs and the documented give-up: where no step can be accepted (all weights zero; the
+ *   centroid exactly on a buoy, which makes every Jacobian entry NaN; a failed Cholesky every time) the 25th rejection
+ *   takes lambda from 1e-3 past 1e12, so iters = min(25, max_iter), pos = the start point (the centroid) and cost = f
+ *   there.  A NaN trial cost compares false and counts as a rejection.
+ * Refusals (RMX_E_INVAL, rmx_last_error set, no output written): a NULL buffer, n_buoys outside 2..64, sample_rate_hz not
+ *   positive (NaN included), max_iter < 1, n_windows < 0, pairs == NULL with n_pairs neither 0 nor n_buoys (n_buoys - 1) / 2,
+ *   a custom list of fewer than 1 or more than 2016 pairs, a pair index outside 0..n_buoys-1.  n_windows == 0 returns
+ *   RMX_OK and writes nothing. */
 int rmx_solve_batch(rmx_ctx* ctx, const double* buoy_xyz, int n_buoys, const int32_t* pairs, int n_pairs,
                     const int32_t* lag_int, const float* lag_frac, const float* weight,
                     double sample_rate_hz, int n_windows, int max_iter, double* pos, double* cost,

@@ -643,7 +643,9 @@ class HyperbolicPositioning:
         """Batched form of triangulate_position on the GPU (rmx_solve_batch): one solve per window
         from the lag arrays XcorrEngine.correlate returned for `buoys` (detection-list order, all
         pairs i<j).  Same objective, start point and accuracy formula as the reference
-        (tdoa_processor.py:249-300).  Returns a list of (lat, lng, altitude, accuracy_meters)."""
+        (tdoa_processor.py:249-300).  confidence: None (every measurement counts 1), [W][P] as the lag arrays, or
+        1-D of length P = one confidence row for all windows (XcorrEngine.solve broadcasts the weight row to [W][P]);
+        any other shape is a ValueError.  Returns a list of (lat, lng, altitude, accuracy_meters)."""
         xyz = np.array([GeodeticCalculator.lat_lng_to_xyz(b.lat, b.lng, b.altitude) for b in buoys])
         weight = None if confidence is None else 1.0 / (np.asarray(confidence, np.float64) + 0.1)
         pos, cost, _ = engine.solve(xyz, lag_int, lag_frac, sample_rate_hz, weight=weight, max_iter=max_iter)

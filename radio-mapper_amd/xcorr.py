@@ -473,19 +473,45 @@ class XcorrEngine:
               pairs: Optional[np.ndarray] = None, max_iter: int = 60):
         """Batched hyperbolic position solve (rmx_solve_batch), host arrays in and out.
         buoy_xyz [B][3] ECEF metres; lag_int/lag_frac [W][P] as returned by correlate().
-        Returns (pos float64 [W][3], cost float64 [W], iters int32 [W])."""
-        bx = np.ascontiguousarray(buoy_xyz, dtype=np.float64).reshape(-1, 3)
+        weight: None (every measurement counts 1), float [W][P], or 1-D of length P = one row for all windows, broadcast
+        to [W][P].  pairs: None (all i < j in nested-loop order, P = B (B - 1) / 2) or int [P][2].
+        Returns (pos float64 [W][3], cost float64 [W], iters int32 [W]).
+        The C entry reads W * P elements from each of lag_int, lag_frac and weight, so every shape is checked here first:
+        a ValueError that names the argument, before any C call."""
+        bx = np.ascontiguousarray(buoy_xyz, dtype=np.float64)
+        if bx.size % 3 != 0 or not 2 <= bx.size // 3 <= 64:
+            raise ValueError(f"buoy_xyz must reshape to [B][3] with 2 <= B <= 64, got shape {bx.shape}")
+        bx = bx.reshape(-1, 3)
+        B = bx.shape[0]
         li = np.ascontiguousarray(lag_int, dtype=np.int32)
+        if li.ndim != 2:
+            raise ValueError(f"lag_int must be [W][P], got shape {li.shape}")
         lf = np.ascontiguousarray(lag_frac, dtype=np.float32)
+        if lf.shape != li.shape:
+            raise ValueError(f"lag_frac must have lag_int's shape {li.shape}, got {lf.shape}")
         W, P = li.shape
         wp = None
         if weight is not None:
-            wgt = np.ascontiguousarray(weight, dtype=np.float32)
+            wgt = np.asarray(weight, dtype=np.float32)
+            if wgt.shape == (P,):
+                wgt = np.broadcast_to(wgt, (W, P))
+            elif wgt.shape != (W, P):
+                raise ValueError(f"weight must be None, [{W}][{P}] or [{P}], got shape {wgt.shape}")
+            wgt = np.ascontiguousarray(wgt)
             wp = wgt.ctypes.data_as(C.c_void_p)
         pp = None
         if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+            pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+            if pairs.size != 2 * P:
+                raise ValueError(f"pairs must be [{P}][2] for lag arrays of {P} columns, got shape {pairs.shape}")
+            pairs = pairs.reshape(-1, 2)
             pp = pairs.ctypes.data_as(C.c_void_p)
+        elif P != B * (B - 1) // 2:
+            raise ValueError(f"pairs is None: lag_int needs {B * (B - 1) // 2} columns for {B} buoys, got {P}")
+        if not int(max_iter) >= 1:
+            raise ValueError(f"max_iter must be >= 1, got {max_iter}")
+        if not float(sample_rate_hz) > 0.0:
+            raise ValueError(f"sample_rate_hz must be positive, got {sample_rate_hz}")
         pos = np.zeros((W, 3), np.float64)
         cost = np.zeros(W, np.float64)
         iters = np.zeros(W, np.int32)

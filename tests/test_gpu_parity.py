@@ -433,8 +433,14 @@ def test_error_codes_on_device(xc):
         assert e.value.code == -5
         with pytest.raises(ValueError):
             eng.caf(np.zeros((2, 4, 4096), np.complex64), [0.0])  # wrong buoy count: refused before C reads it
-        with pytest.raises(xc.RmxError):
-            eng.solve(np.zeros((3, 3)), np.zeros((2, 3), np.int32), np.zeros((2, 3), np.float32), 0.0)   # fs = 0
+        with pytest.raises(ValueError):                          # fs = 0: the binding refuses it before the C call ...
+            eng.solve(np.zeros((3, 3)), np.zeros((2, 3), np.int32), np.zeros((2, 3), np.float32), 0.0)
+        import ctypes as C                                       # ... and the library refuses it on its own
+        bz, lz, fz = np.zeros((3, 3)), np.zeros((2, 3), np.int32), np.zeros((2, 3), np.float32)
+        oz = [np.zeros((2, 3)), np.zeros(2), np.zeros(2, np.int32)]
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        assert lib.rmx_solve_batch(eng._ctx, vp(bz), 3, None, 3, vp(lz), vp(fz), None, 0.0, 2, 60, *map(vp, oz), 0) == -1
+        assert b"sample_rate_hz" in lib.rmx_last_error(eng._ctx)
         # the engine is still usable after errors
         li, lf, pk = eng.correlate(iq[:2])
         assert li.shape == (2, 3) and np.all(li == -(4096 - 1)) and np.all(pk == 0.0)   # all-zero windows
