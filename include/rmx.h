@@ -104,8 +104,7 @@ int rmx_set_stream(rmx_ctx* ctx, void* hip_stream);
  * fused kernel), "stag" (0..5: which waves of the fused N = 4096 kernel run the two halves
  * between barriers in the opposite order; default 1), "win8" / "pk" (two other builds of that kernel,
  * tools/experiments/: present only in a -DRMX_EXPERIMENTS build, RMX_E_UNSUPPORTED otherwise), "dbg"
- * (ablation masks of the -DRMX_ABLATE timing build; every other build rejects the key with
- * RMX_E_UNSUPPORTED and compiles the masks out of all kernels).
+ * (the ablation masks of a timing-only build that was removed; the key is rejected with RMX_E_UNSUPPORTED).
  * Returns RMX_E_INVAL for an unknown key. */
 int rmx_set_option(rmx_ctx* ctx, const char* key, long value);
 

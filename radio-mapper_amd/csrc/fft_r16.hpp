@@ -48,18 +48,6 @@ __device__ __forceinline__ void dft4(float2& a0, float2& a1, float2& a2, float2&
 #define RMX_S1 0.38268343236508977173f  /* sin(pi/8) */
 #define RMX_RH 0.70710678118654752440f   /* sqrt(1/2) */
 
-template <int E>
-__device__ __forceinline__ float2 mul_w16(float2 a) {
-    if constexpr (E == 0) return a;
-    else if constexpr (E == 1) return cmul(a, make_float2(RMX_C1, -RMX_S1));
-    else if constexpr (E == 2) return make_float2((a.x + a.y) * RMX_RH, (a.y - a.x) * RMX_RH);
-    else if constexpr (E == 3) return cmul(a, make_float2(RMX_S1, -RMX_C1));
-    else if constexpr (E == 4) return make_float2(a.y, -a.x);
-    else if constexpr (E == 6) return make_float2((a.y - a.x) * RMX_RH, -(a.x + a.y) * RMX_RH);
-    else if constexpr (E == 9) return cmul(a, make_float2(-RMX_C1, RMX_S1));
-    else return a;
-}
-
 // acc + a*w (4 FMAs)
 __device__ __forceinline__ float2 cfma(float2 acc, float2 a, float2 w) {
     float re = fmaf(a.x, w.x, acc.x);

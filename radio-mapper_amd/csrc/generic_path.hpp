@@ -40,9 +40,7 @@
 namespace rmx {
 namespace gen {
 
-#ifndef RMX_PROD_BATCH
-#define RMX_PROD_BATCH 4
-#endif
+constexpr int kProdBatch = 4;      // spectrum-product loads in flight per thread (g_rows_inv)
 constexpr int kGThreads = 256;
 // threads per row of the row kernels: two threads per radix-16 group (the passes leave half of them idle, the
 // streaming loops use all: measured better than one thread per group on the 2048-point rows of cfg2)
@@ -60,12 +58,8 @@ __device__ __forceinline__ float2 g_cmulc(float2 a, float2 b) {   // a * conj(b)
 // execute in issue order, so the compiler-only fence is enough and no wave waits for another; else a barrier.
 template <bool LOCAL>
 __device__ __forceinline__ void xsync() {
-#ifdef RMX_EXP_NOBAR      // timing experiment only (wrong results): what would the remaining barriers of the register-block kernels cost?
-    wave_lds_order();
-#else
     if constexpr (LOCAL) wave_lds_order();
     else __syncthreads();
-#endif
 }
 // In-place transforms of R = 2^logR points held in LDS; tw[k] = W_R^k, k < R/2.  Up to FOUR radix-2 stages
 // are fused per pass: a radix-16 (8, 4, 2) butterfly in registers -- the blocks of fft_r16.hpp / win8.hpp -- so a
@@ -159,16 +153,11 @@ struct LdsFlat {
     };
     __device__ __forceinline__ H open(int E0) const { return H{x + E0}; }
 };
-#ifndef RMX_TILE_FLAT_FWD
-#define RMX_TILE_FLAT_FWD 1
-#endif
-#ifndef RMX_TILE_FLAT_INV
-#define RMX_TILE_FLAT_INV 0
-#endif
+constexpr bool kTileFlatFwd = true, kTileFlatInv = false;   // tile layout of the forward / inverse transforms
 template <int LOGT, bool FLAT>
 using LdsIOFor = std::conditional_t<LOGT == 0 || !FLAT, LdsIO, LdsFlat>;
-using TileFwd = LdsIOFor<4, RMX_TILE_FLAT_FWD != 0>;      // tile layout of g_cols_fwd / g_cols_inv
-using TileInv = LdsIOFor<4, RMX_TILE_FLAT_INV != 0>;
+using TileFwd = LdsIOFor<4, kTileFlatFwd>;      // tile layout of g_cols_fwd / g_cols_inv
+using TileInv = LdsIOFor<4, kTileFlatInv>;
 // Second layout of the same buffer: 16 complex of padding per 2^BM elements, e -> e + 16 (e >> BM).  lp() keeps a
 // thread's 16 neighbours (and lanes 16 elements apart) on distinct banks but puts 32 CONSECUTIVE elements on 34
 // slots (lanes 0 and 31 collide: every unit-stride access a 2-way conflict); this one keeps unit-stride accesses
@@ -336,7 +325,7 @@ __device__ __forceinline__ void dit_pass_m(int M, int logR, int b, const float2*
 template <int LOGT, class First, class Last>
 __device__ __forceinline__ void fft_dif(float2* x, int logR, const float2* __restrict__ tw, int tid, int nthr,
                                         const First& first, const Last& last) {
-    const LdsIOFor<LOGT, RMX_TILE_FLAT_FWD != 0> mid{x};
+    const LdsIOFor<LOGT, kTileFlatFwd> mid{x};
     int b = logR;
     if (b <= 4) {
         dif_pass_m<LOGT>(b, logR, b, tw, tid, nthr, first, last);
@@ -358,7 +347,7 @@ __device__ __forceinline__ void fft_dif(float2* x, int logR, const float2* __res
 template <int LOGT, class First, class Last>
 __device__ __forceinline__ void fft_dit_inv(float2* x, int logR, const float2* __restrict__ tw, int tid, int nthr,
                                             const First& first, const Last& last, const float2* __restrict__ tw16 = nullptr) {
-    const LdsIOFor<LOGT, RMX_TILE_FLAT_INV != 0> mid{x};
+    const LdsIOFor<LOGT, kTileFlatInv> mid{x};
     if (logR <= 4) {
         dit_pass_m<LOGT>(logR, logR, logR, tw, tid, nthr, first, last);
         return;
@@ -380,13 +369,13 @@ __device__ __forceinline__ void build_tw16(float2* t, const float2* __restrict__
 // in place in LDS, barrier behind the last pass too
 template <int LOGT = 0>
 __device__ __forceinline__ void lds_dif(float2* x, int logR, const float2* __restrict__ tw, int tid, int nthr) {
-    const LdsIOFor<LOGT, RMX_TILE_FLAT_FWD != 0> io{x};
+    const LdsIOFor<LOGT, kTileFlatFwd> io{x};
     fft_dif<LOGT>(x, logR, tw, tid, nthr, io, io);
     __syncthreads();
 }
 template <int LOGT = 0>
 __device__ __forceinline__ void lds_dit_inv(float2* x, int logR, const float2* __restrict__ tw, int tid, int nthr) {
-    const LdsIOFor<LOGT, RMX_TILE_FLAT_INV != 0> io{x};
+    const LdsIOFor<LOGT, kTileFlatInv> io{x};
     fft_dit_inv<LOGT>(x, logR, tw, tid, nthr, io, io);
     __syncthreads();
 }
@@ -731,7 +720,7 @@ __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, c
             const GPair pr = pairs[q];
             const float2* xi = spec + (((long)wl * n_buoys + pr.i) * n_rows + rib) * R;
             const float2* xj = spec_j + (((long)wl * n_buoys + pr.j) * n_rows + rib) * R;
-            batched<RMX_PROD_BATCH>(tid, R, tpr, [&](int n) -> float4 { const float2 u = xj[n], v = xi[n]; return make_float4(u.x, u.y, v.x, v.y); },
+            batched<kProdBatch>(tid, R, tpr, [&](int n) -> float4 { const float2 u = xj[n], v = xi[n]; return make_float4(u.x, u.y, v.x, v.y); },
                        [&](int n, float4 v) { x[lp(n)] = g_cmulc(make_float2(v.x, v.y), make_float2(v.z, v.w)); });
         }
         __syncthreads();
@@ -982,11 +971,7 @@ __device__ __forceinline__ void constexpr_pair(int ij, const float2 (&S)[NB][16]
 }
 // rows of 4096, default plan, at most 3 buoys: the passes' twiddles live in registers (FusedTw)
 __host__ __device__ constexpr bool fused_tw_regs(int nb, int logR, bool def) {
-#ifdef RMX_FUSED_NO_TWREG
-    return false;
-#else
     return def && logR == 12 && nb <= 3;
-#endif
 }
 template <int NB, int LOGR, bool DEF = false>      // DEF: the default plan (all pairs i < j in order), pair loop unrolled
 __global__ __launch_bounds__(kGThreads, 2) void g_rows_fused(const float2* __restrict__ cols, float2* __restrict__ prod,
@@ -1283,8 +1268,8 @@ __global__ __launch_bounds__(kGThreads, 2) void g_win_fused(const void* __restri
 // registers, and runs the inverse with the peak search behind its last pass.  The first pass's twiddles live in registers
 // (one butterfly per thread: they never change), the others' in small LDS tables.  L = 16384 (one 136 KiB transform per
 // CU) runs g_win_scr14 below -- 512 threads x two butterflies -- and this kernel's 1024-thread build only on request.
-// Build knobs (A/B experiments): RMX_WS_TWREG_FROM / RMX_WS_TWG_FROM (first-pass twiddles in
-// registers / from the global table from that log2 L on), RMX_WS_TW2REG (second pass's in registers too).
+// Settled A/Bs: first-pass twiddles in registers from log2 L = 9 on, never from the global table
+// (kTwGlobalFrom = 99), the second pass's not in registers.
 // Pass order: radix 16 from the whole window down (DIF) while more than four stages remain, the left-over 1..4
 // stages last, on the thread's 16 neighbouring elements: they end in registers, and the inverse starts there.
 template <int LOGR>
@@ -1292,18 +1277,10 @@ struct WinPlan {
     static constexpr int R = 1 << LOGR, tpr = R >> 4;
     static constexpr int ML = ((LOGR - 1) & 3) + 1, RADL = 1 << ML, NITL = 16 / RADL;   // the neighbour pass
     static constexpr int NP = (LOGR - ML) / 4;                                            // radix-16 passes, blocks LOGR, LOGR - 4, ..
-#ifndef RMX_WS_TWG_FROM
-#define RMX_WS_TWG_FROM 99
-#endif
-#ifndef RMX_WS_TWREG_FROM
-#define RMX_WS_TWREG_FROM 9
-#endif
-    static constexpr bool TW1REG = LOGR >= RMX_WS_TWREG_FROM && LOGR < RMX_WS_TWG_FROM;                  // first pass's twiddles in registers
-    static constexpr bool TW1GLOBAL = LOGR >= RMX_WS_TWG_FROM;                            // ... or read from the global table
-#ifndef RMX_WS_TW2REG
-#define RMX_WS_TW2REG 0
-#endif
-    static constexpr bool TW2REG = RMX_WS_TW2REG && NP >= 2 && tpr < 1024;               // the second pass's too
+    static constexpr int kTwRegFrom = 9, kTwGlobalFrom = 99;
+    static constexpr bool TW1REG = LOGR >= kTwRegFrom && LOGR < kTwGlobalFrom;                  // first pass's twiddles in registers
+    static constexpr bool TW1GLOBAL = LOGR >= kTwGlobalFrom;                            // ... or read from the global table
+    static constexpr bool TW2REG = false;                                                 // the second pass's too: settled off
     static constexpr int thr = tpr < kGThreads ? kGThreads : tpr, upw = thr / tpr;         // threads, windows per workgroup
     static constexpr int tab_off(int b) {                                                 // entries in front of pass b's LDS table
         int acc = 0;
@@ -1724,11 +1701,7 @@ __host__ __device__ constexpr int col_log_t(int l1) { return l1 >= 10 ? 3 : 4; }
 // at unrelated times.  Remapped, XCD k walks the tiles [k n/8, (k+1) n/8): its 64 resident workgroups read runs of
 // adjacent segments of the same rows together.
 __device__ __forceinline__ int xcd_tile(int bid, int n) {
-#ifdef RMX_NO_XCD_REMAP
-    return bid;
-#else
     return (n & 7) == 0 ? (bid & 7) * (n >> 3) + (bid >> 3) : bid;
-#endif
 }
 // threads of a column kernel: one radix-16 work item per thread and pass, 64 .. 1024
 __host__ __device__ constexpr int cols_threads(int l1, int log_t) {
@@ -1942,25 +1915,9 @@ __global__ __launch_bounds__(1024) void g_cols_inv(const float2* __restrict__ in
     // threads take consecutive columns: the same row segments a tile load would fetch); the last pass never
     // stores r: every output goes into the thread's running (max |r|^2, lowest 'full' index) and leaves only its
     // |r|^2 in the buffer, for the taps and the halo
-#ifdef RMX_EXP_COLS_NOCOMP   // timing experiment only (wrong results): the tile's loads alone, same row segments, 16 in flight per thread
-    {
-        float acc = 0.0f;
-        batched<16>(tid, L1 << kColLogT, nthr,
-                    [&](int E) -> float2 { return src[((E >> kColLogT) << l2) + c0 + (E & (kColT - 1))]; },
-                    [&](int, float2 e) { acc += e.x * e.x + e.y * e.y; });
-        best = acc;
-        bk = tid;
-        x[tid].x = acc;
-    }
-    if (false)
-#endif
     fft_dit_inv<kColLogT>(
         x, l1, twl, tid, nthr,
-#ifdef RMX_EXP_COLS_NOLOAD   // timing experiment only (wrong results): the tile's arithmetic alone, no global loads
-        make_src([&](int E) -> float2 { return make_float2(1e-6f * (float)(E + c0), 1.0f); }),
-#else
         make_src([&](int E) -> float2 { return src[((E >> kColLogT) << l2) + c0 + (E & (kColT - 1))]; }),
-#endif
         make_dst([&](int E0, int off, float2 e) {
             const int E = E0 + off;
             const float v = e.x * e.x + e.y * e.y;

@@ -1,7 +1,7 @@
 // kwin.hpp -- the fused window kernel of the tuned N = 4096 path (k_win), its peak-record resolve routine, the
 // table loaders it shares with k_fwd / the pair kernels, and the host-side builder of its twiddle tables.
-// Split out of rmx_hip.hip so that tools/probe/kwin_bench.hip can compile and time this kernel (and experimental
-// variants of it) on its own; rmx_hip.hip includes it unchanged.
+// Split out of rmx_hip.hip so that tools/probe/kwin_bench.hip can compile and time this kernel on its own; rmx_hip.hip
+// includes it unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,15 +10,7 @@
 #include <vector>
 
 #include "fft_r16.hpp"
-
-// cache policy of the spectrum scratch accesses (buffer instruction aux bits on gfx950: 1 = sc0, 2 = sc1, 4 = nt); A/B'd in
-// tools/probe/kwin_bench.hip (LABNOTES R4.7): the default policy stays
-#ifndef RMX_KWIN_LOAD_AUX
-#define RMX_KWIN_LOAD_AUX 0
-#endif
-#ifndef RMX_KWIN_STORE_AUX
-#define RMX_KWIN_STORE_AUX 0
-#endif
+#include "lag_bounds.hpp"
 
 namespace rmx {
 
@@ -71,29 +63,10 @@ __device__ __forceinline__ void load_tw1(float2 (&tw1)[16], const float4* __rest
 // in another wave.  The pair's winner is resolved by one lane after the NEXT pair's barrier.
 constexpr int kLdsWinImg = kLdsXchg;                                 // 69632 each, two of them
 constexpr int kLdsWinTw2 = 2 * kLdsWinImg;
-#ifdef RMX_KWIN_PEAK2
-// Peak search, second generation (round 5, VERDICT r04 #1b/c; an A/B build, NOT the default): a wave only finds its maximum
-// and the LANE that holds it; that lane and its two neighbours l*-2, l*+2 park their sixteen |r|^2 beside the halo rows, and
-// the slot, the 'full' index and the taps are worked out by the resolver (once per batch, on one of the early waves)
-// instead of by sixteen compares + sixteen selects in every lane of every pair.  Seven rows per wave and slot instead of
-// four: the ring shrinks to 4 slots, batches of 3.  Measured (tools/probe/kwin_bench, same box, bit-identical outputs):
-// SQ_INSTS_VALU 9.03e8 -> 8.62e8 per launch (-4.5 %), SQ_WAIT_ANY 3.95e8 -> 4.52e8 (+14 %), 1.675 -> 1.673 ms: the
-// instructions removed come back as waiting -- the interval between two barriers is set by dependent latencies (LDS round
-// trips, the DPP chain, the barrier itself), not by VALU issue slots.  LABNOTES.md R5.1.
-constexpr int kResSlots = 4;
-constexpr int kResBatch = 3;
-constexpr int kHaloRows = 7;   // lanes 0, 1, 62, 63, then l*-2, l*, l*+2
-#ifndef RMX_KWIN_RES_MASK
-#define RMX_KWIN_RES_MASK 3    /* the resolving wave rotates over waves 0-3 (A/B: 7 = over all eight) */
-#endif
-#else
-#ifndef RMX_KWIN_RES_MASK
-#define RMX_KWIN_RES_MASK 7
-#endif
+constexpr int kResWaveMask = 7;   // the resolving wave rotates over all eight waves (seq & 7)
 constexpr int kResSlots = 8;   // record ring; winners are resolved in batches of kResBatch pairs
 constexpr int kResBatch = 7;   // < kResSlots: the pair after a batch writes a slot the resolver is not reading
 constexpr int kHaloRows = 4;
-#endif
 constexpr int kLdsWinHalo = kLdsWinTw2 + kLdsTw2;                           // [slots][8][rows][16] float
 constexpr int kLdsWinRed = kLdsWinHalo + kResSlots * 8 * kHaloRows * 16 * 4;   // [slots][8] float4
 constexpr int kLdsWinOidx = kLdsWinRed + kResSlots * 8 * 16;                // [slots] int: output slot of the pair
@@ -168,88 +141,6 @@ __device__ __forceinline__ void resolve_batch(int lane, const float4* red, const
     }
 }
 
-#ifdef RMX_KWIN_PEAK2
-// The same for the second-generation records: red[slot][wave] = {max |r|^2 of the wave, the lane l* that holds it}; the
-// halo block holds per (slot, wave) seven rows of sixteen |r|^2: lanes 0, 1, 62, 63 (rows 0-3) and l*-2, l*, l*+2 (rows 4-6,
-// where those are not halo lanes themselves).  lane = 8*g + r works on wave r's record of the g-th pair of the batch: the
-// slot is the lowest one of l*'s row that equals the maximum, the 'full' index follows from (wave, lane, slot).
-__device__ __forceinline__ void resolve_batch2(int lane, const float4* red, const float* halo, const int* oidx,
-                                               int first, int cnt, long obase, float out_scale,
-                                               int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                               float* __restrict__ peak) {
-    const int g = lane >> 3, r = lane & 7;
-    const bool act = g < cnt;
-    const int slot = (first + g) & (kResSlots - 1);
-    const float* rf = reinterpret_cast<const float*>(red) + 4 * (slot * 8 + r);
-    const float ex_raw = rf[0];
-    const int ls = reinterpret_cast<const int*>(rf)[1] & 63;
-    auto row_of = [&](int ln) -> int { return ln < 2 ? ln : (ln >= 62 ? ln - 60 : 5); };
-    const float4* wrow = reinterpret_cast<const float4*>(halo + ((slot * 8 + r) * kHaloRows + row_of(ls)) * 16);
-    int qs = 15;
-#pragma unroll
-    for (int j = 3; j >= 0; --j) {          // descending: the lowest slot wins
-        const float4 v = wrow[j];
-        if (v.w == ex_raw) qs = 4 * j + 3;
-        if (v.z == ex_raw) qs = 4 * j + 2;
-        if (v.y == ex_raw) qs = 4 * j + 1;
-        if (v.x == ex_raw) qs = 4 * j;
-    }
-    const int tw = r * 64 + ls, pw = tw & 1, uw = tw >> 1;
-    const float ex = act ? ex_raw : -3.0f;
-    const int k = act ? (pw ? uw - 1 : uw + kM - 1) + 256 * qs : 0x7fffffff;
-    const int out = oidx[slot];
-    float gmax = ex;                                     // max over the 8 lanes of the group
-    gmax = fmaxf(gmax, __builtin_bit_cast(float, dpp_i<0xB1>(__builtin_bit_cast(int, gmax))));
-    gmax = fmaxf(gmax, __builtin_bit_cast(float, dpp_i<0x4E>(__builtin_bit_cast(int, gmax))));
-    gmax = fmaxf(gmax, __builtin_bit_cast(float, dpp_i<0x141>(__builtin_bit_cast(int, gmax))));
-    int kstar = (ex == gmax) ? k : 0x7fffffff;
-    kstar = min(kstar, dpp_i<0xB1>(kstar));
-    kstar = min(kstar, dpp_i<0x4E>(kstar));
-    kstar = min(kstar, dpp_i<0x141>(kstar));
-    const bool win = act && ex == gmax && k == kstar;     // exactly one lane per active group
-    // neighbour taps k*-1, k*+1: lanes l*-2 / l*+2 of the winner's wave (rows 4 / 6), or a halo lane of some wave
-    auto tap = [&](int kk) -> float {
-        kk = kk < 0 ? 0 : (kk > 2 * kM - 2 ? 2 * kM - 2 : kk);
-        int tt, q;
-        k_to_owner(kk, tt, q);
-        const int ln = tt & 63;
-        int row = ln < 2 ? ln : (ln >= 62 ? ln - 60 : 5 + ((ln - ls) >> 1));
-        row = row < 0 ? 0 : (row > kHaloRows - 1 ? kHaloRows - 1 : row);   // (lanes that lost their group compute garbage: keep it inside)
-        return halo[((slot * 8 + (tt >> 6)) * kHaloRows + row) * 16 + q];
-    };
-    const int kc = win ? k : (kM - 1);
-    const float tm = tap(kc - 1), tp = tap(kc + 1);
-    const float b = sqrtf(fmaxf(ex, 0.0f)) * out_scale;
-    const float a = sqrtf(fmaxf(tm, 0.0f)) * out_scale;
-    const float c = sqrtf(fmaxf(tp, 0.0f)) * out_scale;
-    const double den = (double)a - 2.0 * (double)b + (double)c;
-    float frac = 0.0f;
-    if (kc > 0 && kc < 2 * kM - 2 && den != 0.0) frac = (float)(0.5 * ((double)a - (double)c) / den);
-    if (win) {
-        lag_int[obase + out] = kc - (kM - 1);
-        lag_frac[obase + out] = frac;
-        peak[obase + out] = b;
-    }
-}
-#endif
-
-#ifdef RMX_KWIN_STAMPS
-// diagnostic build (tools/probe/kwin_bench.hip -DRMX_KWIN_STAMPS): shader-clock stamps of workgroup's wave 0 at the phase
-// boundaries of every window it processes; no stamp exists in the product build
-__device__ long long rmx_stamps[256 * 64 * 4];
-__device__ int rmx_stamps_vm[256 * 64 * 8];
-__device__ int rmx_stamps_bar[256 * 64 * 8 * 2];
-__device__ int rmx_stamps_p1[256 * 64 * 8 * 8];   // per wave: ticks of phase 1 by piece (RMX_LAP buckets)
-__device__ int rmx_stamps_pc[256 * 64 * 8 * 2];    // per wave: ticks in the first / second piece between two barriers of the anchor loop   // per wave: ticks draining its LDS stores in front of the barriers / waiting at them   // per wave: ticks spent in the vmcnt wait at the head of h1, summed over the window's pairs
-#define RMX_STAMP(slot)                                                                              \
-    do {                                                                                             \
-        if (t == 0 && (wl / (int)gridDim.x) < 64)                                                    \
-            rmx_stamps[((int)blockIdx.x * 64 + wl / (int)gridDim.x) * 4 + (slot)] = __builtin_readcyclecounter(); \
-    } while (0)
-#else
-#define RMX_STAMP(slot) do { } while (0)
-#endif
-
 // Schedule of one window (all pairs i<j of B buoys; the anchor spectrum X_i is resident in registers,
 // X_j streams one pair ahead):
 //   anchor 0      X_0 is transformed straight into the anchor registers (never stored); every further
@@ -264,7 +155,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_win(const void* __restrict__ iq
                                                      const float2* __restrict__ tw2_g, int n_buoys,
                                                      long first_window, float out_scale,
                                                      int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                                     float* __restrict__ peak, int n_win, int dbg_rt, int stag) {
+                                                     float* __restrict__ peak, int n_win, int /* was dbg_rt */, int stag) {
     constexpr bool BOUNDED = false;
     constexpr LagBounds lb{nullptr, 0, 0, 0};   // (named by the bounded branches only)
 #include "kwin_body.hpp"
@@ -278,7 +169,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_win_lb(const void* __restrict__
                                                         const float2* __restrict__ tw2_g, int n_buoys,
                                                         long first_window, float out_scale,
                                                         int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                                        float* __restrict__ peak, int n_win, int dbg_rt, int stag, LagBounds lb) {
+                                                        float* __restrict__ peak, int n_win, int /* was dbg_rt */, int stag, LagBounds lb) {
     constexpr bool BOUNDED = true;
 #include "kwin_body.hpp"
 }

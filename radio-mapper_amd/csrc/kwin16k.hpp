@@ -22,13 +22,11 @@
 // the XCD's L2 (k_win8k, the same situation at N = 8192: 4.9 us per transform at 7 TB/s of cache traffic).  Here the 32
 // workgroups of an XCD work on the pairs of the SAME one or two windows at a time (item order below), whose spectra then
 // come out of that XCD's 4 MiB L2: the k_win8k probe with XCD-shared spectra runs at 3.4 us per transform
-// (tools/probe/k8_bench.hip -DK8_SHARE=8; LABNOTES R5.6).
+// (LABNOTES R5.6).
 //   k16_fwd    one (window, buoy) per workgroup turn: samples once (64 per thread), four quarter transforms, four 64 KiB
 //              quarter spectra in thread-register order to spec[(w B + b) 4 + h]
 //   k16_pairs  persistent, grid = 8 S: workgroup b belongs to XCD x = b mod 8 (round-robin dispatch) and walks the items
 //              s, s + S, ... (s = b / 8) of that XCD's list [(window x, pair 0..P-1), (window x + 8, ...), ...]
-// -DK16_NO_SPEC / K16_NO_PEAK / K16_NO_SAMPLE / K16_NO_STORE: timing-only builds of the harness (results wrong);
-// -DK16_STORE_AUX=n: cache policy bits of the spectrum stores (measured: +-1 %).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -253,9 +251,7 @@ __global__ __launch_bounds__(kThreads, 2) void k16_fwd(const void* __restrict__ 
                 asm volatile("" : "+v"(x[q].x), "+v"(x[q].y), "+v"(x[q + 1].x), "+v"(x[q + 1].y), "+v"(x[q + 2].x),
                              "+v"(x[q + 2].y), "+v"(x[q + 3].x), "+v"(x[q + 3].y));
             // (behind the last item: its own samples once more, into dead registers -- unconditional requests, see kwin8k.hpp)
-#ifndef K16_NO_SAMPLE
             load_group(xin, xn, hc);
-#endif
             __builtin_amdgcn_sched_barrier(0);
             mul_row(x, reinterpret_cast<const float4*>(tws_lds + (h + 4 * p) * 16));
             dft16(x);
@@ -277,14 +273,7 @@ __global__ __launch_bounds__(kThreads, 2) void k16_fwd(const void* __restrict__ 
                 float e0 = x[2 * j].x, e1 = x[2 * j].y, e2 = x[2 * j + 1].x, e3 = x[2 * j + 1].y;
                 asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3));
                 const u32x4 w = {__float_as_uint(e0), __float_as_uint(e1), __float_as_uint(e2), __float_as_uint(e3)};
-#ifndef K16_NO_STORE
-#ifndef K16_STORE_AUX
-#define K16_STORE_AUX 0
-#endif
-                __builtin_amdgcn_raw_buffer_store_b128(w, ss, soff + (h * 8 + j) * (kThreads * 16), 0, K16_STORE_AUX);
-#else
-                if (e0 == 12345.678f) __builtin_amdgcn_raw_buffer_store_b128(w, ss, soff + (h * 8 + j) * (kThreads * 16), 0, 0);
-#endif
+                __builtin_amdgcn_raw_buffer_store_b128(w, ss, soff + (h * 8 + j) * (kThreads * 16), 0, 0);
             }
         };
         quarter(std::integral_constant<int, 0>{}, x0);
@@ -357,11 +346,9 @@ __global__ __launch_bounds__(kThreads, 2) void k16_pairs(const float4* __restric
         constexpr int J = decltype(part)::value;
         int bo = __builtin_amdgcn_readfirstlane(sidx) * kQuarterBytes;
         asm volatile("" : "+s"(bo));
-#ifndef K16_NO_SPEC
         const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rs, soff, bo + J * (kThreads * 16), 0);
         d.set(2 * J, __uint_as_float(w.x), __uint_as_float(w.y));
         d.set(2 * J + 1, __uint_as_float(w.z), __uint_as_float(w.w));
-#endif
     };
     auto window_rsrc = [&](int w) __attribute__((always_inline)) {
         return __builtin_amdgcn_make_buffer_rsrc(
@@ -527,12 +514,6 @@ __global__ __launch_bounds__(kThreads, 2) void k16_pairs(const float4* __restric
             auto search32 = [&](const float (&lo)[16], const float (&hi)[16], auto rlo_c, auto rhi_c, auto phase_c)
                                 __attribute__((always_inline)) {
                 constexpr int rlo = decltype(rlo_c)::value, rhi = decltype(rhi_c)::value, phase = decltype(phase_c)::value;
-#ifdef K16_NO_PEAK
-                float acc = 0.0f;
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc += lo[q] + hi[q];
-                if (acc == 12345.678f) lag_int[0] = 1;
-#else
                 if (is_halo) {
                     float4* hp = reinterpret_cast<float4*>(halo + ((rb * 8 + wave) * 4 + hl) * 64);
 #pragma unroll
@@ -574,7 +555,6 @@ __global__ __launch_bounds__(kThreads, 2) void k16_pairs(const float4* __restric
                     *reinterpret_cast<u32x4*>(red + (rb * 8 + wave) * 2 + phase) = rec;
                     if (wave == 0 && phase == 0) oidx[rb] = out;
                 }
-#endif
             };
             {
                 float m1[16], m3[16];

@@ -362,9 +362,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
         dft16_tw<false>(v, tw1);
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = cmul(v[q], g2[h]);
-#ifndef K8_NO_TWIST
         twist(v, h);
-#endif
         pair_fmac8(v[0].x, v[0].y, v[1].x, v[1].y, v[2].x, v[2].y, v[3].x, v[3].y, sgn);
         pair_fmac8(v[4].x, v[4].y, v[5].x, v[5].y, v[6].x, v[6].y, v[7].x, v[7].y, sgn);
         pair_fmac8(v[8].x, v[8].y, v[9].x, v[9].y, v[10].x, v[10].y, v[11].x, v[11].y, sgn);
@@ -374,16 +372,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
             for (int q = 0; q < 16; ++q) ev.set(q, v[q].x, v[q].y);
             return;
         } else {
-#ifdef K8_NO_PEAK
-        {
-            float acc = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc += v[q].x * ev.re[q] + v[q].y * ev.im[q];
-            if (acc == 12345.678f) lag_int[0] = 1;
-            ++npend; ++npair;
-            return;
-        }
-#endif
         // held (x, y) = (Im, Re); lanes p = 1 take T' = i V = (V.y, -V.x): r0 = E + T' (m), r1 = E - T' (m + 8192)
         float m0[16], m1[16];
 #pragma unroll
@@ -494,14 +482,12 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
         // every CU of the chip at the same time).  UNCONDITIONAL requests (behind the last buoy: its own samples once more,
         // into dead registers): hipcc merges a condition around them with the loop's exit test and sinks them to the loop
         // latch, where the next fold waits.
-#ifndef K8_NO_SAMPLE
         {
             const int nbu = __builtin_amdgcn_readfirstlane(nb);
             if constexpr (h == 0) load_x(pa, nbu, 0);
             else load_x(pb, nbu, kN8 / 2);
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
         twist(x, h);
         dft16(x);
         mul_tw1(x, tw1);
@@ -524,9 +510,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
     load_x(pb, 0, kN8 / 2);
     int q0 = 0;                            // first pair of the generic loop below
     int ni = 0, nj = 1;                    // default list: the pair the generic loop is at
-#ifdef K8_NO_FWD
-    if (n_win < 0)
-#endif
     if (!pairs && B >= 2) {
         // ---- default pair list: the first anchor's run INTERLEAVED with the forward transforms, k_win's schedule.  With all
         // forward transforms of a window in one block every CU of the chip streams spectra out (and samples in) at the same
@@ -551,9 +534,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
             fold_both();
             // ---- half 0: X_j,0, stored for the later anchors, and e_0 of (0, j)
             fwd_half(std::integral_constant<int, 0>{}, x, j == 1, j + 1 < B ? j + 1 : j);
-#ifndef K8_NO_STORE
             store_spec(x, 2 * j);
-#endif
             pair_h1(std::integral_constant<int, 0>{}, x, [&](auto) __attribute__((always_inline)) {});
             barrier_hook(false);
             xchg_a2_read(img0, v, t);
@@ -561,9 +542,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
             pair_h2(std::integral_constant<int, 0>{}, v, j - 1);
             // ---- half 1
             fwd_half(std::integral_constant<int, 1>{}, x, false, j + 1 < B ? j + 1 : j);
-#ifndef K8_NO_STORE
             store_spec(x, 2 * j + 1);
-#endif
             pair_h1(std::integral_constant<int, 1>{}, x, [&](auto) __attribute__((always_inline)) {});
             barrier_hook(false);
             xchg_a2_read(img0, v, t);
@@ -580,13 +559,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
             cvt_x(pb);
             fold_both();
             fwd_half(std::integral_constant<int, 0>{}, x, true, b + 1 < B ? b + 1 : b);
-#ifndef K8_NO_STORE
             store_spec(x, 2 * b);
-#endif
             fwd_half(std::integral_constant<int, 1>{}, x, true, b + 1 < B ? b + 1 : b);
-#ifndef K8_NO_STORE
             store_spec(x, 2 * b + 1);
-#endif
         }
         __syncthreads();
     }
@@ -609,9 +584,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
         all_parts(sb, 2 * cur.j);
         park_anchor();                         // (phase 1 left half 0's TW1 table in the registers)
         pair_h1(std::integral_constant<int, 0>{}, sb, [&](auto part) __attribute__((always_inline)) {
-#ifndef K8_NO_SPEC
             load_spec_part(sb, 2 * cur.j + 1, part);           // the same pair's half 1
-#endif
         });
         bool pend_anchor = false;
         for (int q = q0; q < n_pairs; ++q) {
@@ -622,36 +595,28 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8kl(const void* __restrict__
             // ---- half 0
             barrier_hook(false);
             xchg_a2_read(img0, v, t);
-#ifndef K8_NO_B2
             __syncthreads();                    // every wave holds its inputs: the image is free for the next transform
-#endif
             if (pend_anchor) park_anchor();     // (requested one transform ago into ev, which half 0 overwrites just below)
             pend_anchor = false;
             pair_h2(std::integral_constant<int, 0>{}, v, q);
             pair_h1(std::integral_constant<int, 1>{}, sb, [&](auto part) __attribute__((always_inline)) {
-#ifndef K8_NO_SPEC
                 if constexpr (decltype(part)::value == 0) {
                     if (new_anchor) all_parts(sa, 2 * nxt.i);                  // sa is idle during this half (the anchor comes from LDS)
                 }
                 load_spec_part(sb, 2 * nxt.j, part);           // next pair's half 0 (behind the last pair: an index that exists)
-#endif
             });
             ++seq;
             // ---- half 1
             barrier_hook(false);
             xchg_a2_read(img0, v, t);
-#ifndef K8_NO_B2
             __syncthreads();
-#endif
             pair_h2(std::integral_constant<int, 1>{}, v, q);
             if (has_next) {
                 pair_h1(std::integral_constant<int, 0>{}, sb, [&](auto part) __attribute__((always_inline)) {
-#ifndef K8_NO_SPEC
                     if constexpr (decltype(part)::value == 0) {
                         if (new_anchor) all_parts(ev, 2 * nxt.i + 1);          // e_0 is dead until the next half 0
                     }
                     load_spec_part(sb, 2 * nxt.j + 1, part);
-#endif
                 });
                 pend_anchor = new_anchor;
             }

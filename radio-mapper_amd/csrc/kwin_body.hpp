@@ -1,12 +1,7 @@
 // kwin_body.hpp -- the body of the fused N = 4096 kernel, included by kwin.hpp into k_win (BOUNDED = false: the unbounded
 // kernel, the same source as before) and into k_win_lb (BOUNDED = true: the caller's lag window per pair, lag_bounds.hpp).
 // Not a header of its own: it expects the kernel's parameters, BOUNDED and lb in scope.
-#ifdef RMX_ABLATE
-    const int dbg = dbg_rt;   // timing-only ablation build (wrong results): tools/ablate.sh, tools/ablate_run.py
-#else
-    constexpr int dbg = 0;
-    (void)dbg_rt;
-#endif
+// A textual include, not a <U8, BOUNDED> device function: that form compiled all four kernels to other instruction bodies.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* img0 = reinterpret_cast<float2*>(smem);
     float2* img1 = reinterpret_cast<float2*>(smem + kLdsWinImg);
@@ -24,30 +19,20 @@
     load_tw2_to_lds_grouped(tw2_lds, tw2_g, t);
     float2 tw1[16];
     load_tw1(tw1, tw1_g, t);
-#ifndef RMX_KWIN_LDS1
     // second-generation exchanges (fft_r16.hpp): roles B and C keep their own digit (n0 / k1) in lane bits 0-3
     const float4* tw2row = reinterpret_cast<const float4*>(tw2_lds + (t & 15) * kTw2RowF2);
     const int loc_m0[2] = {__builtin_amdgcn_readfirstlane(wave * kLocWave),                 // this wave's region of image 0 / 1
                            __builtin_amdgcn_readfirstlane(kLdsWinImg + wave * kLocWave)};
     const int loc_rd = wave * kLocWave + loc_read_off(lane);
-#else
-    const float4* tw2row = reinterpret_cast<const float4*>(tw2_lds + (u & 15) * kTw2RowF2);
-#endif
     const float sgn = p ? -1.0f : 1.0f;
     const int kbase = p ? (u - 1) : (u + kM - 1);
     const int hl = lane < 2 ? lane : lane - 60;            // halo row of lanes 0,1,62,63
     const bool is_halo = lane < 2 || lane >= 62;
-#ifdef RMX_KWIN_PEAK2
-    const int peak_ca = is_halo ? hl * 64 : lane * 32 + 320;   // row byte offset of this lane's |r|^2 row = peak_ca - peak_cb * l*
-    const int peak_cb = is_halo ? 0 : 32;
-    const int wave_halo = __builtin_amdgcn_readfirstlane(wave * (kHaloRows * 64));
-#endif
     __syncthreads();
-#ifndef RMX_TW2_LDS
     // this thread's TW2 row W_256^(n0*k1), k1 = 0..15, kept in registers for the whole launch (30 of the 60 VGPRs
     // this kernel left unused at 2 waves per SIMD) instead of eight ds_read_b128 per transform: LDS array time is
     // not hidden behind the butterflies in this kernel, so the 11 % of it that these reads
-    // were came off the launch time one for one (1.778 -> 1.728 ms); -DRMX_TW2_LDS restores the LDS reads
+    // were came off the launch time one for one (1.778 -> 1.728 ms)
     C16 tw2r;
     {
         const float2* rowf2 = reinterpret_cast<const float2*>(tw2row);
@@ -58,7 +43,6 @@
             tw2r.set(q, w.x, w.y);
         }
     }
-#endif
 
     // persistent workgroup: the tables above are loaded once, then windows blockIdx.x, +gridDim.x, ...
     for (int wl = blockIdx.x; wl < n_win; wl += gridDim.x) {
@@ -71,51 +55,18 @@
     int seq = 0;         // transform counter: selects the exchange image
     int npair = 0;       // pair counter: selects the record slot (ring of kResSlots)
     int npend = 0;       // pairs whose records await a resolve
-#ifdef RMX_KWIN_STAMPS
-    int stamp_vm = 0, stamp_drain = 0, stamp_bar = 0, stamp_pc1 = 0, stamp_pc2 = 0;
-    int lap_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long lap_last = __builtin_readcyclecounter();
-    bool lap_on = true;
-    // lap timer of phase 1: the time since the previous lap goes to bucket k (0 forward role A, 1 its barrier, 2 roles B + C,
-    // 3 spectrum store, 4 h1, 5 the pair's barrier, 6 h2)
-#define RMX_LAP(k) do { if (lap_on) { const long long c_ = __builtin_readcyclecounter(); lap_acc[k] += (int)(c_ - lap_last); lap_last = c_; } } while (0)
-#else
-#define RMX_LAP(k) do { } while (0)
-#endif
-
 
     auto barrier_hook = [&](bool flush) __attribute__((always_inline)) {
-#ifdef RMX_KWIN_STAMPS
-        {   // how long does this wave wait for its own LDS stores to drain, and then at the barrier for the others?
-            const long long c0 = __builtin_readcyclecounter();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const long long c1 = __builtin_readcyclecounter();
-            __syncthreads();
-            const long long c2 = __builtin_readcyclecounter();
-            stamp_drain += (int)(c1 - c0);
-            stamp_bar += (int)(c2 - c1);
-        }
-#else
-        if (!(dbg & 1)) __syncthreads();
-#endif
+        __syncthreads();
         if (npend == kResBatch || (flush && npend > 0)) {
-#ifdef RMX_KWIN_PEAK2
-            // one of waves 0-3: they reach every barrier ~950 ticks ahead of waves 4-7 (the older wave of a SIMD wins every
-            // arbiter), so the resolve is paid out of their waiting time
-            if (!(dbg & 2) && !(dbg & 256) && wave == (seq & RMX_KWIN_RES_MASK))
-                resolve_batch2(lane, red, halo, oidx, (npair - npend) & (kResSlots - 1), npend, obase, out_scale, lag_int,
-                               lag_frac, peak);
-#else
-            if constexpr (BOUNDED) {
-                if (!(dbg & 2) && !(dbg & 256) && wave == (seq & RMX_KWIN_RES_MASK))
+            if (wave == (seq & kResWaveMask)) {
+                if constexpr (BOUNDED)
                     resolve_batch<true>(lane, red, halo, oidx, (npair - npend) & (kResSlots - 1), npend, obase, out_scale,
                                         lag_int, lag_frac, peak, lb, first_window + wl);
-            } else {
-            if (!(dbg & 2) && !(dbg & 256) && wave == (seq & RMX_KWIN_RES_MASK))
-                resolve_batch(lane, red, halo, oidx, (npair - npend) & (kResSlots - 1), npend, obase, out_scale, lag_int,
-                              lag_frac, peak);
+                else
+                    resolve_batch(lane, red, halo, oidx, (npair - npend) & (kResSlots - 1), npend, obase, out_scale, lag_int,
+                                  lag_frac, peak);
             }
-#endif
             npend = 0;
         }
     };
@@ -169,12 +120,7 @@
     // quarter G of the same loads (slots 4G..4G+3): issued between the groups of a butterfly layer
     auto load_x_part_from = [&](const __amdgpu_buffer_rsrc_t& rs, C16& d, int b, auto part) __attribute__((always_inline)) {
         constexpr int G = decltype(part)::value;
-        if (dbg & 64) return;   // ablation: no window-sample requests
-#ifndef RMX_KWIN_NO_SPREAD
         constexpr int Q0 = 2 * G, Q1 = 2 * G + 2;   // eighths: issued from the groups of BOTH butterfly layers of h1
-#else
-        constexpr int Q0 = 4 * G, Q1 = 4 * G + 4;
-#endif
         // (the buoy's byte offset is made opaque HERE so that each request's SGPR offset is computed in front of it (s_mov +
         // s_addk): left to itself hipcc precomputes all of them ahead of the loop, runs out of SGPRs, and every request
         // then pays v_readlane + s_nop 4 to get its offset back out of a spill lane.  One `s_add_i32` per request in a
@@ -206,18 +152,13 @@
     };
     auto load_spec_part = [&](C16& d, int b, auto part) __attribute__((always_inline)) {
         constexpr int G = decltype(part)::value;
-        if (dbg & 32) b = 1;   // ablation: every request hits the same (cache-resident) spectrum
-        if (dbg & 128) return;  // ablation: no spectrum requests
-#ifndef RMX_KWIN_NO_SPREAD
         constexpr int J0 = G, J1 = G + 1;
-#else
-        constexpr int J0 = 2 * G, J1 = 2 * G + 2;
-#endif
         int bo = b * (8 * kThreads * 16);   // (opaque: see load_x_part_from)
+        // (last argument of the scratch loads / stores: cache policy aux bits, 1 = sc0, 2 = sc1, 4 = nt; 0 measured best, LABNOTES R4.7)
         asm volatile("" : "+s"(bo));
 #pragma unroll
         for (int j = J0; j < J1; ++j) {
-            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(ss, soff, bo + j * (kThreads * 16), RMX_KWIN_LOAD_AUX);
+            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(ss, soff, bo + j * (kThreads * 16), 0);
             d.set(2 * j, __uint_as_float(w.x), __uint_as_float(w.y));
             d.set(2 * j + 1, __uint_as_float(w.z), __uint_as_float(w.w));
         }
@@ -240,58 +181,29 @@
             // (an asm that keeps e0..e3 live) were right 200 calls out of 200, as is this immediate-soffset form, for
             // which the compiler inserts the s_nop itself.  (The SGPR form alone is fine: the probe, whose stores
             // do not reuse their data registers, has no wrong float.)
-            __builtin_amdgcn_raw_buffer_store_b128(w, ss, soff + (b * 8 + j) * (kThreads * 16), 0, RMX_KWIN_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(w, ss, soff + (b * 8 + j) * (kThreads * 16), 0, 0);
         }
     };
     // forward spectrum of the samples in x, in place (carries the 2^-6 of the TW1 table)
     auto fwd = [&](C16& xc) __attribute__((always_inline)) {
         float2* img = (seq & 1) ? img1 : img0;
         float2 x[16];
-#ifdef RMX_KWIN_STAMPS
-        RMX_LAP(6);                                       // (cvt_x and whatever else sits between h2 and here)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // bucket 7: waiting for the window samples (and the spectrum stores)
-        RMX_LAP(7);
-#endif
 #pragma unroll
         for (int q = 0; q < 16; ++q) x[q] = xc.get(q);
         mul_w32_odd(x);            // odd sub-transform input x*W32^q (W_L^u is folded into tw1)
         dft16(x);
         mul_tw1(x, tw1);
-#ifndef RMX_KWIN_LDS1
-        if (!(dbg & 8)) xchg_a2_write(img, x, t);
-        RMX_LAP(0);
+        xchg_a2_write(img, x, t);
         barrier_hook(false);
-        RMX_LAP(1);
-        if (!(dbg & 8)) xchg_b2_read(img, x, t);
-#else
-        if (!(dbg & 8)) xchg_a_write(img, x, t);
-        barrier_hook(false);
-        if (!(dbg & 8)) xchg_b_read(img, x, t);
-#endif
+        xchg_b2_read(img, x, t);
         dft16(x);
-#ifdef RMX_TW2_LDS
-        const float4 r0 = tw2row[0], r1 = tw2row[1];   // ahead of the exchange reads (see dft16_tw_row_l1)
-#endif
-        if (!(dbg & 4)) {
-#ifndef RMX_KWIN_LDS1
         loc_write16(loc_m0[seq & 1], x);
         wave_lds_order();
         loc_read16(smem + (seq & 1) * kLdsWinImg + loc_rd, x);
-#else
-        xchg_bc_write_b(img, x, t);
-        wave_lds_order();
-        xchg_bc_read_c(img, x, t);
-#endif
-        }
-#ifndef RMX_TW2_LDS
         dft16_tw<true>(x, tw2r);
-#else
-        dft16_tw_row(x, tw2row, r0, r1);   // W_256^(n0*k1) as pre-twiddle of the last pass
-#endif
 #pragma unroll
         for (int q = 0; q < 16; ++q) xc.set(q, x[q].x, x[q].y);   // (scaled by 2^-6 through the TW1 table)
         ++seq;
-        RMX_LAP(2);
     };
     // One pair = two halves around its only workgroup barrier.
     //   h1  conj-multiply merged into the role-C pass, wave-local exchange, role-B pass, stores into
@@ -306,14 +218,6 @@
     auto pair_h1 = [&](const C16& a, const C16& s, int tr, auto prefetch) __attribute__((always_inline)) {
         float2* img = (tr & 1) ? img1 : img0;
         float2 v[16];
-#ifdef RMX_KWIN_STAMPS
-        {   // how long does this wave wait for the spectra it requested a pair ahead?
-            const long long c0 = __builtin_readcyclecounter();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const long long c1 = __builtin_readcyclecounter();
-            stamp_vm += (int)(c1 - c0);
-        }
-#endif
         // R = X_j conj(X_i), (im,re)-swapped == swap(X_j) * X_i: merged into the first radix-16 pass
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = make_float2(s.im[q], s.re[q]);
@@ -325,58 +229,26 @@
         __builtin_amdgcn_sched_barrier(0);
         {   // layer 2 group by group: each group's outputs go to the wave-local image at once, and a
             // quarter of the next spectra is requested behind it
-            float2* wb = img + (u >> 4) * kBcHalf + (u & 15) * kBcRow + p;
-            (void)wb;
             dft16_layer2_emit(v, [&](auto kac, const float2& x0, const float2& x1, const float2& x2, const float2& x3)
                                      __attribute__((always_inline)) {
                 constexpr int ka = decltype(kac)::value;
-                if (!(dbg & 4)) {
-#ifndef RMX_KWIN_LDS1
-                    loc_write4<ka, ka + 4, ka + 8, ka + 12>(loc_m0[tr & 1], x0, x1, x2, x3);
-#else
-                    wb[2 * ka] = make_float2(x0.x, x0.y);
-                    wb[2 * (ka + 4)] = make_float2(x1.x, x1.y);
-                    wb[2 * (ka + 8)] = make_float2(x2.x, x2.y);
-                    wb[2 * (ka + 12)] = make_float2(x3.x, x3.y);
-#endif
-                }
-                if (!(dbg & 16)) prefetch(kac);
+                loc_write4<ka, ka + 4, ka + 8, ka + 12>(loc_m0[tr & 1], x0, x1, x2, x3);
+                prefetch(kac);
             });
         }
-#ifdef RMX_TW2_LDS
-        const float4 r0 = tw2row[0], r1 = tw2row[1];   // ahead of the exchange reads (see dft16_tw_row_l1)
-#endif
-        if (!(dbg & 4)) {
-            wave_lds_order();
-#ifndef RMX_KWIN_LDS1
-            loc_read16(smem + (tr & 1) * kLdsWinImg + loc_rd, v);
-#else
-            xchg_bc_read_b(img, v, t);
-#endif
-        }
-#ifndef RMX_TW2_LDS
+        wave_lds_order();
+        loc_read16(smem + (tr & 1) * kLdsWinImg + loc_rd, v);
         dft16_tw_l1<true>(v, tw2r);
-#else
-        dft16_tw_row_l1(v, tw2row, r0, r1);      // W_256^(n0*k1), k1 -> n1   (role B), layer 1
-#endif
         {
-#ifndef RMX_KWIN_LDS1
             float2* xb = img + xb2_base(t);                             // own k0 row of the [k0][n1][p][n0] image
-#else
-            float2* xb = img + (u >> 4) * kBcHalf + (u & 15) * 2 + p;   // own half-wave regions
-#endif
             dft16_layer2_emit(v, [&](auto kac, const float2& x0, const float2& x1, const float2& x2, const float2& x3)
                                      __attribute__((always_inline)) {
                 constexpr int ka = decltype(kac)::value;
-                if (!(dbg & 8)) {
-                    xb[ka * 32] = make_float2(x0.x, x0.y);
-                    xb[(ka + 4) * 32] = make_float2(x1.x, x1.y);
-                    xb[(ka + 8) * 32] = make_float2(x2.x, x2.y);
-                    xb[(ka + 12) * 32] = make_float2(x3.x, x3.y);
-                }
-#ifndef RMX_KWIN_NO_SPREAD
-                if (!(dbg & 16)) prefetch(std::integral_constant<int, ka + 4>{});
-#endif
+                xb[ka * 32] = make_float2(x0.x, x0.y);
+                xb[(ka + 4) * 32] = make_float2(x1.x, x1.y);
+                xb[(ka + 8) * 32] = make_float2(x2.x, x2.y);
+                xb[(ka + 12) * 32] = make_float2(x3.x, x3.y);
+                prefetch(std::integral_constant<int, ka + 4>{});
             });
         }
     };
@@ -384,11 +256,7 @@
         const float2* img = (tr & 1) ? img1 : img0;
         const int rb = npair & (kResSlots - 1);
         float2 v[16];
-#ifndef RMX_KWIN_LDS1
-        if (!(dbg & 8)) xchg_a2_read(img, v, t);
-#else
-        if (!(dbg & 8)) xchg_a_read(img, v, t);
-#endif
+        xchg_a2_read(img, v, t);
         dft16_tw<false>(v, tw1);                 // W_M^(u*k0) [* W_L^u odd], k0 -> n2   (role A)
         mul_w32_odd(v);                          // odd lanes: * W32^q
         // last radix-2 stage across the lane pair, up to a sign that |.| does not see:
@@ -407,104 +275,7 @@
 #pragma unroll
             for (int q = 0; q < 16; ++q) mag[q] = lag_mask(mag[q], kbase + q * 256, klo, khi);
         }
-        if (dbg & 2) {
-            float s = 0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) s += mag[q];
-            if (s == 12345.678f) lag_int[0] = 1;
-            ++npend; ++npair;
-            return;
-        }
-#ifdef RMX_KWIN_PEAK2
-        {
-            // lane maximum (8 x v_max3_f32), row maxima by four DPP steps, wave maximum on the scalar unit: |r|^2 >= +0 and
-            // the one sentinel is -1, so the float order is the signed-integer order of the bit patterns (s_max_i32)
-            float tmax, wrow;
-            asm volatile("v_max3_f32 %[t], %[m0], %[m1], %[m2]\n\tv_max3_f32 %[w], %[m3], %[m4], %[m5]\n\t"
-                         "v_max3_f32 %[t], %[t], %[m6], %[m7]\n\tv_max3_f32 %[w], %[w], %[m8], %[m9]\n\t"
-                         "v_max3_f32 %[t], %[t], %[ma], %[mb]\n\tv_max3_f32 %[w], %[w], %[mc], %[md]\n\t"
-                         "v_max3_f32 %[t], %[t], %[me], %[mf]\n\tv_max_f32 %[t], %[t], %[w]\n\t"
-                         "s_nop 1\n\t"
-                         "v_max_f32_dpp %[w], %[t], %[t] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                         "v_max_f32_dpp %[w], %[w], %[w] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                         "v_max_f32_dpp %[w], %[w], %[w] row_half_mirror row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                         "v_max_f32_dpp %[w], %[w], %[w] row_mirror row_mask:0xf bank_mask:0xf"
-                         : [t] "=&v"(tmax), [w] "=&v"(wrow)
-                         : [m0] "v"(mag[0]), [m1] "v"(mag[1]), [m2] "v"(mag[2]), [m3] "v"(mag[3]), [m4] "v"(mag[4]),
-                           [m5] "v"(mag[5]), [m6] "v"(mag[6]), [m7] "v"(mag[7]), [m8] "v"(mag[8]), [m9] "v"(mag[9]),
-                           [ma] "v"(mag[10]), [mb] "v"(mag[11]), [mc] "v"(mag[12]), [md] "v"(mag[13]), [me] "v"(mag[14]),
-                           [mf] "v"(mag[15]));
-            // wave maximum on the scalar unit (four v_readlane, three s_max_i32), winner lane by ballot + s_ff1: everything
-            // behind the DPP steps is one dependent chain, and a dependent instruction costs a wave ~10 cycles where an
-            // independent one costs 4 -- the chain is kept short (first PEAK2 build: ~40 links, no faster than the 75
-            // mostly independent instructions it replaced)
-            const int wi = __builtin_bit_cast(int, wrow);   // every lane: the max of its row of 16
-            const int r0 = __builtin_amdgcn_readlane(wi, 0), r1 = __builtin_amdgcn_readlane(wi, 16);
-            const int r2 = __builtin_amdgcn_readlane(wi, 32), r3 = __builtin_amdgcn_readlane(wi, 48);
-            int wmaxi, wtmp;
-            asm("s_max_i32 %0, %2, %3\n\ts_max_i32 %1, %4, %5\n\ts_max_i32 %0, %0, %1"
-                : "=&s"(wmaxi), "=&s"(wtmp) : "s"(r0), "s"(r1), "s"(r2), "s"(r3));
-            const unsigned long long hit = __ballot(__builtin_bit_cast(int, tmax) == wmaxi);
-            int ls;
-            if (__builtin_expect(__popcll(hit) == 1, 1)) {
-                ls = __ffsll((long long)hit) - 1;
-            } else {
-                // several lanes hold the maximum exactly (an exact tie, or an all-zero window): the lowest 'full' index decides,
-                // found the old way -- lowest slot per lane, wave minimum of the indices
-                const float wmaxf = __builtin_bit_cast(float, wmaxi);
-                int qa = 16, qb = 16, qc = 16, qd = 16;
-                argsel4<12>(qa, qb, qc, qd, mag[12], mag[13], mag[14], mag[15], wmaxf);
-                argsel4<8>(qa, qb, qc, qd, mag[8], mag[9], mag[10], mag[11], wmaxf);
-                argsel4<4>(qa, qb, qc, qd, mag[4], mag[5], mag[6], mag[7], wmaxf);
-                argsel4<0>(qa, qb, qc, qd, mag[0], mag[1], mag[2], mag[3], wmaxf);
-                const int qsel = min(min(qa, qb), min(qc, qd));
-                const int kw = wave_min_i32(qsel < 16 ? kbase + qsel * 256 : 0x7fffffff);
-                int ts, qs;
-                k_to_owner(kw, ts, qs);
-                ls = __builtin_amdgcn_readfirstlane(ts & 63);
-            }
-            // rows: the halo lanes always, l*-2 / l* / l*+2 where they are not halo lanes (whose row the resolver reads
-            // instead).  Writers' mask on the scalar unit: bits l*-2, l*, l*+2 (what falls off either end of the shifts is a
-            // halo lane or no lane) | lanes 0, 1, 62, 63.  Row byte offset: halo lanes hl * 64; the others
-            // (4 + (lane - l* + 2) / 2) * 64 = lane * 32 + 320 - l* * 32, i.e. peak_ca - peak_cb * l* with two per-lane constants.
-            const unsigned long long wmask = ((0x15ull << ls) >> 2) | 0xC000000000000003ull;
-            const int sbase = kLdsWinHalo + rb * (8 * kHaloRows * 64) + wave_halo;   // (scalar: wave_halo is held in an SGPR)
-#ifndef RMX_ABLATE
-            {
-                int addr;
-                unsigned long long sv;
-                const f32x4 d0 = {mag[0], mag[1], mag[2], mag[3]}, d1 = {mag[4], mag[5], mag[6], mag[7]};
-                const f32x4 d2 = {mag[8], mag[9], mag[10], mag[11]}, d3 = {mag[12], mag[13], mag[14], mag[15]};
-                asm volatile("v_mad_i32_i24 %[a], %[cb], %[nls], %[ca]\n\t"
-                             "v_add_u32 %[a], %[sb], %[a]\n\t"
-                             "s_mov_b64 %[sv], exec\n\t"
-                             "s_mov_b64 exec, %[m]\n\t"
-                             "ds_write_b128 %[a], %[d0]\n\t"
-                             "ds_write_b128 %[a], %[d1] offset:16\n\t"
-                             "ds_write_b128 %[a], %[d2] offset:32\n\t"
-                             "ds_write_b128 %[a], %[d3] offset:48\n\t"
-                             "s_mov_b64 exec, %[sv]"
-                             : [a] "=&v"(addr), [sv] "=&s"(sv)
-                             : [cb] "v"(peak_cb), [nls] "s"(-ls), [ca] "v"(peak_ca), [sb] "s"(sbase), [m] "s"(wmask), [d0] "v"(d0),
-                               [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3)
-                             : "memory");
-            }
-#else
-            if (((wmask >> lane) & 1) && !(dbg & 512)) {
-                float4* hp = reinterpret_cast<float4*>(smem + sbase + peak_ca - peak_cb * ls);
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4)
-                    hp[q4] = make_float4(mag[4 * q4], mag[4 * q4 + 1], mag[4 * q4 + 2], mag[4 * q4 + 3]);
-            }
-#endif
-            if (lane == 0) {
-                const u32x2 rec = {(unsigned)wmaxi, (unsigned)ls};
-                *reinterpret_cast<u32x2*>(red + rb * 8 + wave) = rec;
-                if (wave == 0) oidx[rb] = out_idx;
-            }
-        }
-#else
-        if (is_halo && !(dbg & 512)) {
+        if (is_halo) {
             float4* hp = reinterpret_cast<float4*>(halo + ((rb * 8 + wave) * kHaloRows + hl) * 16);
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4)
@@ -513,7 +284,6 @@
         float tmax = mag[0];
 #pragma unroll
         for (int q = 1; q < 16; ++q) tmax = fmaxf(tmax, mag[q]);
-#ifndef RMX_KWIN_OLD_PEAK
         // Lowest slot holding the lane's max (four select chains, descending so that lower slots win), with the four
         // row steps of the wave maximum issued BETWEEN the chains' groups: the DPP steps depend on each other, the
         // groups do not depend on them, so neither the 2 wait states in front of a DPP read nor the steps' latency
@@ -564,22 +334,6 @@
             k_to_owner(kw, ts, qs);
             ls = ts & 63;
         }
-#else
-        // lowest slot holding the max: four independent select chains
-        int qa = 16, qb = 16, qc = 16, qd = 16;
-        argsel4<12>(qa, qb, qc, qd, mag[12], mag[13], mag[14], mag[15], tmax);   // descending: lower slots win
-        argsel4<8>(qa, qb, qc, qd, mag[8], mag[9], mag[10], mag[11], tmax);
-        argsel4<4>(qa, qb, qc, qd, mag[4], mag[5], mag[6], mag[7], tmax);
-        argsel4<0>(qa, qb, qc, qd, mag[0], mag[1], mag[2], mag[3], tmax);
-        const int qsel = min(min(qa, qb), min(qc, qd));
-        const int kq = kbase + qsel * 256;
-        const float wmax = wave_max_f32(tmax);
-        const int kw = wave_min_i32(tmax == wmax ? kq : 0x7fffffff);
-        // the winner's neighbours k*-1, k*+1 live in lanes l*-2, l*+2 (same slot) when those exist
-        int ts, qs;
-        k_to_owner(kw, ts, qs);
-        const int ls = ts & 63;
-#endif
         // qs is wave-uniform (it comes out of the wave reductions): one indexed register read
         // (s_set_gpr_idx) instead of a 16-way select chain
         typedef float f16v __attribute__((ext_vector_type(16)));
@@ -594,24 +348,19 @@
             *reinterpret_cast<u32x4*>(red + rb * 8 + wave) = rec;
             if (wave == 0) oidx[rb] = out_idx;
         }
-#endif   // RMX_KWIN_PEAK2
         ++npend;
         ++npair;
     };
     auto pair = [&](const C16& a, const C16& s, int out_idx, auto prefetch) __attribute__((always_inline)) {
         pair_h1(a, s, seq, prefetch);
-        RMX_LAP(4);
         barrier_hook(false);                     // the pair's only barrier
-        RMX_LAP(5);
         pair_h2(seq, out_idx);
-        RMX_LAP(6);
         ++seq;
     };
     auto out_of = [&](int i, int j) -> int { return i * B - (i * (i + 1)) / 2 + (j - i - 1); };
 
     // ---- anchor 0: X_0 goes straight into the anchor registers (never stored); every other X_e is
     // transformed once, stored once for the later anchors, and used at once from registers for (0,e)
-    RMX_STAMP(0);
     load_x(sa, 0);
     if (B > 1) load_x(sb, 1);          // sb is free: X_1's samples travel while X_0 is transformed
     cvt_x(sa);
@@ -623,14 +372,12 @@
         cvt_x(sb);
         fwd(sb);
         store_spec(sb, e);
-        RMX_LAP(3);
         pair(sa, sb, out_of(0, e), [&](auto part) __attribute__((always_inline)) { load_x_part(sb, e + 1, part); });
     }
     if (B > 1) {
         cvt_x(sb);
         fwd(sb);
         store_spec(sb, B - 1);
-        RMX_LAP(3);
         pair(sa, sb, out_of(0, B - 1), [&](auto part) __attribute__((always_inline)) {
             if (B > 2) {               // next anchor 1 streams downwards from B-1: X_{B-1} is L2-hot
                 load_spec_part(sa, 1, part);
@@ -638,10 +385,6 @@
             }
         });
     }
-    RMX_STAMP(1);
-#ifdef RMX_KWIN_STAMPS
-    lap_on = false;
-#endif
     // ---- anchors 1..B-2: the stream direction alternates (odd anchors walk j down, even ones up), so
     // the first spectra an anchor streams are the ones the previous anchor touched last (L2 hits).
     // Between two barriers sit h2 of pair m and h1 of pair m+1, which are independent: waves 0-3 run
@@ -663,12 +406,7 @@
             int pi = hi, ps = hs + 1;
             if (ps >= B - 1 - pi) { ++pi; ps = 0; }
             const bool valid = pi + 1 < B;
-#ifdef RMX_KWIN_FORCE_ANCHOR   // timing experiment (results unchanged): the anchor spectrum is requested again for EVERY pair -- the
-            const bool new_anchor = valid;   // scratch traffic of a design that cannot keep its anchor resident (LABNOTES R4.6)
-#else
             const bool new_anchor = valid && pi != hi;
-#endif
-#ifndef RMX_KWIN_REQ_BRANCHY
             // Every instruction costs the issuing wave ~2 ns whatever its kind (tools/probe/valu_forms.hip), and the two
             // uniform branches around each of the eight requests were 45 scalar instructions per pair plus the vector
             // instructions hipcc used to carry their conditions: the streamed spectrum is now requested unconditionally
@@ -690,89 +428,35 @@
                 }
                 load_spec_part(sb, pj, part);
             });
-#else
-            const int pj = j_of(pi, ps);
-            pair_h1(sa, sb, tr, [&](auto part) __attribute__((always_inline)) {
-                if (valid) {
-                    if (pi != hi) load_spec_part(sa, pi, part);
-                    load_spec_part(sb, pj, part);
-                }
-            });
-#endif
         };
         if (M2 > 0) h1_of(ci, cs, seq);
         for (int m = 0; m < M2; ++m) {
             barrier_hook(false);
             const bool has_next = m + 1 < M2;
             const int out_idx = out_of(ci, j_of(ci, cs));
-#ifndef RMX_KWIN_PRIO_MODE
-#define RMX_KWIN_PRIO_MODE 1
-#endif
-#if !defined(RMX_KWIN_PRIO) && !defined(RMX_KWIN_NO_PRIO)
-#define RMX_KWIN_PRIO 1      /* default: on (-0.8 ... -1.0 % in three A/B runs, tools/probe/kwin_bench.hip) */
-#endif
-#ifdef RMX_KWIN_PRIO
             // The two waves of a SIMD share its issue slots (and the CU's LDS / vector-memory request paths), and every
-            // arbiter prefers the OLDER one: in-kernel stamps (tools/probe/kwin_bench.hip -DRMX_KWIN_STAMPS) show waves 0-3
+            // arbiter prefers the OLDER one: in-kernel shader-clock stamps (LABNOTES 6.2) showed waves 0-3
             // spending 51-60 k ticks per window in the two pieces between barriers where waves 4-7 need 57-64 k, and then
             // waiting ~950 ticks at every barrier for them (waves 4-7: ~270).  Priority outranks age, so waves 4-7 run the
             // FIRST of their two pieces at priority 1 and the second at 0.  It only helps the piece that is VALU-bound (h2
             // as first piece: 63.9 -> 58.1 k ticks; h1 does not react to priority), so the launch gains 0.8-1.0 %, not the 8 %
-            // an even split would give; priority during h2 only (mode 2) and priority 3 measured the same or less.
-#if RMX_KWIN_PRIO_MODE == 2   /* priority during h2 only (where it was seen to help), whichever piece that is */
-            if (wave >= 4) { if (late_h2) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(RMX_KWIN_PRIO); }
-#define RMX_PRIO_MID() do { if (wave >= 4) { if (late_h2) __builtin_amdgcn_s_setprio(RMX_KWIN_PRIO); else __builtin_amdgcn_s_setprio(0); } } while (0)
-#else
-            if (wave >= 4) __builtin_amdgcn_s_setprio(RMX_KWIN_PRIO);
-#define RMX_PRIO_MID() do { if (wave >= 4) __builtin_amdgcn_s_setprio(0); } while (0)
-#endif
-#else
-#define RMX_PRIO_MID() do { } while (0)
-#endif
-#ifdef RMX_KWIN_STAMPS
-            const long long p0 = __builtin_readcyclecounter();
-            long long p1;
-#define RMX_PIECE_MID() p1 = __builtin_readcyclecounter()
-#else
-#define RMX_PIECE_MID() do { } while (0)
-#endif
+            // an even split would give; priority during h2 only and priority 3 measured the same or less.
+            if (wave >= 4) __builtin_amdgcn_s_setprio(1);
             if (late_h2) {
                 if (has_next) h1_of(ni, ns, seq + 1);
-                RMX_PRIO_MID();
-                RMX_PIECE_MID();
+                if (wave >= 4) __builtin_amdgcn_s_setprio(0);
                 pair_h2(seq, out_idx);
             } else {
                 pair_h2(seq, out_idx);
-                RMX_PRIO_MID();
-                RMX_PIECE_MID();
+                if (wave >= 4) __builtin_amdgcn_s_setprio(0);
                 if (has_next) h1_of(ni, ns, seq + 1);
             }
-#ifdef RMX_KWIN_STAMPS
-            {
-                const long long p2 = __builtin_readcyclecounter();
-                stamp_pc1 += (int)(p1 - p0);
-                stamp_pc2 += (int)(p2 - p1);
-            }
-#endif
-#undef RMX_PIECE_MID
-#undef RMX_PRIO_MID
             ++seq;
             ci = ni; cs = ns;
             ++ns;
             if (ns >= B - 1 - ni) { ++ni; ns = 0; }
         }
     }
-    RMX_STAMP(2);
-#ifdef RMX_KWIN_STAMPS
-    if (lane == 0 && (wl / (int)gridDim.x) < 64) {
-        rmx_stamps_vm[((int)blockIdx.x * 64 + wl / (int)gridDim.x) * 8 + wave] = stamp_vm;
-        rmx_stamps_bar[(((int)blockIdx.x * 64 + wl / (int)gridDim.x) * 8 + wave) * 2] = stamp_drain;
-        rmx_stamps_bar[(((int)blockIdx.x * 64 + wl / (int)gridDim.x) * 8 + wave) * 2 + 1] = stamp_bar;
-        for (int k = 0; k < 8; ++k) rmx_stamps_p1[(((int)blockIdx.x * 64 + wl / (int)gridDim.x) * 8 + wave) * 8 + k] = lap_acc[k];
-        rmx_stamps_pc[(((int)blockIdx.x * 64 + wl / (int)gridDim.x) * 8 + wave) * 2] = stamp_pc1;
-        rmx_stamps_pc[(((int)blockIdx.x * 64 + wl / (int)gridDim.x) * 8 + wave) * 2 + 1] = stamp_pc2;
-    }
-#endif
     seq = 0;   // any wave may resolve the last pairs; take wave 0
     barrier_hook(true);
     }   // next window of this workgroup

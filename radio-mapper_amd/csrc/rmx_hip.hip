@@ -517,15 +517,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     const float4* __restrict__ spec, const float4* __restrict__ spec_j, const float4* __restrict__ tw1_g, const float2* __restrict__ tw2_g,
     const PairItem* __restrict__ items, const int* __restrict__ part_begin, int n_parts, int n_buoys, int n_pairs,
     int xcd_map, long first_window, float out_scale, int* __restrict__ lag_int, float* __restrict__ lag_frac,
-    float* __restrict__ peak, int dbg_rt, int i_wrap, LB... lb_pack) {
+    float* __restrict__ peak, int /* was dbg_rt */, int i_wrap, LB... lb_pack) {
     constexpr bool BOUNDED = sizeof...(LB) > 0;
     const LagBounds lb = lag_bounds_of(lb_pack...);
-#ifdef RMX_ABLATE
-    const int dbg = dbg_rt;   // timing-only ablation build (wrong results), as in k_win
-#else
-    constexpr int dbg = 0;
-    (void)dbg_rt;
-#endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* xl = reinterpret_cast<float2*>(smem);
     float2* tw2_lds = reinterpret_cast<float2*>(smem + kLdsXchg);
@@ -584,7 +578,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
             v[2 * j] = make_float2(b.y * a.x - b.x * a.y, b.x * a.x + b.y * a.y);
             v[2 * j + 1] = make_float2(b.w * a.z - b.z * a.w, b.z * a.z + b.w * a.w);
         }
-        if (it + 1 < it_end && !(dbg & 16)) {   // request the next pair's spectra: a whole pair of compute hides it
+        if (it + 1 < it_end) {   // request the next pair's spectra: a whole pair of compute hides it
             pi = items[it + 1];
             const float4* xj = spec_j + (wbase + pi.j) * (8 * kThreads);
 #pragma unroll
@@ -598,18 +592,16 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
         }
         dft16(v);                     // k2 -> n0   (role C)
         mul_tw2(v, tw2_lds, u & 15);  // W_256^(k1*n0)
-        if (!(dbg & 4)) {
         xchg_bc_write_c(xl, v, t);
         wave_lds_fence();
         xchg_bc_read_b(xl, v, t);
-        }
         dft16(v);                     // k1 -> n1   (role B)
-        if (!(dbg & 8)) xchg_b_write(xl, v, t);       // into this half wave's own region
-        if (!(dbg & 1)) __syncthreads();              // the pair's only barrier; also publishes pair it-1's winners
-        if (!(dbg & 2) && prev_out >= 0 && t == ((it - it_begin) & 7) * 64)
+        xchg_b_write(xl, v, t);       // into this half wave's own region
+        __syncthreads();              // the pair's only barrier; also publishes pair it-1's winners
+        if (prev_out >= 0 && t == ((it - it_begin) & 7) * 64)
             resolve_pair<BOUNDED>(reinterpret_cast<const float*>(magbuf + (buf ^ 1) * (4 * kThreads)), red + (buf ^ 1) * 8,
                                   obase + prev_out, out_scale, lag_int, lag_frac, peak, lb, first_window + wl, prev_out);
-        if (!(dbg & 8)) xchg_a_read(xl, v, t);
+        xchg_a_read(xl, v, t);
         mul_tw1(v, tw1);              // W_M^(u*k0) [* W_L^u on odd lanes]
         dft16(v);                     // k0 -> n2   (role A): e[n] (even lanes) / o[n]*W_L^u (odd lanes)
         if (p) {
@@ -630,10 +622,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
 #pragma unroll
             for (int q = 0; q < 16; ++q) mag[q] = lag_mask(mag[q], kbase + q * 256, klo, khi);
         }
-        if (dbg & 2) { float s = 0; 
-#pragma unroll
-            for (int q = 0; q < 16; ++q) s += mag[q];
-            if (s == 12345.678f) lag_int[0] = 1; prev_out = out_idx; continue; }
         float4* mb = magbuf + buf * (4 * kThreads) + t;
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4)
@@ -891,7 +879,6 @@ struct rmx_ctx {
     bool ppb_user = false;  // set through rmx_set_option: the small-batch rule then leaves it alone
     bool small_batch = true; // option small4096: few windows of N = 4096 through the per-transform kernels (see rmx_xcorr_batch)
     bool timing = false;
-    int dbg = 0;
     bool resident = true;
     int pk = 0;             // fused path: 1 = k_winp (k_win on packed fp32)
     int win8 = 0;           // fused path: 1 = k_win8 (8 points x 1024 threads, 4 waves/SIMD), 0 = k_win
@@ -1874,7 +1861,7 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
     wc *= n_bins;
     const int xcd_map = (wc % 8 == 0) ? 1 : 0;
     const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
-    // the streaming and the resident kernel (which takes c->dbg as well), each with or without its trailing structs
+    // the streaming and the resident kernel (which keeps one unused int argument), each with or without its trailing structs
     auto str = [&](auto kern, int windows, int xmap, long first, int wrap, auto... tail) {
         hipLaunchKernelGGL(kern, dim3(windows * n_parts), dim3(kThreads), kLdsBytes, c->stream, (const float4*)c->d_spec, spec_j,
                            c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xmap, first, out_scale,
@@ -1883,7 +1870,7 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
     auto res = [&](auto kern, auto... lb) {
         hipLaunchKernelGGL(kern, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream, (const float4*)c->d_spec, spec_j,
                            c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, (long)w0,
-                           out_scale, d_lag, d_frac, d_peak, c->dbg, i_wrap, lb...);
+                           out_scale, d_lag, d_frac, d_peak, 0, i_wrap, lb...);
     };
     RMX_TM_BEGIN(c);
     if (call.integrated()) {
@@ -2292,12 +2279,7 @@ int rmx_set_option(rmx_ctx* c, const char* key, long value) {
         return RMX_OK;
     }
     if (!strcmp(key, "dbg")) {
-#ifdef RMX_ABLATE
-        c->dbg = (int)value;
-        return RMX_OK;
-#else
-        return fail(c, RMX_E_UNSUPPORTED, "option 'dbg' exists only in the -DRMX_ABLATE timing build");
-#endif
+        return fail(c, RMX_E_UNSUPPORTED, "option 'dbg': the timing-only ablation build was removed");
     }
     if (!strcmp(key, "pk") || !strcmp(key, "win8")) {
 #ifdef RMX_EXPERIMENTS
@@ -2584,7 +2566,7 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
                 constexpr bool U8 = decltype(U)::value;
                 auto launch = [&](auto kern, auto... lb) {
                     hipLaunchKernelGGL(kern, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec, c->d_tw1,
-                                       c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, c->dbg, c->stag, lb...);
+                                       c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, 0, c->stag, lb...);
                 };
 #ifdef RMX_EXPERIMENTS
                 if (c->win8)

@@ -429,7 +429,7 @@ def test_error_codes_on_device(xc):
         with pytest.raises(xc.RmxError):
             eng.set_option("no_such_option", 1)
         with pytest.raises(xc.RmxError) as e:
-            eng.set_option("dbg", 2)                             # ablation masks exist only under -DRMX_ABLATE
+            eng.set_option("dbg", 2)                             # the ablation build was removed: refused
         assert e.value.code == -5
         with pytest.raises(ValueError):
             eng.caf(np.zeros((2, 4, 4096), np.complex64), [0.0])  # wrong buoy count: refused before C reads it

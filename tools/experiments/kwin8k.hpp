@@ -145,9 +145,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8k(const void* __restrict__ 
     // ---- phase 1: forward transforms, half-major (one TW1 table per half) ------------------------------------------
     load_x(sa, 0, 0);
     load_x(sb, 0, kN8 / 2);
-#ifdef K8_NO_FWD
-    if (n_win < 0)
-#endif
     for (int h = 0; h < 2; ++h) {
         load_tw1_half(h);
         for (int b = 0; b < B; ++b) {
@@ -169,12 +166,10 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8k(const void* __restrict__ 
                              "+v"(x[q + 2].y), "+v"(x[q + 3].x), "+v"(x[q + 3].y));
             {   // the next transform's samples travel during this one (the sample registers are free behind the fold)
                 const int nb = b + 1 < B ? b + 1 : 0;
-#ifndef K8_NO_SAMPLE
                 if (b + 1 < B || h == 0) {
                     load_x(sa, nb, 0);
                     load_x(sb, nb, kN8 / 2);
                 }
-#endif
             }
             twist(x, h);
             dft16(x);
@@ -188,9 +183,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8k(const void* __restrict__ 
             wave_lds_order();
             loc_read16(smem + (seq & 1) * kLdsWinImg + loc_rd, x);
             dft16_tw_row(x, tw2row, r0, r1);
-#ifndef K8_NO_STORE
             store_spec(x, 2 * b + h);
-#endif
             ++seq;
         }
     }
@@ -234,12 +227,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8k(const void* __restrict__ 
         float2 v[16];
         xchg_a2_read(img, v, t);
         dft16_tw<false>(v, tw1);
-#ifndef K8_NO_TW1
         load_tw1_half(h ^ 1);                   // the other half's table travels while the rest of this piece runs
-#endif
-#ifndef K8_NO_TWIST
         twist(v, h);
-#endif
         pair_fmac8(v[0].x, v[0].y, v[1].x, v[1].y, v[2].x, v[2].y, v[3].x, v[3].y, sgn);
         pair_fmac8(v[4].x, v[4].y, v[5].x, v[5].y, v[6].x, v[6].y, v[7].x, v[7].y, sgn);
         pair_fmac8(v[8].x, v[8].y, v[9].x, v[9].y, v[10].x, v[10].y, v[11].x, v[11].y, sgn);
@@ -249,16 +238,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8k(const void* __restrict__ 
             for (int q = 0; q < 16; ++q) ev.set(q, v[q].x, v[q].y);
             return;
         }
-#ifdef K8_NO_PEAK
-        {
-            float acc = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc += v[q].x * ev.re[q] + v[q].y * ev.im[q];
-            if (acc == 12345.678f) lag_int[0] = 1;
-            ++npend; ++npair;
-            return;
-        }
-#endif
         // held (x, y) = (Im, Re); lanes p = 1 take T' = i V = (V.y, -V.x): r0 = E + T' (m), r1 = E - T' (m + 8192)
         float m0[16], m1[16];
 #pragma unroll
@@ -339,14 +318,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_win8k(const void* __restrict__ 
             const Pair2 pr = pair_of(nx >> 1);
             const int si = __builtin_amdgcn_readfirstlane(2 * pr.i + (nx & 1)), sj = __builtin_amdgcn_readfirstlane(2 * pr.j + (nx & 1));
             pair_h1(sa, sb, tr, [&](auto part) __attribute__((always_inline)) {
-#ifndef K8_NO_SPEC
-#ifdef K8_ANCHOR_HOT      // timing experiment (wrong results): every anchor request hits one L2-resident spectrum
-                load_spec_part(sa, 0, part);
-#elif !defined(K8_NO_ANCHOR)
                 load_spec_part(sa, si, part);
-#endif
                 load_spec_part(sb, sj, part);
-#endif
             });
         };
         if (T2 > 0) {

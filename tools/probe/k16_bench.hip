@@ -63,7 +63,7 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(k_gen, dim3((unsigned)((long)W * B * N / 256)), dim3(256), 0, 0, iq, B, N);
     CK(hipDeviceSynchronize());
     CK(hipFuncSetAttribute((const void*)k16::k16_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsFwdBytes));
-    CK(hipFuncSetAttribute((const void*)k16::k16_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsPairBytes));
+    CK(hipFuncSetAttribute((const void*)k16::k16_pairs<>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsPairBytes));
     const float out_scale = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 15);
     hipEvent_t e0, e1, f0, f1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1)); CK(hipEventCreate(&f0)); CK(hipEventCreate(&f1));
@@ -78,7 +78,7 @@ int main(int argc, char** argv) {
             if (time_fwd) { CK(hipEventRecord(f1)); CK(hipEventSynchronize(f1)); float ms; CK(hipEventElapsedTime(&ms, f0, f1)); fwd_ms += ms; ++fwd_n; }
             long per_xcd = (long)((wc + 7) / 8) * P;
             const int s = per_xcd < S ? (int)per_xcd : S;
-            hipLaunchKernelGGL(k16::k16_pairs, dim3(8 * s), dim3(kThreads), k16::kLdsPairBytes, 0, spec, tw1, gq, tw2, tws, B, prs, P,
+            hipLaunchKernelGGL(k16::k16_pairs<>, dim3(8 * s), dim3(kThreads), k16::kLdsPairBytes, 0, spec, tw1, gq, tw2, tws, B, prs, P,
                                (long)w0 * P, wc, 0, out_scale, li, lf, pk);
         }
     };
@@ -105,7 +105,7 @@ int main(int argc, char** argv) {
             long per_xcd = (long)((wc + 7) / 8) * P;
             const int sp = last ? S : Sp;
             const int s = per_xcd < sp ? (int)per_xcd : sp;
-            hipLaunchKernelGGL(k16::k16_pairs, dim3(8 * s), dim3(kThreads), k16::kLdsPairBytes, sP, buf, tw1, gq, tw2, tws, B, prs, P,
+            hipLaunchKernelGGL(k16::k16_pairs<>, dim3(8 * s), dim3(kThreads), k16::kLdsPairBytes, sP, buf, tw1, gq, tw2, tws, B, prs, P,
                                (long)w0 * P, wc, 0, out_scale, li, lf, pk);
             CK(hipEventRecord(evP[c], sP));
             if (!last) {

@@ -1,4 +1,4 @@
-// Standalone A/B harness for the fused window kernel (GPU box): compiles kwin.hpp (+ experimental variants) without the
+// Standalone A/B harness for the fused window kernel (GPU box): compiles kwin.hpp (+ the k_win2 probe) without the
 // rest of the library (seconds instead of a minute), runs each variant on the cfg3 shape (4096 windows x 8 buoys x
 // 4096 samples, synthetic: a common random source with integer delays per buoy + noise), checks every integer lag
 // against the generator's delays and compares the three output arrays of every variant bit for bit with variant 0.
@@ -67,23 +67,6 @@ static void launch_stag0(const Bufs& b, hipStream_t s) {
     hipLaunchKernelGGL(k_win<false>, dim3(256), dim3(kThreads), kLdsWinBytes, s, (const void*)b.iq, b.spec, b.tw1, b.tw2, b.B, 0L,
                        b.out_scale, b.li, b.lf, b.pk, b.W, 0, 0);
 }
-#ifdef RMX_ABLATE
-#define KWB_ABL(NAME, DBG)                                                                                              \
-    static void NAME(const Bufs& b, hipStream_t s) {                                                                    \
-        hipLaunchKernelGGL(k_win<false>, dim3(256), dim3(kThreads), kLdsWinBytes, s, (const void*)b.iq, b.spec, b.tw1, b.tw2, \
-                           b.B, 0L, b.out_scale, b.li, b.lf, b.pk, b.W, DBG, 1);                                       \
-    }
-KWB_ABL(launch_d128, 128)
-KWB_ABL(launch_d64, 64)
-KWB_ABL(launch_d192, 192)
-KWB_ABL(launch_d2, 2)
-KWB_ABL(launch_d4, 4)
-KWB_ABL(launch_d8, 8)
-KWB_ABL(launch_d12, 12)
-KWB_ABL(launch_d206, 206)
-KWB_ABL(launch_d256, 256)
-KWB_ABL(launch_d512, 512)
-#endif
 #ifdef KWB_HAVE_KWIN2
 #define KWB_V2(NAME, ...)                                                                                               \
     static void NAME(const Bufs& b, hipStream_t s) {                                                                    \
@@ -142,18 +125,6 @@ int main(int argc, char** argv) {
 #ifdef KWB_HAVE_KWIN2
         KWB_KWIN2_TABLE
 #endif
-#ifdef RMX_ABLATE
-        {"k_win dbg 128: no spectrum requests", launch_d128, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 64: no sample requests", launch_d64, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 192: neither", launch_d192, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 2: no peak search behind |r|^2", launch_d2, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 4: no wave-local exchange", launch_d4, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 8: no barrier exchange traffic", launch_d8, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 12: no LDS exchange traffic", launch_d12, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 206: none of the above", launch_d206, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 256: no resolve_batch", launch_d256, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win dbg 512: no halo stores", launch_d512, (const void*)k_win<false>, kLdsWinBytes},
-#endif
     };
     for (auto& v : vars) CK(hipFuncSetAttribute(v.kfn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds));
 
@@ -192,59 +163,7 @@ int main(int argc, char** argv) {
                     diff_lf += memcmp(&lf[k], &lf0[k], 4) != 0;
                     diff_pk += memcmp(&pk[k], &pk0[k], 4) != 0;
                 }
-#ifdef RMX_KWIN_STAMPS
-            if (true) {
-                std::vector<long long> st(256 * 64 * 4);
-                CK(hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(rmx_stamps), st.size() * 8));
-                double p1 = 0, p2 = 0, tot = 0; int n = 0;
-                for (int wg = 0; wg < 256; ++wg)
-                    for (int k = 0; k + 1 < W / 256 && k + 1 < 64; ++k) {
-                        const long long* a = &st[(wg * 64 + k) * 4];
-                        p1 += (double)(a[1] - a[0]); p2 += (double)(a[2] - a[1]); tot += (double)(a[4] - a[0]); ++n;
-                    }
-                std::vector<int> vm(256 * 64 * 8);
-                CK(hipMemcpyFromSymbol(vm.data(), HIP_SYMBOL(rmx_stamps_vm), vm.size() * 4));
-                double wv[8] = {0};
-                for (int wg = 0; wg < 256; ++wg) for (int k = 0; k + 1 < W / 256 && k + 1 < 64; ++k) for (int w8 = 0; w8 < 8; ++w8) wv[w8] += vm[(wg * 64 + k) * 8 + w8];
-                printf("    vmcnt wait at the head of h1, ticks per window, waves 0..7:");
-                for (int w8 = 0; w8 < 8; ++w8) printf(" %.0f", wv[w8] / n);
-                printf("\n");
-                std::vector<int> br(256 * 64 * 8 * 2);
-                CK(hipMemcpyFromSymbol(br.data(), HIP_SYMBOL(rmx_stamps_bar), br.size() * 4));
-                double dr[8] = {0}, bw[8] = {0};
-                for (int wg = 0; wg < 256; ++wg) for (int k = 0; k + 1 < W / 256 && k + 1 < 64; ++k) for (int w8 = 0; w8 < 8; ++w8) {
-                    dr[w8] += br[((wg * 64 + k) * 8 + w8) * 2]; bw[w8] += br[((wg * 64 + k) * 8 + w8) * 2 + 1]; }
-                printf("    LDS drain before the barriers, ticks per window, waves 0..7:");
-                for (int w8 = 0; w8 < 8; ++w8) printf(" %.0f", dr[w8] / n);
-                printf("\n    waiting at the barriers, ticks per window, waves 0..7:        ");
-                for (int w8 = 0; w8 < 8; ++w8) printf(" %.0f", bw[w8] / n);
-                printf("\n");
-                std::vector<int> pc(256 * 64 * 8 * 2);
-                CK(hipMemcpyFromSymbol(pc.data(), HIP_SYMBOL(rmx_stamps_pc), pc.size() * 4));
-                double c1[8] = {0}, c2[8] = {0};
-                for (int wg = 0; wg < 256; ++wg) for (int k = 0; k + 1 < W / 256 && k + 1 < 64; ++k) for (int w8 = 0; w8 < 8; ++w8) {
-                    c1[w8] += pc[((wg * 64 + k) * 8 + w8) * 2]; c2[w8] += pc[((wg * 64 + k) * 8 + w8) * 2 + 1]; }
-                printf("    anchor loop, first piece of the interval, ticks per window, waves 0..7: ");
-                for (int w8 = 0; w8 < 8; ++w8) printf(" %.0f", c1[w8] / n);
-                printf("\n    anchor loop, second piece, ticks per window, waves 0..7:                ");
-                for (int w8 = 0; w8 < 8; ++w8) printf(" %.0f", c2[w8] / n);
-                printf("\n");
-                std::vector<int> l1(256 * 64 * 8 * 8);
-                CK(hipMemcpyFromSymbol(l1.data(), HIP_SYMBOL(rmx_stamps_p1), l1.size() * 4));
-                static const char* lapname[8] = {"forward role A (+ load wait, cvt)", "forward barrier", "forward roles B + C", "spectrum store",
-                                                 "h1 of (0, e)", "pair barrier", "h2 of (0, e)", "vmcnt wait at the head of forward"};
-                for (int k7 = 0; k7 < 8; ++k7) {
-                    double a8[8] = {0};
-                    for (int wg = 0; wg < 256; ++wg) for (int k = 0; k + 1 < W / 256 && k + 1 < 64; ++k) for (int w8 = 0; w8 < 8; ++w8)
-                        a8[w8] += l1[((wg * 64 + k) * 8 + w8) * 8 + k7];
-                    printf("    phase 1, %-34s ticks per window, waves 0..7:", lapname[k7]);
-                    for (int w8 = 0; w8 < 8; ++w8) printf(" %.0f", a8[w8] / n);
-                    printf("\n");
-                }
-                printf("    stamps (s_memtime ticks, mean over %d windows): phase 1 %.0f  phase 2 %.0f  whole window %.0f\n", n, p1 / n, p2 / n, tot / n);
-            }
-#endif
-            // FNV-1a over the three output arrays: binaries built with different -D switches are compared through it
+            // FNV-1a over the three output arrays: two builds of the harness are compared through it
             unsigned long long hsum = 1469598103934665603ULL;
             auto fnv = [&](const void* ptr, size_t nb) {
                 const unsigned char* c = (const unsigned char*)ptr;

@@ -5,7 +5,7 @@ set -o pipefail
 out=$PWD/gpurun_out/${K16_PMC_OUT:-pmc_k16}
 rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
-BIN=${K16_BIN:-$PWD/tools/probe/k16_bench}
+BIN=$PWD/tools/probe/k16_bench
 args=${@:-8 256 1 256 32 1}
 cd /tmp
 i=0

@@ -1,7 +1,7 @@
 // valu_forms.hip -- what does one VALU instruction cost a SIMD of gfx950 at k_win's occupancy (two waves per SIMD)?
 //
-// The fused kernel's pieces run at 6.5-7.5 cycles per VALU instruction and wave (tools/probe/kwin_bench.hip
-// -DRMX_KWIN_STAMPS), i.e. one instruction per ~3.4 cycles and SIMD.  Against the 2 cycles a SIMD-32 needs for a
+// The fused kernel's pieces run at 6.5-7.5 cycles per VALU instruction and wave (in-kernel shader-clock
+// stamps, LABNOTES 6.2), i.e. one instruction per ~3.4 cycles and SIMD.  Against the 2 cycles a SIMD-32 needs for a
 // wave64 instruction that looks like 60 % utilisation; this probe measures what two waves CAN issue, per encoding:
 // one workgroup of 128 / 256 / 512 / 1024 threads per CU (0.5 / 1 / 2 / 4 waves per SIMD), 8 independent
 // accumulators per lane, straight-line blocks of 64 instructions.
