@@ -1,6 +1,6 @@
 // generic_path.hpp -- the same path for every power-of-two window length N (16 .. 4 Mi samples).
 //
-// N = 4096 (BASELINE cfg3/cfg4) has the register/LDS-resident radix-16 kernels of rmx_hip.hip.  All
+// N = 4096 (BASELINE cfg3/cfg4) has the register/LDS-resident radix-16 kernels of kwin.hpp / pair4096.hpp.  All
 // other lengths run here: simpler kernels, same definition, same output contract.
 //   512 <= L = 2N <= 16384 (N = 8192: the reference's iq_stream_client captures), batches that fill the chip:
 //                    a workgroup owns a WINDOW and runs all its B + P transforms, spectra never travel as spectra:

@@ -10,7 +10,7 @@
 // into per-thread registers -- each thread owns the same lags in every window, at most 16 of them, so the order of
 // the additions is the window order whatever the scheduling -- and runs the masking, the argmax, the taps and the
 // parabola once, on the sums:
-//   k_pair_str    (N = 4096)        pair_body_integ, rmx_hip.hip: acc[16] beside mag[16]
+//   k_pair_str    (N = 4096)        pair_body_integ, pair4096.hpp: acc[16] beside mag[16]
 //   g_pair_small  (L <= small_maxl) pair_small_integ, generic_path.hpp: lag m = tid + e nthr in acc[e]
 //   g_cols_inv    (four-step)       cols_inv_integ, generic_path.hpp: a tile is a set of whole columns and the column
 //                                   pass is the last one, so the sum is local to the tile; the summed |r|^2 goes back

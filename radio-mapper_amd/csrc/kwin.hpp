@@ -1,6 +1,6 @@
 // kwin.hpp -- the fused window kernel of the tuned N = 4096 path (k_win), its peak-record resolve routine, the
 // table loaders it shares with k_fwd / the pair kernels, and the host-side builder of its twiddle tables.
-// Split out of rmx_hip.hip so that tools/probe/kwin_bench.hip can compile and time this kernel on its own; rmx_hip.hip
+// A header of its own so that tools/probe/kwin_bench.hip can compile and time this kernel on its own; rmx_hip.hip
 // includes it unchanged.
 #pragma once
 #include <hip/hip_runtime.h>

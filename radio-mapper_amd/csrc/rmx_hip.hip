@@ -1,16 +1,14 @@
-// rmx_hip.hip -- gfx950 kernels and the C ABI (include/rmx.h) of the TDoA cross-correlation engine.
+// rmx_hip.hip -- the host side and the C ABI (include/rmx.h) of the TDoA cross-correlation engine; every kernel it
+// launches lives in a header of this directory.
 //
 // Path (conventions of tdoa_processor.py:20,51,156-157,166-170):
 //   per window w, pair (i<j):  r = IFFT_L( FFT_L(x_j) * conj(FFT_L(x_i)) ), L = 2N (zero padded)
 //                               m = |r|, k = argmax over the 2N-1 'full' lags, parabolic offset.
-// Two kernel families, launched back to back per chunk of windows on one stream:
-//   k_fwd   one workgroup per (window, buoy): forward spectrum -> HBM/L2 scratch, stored in the
-//           *register layout* of the pair kernel (every thread later reads back exactly the 16
-//           bins it wrote: 16-B-per-lane coalesced both ways, no reordering pass);
-//   k_pair  one workgroup per (window, group of pairs): loads the two spectra, multiplies in
-//           registers, inverse transform (3 radix-16 passes, 2 LDS exchanges), |.|^2, workgroup
-//           argmax with numpy tie-breaking, 3-tap parabola, 12 bytes out per pair-window.
-// No MFMA (not a contraction), no library FFT: everything below is hand written for wave64 / LDS.
+// N = 4096 runs the fused kernel k_win (kwin.hpp) or, per chunk of windows on one stream, the two families of
+// pair4096.hpp: k_fwd (forward spectra -> HBM/L2 scratch) and k_pair_* (product, inverse transform, peak search).  The
+// other lengths run generic_path.hpp / win_eo.hpp / kwin8k.hpp / kwin16k.hpp.  host_plan.hpp chooses among them per
+// call; every launch goes through rmx::launch below.
+// No MFMA (not a contraction), no library FFT: every kernel is hand written for wave64 / LDS.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,6 +19,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/rmx.h"
@@ -39,835 +38,44 @@
 #endif
 #include "generic_path.hpp"
 #include "win_eo.hpp"
+#include "pair4096.hpp"                         // N = 4096 per transform: k_fwd, k_pair_res, k_pair_str
 #include "kwin8k.hpp"                           // N = 8192 on k_win's network, one anchor half resident in LDS (k_win8kl)
 #include "kwin16k.hpp"                          // N = 16384 on the same network: four quarter transforms, two kernels (k16_fwd, k16_pairs)
 #ifdef RMX_EXPERIMENTS
 #include "../../tools/experiments/kwin8k.hpp"   // its two predecessors: parity-green, not faster (LABNOTES.md R4.6)
 #endif
+#include "caf_select.hpp"
+#include "solve_path.hpp"
 #include "detect_path.hpp"
 
-namespace rmx {
-
-
-
-
-// ------------------------------------------------------------------------------------------------
-// Forward spectra.  grid = n_items workgroups of 512; item = wl * B + b inside the chunk.
-//   spec layout: [item][j = 0..7][t = 0..511] float4 = bins of slots (2j, 2j+1) of thread t,
-//   scaled by `scale` (a power of two; the pair kernel's product then carries 1/L exactly).
-template <bool U8, class... WT>   // WT: empty, or one XWeight (the weighted instantiation, xspec_weight.hpp)
-__global__ __launch_bounds__(kThreads, 4) void k_fwd(const void* __restrict__ iq_v, float4* __restrict__ spec,
-                                                     const float4* __restrict__ tw1_g,
-                                                     const float2* __restrict__ tw2_g, long first_item,
-                                                     float scale, const float2* __restrict__ rot, int wrap_items,
-                                                     WT... wt_pack) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2* xl = reinterpret_cast<float2*>(smem);
-    float2* tw2_lds = reinterpret_cast<float2*>(smem + kLdsXchg);
-    const int t = threadIdx.x;
-    const int p = t & 1, u = t >> 1;
-    // wrap_items > 0 (rmx_caf_batch, all hypotheses in one launch): workgroup b transforms real item b % wrap_items
-    // de-rotated by hypothesis b / wrap_items; its spectrum still goes to slot b
-    const long item = first_item + (wrap_items > 0 ? (long)(blockIdx.x % (unsigned)wrap_items) : (long)blockIdx.x);
-    if (wrap_items > 0 && rot) rot += (size_t)(blockIdx.x / (unsigned)wrap_items) * kM;
-
-    load_tw2_to_lds(tw2_lds, tw2_g, t);
-    float2 tw1[16];
-    load_tw1(tw1, tw1_g, t);
-
-    float2 v[16];
-    if constexpr (U8) {
-        const uchar2* x = reinterpret_cast<const uchar2*>(iq_v) + item * kM;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const uchar2 b = x[q * 256 + u];
-            v[q] = make_float2((float)b.x - 127.5f, (float)b.y - 127.5f);
-        }
-    } else {
-        const float2* x = reinterpret_cast<const float2*>(iq_v) + item * kM;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = x[q * 256 + u];
-    }
-    if (rot) {   // rmx_caf_batch: the window de-rotated by this Doppler hypothesis (rounded as numpy rounds it)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = gen::rot_mul(v[q], rot[q * 256 + u]);
-    }
-    // odd sub-transform: x[n] * W_L^n = x * W32^q * W_L^u ; W_L^u is folded into tw1 (odd lanes)
-    if (p) {
-#pragma unroll
-        for (int q = 1; q < 16; ++q) v[q] = cmul(v[q], w32(q));
-    }
-    dft16(v);        // n2 -> k0
-    mul_tw1(v, tw1); // W_M^(u*k0) [* W_L^u on odd lanes]
-    xchg_a_write(xl, v, t);
-    __syncthreads();
-    xchg_b_read(xl, v, t);
-    dft16(v);                         // n1 -> k1
-    mul_tw2(v, tw2_lds, u & 15);      // W_256^(n0*k1)
-    xchg_bc_write_b(xl, v, t);        // own half-wave region: no barrier
-    wave_lds_fence();
-    xchg_bc_read_c(xl, v, t);
-    dft16(v);                         // n0 -> k2
-    if constexpr (sizeof...(WT) > 0) {   // rmx_xcorr_batch_weighted (wrap_items == 0: item is the global item)
-        const XWeight wt = xweight_of(wt_pack...);
-        const XBand bd = xband_of(wt, item / wt.n_buoys);
-        // role C (fft_r16.hpp): u = 16 k0 + k1, slot s = k2 -> natural bin 2 (k0 + 16 k1 + 256 s) + p
-        const int kb = RMX_XBIN_KFWD(p, u);   // (xspec_weight.hpp: the map k_refine reads the spectra back with)
-#pragma unroll
-        for (int s = 0; s < 16; ++s) v[s] = xweight_apply(wt, bd, kb + kXbinKfwdSlot * s, kL - 1, v[s]);
-    }
-    float4* out = spec + (long)blockIdx.x * (8 * kThreads);
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        out[j * kThreads + t] = make_float4(v[2 * j].x * scale, v[2 * j].y * scale,
-                                            v[2 * j + 1].x * scale, v[2 * j + 1].y * scale);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Pair kernel.  grid = n_windows_in_chunk * n_parts; each workgroup walks items[part_begin..end).
-//   out arrays are indexed [(first_window + wl) * n_pairs + item.out].
-// Streaming variant (k_pair_str, option "resident" = 0): two workgroups per CU (<= 128 VGPRs); TW1,
-// X_i and X_j are re-read every pair.  The resident variant is k_pair_res below.
-template <bool BOUNDED>
-__device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const float4* __restrict__ spec_j,
-                                          const float4* __restrict__ tw1_g,
-                                          const float2* __restrict__ tw2_g, const PairItem* __restrict__ items,
-                                          const int* __restrict__ part_begin, int n_parts, int n_buoys,
-                                          int n_pairs, int xcd_map, long first_window, float out_scale,
-                                          int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                          float* __restrict__ peak, int i_wrap, LagBounds lb) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2* xl = reinterpret_cast<float2*>(smem);
-    float2* tw2_lds = reinterpret_cast<float2*>(smem + kLdsXchg);
-    float* red_max = reinterpret_cast<float*>(smem + kLdsXchg + kLdsTw2);      // [8]
-    int* red_k = reinterpret_cast<int*>(smem + kLdsXchg + kLdsTw2 + 32);       // [1]
-    float* red_tap = reinterpret_cast<float*>(smem + kLdsXchg + kLdsTw2 + 48); // [3]
-
-    const int t = threadIdx.x;
-    const int p = t & 1, u = t >> 1;
-    const int lane = t & 63, wave = t >> 6;
-
-    // blockIdx -> (window, part).  Workgroups of one window share its spectra through the XCD's
-    // L2, so keep them on one XCD (blocks b and b+8 share an XCD) and adjacent in dispatch order.
-    // Placement only changes speed, never results.
-    int wl, part;
-    {
-        const int b = blockIdx.x;
-        if (xcd_map) {
-            const int xcd = b & 7, s = b >> 3;
-            wl = (s / n_parts) * 8 + xcd;
-            part = s % n_parts;
-        } else {
-            wl = b / n_parts;
-            part = b % n_parts;
-        }
-    }
-
-    load_tw2_to_lds(tw2_lds, tw2_g, t);
-    __syncthreads();
-
-    const float sgn = p ? -1.0f : 1.0f;
-    const int it_begin = part_begin[part];
-    const int it_end = part_begin[part + 1];
-    const long wbase = (long)wl * n_buoys;
-    const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wl) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
-    float4 sa[8], sb[8];   // X_i (anchor) and X_j of the pair about to be processed
-    PairItem pi = items[it_begin < it_end ? it_begin : 0];
-    if (it_begin < it_end) {
-        const float4* xi = spec + (wbase_i + pi.i) * (8 * kThreads);
-        const float4* xj = spec_j + (wbase + pi.j) * (8 * kThreads);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            sa[j] = xi[j * kThreads + t];
-            sb[j] = xj[j * kThreads + t];
-        }
-    }
-    for (int it = it_begin; it < it_end; ++it) {
-        const int out_idx = pi.out;
-        float2 v[16];
-        // R = X_j * conj(X_i), written (im, re)-swapped: the forward blocks below then compute the
-        // inverse transform (swap o F o swap = conj F).
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 a = sa[j];
-            const float4 b = sb[j];
-            v[2 * j] = make_float2(b.y * a.x - b.x * a.y, b.x * a.x + b.y * a.y);
-            v[2 * j + 1] = make_float2(b.w * a.z - b.z * a.w, b.z * a.z + b.w * a.w);
-        }
-        dft16(v);                     // k2 -> n0   (role C)
-        mul_tw2(v, tw2_lds, u & 15);  // W_256^(k1*n0)
-        xchg_bc_write_c(xl, v, t);
-        wave_lds_fence();
-        xchg_bc_read_b(xl, v, t);
-        dft16(v);                     // k1 -> n1   (role B)
-        float2 tw1s[16];
-        {
-            // TW1 re-read every pair (64 KiB per workgroup from L2); the pointer is laundered so
-            // that the loads stay here, in flight across the exchange.
-            const float4* twp = tw1_g;
-            asm volatile("" : "+s"(twp));
-            load_tw1(tw1s, twp, t);
-        }
-        xchg_b_write(xl, v, t);       // into this half wave's own region: no barrier needed before
-        __syncthreads();
-        xchg_a_read(xl, v, t);
-        mul_tw1(v, tw1s);             // W_M^(u*k0) [* W_L^u odd]
-        dft16(v);                     // k0 -> n2   (role A): lane holds e[n] (p=0) or o[n]*W_L^u (p=1)
-        if (p) {
-#pragma unroll
-            for (int q = 1; q < 16; ++q) v[q] = cmul(v[q], w32(q));
-        }
-        // last radix-2 stage across the lane pair: even lane r[n] = e + o', odd lane r[n+M] = e - o'
-        float mag[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const float rx = sgn * v[q].x + dpp_xor1(v[q].x);
-            const float ry = sgn * v[q].y + dpp_xor1(v[q].y);
-            mag[q] = rx * rx + ry * ry;
-        }
-        {
-            if (it + 1 < it_end) {
-                pi = items[it + 1];
-                const float4* xi = spec + (wbase_i + pi.i) * (8 * kThreads);
-                const float4* xj = spec_j + (wbase + pi.j) * (8 * kThreads);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    sa[j] = xi[j * kThreads + t];
-                    sb[j] = xj[j * kThreads + t];
-                }
-            }
-        }
-        // 'full' order index of slot q: even lanes lag tau = n >= 0 -> k = n + M - 1;
-        // odd lanes tau = n - M -> k = n - 1 (n = 0, i.e. tau = -M, is not part of 'full').
-        if (p && u == 0) mag[0] = -1.0f;
-        int klo = 0, khi = 2 * kM - 2;
-        if constexpr (BOUNDED) {   // lag window: |r|^2 outside it -> the same sentinel (lag_bounds.hpp)
-            lag_window(lb, first_window + wl, out_idx, kM - 1, klo, khi);
-            const int kb = p ? (u - 1) : (u + kM - 1);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) mag[q] = lag_mask(mag[q], kb + q * 256, klo, khi);
-        }
-        float tmax = mag[0];
-#pragma unroll
-        for (int q = 1; q < 16; ++q) tmax = fmaxf(tmax, mag[q]);
-        float wmax = tmax;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, off, 64));
-        if (lane == 0) red_max[wave] = wmax;
-        if (t == 0) *red_k = 0x7fffffff;
-        __syncthreads();
-        float gmax = red_max[0];
-#pragma unroll
-        for (int w = 1; w < 8; ++w) gmax = fmaxf(gmax, red_max[w]);
-        const int kbase = p ? (u - 1) : (u + kM - 1);
-        if (tmax == gmax) {
-            int kmin = 0x7fffffff;
-#pragma unroll
-            for (int q = 15; q >= 0; --q)
-                if (mag[q] == gmax) kmin = kbase + q * 256;
-            atomicMin(red_k, kmin);
-        }
-        __syncthreads();
-        const int kstar = *red_k;
-        // owners of taps k*-1, k*, k*+1 publish |r| (scipy scaling)
-#pragma unroll
-        for (int d = -1; d <= 1; ++d) {
-            const int kk = kstar + d;
-            if (kk >= 0 && kk <= 2 * kM - 2) {
-                const int par = (kk >= kM - 1) ? 0 : 1;
-                const int n = par ? (kk + 1) : (kk - (kM - 1));
-                if (p == par && u == (n & 255)) {
-                    const int qo = n >> 8;
-                    float val = 0.0f;
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if (q == qo) val = mag[q];
-                    red_tap[d + 1] = sqrtf(val) * out_scale;
-                }
-            }
-        }
-        __syncthreads();
-        if (t == 0) {
-            const double b = (double)red_tap[1];
-            double frac = 0.0;
-            if (kstar > klo && kstar < khi) {   // (klo = 0, khi = 2M - 2 unbounded)
-                const double a = (double)red_tap[0], c = (double)red_tap[2];
-                const double den = a - 2.0 * b + c;
-                if (den != 0.0) frac = 0.5 * (a - c) / den;
-            }
-            const long o = (first_window + wl) * (long)n_pairs + out_idx;
-            lag_int[o] = kstar - (kM - 1);
-            lag_frac[o] = (float)frac;
-            peak[o] = (float)b;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The integrating instantiation of k_pair_str (integrate.hpp).  grid = groups_in_chunk * n_parts; a work item is
-// (group, pair): the workgroup walks the group's K windows -- product, the three radix-16 passes, |.|^2 as in pair_body --
-// and adds each window's mag[16] into acc[16], in window order; masking, argmax, tap publication and parabola then run
-// once, on acc.  The next window's spectra (or the next pair's first window's) are requested where pair_body requests
-// the next pair's.  With the 16 sums on top of pair_body's registers the kernel does not fit 128 VGPRs (pair_body itself
-// spills there), so this instantiation is built for two waves per SIMD, one workgroup per CU, like k_pair_res, and keeps
-// TW1 in registers as that kernel does.  One more barrier per window than pair_body has per pair: the A<->B image of window w is read across
-// waves, and window w + 1 writes the exchange buffer again without the argmax's barriers in between.
-//   out arrays and lag windows are indexed [(first_group + gl) * n_pairs + item.out].
-__device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec, const float4* __restrict__ tw1_g,
-                                                const float2* __restrict__ tw2_g, const PairItem* __restrict__ items,
-                                                const int* __restrict__ part_begin, int n_parts, int n_buoys, int n_pairs,
-                                                int xcd_map, long first_group, float out_scale, int* __restrict__ lag_int,
-                                                float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K) {
-    extern __shared__ __attribute__((aligned(16))) char smem_ig[];   // (pair_body's carve)
-    float2* xl = reinterpret_cast<float2*>(smem_ig);
-    float2* tw2_lds = reinterpret_cast<float2*>(smem_ig + kLdsXchg);
-    float* red_max = reinterpret_cast<float*>(smem_ig + kLdsXchg + kLdsTw2);      // [8]
-    int* red_k = reinterpret_cast<int*>(smem_ig + kLdsXchg + kLdsTw2 + 32);       // [1]
-    float* red_tap = reinterpret_cast<float*>(smem_ig + kLdsXchg + kLdsTw2 + 48); // [3]
-
-    const int t = threadIdx.x;
-    const int p = t & 1, u = t >> 1;
-    const int lane = t & 63, wave = t >> 6;
-    int gl, part;   // (the placement of pair_body, with groups for windows)
-    {
-        const int b = blockIdx.x;
-        if (xcd_map) {
-            const int xcd = b & 7, s = b >> 3;
-            gl = (s / n_parts) * 8 + xcd;
-            part = s % n_parts;
-        } else {
-            gl = b / n_parts;
-            part = b % n_parts;
-        }
-    }
-    if (t < 256) tw2_lds[(t >> 4) * kTw2RowF2 + (t & 15)] = tw2_g[t];   // (load_tw2_to_lds)
-    float2 tw1[16];   // resident over all windows and pairs (this instantiation has the registers: two waves per SIMD)
-    load_tw1(tw1, tw1_g, t);
-    __syncthreads();
-
-    const float sgn = p ? -1.0f : 1.0f;
-    const int kbase = p ? (u - 1) : (u + kM - 1);
-    const int it_begin = part_begin[part];
-    const int it_end = part_begin[part + 1];
-    const long gbase = (long)gl * K * n_buoys;   // item of the group's first window, buoy 0 (chunk-local)
-    float4 sa[8], sb[8];   // X_i and X_j of the window about to be processed
-    PairItem pi = items[it_begin < it_end ? it_begin : 0];
-    auto request = [&](const PairItem& pr, int kw) {
-        const float4* xi = spec + (gbase + (long)kw * n_buoys + pr.i) * (8 * kThreads);
-        const float4* xj = spec + (gbase + (long)kw * n_buoys + pr.j) * (8 * kThreads);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            sa[j] = xi[j * kThreads + t];
-            sb[j] = xj[j * kThreads + t];
-        }
-    };
-    if (it_begin < it_end) request(pi, 0);
-    for (int it = it_begin; it < it_end; ++it) {
-        const int out_idx = pi.out;
-        float acc[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
-        for (int kw = 0; kw < K; ++kw) {
-            float2 v[16];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {   // R = X_j * conj(X_i), (im, re)-swapped (pair_body)
-                const float4 a = sa[j];
-                const float4 b = sb[j];
-                v[2 * j] = make_float2(b.y * a.x - b.x * a.y, b.x * a.x + b.y * a.y);
-                v[2 * j + 1] = make_float2(b.w * a.z - b.z * a.w, b.z * a.z + b.w * a.w);
-            }
-            dft16(v);                     // k2 -> n0   (role C)
-            mul_tw2(v, tw2_lds, u & 15);  // W_256^(k1*n0)
-            xchg_bc_write_c(xl, v, t);
-            wave_lds_fence();
-            xchg_bc_read_b(xl, v, t);
-            dft16(v);                     // k1 -> n1   (role B)
-            xchg_b_write(xl, v, t);
-            __syncthreads();
-            xchg_a_read(xl, v, t);
-            mul_tw1(v, tw1);              // W_M^(u*k0) [* W_L^u odd]
-            dft16(v);                     // k0 -> n2   (role A)
-            if (p) {
-#pragma unroll
-                for (int q = 1; q < 16; ++q) v[q] = cmul(v[q], w32(q));
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {   // last radix-2 stage across the lane pair, |.|^2, the running sum
-                const float rx = sgn * v[q].x + dpp_xor1(v[q].x);
-                const float ry = sgn * v[q].y + dpp_xor1(v[q].y);
-                acc[q] += rx * rx + ry * ry;
-            }
-            if (kw + 1 < K) {
-                request(pi, kw + 1);
-            } else if (it + 1 < it_end) {
-                pi = items[it + 1];
-                request(pi, 0);
-            }
-            __syncthreads();   // every wave has read the A<->B image: the next window may write the exchange buffer
-        }
-        if (p && u == 0) acc[0] = -1.0f;   // lag -M is not part of 'full'
-        int klo, khi;
-        lag_window(lb, first_group + gl, out_idx, kM - 1, klo, khi);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[q] = lag_mask(acc[q], kbase + q * 256, klo, khi);
-        float tmax = acc[0];
-#pragma unroll
-        for (int q = 1; q < 16; ++q) tmax = fmaxf(tmax, acc[q]);
-        float wmax = tmax;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, off, 64));
-        if (lane == 0) red_max[wave] = wmax;
-        if (t == 0) *red_k = 0x7fffffff;
-        __syncthreads();
-        float gmax = red_max[0];
-#pragma unroll
-        for (int w = 1; w < 8; ++w) gmax = fmaxf(gmax, red_max[w]);
-        if (tmax == gmax) {
-            int kmin = 0x7fffffff;
-#pragma unroll
-            for (int q = 15; q >= 0; --q)
-                if (acc[q] == gmax) kmin = kbase + q * 256;
-            atomicMin(red_k, kmin);
-        }
-        __syncthreads();
-        const int kstar = *red_k;
-#pragma unroll
-        for (int d = -1; d <= 1; ++d) {   // owners of taps k*-1, k*, k*+1 publish sqrt(sum) (scipy scaling)
-            const int kk = kstar + d;
-            if (kk >= 0 && kk <= 2 * kM - 2) {
-                const int par = (kk >= kM - 1) ? 0 : 1;
-                const int n = par ? (kk + 1) : (kk - (kM - 1));
-                if (p == par && u == (n & 255)) {
-                    const int qo = n >> 8;
-                    float val = 0.0f;
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if (q == qo) val = acc[q];
-                    red_tap[d + 1] = sqrtf(val) * out_scale;
-                }
-            }
-        }
-        __syncthreads();
-        if (t == 0) {
-            const double b = (double)red_tap[1];
-            double frac = 0.0;
-            if (kstar > klo && kstar < khi) {
-                const double a = (double)red_tap[0], c = (double)red_tap[2];
-                const double den = a - 2.0 * b + c;
-                if (den != 0.0) frac = 0.5 * (a - c) / den;
-            }
-            const long o = (first_group + gl) * (long)n_pairs + out_idx;
-            lag_int[o] = kstar - (kM - 1);
-            lag_frac[o] = (float)frac;
-            peak[o] = (float)b;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Resident pair kernel (one workgroup per CU, <= 256 VGPRs).  One workgroup barrier per pair:
-//   pair n:  product -> [request X_j of pair n+1] -> DFT16 -> TW2 -> wave-local exchange -> DFT16 ->
-//            write A<->B image -> BARRIER -> [resolve pair n-1] -> read image -> TW1 -> DFT16 -> W32 ->
-//            lane-pair butterfly, |.|^2 -> publish: all |.|^2 to an LDS tap buffer, wave winner
-//            (max, lowest 'full' index) to an LDS slot.
-// The cross-wave part of the argmax and the 3-tap parabola of pair n are "resolved" by one lane
-// after the barrier of pair n+1 (both LDS buffers are double buffered by pair parity), so the
-// reduction's latency chain hides behind the next pair's arithmetic.
-constexpr int kLdsMag = kL * 4;                         // one |.|^2 image: [q4][t] float4
-constexpr int kLdsResOff = kLdsXchg + kLdsTw2;
-constexpr int kLdsResBytes = kLdsXchg + kLdsTw2 + 2 * kLdsMag + 256;
-
-template <bool BOUNDED>
-__device__ __forceinline__ void resolve_pair(const float* magbuf, const float2* red, long out_pos, float out_scale,
-                                             int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                             float* __restrict__ peak, LagBounds lb, long w, int q_out) {
-    // red[w] = (wave max of |r|^2 as float bits, lowest 'full' index attaining it), w = 0..7
-    float gmax = -2.0f;
-    int kstar = 0x7fffffff;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-        const float2 e = red[w];
-        const float m = e.x;
-        const float ey = e.y;
-        const int k = __builtin_bit_cast(int, ey);
-        if (m > gmax || (m == gmax && k < kstar)) { gmax = m; kstar = k; }
-    }
-    auto tap = [&](int kk) -> float {
-        const int par = (kk >= kM - 1) ? 0 : 1;
-        const int n = par ? (kk + 1) : (kk - (kM - 1));
-        const int tt = 2 * (n & 255) + par, q = n >> 8;
-        return sqrtf(magbuf[((q >> 2) * kThreads + tt) * 4 + (q & 3)]) * out_scale;
-    };
-    const float b = sqrtf(gmax) * out_scale;
-    float frac = 0.0f;
-    int klo = 0, khi = 2 * kM - 2;
-    if constexpr (BOUNDED) lag_window(lb, w, q_out, kM - 1, klo, khi);
-    if (kstar > klo && kstar < khi) {
-        const float a = tap(kstar - 1), c = tap(kstar + 1);
-        const double den = (double)a - 2.0 * (double)b + (double)c;
-        if (den != 0.0) frac = (float)(0.5 * ((double)a - (double)c) / den);
-    }
-    lag_int[out_pos] = kstar - (kM - 1);
-    lag_frac[out_pos] = frac;
-    peak[out_pos] = b;
-}
-
-template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation)
-__global__ __launch_bounds__(kThreads, 2) void k_pair_res(
-    const float4* __restrict__ spec, const float4* __restrict__ spec_j, const float4* __restrict__ tw1_g, const float2* __restrict__ tw2_g,
-    const PairItem* __restrict__ items, const int* __restrict__ part_begin, int n_parts, int n_buoys, int n_pairs,
-    int xcd_map, long first_window, float out_scale, int* __restrict__ lag_int, float* __restrict__ lag_frac,
-    float* __restrict__ peak, int /* was dbg_rt */, int i_wrap, LB... lb_pack) {
-    constexpr bool BOUNDED = sizeof...(LB) > 0;
-    const LagBounds lb = lag_bounds_of(lb_pack...);
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2* xl = reinterpret_cast<float2*>(smem);
-    float2* tw2_lds = reinterpret_cast<float2*>(smem + kLdsXchg);
-    float4* magbuf = reinterpret_cast<float4*>(smem + kLdsResOff);                 // [2][4][512] float4
-    float2* red = reinterpret_cast<float2*>(smem + kLdsResOff + 2 * kLdsMag);      // [2][8]
-
-    const int t = threadIdx.x;
-    const int p = t & 1, u = t >> 1;
-    const int lane = t & 63, wave = t >> 6;
-    int wl, part;
-    {
-        const int b = blockIdx.x;
-        if (xcd_map) {
-            const int xcd = b & 7, s = b >> 3;
-            wl = (s / n_parts) * 8 + xcd;
-            part = s % n_parts;
-        } else {
-            wl = b / n_parts;
-            part = b % n_parts;
-        }
-    }
-    load_tw2_to_lds(tw2_lds, tw2_g, t);
-    float2 tw1[16];
-    load_tw1(tw1, tw1_g, t);
-    __syncthreads();
-
-    const float sgn = p ? -1.0f : 1.0f;
-    const int kbase = p ? (u - 1) : (u + kM - 1);
-    const int it_begin = part_begin[part];
-    const int it_end = part_begin[part + 1];
-    if (it_begin >= it_end) return;
-    const long wbase = (long)wl * n_buoys;
-    const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wl) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
-    const long obase = (first_window + wl) * (long)n_pairs;
-    float4 sa[8], sb[8];
-    PairItem pi = items[it_begin];
-    int cur_i = pi.i;
-    {
-        const float4* xi = spec + (wbase_i + pi.i) * (8 * kThreads);
-        const float4* xj = spec_j + (wbase + pi.j) * (8 * kThreads);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            sa[j] = xi[j * kThreads + t];
-            sb[j] = xj[j * kThreads + t];
-        }
-    }
-    int prev_out = -1;
-    for (int it = it_begin; it < it_end; ++it) {
-        const int out_idx = pi.out;
-        const int buf = (it - it_begin) & 1;
-        float2 v[16];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 a = sa[j];
-            const float4 b = sb[j];
-            v[2 * j] = make_float2(b.y * a.x - b.x * a.y, b.x * a.x + b.y * a.y);
-            v[2 * j + 1] = make_float2(b.w * a.z - b.z * a.w, b.z * a.z + b.w * a.w);
-        }
-        if (it + 1 < it_end) {   // request the next pair's spectra: a whole pair of compute hides it
-            pi = items[it + 1];
-            const float4* xj = spec_j + (wbase + pi.j) * (8 * kThreads);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sb[j] = xj[j * kThreads + t];
-            if (pi.i != cur_i) {
-                cur_i = pi.i;
-                const float4* xi = spec + (wbase_i + pi.i) * (8 * kThreads);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sa[j] = xi[j * kThreads + t];
-            }
-        }
-        dft16(v);                     // k2 -> n0   (role C)
-        mul_tw2(v, tw2_lds, u & 15);  // W_256^(k1*n0)
-        xchg_bc_write_c(xl, v, t);
-        wave_lds_fence();
-        xchg_bc_read_b(xl, v, t);
-        dft16(v);                     // k1 -> n1   (role B)
-        xchg_b_write(xl, v, t);       // into this half wave's own region
-        __syncthreads();              // the pair's only barrier; also publishes pair it-1's winners
-        if (prev_out >= 0 && t == ((it - it_begin) & 7) * 64)
-            resolve_pair<BOUNDED>(reinterpret_cast<const float*>(magbuf + (buf ^ 1) * (4 * kThreads)), red + (buf ^ 1) * 8,
-                                  obase + prev_out, out_scale, lag_int, lag_frac, peak, lb, first_window + wl, prev_out);
-        xchg_a_read(xl, v, t);
-        mul_tw1(v, tw1);              // W_M^(u*k0) [* W_L^u on odd lanes]
-        dft16(v);                     // k0 -> n2   (role A): e[n] (even lanes) / o[n]*W_L^u (odd lanes)
-        if (p) {
-#pragma unroll
-            for (int q = 1; q < 16; ++q) v[q] = cmul(v[q], w32(q));
-        }
-        float mag[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const float rx = sgn * v[q].x + dpp_xor1(v[q].x);
-            const float ry = sgn * v[q].y + dpp_xor1(v[q].y);
-            mag[q] = rx * rx + ry * ry;
-        }
-        if (p && u == 0) mag[0] = -1.0f;   // lag -M is not part of the 'full' output
-        if constexpr (BOUNDED) {           // lag window: |r|^2 outside it -> the same sentinel (lag_bounds.hpp)
-            int klo, khi;
-            lag_window(lb, first_window + wl, out_idx, kM - 1, klo, khi);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) mag[q] = lag_mask(mag[q], kbase + q * 256, klo, khi);
-        }
-        float4* mb = magbuf + buf * (4 * kThreads) + t;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4)
-            mb[q4 * kThreads] = make_float4(mag[4 * q4], mag[4 * q4 + 1], mag[4 * q4 + 2], mag[4 * q4 + 3]);
-        float tmax = mag[0];
-#pragma unroll
-        for (int q = 1; q < 16; ++q) tmax = fmaxf(tmax, mag[q]);
-        int kq = 0;
-#pragma unroll
-        for (int q = 15; q >= 0; --q)
-            if (mag[q] == tmax) kq = kbase + q * 256;   // lowest 'full' index of this lane's maximum
-        const float wmax = wave_max_f32(tmax);
-        const int kw = wave_min_i32(tmax == wmax ? kq : 0x7fffffff);
-        if (lane == 0) red[buf * 8 + wave] = make_float2(wmax, __builtin_bit_cast(float, kw));
-        prev_out = out_idx;
-    }
-    __syncthreads();
-    if (t == 0) {
-        const int buf = (it_end - 1 - it_begin) & 1;
-        resolve_pair<BOUNDED>(reinterpret_cast<const float*>(magbuf + buf * (4 * kThreads)), red + buf * 8, obase + prev_out,
-                              out_scale, lag_int, lag_frac, peak, lb, first_window + wl, prev_out);
-    }
-}
-
-
-#ifdef RMX_EXPERIMENTS
-// k_win on packed fp32 (winpk.hpp): same protocol, same resolve routine
-template <bool U8>
-__global__ __launch_bounds__(kThreads, 2) void k_winp(const void* __restrict__ iq_v, float4* __restrict__ spec,
-                                                      const float4* __restrict__ tw1_g,
-                                                      const float2* __restrict__ tw2_g, int n_buoys,
-                                                      long first_window, float out_scale, int* __restrict__ lag_int,
-                                                      float* __restrict__ lag_frac, float* __restrict__ peak, int n_win) {
-    pk::winp_body<U8>(iq_v, spec, tw1_g, tw2_g, n_buoys, first_window, out_scale, lag_int, lag_frac, peak, n_win,
-                      [](int lane, const float4* red, const float* halo, const int* oidx, int first, int cnt, long obase,
-                         float osc, int* li, float* lf, float* pk_) __attribute__((always_inline)) {
-                          resolve_batch(lane, red, halo, oidx, first, cnt, obase, osc, li, lf, pk_);
-                      });
-}
-#endif
-
-#define RMX_PAIR_ARGS                                                                                         \
-    const float4 *__restrict__ spec, const float4 *__restrict__ spec_j, const float4 *__restrict__ tw1_g,     \
-        const float2 *__restrict__ tw2_g,                                                                     \
-        const PairItem *__restrict__ items, const int *__restrict__ part_begin, int n_parts, int n_buoys,     \
-        int n_pairs, int xcd_map, long first_window, float out_scale, int *__restrict__ lag_int,              \
-        float *__restrict__ lag_frac, float *__restrict__ peak, int i_wrap
-#define RMX_PAIR_PASS                                                                                         \
-    spec, spec_j, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,      \
-        lag_int, lag_frac, peak, i_wrap
-
-// LB: empty, one LagBounds (the bounded instantiation), or <LagBounds, Integrate> (the integrating one, integrate.hpp:
-// first_window is then the chunk's first GROUP; spec_j and i_wrap are not used)
-template <class... LB>
-__global__ __launch_bounds__(kThreads, kIntegrating<LB...> ? 2 : 4) void k_pair_str(RMX_PAIR_ARGS, LB... lb) {
-    if constexpr (kIntegrating<LB...>) {
-        pair_body_integ(spec, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
-                        lag_int, lag_frac, peak, integ_bounds(lb...), integ_windows(lb...));
-    } else {
-        pair_body<(sizeof...(LB) > 0)>(RMX_PAIR_PASS, lag_bounds_of(lb...));
-    }
-}
-
-
-// ---- CAF helper: running best hypothesis per pair-window -------------------------------------------
-__global__ void k_caf_select(int d, long first, long n, const int* __restrict__ lag_d, const float* __restrict__ frac_d,
-                             const float* __restrict__ peak_d, int* __restrict__ dop, int* __restrict__ lag,
-                             float* __restrict__ frac, float* __restrict__ peak) {
-    const long i = first + (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= first + n) return;
-    if (d == 0 || peak_d[i] > peak[i]) {   // strict: ties keep the lowest d
-        dop[i] = d; lag[i] = lag_d[i]; frac[i] = frac_d[i]; peak[i] = peak_d[i];
-    }
-}
-
-
-// the same over all hypotheses of one launch: arrays [n_dop][n], d-major first maximum (strict >: ties keep the lowest d)
-__global__ void k_caf_select_all(int n_dop, long n, const int* __restrict__ lag_d, const float* __restrict__ frac_d,
-                                 const float* __restrict__ peak_d, int* __restrict__ dop, int* __restrict__ lag,
-                                 float* __restrict__ frac, float* __restrict__ peak) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int bd = 0;
-    float bp = peak_d[i];
-    for (int d = 1; d < n_dop; ++d) {
-        const float pd = peak_d[(long)d * n + i];
-        if (pd > bp) { bp = pd; bd = d; }
-    }
-    dop[i] = bd; lag[i] = lag_d[(long)bd * n + i]; frac[i] = frac_d[(long)bd * n + i]; peak[i] = bp;
-}
-
-
-// ---- batched hyperbolic position solve (rmx_solve_batch) --------------------------------------------
-// One thread per window: 3 unknowns, P residuals, everything in float64 registers; the buoy table and
-// the pair list sit in LDS.  The lag arrays are read transposed-strided (lane = window), which is a
-// few hundred bytes per window and iteration: the kernel is latency-bound by its dependent
-// sqrt/divide chains, not by memory.
-constexpr int kSolveMaxBuoys = 64;
-constexpr int kSolveMaxPairs = kSolveMaxBuoys * (kSolveMaxBuoys - 1) / 2;
-__global__ __launch_bounds__(64) void k_solve(const double* __restrict__ buoy_xyz, int n_buoys,
-                                              const int* __restrict__ pairs, int n_pairs,
-                                              const int* __restrict__ lag_int, const float* __restrict__ lag_frac,
-                                              const float* __restrict__ weight, double metres_per_sample,
-                                              int n_windows, int max_iter, double* __restrict__ pos,
-                                              double* __restrict__ cost, int* __restrict__ iters) {
-#pragma clang fp contract(off)   // same roundings as the numpy restatement wherever the order is the same
-    __shared__ double sb[kSolveMaxBuoys * 3];
-    __shared__ short spair[kSolveMaxPairs * 2];
-    for (int i = threadIdx.x; i < n_buoys * 3; i += blockDim.x) sb[i] = buoy_xyz[i];
-    for (int i = threadIdx.x; i < n_pairs * 2; i += blockDim.x) spair[i] = (short)pairs[i];
-    __syncthreads();
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= n_windows) return;
-    const int* li = lag_int + (long)w * n_pairs;
-    const float* lf = lag_frac + (long)w * n_pairs;
-    const float* wg = weight ? weight + (long)w * n_pairs : nullptr;
-    double px = 0, py = 0, pz = 0;
-    for (int b = 0; b < n_buoys; ++b) { px += sb[3 * b]; py += sb[3 * b + 1]; pz += sb[3 * b + 2]; }
-    px /= n_buoys; py /= n_buoys; pz /= n_buoys;
-    auto f_at = [&](double x, double y, double z) -> double {
-        double f = 0;
-        for (int q = 0; q < n_pairs; ++q) {
-            const double* b1 = sb + 3 * spair[2 * q];
-            const double* b2 = sb + 3 * spair[2 * q + 1];
-            const double n1 = sqrt((x - b1[0]) * (x - b1[0]) + (y - b1[1]) * (y - b1[1]) + (z - b1[2]) * (z - b1[2]));
-            const double n2 = sqrt((x - b2[0]) * (x - b2[0]) + (y - b2[1]) * (y - b2[1]) + (z - b2[2]) * (z - b2[2]));
-            const double d = ((double)li[q] + (double)lf[q]) * metres_per_sample;
-            const double r = n2 - n1 - d;
-            f += (wg ? (double)wg[q] : 1.0) * r * r;
-        }
-        return f;
-    };
-    double lam = 1e-3;
-    double f = f_at(px, py, pz);
-    int it = 0;
-    while (it < max_iter) {
-        ++it;
-        double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0, g0 = 0, g1 = 0, g2 = 0;
-        for (int q = 0; q < n_pairs; ++q) {
-            const double* b1 = sb + 3 * spair[2 * q];
-            const double* b2 = sb + 3 * spair[2 * q + 1];
-            const double v1x = px - b1[0], v1y = py - b1[1], v1z = pz - b1[2];
-            const double v2x = px - b2[0], v2y = py - b2[1], v2z = pz - b2[2];
-            const double n1 = sqrt(v1x * v1x + v1y * v1y + v1z * v1z);
-            const double n2 = sqrt(v2x * v2x + v2y * v2y + v2z * v2z);
-            const double d = ((double)li[q] + (double)lf[q]) * metres_per_sample;
-            const double r = n2 - n1 - d;
-            const double jx = v2x / n2 - v1x / n1, jy = v2y / n2 - v1y / n1, jz = v2z / n2 - v1z / n1;
-            const double ww = wg ? (double)wg[q] : 1.0;
-            a00 += ww * jx * jx; a01 += ww * jx * jy; a02 += ww * jx * jz;
-            a11 += ww * jy * jy; a12 += ww * jy * jz; a22 += ww * jz * jz;
-            g0 += ww * jx * r; g1 += ww * jy * r; g2 += ww * jz * r;
-        }
-        // (A + lam diag A) delta = -g by Cholesky; a failed factorisation counts as a rejected step
-        const double d00 = a00 * (1.0 + lam), d11 = a11 * (1.0 + lam), d22 = a22 * (1.0 + lam);
-        bool ok = d00 > 0.0;
-        const double l00 = sqrt(ok ? d00 : 1.0);
-        const double l10 = a01 / l00, l20 = a02 / l00;
-        const double t11 = d11 - l10 * l10;
-        ok = ok && t11 > 0.0;
-        const double l11 = sqrt(ok ? t11 : 1.0);
-        const double l21 = (a12 - l20 * l10) / l11;
-        const double t22 = d22 - l20 * l20 - l21 * l21;
-        ok = ok && t22 > 0.0;
-        const double l22 = sqrt(ok ? t22 : 1.0);
-        bool accepted = false;
-        double dn = 0.0;
-        if (ok) {
-            const double y0 = -g0 / l00;
-            const double y1 = (-g1 - l10 * y0) / l11;
-            const double y2 = (-g2 - l20 * y0 - l21 * y1) / l22;
-            const double dz = y2 / l22;
-            const double dy = (y1 - l21 * dz) / l11;
-            const double dx = (y0 - l10 * dy - l20 * dz) / l00;
-            const double fn = f_at(px + dx, py + dy, pz + dz);
-            if (fn < f) {
-                px += dx; py += dy; pz += dz;
-                f = fn;
-                accepted = true;
-                dn = sqrt(dx * dx + dy * dy + dz * dz);
-            }
-        }
-        if (accepted) {
-            lam = lam / 3.0 > 1e-12 ? lam / 3.0 : 1e-12;
-            if (dn < 1e-4) break;
-        } else {
-            lam *= 4.0;
-            if (lam > 1e12) break;
-        }
-    }
-    pos[3 * (long)w] = px; pos[3 * (long)w + 1] = py; pos[3 * (long)w + 2] = pz;
-    cost[w] = f;
-    iters[w] = it;
-}
-
-// ================================================================================================
-// host side
-// ================================================================================================
-static thread_local std::string g_create_error;
-
-// What ONE correlation call asks of the launch code beyond the plain call: built by the entry (xcorr_request), handed
-// down by const reference to every function that launches a kernel, never stored.  The default is the plain, unrefined
-// call; rmx_caf_batch passes exactly that.
-struct XcorrCall {
-    LagBounds lb{nullptr, 0, 0, 0};          // lag intervals on the device (rmx_xcorr_batch_bounded), or none
-    XWeight wt{nullptr, 0, 0, 0, 0, 0.0f};   // bands as signed bins on the device + weighting (rmx_xcorr_batch_weighted)
-    int integ = 1;                           // windows per group (rmx_xcorr_batch_integrated): the bounds and the outputs
-                                             // are then per GROUP, the bands stay per window, a chunk holds whole groups
-    int refine = 0;                          // U of rmx_xcorr_batch_refined: k_refine behind every chunk's pair kernels, or 0
-    bool bounded() const { return lb.b != nullptr; }         // the bounded instantiations of the peak-searching kernels
-    bool integrated() const { return integ > 1; }            // the integrating instantiations of the pair kernels
-    float* quality = nullptr;                // rmx_xcorr_batch_quality: [rows][n_pairs][4] on the device (k_quality behind every
-                                             // chunk's pair kernels, in front of k_refine), or none
-    bool refined() const { return refine > 0; }              // k_refine reads both spectra of a pair from HBM
-    bool qualified() const { return quality != nullptr; }    // k_quality does too
-    // only the per-transform routes can serve it
-    bool weighted() const { return wt.band != nullptr || integ > 1 || refine > 0 || quality != nullptr; }
-};
-
-// Where a ctx's per-transform spectra lie once a chunk's forward kernels have run, and the launchers that write and read
-// them (N = 4096: k_fwd / k_pair_*; generic: g_fwd_small / g_pair_small or the four-step passes).  Filled by spec_view().
-struct SpecView {
-    int layout;  const void* base;          // RefLayout (refine.hpp); d_spec / g_spec
-    int logL, row_bits, unit_log2;          // log2 of the transform length; kRefRows: log2 of the rows per spectrum; the stored bins carry 2^unit_log2
-    // rows_fused: four-step, g_rows_fused does both row passes (forward: the column pass only)
-    int (*forward)(rmx_ctx*, const XcorrCall&, const void* d_iq, int w0, int wc, bool u8, const float2* rot, bool rows_fused);
-    int (*pairs)(rmx_ctx*, const XcorrCall&, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, bool use_rot,
-                 bool rows_fused);
-};
-
-// a small host array that kernels read: staged through pinned memory into a ctx-owned device buffer (stage_to_device)
-struct DevStage {
-    int32_t* h = nullptr;  size_t h_elems = 0;
-    int* d = nullptr;      size_t d_elems = 0;
-    hipEvent_t ev = nullptr;   // the last copy out of h: the next call waits for it before it rewrites h
-};
-
-// U8 as a compile-time constant: f(std::true_type) or f(std::false_type)
-template <class F>
-static void with_u8(bool u8, F&& f) {
-    if (u8) f(std::true_type{}); else f(std::false_type{});
-}
-
-}  // namespace rmx
-
 struct rmx_ctx {
+    // a small host array that kernels read: staged through pinned memory into a ctx-owned device buffer (stage_to_device)
+    struct DevStage {
+        int32_t* h = nullptr;  size_t h_elems = 0;
+        int* d = nullptr;      size_t d_elems = 0;
+        hipEvent_t ev = nullptr;   // the last copy out of h: the next call waits for it before it rewrites h
+    };
+    // The generic path's kernels as rmx::pick_generic_kernels chose them for this ctx: one typed pointer per signature
+    // (the template arguments below only name the signature), null = this ctx does not have that kernel.
+    struct GenericKernels {
+        decltype(&rmx::gen::g_cols_inv<4>) cols_inv = nullptr;
+        decltype(&rmx::gen::g_cols_inv<4, 0, rmx::LagBounds>) cols_inv_lb = nullptr;                    // its bounded instantiation (rmx_xcorr_batch_bounded)
+        decltype(&rmx::gen::g_cols_inv<4, 0, rmx::LagBounds, rmx::Integrate>) cols_inv_int = nullptr;   // its integrating one (integrate.hpp)
+        decltype(&rmx::gen::g_cols_fwd<false, 4>) cols_fwd[2] = {nullptr, nullptr};                     // [u8]
+        decltype(&rmx::gen::g_rows<true, false>) rows_fwd = nullptr;   // g_rows compiled for this row length (or the run-time one)
+        decltype(&rmx::gen::g_rows<true, false, false, 0, rmx::XWeight>) rows_fwd_wt = nullptr;         // its weighted instantiation
+        decltype(&rmx::gen::g_rows<false, true, true>) rows_inv = nullptr;
+        decltype(&rmx::gen::g_rows_anchor<9>) rows_anchor = nullptr;   // inverse rows with a resident anchor (default pair list)
+        decltype(&rmx::gen::g_rows_fused<2, 9>) fused = nullptr;       // four-step: both row passes in one kernel (n_buoys <= 4)
+        decltype(&rmx::gen::g_rows_fused<2, 9>) fused_def = nullptr;   // the same for the default plan (pair loop unrolled)
+        decltype(&rmx::gen::g_win_fused<2, 9, false, false>) wf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [default plan][u8]
+        size_t wf_lds[2] = {0, 0};                                                                      // [default plan]
+        decltype(&rmx::gen::g_win_scr<9, false>) ws[2] = {nullptr, nullptr};    // [u8]: g_win_scr<log2 L> or g_win_scr14
+        decltype(&rmx::gen::g_win_eo15<false>) ws15[2] = {nullptr, nullptr};    // [u8]: N = 16384 (one more table)
+        size_t ws_lds = 0;                                                      // of ws or ws15, whichever is there
+        int ws_thr = 0, ws_upw = 0;                                             // its threads and windows per workgroup
+    };
+
     rmx::host::Knobs knobs;   // kernel-selection options as they were at rmx_create (host_plan.hpp)
     int device = 0;
     int n_cus = 256;   // compute units of the device (persistent-grid size of the fused kernel)
@@ -903,18 +111,13 @@ struct rmx_ctx {
     bool generic = false;
     int g_logL = 0, g_logL1 = 0, g_logL2 = 0, g_lo_bits = 0, g_chunk = 0;
     size_t g_dyn_bytes = 0, g_pair_bytes = 0;   // chunk-sized buffers of generic_ensure (all of them / the pair-dependent ones)
+    GenericKernels gk;
     bool g_fused = false;      // four-step: both row passes in g_rows_fused (n_buoys <= 4, plain batches)
     bool g_fused_always = false;
-    const void* g_fused_fn = nullptr;
-    const void* g_fused_def_fn = nullptr;  // the same for the default plan (pair loop unrolled)
     bool g_wfused = false;     // LDS-resident lengths, n_buoys <= 4: whole windows in g_win_fused (no spectra in HBM)
-    const void* g_wf_fn[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [default plan][u8]
-    size_t g_wf_lds[2] = {0, 0};           // [default plan]
     bool g_wscr = false;       // 512 <= L <= 16384, any buoy count: whole windows in g_win_scr (spectra in a cache-resident scratch)
     bool g_wscr_always = false;
-    const void* g_ws_fn[2] = {nullptr, nullptr};   // [u8]
-    size_t g_ws_lds = 0;
-    int g_ws_thr = 0, g_ws_upw = 0, g_ws_grid = 0;
+    int g_ws_grid = 0;
     float4* g_ws_scratch = nullptr;
     float2* g_tw_win = nullptr;            // W_L half table of that kernel
     float2* g_tw_l = nullptr;              // g_win_eo15 (N = 16384): W_32768^i, i < 1024
@@ -925,13 +128,7 @@ struct rmx_ctx {
     int g_k16 = 0;                         // N = 16384: k16_fwd + k16_pairs (kwin16k.hpp); 1 = from the measured batch size on, 2 = always
     float4* g_k16_tw1 = nullptr;           // slot factors of TW1
     float2 *g_k16_gq = nullptr, *g_k16_tw2 = nullptr, *g_k16_tws = nullptr;   // per-quarter thread factors, k_win's TW2, W_128 rows
-    const void* g_cols_inv_fn = nullptr;
-    const void* g_cols_inv_lb_fn = nullptr;   // its bounded instantiation (rmx_xcorr_batch_bounded)
-    const void* g_cols_fwd_fn[2] = {nullptr, nullptr};   // [u8]
-    const void* g_rows_inv_fn = nullptr;
-    const void* g_rows_anchor_fn = nullptr;   // inverse rows with a resident anchor (default pair list), or null
-    int g_rows_anchor_min_b = 6;              // ... from this many buoys on (RMX_ROWS_ANCHOR=n sets it, 0 = never)
-    const void* g_rows_fwd_fn = nullptr;   // g_rows<inverse> compiled for this row length (or the run-time one)
+    int g_rows_anchor_min_b = 6;           // gk.rows_anchor from this many buoys on (option rows_anchor = n sets it, 0 = never)
     float2 *g_tw = nullptr, *g_tw1 = nullptr, *g_tw2 = nullptr, *g_thi = nullptr, *g_tlo = nullptr;
     float2 *g_spec = nullptr, *g_spec_r = nullptr, *g_prod = nullptr;   // spectra, de-rotated spectra (CAF), products
     rmx::gen::GTile* g_rec = nullptr;   // per column tile: partial argmax + taps
@@ -957,9 +154,7 @@ struct rmx_ctx {
     std::vector<double> caf_grid;
     // the caller's lag windows (rmx_xcorr_batch_bounded) and its bands as signed bins (rmx_xcorr_batch_weighted): the
     // device copies that a call's XcorrCall points into
-    rmx::DevStage lb_stage, band_stage;
-    const void* g_rows_fwd_wt_fn = nullptr;   // the weighted instantiation of g_rows_fwd_fn
-    const void* g_cols_inv_int_fn = nullptr;   // the integrating instantiation of g_cols_inv_fn (integrate.hpp)
+    DevStage lb_stage, band_stage;
     rmx::RefPair* rf_pairs = nullptr;          // k_refine's and k_quality's pair list (refine.hpp): the plan's pairs in output order
     std::vector<int32_t> rf_pairs_plan;
     // cached pair plan
@@ -976,6 +171,59 @@ struct rmx_ctx {
 };
 
 namespace rmx {
+
+using DevStage = rmx_ctx::DevStage;
+using GenericKernels = rmx_ctx::GenericKernels;
+
+static thread_local std::string g_create_error;
+
+// What ONE correlation call asks of the launch code beyond the plain call: built by the entry (xcorr_request), handed
+// down by const reference to every function that launches a kernel, never stored.  The default is the plain, unrefined
+// call; rmx_caf_batch passes exactly that.
+struct XcorrCall {
+    LagBounds lb{nullptr, 0, 0, 0};          // lag intervals on the device (rmx_xcorr_batch_bounded), or none
+    XWeight wt{nullptr, 0, 0, 0, 0, 0.0f};   // bands as signed bins on the device + weighting (rmx_xcorr_batch_weighted)
+    int integ = 1;                           // windows per group (rmx_xcorr_batch_integrated): the bounds and the outputs
+                                             // are then per GROUP, the bands stay per window, a chunk holds whole groups
+    int refine = 0;                          // U of rmx_xcorr_batch_refined: k_refine behind every chunk's pair kernels, or 0
+    bool bounded() const { return lb.b != nullptr; }         // the bounded instantiations of the peak-searching kernels
+    bool integrated() const { return integ > 1; }            // the integrating instantiations of the pair kernels
+    float* quality = nullptr;                // rmx_xcorr_batch_quality: [rows][n_pairs][4] on the device (k_quality behind every
+                                             // chunk's pair kernels, in front of k_refine), or none
+    bool refined() const { return refine > 0; }              // k_refine reads both spectra of a pair from HBM
+    bool qualified() const { return quality != nullptr; }    // k_quality does too
+    // only the per-transform routes can serve it
+    bool weighted() const { return wt.band != nullptr || integ > 1 || refine > 0 || quality != nullptr; }
+};
+
+// Where a ctx's per-transform spectra lie once a chunk's forward kernels have run, and the launchers that write and read
+// them (N = 4096: k_fwd / k_pair_*; generic: g_fwd_small / g_pair_small or the four-step passes).  Filled by spec_view().
+struct SpecView {
+    int layout;  const void* base;          // RefLayout (refine.hpp); d_spec / g_spec
+    int logL, row_bits, unit_log2;          // log2 of the transform length; kRefRows: log2 of the rows per spectrum; the stored bins carry 2^unit_log2
+    // rows_fused: four-step, g_rows_fused does both row passes (forward: the column pass only)
+    int (*forward)(rmx_ctx*, const XcorrCall&, const void* d_iq, int w0, int wc, bool u8, const float2* rot, bool rows_fused);
+    int (*pairs)(rmx_ctx*, const XcorrCall&, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, bool use_rot,
+                 bool rows_fused);
+};
+
+// U8 as a compile-time constant: f(std::true_type) or f(std::false_type); returns what f returns
+template <class F>
+static auto with_u8(bool u8, F&& f) {
+    if (u8) return f(std::true_type{});
+    return f(std::false_type{});
+}
+// v as a compile-time constant: f(std::integral_constant<int, V>{}) for the V of the list that equals v; a v that is not
+// in the list gets the LAST V (every table below names its fallback there).  Returns what f returns, one type for all V.
+template <int V0, int... Vs, class F>
+static auto with_one_of(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) {
+        return f(std::integral_constant<int, V0>{});
+    } else {
+        if (v == V0) return f(std::integral_constant<int, V0>{});
+        return with_one_of<Vs...>(v, f);
+    }
+}
 
 static int fail(rmx_ctx* c, int code, const char* fmt, ...) {
     char buf[512];
@@ -1042,6 +290,7 @@ static int ensure_events(rmx_ctx* c, size_t n) {
 // front of every record (a budget computed ahead of the chunk loop was too small once every chunk could take
 // the partial-round route), so no call pattern can index past it.
 enum TimeKind {
+    kTkNone = -1,        // launch(): no record (k_solve, the detection kernels)
     kTkFwd4096 = 0,      // k_fwd
     kTkPair4096 = 1,     // k_win (fused forward + pairs) or k_pair_res / k_pair_str
     kTkColsFwd = 2,      // g_cols_fwd
@@ -1083,8 +332,39 @@ static void tm_reset(rmx_ctx* c) {
     c->ev_used = 0;
     c->ev_kind.clear();
 }
-#define RMX_TM_BEGIN(c) do { const int rc_tm_ = tm_begin(c); if (rc_tm_ != RMX_OK) return rc_tm_; } while (0)
-#define RMX_TM_END(c, kind) do { const int rc_tm_ = tm_end((c), (kind)); if (rc_tm_ != RMX_OK) return rc_tm_; } while (0)
+
+// THE kernel launch: kern on c->stream with args converted to its parameter types P... (a wrong count or an
+// inconvertible argument does not compile), bracketed by the timing record of family `kind` (kTkNone: none).  A launch
+// the runtime refuses -- a null kern included -- is RMX_E_HIP under the family's name.
+template <class... P, class... A>
+static int launch(rmx_ctx* c, int kind, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, A&&... args) {
+    static_assert(sizeof...(P) == sizeof...(A), "launch: one argument per kernel parameter");
+    const char* family = kind == kTkNone ? "kernel" : kTimeKindName[kind];
+    if (!kern) return fail(c, RMX_E_HIP, "%s: this ctx has no such kernel", family);
+    if (kind != kTkNone) {
+        const int rc = tm_begin(c);
+        if (rc != RMX_OK) return rc;
+    }
+    const hipError_t e = [&](P... p) {
+        void* ptrs[] = {(void*)&p...};
+        return hipLaunchKernel((const void*)kern, grid, block, ptrs, lds, c->stream);
+    }(std::forward<A>(args)...);
+    if (e != hipSuccess) {   // (the launch's own code: the runtime's last-error slot is read only to clear it)
+        (void)hipGetLastError();
+        return fail(c, RMX_E_HIP, "%s launch failed: %s", family, hipGetErrorString(e));
+    }
+    return kind == kTkNone ? RMX_OK : tm_end(c, kind);
+}
+
+// lets each of `kern` (typed kernel pointers; a null one is skipped) use `bytes` of dynamic LDS
+template <class... P>
+static const void* kernel_handle(void (*kern)(P...)) { return (const void*)kern; }
+template <class... K>
+static int allow_lds(rmx_ctx* c, size_t bytes, K... kern) {
+    for (const void* k : {kernel_handle(kern)...})
+        if (k) RMX_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return RMX_OK;
+}
 
 // pair plan (host_plan.hpp: validation, anchor runs, parts of <= pairs_per_block consecutive items) -> device copies
 static int build_plan(rmx_ctx* c, const int32_t* pairs, int n_pairs) {
@@ -1106,9 +386,6 @@ static int build_plan(rmx_ctx* c, const int32_t* pairs, int n_pairs) {
     return RMX_OK;
 }
 
-// The fine lag search of a refined call (refine.hpp) on the chunk the pair kernels have just finished: windows
-// [w0, w0 + wc), whose spectra `spec` still holds in the order `layout` names.  One workgroup per output slot of the
-// chunk; lag_int is read (the coarse lag0) and all three outputs are overwritten in place.
 // the plan's pairs in output order on the device, for the kernels that take one output slot per workgroup
 static int ensure_ref_pairs(rmx_ctx* c, int n_pairs) {
     if (c->rf_pairs_plan != c->plan_pairs || !c->rf_pairs) {
@@ -1122,6 +399,9 @@ static int ensure_ref_pairs(rmx_ctx* c, int n_pairs) {
     return RMX_OK;
 }
 
+// The fine lag search of a refined call (refine.hpp) on the chunk the pair kernels have just finished: windows
+// [w0, w0 + wc), whose spectra `spec` still holds in the order `layout` names.  One workgroup per output slot of the
+// chunk; lag_int is read (the coarse lag0) and all three outputs are overwritten in place.
 static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, int w0, int wc, int n_pairs, int* d_lag, float* d_frac,
                         float* d_peak) {
     const int rc_p = ensure_ref_pairs(c, n_pairs), logL = sv.logL, unit_log2 = sv.unit_log2;
@@ -1138,23 +418,13 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, i
     a.k = call.integ;
     a.scale = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the two stored forward scales 2^unit_log2
     const unsigned grid = (unsigned)(wc / call.integ * n_pairs);
-    RMX_TM_BEGIN(c);
-    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefThreads), 0, c->stream, a, d_lag, d_frac, d_peak); };
-    auto with_u = [&](auto lay) {
-        constexpr int LAY = decltype(lay)::value;
-        switch (call.refine) {
-            case 2: launch(k_refine<2, LAY>); break;
-            case 4: launch(k_refine<4, LAY>); break;
-            case 8: launch(k_refine<8, LAY>); break;
-            default: launch(k_refine<16, LAY>); break;
-        }
-    };
-    if (sv.layout == kRefKfwd) with_u(std::integral_constant<int, kRefKfwd>{});
-    else if (sv.layout == kRefSmall) with_u(std::integral_constant<int, kRefSmall>{});
-    else with_u(std::integral_constant<int, kRefRows>{});
-    RMX_HIP(c, hipGetLastError());
-    RMX_TM_END(c, kTkRefine);
-    return RMX_OK;
+    // k_refine<U, layout>; U was checked by the entry (16 is the last it admits), the four-step layout is the last one
+    return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
+        return with_one_of<2, 4, 8, 16>(call.refine, [&](auto u) {
+            return launch(c, kTkRefine, k_refine<decltype(u)::value, decltype(lay)::value>, dim3(grid), dim3(kRefThreads), 0, a, d_lag,
+                          d_frac, d_peak);
+        });
+    });
 }
 
 // The quality figures of a quality call (quality.hpp) on the chunk the pair kernels have just finished, in front of
@@ -1175,19 +445,10 @@ static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, 
     a.sa = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the stored forward scale 2^unit_log2, squared
     a.sc = std::ldexp(1.0f, -logL - 4 * unit_log2);   // ... to the fourth power
     const unsigned grid = (unsigned)(wc / call.integ * n_pairs);
-    RMX_TM_BEGIN(c);
-    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefThreads), 0, c->stream, a, d_peak, call.quality); };
-    if (sv.layout == kRefKfwd) launch(k_quality<kRefKfwd>);
-    else if (sv.layout == kRefSmall) launch(k_quality<kRefSmall>);
-    else launch(k_quality<kRefRows>);
-    RMX_HIP(c, hipGetLastError());
-    RMX_TM_END(c, kTkQuality);
-    return RMX_OK;
+    return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
+        return launch(c, kTkQuality, k_quality<decltype(lay)::value>, dim3(grid), dim3(kRefThreads), 0, a, d_peak, call.quality);
+    });
 }
-
-}  // namespace rmx
-
-namespace rmx {
 
 static int upload(rmx_ctx* c, float2** dst, const std::vector<float2>& v) {
     RMX_HIP(c, hipMalloc((void**)dst, v.size() * sizeof(float2)));
@@ -1216,124 +477,74 @@ static size_t gen_rows_lds(const rmx_ctx* c, int R) {   // rows + per-row twiddl
     const int a = logR >> 1;
     return ((size_t)(gen::kGThreads / tpr) * ((size_t)gen::lp(R) + (1 << a) + (R >> a)) + (size_t)(R >> 1) + (R < 4096 ? 240 : 0)) * 8;   // + W_R table + the q = 16 pass's own
 }
+
+// ---- the selection tables: a run-time length -> the instantiation compiled for it (with_one_of: a length outside a
+// list gets the list's last entry; 0 stands for the run-time-length instantiation) -----------------------------------
 // column kernels with the column length compiled in (16-column tiles, the default thread count), else the run-time ones
-// (LB: empty, or LagBounds for the bounded instantiations of the same set)
+// (LB: empty, or LagBounds / LagBounds, Integrate for the bounded / integrating instantiations of the same set)
 template <class... LB>
-static const void* cols_inv_fn(int l1, int lt, int thr) {
+static auto cols_inv_fn(int l1, int lt, int thr) {
     using namespace gen;
-    if (lt == 3) return (const void*)g_cols_inv<3, 0, LB...>;
-    if (lt == 5) {          // 32-column tiles (256-byte row segments): option col_logt = 5, an A/B switch (VERDICT r04 #3a)
-        if (thr == cols_threads(l1, 5) && l1 == 8) return (const void*)g_cols_inv<5, 8, LB...>;
-        if (thr == cols_threads(l1, 5) && l1 == 9) return (const void*)g_cols_inv<5, 9, LB...>;
-        return (const void*)g_cols_inv<5, 0, LB...>;
-    }
-    if (thr == cols_threads(l1, 4)) switch (l1) {
-        case 5: return (const void*)g_cols_inv<4, 5, LB...>;
-        case 6: return (const void*)g_cols_inv<4, 6, LB...>;
-        case 7: return (const void*)g_cols_inv<4, 7, LB...>;
-        case 8: return (const void*)g_cols_inv<4, 8, LB...>;
-        case 9: return (const void*)g_cols_inv<4, 9, LB...>;
-        default: break;
-    }
-    return (const void*)g_cols_inv<4, 0, LB...>;
+    if (lt == 3) return &g_cols_inv<3, 0, LB...>;
+    if (lt == 5)            // 32-column tiles (256-byte row segments): option col_logt = 5, an A/B switch (VERDICT r04 #3a)
+        return with_one_of<8, 9, 0>(thr == cols_threads(l1, 5) ? l1 : 0, [](auto L1) { return &g_cols_inv<5, decltype(L1)::value, LB...>; });
+    return with_one_of<5, 6, 7, 8, 9, 0>(thr == cols_threads(l1, 4) ? l1 : 0, [](auto L1) { return &g_cols_inv<4, decltype(L1)::value, LB...>; });
 }
 template <bool U8>
-static const void* cols_fwd_fn(int l1, int lt, int thr) {
+static auto cols_fwd_fn(int l1, int lt, int thr) {
     using namespace gen;
-    if (lt == 3) return (const void*)g_cols_fwd<U8, 3>;
-    if (lt == 5) {
-        if (thr == cols_threads(l1, 5) && l1 == 8) return (const void*)g_cols_fwd<U8, 5, 8>;
-        if (thr == cols_threads(l1, 5) && l1 == 9) return (const void*)g_cols_fwd<U8, 5, 9>;
-        return (const void*)g_cols_fwd<U8, 5>;
-    }
-    if (thr == cols_threads(l1, 4)) switch (l1) {
-        case 5: return (const void*)g_cols_fwd<U8, 4, 5>;
-        case 6: return (const void*)g_cols_fwd<U8, 4, 6>;
-        case 7: return (const void*)g_cols_fwd<U8, 4, 7>;
-        case 8: return (const void*)g_cols_fwd<U8, 4, 8>;
-        case 9: return (const void*)g_cols_fwd<U8, 4, 9>;
-        default: break;
-    }
-    return (const void*)g_cols_fwd<U8, 4>;
+    if (lt == 3) return &g_cols_fwd<U8, 3>;
+    if (lt == 5) return with_one_of<8, 9, 0>(thr == cols_threads(l1, 5) ? l1 : 0, [](auto L1) { return &g_cols_fwd<U8, 5, decltype(L1)::value>; });
+    return with_one_of<5, 6, 7, 8, 9, 0>(thr == cols_threads(l1, 4) ? l1 : 0, [](auto L1) { return &g_cols_fwd<U8, 4, decltype(L1)::value>; });
 }
+// row kernels with the row length compiled in where we have it and the threads per row are the default (option rows_tpr)
 template <class... WT>   // WT: empty, or XWeight for the weighted instantiations of the same set
-static const void* rows_fwd_fn(int logR, int tpr) {
-    using namespace gen;
-    if (tpr != rows_tpr(1 << logR)) return (const void*)g_rows<true, false, false, 0, WT...>;
-    switch (logR) {
-        case 9: return (const void*)g_rows<true, false, false, 9, WT...>;
-        case 10: return (const void*)g_rows<true, false, false, 10, WT...>;
-        case 11: return (const void*)g_rows<true, false, false, 11, WT...>;
-        case 12: return (const void*)g_rows<true, false, false, 12, WT...>;
-        case 13: return (const void*)g_rows<true, false, false, 13, WT...>;
-        default: return (const void*)g_rows<true, false, false, 0, WT...>;
-    }
+static auto rows_fwd_fn(int logR, int tpr) {
+    return with_one_of<9, 10, 11, 12, 13, 0>(tpr == gen::rows_tpr(1 << logR) ? logR : 0,
+                                             [](auto R) { return &gen::g_rows<true, false, false, decltype(R)::value, WT...>; });
 }
-static const void* rows_inv_fn(int logR, int tpr) {       // the inverse row kernel, row length compiled in where we have it
-    using namespace gen;
-    if (tpr != rows_tpr(1 << logR)) return (const void*)g_rows<false, true, true>;      // RMX_ROWS_TPR override
-    switch (logR) {
-        case 9: return (const void*)g_rows<false, true, true, 9>;
-        case 10: return (const void*)g_rows<false, true, true, 10>;
-        case 11: return (const void*)g_rows<false, true, true, 11>;
-        case 12: return (const void*)g_rows<false, true, true, 12>;
-        case 13: return (const void*)g_rows<false, true, true, 13>;
-        default: return (const void*)g_rows<false, true, true>;
-    }
+static auto rows_inv_fn(int logR, int tpr) {
+    return with_one_of<9, 10, 11, 12, 13, 0>(tpr == gen::rows_tpr(1 << logR) ? logR : 0,
+                                             [](auto R) { return &gen::g_rows<false, true, true, decltype(R)::value>; });
 }
-static const void* rows_anchor_fn(int logR, int tpr) {
-    using namespace gen;
-    if (tpr != rows_tpr(1 << logR)) return nullptr;
-    switch (logR) {
-        case 9: return (const void*)g_rows_anchor<9>;
-        case 10: return (const void*)g_rows_anchor<10>;
-        case 11: return (const void*)g_rows_anchor<11>;
-        case 12: return (const void*)g_rows_anchor<12>;
-        case 13: return (const void*)g_rows_anchor<13>;
-        default: return nullptr;
-    }
+static decltype(GenericKernels::rows_anchor) rows_anchor_fn(int logR, int tpr) {   // (no run-time-length instantiation: null)
+    if (tpr != gen::rows_tpr(1 << logR) || logR < 9 || logR > 13) return nullptr;
+    return with_one_of<9, 10, 11, 12, 13>(logR, [](auto R) { return &gen::g_rows_anchor<decltype(R)::value>; });
 }
-static const void* fused_fn(int nb, int logR, bool def) {   // g_rows_fused<n_buoys, log2 row length, default plan>
-#define RMX_FF(NB, D) (logR == 9 ? (const void*)gen::g_rows_fused<NB, 9, D> : logR == 10 ? (const void*)gen::g_rows_fused<NB, 10, D> : \
-                       logR == 11 ? (const void*)gen::g_rows_fused<NB, 11, D> : (const void*)gen::g_rows_fused<NB, 12, D>)
-    if (def) return nb == 2 ? RMX_FF(2, true) : nb == 3 ? RMX_FF(3, true) : RMX_FF(4, true);
-    return nb == 2 ? RMX_FF(2, false) : nb == 3 ? RMX_FF(3, false) : RMX_FF(4, false);
-#undef RMX_FF
+template <bool DEF>
+static auto fused_fn(int nb, int logR) {                    // g_rows_fused<n_buoys, log2 row length, default plan>
+    return with_one_of<2, 3, 4>(nb, [&](auto NB) {
+        return with_one_of<9, 10, 11, 12>(logR, [](auto R) { return &gen::g_rows_fused<decltype(NB)::value, decltype(R)::value, DEF>; });
+    });
 }
 template <bool DEF, bool U8>
-static const void* wfused_fn(int nb, int logR) {            // g_win_fused<n_buoys, log2 L, default plan, uint8 input>
-#define RMX_WF(NB) (logR == 9 ? (const void*)gen::g_win_fused<NB, 9, DEF, U8> : logR == 10 ? (const void*)gen::g_win_fused<NB, 10, DEF, U8> : \
-                    logR == 11 ? (const void*)gen::g_win_fused<NB, 11, DEF, U8> : (const void*)gen::g_win_fused<NB, 12, DEF, U8>)
-    return nb == 2 ? RMX_WF(2) : nb == 3 ? RMX_WF(3) : RMX_WF(4);
-#undef RMX_WF
+static auto wfused_fn(int nb, int logR) {                   // g_win_fused<n_buoys, log2 L, default plan, uint8 input>
+    return with_one_of<2, 3, 4>(nb, [&](auto NB) {
+        return with_one_of<9, 10, 11, 12>(logR, [](auto R) { return &gen::g_win_fused<decltype(NB)::value, decltype(R)::value, DEF, U8>; });
+    });
+}
+static int fused_plan_buf(int logR) {
+    return with_one_of<9, 10, 11, 12>(logR, [](auto R) { return (int)gen::FusedPlan<decltype(R)::value>::buf; });
 }
 static size_t gen_wfused_lds(int logR, bool tw_regs) {     // transform buffers + the passes' twiddle tables + argmax words
     const int tpr = (1 << logR) >> 4, upw = gen::kGThreads / tpr;
-    const int buf = logR == 9 ? gen::FusedPlan<9>::buf : logR == 10 ? gen::FusedPlan<10>::buf : logR == 11 ? gen::FusedPlan<11>::buf : gen::FusedPlan<12>::buf;
-    return ((size_t)upw * buf + (size_t)(tw_regs ? 0 : gen::fused_tab_total(logR)) + 8) * 8;
+    return ((size_t)upw * fused_plan_buf(logR) + (size_t)(tw_regs ? 0 : gen::fused_tab_total(logR)) + 8) * 8;
 }
 template <bool U8>
-static const void* wscr_fn(int logR) {                      // g_win_scr<log2 L, uint8 input>
-    switch (logR) {
-        case 9: return (const void*)gen::g_win_scr<9, U8>;
-        case 10: return (const void*)gen::g_win_scr<10, U8>;
-        case 11: return (const void*)gen::g_win_scr<11, U8>;
-        case 12: return (const void*)gen::g_win_scr<12, U8>;
-        case 13: return (const void*)gen::g_win_scr<13, U8>;
-        default: return (const void*)gen::g_win_scr<14, U8>;
-    }
+static auto wscr_fn(int logR) {                             // g_win_scr<log2 L, uint8 input>
+    return with_one_of<9, 10, 11, 12, 13, 14>(logR, [](auto R) { return &gen::g_win_scr<decltype(R)::value, U8>; });
 }
 static void wscr_shape(int logR, int* thr, int* upw, size_t* lds) {
-#define RMX_WS(L) case L: *thr = gen::WinPlan<L>::thr; *upw = gen::WinPlan<L>::upw; *lds = gen::WinPlan<L>::lds_bytes; break;
-    switch (logR) { RMX_WS(9) RMX_WS(10) RMX_WS(11) RMX_WS(12) RMX_WS(13) default: RMX_WS(14) }
-#undef RMX_WS
+    with_one_of<9, 10, 11, 12, 13, 14>(logR, [&](auto R) {
+        using Plan = gen::WinPlan<decltype(R)::value>;
+        *thr = Plan::thr;  *upw = Plan::upw;  *lds = Plan::lds_bytes;
+    });
 }
 static size_t gen_fused_lds(int R, bool tw_regs = false) {   // g_rows_fused: R/16 threads per row (tw_regs: no twiddle tables)
     int logR = 0;
     while ((1 << logR) < R) ++logR;
     const int a = logR >> 1, tpr = R >> 4, upw = gen::kGThreads / (tpr > 0 ? tpr : 1);
-    const int buf = logR == 9 ? gen::FusedPlan<9>::buf : logR == 10 ? gen::FusedPlan<10>::buf : logR == 11 ? gen::FusedPlan<11>::buf : gen::FusedPlan<12>::buf;
-    return ((size_t)upw * ((size_t)buf + (1 << a) + (R >> a)) + (size_t)(tw_regs ? 0 : gen::fused_tab_total(logR))) * 8;   // + the passes' twiddle tables
+    return ((size_t)upw * ((size_t)fused_plan_buf(logR) + (1 << a) + (R >> a)) + (size_t)(tw_regs ? 0 : gen::fused_tab_total(logR))) * 8;   // + the passes' twiddle tables
 }
 static int host_col_log_t(const rmx_ctx* c, int l1) {   // gen::col_log_t, or the "col_logt" option (3 | 4) for experiments
     return (int)c->knobs.get_or("col_logt", gen::col_log_t(l1));
@@ -1349,6 +560,65 @@ static int gen_cols_threads(const rmx_ctx* c, int l1) { // one radix-16 work ite
     return work >= 1024 ? 1024 : (work < 64 ? 64 : (int)work);
 }
 
+// Every kernel choice of the generic path, from the lengths and the options alone (no HIP call).  logL1 = 0: the
+// LDS-resident lengths (g_fwd_small / g_pair_small need no choice), else the four-step split L = L1 x L2 with its
+// column tile, column threads and threads per row.
+static GenericKernels pick_generic_kernels(int n_buoys, int logL, int logL1, int logL2, int col_log_t, int cols_threads, int rows_tpr,
+                                           const host::Knobs& knobs) {
+    GenericKernels k;
+    if (logL1 == 0) {
+        // at most four buoys, 512 <= L <= 4096: whole windows in one kernel, spectra in registers (option wfused = 0: the
+        // two per-transform kernels, as for custom Doppler searches)
+        if (n_buoys >= 2 && n_buoys <= 4 && logL >= 9 && logL <= 12 && knobs.get_or("wfused", 1) != 0) {
+            k.wf[0][0] = wfused_fn<false, false>(n_buoys, logL);
+            k.wf[0][1] = wfused_fn<false, true>(n_buoys, logL);
+            k.wf[1][0] = wfused_fn<true, false>(n_buoys, logL);
+            k.wf[1][1] = wfused_fn<true, true>(n_buoys, logL);
+            k.wf_lds[0] = gen_wfused_lds(logL, false);
+            k.wf_lds[1] = gen_wfused_lds(logL, gen::fused_tw_regs(n_buoys, logL, true));
+        }
+    } else {
+        k.cols_inv = cols_inv_fn<>(logL1, col_log_t, cols_threads);
+        k.cols_inv_lb = cols_inv_fn<LagBounds>(logL1, col_log_t, cols_threads);
+        k.cols_inv_int = cols_inv_fn<LagBounds, Integrate>(logL1, col_log_t, cols_threads);
+        k.cols_fwd[0] = cols_fwd_fn<false>(logL1, col_log_t, cols_threads);
+        k.cols_fwd[1] = cols_fwd_fn<true>(logL1, col_log_t, cols_threads);
+        k.rows_fwd = rows_fwd_fn<>(logL2, rows_tpr);
+        k.rows_fwd_wt = rows_fwd_fn<XWeight>(logL2, rows_tpr);
+        k.rows_inv = rows_inv_fn(logL2, rows_tpr);
+        if (knobs.get_or("rows_anchor", 1) != 0) k.rows_anchor = rows_anchor_fn(logL2, rows_tpr);
+        // both row passes in one kernel when the buoys' spectra rows fit the register file (generic_path.hpp); option
+        // fused = 0: never, fused_def = 0: without the unrolled default-plan instantiation
+        if (n_buoys <= 4 && logL2 >= 9 && logL2 <= 12 && knobs.get_or("fused", 1) != 0) {
+            k.fused = fused_fn<false>(n_buoys, logL2);
+            if (knobs.get_or("fused_def", 1) != 0) k.fused_def = fused_fn<true>(n_buoys, logL2);
+        }
+    }
+    // any buoy count, 512 <= L <= 16384 (15: the even / odd-bin halves, win_eo.hpp): whole windows in one persistent
+    // kernel, spectra in a per-workgroup scratch (option wscr = 0: the two-kernel LDS path / the four-step path, which
+    // the Doppler search uses in any case)
+    if (!k.wf[0][0] && logL >= 9 && logL <= 15 && knobs.get_or("wscr", 1) != 0) {
+        wscr_shape(logL, &k.ws_thr, &k.ws_upw, &k.ws_lds);
+        if (logL == 15) {
+            k.ws15[0] = gen::g_win_eo15<false>;
+            k.ws15[1] = gen::g_win_eo15<true>;
+            k.ws_thr = 512;
+            k.ws_upw = 1;
+            k.ws_lds = gen::kWinEoLds;
+        } else if (logL == 14 && knobs.get_or("wscr14", 1) != 0) {
+            // L = 16384: 512 threads x two butterflies (g_win_scr14) unless wscr14 = 0 (1024 threads x one: g_win_scr<14>)
+            k.ws[0] = gen::g_win_scr14<false>;
+            k.ws[1] = gen::g_win_scr14<true>;
+            k.ws_thr = 512;
+            k.ws_lds = ((size_t)gen::lp(16384) + 15 * 64 + 15 * 4 + 16) * 8;
+        } else {
+            k.ws[0] = wscr_fn<false>(logL);
+            k.ws[1] = wscr_fn<true>(logL);
+        }
+    }
+    return k;
+}
+
 static int generic_init(rmx_ctx* c) {
     using namespace gen;
     c->generic = true;
@@ -1356,35 +626,17 @@ static int generic_init(rmx_ctx* c) {
     while ((1 << logn) < c->n_samples) ++logn;
     c->g_logL = logn + 1;
     const long L = 1L << c->g_logL;
-    const int all_pairs = c->n_buoys * (c->n_buoys - 1) / 2;
     std::vector<float2> t;
+    int rc = RMX_OK;
     if (L <= kGenSmallMaxL) {
         make_row_table(t, (int)L);
-        int rc = upload(c, &c->g_tw, t);
+        rc = upload(c, &c->g_tw, t);
         if (rc) return rc;
-        const int slds = (int)(gen::lp(L) * 8 + 1024 * 8);
-        RMX_HIP(c, hipFuncSetAttribute((const void*)g_pair_small<>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)g_pair_small<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)(g_pair_small<LagBounds, Integrate>), hipFuncAttributeMaxDynamicSharedMemorySize, slds));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<false>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<true>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<false, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)g_fwd_small<true, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, slds));
-        // at most four buoys, 512 <= L <= 4096: whole windows in one kernel, spectra in registers (RMX_WFUSED=0: the two
-        // kernels above, as for custom Doppler searches)
-        c->g_wfused = c->n_buoys >= 2 && c->n_buoys <= 4 && c->g_logL >= 9 && c->g_logL <= 12;
-        c->g_wfused = c->g_wfused && c->knobs.get_or("wfused", 1) != 0;
-        if (c->g_wfused) {
-            c->g_wf_fn[0][0] = wfused_fn<false, false>(c->n_buoys, c->g_logL);
-            c->g_wf_fn[0][1] = wfused_fn<false, true>(c->n_buoys, c->g_logL);
-            c->g_wf_fn[1][0] = wfused_fn<true, false>(c->n_buoys, c->g_logL);
-            c->g_wf_fn[1][1] = wfused_fn<true, true>(c->n_buoys, c->g_logL);
-            c->g_wf_lds[0] = gen_wfused_lds(c->g_logL, false);
-            c->g_wf_lds[1] = gen_wfused_lds(c->g_logL, gen::fused_tw_regs(c->n_buoys, c->g_logL, true));
-            for (int d = 0; d < 2; ++d)
-                for (int u = 0; u < 2; ++u)
-                    RMX_HIP(c, hipFuncSetAttribute(c->g_wf_fn[d][u], hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->g_wf_lds[d]));
-        }
+        c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, 0, 0, 0, 0, 0, c->knobs);
+        rc = allow_lds(c, (size_t)gen::lp(L) * 8 + 1024 * 8, g_pair_small<>, g_pair_small<LagBounds>, g_pair_small<LagBounds, Integrate>,
+                       g_fwd_small<false>, g_fwd_small<true>, g_fwd_small<false, XWeight>, g_fwd_small<true, XWeight>);
+        for (int d = 0; d < 2 && rc == RMX_OK; ++d) rc = allow_lds(c, c->gk.wf_lds[d], c->gk.wf[d][0], c->gk.wf[d][1]);
+        if (rc) return rc;
     } else {
         // columns of length L1 <= 1024 (a tile of 16 columns is L1*128 bytes of LDS), rows of L2 = L/L1 <= 8192
         // columns a little shorter than rows (measured: 512 x 4096 beats 1024 x 2048 at L = 2^21, 256 x 2048 beats
@@ -1397,7 +649,7 @@ static int generic_init(rmx_ctx* c) {
         c->g_logL2 = c->g_logL - c->g_logL1;
         c->g_lo_bits = (c->g_logL + 1) / 2;
         make_row_table(t, 1 << c->g_logL1);
-        int rc = upload(c, &c->g_tw1, t);
+        rc = upload(c, &c->g_tw1, t);
         if (rc) return rc;
         make_row_table(t, 1 << c->g_logL2);
         rc = upload(c, &c->g_tw2, t);
@@ -1408,97 +660,48 @@ static int generic_init(rmx_ctx* c) {
         if (rc) return rc;
         rc = upload(c, &c->g_tlo, tlo);
         if (rc) return rc;
-        const int cols_lds = (int)gen_cols_lds(c, c->g_logL1), rows_lds = (int)gen_rows_lds(c, 1 << c->g_logL2);
-        {
-            const int lt = host_col_log_t(c, c->g_logL1), thr = gen_cols_threads(c, c->g_logL1);
-            c->g_cols_inv_fn = cols_inv_fn<>(c->g_logL1, lt, thr);
-            c->g_cols_inv_lb_fn = cols_inv_fn<LagBounds>(c->g_logL1, lt, thr);
-            RMX_HIP(c, hipFuncSetAttribute(c->g_cols_inv_lb_fn, hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
-            c->g_cols_inv_int_fn = cols_inv_fn<LagBounds, Integrate>(c->g_logL1, lt, thr);   // (integrated calls)
-            RMX_HIP(c, hipFuncSetAttribute(c->g_cols_inv_int_fn, hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
-            c->g_cols_fwd_fn[0] = cols_fwd_fn<false>(c->g_logL1, lt, thr);
-            c->g_cols_fwd_fn[1] = cols_fwd_fn<true>(c->g_logL1, lt, thr);
-            RMX_HIP(c, hipFuncSetAttribute(c->g_cols_inv_fn, hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
-            RMX_HIP(c, hipFuncSetAttribute(c->g_cols_fwd_fn[0], hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
-            RMX_HIP(c, hipFuncSetAttribute(c->g_cols_fwd_fn[1], hipFuncAttributeMaxDynamicSharedMemorySize, cols_lds));
-        }
-        RMX_HIP(c, hipFuncSetAttribute((const void*)(g_rows<true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)(g_rows<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
-        c->g_rows_inv_fn = rows_inv_fn(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));
-        c->g_rows_fwd_fn = rows_fwd_fn<>(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));
-        RMX_HIP(c, hipFuncSetAttribute(c->g_rows_fwd_fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
-        c->g_rows_fwd_wt_fn = rows_fwd_fn<XWeight>(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));   // (weighted calls)
-        RMX_HIP(c, hipFuncSetAttribute(c->g_rows_fwd_wt_fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
-        RMX_HIP(c, hipFuncSetAttribute(c->g_rows_inv_fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
-        c->g_rows_anchor_fn = rows_anchor_fn(c->g_logL2, gen_rows_tpr(c, 1 << c->g_logL2));
-        { long v; if (c->knobs.get("rows_anchor", &v)) { if (v == 0) c->g_rows_anchor_fn = nullptr; else if (v >= 2) c->g_rows_anchor_min_b = (int)v; } }
-        if (c->g_rows_anchor_fn)
-            RMX_HIP(c, hipFuncSetAttribute(c->g_rows_anchor_fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows_lds));
-        // both row passes in one kernel when the buoys' spectra rows fit the register file (generic_path.hpp)
-        c->g_fused = c->n_buoys <= 4 && c->g_logL2 >= 9 && c->g_logL2 <= 12;
-        { long v; if (c->knobs.get("fused", &v)) {      // 0: never, 2: also for batches too small to fill the chip (tests)
-            c->g_fused = c->g_fused && v != 0;
-            c->g_fused_always = v == 2;
-        } }
-        if (c->g_fused) {
-            const int flds = (int)gen_fused_lds(1 << c->g_logL2);
-            const void* fn = fused_fn(c->n_buoys, c->g_logL2, false);
-            c->g_fused_fn = fn;
-            c->g_fused_def_fn = fused_fn(c->n_buoys, c->g_logL2, true);
-            if (c->knobs.get_or("fused_def", 1) == 0) c->g_fused_def_fn = nullptr;
-            if (c->g_fused_def_fn) {
-                const int dlds = (int)gen_fused_lds(1 << c->g_logL2, gen::fused_tw_regs(c->n_buoys, c->g_logL2, true));
-                RMX_HIP(c, hipFuncSetAttribute(c->g_fused_def_fn, hipFuncAttributeMaxDynamicSharedMemorySize, dlds));
-            }
-            RMX_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, flds));
-        }
-    }
-    // any buoy count, 512 <= L <= 16384: whole windows in one persistent kernel, spectra in a per-workgroup scratch
-    // (RMX_WSCR=0: the two-kernel LDS path / the four-step path, which the Doppler search uses in any case)
-    c->g_wscr = !c->g_wfused && c->g_logL >= 9 && c->g_logL <= 15;   // (15: the even / odd-bin halves, win_eo.hpp)
-    { long v; if (c->knobs.get("wscr", &v)) {          // 0: never, 2: also for batches that do not fill the chip (tests)
-        c->g_wscr = c->g_wscr && v != 0;
-        c->g_wscr_always = v == 2;
-    } }
-    if (c->g_wscr) {
-        make_row_table(t, c->g_logL == 15 ? 16384 : (int)L);       // (N = 16384: two 16384-point halves)
-        int rc = upload(c, &c->g_tw_win, t);
+        c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, c->g_logL1, c->g_logL2, host_col_log_t(c, c->g_logL1),
+                                     gen_cols_threads(c, c->g_logL1), gen_rows_tpr(c, 1 << c->g_logL2), c->knobs);
+        const GenericKernels& k = c->gk;
+        const size_t rows_lds = gen_rows_lds(c, 1 << c->g_logL2);
+        rc = allow_lds(c, gen_cols_lds(c, c->g_logL1), k.cols_inv, k.cols_inv_lb, k.cols_inv_int, k.cols_fwd[0], k.cols_fwd[1]);
+        // (the run-time-length row kernels too, whichever the tables chose)
+        if (rc == RMX_OK)
+            rc = allow_lds(c, rows_lds, g_rows<true, false, false>, g_rows<false, true, true>, k.rows_fwd, k.rows_fwd_wt, k.rows_inv, k.rows_anchor);
+        if (rc == RMX_OK) rc = allow_lds(c, gen_fused_lds(1 << c->g_logL2), k.fused);
+        if (rc == RMX_OK) rc = allow_lds(c, gen_fused_lds(1 << c->g_logL2, gen::fused_tw_regs(c->n_buoys, c->g_logL2, true)), k.fused_def);
         if (rc) return rc;
-        c->g_ws_fn[0] = wscr_fn<false>(c->g_logL);
-        c->g_ws_fn[1] = wscr_fn<true>(c->g_logL);
-        wscr_shape(c->g_logL, &c->g_ws_thr, &c->g_ws_upw, &c->g_ws_lds);
+        { long v; if (c->knobs.get("rows_anchor", &v) && v >= 2) c->g_rows_anchor_min_b = (int)v; }
+        c->g_fused = k.fused != nullptr;
+        c->g_fused_always = c->knobs.get_or("fused", 1) == 2;   // 2: also for batches too small to fill the chip (tests)
+    }
+    c->g_wfused = c->gk.wf[0][0] != nullptr;
+    c->g_wscr = c->gk.ws[0] != nullptr || c->gk.ws15[0] != nullptr;
+    c->g_wscr_always = c->knobs.get_or("wscr", 1) == 2;         // 2: also for batches that do not fill the chip (tests)
+    if (c->g_wscr) {
+        const GenericKernels& k = c->gk;
+        make_row_table(t, c->g_logL == 15 ? 16384 : (int)L);       // (N = 16384: two 16384-point halves)
+        rc = upload(c, &c->g_tw_win, t);
+        if (rc) return rc;
         if (c->g_logL == 15) {
             const double two_pi = 6.283185307179586476925286766559;
             std::vector<float2> wl(1024);
             for (int i = 0; i < 1024; ++i) wl[i] = make_float2((float)std::cos(two_pi * i / 32768.0), (float)-std::sin(two_pi * i / 32768.0));
             rc = upload(c, &c->g_tw_l, wl);
             if (rc) return rc;
-            c->g_ws_fn[0] = (const void*)gen::g_win_eo15<false>;
-            c->g_ws_fn[1] = (const void*)gen::g_win_eo15<true>;
-            c->g_ws_thr = 512;
-            c->g_ws_upw = 1;
-            c->g_ws_lds = gen::kWinEoLds;
         }
-        // L = 16384: 512 threads x two butterflies (g_win_scr14) unless RMX_WSCR14=0 (1024 threads x one: g_win_scr<14>)
-        bool two = c->g_logL == 14;
-        two = two && c->knobs.get_or("wscr14", 1) != 0;
-        if (two) {
-            c->g_ws_fn[0] = (const void*)gen::g_win_scr14<false>;
-            c->g_ws_fn[1] = (const void*)gen::g_win_scr14<true>;
-            c->g_ws_thr = 512;
-            c->g_ws_lds = ((size_t)gen::lp(16384) + 15 * 64 + 15 * 4 + 16) * 8;
-        }
+        rc = allow_lds(c, k.ws_lds, k.ws[0], k.ws[1], k.ws15[0], k.ws15[1]);
+        if (rc) return rc;
         int per_cu = 1;
-        for (int u = 0; u < 2; ++u)
-            RMX_HIP(c, hipFuncSetAttribute(c->g_ws_fn[u], hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->g_ws_lds));
-        RMX_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->g_ws_fn[0], c->g_ws_thr, c->g_ws_lds));
+        RMX_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.ws15[0] ? kernel_handle(k.ws15[0]) : kernel_handle(k.ws[0]), k.ws_thr,
+                                                                k.ws_lds));
         if (per_cu < 1) per_cu = 1;
         { long v; if (c->knobs.get("wscr_per_cu", &v) && v >= 1 && v <= per_cu) per_cu = (int)v; }
         long grid = (long)c->n_cus * per_cu;
-        const long need = ((long)c->max_windows + c->g_ws_upw - 1) / c->g_ws_upw;
+        const long need = ((long)c->max_windows + k.ws_upw - 1) / k.ws_upw;
         if (grid > need) grid = need;
         c->g_ws_grid = (int)grid;
-        const size_t sbytes = (size_t)grid * c->g_ws_upw * c->n_buoys * L * 8;
+        const size_t sbytes = (size_t)grid * k.ws_upw * c->n_buoys * L * 8;
         RMX_HIP(c, hipMalloc((void**)&c->g_ws_scratch, sbytes));
         c->scratch_bytes += sbytes;
         // N = 8192: the two bin-parity halves on the fused N = 4096 kernel's network (kwin8k.hpp), same scratch size
@@ -1520,15 +723,13 @@ static int generic_init(rmx_ctx* c) {
             RMX_HIP(c, hipMalloc((void**)&c->g_k8_tw2, t2.size() * sizeof(float2)));
             RMX_HIP(c, hipMemcpy(c->g_k8_tw2, t2.data(), t2.size() * sizeof(float2), hipMemcpyHostToDevice));
             c->scratch_bytes += t1.size() * sizeof(float4) + t2.size() * sizeof(float2);
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8kl<false>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLdsLBytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8kl<true>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLdsLBytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8kl<false, LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLdsLBytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8kl<true, LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLdsLBytes));
-            c->g_k8 = c->g_ws_upw == 1 && grid <= c->n_cus;      // (its grid is the scratch's: one window slot per workgroup)
+            rc = allow_lds(c, k8::kLdsLBytes, k8::k_win8kl<false>, k8::k_win8kl<true>, k8::k_win8kl<false, LagBounds>, k8::k_win8kl<true, LagBounds>);
+            if (rc) return rc;
+            c->g_k8 = k.ws_upw == 1 && grid <= c->n_cus;      // (its grid is the scratch's: one window slot per workgroup)
             c->g_k8_kind = (int)c->knobs.get_or("kwin8k", 1);
 #ifdef RMX_EXPERIMENTS
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLds8Bytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k8::k_win8k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, k8::kLds8Bytes));
+            rc = allow_lds(c, k8::kLds8Bytes, k8::k_win8k<false>, k8::k_win8k<true>);
+            if (rc) return rc;
 #else
             if (c->g_k8_kind == 2) return fail(c, RMX_E_UNSUPPORTED, "option kwin8k = 2 (k_win8k) exists only in a -DRMX_EXPERIMENTS build");
 #endif
@@ -1536,7 +737,7 @@ static int generic_init(rmx_ctx* c) {
         // N = 16384: four quarter transforms on the same network, forward and pair kernels per chunk of g_ws_grid windows
         // (kwin16k.hpp; the spectra of a chunk take the SAME B x 256 KiB per window as g_win_eo15's per-workgroup scratch, so
         // the buffer is shared).  Option kwin16k: 1 (default) = from the measured batch size on, 2 = every batch, 0 = g_win_eo15.
-        if (c->g_logL == 15 && c->knobs.get_or("kwin16k", 1) != 0 && c->g_ws_upw == 1) {
+        if (c->g_logL == 15 && c->knobs.get_or("kwin16k", 1) != 0 && k.ws_upw == 1) {
             std::vector<float4> t1, t1_4096;
             std::vector<float2> t2, gq, tws;
             build_tables(t1_4096, t2);
@@ -1550,10 +751,9 @@ static int generic_init(rmx_ctx* c) {
             rc = upload(c, &c->g_k16_tws, tws);
             if (rc) return rc;
             c->scratch_bytes += t1.size() * sizeof(float4);
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsFwdBytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsFwdBytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_pairs<>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsPairBytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k16::k16_pairs<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, k16::kLdsPairBytes));
+            rc = allow_lds(c, k16::kLdsFwdBytes, k16::k16_fwd<false>, k16::k16_fwd<true>);
+            if (rc == RMX_OK) rc = allow_lds(c, k16::kLdsPairBytes, k16::k16_pairs<>, k16::k16_pairs<LagBounds>);
+            if (rc) return rc;
             c->g_k16 = (int)c->knobs.get_or("kwin16k", 1);
         }
     }
@@ -1631,7 +831,6 @@ static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, 
     const int N = c->n_samples, logL = c->g_logL, B = c->n_buoys;
     const long L = 1L << logL;
     const float fwd_scale = std::ldexp(1.0f, -(logL / 2));
-    hipStream_t st = c->stream;
     const int items = wc * B;
     const long first_item = (long)w0 * B;
     if (rot && !c->g_spec_r) {
@@ -1640,68 +839,36 @@ static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, 
         c->g_dyn_bytes += (size_t)c->g_chunk * B * L * 8;
     }
     float2* dst = rot ? c->g_spec_r : c->g_spec;
+    XWeight wt = call.wt;   // weighted call (never with rot): the stored bins carry fwd_scale
+    wt.unit = fwd_scale;
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
-        RMX_TM_BEGIN(c);
-        auto launch = [&](auto kern, const float2* a_rot, auto... wt) {
-            hipLaunchKernelGGL(kern, dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, st, d_iq, dst, c->g_tw, N, logL, first_item,
-                               fwd_scale, a_rot, wt...);
-        };
-        with_u8(u8, [&](auto U) {
+        return with_u8(u8, [&](auto U) {
             constexpr bool U8 = decltype(U)::value;
-            if (call.wt.band) {   // weighted call (never with rot): the stored bins carry fwd_scale
-                XWeight a_wt = call.wt;
-                a_wt.unit = fwd_scale;
-                launch(g_fwd_small<U8, XWeight>, nullptr, a_wt);
-            } else
-                launch(g_fwd_small<U8>, rot);
+            auto go = [&](auto kern, const float2* a_rot, auto... a_wt) {
+                return launch(c, kTkFwdSmall, kern, dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, d_iq, dst, c->g_tw, N, logL, first_item,
+                              fwd_scale, a_rot, a_wt...);
+            };
+            return call.wt.band ? go(g_fwd_small<U8, XWeight>, nullptr, wt) : go(g_fwd_small<U8>, rot);
         });
-        RMX_HIP(c, hipGetLastError());
-        RMX_TM_END(c, kTkFwdSmall);
-        return RMX_OK;
     }
     const int l1 = c->g_logL1, l2 = c->g_logL2, L1 = 1 << l1, L2 = 1 << l2;
     const int cthr = gen_cols_threads(c, l1), tpr = gen_rows_tpr(c, L2);
-    const size_t clds = gen_cols_lds(c, l1), rlds = gen_rows_lds(c, L2);
-    const int lt = host_col_log_t(c, l1), ntiles = L2 >> lt;
+    const int ntiles = L2 >> host_col_log_t(c, l1);
     // column pass (zero-padded window -> [k1'][n2] * W_L^(n2 k1)), row pass in place (-> [k1'][k2'])
-    {
-        const void* a_iq = d_iq;
-        float2* a_out = dst;
-        const float2 *a_tw = c->g_tw1, *a_thi = c->g_thi, *a_tlo = c->g_tlo, *a_rot = rot;
-        int a_l1 = l1, a_l2 = l2, a_lo = c->g_lo_bits;
-        long a_first = first_item;
-        void* args[] = {&a_iq, &a_out, &a_tw, &a_l1, &a_l2, &a_first, &a_lo, &a_thi, &a_tlo, &a_rot};
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_cols_fwd_fn[u8 ? 1 : 0], dim3(ntiles, items), dim3(cthr), args, clds, st));
-        RMX_TM_END(c, kTkColsFwd);
-    }
-    if (cols_only) {                      // g_rows_fused does the rows
-        RMX_HIP(c, hipGetLastError());
-        return RMX_OK;
-    }
+    int rc = launch(c, kTkColsFwd, c->gk.cols_fwd[u8 ? 1 : 0], dim3(ntiles, items), dim3(cthr), gen_cols_lds(c, l1), d_iq, dst, c->g_tw1,
+                    l1, l2, first_item, c->g_lo_bits, c->g_thi, c->g_tlo, rot);
+    if (rc != RMX_OK || cols_only) return rc;   // (cols_only: g_rows_fused does the rows)
     const long rows = (long)items * L1;
     const int rpw = kGThreads / tpr;
-    {
-        float2* a_data = dst;
-        const float2 *a_tw = c->g_tw2, *a_thi = c->g_thi, *a_tlo = c->g_tlo, *a_null = nullptr;
-        const GPair* a_pairs = nullptr;
-        int a_l2 = l2, a_L1 = L1, a_l1 = l1, a_lo = c->g_lo_bits, a_zero = 0, a_tpr = tpr;
-        long a_L = L, a_rows = rows;
-        float a_scale = fwd_scale;
-        // weighted call: the same arguments plus the weight, whose chunk starts at window w0
-        XWeight a_wt = call.wt;
-        a_wt.w0 = w0;
-        a_wt.unit = fwd_scale;
-        void* args[] = {&a_data, &a_tw, &a_l2, &a_L1, &a_l1, &a_L, &a_lo, &a_thi, &a_tlo, &a_scale, &a_rows, &a_null, &a_null,
-                        &a_pairs, &a_zero, &a_zero, &a_tpr, &a_wt};
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(call.wt.band ? c->g_rows_fwd_wt_fn : c->g_rows_fwd_fn, dim3((unsigned)((rows + rpw - 1) / rpw)),
-                                   dim3(kGThreads), args, rlds, st));
-        RMX_TM_END(c, kTkRowsFwd);
-    }
-    RMX_HIP(c, hipGetLastError());
-    return RMX_OK;
+    // forward rows read no second operand: no spectra, no pair list; a weighted call's chunk starts at window w0
+    auto go = [&](auto kern, auto... a_wt) {
+        return launch(c, kTkRowsFwd, kern, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), gen_rows_lds(c, L2), dst, c->g_tw2, l2,
+                      L1, l1, L, c->g_lo_bits, c->g_thi, c->g_tlo, fwd_scale, rows, /* spec */ nullptr, /* spec_j */ nullptr,
+                      /* pairs */ nullptr, /* n_pairs */ 0, /* n_buoys */ 0, tpr, a_wt...);
+    };
+    wt.w0 = w0;
+    return call.wt.band ? go(c->gk.rows_fwd_wt, wt) : go(c->gk.rows_fwd);
 }
 
 // pair kernels of that chunk: X_i from g_spec, X_j from g_spec (use_rot false) or g_spec_r; results at
@@ -1713,108 +880,66 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     const long L = 1L << logL;
     const int hs = logL / 2;
     const float out_scale = std::ldexp(1.0f, -(logL - 2 * hs));
-    hipStream_t st = c->stream;
     const int slots = wc * n_pairs;
     const float2* spec_j = use_rot ? c->g_spec_r : c->g_spec;
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
-        RMX_TM_BEGIN(c);
-        auto launch = [&](auto kern, int grid, long first, auto... tail) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, st, c->g_spec, spec_j, c->g_tw,
-                               c->g_pairs, n_pairs, B, N, logL, first, out_scale, d_lag, d_frac, d_peak, tail...);
+        auto go = [&](auto kern, int grid, long first, auto... tail) {
+            return launch(c, kTkPairSmall, kern, dim3(grid), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, c->g_spec, spec_j, c->g_tw,
+                          c->g_pairs, n_pairs, B, N, logL, first, out_scale, d_lag, d_frac, d_peak, tail...);
         };
         if (call.integrated())   // one workgroup per (group, pair); w0 and wc are whole groups, the bounds per group
-            launch(g_pair_small<LagBounds, Integrate>, slots / call.integ, (long)(w0 / call.integ), call.lb, Integrate{call.integ});
-        else if (call.bounded())
-            launch(g_pair_small<LagBounds>, slots, (long)w0, call.lb);
-        else
-            launch(g_pair_small<>, slots, (long)w0);
-        RMX_HIP(c, hipGetLastError());
-        RMX_TM_END(c, kTkPairSmall);
-        return RMX_OK;
+            return go(g_pair_small<LagBounds, Integrate>, slots / call.integ, (long)(w0 / call.integ), call.lb, Integrate{call.integ});
+        if (call.bounded()) return go(g_pair_small<LagBounds>, slots, (long)w0, call.lb);
+        return go(g_pair_small<>, slots, (long)w0);
     }
+    const GenericKernels& k = c->gk;
     const int l1 = c->g_logL1, l2 = c->g_logL2, L1 = 1 << l1, L2 = 1 << l2;
     const int cthr = gen_cols_threads(c, l1), tpr = gen_rows_tpr(c, L2);
     const size_t clds = gen_cols_lds(c, l1), rlds = gen_rows_lds(c, L2);
     const int lt = host_col_log_t(c, l1), ntiles = L2 >> lt;
     const long rows = (long)slots * L1;
     const int rpw = kGThreads / tpr;
+    const bool all_pairs = c->plan_all_pairs && n_pairs == B * (B - 1) / 2;
     // row pass ([product on load] rows(L2)^-1 * conj W_L^(n2 k1)), column pass (-> tile records + halo), reduction
+    int rc;
     if (fused) {
         // g_spec holds the column pass's output: forward rows, products and inverse rows in one kernel
         const long units = (long)wc * L1;
         const int upw = kGThreads / (L2 >> 4 > 0 ? L2 >> 4 : 1);
-        const long blocks = (units + upw - 1) / upw;
-        const bool def_plan = c->g_fused_def_fn && c->plan_all_pairs && n_pairs == B * (B - 1) / 2;
-        const dim3 grid((unsigned)blocks);
+        const bool def_plan = k.fused_def && all_pairs;
         const float fs = std::ldexp(1.0f, -(logL / 2));
-        const float2* colsp = c->g_spec;
-        float2* prodp = c->g_prod;
-        const float2 *twp = c->g_tw2, *thip = c->g_thi, *tlop = c->g_tlo;
-        const GPair* pp = c->g_pairs;
-        int a_L1 = L1, a_l1 = l1, a_lo = c->g_lo_bits, a_np = n_pairs;
-        long a_L = L, a_units = units;
-        float a_scale = fs * fs;
-        void* args[] = {&colsp, &prodp, &twp, &a_L1, &a_l1, &a_L, &a_lo, &thip, &tlop, &a_scale, &a_units, &pp, &a_np};
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(def_plan ? c->g_fused_def_fn : c->g_fused_fn, grid, dim3(kGThreads), args,
-                                   gen_fused_lds(L2, def_plan && gen::fused_tw_regs(B, l2, true)), st));
-        RMX_TM_END(c, kTkRowsFused);
-    } else if (c->g_rows_anchor_fn && c->plan_all_pairs && n_pairs == B * (B - 1) / 2 && B >= c->g_rows_anchor_min_b) {
+        rc = launch(c, kTkRowsFused, def_plan ? k.fused_def : k.fused, dim3((unsigned)((units + upw - 1) / upw)), dim3(kGThreads),
+                    gen_fused_lds(L2, def_plan && gen::fused_tw_regs(B, l2, true)), c->g_spec, c->g_prod, c->g_tw2, L1, l1, L, c->g_lo_bits,
+                    c->g_thi, c->g_tlo, fs * fs, units, c->g_pairs, n_pairs);
+    } else if (k.rows_anchor && all_pairs && B >= c->g_rows_anchor_min_b) {
         // default pair list: the anchor's row stays in registers over its run of pairs (from 6 buoys on: with 5 the runs are
         // too short for the per-workgroup set-up, 0.649 -> 0.692 ms at N = 16384; with 6 / 7 / 8 buoys 0.89 -> 0.84, 1.16 -> 1.10,
         // 1.54 -> 1.39 ms, cfg5 250 -> 203 ms)
-        float2* a_data = c->g_prod;
-        const float2 *a_tw = c->g_tw2, *a_thi = c->g_thi, *a_tlo = c->g_tlo, *a_spec = c->g_spec, *a_specj = spec_j;
-        int a_L1 = L1, a_l1 = l1, a_lo = c->g_lo_bits, a_np = n_pairs, a_B = B;
-        long a_L = L;
-        float a_scale = 1.0f;
-        void* args[] = {&a_data, &a_tw, &a_L1, &a_l1, &a_L, &a_lo, &a_thi, &a_tlo, &a_scale, &a_spec, &a_specj, &a_np, &a_B};
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_rows_anchor_fn, dim3((unsigned)((L1 / rpw) * (B - 1)), (unsigned)wc), dim3(kGThreads), args, rlds, st));
-        RMX_TM_END(c, kTkRowsAnchor);
-    } else
-    {
-        float2* a_data = c->g_prod;
-        const float2 *a_tw = c->g_tw2, *a_thi = c->g_thi, *a_tlo = c->g_tlo, *a_spec = c->g_spec, *a_specj = spec_j;
-        const GPair* a_pairs = c->g_pairs;
-        int a_l2 = l2, a_L1 = L1, a_l1 = l1, a_lo = c->g_lo_bits, a_np = n_pairs, a_B = B, a_tpr = tpr;
-        long a_L = L, a_rows = rows;
-        float a_scale = 1.0f;
-        void* args[] = {&a_data, &a_tw, &a_l2, &a_L1, &a_l1, &a_L, &a_lo, &a_thi, &a_tlo, &a_scale, &a_rows, &a_spec, &a_specj,
-                        &a_pairs, &a_np, &a_B, &a_tpr};
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_rows_inv_fn, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), args, rlds, st));
-        RMX_TM_END(c, kTkRowsInv);
+        rc = launch(c, kTkRowsAnchor, k.rows_anchor, dim3((unsigned)((L1 / rpw) * (B - 1)), (unsigned)wc), dim3(kGThreads), rlds, c->g_prod,
+                    c->g_tw2, L1, l1, L, c->g_lo_bits, c->g_thi, c->g_tlo, 1.0f, c->g_spec, spec_j, n_pairs, B);
+    } else {
+        rc = launch(c, kTkRowsInv, k.rows_inv, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), rlds, c->g_prod, c->g_tw2, l2, L1,
+                    l1, L, c->g_lo_bits, c->g_thi, c->g_tlo, 1.0f, rows, c->g_spec, spec_j, c->g_pairs, n_pairs, B, tpr);
     }
+    if (rc != RMX_OK) return rc;
     // integrated call: the column pass sums the |r|^2 of a group's K product slots tile by tile and leaves one tile record
     // and halo per (group, pair) slot; g_final then reduces those slots as it reduces a window's (the bounds are per group:
     // slot -> group w0 / K + slot / P).  Otherwise K = 1: slot -> window w0 + slot / P, pair slot % P.
     const int oslots = slots / call.integ;
-    LagBounds a_lb = call.lb;
-    a_lb.w0 = w0 / call.integ;
-    a_lb.n_pairs = n_pairs;
-    {
-        const float2 *a_in = c->g_prod, *a_tw = c->g_tw1;
-        int a_l1 = l1, a_l2 = l2;
-        GTile* a_rec = c->g_rec;
-        float* a_halo = c->g_halo;
-        Integrate a_ig{call.integ};
-        void* args[] = {&a_in, &a_tw, &a_l1, &a_l2, &a_rec, &a_halo, &a_lb, &a_ig};   // (each kernel reads its own leading part)
-        const void* fn = call.integrated() ? c->g_cols_inv_int_fn : call.bounded() ? c->g_cols_inv_lb_fn : c->g_cols_inv_fn;
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(fn, dim3(ntiles, oslots), dim3(cthr), args, clds, st));
-        RMX_TM_END(c, kTkColsInv);
-    }
-    RMX_TM_BEGIN(c);
-    auto reduce = [&](auto kern, auto... lb) {
-        hipLaunchKernelGGL(kern, dim3(oslots), dim3(64), 0, st, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, oslots,
-                           a_lb.w0 * n_pairs, out_scale, d_lag, d_frac, d_peak, lb...);
+    LagBounds lb = call.lb;
+    lb.w0 = w0 / call.integ;
+    lb.n_pairs = n_pairs;
+    auto cols = [&](auto kern, auto... tail) {
+        return launch(c, kTkColsInv, kern, dim3(ntiles, oslots), dim3(cthr), clds, c->g_prod, c->g_tw1, l1, l2, c->g_rec, c->g_halo, tail...);
     };
-    if (call.bounded()) reduce(g_final<LagBounds>, a_lb); else reduce(g_final<>);   // (an integrated call always carries bounds)
-    RMX_HIP(c, hipGetLastError());
-    RMX_TM_END(c, kTkFinal);
-    return RMX_OK;
+    rc = call.integrated() ? cols(k.cols_inv_int, lb, Integrate{call.integ}) : call.bounded() ? cols(k.cols_inv_lb, lb) : cols(k.cols_inv);
+    if (rc != RMX_OK) return rc;
+    auto reduce = [&](auto kern, auto... tail) {
+        return launch(c, kTkFinal, kern, dim3(oslots), dim3(64), 0, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, oslots, lb.w0 * n_pairs,
+                      out_scale, d_lag, d_frac, d_peak, tail...);
+    };
+    return call.bounded() ? reduce(g_final<LagBounds>, lb) : reduce(g_final<>);   // (an integrated call always carries bounds)
 }
 
 // N = 4096, unfused path: forward spectra of windows [w0, w0 + wc) into d_spec (rot == nullptr) or, de-rotated by
@@ -1836,23 +961,17 @@ static int fwd4096(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, 
         }
     }
     float4* dst = rot ? c->d_spec_r : c->d_spec;
-    RMX_TM_BEGIN(c);
-    auto launch = [&](auto kern, const float2* a_rot, int a_wrap, auto... wt) {
-        hipLaunchKernelGGL(kern, dim3(n_items), dim3(kThreads), kLdsBytes, c->stream, d_iq, dst, c->d_tw1, c->d_tw2, first_item,
-                           1.0f, a_rot, a_wrap, wt...);
-    };
-    with_u8(u8, [&](auto U) {
+    return with_u8(u8, [&](auto U) {
         constexpr bool U8 = decltype(U)::value;
-        if (call.wt.band) {   // weighted call (never with rot): the stored bins carry the TW1 scale
-            XWeight a_wt = call.wt;
-            a_wt.unit = (float)kTw1Scale;
-            launch(k_fwd<U8, XWeight>, nullptr, 0, a_wt);
-        } else
-            launch(k_fwd<U8>, rot, wrap);
+        auto go = [&](auto kern, const float2* a_rot, int a_wrap, auto... wt) {
+            return launch(c, kTkFwd4096, kern, dim3(n_items), dim3(kThreads), kLdsBytes, d_iq, dst, c->d_tw1, c->d_tw2, first_item, 1.0f, a_rot,
+                          a_wrap, wt...);
+        };
+        if (!call.wt.band) return go(k_fwd<U8>, rot, wrap);
+        XWeight wt = call.wt;   // weighted call (never with rot): the stored bins carry the TW1 scale
+        wt.unit = (float)kTw1Scale;
+        return go(k_fwd<U8, XWeight>, nullptr, 0, wt);
     });
-    RMX_HIP(c, hipGetLastError());
-    RMX_TM_END(c, kTkFwd4096);
-    return RMX_OK;
 }
 static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, float out_scale,
                      bool use_rot, int n_bins = 1) {
@@ -1863,30 +982,22 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
     const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
     // the streaming and the resident kernel (which keeps one unused int argument), each with or without its trailing structs
     auto str = [&](auto kern, int windows, int xmap, long first, int wrap, auto... tail) {
-        hipLaunchKernelGGL(kern, dim3(windows * n_parts), dim3(kThreads), kLdsBytes, c->stream, (const float4*)c->d_spec, spec_j,
-                           c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xmap, first, out_scale,
-                           d_lag, d_frac, d_peak, wrap, tail...);
+        return launch(c, kTkPair4096, kern, dim3(windows * n_parts), dim3(kThreads), kLdsBytes, c->d_spec, spec_j, c->d_tw1, c->d_tw2,
+                      c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xmap, first, out_scale, d_lag, d_frac, d_peak, wrap, tail...);
     };
     auto res = [&](auto kern, auto... lb) {
-        hipLaunchKernelGGL(kern, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->stream, (const float4*)c->d_spec, spec_j,
-                           c->d_tw1, c->d_tw2, c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, (long)w0,
-                           out_scale, d_lag, d_frac, d_peak, 0, i_wrap, lb...);
+        return launch(c, kTkPair4096, kern, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->d_spec, spec_j, c->d_tw1, c->d_tw2,
+                      c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, (long)w0, out_scale, d_lag, d_frac, d_peak, 0, i_wrap,
+                      lb...);
     };
-    RMX_TM_BEGIN(c);
     if (call.integrated()) {
         // always the streaming kernel's integrating instantiation, one work item per (group, pair); w0 and wc are whole
         // groups, the bounds per group
         const int gc = wc / call.integ;
-        str(k_pair_str<LagBounds, Integrate>, gc, (gc % 8 == 0) ? 1 : 0, (long)(w0 / call.integ), 0, call.lb, Integrate{call.integ});
-    } else if (c->resident) {
-        if (call.bounded()) res(k_pair_res<LagBounds>, call.lb); else res(k_pair_res<>);
-    } else {
-        if (call.bounded()) str(k_pair_str<LagBounds>, wc, xcd_map, (long)w0, i_wrap, call.lb);
-        else str(k_pair_str<>, wc, xcd_map, (long)w0, i_wrap);
+        return str(k_pair_str<LagBounds, Integrate>, gc, (gc % 8 == 0) ? 1 : 0, (long)(w0 / call.integ), 0, call.lb, Integrate{call.integ});
     }
-    RMX_HIP(c, hipGetLastError());
-    RMX_TM_END(c, kTkPair4096);
-    return RMX_OK;
+    if (c->resident) return call.bounded() ? res(k_pair_res<LagBounds>, call.lb) : res(k_pair_res<>);
+    return call.bounded() ? str(k_pair_str<LagBounds>, wc, xcd_map, (long)w0, i_wrap, call.lb) : str(k_pair_str<>, wc, xcd_map, (long)w0, i_wrap);
 }
 static_assert(kL == 1 << 13, "spec_view and out_scale4096 say log2 kL = 13");
 static float out_scale4096() {
@@ -1918,7 +1029,7 @@ static host::RouteCaps route_caps(const rmx_ctx* c) {
     if (!c->generic) return k;
     k.logL = c->g_logL;  k.logL1 = c->g_logL1;  k.logL2 = c->g_logL2;  k.small_maxl = kGenSmallMaxL;
     k.g_chunk = c->g_chunk;  k.wfused = c->g_wfused;  k.wscr = c->g_wscr;  k.wscr_always = c->g_wscr_always;
-    k.ws_upw = c->g_ws_upw;  k.ws_grid = c->g_ws_grid;  k.k8 = c->g_k8;  k.k16 = c->g_k16;
+    k.ws_upw = c->gk.ws_upw;  k.ws_grid = c->g_ws_grid;  k.k8 = c->g_k8;  k.k16 = c->g_k16;
     if (c->g_k16 == 1) k.k16_min_windows = c->knobs.get_or("k16_min_windows", 0);
     k.g_fused = c->g_fused;  k.g_fused_always = c->g_fused_always;
     k.max_pairs8 = k8::kMaxPairs8;  k.max_pairs16 = k16::kMaxPairs16;  k.integ_max_per_thread = kIntegMaxPerThread;
@@ -1957,13 +1068,11 @@ static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_
         const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
         const int items = wc * B;
         const unsigned fgrid = (unsigned)(items < c->n_cus ? items : c->n_cus);
-        RMX_TM_BEGIN(c);
-        with_u8(u8, [&](auto U) {
-            hipLaunchKernelGGL(k16::k16_fwd<decltype(U)::value>, dim3(fgrid), dim3(kThreads), k16::kLdsFwdBytes, c->stream, d_iq,
-                               c->g_ws_scratch, c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, (long)w0 * B, items);
+        int rc = with_u8(u8, [&](auto U) {
+            return launch(c, kTkFwd16k, k16::k16_fwd<decltype(U)::value>, dim3(fgrid), dim3(kThreads), k16::kLdsFwdBytes, d_iq, c->g_ws_scratch,
+                          c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, (long)w0 * B, items);
         });
-        RMX_HIP(c, hipGetLastError());
-        RMX_TM_END(c, kTkFwd16k);
+        if (rc != RMX_OK) return rc;
         // XCD-aware item order (the pairs of a window on one XCD) unless the windows do not spread evenly over eight XCDs
         // and are few: 9 windows would give XCD 0 two windows' work and leave the batch waiting for it
         const int flat = (wc < 32 && wc % 8 != 0) || c->n_cus < 8 ? 1 : 0;
@@ -1972,21 +1081,19 @@ static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_
         if (per_xcd < S) S = per_xcd;
         long pgrid = 8 * S;
         if (flat) pgrid = (long)wc * n_pairs < c->n_cus ? (long)wc * n_pairs : c->n_cus;
-        RMX_TM_BEGIN(c);
         auto pairs = [&](auto kern, auto... lb) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)pgrid), dim3(kThreads), k16::kLdsPairBytes, c->stream, c->g_ws_scratch,
-                               c->g_k16_tw1, c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, B, prs, n_pairs, (long)w0 * n_pairs, wc, flat,
-                               out_scale, d_lag, d_frac, d_peak, lb...);
+            return launch(c, kTkPairs16k, kern, dim3((unsigned)pgrid), dim3(kThreads), k16::kLdsPairBytes, c->g_ws_scratch, c->g_k16_tw1,
+                          c->g_k16_gq, c->g_k16_tw2, c->g_k16_tws, B, prs, n_pairs, (long)w0 * n_pairs, wc, flat, out_scale, d_lag, d_frac,
+                          d_peak, lb...);
         };
         if (call.bounded()) {   // the same kernel with the lag windows (lb.w0: window 0 of this launch)
-            LagBounds a_lb = call.lb;
-            a_lb.w0 = w0;
-            a_lb.n_pairs = n_pairs;
-            pairs(k16::k16_pairs<LagBounds>, a_lb);
+            LagBounds lb = call.lb;
+            lb.w0 = w0;
+            lb.n_pairs = n_pairs;
+            rc = pairs(k16::k16_pairs<LagBounds>, lb);
         } else
-            pairs(k16::k16_pairs<>);
-        RMX_HIP(c, hipGetLastError());
-        RMX_TM_END(c, kTkPairs16k);
+            rc = pairs(k16::k16_pairs<>);
+        if (rc != RMX_OK) return rc;
     }
     return RMX_OK;
 }
@@ -2006,6 +1113,7 @@ static int route_refusal(rmx_ctx* c, const host::RoutePlan& plan, const host::Ro
 static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps, const host::RouteCall& rq, host::RoutePlan plan,
                          const void* d_iq, int* d_lag, float* d_frac, float* d_peak, bool u8) {
     using namespace host;
+    const GenericKernels& k = c->gk;
     const int n_pairs = rq.n_pairs, logL = c->g_logL, hs = logL / 2;
     // device buffers on first need; a failed allocation halves g_chunk, and the plan follows (the route does not depend on it)
     auto ensure = [&](bool need_spec, bool need_pairbufs) -> int {
@@ -2020,53 +1128,40 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps
     if (rc != RMX_OK) return rc;
     if (per_transform) return run_chunks(c, call, caps, d_iq, 0, rq.n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
     if (plan.route == kRouteK16) return k16_batch(c, call, d_iq, rq.n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
-    const void* a_iq = d_iq;
-    long a_nw = plan.n_head, a_first = 0;
-    float a_fs = std::ldexp(1.0f, -hs), a_os = std::ldexp(1.0f, -(logL - 2 * hs));
-    const gen::GPair* a_pairs = c->g_pairs;
-    int a_nb = c->n_buoys, a_np = n_pairs;
+    const long n_head = plan.n_head;
+    const float fwd_scale = std::ldexp(1.0f, -hs), out_scale = std::ldexp(1.0f, -(logL - 2 * hs));
     if (plan.route == kRouteWinFused) {
         const int upw = gen::kGThreads / ((1 << logL) >> 4), def = rq.all_pairs ? 1 : 0;
-        const float2* a_tw = c->g_tw;
-        void* args[] = {&a_iq, &a_tw, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
-        RMX_TM_BEGIN(c);
-        RMX_HIP(c, hipLaunchKernel(c->g_wf_fn[def][u8 ? 1 : 0], dim3((unsigned)((rq.n_windows + upw - 1) / upw)), dim3(gen::kGThreads), args,
-                                   c->g_wf_lds[def], c->stream));
-        RMX_TM_END(c, kTkWindow);
-        return RMX_OK;
+        return launch(c, kTkWindow, k.wf[def][u8 ? 1 : 0], dim3((unsigned)((rq.n_windows + upw - 1) / upw)), dim3(gen::kGThreads), k.wf_lds[def],
+                      d_iq, c->g_tw, n_head, 0L, fwd_scale, out_scale, c->g_pairs, n_pairs, d_lag, d_frac, d_peak);
     }
     // g_win_scr*, g_win_eo15, k_win8kl: persistent workgroups over the ctx's scratch; the full rounds here, the planned
     // partial round behind them through the per-transform kernels on the same stream
-    float4* a_scr = c->g_ws_scratch;
-    const float2 *a_tw = c->g_tw_win, *a_twl = c->g_tw_l;
-    long grid = ((long)rq.n_windows + c->g_ws_upw - 1) / c->g_ws_upw;
+    long grid = ((long)rq.n_windows + k.ws_upw - 1) / k.ws_upw;
     if (grid > c->g_ws_grid) grid = c->g_ws_grid;
-    RMX_TM_BEGIN(c);
     if (plan.route == kRouteKWin8) {            // N = 8192 on k_win's network (kwin8k.hpp)
-        const float out_scale = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 14);
+        const float out_scale8 = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 14);
         const k8::Pair2* prs = rq.all_pairs ? nullptr : reinterpret_cast<const k8::Pair2*>(c->g_pairs);
         const int stag = (int)c->knobs.get_or("stag", 1);
-        auto launch = [&](auto kern, size_t lds, auto... lb) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, c->stream, d_iq, c->g_ws_scratch, c->g_k8_tw1,
-                               c->g_k8_tw2, c->n_buoys, prs, n_pairs, 0L, out_scale, d_lag, d_frac, d_peak, plan.n_head, stag, lb...);
-        };
-        with_u8(u8, [&](auto U) {
+        rc = with_u8(u8, [&](auto U) {
             constexpr bool U8 = decltype(U)::value;
+            auto go = [&](auto kern, size_t lds, auto... lb) {
+                return launch(c, kTkWindow, kern, dim3((unsigned)grid), dim3(kThreads), lds, d_iq, c->g_ws_scratch, c->g_k8_tw1, c->g_k8_tw2,
+                              c->n_buoys, prs, n_pairs, 0L, out_scale8, d_lag, d_frac, d_peak, plan.n_head, stag, lb...);
+            };
 #ifdef RMX_EXPERIMENTS
-            if (c->g_k8_kind == 2) launch(k8::k_win8k<U8>, k8::kLds8Bytes);
-            else
+            if (c->g_k8_kind == 2) return go(k8::k_win8k<U8>, k8::kLds8Bytes);
 #endif
-            if (call.bounded()) launch(k8::k_win8kl<U8, LagBounds>, k8::kLdsLBytes, call.lb); else launch(k8::k_win8kl<U8>, k8::kLdsLBytes);
+            return call.bounded() ? go(k8::k_win8kl<U8, LagBounds>, k8::kLdsLBytes, call.lb) : go(k8::k_win8kl<U8>, k8::kLdsLBytes);
         });
-        RMX_HIP(c, hipGetLastError());
-    } else {                                    // (g_win_eo15: one more table)
-        void* args15[] = {&a_iq, &a_scr, &a_tw, &a_twl, &a_nb, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
-        void* args[] = {&a_iq, &a_scr, &a_tw, &a_nb, &a_nw, &a_first, &a_fs, &a_os, &a_pairs, &a_np, &d_lag, &d_frac, &d_peak};
-        RMX_HIP(c, hipLaunchKernel(c->g_ws_fn[u8 ? 1 : 0], dim3((unsigned)grid), dim3(c->g_ws_thr), plan.route == kRouteWinEo15 ? args15 : args,
-                                   c->g_ws_lds, c->stream));
+    } else if (plan.route == kRouteWinEo15) {   // (g_win_eo15: one more table)
+        rc = launch(c, kTkWindow, k.ws15[u8 ? 1 : 0], dim3((unsigned)grid), dim3(k.ws_thr), k.ws_lds, d_iq, c->g_ws_scratch, c->g_tw_win,
+                    c->g_tw_l, c->n_buoys, n_head, 0L, fwd_scale, out_scale, c->g_pairs, n_pairs, d_lag, d_frac, d_peak);
+    } else {
+        rc = launch(c, kTkWindow, k.ws[u8 ? 1 : 0], dim3((unsigned)grid), dim3(k.ws_thr), k.ws_lds, d_iq, c->g_ws_scratch, c->g_tw_win,
+                    c->n_buoys, n_head, 0L, fwd_scale, out_scale, c->g_pairs, n_pairs, d_lag, d_frac, d_peak);
     }
-    RMX_TM_END(c, kTkWindow);
-    if (!plan.n_tail) return RMX_OK;
+    if (rc != RMX_OK || !plan.n_tail) return rc;
     rc = ensure(true, true);
     return rc != RMX_OK ? rc : run_chunks(c, call, caps, d_iq, plan.n_head, plan.n_tail, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
 }
@@ -2168,29 +1263,20 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
             RMX_HIP(c, hipMemcpy(c->d_tb8, tb.data(), tb.size() * sizeof(float2), hipMemcpyHostToDevice));
             RMX_HIP(c, hipMemcpy(c->d_tc8, tc.data(), tc.size() * sizeof(float2), hipMemcpyHostToDevice));
             c->scratch_bytes += t1.size() * sizeof(float4) + (tb.size() + tc.size()) * sizeof(float2);
-            RMX_HIP(c, hipFuncSetAttribute((const void*)w8::k_win8<false>, hipFuncAttributeMaxDynamicSharedMemorySize, w8::kLdsWin8Bytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)w8::k_win8<true>, hipFuncAttributeMaxDynamicSharedMemorySize, w8::kLdsWin8Bytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k_winp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, pk::kLdsWinpBytes));
-            RMX_HIP(c, hipFuncSetAttribute((const void*)k_winp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, pk::kLdsWinpBytes));
+            int rc_x = allow_lds(c, w8::kLdsWin8Bytes, w8::k_win8<false>, w8::k_win8<true>);
+            if (rc_x == RMX_OK) rc_x = allow_lds(c, pk::kLdsWinpBytes, k_winp<false>, k_winp<true>);
+            if (rc_x != RMX_OK) return rc_x;
             c->pk = (int)c->knobs.get_or("pk", 0);
             c->win8 = (int)c->knobs.get_or("win8", 0);
         }
 #endif
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        // the weighted instantiations (rmx_xcorr_batch_weighted)
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<false, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_fwd<true, XWeight>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_res<>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsResBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_win<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_win<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_str<>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        // the bounded instantiations (rmx_xcorr_batch_bounded)
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_res<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsResBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_win_lb<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_win_lb<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWinBytes));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)k_pair_str<LagBounds>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        return RMX_OK;
+        // every instantiation of the N = 4096 kernels: plain, weighted (rmx_xcorr_batch_weighted: k_fwd) and bounded
+        // (rmx_xcorr_batch_bounded: the peak-searching ones)
+        int rc_l = allow_lds(c, kLdsBytes, k_fwd<false>, k_fwd<true>, k_fwd<false, XWeight>, k_fwd<true, XWeight>, k_pair_str<>,
+                             k_pair_str<LagBounds>);
+        if (rc_l == RMX_OK) rc_l = allow_lds(c, kLdsResBytes, k_pair_res<>, k_pair_res<LagBounds>);
+        if (rc_l == RMX_OK) rc_l = allow_lds(c, kLdsWinBytes, k_win<false>, k_win<true>, k_win_lb<false>, k_win_lb<true>);
+        return rc_l;
     };
     rc = init();
     if (rc != RMX_OK) return bail(rc);
@@ -2230,7 +1316,7 @@ void rmx_destroy(rmx_ctx* c) {
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->rf_pairs) (void)hipFree(c->rf_pairs);
     if (c->d_quality) (void)hipFree(c->d_quality);
-    for (rmx::DevStage* s : {&c->lb_stage, &c->band_stage}) {
+    for (DevStage* s : {&c->lb_stage, &c->band_stage}) {
         if (s->d) (void)hipFree(s->d);
         if (s->h) (void)hipHostFree(s->h);
         if (s->ev) (void)hipEventDestroy(s->ev);
@@ -2561,28 +1647,23 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
             }
             // one persistent workgroup per CU (the kernel's LDS footprint allows exactly one)
             const int wgrid = sc < c->n_cus ? sc : c->n_cus;
-            RMX_TM_BEGIN(c);
-            with_u8(u8, [&](auto U) {
+            rc = with_u8(u8, [&](auto U) {
                 constexpr bool U8 = decltype(U)::value;
-                auto launch = [&](auto kern, auto... lb) {
-                    hipLaunchKernelGGL(kern, dim3(wgrid), dim3(kThreads), kLdsWinBytes, c->stream, d_iq, c->d_spec, c->d_tw1,
-                                       c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, 0, c->stag, lb...);
+                auto go = [&](auto kern, auto... lb) {
+                    return launch(c, kTkPair4096, kern, dim3(wgrid), dim3(kThreads), kLdsWinBytes, d_iq, c->d_spec, c->d_tw1, c->d_tw2,
+                                  c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, 0, c->stag, lb...);
                 };
 #ifdef RMX_EXPERIMENTS
                 if (c->win8)
-                    hipLaunchKernelGGL(w8::k_win8<U8>, dim3(wgrid), dim3(w8::kT8), w8::kLdsWin8Bytes, c->stream, d_iq, c->d_spec,
-                                       c->d_tw1_8, c->d_tb8, c->d_tc8, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc,
-                                       c->stag);
-                else if (c->pk)
-                    hipLaunchKernelGGL(k_winp<U8>, dim3(wgrid), dim3(kThreads), pk::kLdsWinpBytes, c->stream, d_iq, c->d_spec,
-                                       c->d_tw1, c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc);
-                else
+                    return launch(c, kTkPair4096, w8::k_win8<U8>, dim3(wgrid), dim3(w8::kT8), w8::kLdsWin8Bytes, d_iq, c->d_spec, c->d_tw1_8,
+                                  c->d_tb8, c->d_tc8, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, c->stag);
+                if (c->pk)
+                    return launch(c, kTkPair4096, k_winp<U8>, dim3(wgrid), dim3(kThreads), pk::kLdsWinpBytes, d_iq, c->d_spec, c->d_tw1,
+                                  c->d_tw2, c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc);
 #endif
-                if (call.bounded()) launch(k_win_lb<U8>, call.lb);   // k_win's bounded instantiation
-                else launch(k_win<U8>);
+                return call.bounded() ? go(k_win_lb<U8>, call.lb) : go(k_win<U8>);   // (k_win_lb: k_win's bounded instantiation)
             });
-            RMX_HIP(c, hipGetLastError());
-            RMX_TM_END(c, kTkPair4096);
+            if (rc != RMX_OK) return rc;
         }
         if (wtail) {
             rc = run_chunks(c, call, caps, d_iq, w0 + wf, wtail, wtail, n_pairs, d_lag, d_frac, d_peak, u8);
@@ -2866,13 +1947,9 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
         rc = fwd4096(c, call, d_iq, 0, n_windows, u8, nullptr);
         if (rc == RMX_OK) rc = fwd4096(c, call, d_iq, 0, n_windows, u8, c->caf_rot, n_dopplers);
         if (rc == RMX_OK) rc = pairs4096(c, call, 0, n_windows, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, osc, true, n_dopplers);
-        if (rc == RMX_OK) rc = tm_begin(c);
-        if (rc == RMX_OK) {
-            hipLaunchKernelGGL(k_caf_select_all, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, c->stream, n_dopplers,
-                               (long)out_elems, c->caf_lag, c->caf_frac, c->caf_peak, b_dop, b_lag, b_frac, b_peak);
-            if (hipGetLastError() != hipSuccess) rc = fail(c, RMX_E_HIP, "k_caf_select_all launch failed");
-        }
-        if (rc == RMX_OK) rc = tm_end(c, kTkCafSelect);
+        if (rc == RMX_OK)
+            rc = launch(c, kTkCafSelect, k_caf_select_all, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, n_dopplers, (long)out_elems,
+                        c->caf_lag, c->caf_frac, c->caf_peak, b_dop, b_lag, b_frac, b_peak);
     }
     for (int w0 = 0; !batch_bins && w0 < n_windows && rc == RMX_OK; w0 += chunk) {
         const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
@@ -2884,12 +1961,8 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
             rc = sv.pairs(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true, false);
             if (rc != RMX_OK) break;
             const long first = (long)w0 * n_pairs, cnt = (long)wc * n_pairs;
-            rc = tm_begin(c);
-            if (rc != RMX_OK) break;
-            hipLaunchKernelGGL(k_caf_select, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, d, first, cnt,
-                               c->caf_lag, c->caf_frac, c->caf_peak, b_dop, b_lag, b_frac, b_peak);
-            if (hipGetLastError() != hipSuccess) rc = fail(c, RMX_E_HIP, "k_caf_select launch failed");
-            if (rc == RMX_OK) rc = tm_end(c, kTkCafSelect);
+            rc = launch(c, kTkCafSelect, k_caf_select, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, d, first, cnt, c->caf_lag, c->caf_frac,
+                        c->caf_peak, b_dop, b_lag, b_frac, b_peak);
         }
     }
     if (rc != RMX_OK) return rc;
@@ -2969,9 +2042,9 @@ int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32
         d_cost = d_pos + (size_t)n_windows * 3;
         d_it = (int*)(d_cost + n_windows);
     }
-    hipLaunchKernelGGL(rmx::k_solve, dim3((n_windows + 63) / 64), dim3(64), 0, c->stream, c->sv_buoys, n_buoys, c->sv_pairs,
-                       n_pairs, d_li, d_lf, d_wg, 299792458.0 / sample_rate_hz, n_windows, max_iter, d_pos, d_cost, d_it);
-    RMX_HIP(c, hipGetLastError());
+    const int rc_k = launch(c, kTkNone, k_solve, dim3((n_windows + 63) / 64), dim3(64), 0, c->sv_buoys, n_buoys, c->sv_pairs, n_pairs, d_li, d_lf,
+                            d_wg, 299792458.0 / sample_rate_hz, n_windows, max_iter, d_pos, d_cost, d_it);
+    if (rc_k != RMX_OK) return rc_k;
     if (!out_dev) {
         RMX_HIP(c, hipMemcpyAsync(pos, d_pos, (size_t)n_windows * 3 * 8, hipMemcpyDeviceToHost, c->stream));
         RMX_HIP(c, hipMemcpyAsync(cost, d_cost, (size_t)n_windows * 8, hipMemcpyDeviceToHost, c->stream));
@@ -3003,10 +2076,9 @@ int rmx_detect_batch(rmx_ctx* c, const void* iq, int n_windows, int n_samples, f
         RMX_HIP(c, hipMalloc((void**)&c->dt_tw, t.size() * sizeof(float2)));
         RMX_HIP(c, hipMemcpy(c->dt_tw, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
         c->dt_logn = logn;
-        RMX_HIP(c, hipFuncSetAttribute((const void*)rmx::det::d_fft_db<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rmx::gen::lp(16384) * 8));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)rmx::det::d_fft_db<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rmx::gen::lp(16384) * 8));
-        RMX_HIP(c, hipFuncSetAttribute((const void*)rmx::det::d_peaks, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       16384 * 6 + 8192));
+        int rc_l = allow_lds(c, (size_t)rmx::gen::lp(16384) * 8, det::d_fft_db<false>, det::d_fft_db<true>);
+        if (rc_l == RMX_OK) rc_l = allow_lds(c, 16384 * 6 + 8192, det::d_peaks);
+        if (rc_l != RMX_OK) return rc_l;
     }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
     auto grow = [&](void** p, size_t* have, size_t need) -> int {
@@ -3039,21 +2111,19 @@ int rmx_detect_batch(rmx_ctx* c, const void* iq, int n_windows, int n_samples, f
         d_count = (int*)(b + per * 16); d_floor = (float*)(b + per * 16 + (size_t)n_windows * 4);
     }
     const int fthr = N >= 4096 ? 1024 : (N >= 1024 ? 256 : 64);
-    if (u8)
-        hipLaunchKernelGGL(rmx::det::d_fft_db<true>, dim3(n_windows), dim3(fthr), (size_t)rmx::gen::lp(N) * 8, c->stream, d_iq, c->dt_pdb,
-                           c->dt_tw, logn);
-    else
-        hipLaunchKernelGGL(rmx::det::d_fft_db<false>, dim3(n_windows), dim3(fthr), (size_t)rmx::gen::lp(N) * 8, c->stream, d_iq, c->dt_pdb,
-                           c->dt_tw, logn);
-    RMX_HIP(c, hipGetLastError());
+    rc = with_u8(u8, [&](auto U) {
+        return launch(c, kTkNone, det::d_fft_db<decltype(U)::value>, dim3(n_windows), dim3(fthr), (size_t)rmx::gen::lp(N) * 8, d_iq, c->dt_pdb,
+                      c->dt_tw, logn);
+    });
+    if (rc != RMX_OK) return rc;
     const int pthr = N >= 4096 ? 1024 : 256;
     const size_t plds = (size_t)N * 4 + N + (size_t)N + 256 * 4 + 8 * 4 + (size_t)pthr * 4;
     // a distance >= N keeps the single highest candidate, as N does: clamped, so that the kernel's neighbour span
     // 2 (distance - 1) + 1 stays in int range and each candidate scans at most 2 N - 1 bins
     const int dist = distance < N ? distance : N;
-    hipLaunchKernelGGL(rmx::det::d_peaks, dim3(n_windows), dim3(pthr), plds, c->stream, c->dt_pdb, logn, threshold_db, dist,
-                       dc_exclude_bins, min_confidence, max_peaks, d_count, d_bin, d_pw, d_snr, d_conf, d_floor);
-    RMX_HIP(c, hipGetLastError());
+    rc = launch(c, kTkNone, det::d_peaks, dim3(n_windows), dim3(pthr), plds, c->dt_pdb, logn, threshold_db, dist, dc_exclude_bins,
+                min_confidence, max_peaks, d_count, d_bin, d_pw, d_snr, d_conf, d_floor);
+    if (rc != RMX_OK) return rc;
     if (!out_dev) {
         RMX_HIP(c, hipMemcpyAsync(bin, d_bin, per * 4, hipMemcpyDeviceToHost, c->stream));
         RMX_HIP(c, hipMemcpyAsync(power_db, d_pw, per * 4, hipMemcpyDeviceToHost, c->stream));

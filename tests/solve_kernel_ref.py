@@ -1,4 +1,4 @@
-"""Kernel-order restatement of k_solve (radio-mapper_amd/csrc/rmx_hip.hip), TEST INFRASTRUCTURE ONLY.
+"""Kernel-order restatement of k_solve (radio-mapper_amd/csrc/solve_path.hpp), TEST INFRASTRUCTURE ONLY.
 
 oracle/solve_ref.py states the Levenberg-Marquardt rule of rmx_solve_batch with numpy's own sums (`@`, np.linalg.solve,
 mean), so it agrees with the kernel only where the walk is well conditioned.  This file follows the kernel operation by

@@ -1,4 +1,4 @@
-// winpk.hpp -- k_winp: the fused window kernel k_win (rmx_hip.hip) with its butterfly arithmetic on packed
+// winpk.hpp -- k_winp: the fused window kernel k_win (kwin.hpp) with its butterfly arithmetic on packed
 // fp32 (fft_pk.hpp).  Same decomposition, schedule, LDS images, spectrum scratch and peak search: one
 // persistent 512-thread workgroup per CU, thread t = 2u + p holds 16 complex points of sub-transform p,
 // three radix-16 passes, one workgroup barrier per transform.  Only the instruction selection differs:
@@ -9,6 +9,7 @@
 
 #include <type_traits>
 
+#include "../../radio-mapper_amd/csrc/kwin.hpp"
 #include "fft_pk.hpp"
 
 namespace rmx {
@@ -17,7 +18,7 @@ namespace pk {
 using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
 using u32x2 = unsigned int __attribute__((ext_vector_type(2)));
 
-// LDS carve: identical to k_win's (rmx_hip.hip: kLdsWin*)
+// LDS carve: identical to k_win's (kwin.hpp: kLdsWin*)
 constexpr int kPImg = kXchgF2 * 8;                                   // 69632 each, two of them
 constexpr int kPTw2 = 2 * kPImg;
 constexpr int kPSlots = 8;
@@ -28,8 +29,7 @@ constexpr int kPOidx = kPRed + kPSlots * 8 * 16;                    // [slots] i
 constexpr int kLdsWinpBytes = kPOidx + kPSlots * 4;
 static_assert(kLdsWinpBytes <= 160 * 1024, "k_winp LDS");
 
-// resolve_batch / k_to_owner / load_tw2_to_lds_grouped are k_win's (declared in rmx_hip.hip before this
-// header is included)
+// resolve_batch / k_to_owner / load_tw2_to_lds_grouped are k_win's (kwin.hpp)
 template <bool U8, class ResolveFn>
 __device__ __forceinline__ void winp_body(const void* __restrict__ iq_v, float4* __restrict__ spec,
                                           const float4* __restrict__ tw1_g, const float2* __restrict__ tw2_g,
@@ -342,4 +342,19 @@ __device__ __forceinline__ void winp_body(const void* __restrict__ iq_v, float4*
 }
 
 }  // namespace pk
+
+// k_win on packed fp32 (winpk.hpp): same protocol, same resolve routine
+template <bool U8>
+__global__ __launch_bounds__(kThreads, 2) void k_winp(const void* __restrict__ iq_v, float4* __restrict__ spec,
+                                                      const float4* __restrict__ tw1_g,
+                                                      const float2* __restrict__ tw2_g, int n_buoys,
+                                                      long first_window, float out_scale, int* __restrict__ lag_int,
+                                                      float* __restrict__ lag_frac, float* __restrict__ peak, int n_win) {
+    pk::winp_body<U8>(iq_v, spec, tw1_g, tw2_g, n_buoys, first_window, out_scale, lag_int, lag_frac, peak, n_win,
+                      [](int lane, const float4* red, const float* halo, const int* oidx, int first, int cnt, long obase,
+                         float osc, int* li, float* lf, float* pk_) __attribute__((always_inline)) {
+                          resolve_batch(lane, red, halo, oidx, first, cnt, obase, osc, li, lf, pk_);
+                      });
+}
+
 }  // namespace rmx
