@@ -69,8 +69,11 @@ __device__ __forceinline__ void xsync() {
 // W_{2^b}^(l k) (l = element index inside the sub-block) and stores it at j + bitrev_M(k) q.  LOGT > 0: 2^LOGT
 // interleaved transforms at once (element e of transform c at x[(e << LOGT) | c]: a tile of columns of a
 // row-major matrix; consecutive threads take consecutive columns, so LDS accesses stay conflict free).
-// De-rotation of a window sample by a Doppler phasor (rmx_caf_batch): separately rounded products and sums, as
-// numpy multiplies complex64 arrays (no contraction), so that the rotated window equals the oracle's bit for bit.
+// De-rotation of a window sample by a Doppler phasor (rmx_caf_batch): four separately rounded products, one rounded
+// difference and one rounded sum (no contraction), whatever the compiler would fuse.  That pins the rotated window bit
+// for bit (tests/caf_ref.py: rot_mul restates it); it is NOT always the oracle's own rounding: numpy's complex64 array
+// product fuses one product of each component into the sum on CPUs with FMA, so the oracle's rotated window may differ
+// from this one in the last bit, which the parity bars (1e-5) absorb.
 __device__ __forceinline__ float2 rot_mul(float2 v, float2 r) {
 #pragma clang fp contract(off)
     const float re = v.x * r.x - v.y * r.y;

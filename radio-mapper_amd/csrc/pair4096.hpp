@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_fwd(const void* __restrict__ iq
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = x[q * 256 + u];
     }
-    if (rot) {   // rmx_caf_batch: the window de-rotated by this Doppler hypothesis (rounded as numpy rounds it)
+    if (rot) {   // rmx_caf_batch: the window de-rotated by this Doppler hypothesis (gen::rot_mul: nothing fused)
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = gen::rot_mul(v[q], rot[q * 256 + u]);
     }
