@@ -33,6 +33,10 @@
  *               differed by 3.3e-5.  The rule -- within 1e-5, or within four such
  *               one-ulp bounds, nothing else -- is pinned in tests/test_gpu_parity.py::test_flat_peak_rule_on_short_noisy_windows
  *               and used by tests/soak_parity.py.)
+ *               (Far from lag 0 that scaled bar says little -- 0.16 samples at lag 16000 --, so
+ *               tests/test_gpu_far_lags.py holds d ITSELF to 1e-5 absolute, or the flat-peak bound, against a float64
+ *               reference with the peak placed anywhere in +-(N-1), seams of every kernel's output order included, on
+ *               every route: worst 4.0e-7 on an MI355X, where scipy's float32 path holds 3.0e-7.)
  *         peak = m[k]
  *     lag = lag_int + lag_frac samples = delay(buoy j) - delay(buoy i)   (sign of
  *     TDoAMeasurement.time_difference_ns: buoy2 - buoy1, tdoa_processor.py:51).
