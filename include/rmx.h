@@ -337,6 +337,43 @@ int rmx_caf_batch(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pa
                   const double* doppler_cps, int n_dopplers, int32_t* dop_idx, int32_t* lag_int,
                   float* lag_frac, float* peak, unsigned flags);
 
+/* The Doppler search with the per-call request of the correlation entries -- a band, PHAT, lag bounds -- and a sub-grid
+ * Doppler estimate.  Free-running receivers that differ by hundreds of hertz are also the ones with a common DC offset,
+ * LO leakage and echoes; the DC offset correlates at lag 0 and nu = 0, and a search over D hypotheses gives it D times
+ * as many chances to win.  PHAT, or a band that leaves out DC, repairs that.
+ *   band_cps, band_per_window, weighting   exactly as in rmx_xcorr_batch_weighted ([n_windows][2] or [2]; shared by all hypotheses).
+ *   lag_bounds, bounds_per_window          exactly as in rmx_xcorr_batch_bounded, or NULL; the interval of a (window, pair)
+ *               is shared by all its hypotheses.
+ *   dop_frac    float32 [n_windows][n_pairs], a device pointer with RMX_OUT_DEVICE; NULL: not computed.  The offset of the
+ *               Doppler estimate from doppler_cps[dop_idx], in grid INDICES: it presumes a uniformly spaced grid
+ *               (xcorr.doppler_estimate turns it into cycles per sample and refuses other grids).  It must not overlap
+ *               one of the other four outputs.
+ * Definition, for window w, pair (i, j) and hypothesis d:
+ *     Y_i   = weight_w(FFT_L(x_i))                 Y_j,d = weight_w(FFT_L(x_j * rot_d))
+ *   with rot_d the phasor table of rmx_caf_batch and weight_w the band mask and PHAT of rmx_xcorr_batch_weighted, applied
+ *   to the stored spectrum of each transform, after the rotation;  r_d = IFFT_L(Y_j,d conj(Y_i)), m_d its 'full' magnitudes.
+ *   Per hypothesis S4-S6 of rmx_xcorr_batch on m_d -- the sliced rule of rmx_xcorr_batch_bounded with lag_bounds -- give
+ *   (lag_d, frac_d, peak_d); dop_idx = d* is the d-major first maximum of peak_d (strict >: ties keep the lowest d), and
+ *   lag_int, lag_frac, peak are lag_d*, frac_d*, peak_d*.
+ *     dop_frac = (float)((a - c) / (2 (a - 2 b + c))) in double, a, b, c = the float32 peak_d of d* - 1, d*, d* + 1;
+ *     dop_frac = 0 when d* is 0 or n_dopplers - 1.
+ *   The first-maximum rule gives a < b and c <= b: the denominator is negative and dop_frac lies in (-0.5, 0.5].
+ * rmx_caf_batch IS this call with no band, RMX_WEIGHT_NONE, no bounds and dop_frac == NULL: the same kernels, bit-identical
+ *   outputs.  A full band with RMX_WEIGHT_NONE and full-interval bounds is that plain call too.  A non-NULL dop_frac changes
+ *   nothing in the other four outputs.
+ * Refusals (RMX_E_INVAL, the text in rmx_last_error, nothing written): the checks of rmx_caf_batch, then those of the
+ *   weighted entry, then those of the bounded entry, then dop_frac overlapping another output.
+ * The routes are rmx_caf_batch's: every weighted or bounded instantiation runs where the plain one runs, with the same
+ *   launch counts (the N = 4096 one-launch path included); a non-NULL dop_frac swaps k_caf_select(_all) for
+ *   k_caf_select(_all)_fd (radio-mapper_amd/csrc/caf_select.hpp).
+ * There is no integration, refinement or quality here: rmx_caf_batch_request is not refined and reports no quality. */
+int rmx_caf_batch_request(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                          const double* doppler_cps, int n_dopplers,
+                          const double* band_cps, int band_per_window, unsigned weighting,
+                          const int32_t* lag_bounds, int bounds_per_window,
+                          int32_t* dop_idx, float* dop_frac,
+                          int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
+
 /* Batched hyperbolic position solve: the consumer of the lags.  One
  * independent 3-unknown least-squares problem per window with the reference's objective
  * (HyperbolicPositioning.triangulate_position, tdoa_processor.py:249-273),

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_fwd(const void* __restrict__ iq
     wave_lds_fence();
     xchg_bc_read_c(xl, v, t);
     dft16(v);                         // n0 -> k2
-    if constexpr (sizeof...(WT) > 0) {   // rmx_xcorr_batch_weighted (wrap_items == 0: item is the global item)
+    if constexpr (sizeof...(WT) > 0) {   // weighted call; item is the REAL global item under wrap_items too: its window's band
         const XWeight wt = xweight_of(wt_pack...);
         const XBand bd = xband_of(wt, item / wt.n_buoys);
         // role C (fft_r16.hpp): u = 16 k0 + k1, slot s = k2 -> natural bin 2 (k0 + 16 k1 + 256 s) + p
@@ -206,7 +206,8 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
         if (p && u == 0) mag[0] = -1.0f;
         int klo = 0, khi = 2 * kM - 2;
         if constexpr (BOUNDED) {   // lag window: |r|^2 outside it -> the same sentinel (lag_bounds.hpp)
-            lag_window(lb, first_window + wl, out_idx, kM - 1, klo, khi);
+            // (one launch for all hypotheses: the bounds are the REAL window's, wl % i_wrap; the output slot stays virtual)
+            lag_window(lb, first_window + (i_wrap > 0 ? wl % i_wrap : wl), out_idx, kM - 1, klo, khi);
             const int kb = p ? (u - 1) : (u + kM - 1);
 #pragma unroll
             for (int q = 0; q < 16; ++q) mag[q] = lag_mask(mag[q], kb + q * 256, klo, khi);
@@ -518,6 +519,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     const long wbase = (long)wl * n_buoys;
     const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wl) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
     const long obase = (first_window + wl) * (long)n_pairs;
+    // the window whose lag bounds apply (one launch for all hypotheses: the REAL window; the output slot stays virtual)
+    [[maybe_unused]] const long lbw = first_window + (i_wrap > 0 ? wl % i_wrap : wl);
     float4 sa[8], sb[8];
     PairItem pi = items[it_begin];
     int cur_i = pi.i;
@@ -564,7 +567,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
         __syncthreads();              // the pair's only barrier; also publishes pair it-1's winners
         if (prev_out >= 0 && t == ((it - it_begin) & 7) * 64)
             resolve_pair<BOUNDED>(reinterpret_cast<const float*>(magbuf + (buf ^ 1) * (4 * kThreads)), red + (buf ^ 1) * 8,
-                                  obase + prev_out, out_scale, lag_int, lag_frac, peak, lb, first_window + wl, prev_out);
+                                  obase + prev_out, out_scale, lag_int, lag_frac, peak, lb, lbw, prev_out);
         xchg_a_read(xl, v, t);
         mul_tw1(v, tw1);              // W_M^(u*k0) [* W_L^u on odd lanes]
         dft16(v);                     // k0 -> n2   (role A): e[n] (even lanes) / o[n]*W_L^u (odd lanes)
@@ -582,7 +585,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
         if (p && u == 0) mag[0] = -1.0f;   // lag -M is not part of the 'full' output
         if constexpr (BOUNDED) {           // lag window: |r|^2 outside it -> the same sentinel (lag_bounds.hpp)
             int klo, khi;
-            lag_window(lb, first_window + wl, out_idx, kM - 1, klo, khi);
+            lag_window(lb, lbw, out_idx, kM - 1, klo, khi);
 #pragma unroll
             for (int q = 0; q < 16; ++q) mag[q] = lag_mask(mag[q], kbase + q * 256, klo, khi);
         }
@@ -606,7 +609,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     if (t == 0) {
         const int buf = (it_end - 1 - it_begin) & 1;
         resolve_pair<BOUNDED>(reinterpret_cast<const float*>(magbuf + buf * (4 * kThreads)), red + buf * 8, obase + prev_out,
-                              out_scale, lag_int, lag_frac, peak, lb, first_window + wl, prev_out);
+                              out_scale, lag_int, lag_frac, peak, lb, lbw, prev_out);
     }
 }
 

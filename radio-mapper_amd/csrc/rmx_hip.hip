@@ -151,6 +151,8 @@ struct rmx_ctx {
     float2* caf_rot = nullptr;  size_t caf_rot_elems = 0;
     int* caf_lag = nullptr;  float* caf_frac = nullptr;  float* caf_peak = nullptr;  int* caf_dop = nullptr;
     size_t caf_out_elems = 0;
+    float* caf_nb = nullptr;  size_t caf_nb_elems = 0;   // rmx_caf_batch_request with dop_frac: [3][slots] neighbour peaks of
+                                                         // k_caf_select_fd, then [slots] dop_frac of a host-pointer call
     std::vector<double> caf_grid;
     // the caller's lag windows (rmx_xcorr_batch_bounded) and its bands as signed bins (rmx_xcorr_batch_weighted): the
     // device copies that a call's XcorrCall points into
@@ -179,7 +181,7 @@ static thread_local std::string g_create_error;
 
 // What ONE correlation call asks of the launch code beyond the plain call: built by the entry (xcorr_request), handed
 // down by const reference to every function that launches a kernel, never stored.  The default is the plain, unrefined
-// call; rmx_caf_batch passes exactly that.
+// call; rmx_caf_batch passes exactly that, rmx_caf_batch_request its bounds and its weighting.
 struct XcorrCall {
     LagBounds lb{nullptr, 0, 0, 0};          // lag intervals on the device (rmx_xcorr_batch_bounded), or none
     XWeight wt{nullptr, 0, 0, 0, 0, 0.0f};   // bands as signed bins on the device + weighting (rmx_xcorr_batch_weighted)
@@ -824,7 +826,7 @@ static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool n
 }
 
 // forward spectra of windows [w0, w0 + wc) of d_iq into g_spec (rot == nullptr) or, de-rotated by the phasor
-// table rot[N], into g_spec_r (rmx_caf_batch)
+// table rot[N], into g_spec_r (rmx_caf_batch); a weighted call weights either (rmx_caf_batch_request)
 static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot,
                            bool cols_only) {
     using namespace gen;
@@ -839,7 +841,7 @@ static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, 
         c->g_dyn_bytes += (size_t)c->g_chunk * B * L * 8;
     }
     float2* dst = rot ? c->g_spec_r : c->g_spec;
-    XWeight wt = call.wt;   // weighted call (never with rot): the stored bins carry fwd_scale
+    XWeight wt = call.wt;   // weighted call: the stored bins carry fwd_scale
     wt.unit = fwd_scale;
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
@@ -849,7 +851,7 @@ static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, 
                 return launch(c, kTkFwdSmall, kern, dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, d_iq, dst, c->g_tw, N, logL, first_item,
                               fwd_scale, a_rot, a_wt...);
             };
-            return call.wt.band ? go(g_fwd_small<U8, XWeight>, nullptr, wt) : go(g_fwd_small<U8>, rot);
+            return call.wt.band ? go(g_fwd_small<U8, XWeight>, rot, wt) : go(g_fwd_small<U8>, rot);
         });
     }
     const int l1 = c->g_logL1, l2 = c->g_logL2, L1 = 1 << l1, L2 = 1 << l2;
@@ -943,7 +945,7 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
 }
 
 // N = 4096, unfused path: forward spectra of windows [w0, w0 + wc) into d_spec (rot == nullptr) or, de-rotated by
-// the phasor table rot[N], into d_spec_r (rmx_caf_batch); then the pair kernels over the plan's pair list
+// the phasor table rot[N], into d_spec_r (rmx_caf_batch), weighted where the call says so; then the pair kernels over the plan's pair list
 static int fwd4096(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot, int n_bins = 1) {
     const long first_item = (long)w0 * c->n_buoys;
     const int wrap = n_bins > 1 ? wc * c->n_buoys : 0;
@@ -968,9 +970,9 @@ static int fwd4096(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, 
                           a_wrap, wt...);
         };
         if (!call.wt.band) return go(k_fwd<U8>, rot, wrap);
-        XWeight wt = call.wt;   // weighted call (never with rot): the stored bins carry the TW1 scale
+        XWeight wt = call.wt;   // weighted call: the stored bins carry the TW1 scale; the band is the real window's under wrap
         wt.unit = (float)kTw1Scale;
-        return go(k_fwd<U8, XWeight>, nullptr, 0, wt);
+        return go(k_fwd<U8, XWeight>, rot, wrap, wt);
     });
 }
 static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, float out_scale,
@@ -1302,7 +1304,7 @@ void rmx_destroy(rmx_ctx* c) {
     for (void* p : {(void*)c->sv_buoys, (void*)c->sv_pairs, c->sv_in, c->sv_out})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)c->d_spec_r, (void*)c->caf_rot, (void*)c->caf_lag, (void*)c->caf_frac, (void*)c->caf_peak,
-                    (void*)c->caf_dop})
+                    (void*)c->caf_dop, (void*)c->caf_nb})
         if (p) (void)hipFree(p);
     if (c->d_spec) (void)hipFree(c->d_spec);
     if (c->d_tw1) (void)hipFree(c->d_tw1);
@@ -1723,6 +1725,25 @@ static int check_bounded(rmx_ctx* c, int n_windows, int n_pairs, int integrate, 
     return RMX_OK;
 }
 
+// The request's small host arrays onto the device, through the ctx's own staging (the caller may reuse its arrays on
+// return), and into `call`: the bands as signed bins where the call is weighted, the lag intervals where it is bounded.
+// Both the correlation entries (xcorr_request) and the Doppler search (rmx_caf_batch_request) describe their call so.
+static int stage_request(rmx_ctx* c, XcorrCall* call, bool weighted, const std::vector<int32_t>& bins, bool band_rows_per_window,
+                         unsigned weighting, bool bounded, const int32_t* lag_bounds, long bound_rows, int bounds_per_window,
+                         int n_pairs) {
+    if (weighted) {
+        const int rc = stage_to_device(c, &c->band_stage, bins.data(), bins.size());
+        if (rc != RMX_OK) return rc;
+        call->wt = XWeight{c->band_stage.d, band_rows_per_window ? 2L : 0L, 0L, c->n_buoys, weighting == RMX_WEIGHT_PHAT ? 1 : 0, 1.0f};
+    }
+    if (bounded) {
+        const int rc = stage_to_device(c, &c->lb_stage, lag_bounds, (size_t)(2 * bound_rows));
+        if (rc != RMX_OK) return rc;
+        call->lb = LagBounds{c->lb_stage.d, bounds_per_window ? 2L * n_pairs : 0L, 0L, n_pairs};
+    }
+    return RMX_OK;
+}
+
 // What all six correlation entries do, and none of them through another: check the arguments -- the checks of the entries
 // that take `integrate` (grouped), then the weighted entry's, then the bounded entry's, so an input with several bad
 // arguments is refused for the same one whichever entry it came through --, copy the bands (as signed bins) and the lag
@@ -1786,17 +1807,9 @@ static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_
     call.integ = integrate;
     call.refine = refine;
     call.quality = quality;
-    if (weighted) {
-        rc = stage_to_device(c, &c->band_stage, bins.data(), bins.size());
-        if (rc != RMX_OK) return rc;
-        call.wt = XWeight{c->band_stage.d, (band_cps && band_per_window) ? 2L : 0L, 0L, c->n_buoys,
-                          weighting == RMX_WEIGHT_PHAT ? 1 : 0, 1.0f};
-    }
-    if (bounded) {
-        rc = stage_to_device(c, &c->lb_stage, lag_bounds, (size_t)(2 * bound_rows));
-        if (rc != RMX_OK) return rc;
-        call.lb = LagBounds{c->lb_stage.d, bounds_per_window ? 2L * n_pairs : 0L, 0L, n_pairs};
-    }
+    rc = stage_request(c, &call, weighted, bins, band_cps && band_per_window, weighting, bounded, lag_bounds, bound_rows,
+                       bounds_per_window, n_pairs);
+    if (rc != RMX_OK) return rc;
     return xcorr_dispatch(c, call, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
 }
 
@@ -1857,9 +1870,22 @@ int rmx_xcorr_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int
                          bounds_per_group, refine, lag_int, lag_frac, peak, quality, flags);
 }
 
+// The Doppler search is rmx_caf_batch_request with nothing requested: the same kernels, the same launches
 int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                   const double* doppler_cps, int n_dopplers, int32_t* dop_idx, int32_t* lag_int, float* lag_frac,
                   float* peak, unsigned flags) {
+    return rmx_caf_batch_request(c, iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0,
+                                 dop_idx, nullptr, lag_int, lag_frac, peak, flags);
+}
+
+// The Doppler search under a request: a band and PHAT on every stored spectrum, the rotated ones included, lag intervals
+// in every hypothesis' peak search, and (dop_frac) the parabola through the winner's and its two neighbours' peaks.
+int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                          const double* doppler_cps, int n_dopplers,
+                          const double* band_cps, int band_per_window, unsigned weighting,
+                          const int32_t* lag_bounds, int bounds_per_window,
+                          int32_t* dop_idx, float* dop_frac,
+                          int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
     if (!iq || !dop_idx || !lag_int || !lag_frac || !peak || !doppler_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
     if (n_dopplers < 1 || n_dopplers > 4096) return fail(c, RMX_E_INVAL, "n_dopplers %d not in 1..4096", n_dopplers);
@@ -1867,7 +1893,7 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
     if (rc != RMX_OK) return rc;
     if (n_windows == 0 || n_pairs == 0) return RMX_OK;
     const int B = c->n_buoys, N = c->n_samples;
-    const XcorrCall call;   // the plain request: no bounds, no weighting, nothing integrated, whatever ran before
+    XcorrCall call;   // the plain request unless the checks below say otherwise; never integrated, refined or qualified
     RMX_HIP(c, hipSetDevice(c->device));
     // N = 4096, one chunk: all hypotheses in ONE forward launch and ONE pair launch (virtual window = hypothesis x
     // window) instead of three launches per hypothesis -- 21 hypotheses on one frequency group: 431 -> ~60 us
@@ -1881,6 +1907,33 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
     }
     rc = build_plan(c, pairs, n_pairs);              // validates the pair list
     if (rc != RMX_OK) return rc;
+    const size_t out_elems = (size_t)n_windows * n_pairs;
+    {   // the request: the weighted entry's checks, the bounded entry's, then dop_frac; nothing is staged before the last
+        std::vector<int32_t> bins;
+        bool weighted = false, bounded = false;
+        long bound_rows = 0;
+        if (band_cps || weighting != RMX_WEIGHT_NONE) {
+            rc = check_weighted(c, n_windows, band_cps, band_per_window, weighting, &bins, &weighted);
+            if (rc != RMX_OK) return rc;
+        }
+        if (lag_bounds) {
+            rc = check_bounded(c, n_windows, n_pairs, 1, lag_bounds, bounds_per_window, &bound_rows, &bounded);
+            if (rc != RMX_OK) return rc;
+        }
+        if (dop_frac) {
+            const char *f0 = reinterpret_cast<const char*>(dop_frac), *f1 = f0 + out_elems * sizeof(float);
+            const struct { const char* name; const void* p; } outs[4] = {{"dop_idx", dop_idx}, {"lag_int", lag_int}, {"lag_frac", lag_frac},
+                                                                        {"peak", peak}};
+            for (const auto& o : outs) {
+                const char* p0 = static_cast<const char*>(o.p);
+                if (p0 < f1 && f0 < p0 + out_elems * sizeof(float))
+                    return fail(c, RMX_E_INVAL, "dop_frac overlaps %s: its %zu floats need a buffer of their own", o.name, out_elems);
+            }
+        }
+        rc = stage_request(c, &call, weighted, bins, band_cps && band_per_window, weighting, bounded, lag_bounds, bound_rows,
+                           bounds_per_window, n_pairs);
+        if (rc != RMX_OK) return rc;
+    }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
     const size_t in_bytes = (size_t)n_windows * B * N * (u8 ? 2 : 8);
     const void* d_iq = iq;
@@ -1907,7 +1960,6 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
         c->caf_rot_elems = rot.size();
         c->caf_grid = grid;
     }
-    const size_t out_elems = (size_t)n_windows * n_pairs;
     const size_t caf_elems = batch_bins ? out_elems * (size_t)n_dopplers : out_elems;   // per-hypothesis results: [d][w][pair]
     if (c->caf_out_elems < caf_elems) {
         for (void* p : {(void*)c->caf_lag, (void*)c->caf_frac, (void*)c->caf_peak, (void*)c->caf_dop})
@@ -1926,6 +1978,17 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
             if (rc_out != RMX_OK) return rc_out;
         }
         b_dop = c->d_dop; b_lag = c->d_lag; b_frac = c->d_frac; b_peak = c->d_peak;
+    }
+    float* b_dfrac = dop_frac;
+    if (dop_frac && (!batch_bins || !out_dev)) {   // k_caf_select_fd's three neighbour rows, and dop_frac of a host-pointer call
+        if (c->caf_nb_elems < 4 * out_elems) {
+            RMX_HIP(c, hipStreamSynchronize(c->stream));
+            if (c->caf_nb) (void)hipFree(c->caf_nb);
+            c->caf_nb = nullptr; c->caf_nb_elems = 0;
+            RMX_HIP(c, hipMalloc((void**)&c->caf_nb, 4 * out_elems * sizeof(float)));
+            c->caf_nb_elems = 4 * out_elems;
+        }
+        if (!out_dev) b_dfrac = c->caf_nb + 3 * out_elems;
     }
     // Per chunk of windows: the un-rotated spectra once, then per hypothesis the de-rotated spectra (the rotation
     // is applied as the window is loaded), the pair kernels with X_i un-rotated and X_j de-rotated, and the
@@ -1947,9 +2010,13 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
         rc = fwd4096(c, call, d_iq, 0, n_windows, u8, nullptr);
         if (rc == RMX_OK) rc = fwd4096(c, call, d_iq, 0, n_windows, u8, c->caf_rot, n_dopplers);
         if (rc == RMX_OK) rc = pairs4096(c, call, 0, n_windows, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, osc, true, n_dopplers);
-        if (rc == RMX_OK)
-            rc = launch(c, kTkCafSelect, k_caf_select_all, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, n_dopplers, (long)out_elems,
-                        c->caf_lag, c->caf_frac, c->caf_peak, b_dop, b_lag, b_frac, b_peak);
+        const dim3 sgrid((unsigned)((out_elems + 255) / 256));
+        if (rc == RMX_OK && !dop_frac)
+            rc = launch(c, kTkCafSelect, k_caf_select_all, sgrid, dim3(256), 0, n_dopplers, (long)out_elems, c->caf_lag, c->caf_frac,
+                        c->caf_peak, b_dop, b_lag, b_frac, b_peak);
+        if (rc == RMX_OK && dop_frac)
+            rc = launch(c, kTkCafSelect, k_caf_select_all_fd, sgrid, dim3(256), 0, n_dopplers, (long)out_elems, c->caf_lag, c->caf_frac,
+                        c->caf_peak, b_dop, b_lag, b_frac, b_peak, b_dfrac);
     }
     for (int w0 = 0; !batch_bins && w0 < n_windows && rc == RMX_OK; w0 += chunk) {
         const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
@@ -1961,13 +2028,20 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
             rc = sv.pairs(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true, false);
             if (rc != RMX_OK) break;
             const long first = (long)w0 * n_pairs, cnt = (long)wc * n_pairs;
-            rc = launch(c, kTkCafSelect, k_caf_select, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, d, first, cnt, c->caf_lag, c->caf_frac,
-                        c->caf_peak, b_dop, b_lag, b_frac, b_peak);
+            const dim3 sgrid((unsigned)((cnt + 255) / 256));
+            if (dop_frac)
+                rc = launch(c, kTkCafSelect, k_caf_select_fd, sgrid, dim3(256), 0, d, n_dopplers, first, cnt, (long)out_elems, c->caf_lag,
+                            c->caf_frac, c->caf_peak, b_dop, b_lag, b_frac, b_peak, c->caf_nb, b_dfrac);
+            else
+                rc = launch(c, kTkCafSelect, k_caf_select, sgrid, dim3(256), 0, d, first, cnt, c->caf_lag, c->caf_frac, c->caf_peak, b_dop,
+                            b_lag, b_frac, b_peak);
         }
     }
     if (rc != RMX_OK) return rc;
-    if (!out_dev) return fetch_out(c, out_elems, lag_int, lag_frac, peak, dop_idx);
-    return RMX_OK;
+    if (out_dev) return RMX_OK;
+    // host-pointer results: dop_frac is queued in front of fetch_out, which waits for the stream
+    if (dop_frac) RMX_HIP(c, hipMemcpyAsync(dop_frac, b_dfrac, out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return fetch_out(c, out_elems, lag_int, lag_frac, peak, dop_idx);
 }
 
 int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32_t* pairs, int n_pairs,

@@ -192,11 +192,25 @@ class MultiXcorrEngine:
         return self._run(W, block_call, n_out, (np.int32, np.float32, np.float32, np.float32)[:n_out], P, n_rows=G,
                          tails=[(), (), (), (4,)][:n_out])
 
-    def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None):
-        """Cross-ambiguity search -> (doppler_idx, lag_int, lag_frac, peak), each [W][P]."""
+    def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
+            whiten: bool = False, fine: bool = False):
+        """Cross-ambiguity search -> (doppler_idx, lag_int, lag_frac, peak), each [W][P]; with fine=True (doppler_idx,
+        dop_frac, lag_int, lag_frac, peak) (XcorrEngine.caf).  lag_bounds [P][2] and band [2] go to every block whole,
+        [W][P][2] and [W][2] are cut into each block's own windows' rows, as correlate() cuts them."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
-        return self._run(iq.shape[0], lambda eng, s, c: eng.caf(iq[s:s + c], doppler_cps, pairs), 4,
-                         (np.int32, np.int32, np.float32, np.float32), P)
+        lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
+        bd, band_pw = check_band(band, iq.shape[0])
+        if lb is None and bd is None and not whiten and not fine:
+            return self._run(iq.shape[0], lambda eng, s, c: eng.caf(iq[s:s + c], doppler_cps, pairs), 4,
+                             (np.int32, np.int32, np.float32, np.float32), P)
+
+        def block_call(eng, s, c):
+            return eng.caf(iq[s:s + c], doppler_cps, pairs,
+                           lag_bounds=None if lb is None else (lb[s:s + c] if per_window else lb),
+                           band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, fine=fine)
+        if fine:
+            return self._run(iq.shape[0], block_call, 5, (np.int32, np.float32, np.int32, np.float32, np.float32), P)
+        return self._run(iq.shape[0], block_call, 4, (np.int32, np.int32, np.float32, np.float32), P)

@@ -82,6 +82,9 @@ class TDoAMeasurement:
     distance_difference_m: float
     confidence: float
     frequency_mhz: float
+    # extension: TDoACalculator(doppler_search_hz=...) -- the estimated frequency offset of buoy2's copy of the signal
+    # against buoy1's, in hertz (the two receivers' oscillator difference plus any Doppler); None without the search
+    frequency_offset_hz: Optional[float] = None
 
 
 @dataclass
@@ -151,7 +154,8 @@ class TDoACalculator:
 
     def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, min_cut_samples: int = 128,
                  bound_lags: bool = False, band_limit: bool = False, whiten: bool = False, integrate: int = 1,
-                 refine: int = 0, min_psr: Optional[float] = None, correlation_confidence: bool = False):
+                 refine: int = 0, min_psr: Optional[float] = None, correlation_confidence: bool = False,
+                 doppler_search_hz: Optional[Tuple[float, float]] = None):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
@@ -178,7 +182,14 @@ class TDoACalculator:
         is noise (xcorr.psr_threshold gives the value for a false-alarm rate).  correlation_confidence: the measurement's
         confidence, built from the detector's confidence and a timing term only, is additionally multiplied by the pair's
         coherence in [0, 1].  Plain attributes; None and False (off) by default: the engine is then called exactly as
-        before.  Neither applies to groups without IQ (the time-tag arithmetic has no correlation)."""
+        before.  Neither applies to groups without IQ (the time-tag arithmetic has no correlation).
+        doppler_search_hz: (max_hz, step_hz); every group with IQ goes through the Doppler search (rmx_caf_batch_request)
+        on the symmetric grid 0, +-step_hz, ... up to max_hz instead of the plain correlation: receivers with free-running
+        oscillators decorrelate over a long window unless the later buoy's copy is de-rotated first.  bound_lags,
+        band_limit and whiten apply as they do without it, and every measurement carries the estimated offset
+        (frequency_offset_hz: the winning hypothesis plus the sub-grid parabola).  The search has no integration,
+        refinement or quality: together with integrate > 1, refine > 0, min_psr or correlation_confidence the
+        construction raises ValueError.  None (off) by default: every other path is then as before."""
         from .xcorr import check_refine
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
@@ -191,6 +202,22 @@ class TDoACalculator:
         self.refine = check_refine(refine)
         self.min_psr = None if min_psr is None else float(min_psr)
         self.correlation_confidence = bool(correlation_confidence)
+        self.doppler_search_hz = None
+        if doppler_search_hz is not None:
+            try:
+                max_hz, step_hz = (float(v) for v in doppler_search_hz)
+            except (TypeError, ValueError):
+                raise ValueError(f"doppler_search_hz must be (max_hz, step_hz), got {doppler_search_hz!r}") from None
+            if not (step_hz > 0.0 and max_hz >= step_hz and math.isfinite(max_hz)):
+                raise ValueError(f"doppler_search_hz = (max_hz, step_hz) needs 0 < step_hz <= max_hz, got {doppler_search_hz!r}")
+            if 2 * int(math.floor(max_hz / step_hz + 1e-9)) + 1 > 4096:
+                raise ValueError(f"doppler_search_hz = {doppler_search_hz!r} asks for more than 4096 hypotheses")
+            for name, on in (("integrate", self.integrate > 1), ("refine", self.refine > 0), ("min_psr", self.min_psr is not None),
+                             ("correlation_confidence", self.correlation_confidence)):
+                if on:
+                    raise ValueError(f"doppler_search_hz and {name} cannot be combined: the Doppler search has no "
+                                     f"integration, refinement or quality")
+            self.doppler_search_hz = (max_hz, step_hz)
         self._engines: Dict[Tuple[int, int], Any] = {}   # insertion order = recency
         self._tconf: Dict[Tuple[int, int], float] = {}
 
@@ -233,7 +260,14 @@ class TDoACalculator:
     def _wants_quality(self) -> bool:
         return self.min_psr is not None or self.correlation_confidence
 
-    def measure_lags(self, iq, pairs=None, lag_bounds=None, band=None, whiten=False, integrate=1, refine=0, quality=False):
+    def doppler_grid(self, fs: float) -> np.ndarray:
+        """doppler_search_hz: the symmetric grid of hypotheses at sample rate fs, float64 in cycles per sample"""
+        max_hz, step_hz = self.doppler_search_hz
+        n = int(math.floor(max_hz / step_hz + 1e-9))
+        return np.arange(-n, n + 1, dtype=np.float64) * (step_hz / float(fs))
+
+    def measure_lags(self, iq, pairs=None, lag_bounds=None, band=None, whiten=False, integrate=1, refine=0, quality=False,
+                     doppler_cps=None):
         """Batched hot path.  iq: complex64 [W][B][N] (or uint8 [W][B][2N]) ->
         (lag_int [W][P], lag_frac [W][P], peak [W][P]); lag = delay(j) - delay(i) in samples.
         A leading channel axis is a batch axis: [C][W][B][N] -> three [C][W][P] arrays (channels and
@@ -244,9 +278,18 @@ class TDoACalculator:
         per pair and group (rmx_xcorr_batch_integrated): W must be a multiple of K, the results and per-window lag_bounds
         have W // K rows where they have W otherwise; band stays per window.  refine: U of the fine lag search
         (rmx_xcorr_batch_refined), 0 for none.  quality: True returns a fourth array [W][P][4] (with a channel axis:
-        [C][W][P][4]), the quality figures of every lag (rmx_xcorr_batch_quality)."""
+        [C][W][P][4]), the quality figures of every lag (rmx_xcorr_batch_quality).
+        doppler_cps: None, or the hypotheses of a Doppler search in cycles per sample (a uniformly spaced grid): the call
+        goes to caf() (rmx_caf_batch_request) with the same lag_bounds, band and whiten, and returns (lag_int, lag_frac,
+        peak, dop_idx int32, doppler float64 in cycles per sample = xcorr.doppler_estimate of the winner and its sub-grid
+        part).  Not together with integrate > 1, refine > 0 or quality (ValueError)."""
         from .xcorr import check_integrate, check_refine
         refine = check_refine(refine)
+        if doppler_cps is not None:
+            for name, on in (("integrate", integrate != 1), ("refine", refine > 0), ("quality", bool(quality))):
+                if on:
+                    raise ValueError(f"doppler_cps and {name} cannot be combined: the Doppler search has no integration, "
+                                     f"refinement or quality")
         iq = np.asarray(iq)
         lead = None
         if iq.ndim == 4:
@@ -265,7 +308,16 @@ class TDoACalculator:
             lb = np.asarray(lag_bounds)
             if lead is not None and lb.ndim == 4:
                 lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
-        if band is not None or whiten or integrate > 1 or refine > 0 or quality:
+        if doppler_cps is not None:
+            from .xcorr import doppler_estimate
+            bd = None
+            if band is not None:
+                bd = np.asarray(band)
+                if lead is not None and bd.ndim == 3:
+                    bd = bd.reshape((-1,) + bd.shape[2:])
+            dop, dfrac, li, lf, pk = eng.caf(iq, doppler_cps, pairs, lag_bounds=lb, band=bd, whiten=bool(whiten), fine=True)
+            out = (li, lf, pk, dop, doppler_estimate(doppler_cps, dop, dfrac))
+        elif band is not None or whiten or integrate > 1 or refine > 0 or quality:
             bd = None
             if band is not None:
                 bd = np.asarray(band)
@@ -428,11 +480,12 @@ class TDoACalculator:
                           f"{max(self.min_cut_samples, 16)}")
         return n // k, None
 
-    def _measure_groups(self, stacked: np.ndarray, lag_bounds=None, band=None, with_quality: bool = False):
+    def _measure_groups(self, stacked: np.ndarray, lag_bounds=None, band=None, with_quality: bool = False, fs=None):
         """[G][B][N] -> lag [G][P] float64, or None after logging: the reference's seam never raises
         (tdoa_processor.py:151-153) and there is no fallback to time tags once IQ was supplied.  lag_bounds: None, or
         int [G][P][2] (bound_lags); band: None, or float [G][2] (band_limit); whiten applies to every group.
-        with_quality: -> (lag [G][P], quality [G][P][4]) instead (min_psr / correlation_confidence), None all the same."""
+        with_quality: -> (lag [G][P], quality [G][P][4]) instead (min_psr / correlation_confidence), None all the same.
+        doppler_search_hz (fs, the groups' sample rate, must be given): -> (lag [G][P], offset in hertz [G][P]) instead."""
         kw = {}
         if lag_bounds is not None:
             kw["lag_bounds"] = lag_bounds
@@ -452,6 +505,9 @@ class TDoACalculator:
         if self.refine > 0:
             kw["refine"] = self.refine
         try:
+            if self.doppler_search_hz is not None:
+                li, lf, _, _, dop = self.measure_lags(stacked, doppler_cps=self.doppler_grid(fs), **kw)
+                return li.astype(np.float64) + lf.astype(np.float64), np.asarray(dop, np.float64) * float(fs)
             if with_quality:
                 li, lf, _, qual = self.measure_lags(stacked, quality=True, **kw)
                 return li.astype(np.float64) + lf.astype(np.float64), np.asarray(qual)
@@ -488,7 +544,8 @@ class TDoACalculator:
         """The reference's pair loop (tdoa_processor.py:146-198).  `_lag` (private): (lags [P], sample rate) of this
         group, already measured in a batch with other groups by TDoAProcessor; None when that batch failed or the
         group's IQ could not be batched; `_TIME_TAGS` when TDoAProcessor found no IQ on the group.  The tuple may go on
-        with the empty-interval flags [P] (or None) and the quality figures [P][4] of the group."""
+        with the empty-interval flags [P] (or None), the quality figures [P][4] of the group (or None) and the frequency
+        offsets in hertz [P] of a Doppler search."""
         out: List[TDoAMeasurement] = []
         nd = len(detections)
         if nd < 2:
@@ -498,6 +555,7 @@ class TDoACalculator:
         fs = None
         empty = None   # bound_lags: pairs whose lag window is empty (skipped below)
         qual = None    # min_psr / correlation_confidence: the quality figures [P][4] of the group's lags
+        dop_hz = None  # doppler_search_hz: the estimated frequency offset of every pair [P]
         if _lag is self._NO_LAG:
             key, stacked = self._iq_batch_key(detections)
             if key is False:
@@ -520,7 +578,12 @@ class TDoACalculator:
                     if why:
                         self.logger.error(f"Cannot band limit the group: {why}; no TDoA measurements for it")
                         return out
-                if self._wants_quality():
+                if self.doppler_search_hz is not None:
+                    res = self._measure_groups(stacked[None], lb, None if band is None else band[None], fs=key[3])
+                    if res is None:
+                        return out
+                    res, dop_hz = res[0], res[1][0]
+                elif self._wants_quality():
                     res = self._measure_groups(stacked[None], lb, None if band is None else band[None], with_quality=True)
                     if res is None:
                         return out
@@ -536,6 +599,7 @@ class TDoACalculator:
             lag, fs = _lag[0], _lag[1]
             empty = _lag[2] if len(_lag) > 2 else None
             qual = _lag[3] if len(_lag) > 3 else None
+            dop_hz = _lag[4] if len(_lag) > 4 else None
         q = -1
         if lag is not None:
             # the same float64 arithmetic as `round(lag[q] / fs * 1e9)` per pair, done once for the group (numpy scalars make
@@ -571,7 +635,10 @@ class TDoACalculator:
                         continue
                     if self.correlation_confidence:
                         conf *= float(qual[q][0])   # (RMX_Q_COHERENCE)
-                out.append(TDoAMeasurement(d1.buoy_id, d2.buoy_id, dt_ns, dist_m, conf, d1.frequency_mhz))
+                if dop_hz is not None:
+                    out.append(TDoAMeasurement(d1.buoy_id, d2.buoy_id, dt_ns, dist_m, conf, d1.frequency_mhz, float(dop_hz[q])))
+                else:
+                    out.append(TDoAMeasurement(d1.buoy_id, d2.buoy_id, dt_ns, dist_m, conf, d1.frequency_mhz))
                 if debug:
                     self.logger.debug("TDoA %s-%s dT=%.1f us dD=%.1f m", d1.buoy_id, d2.buoy_id, dt_ns / 1000, dist_m)
         return out
@@ -659,12 +726,14 @@ class HyperbolicPositioning:
 # --------------------------------------------------------------------------------------------------
 class TDoAProcessor:
     def __init__(self, band_limit: bool = False, whiten: bool = False, integrate: int = 1, refine: int = 0,
-                 min_psr: Optional[float] = None, correlation_confidence: bool = False):
-        """band_limit, whiten, integrate, refine, min_psr, correlation_confidence: the TDoACalculator settings of the same
-        names (off by default)."""
+                 min_psr: Optional[float] = None, correlation_confidence: bool = False,
+                 doppler_search_hz: Optional[Tuple[float, float]] = None):
+        """band_limit, whiten, integrate, refine, min_psr, correlation_confidence, doppler_search_hz: the TDoACalculator
+        settings of the same names (off by default)."""
         self.logger = logging.getLogger(__name__ + ".TDoAProcessor")
         self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten, integrate=integrate, refine=refine,
-                                              min_psr=min_psr, correlation_confidence=correlation_confidence)
+                                              min_psr=min_psr, correlation_confidence=correlation_confidence,
+                                              doppler_search_hz=doppler_search_hz)
         self.hyperbolic_positioner = HyperbolicPositioning()
         self.buoy_positions: Dict[str, BuoyPosition] = {}
         self.correlation_window_s = 10.0
@@ -743,6 +812,12 @@ class TDoAProcessor:
             stacked = np.stack([work[n][3] for n in members])
             # (min_psr / correlation_confidence: the quality figures ride along as the tuple's fourth entry)
             more = {"with_quality": True} if calc._wants_quality() else {}
+            if calc.doppler_search_hz is not None:   # (lag, offset in hertz) per group; the offsets ride as the fifth entry
+                per = [calc.lag_bounds(work[n][1], self.buoy_positions, n_samp, key[3]) for n in members] if calc.bound_lags else None
+                res = calc._measure_groups(stacked, None if per is None else np.stack([b for b, _ in per]), band, fs=key[3])
+                for k, n in enumerate(members):
+                    work[n][4] = None if res is None else (res[0][k], key[3], None if per is None else per[k][1], None, res[1][k])
+                continue
             if calc.bound_lags:   # per-window bounds [G][P][2]: each group has its own buoys and window starts
                 per = [calc.lag_bounds(work[n][1], self.buoy_positions, n_samp, key[3]) for n in members]
                 lags = calc._measure_groups(stacked, np.stack([b for b, _ in per]), band, **more)

@@ -89,6 +89,8 @@ def load_library():
     lib.rmx_xcorr_batch_quality.restype = ci
     lib.rmx_caf_batch.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, cu]
     lib.rmx_caf_batch.restype = ci
+    lib.rmx_caf_batch_request.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, cu, vp, ci, vp, vp, vp, vp, vp, cu]
+    lib.rmx_caf_batch_request.restype = ci
     lib.rmx_solve_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, ci, ci, vp, vp, vp, cu]
     lib.rmx_solve_batch.restype = ci
     lib.rmx_detect_batch.argtypes = [vp, vp, ci, ci, C.c_float, ci, C.c_double, C.c_float, ci, vp, vp, vp, vp, vp, vp, cu]
@@ -231,8 +233,36 @@ def lag_sigma(quality) -> np.ndarray:
     return np.where(ok, sig, np.inf)
 
 
+def doppler_estimate(doppler_cps, dop_idx, dop_frac) -> np.ndarray:
+    """The frequency offset, float64 in cycles per sample, that caf(..., fine=True) found:
+        doppler_cps[dop_idx] + dop_frac * step,   step = the grid's spacing.
+    dop_frac is in grid indices, so the grid must be uniformly spaced: ValueError for one that is not (a relative 1e-9
+    of the step is allowed), for a grid of fewer than 2 points when a dop_frac is not 0, and for indices outside the
+    grid.  numpy only; no call into the library."""
+    grid = np.asarray(doppler_cps, np.float64).reshape(-1)
+    idx = np.asarray(dop_idx)
+    frac = np.asarray(dop_frac, np.float64)
+    if idx.dtype.kind not in "iu":
+        raise ValueError(f"dop_idx must be an integer array, got dtype {idx.dtype}")
+    if idx.shape != frac.shape:
+        raise ValueError(f"dop_frac must have dop_idx's shape {idx.shape}, got {frac.shape}")
+    if grid.size < 1 or not np.all(np.isfinite(grid)):
+        raise ValueError("doppler_cps must be a non-empty finite grid")
+    if idx.size and (idx.min() < 0 or idx.max() >= grid.size):
+        raise ValueError(f"dop_idx must lie in 0..{grid.size - 1}")
+    if grid.size < 2:
+        if np.any(frac != 0.0):
+            raise ValueError("a grid of fewer than 2 points has no spacing: dop_frac must be 0")
+        return grid[idx] + 0.0 * frac
+    steps = np.diff(grid)
+    step = (grid[-1] - grid[0]) / (grid.size - 1)
+    if step == 0.0 or np.any(np.abs(steps - step) > 1e-9 * abs(step)):
+        raise ValueError("doppler_cps is not uniformly spaced: dop_frac is in grid indices and has no meaning on it")
+    return grid[idx] + frac * step
+
+
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_caf_batch", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -443,31 +473,50 @@ class XcorrEngine:
                     vp(qual) if quality else None)
         return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
 
-    def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None):
-        """Cross-ambiguity search (rmx_caf_batch): host arrays in and out.  doppler_cps: hypotheses in
-        cycles/sample.  Returns (doppler_idx int32, lag_int int32, lag_frac float32, peak float32),
-        each [W][P]."""
+    def _pairs_arg(self, pairs):
+        """pairs as the entries take it -> (kept int32 array or None, its pointer or None, P)"""
+        if pairs is None:
+            return None, None, self.n_buoys * (self.n_buoys - 1) // 2
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        return pairs, pairs.ctypes.data_as(C.c_void_p), pairs.shape[0]
+
+    def _caf(self, iq_p, W: int, pp, P: int, dc, bd, band_pw: bool, whiten: bool, lb, per_window: bool, dop_p, dop_frac_p,
+             lag_int_p, lag_frac_p, peak_p, flags: int):
+        """One Doppler search through the C entry its arguments name: rmx_caf_batch when nothing is requested, else
+        rmx_caf_batch_request.  dop_frac_p: a pointer, or None (not computed)."""
+        grid = (dc.ctypes.data_as(C.c_void_p), dc.shape[0])
+        if bd is None and not whiten and lb is None and dop_frac_p is None:
+            rc = self._lib.rmx_caf_batch(self._ctx, iq_p, W, pp, P, *grid, dop_p, lag_int_p, lag_frac_p, peak_p, flags)
+        else:
+            rc = self._lib.rmx_caf_batch_request(
+                self._ctx, iq_p, W, pp, P, *grid, None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
+                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
+                int(per_window), dop_p, dop_frac_p, lag_int_p, lag_frac_p, peak_p, flags)
+        self._check(rc)
+
+    def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
+            whiten: bool = False, fine: bool = False):
+        """Cross-ambiguity search (rmx_caf_batch, rmx_caf_batch_request): host arrays in and out.  doppler_cps: hypotheses
+        in cycles/sample.  lag_bounds, band, whiten: as for correlate(), shared by all hypotheses of a (window, pair).
+        Returns (doppler_idx int32, lag_int int32, lag_frac float32, peak float32), each [W][P]; with fine=True
+        (doppler_idx, dop_frac float32, lag_int, lag_frac, peak): dop_frac is the sub-grid Doppler estimate in grid
+        indices (doppler_estimate turns it into cycles per sample); the other four are bit for bit those without it."""
         iq, flags = self._check_iq(iq)
         W = iq.shape[0]
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-            P = pairs.shape[0]
-            pp = pairs.ctypes.data_as(C.c_void_p)
-        else:
-            P = self.n_buoys * (self.n_buoys - 1) // 2
-            pp = None
+        pairs, pp, P = self._pairs_arg(pairs)
         dc = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
+        lb, per_window = check_lag_bounds(lag_bounds, W, P)
+        bd, band_pw = check_band(band, W)
         dop = np.zeros((W, P), np.int32)
+        dfrac = np.zeros((W, P), np.float32) if fine else None
         lag_int = np.zeros((W, P), np.int32)
         lag_frac = np.zeros((W, P), np.float32)
         peak = np.zeros((W, P), np.float32)
-        if W == 0 or P == 0:
-            return dop, lag_int, lag_frac, peak
-        self._check(self._lib.rmx_caf_batch(
-            self._ctx, iq.ctypes.data_as(C.c_void_p), W, pp, P, dc.ctypes.data_as(C.c_void_p), dc.shape[0],
-            dop.ctypes.data_as(C.c_void_p), lag_int.ctypes.data_as(C.c_void_p),
-            lag_frac.ctypes.data_as(C.c_void_p), peak.ctypes.data_as(C.c_void_p), flags))
-        return dop, lag_int, lag_frac, peak
+        if W and P:
+            vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
+            self._caf(vp(iq), W, pp, P, dc, bd, band_pw, bool(whiten), lb, per_window, vp(dop), vp(dfrac) if fine else None,
+                      vp(lag_int), vp(lag_frac), vp(peak), flags)
+        return (dop, dfrac, lag_int, lag_frac, peak) if fine else (dop, lag_int, lag_frac, peak)
 
     def solve(self, buoy_xyz, lag_int, lag_frac, sample_rate_hz: float, weight=None,
               pairs: Optional[np.ndarray] = None, max_iter: int = 60):
@@ -560,22 +609,25 @@ class XcorrEngine:
         return out
 
     def caf_device(self, iq_ptr: int, n_windows: int, doppler_cps, dop_ptr: int, lag_int_ptr: int,
-                   lag_frac_ptr: int, peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False):
-        """rmx_caf_batch with device pointers in and out (the Doppler grid and the pair list stay host
-        arrays); asynchronous on the ctx stream."""
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-            P = pairs.shape[0]
-            pp = pairs.ctypes.data_as(C.c_void_p)
-        else:
-            P = self.n_buoys * (self.n_buoys - 1) // 2
-            pp = None
+                   lag_frac_ptr: int, peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
+                   band=None, whiten: bool = False, dop_frac_ptr: int = 0):
+        """rmx_caf_batch / rmx_caf_batch_request with device pointers in and out (the Doppler grid, the pair list, the
+        bounds and the bands stay host arrays; the library keeps its own copies); asynchronous on the ctx stream.
+        dop_frac_ptr: 0, or a device buffer of [n_windows][P] float32 for the sub-grid Doppler estimate."""
+        pairs, pp, P = self._pairs_arg(pairs)
         dc = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
-        self._check(self._lib.rmx_caf_batch(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
-                                            dc.ctypes.data_as(C.c_void_p), dc.shape[0], C.c_void_p(dop_ptr),
-                                            C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr),
-                                            flags))
+        if lag_bounds is None and band is None and not whiten and not dop_frac_ptr:   # the plain call, as ever
+            self._check(self._lib.rmx_caf_batch(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
+                                                dc.ctypes.data_as(C.c_void_p), dc.shape[0], C.c_void_p(dop_ptr),
+                                                C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr),
+                                                flags))
+            return
+        lb, per_window = check_lag_bounds(lag_bounds, n_windows, P)
+        bd, band_pw = check_band(band, n_windows)
+        self._caf(C.c_void_p(iq_ptr), n_windows, pp, P, dc, bd, band_pw, bool(whiten), lb, per_window, C.c_void_p(dop_ptr),
+                  C.c_void_p(dop_frac_ptr) if dop_frac_ptr else None, C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
+                  C.c_void_p(peak_ptr), flags)
 
     def correlate_device(self, iq_ptr: int, n_windows: int, lag_int_ptr: int, lag_frac_ptr: int,
                          peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
