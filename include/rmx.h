@@ -36,7 +36,10 @@
  *               (Far from lag 0 that scaled bar says little -- 0.16 samples at lag 16000 --, so
  *               tests/test_gpu_far_lags.py holds d ITSELF to 1e-5 absolute, or the flat-peak bound, against a float64
  *               reference with the peak placed anywhere in +-(N-1), seams of every kernel's output order included, on
- *               every route: worst 4.0e-7 on an MI355X, where scipy's float32 path holds 3.0e-7.)
+ *               every route: worst 4.0e-7 on an MI355X, where scipy's float32 path holds 3.0e-7.  With full 24-bit
+ *               mantissas in every sample -- floats normalised to +-1 by a non-power-of-two factor, int16-scaled
+ *               floats -- instead of the 8 bits of the uint8 grid, tests/test_gpu_dynamic_range.py holds every route to
+ *               the same bars: worst 3.8e-7 on lag_frac and 4.8e-7 relative on peak on an MI355X.)
  *         peak = m[k]
  *     lag = lag_int + lag_frac samples = delay(buoy j) - delay(buoy i)   (sign of
  *     TDoAMeasurement.time_difference_ns: buoy2 - buoy1, tdoa_processor.py:51).
@@ -133,8 +136,28 @@ void rmx_clear_default_options(void);
  *   lag_int   int32   [n_windows][n_pairs]
  *   lag_frac  float32 [n_windows][n_pairs]   sub-sample offset in [-0.5, 0.5]
  *   peak      float32 [n_windows][n_pairs]   |c| at the integer peak (scipy scaling)
- * Range: everything is float32 with exact power-of-two scaling inside; at N = 4096 the squared
- * magnitudes stay finite for fully coherent inputs up to |sample| ~ 4e6 (rtl_sdr data is +-127.5).
+ * Range: everything is float32 with exact power-of-two scaling inside, so the level of the input is immaterial inside the
+ * range: multiplying the window of any (window, buoy) by 2^e leaves lag_int and lag_frac bit-identical and multiplies peak
+ * by 2^(e_i + e_j) exactly, on every route and for every request below (bounds, band, integration of groups at one level,
+ * refinement, the Doppler search; the quality figures and all three outputs under PHAT do not move at all).
+ * tests/test_gpu_dynamic_range.py holds every route to that bit for bit with e drawn per (window, buoy) from -20 ... +14
+ * around rtl_sdr's +-127.5, i.e. from samples of 3e-5 rms to |sample| = 2.95e6.
+ * The top: every route searches |c_s|^2 in float32, c_s = c / out_scale, and the largest |c| an input can produce is that
+ * of a fully coherent window, N |sample|^2.  The squared magnitudes stay finite while
+ *     |sample| < 2^32 sqrt(out_scale / N),
+ * with out_scale = 2^5 at N = 4096 (k_win, k_fwd + k_pair), 2^4 at N = 8192 through k_win8kl, 2^3 at N = 16384 through
+ * k16_fwd + k16_pairs, and 1 (log2 N odd) or 1/2 (log2 N even) through every other kernel at every length:
+ *     N            16     64    256   1024   2048   4096   8192  16384  65536   2^18   2^20   2^22
+ *     |sample| <  7.6e8  3.8e8  1.9e8  9.5e7  9.5e7  3.8e8  1.9e8  9.5e7  1.2e7  5.9e6  3.0e6  1.5e6
+ *   (N = 4096, 8192 and 16384 through the generic kernels -- "generic4096", batches that k_win8kl / k16_* do not take --:
+ *   4.7e7, 4.7e7 and 2.4e7; the lengths between follow the formula.)  Fully coherent windows (127.5 + 127.5j) 2^k are
+ *   tested at the largest k below each bound and at k = 14 on every route.  Beyond the bound |c_s|^2 overflows and the
+ *   outputs carry no meaning.
+ *   integrate = K sums K squared magnitudes: divide the bound by K^(1/4).  The quality figures form the energy product
+ *   (N |sample|^2)^2 and the fourth power of the stored spectra in float32: |sample| < 2^32 / sqrt(N) at every length
+ *   (6.7e7 at N = 4096, 4.7e7 at 8192, 2.7e8 at 256).
+ * The bottom: the three taps must stay normal float32 numbers, |c| / out_scale > 2^-63 at the peak and its neighbours;
+ *   2^-20 x rtl_sdr's level on both buoys of a pair (|c|^2 near 2^-46 at N = 4096) is tested and exact.
  */
 int rmx_xcorr_batch(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                     int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);

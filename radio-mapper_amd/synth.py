@@ -36,6 +36,9 @@ def make_windows(n_windows: int, n_buoys: int, n_samples: int, sample_rate_hz: f
     """Returns (iq complex64 [W][B][N], delays float64 [W][B]) and, with return_u8, also the raw
     interleaved uint8 [W][B][2N] that decodes (u8 - 127.5) to exactly ``iq``.
 
+    quantise=False keeps the float32 samples (full mantissas) but still clips both parts to +-127.5, the
+    range of the decoded uint8 grid: the level of the output is the same either way.
+
     True lag of pair (i, j) is delays[:, j] - delays[:, i] (buoy2 - buoy1, tdoa_processor.py:51).
     delays: optional [W][B] true delays in samples (default: uniform in +-max_delay).
     doppler_cps: optional [W][B] (or [B]) frequency offsets in cycles/sample applied per buoy as
