@@ -216,6 +216,38 @@ int rmx_xcorr_batch_weighted(rmx_ctx* ctx, const void* iq, int n_windows, const 
                              const int32_t* lag_bounds, int bounds_per_window,
                              int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
 
+/* Several bands per window over ONE set of forward spectra: every window is correlated under n_bands bands -- one per
+ * emitter heard in the capture -- for B + n_bands P transforms and one upload of the samples, where n_bands repeated
+ * windows through rmx_xcorr_batch_weighted cost n_bands (B + P) transforms and n_bands times the input bytes.
+ *   band_cps    host double [lo, hi] in cycles per sample: [n_windows][n_bands][2] when bands_per_window is non-zero, else
+ *               [n_bands][2] shared by every window.  Never NULL.  Every band obeys rmx_xcorr_batch_weighted's rules
+ *               (finite, -0.5 <= lo <= hi <= 0.5, keeps at least one bin; no wrap across +-fs/2).
+ *   n_bands     1 .. 64.
+ *   weighting, lag_bounds, bounds_per_window   exactly as in rmx_xcorr_batch_weighted.  The bounds are per (window, pair)
+ *               and shared by that window's bands: they come from the geometry, not from the emitter.
+ *   lag_int, lag_frac, peak   [n_windows][n_bands][n_pairs].
+ * Definition: slot (w, m, q) is slot (w, q) of rmx_xcorr_batch_weighted called with band[w][m] (band[m] when shared) and
+ *   otherwise the same arguments: the same peak rule, sliced rule, parity statement (tests/bands_ref.py stacks
+ *   tests/weighted_ref.py per band) and range statement.  The mask is a 0/1 weight, so it is applied where the product
+ *   X_j conj(X_i) is formed instead of where the spectra are stored; the forward kernels run once per (window, buoy),
+ *   unmasked (under PHAT: whitened), and the pair kernels walk n_bands virtual windows per window.
+ *   It takes the per-transform kernels at every batch size, as the weighted call does; beyond L = small_maxl always the
+ *   product-on-load inverse rows, never g_rows_anchor or g_rows_fused.
+ * n_bands == 1 IS rmx_xcorr_batch_weighted with the same arguments: the same kernels, bit-identical outputs.
+ * Refusals (RMX_E_INVAL, the text in rmx_last_error, nothing staged or written), in this order: a NULL buffer (band_cps
+ *   included); n_bands outside 1 .. 64; rmx_xcorr_batch_weighted's weighting and band checks, the text naming the window and
+ *   the band index; the batch shape (n_windows, pairs, n_pairs); rmx_xcorr_batch_bounded's checks.
+ *   n_windows == 0 or n_pairs == 0 returns RMX_OK and writes nothing.
+ * Every flag (RMX_IN_DEVICE, RMX_OUT_DEVICE, RMX_IN_U8), the custom pair lists and the chunking work as in
+ * rmx_xcorr_batch_weighted.  The library copies the bands and the bounds through its own staging: the caller may reuse its
+ * arrays as soon as the call returns, with RMX_OUT_DEVICE too.
+ * There is no integration, refinement or quality here: rmx_xcorr_batch_bands sums over no windows, is not refined and
+ * reports no quality. */
+int rmx_xcorr_batch_bands(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                          const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
+                          const int32_t* lag_bounds, int bounds_per_window,
+                          int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
+
 /* Noncoherent integration: rmx_xcorr_batch_weighted with ONE peak search per group of `integrate` consecutive windows,
  * on the lag-by-lag sum of the windows' squared correlation magnitudes.  Two receivers with free-running oscillators stay
  * phase-coherent over a short segment only (a frequency offset rotates the cross-spectrum and the coherent peak of a long

@@ -563,7 +563,9 @@ __device__ __forceinline__ void pair_small_integ(const float2* __restrict__ spec
     }
 }
 
-// LB: empty, one LagBounds (the bounded instantiation, lag_bounds.hpp), or <LagBounds, Integrate> (integrate.hpp)
+// LB: empty, one LagBounds (the bounded instantiation, lag_bounds.hpp), <LagBounds, Integrate> (integrate.hpp), or
+// <BandSet> / <LagBounds, BandSet> (the banded ones, xspec_bands.hpp: a workgroup is a (VIRTUAL window, pair), first_window
+// the chunk's first virtual window)
 template <class... LB>
 __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ spec, const float2* __restrict__ spec_j,
                                                           const float2* __restrict__ tw,
@@ -577,7 +579,7 @@ __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ 
                          integ_bounds(lb_pack...), integ_windows(lb_pack...));
         return;
     }
-    constexpr bool BOUNDED = sizeof...(LB) > 0;
+    constexpr bool BOUNDED = kHasBounds<LB...>, BANDED = kBanded<LB...>;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     float2* x = reinterpret_cast<float2*>(gsm);
     const int L = 1 << logL, tid = threadIdx.x, nthr = blockDim.x;
@@ -585,10 +587,25 @@ __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ 
     int* sk = reinterpret_cast<int*>(sv + nthr);
     const int wl = blockIdx.x / n_pairs, q = blockIdx.x % n_pairs;
     const GPair pr = pairs[q];
+    if constexpr (BANDED) {   // both spectra are the real window's; a bin outside the band loads nothing: its product is +0
+        const BandSet bs = band_set_of(lb_pack...);
+        const XBand bd = band_of_virtual(bs, wl);
+        const int wr = band_real_window(bs, wl);
+        const float2* xi = spec + ((long)wr * n_buoys + pr.i) * L;
+        const float2* xj = spec_j + ((long)wr * n_buoys + pr.j) * L;
+        batched<4>(tid, L, nthr,
+                   [&](int n) -> float4 {
+                       if (!xband_keeps(bd, xbin_small(n, logL), L - 1)) return make_float4(0.f, 0.f, 0.f, 0.f);
+                       const float2 a = xj[n], b = xi[n];
+                       return make_float4(a.x, a.y, b.x, b.y);
+                   },
+                   [&](int n, float4 v) { x[lp(n)] = g_cmulc(make_float2(v.x, v.y), make_float2(v.z, v.w)); });
+    } else {
     const float2* xi = spec + ((long)wl * n_buoys + pr.i) * L;
     const float2* xj = spec_j + ((long)wl * n_buoys + pr.j) * L;
     batched<4>(tid, L, nthr, [&](int n) -> float4 { const float2 a = xj[n], b = xi[n]; return make_float4(a.x, a.y, b.x, b.y); },
                [&](int n, float4 v) { x[lp(n)] = g_cmulc(make_float2(v.x, v.y), make_float2(v.z, v.w)); });   // X_j conj(X_i)
+    }
     __syncthreads();
     lds_dit_inv(x, logL, tw, tid, nthr);
     float best = -1.0f;
@@ -646,7 +663,8 @@ __device__ __forceinline__ float2 big_tw(long m, int lo_bits, const float2* __re
 //        X_j[row] conj(X_i[row]) from the spectra (slot = window-in-chunk * n_pairs + pair), which
 //        saves the product's own pass through HBM; the result is written to `data`.
 // LOGR > 0: the row length as a compile-time constant (pass loops unrolled, strides and LDS offsets immediates)
-// WT (forward only): empty, or one XWeight (the weighted instantiation, xspec_weight.hpp)
+// WT: empty; forward: or one XWeight (the weighted instantiation, xspec_weight.hpp); inverse: or one BandSet (the banded
+// instantiation, xspec_bands.hpp: a slot is then VIRTUAL window * n_pairs + pair)
 template <bool FWD, bool TW, bool PROD = false, int LOGR = 0, class... WT>
 __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, const float2* __restrict__ tw, int logR_arg,
                                                     int n_rows, int row_bits, long Ltot, int lo_bits,
@@ -721,10 +739,26 @@ __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, c
             const long slot = ridx >> row_bits;
             const int wl = (int)(slot / n_pairs), q = (int)(slot % n_pairs);
             const GPair pr = pairs[q];
+            if constexpr (sizeof...(WT) > 0) {   // banded: the real window's rows; a bin outside the band loads nothing (+0)
+                const BandSet bs = band_set_of(wt_pack...);
+                const XBand bd = band_of_virtual(bs, wl);
+                const int wr = band_real_window(bs, wl);
+                const int k1 = xbin_rows_k1(rib, row_bits), lmask = (int)(Ltot - 1);
+                const float2* xi = spec + (((long)wr * n_buoys + pr.i) * n_rows + rib) * R;
+                const float2* xj = spec_j + (((long)wr * n_buoys + pr.j) * n_rows + rib) * R;
+                batched<kProdBatch>(tid, R, tpr,
+                           [&](int n) -> float4 {
+                               if (!xband_keeps(bd, xbin_rows(k1, n, row_bits, logR), lmask)) return make_float4(0.f, 0.f, 0.f, 0.f);
+                               const float2 u = xj[n], v = xi[n];
+                               return make_float4(u.x, u.y, v.x, v.y);
+                           },
+                           [&](int n, float4 v) { x[lp(n)] = g_cmulc(make_float2(v.x, v.y), make_float2(v.z, v.w)); });
+            } else {
             const float2* xi = spec + (((long)wl * n_buoys + pr.i) * n_rows + rib) * R;
             const float2* xj = spec_j + (((long)wl * n_buoys + pr.j) * n_rows + rib) * R;
             batched<kProdBatch>(tid, R, tpr, [&](int n) -> float4 { const float2 u = xj[n], v = xi[n]; return make_float4(u.x, u.y, v.x, v.y); },
                        [&](int n, float4 v) { x[lp(n)] = g_cmulc(make_float2(v.x, v.y), make_float2(v.z, v.w)); });
+            }
         }
         __syncthreads();
         fft_dit_inv<0>(x, logR, twl, tid, tpr, lds, lds, own16 ? tw16 : nullptr);

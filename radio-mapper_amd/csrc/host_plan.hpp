@@ -210,6 +210,53 @@ inline long generic_chunk_windows(int n_buoys, long L, int max_windows, long bud
     return chunk;
 }
 
+// ---- several bands per window (rmx_xcorr_batch_bands): the buffer arithmetic ---------------------------------------------
+// A banded call correlates every real window under n_bands bands: a chunk of `chunk` real windows is chunk * n_bands
+// VIRTUAL windows to the pair kernels, and every per-slot buffer holds chunk * n_bands * n_pairs slots instead of
+// chunk * n_pairs -- the four-step products, tile records and halo rows, and (per call) the three outputs.  plan_bands is
+// the one place that arithmetic lives: it SHRINKS the chunk until a chunk's virtual windows are at most `max_vwindows`
+// (the cap generic_chunk_windows puts on a chunk's windows) and, on the four-step route, its spectra and products fit
+// `budget_bytes`, and it STATES the bytes each buffer must then hold; the launch code allocates exactly those and launches
+// at most `chunk` windows at a time (a launch sized by one rule over a buffer sized by another ran past it).
+// n_bands = 1 leaves the chunk as it is.
+constexpr long kGenericBudgetBytes = 32L << 30;   // spectra + products of a chunk (generic_chunk_windows)
+constexpr long kGenericMaxChunk = 4096;
+constexpr long kMaxGridY = 65535;                 // the largest second grid dimension of a launch
+struct BandsPlan {
+    long chunk = 0;          // real windows per chunk, >= 1
+    long vwindows = 0;       // virtual windows of a full chunk: chunk * n_bands
+    long slots = 0;          // slots of a full chunk: vwindows * n_pairs
+    size_t prod_bytes = 0;   // four-step: slots * L * 8 (g_prod); 0 on the other routes
+    size_t rec_bytes = 0;    // four-step: slots * col_tiles * rec_size (g_rec)
+    size_t halo_bytes = 0;   // four-step: slots * col_tiles * 2 * 4 << logL1 (g_halo)
+    size_t out_elems = 0;    // elements of each of the call's three outputs: n_windows * n_bands * n_pairs
+};
+inline BandsPlan plan_bands(long chunk, long n_windows, int n_bands, int n_buoys, int n_pairs, long L, bool four_step, long col_tiles,
+                            int logL1, size_t rec_size, long budget_bytes = kGenericBudgetBytes, long max_vwindows = kGenericMaxChunk) {
+    BandsPlan b;
+    const long nb = n_bands > 0 ? n_bands : 1, np = n_pairs > 0 ? n_pairs : 0;
+    if (chunk < 1) chunk = 1;
+    if (nb > 1) {
+        if (chunk * nb > max_vwindows) chunk = max_vwindows / nb;
+        if (four_step) {
+            const long per_win = ((long)n_buoys + nb * np) * L * 8;
+            if (per_win > 0 && chunk > budget_bytes / per_win) chunk = budget_bytes / per_win;
+            if (np > 0 && chunk * nb * np > kMaxGridY) chunk = kMaxGridY / (nb * np);   // g_cols_inv: one grid row per slot
+        }
+        if (chunk < 1) chunk = 1;
+    }
+    b.chunk = chunk;
+    b.vwindows = chunk * nb;
+    b.slots = b.vwindows * np;
+    if (four_step) {
+        b.prod_bytes = (size_t)b.slots * (size_t)L * 8;
+        b.rec_bytes = (size_t)b.slots * (size_t)col_tiles * rec_size;
+        b.halo_bytes = ((size_t)b.slots * (size_t)col_tiles * 2 * sizeof(float)) << logL1;
+    }
+    b.out_elems = (size_t)(n_windows > 0 ? n_windows : 0) * (size_t)nb * (size_t)np;
+    return b;
+}
+
 // ---- N = 4096: fused kernel or per-transform kernels, and how many pairs per workgroup -----------------------------
 // Estimated microseconds, fitted to tools/exp_small4096.py on MI355X: 2.6 per transform of the
 // fused kernel (one workgroup per window, a round = one window on every CU); 3.5 per round of forward workgroups (two per
@@ -274,6 +321,7 @@ struct RouteCall {
     bool bounded = false, weighted = false;       // XcorrCall::bounded(), XcorrCall::weighted()
     int integ = 1;
     bool in_dev = true;
+    int n_bands = 1;                              // rmx_xcorr_batch_bands: the pair kernels see n_windows * n_bands virtual windows
 };
 struct RoutePlan {
     Route route = kRoutePer4096;
@@ -324,7 +372,7 @@ inline RoutePlan plan_route4096(const RouteCaps& k, const RouteCall& a) {
     // a weighted call weights the spectra where k_fwd stores them: the per-transform kernels at every batch size, never
     // k_win (whose spectra stay inside the workgroup); an integrated call sums over windows inside k_pair_str: the same
     // kernels, with one work item per (group, pair)
-    if (a.weighted) { (void)split(W / a.integ, &ppb_small); small = true; }
+    if (a.weighted) { (void)split((long)W * a.n_bands / a.integ, &ppb_small); small = true; }
     // The same arithmetic for the LAST round of a larger batch: W = k CUs + r windows cost the fused kernel k + 1 rounds
     // (300 windows of 8 buoys: two rounds, 184 us); when the model says the r windows are cheaper through the
     // per-transform kernels than a round of the fused one, they go there (after the k full rounds, on the same stream).
@@ -412,7 +460,12 @@ inline RoutePlan plan_route(const RouteCaps& k, const RouteCall& a) {
     }
     if (!a.weighted && k.wfused && !a.bounded) { p.route = kRouteWinFused; return p; }
     p.route = (1L << k.logL) <= k.small_maxl ? kRouteSmallL : kRouteFourStep;
-    p.chunk = k.g_chunk / a.integ * a.integ;   // (integrated call: a chunk holds whole groups -- never a silent split of a group)
+    p.chunk = k.g_chunk / a.integ * a.integ;
+    // banded call (never integrated): the chunk whose virtual windows the per-slot buffers hold (plan_bands: the sizes)
+    if (a.n_bands > 1) {
+        const bool four_step = p.route == kRouteFourStep;
+        p.chunk = (int)plan_bands(k.g_chunk, W, a.n_bands, k.n_buoys, a.n_pairs, 1L << k.logL, four_step, 0, 0, 0).chunk;
+    }   // (integrated call: a chunk holds whole groups -- never a silent split of a group)
     if (p.chunk == 0) p.refused = kRefuseIntegChunk;
     else if (a.integ > 1 && p.route == kRouteFourStep && k.col_tile > (long)k.integ_max_per_thread * k.cols_threads)
         p.refused = kRefuseIntegTile;

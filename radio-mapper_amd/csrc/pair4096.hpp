@@ -11,6 +11,7 @@
 #include "integrate.hpp"
 #include "kwin.hpp"           // the LDS carve (kLdsXchg, kLdsTw2, kLdsBytes) and the table loaders
 #include "lag_bounds.hpp"
+#include "xspec_bands.hpp"
 #include "xspec_weight.hpp"
 
 namespace rmx {
@@ -92,14 +93,15 @@ __global__ __launch_bounds__(kThreads, 4) void k_fwd(const void* __restrict__ iq
 //   out arrays are indexed [(first_window + wl) * n_pairs + item.out].
 // Streaming variant (k_pair_str, option "resident" = 0): two workgroups per CU (<= 128 VGPRs); TW1,
 // X_i and X_j are re-read every pair.  The resident variant is k_pair_res below.
-template <bool BOUNDED>
+template <bool BOUNDED, class... BS>   // BS: empty, or one BandSet (the banded instantiations, xspec_bands.hpp)
 __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const float4* __restrict__ spec_j,
                                           const float4* __restrict__ tw1_g,
                                           const float2* __restrict__ tw2_g, const PairItem* __restrict__ items,
                                           const int* __restrict__ part_begin, int n_parts, int n_buoys,
                                           int n_pairs, int xcd_map, long first_window, float out_scale,
                                           int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                          float* __restrict__ peak, int i_wrap, LagBounds lb) {
+                                          float* __restrict__ peak, int i_wrap, LagBounds lb, BS... bs_pack) {
+    constexpr bool BANDED = sizeof...(BS) > 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* xl = reinterpret_cast<float2*>(smem);
     float2* tw2_lds = reinterpret_cast<float2*>(smem + kLdsXchg);
@@ -133,8 +135,21 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
     const float sgn = p ? -1.0f : 1.0f;
     const int it_begin = part_begin[part];
     const int it_end = part_begin[part + 1];
-    const long wbase = (long)wl * n_buoys;
-    const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wl) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
+    // banded: wl is a VIRTUAL window (real window wl / n_bands, band wl % n_bands); both spectra are the real window's,
+    // and bit s of `keep` says whether this thread's slot s lies in the band (role C: xspec_weight.hpp's k_fwd map)
+    int wr = wl;
+    [[maybe_unused]] unsigned keep = 0xffffu;
+    if constexpr (BANDED) {
+        const BandSet bs = band_set_of(bs_pack...);
+        wr = band_real_window(bs, wl);
+        const XBand bd = band_of_virtual(bs, wl);
+        const int kb = RMX_XBIN_KFWD(p, u);
+        keep = 0u;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) keep |= (xband_keeps(bd, kb + kXbinKfwdSlot * s, kL - 1) ? 1u : 0u) << s;
+    }
+    const long wbase = (long)wr * n_buoys;
+    const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wr) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
     float4 sa[8], sb[8];   // X_i (anchor) and X_j of the pair about to be processed
     PairItem pi = items[it_begin < it_end ? it_begin : 0];
     if (it_begin < it_end) {
@@ -157,6 +172,11 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
             const float4 b = sb[j];
             v[2 * j] = make_float2(b.y * a.x - b.x * a.y, b.x * a.x + b.y * a.y);
             v[2 * j + 1] = make_float2(b.w * a.z - b.z * a.w, b.z * a.z + b.w * a.w);
+        }
+        if constexpr (BANDED) {       // the band: a dropped bin's product is +0
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                if (!((keep >> s) & 1u)) v[s] = make_float2(0.0f, 0.0f);
         }
         dft16(v);                     // k2 -> n0   (role C)
         mul_tw2(v, tw2_lds, u & 15);  // W_256^(k1*n0)
@@ -477,13 +497,14 @@ __device__ __forceinline__ void resolve_pair(const float* magbuf, const float2* 
     peak[out_pos] = b;
 }
 
-template <class... LB>   // LB: empty, or one LagBounds (the bounded instantiation)
+// LB: empty, one LagBounds (the bounded instantiation), or <BandSet> / <LagBounds, BandSet> (the banded ones, xspec_bands.hpp)
+template <class... LB>
 __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     const float4* __restrict__ spec, const float4* __restrict__ spec_j, const float4* __restrict__ tw1_g, const float2* __restrict__ tw2_g,
     const PairItem* __restrict__ items, const int* __restrict__ part_begin, int n_parts, int n_buoys, int n_pairs,
     int xcd_map, long first_window, float out_scale, int* __restrict__ lag_int, float* __restrict__ lag_frac,
     float* __restrict__ peak, int /* was dbg_rt */, int i_wrap, LB... lb_pack) {
-    constexpr bool BOUNDED = sizeof...(LB) > 0;
+    constexpr bool BOUNDED = kHasBounds<LB...>, BANDED = kBanded<LB...>;
     const LagBounds lb = lag_bounds_of(lb_pack...);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* xl = reinterpret_cast<float2*>(smem);
@@ -516,8 +537,21 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     const int it_begin = part_begin[part];
     const int it_end = part_begin[part + 1];
     if (it_begin >= it_end) return;
-    const long wbase = (long)wl * n_buoys;
-    const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wl) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
+    // banded: wl is a VIRTUAL window (real window wl / n_bands, band wl % n_bands); both spectra are the real window's,
+    // and bit s of `keep` says whether this thread's slot s lies in the band (role C: xspec_weight.hpp's k_fwd map)
+    int wr = wl;
+    [[maybe_unused]] unsigned keep = 0xffffu;
+    if constexpr (BANDED) {
+        const BandSet bs = band_set_of(lb_pack...);
+        wr = band_real_window(bs, wl);
+        const XBand bd = band_of_virtual(bs, wl);
+        const int kb = RMX_XBIN_KFWD(p, u);
+        keep = 0u;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) keep |= (xband_keeps(bd, kb + kXbinKfwdSlot * s, kL - 1) ? 1u : 0u) << s;
+    }
+    const long wbase = (long)wr * n_buoys;
+    const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wr) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
     const long obase = (first_window + wl) * (long)n_pairs;
     // the window whose lag bounds apply (one launch for all hypotheses: the REAL window; the output slot stays virtual)
     [[maybe_unused]] const long lbw = first_window + (i_wrap > 0 ? wl % i_wrap : wl);
@@ -544,6 +578,11 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
             const float4 b = sb[j];
             v[2 * j] = make_float2(b.y * a.x - b.x * a.y, b.x * a.x + b.y * a.y);
             v[2 * j + 1] = make_float2(b.w * a.z - b.z * a.w, b.z * a.z + b.w * a.w);
+        }
+        if constexpr (BANDED) {   // the band: a dropped bin's product is +0
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                if (!((keep >> s) & 1u)) v[s] = make_float2(0.0f, 0.0f);
         }
         if (it + 1 < it_end) {   // request the next pair's spectra: a whole pair of compute hides it
             pi = items[it + 1];
@@ -623,13 +662,16 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     spec, spec_j, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,      \
         lag_int, lag_frac, peak, i_wrap
 
-// LB: empty, one LagBounds (the bounded instantiation), or <LagBounds, Integrate> (the integrating one, integrate.hpp:
-// first_window is then the chunk's first GROUP; spec_j and i_wrap are not used)
+// LB: empty, one LagBounds (the bounded instantiation), <LagBounds, Integrate> (the integrating one, integrate.hpp:
+// first_window is then the chunk's first GROUP; spec_j and i_wrap are not used), or <BandSet> / <LagBounds, BandSet> (the
+// banded ones, xspec_bands.hpp: first_window is then the chunk's first VIRTUAL window)
 template <class... LB>
 __global__ __launch_bounds__(kThreads, kIntegrating<LB...> ? 2 : 4) void k_pair_str(RMX_PAIR_ARGS, LB... lb) {
     if constexpr (kIntegrating<LB...>) {
         pair_body_integ(spec, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
                         lag_int, lag_frac, peak, integ_bounds(lb...), integ_windows(lb...));
+    } else if constexpr (kBanded<LB...>) {
+        pair_body<kHasBounds<LB...>>(RMX_PAIR_PASS, lag_bounds_of(lb...), band_set_of(lb...));
     } else {
         pair_body<(sizeof...(LB) > 0)>(RMX_PAIR_PASS, lag_bounds_of(lb...));
     }

@@ -26,6 +26,7 @@
 #include "host_plan.hpp"
 #include "lag_bounds.hpp"
 #include "xspec_weight.hpp"
+#include "xspec_bands.hpp"
 #include "integrate.hpp"
 #include "refine.hpp"
 #include "quality.hpp"
@@ -65,6 +66,7 @@ struct rmx_ctx {
         decltype(&rmx::gen::g_rows<true, false>) rows_fwd = nullptr;   // g_rows compiled for this row length (or the run-time one)
         decltype(&rmx::gen::g_rows<true, false, false, 0, rmx::XWeight>) rows_fwd_wt = nullptr;         // its weighted instantiation
         decltype(&rmx::gen::g_rows<false, true, true>) rows_inv = nullptr;
+        decltype(&rmx::gen::g_rows<false, true, true, 0, rmx::BandSet>) rows_inv_bs = nullptr;          // its banded instantiation (rmx_xcorr_batch_bands)
         decltype(&rmx::gen::g_rows_anchor<9>) rows_anchor = nullptr;   // inverse rows with a resident anchor (default pair list)
         decltype(&rmx::gen::g_rows_fused<2, 9>) fused = nullptr;       // four-step: both row passes in one kernel (n_buoys <= 4)
         decltype(&rmx::gen::g_rows_fused<2, 9>) fused_def = nullptr;   // the same for the default plan (pair loop unrolled)
@@ -155,7 +157,7 @@ struct rmx_ctx {
                                                          // k_caf_select_fd, then [slots] dop_frac of a host-pointer call
     std::vector<double> caf_grid;
     // the caller's lag windows (rmx_xcorr_batch_bounded) and its bands as signed bins (rmx_xcorr_batch_weighted): the
-    // device copies that a call's XcorrCall points into
+    // device copies that a call's XcorrCall points into (rmx_xcorr_batch_bands: the full band, then the band set)
     DevStage lb_stage, band_stage;
     rmx::RefPair* rf_pairs = nullptr;          // k_refine's and k_quality's pair list (refine.hpp): the plan's pairs in output order
     std::vector<int32_t> rf_pairs_plan;
@@ -185,17 +187,21 @@ static thread_local std::string g_create_error;
 struct XcorrCall {
     LagBounds lb{nullptr, 0, 0, 0};          // lag intervals on the device (rmx_xcorr_batch_bounded), or none
     XWeight wt{nullptr, 0, 0, 0, 0, 0.0f};   // bands as signed bins on the device + weighting (rmx_xcorr_batch_weighted)
+    BandSet bs{nullptr, 0, 0, 1};            // several bands per window on the device (rmx_xcorr_batch_bands): the pair kernels
+                                             // then walk n_bands virtual windows per window, lb and the outputs are per virtual
+                                             // window, and wt is the full band (PHAT) or none
     int integ = 1;                           // windows per group (rmx_xcorr_batch_integrated): the bounds and the outputs
                                              // are then per GROUP, the bands stay per window, a chunk holds whole groups
     int refine = 0;                          // U of rmx_xcorr_batch_refined: k_refine behind every chunk's pair kernels, or 0
     bool bounded() const { return lb.b != nullptr; }         // the bounded instantiations of the peak-searching kernels
     bool integrated() const { return integ > 1; }            // the integrating instantiations of the pair kernels
+    bool banded() const { return bs.bins != nullptr; }       // the banded instantiations of the kernels that form the product
     float* quality = nullptr;                // rmx_xcorr_batch_quality: [rows][n_pairs][4] on the device (k_quality behind every
                                              // chunk's pair kernels, in front of k_refine), or none
     bool refined() const { return refine > 0; }              // k_refine reads both spectra of a pair from HBM
     bool qualified() const { return quality != nullptr; }    // k_quality does too
     // only the per-transform routes can serve it
-    bool weighted() const { return wt.band != nullptr || integ > 1 || refine > 0 || quality != nullptr; }
+    bool weighted() const { return wt.band != nullptr || bs.bins != nullptr || integ > 1 || refine > 0 || quality != nullptr; }
 };
 
 // Where a ctx's per-transform spectra lie once a chunk's forward kernels have run, and the launchers that write and read
@@ -505,9 +511,10 @@ static auto rows_fwd_fn(int logR, int tpr) {
     return with_one_of<9, 10, 11, 12, 13, 0>(tpr == gen::rows_tpr(1 << logR) ? logR : 0,
                                              [](auto R) { return &gen::g_rows<true, false, false, decltype(R)::value, WT...>; });
 }
+template <class... BS>   // BS: empty, or BandSet for the banded instantiations of the same set
 static auto rows_inv_fn(int logR, int tpr) {
     return with_one_of<9, 10, 11, 12, 13, 0>(tpr == gen::rows_tpr(1 << logR) ? logR : 0,
-                                             [](auto R) { return &gen::g_rows<false, true, true, decltype(R)::value>; });
+                                             [](auto R) { return &gen::g_rows<false, true, true, decltype(R)::value, BS...>; });
 }
 static decltype(GenericKernels::rows_anchor) rows_anchor_fn(int logR, int tpr) {   // (no run-time-length instantiation: null)
     if (tpr != gen::rows_tpr(1 << logR) || logR < 9 || logR > 13) return nullptr;
@@ -587,7 +594,8 @@ static GenericKernels pick_generic_kernels(int n_buoys, int logL, int logL1, int
         k.cols_fwd[1] = cols_fwd_fn<true>(logL1, col_log_t, cols_threads);
         k.rows_fwd = rows_fwd_fn<>(logL2, rows_tpr);
         k.rows_fwd_wt = rows_fwd_fn<XWeight>(logL2, rows_tpr);
-        k.rows_inv = rows_inv_fn(logL2, rows_tpr);
+        k.rows_inv = rows_inv_fn<>(logL2, rows_tpr);
+        k.rows_inv_bs = rows_inv_fn<BandSet>(logL2, rows_tpr);
         if (knobs.get_or("rows_anchor", 1) != 0) k.rows_anchor = rows_anchor_fn(logL2, rows_tpr);
         // both row passes in one kernel when the buoys' spectra rows fit the register file (generic_path.hpp); option
         // fused = 0: never, fused_def = 0: without the unrolled default-plan instantiation
@@ -636,7 +644,8 @@ static int generic_init(rmx_ctx* c) {
         if (rc) return rc;
         c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, 0, 0, 0, 0, 0, c->knobs);
         rc = allow_lds(c, (size_t)gen::lp(L) * 8 + 1024 * 8, g_pair_small<>, g_pair_small<LagBounds>, g_pair_small<LagBounds, Integrate>,
-                       g_fwd_small<false>, g_fwd_small<true>, g_fwd_small<false, XWeight>, g_fwd_small<true, XWeight>);
+                       g_pair_small<BandSet>, g_pair_small<LagBounds, BandSet>, g_fwd_small<false>, g_fwd_small<true>,
+                       g_fwd_small<false, XWeight>, g_fwd_small<true, XWeight>);
         for (int d = 0; d < 2 && rc == RMX_OK; ++d) rc = allow_lds(c, c->gk.wf_lds[d], c->gk.wf[d][0], c->gk.wf[d][1]);
         if (rc) return rc;
     } else {
@@ -669,7 +678,8 @@ static int generic_init(rmx_ctx* c) {
         rc = allow_lds(c, gen_cols_lds(c, c->g_logL1), k.cols_inv, k.cols_inv_lb, k.cols_inv_int, k.cols_fwd[0], k.cols_fwd[1]);
         // (the run-time-length row kernels too, whichever the tables chose)
         if (rc == RMX_OK)
-            rc = allow_lds(c, rows_lds, g_rows<true, false, false>, g_rows<false, true, true>, k.rows_fwd, k.rows_fwd_wt, k.rows_inv, k.rows_anchor);
+            rc = allow_lds(c, rows_lds, g_rows<true, false, false>, g_rows<false, true, true>, k.rows_fwd, k.rows_fwd_wt, k.rows_inv, k.rows_inv_bs,
+                           k.rows_anchor);
         if (rc == RMX_OK) rc = allow_lds(c, gen_fused_lds(1 << c->g_logL2), k.fused);
         if (rc == RMX_OK) rc = allow_lds(c, gen_fused_lds(1 << c->g_logL2, gen::fused_tw_regs(c->n_buoys, c->g_logL2, true)), k.fused_def);
         if (rc) return rc;
@@ -771,7 +781,8 @@ static int generic_init(rmx_ctx* c) {
 //                  run (g_win_fused, g_win_scr never touch them: an 8-buoy, 4096-window engine of 8192-sample windows
 //                  would otherwise pin 15 GB it never uses)
 // A failed hipMalloc halves the chunk and retries (down to one window) instead of giving up.
-static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool need_pairbufs = true) {
+// n_bands > 1 (rmx_xcorr_batch_bands): the pair-dependent buffers hold the slots host::plan_bands states for the chunk.
+static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool need_pairbufs = true, int n_bands = 1) {
     using namespace gen;
     const long L = 1L << c->g_logL;
     const bool four_step = L > kGenSmallMaxL;
@@ -783,7 +794,9 @@ static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool n
         c->g_slots_alloc = 0;
     };
     for (;;) {
-        const long items = (long)c->g_chunk * c->n_buoys, slots = (long)c->g_chunk * n_pairs;
+        const long parts = four_step ? (1L << c->g_logL2) >> host_col_log_t(c, c->g_logL1) : 0;   // one record per column tile
+        const host::BandsPlan bp = host::plan_bands(c->g_chunk, 0, n_bands, c->n_buoys, n_pairs, L, four_step, parts, c->g_logL1, sizeof(GTile));
+        const long items = (long)c->g_chunk * c->n_buoys, slots = bp.slots;   // (n_bands = 1: g_chunk * n_pairs)
         bool ok = true;
         auto grab = [&](void** p, size_t bytes) {
             if (!ok) return;
@@ -801,10 +814,9 @@ static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool n
             c->g_pair_bytes = 0;
             c->g_slots_alloc = 0;
             const size_t before = c->g_dyn_bytes;
-            const long parts = (1L << c->g_logL2) >> host_col_log_t(c, c->g_logL1);   // one record per column tile
-            grab((void**)&c->g_prod, (size_t)slots * L * 8);
-            grab((void**)&c->g_rec, (size_t)slots * parts * sizeof(GTile));
-            grab((void**)&c->g_halo, (size_t)slots * parts * 2 * sizeof(float) << c->g_logL1);
+            grab((void**)&c->g_prod, bp.prod_bytes);
+            grab((void**)&c->g_rec, bp.rec_bytes);
+            grab((void**)&c->g_halo, bp.halo_bytes);
             c->g_pair_bytes = c->g_dyn_bytes - before;
             if (ok) c->g_slots_alloc = slots;
         }
@@ -882,7 +894,12 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     const long L = 1L << logL;
     const int hs = logL / 2;
     const float out_scale = std::ldexp(1.0f, -(logL - 2 * hs));
-    const int slots = wc * n_pairs;
+    // banded call: n_bands virtual windows per window, from virtual window v0 on; every slot count below is virtual
+    const int nb = call.banded() ? call.bs.n_bands : 1;
+    const long v0 = (long)w0 * nb;
+    BandSet bs = call.bs;
+    bs.w0 = w0;
+    const int slots = wc * nb * n_pairs;
     const float2* spec_j = use_rot ? c->g_spec_r : c->g_spec;
     if (L <= kGenSmallMaxL) {
         const int sthr = gen_small_threads(L);
@@ -892,6 +909,7 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
         };
         if (call.integrated())   // one workgroup per (group, pair); w0 and wc are whole groups, the bounds per group
             return go(g_pair_small<LagBounds, Integrate>, slots / call.integ, (long)(w0 / call.integ), call.lb, Integrate{call.integ});
+        if (call.banded()) return call.bounded() ? go(g_pair_small<LagBounds, BandSet>, slots, v0, call.lb, bs) : go(g_pair_small<BandSet>, slots, v0, bs);
         if (call.bounded()) return go(g_pair_small<LagBounds>, slots, (long)w0, call.lb);
         return go(g_pair_small<>, slots, (long)w0);
     }
@@ -905,7 +923,11 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     const bool all_pairs = c->plan_all_pairs && n_pairs == B * (B - 1) / 2;
     // row pass ([product on load] rows(L2)^-1 * conj W_L^(n2 k1)), column pass (-> tile records + halo), reduction
     int rc;
-    if (fused) {
+    if (call.banded()) {
+        // always the product-on-load rows: their banded instantiation masks the product (never g_rows_anchor / g_rows_fused)
+        rc = launch(c, kTkRowsInv, k.rows_inv_bs, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), rlds, c->g_prod, c->g_tw2, l2, L1,
+                    l1, L, c->g_lo_bits, c->g_thi, c->g_tlo, 1.0f, rows, c->g_spec, spec_j, c->g_pairs, n_pairs, B, tpr, bs);
+    } else if (fused) {
         // g_spec holds the column pass's output: forward rows, products and inverse rows in one kernel
         const long units = (long)wc * L1;
         const int upw = kGThreads / (L2 >> 4 > 0 ? L2 >> 4 : 1);
@@ -930,7 +952,7 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     // slot -> group w0 / K + slot / P).  Otherwise K = 1: slot -> window w0 + slot / P, pair slot % P.
     const int oslots = slots / call.integ;
     LagBounds lb = call.lb;
-    lb.w0 = w0 / call.integ;
+    lb.w0 = v0 / call.integ;   // (banded: the bounds are per virtual window)
     lb.n_pairs = n_pairs;
     auto cols = [&](auto kern, auto... tail) {
         return launch(c, kTkColsInv, kern, dim3(ntiles, oslots), dim3(cthr), clds, c->g_prod, c->g_tw1, l1, l2, c->g_rec, c->g_halo, tail...);
@@ -979,7 +1001,9 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
                      bool use_rot, int n_bins = 1) {
     const int n_parts = c->plan_n_parts;
     const int i_wrap = n_bins > 1 ? wc : 0;     // (all hypotheses in one launch: virtual window = hypothesis * wc + window)
-    wc *= n_bins;
+    const int nb = call.banded() ? call.bs.n_bands : 1;   // (banded call: virtual window = window * n_bands + band)
+    const long first = (long)w0 * nb;
+    wc *= n_bins * nb;
     const int xcd_map = (wc % 8 == 0) ? 1 : 0;
     const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
     // the streaming and the resident kernel (which keeps one unused int argument), each with or without its trailing structs
@@ -989,7 +1013,7 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
     };
     auto res = [&](auto kern, auto... lb) {
         return launch(c, kTkPair4096, kern, dim3(wc * n_parts), dim3(kThreads), kLdsResBytes, c->d_spec, spec_j, c->d_tw1, c->d_tw2,
-                      c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, (long)w0, out_scale, d_lag, d_frac, d_peak, 0, i_wrap,
+                      c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, first, out_scale, d_lag, d_frac, d_peak, 0, i_wrap,
                       lb...);
     };
     if (call.integrated()) {
@@ -997,6 +1021,12 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
         // groups, the bounds per group
         const int gc = wc / call.integ;
         return str(k_pair_str<LagBounds, Integrate>, gc, (gc % 8 == 0) ? 1 : 0, (long)(w0 / call.integ), 0, call.lb, Integrate{call.integ});
+    }
+    if (call.banded()) {   // the banded instantiations: both spectra of a virtual window are its real window's
+        BandSet bs = call.bs;
+        bs.w0 = w0;
+        if (c->resident) return call.bounded() ? res(k_pair_res<LagBounds, BandSet>, call.lb, bs) : res(k_pair_res<BandSet>, bs);
+        return call.bounded() ? str(k_pair_str<LagBounds, BandSet>, wc, xcd_map, first, 0, call.lb, bs) : str(k_pair_str<BandSet>, wc, xcd_map, first, 0, bs);
     }
     if (c->resident) return call.bounded() ? res(k_pair_res<LagBounds>, call.lb) : res(k_pair_res<>);
     return call.bounded() ? str(k_pair_str<LagBounds>, wc, xcd_map, (long)w0, i_wrap, call.lb) : str(k_pair_str<>, wc, xcd_map, (long)w0, i_wrap);
@@ -1119,7 +1149,7 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps
     const int n_pairs = rq.n_pairs, logL = c->g_logL, hs = logL / 2;
     // device buffers on first need; a failed allocation halves g_chunk, and the plan follows (the route does not depend on it)
     auto ensure = [&](bool need_spec, bool need_pairbufs) -> int {
-        const int rc_e = generic_ensure(c, n_pairs, need_spec, need_pairbufs);
+        const int rc_e = generic_ensure(c, n_pairs, need_spec, need_pairbufs, rq.n_bands);
         if (rc_e == RMX_OK && c->g_chunk != caps.g_chunk) { caps.g_chunk = c->g_chunk; plan = plan_route(caps, rq); }
         return rc_e;
     };
@@ -1275,8 +1305,9 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
         // every instantiation of the N = 4096 kernels: plain, weighted (rmx_xcorr_batch_weighted: k_fwd) and bounded
         // (rmx_xcorr_batch_bounded: the peak-searching ones)
         int rc_l = allow_lds(c, kLdsBytes, k_fwd<false>, k_fwd<true>, k_fwd<false, XWeight>, k_fwd<true, XWeight>, k_pair_str<>,
-                             k_pair_str<LagBounds>);
-        if (rc_l == RMX_OK) rc_l = allow_lds(c, kLdsResBytes, k_pair_res<>, k_pair_res<LagBounds>);
+                             k_pair_str<LagBounds>, k_pair_str<BandSet>, k_pair_str<LagBounds, BandSet>);
+        if (rc_l == RMX_OK)
+            rc_l = allow_lds(c, kLdsResBytes, k_pair_res<>, k_pair_res<LagBounds>, k_pair_res<BandSet>, k_pair_res<LagBounds, BandSet>);
         if (rc_l == RMX_OK) rc_l = allow_lds(c, kLdsWinBytes, k_win<false>, k_win<true>, k_win_lb<false>, k_win_lb<true>);
         return rc_l;
     };
@@ -1576,7 +1607,7 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
     // the route (host_plan.hpp: plan_route), and the pair plan with the pairs per workgroup it chose
     const host::RouteCall rq{n_windows, n_pairs, host::is_default_list(c->n_buoys, pairs, n_pairs), pairs != nullptr, call.bounded(),
-                             call.weighted(), call.integ, in_dev};
+                             call.weighted(), call.integ, in_dev, call.banded() ? call.bs.n_bands : 1};
     const host::RouteCaps caps = route_caps(c);
     const host::RoutePlan plan = host::plan_route(caps, rq);
     if (!c->generic) c->pairs_per_block = plan.ppb;
@@ -1606,7 +1637,8 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
     }
     int* d_lag = lag_int;
     float *d_frac = lag_frac, *d_peak = peak;
-    const size_t out_elems = (size_t)(n_windows / call.integ) * n_pairs;   // (integrated call: one row per group)
+    // (integrated call: one row per group; banded call: one row per virtual window, host::plan_bands' out_elems)
+    const size_t out_elems = (size_t)(n_windows / call.integ) * n_pairs * (size_t)rq.n_bands;
     if (!out_dev) {
         rc = ensure_out(c, out_elems);
         if (rc == RMX_OK && call.qualified()) rc = ensure_quality(c, 4 * out_elems);
@@ -1837,6 +1869,71 @@ int rmx_xcorr_batch_weighted(rmx_ctx* c, const void* iq, int n_windows, const in
                              int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, band_cps, band_per_window, weighting, lag_bounds,
                          bounds_per_window, 0, lag_int, lag_frac, peak, nullptr, flags);
+}
+
+// rmx_xcorr_batch_weighted under n_bands bands per window over ONE set of forward spectra (xspec_bands.hpp): the forward
+// kernels run unmasked -- plain, or under PHAT weighted with the full band --, the kernels that form the product mask it,
+// and the pair kernels see n_windows * n_bands virtual windows.  n_bands = 1 IS the weighted call.
+int rmx_xcorr_batch_bands(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                          const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
+                          const int32_t* lag_bounds, int bounds_per_window,
+                          int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    if (!c) return RMX_E_INVAL;
+    if (!iq || !lag_int || !lag_frac || !peak || !band_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
+    if (n_bands < 1 || n_bands > 64) return fail(c, RMX_E_INVAL, "n_bands %d not in 1..64", n_bands);
+    // the weighted entry's checks, per (window, band): [full band | band set] as signed bins
+    if (weighting != RMX_WEIGHT_NONE && weighting != RMX_WEIGHT_PHAT)
+        return fail(c, RMX_E_INVAL, "unknown weighting %u (RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1)", weighting);
+    int rc = check_n_windows(c, n_windows);
+    if (rc != RMX_OK) return rc;
+    const int N = c->n_samples;
+    const long band_rows = bands_per_window ? (long)n_windows : 1L;
+    std::vector<int32_t> bins((size_t)(2 + 2 * band_rows * n_bands));
+    bins[0] = -N;
+    bins[1] = N - 1;
+    for (long r = 0; r < band_rows * n_bands; ++r) {
+        const double lo = band_cps[2 * r], hi = band_cps[2 * r + 1];
+        const char* shared = bands_per_window ? "" : " (one band set shared by every window)";
+        const host::BandCheck bc = host::band_to_bins(lo, hi, N, &bins[2 + 2 * r], &bins[3 + 2 * r]);
+        if (bc == host::kBandNoInterval)
+            return fail(c, RMX_E_INVAL, "band %ld of window %ld%s: [%g, %g] is not an interval inside [-0.5, 0.5] cycles per sample",
+                        r % n_bands, r / n_bands, shared, lo, hi);
+        if (bc == host::kBandNoBin)
+            return fail(c, RMX_E_INVAL, "band %ld of window %ld%s: [%g, %g] keeps no bin of the %ld-point transform", r % n_bands,
+                        r / n_bands, shared, lo, hi, 2L * N);
+    }
+    if (n_bands == 1)   // the weighted call itself (its own checks repeat the ones above and pass)
+        return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, band_cps, bands_per_window, weighting, lag_bounds,
+                             bounds_per_window, 0, lag_int, lag_frac, peak, nullptr, flags);
+    if (n_windows == 0) return RMX_OK;   // (as the weighted entry: it does not look at the pairs of an empty batch)
+    rc = check_batch(c, n_windows, pairs, &n_pairs);
+    if (rc != RMX_OK) return rc;
+    if (n_pairs == 0) return RMX_OK;
+    bool bounded = false;
+    long bound_rows = 0;
+    if (lag_bounds) {
+        rc = check_bounded(c, n_windows, n_pairs, 1, lag_bounds, bounds_per_window, &bound_rows, &bounded);
+        if (rc != RMX_OK) return rc;
+    }
+    RMX_HIP(c, hipSetDevice(c->device));
+    // the bounds are per (window, pair) and shared by the window's bands: per-window bounds go to the device once per
+    // VIRTUAL window (window-major), so the bounded kernels index them with the virtual window as they index their outputs
+    std::vector<int32_t> vb;
+    if (bounded && bounds_per_window) {
+        const size_t row = 2 * (size_t)n_pairs;
+        vb.resize((size_t)n_windows * n_bands * row);
+        for (long v = 0; v < (long)n_windows * n_bands; ++v) std::memcpy(&vb[(size_t)v * row], lag_bounds + (size_t)(v / n_bands) * row, row * sizeof(int32_t));
+        lag_bounds = vb.data();
+        bound_rows *= n_bands;
+    }
+    XcorrCall call;
+    rc = stage_request(c, &call, true, bins, false, weighting, bounded, lag_bounds, bound_rows, bounds_per_window, n_pairs);
+    if (rc != RMX_OK) return rc;
+    // band_stage: [full band | band set].  PHAT keeps call.wt on the full band (every bin whitened, none dropped); without
+    // it the forward kernels are the plain ones
+    call.bs = BandSet{c->band_stage.d + 2, bands_per_window ? 2L * n_bands : 0L, 0L, n_bands};
+    if (weighting != RMX_WEIGHT_PHAT) call.wt = XWeight{nullptr, 0, 0, 0, 0, 0.0f};
+    return xcorr_dispatch(c, call, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
 }
 
 // rmx_xcorr_batch_weighted with one peak search per group of `integrate` consecutive windows, on the lag-by-lag sum of the

@@ -21,7 +21,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .shard import window_shard
-from .xcorr import check_band, check_integrate, check_lag_bounds, check_refine
+from .xcorr import check_band, check_bands, check_integrate, check_lag_bounds, check_refine
 
 
 class MultiXcorrEngine:
@@ -163,6 +163,25 @@ class MultiXcorrEngine:
                 return eng.correlate(iq[s:s + c], pairs, block_bounds(s, c))
             return eng.correlate(iq[s:s + c], pairs)
         return self._run(iq.shape[0], block_call, n_out, dtypes, P, tails=tails)
+
+    def correlate_bands(self, iq: np.ndarray, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
+                        whiten: bool = False):
+        """XcorrEngine.correlate_bands over the devices -> three [W][M][P] arrays.  The windows are sharded as correlate()
+        shards them: bands [M][2] and lag_bounds [P][2] go to every block whole, [W][M][2] and [W][P][2] are cut into each
+        block's own windows' rows."""
+        iq = np.asarray(iq)
+        if iq.ndim != 3:
+            raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
+        W = iq.shape[0]
+        P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
+        bd, bands_pw = check_bands(bands, W)
+        lb, per_window = check_lag_bounds(lag_bounds, W, P)
+
+        def block_call(eng, s, c):
+            return eng.correlate_bands(iq[s:s + c], bd[s:s + c] if bands_pw else bd, pairs,
+                                       lag_bounds=None if lb is None else (lb[s:s + c] if per_window else lb), whiten=whiten)
+        # (_run's rows are [W][n_pairs] + tail: here [W][M] + (P,))
+        return self._run(W, block_call, 3, (np.int32, np.float32, np.float32), bd.shape[-2], tails=[(P,)] * 3)
 
     def _correlate_integrated(self, iq, pairs, lag_bounds, band, whiten, K, P, U=0, quality=False):
         W = iq.shape[0]

@@ -155,7 +155,7 @@ class TDoACalculator:
     def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, min_cut_samples: int = 128,
                  bound_lags: bool = False, band_limit: bool = False, whiten: bool = False, integrate: int = 1,
                  refine: int = 0, min_psr: Optional[float] = None, correlation_confidence: bool = False,
-                 doppler_search_hz: Optional[Tuple[float, float]] = None):
+                 doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
@@ -189,7 +189,13 @@ class TDoACalculator:
         band_limit and whiten apply as they do without it, and every measurement carries the estimated offset
         (frequency_offset_hz: the winning hypothesis plus the sub-grid parabola).  The search has no integration,
         refinement or quality: together with integrate > 1, refine > 0, min_psr or correlation_confidence the
-        construction raises ValueError.  None (off) by default: every other path is then as before."""
+        construction raises ValueError.  None (off) by default: every other path is then as before.
+        share_captures: together with band_limit, TDoAProcessor.process_signal_detections correlates frequency groups
+        that were cut from ONE capture (byte-identical windows, identical lag bounds) as one window under several bands
+        (rmx_xcorr_batch_bands: one upload and one forward transform per buoy instead of one per emitter); the lags are
+        those of the separate calls.  Not for groups under integrate, refine, min_psr / correlation_confidence or
+        doppler_search_hz, which go the usual way.  A plain attribute, False (off) by default: the engine is then called
+        exactly as before."""
         from .xcorr import check_refine
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
@@ -198,6 +204,7 @@ class TDoACalculator:
         self.bound_lags = bool(bound_lags)
         self.band_limit = bool(band_limit)
         self.whiten = bool(whiten)
+        self.share_captures = bool(share_captures)
         self.integrate = int(integrate)
         self.refine = check_refine(refine)
         self.min_psr = None if min_psr is None else float(min_psr)
@@ -267,7 +274,7 @@ class TDoACalculator:
         return np.arange(-n, n + 1, dtype=np.float64) * (step_hz / float(fs))
 
     def measure_lags(self, iq, pairs=None, lag_bounds=None, band=None, whiten=False, integrate=1, refine=0, quality=False,
-                     doppler_cps=None):
+                     doppler_cps=None, bands=None):
         """Batched hot path.  iq: complex64 [W][B][N] (or uint8 [W][B][2N]) ->
         (lag_int [W][P], lag_frac [W][P], peak [W][P]); lag = delay(j) - delay(i) in samples.
         A leading channel axis is a batch axis: [C][W][B][N] -> three [C][W][P] arrays (channels and
@@ -282,9 +289,18 @@ class TDoACalculator:
         doppler_cps: None, or the hypotheses of a Doppler search in cycles per sample (a uniformly spaced grid): the call
         goes to caf() (rmx_caf_batch_request) with the same lag_bounds, band and whiten, and returns (lag_int, lag_frac,
         peak, dop_idx int32, doppler float64 in cycles per sample = xcorr.doppler_estimate of the winner and its sub-grid
-        part).  Not together with integrate > 1, refine > 0 or quality (ValueError)."""
+        part).  Not together with integrate > 1, refine > 0 or quality (ValueError).
+        bands: None, or float [W][M][2] (with a channel axis: [C][W][M][2]): every window under M bands with one forward
+        transform per buoy (rmx_xcorr_batch_bands); the three results are then [W][M][P] ([C][W][M][P]), lag_bounds stay
+        per (window, pair).  Not together with band, integrate > 1, refine > 0, quality or doppler_cps (ValueError)."""
         from .xcorr import check_integrate, check_refine
         refine = check_refine(refine)
+        if bands is not None:
+            for name, on in (("band", band is not None), ("integrate", integrate != 1), ("refine", refine > 0),
+                             ("quality", bool(quality)), ("doppler_cps", doppler_cps is not None)):
+                if on:
+                    raise ValueError(f"bands and {name} cannot be combined: the multi-band correlation takes one band set "
+                                     f"and has no integration, refinement, quality or Doppler search")
         if doppler_cps is not None:
             for name, on in (("integrate", integrate != 1), ("refine", refine > 0), ("quality", bool(quality))):
                 if on:
@@ -308,7 +324,14 @@ class TDoACalculator:
             lb = np.asarray(lag_bounds)
             if lead is not None and lb.ndim == 4:
                 lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
-        if doppler_cps is not None:
+        if bands is not None:
+            bs = np.asarray(bands)
+            if lead is not None and bs.ndim == 4:
+                bs = bs.reshape((-1,) + bs.shape[2:])
+            if bs.ndim != 3 or bs.shape[0] != iq.shape[0] or bs.shape[2] != 2:
+                raise ValueError(f"bands must be [W][M][2] or [C][W][M][2] for {iq.shape[0]} windows, got shape {np.shape(bands)}")
+            out = eng.correlate_bands(iq, bs, pairs, lag_bounds=lb, whiten=bool(whiten))
+        elif doppler_cps is not None:
             from .xcorr import doppler_estimate
             bd = None
             if band is not None:
@@ -523,6 +546,22 @@ class TDoACalculator:
             self.logger.error(f"Cross-correlation engine failed: {e}")   # no device, engine refused the batch
             return None
 
+    def _measure_shared(self, stacked: np.ndarray, lag_bounds, bands: np.ndarray):
+        """share_captures: [G][B][N] captures, each under the M bands of bands [G][M][2] -> lag [G][M][P] float64, or None
+        after logging, as _measure_groups does.  lag_bounds: None, or int [G][P][2]."""
+        try:
+            li, lf, _ = self.measure_lags(stacked, lag_bounds=lag_bounds, bands=bands, whiten=self.whiten)
+            return li.astype(np.float64) + lf.astype(np.float64)
+        except (ImportError, OSError) as e:   # library not built / not loadable
+            self.logger.error(f"Cross-correlation engine failed: {e}")
+            return None
+        except Exception as e:
+            from . import xcorr
+            if not isinstance(e, xcorr.RmxError):    # programming errors (shapes, types) surface
+                raise
+            self.logger.error(f"Cross-correlation engine failed: {e}")
+            return None
+
     def _timing_confidence(self, b1: BuoyPosition, b2: BuoyPosition) -> float:
         # exp(-rss(timing accuracies) / 100 us), capped at 1 (tdoa_processor.py:200-210); a handful of distinct values
         key = (b1.timing_accuracy_ns, b2.timing_accuracy_ns)
@@ -727,13 +766,13 @@ class HyperbolicPositioning:
 class TDoAProcessor:
     def __init__(self, band_limit: bool = False, whiten: bool = False, integrate: int = 1, refine: int = 0,
                  min_psr: Optional[float] = None, correlation_confidence: bool = False,
-                 doppler_search_hz: Optional[Tuple[float, float]] = None):
-        """band_limit, whiten, integrate, refine, min_psr, correlation_confidence, doppler_search_hz: the TDoACalculator
-        settings of the same names (off by default)."""
+                 doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False):
+        """band_limit, whiten, integrate, refine, min_psr, correlation_confidence, doppler_search_hz, share_captures: the
+        TDoACalculator settings of the same names (off by default)."""
         self.logger = logging.getLogger(__name__ + ".TDoAProcessor")
         self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten, integrate=integrate, refine=refine,
                                               min_psr=min_psr, correlation_confidence=correlation_confidence,
-                                              doppler_search_hz=doppler_search_hz)
+                                              doppler_search_hz=doppler_search_hz, share_captures=share_captures)
         self.hyperbolic_positioner = HyperbolicPositioning()
         self.buoy_positions: Dict[str, BuoyPosition] = {}
         self.correlation_window_s = 10.0
@@ -807,6 +846,11 @@ class TDoAProcessor:
                         bands[n] = b
                 if not members:
                     continue
+                if calc.share_captures and calc.integrate == 1 and calc.refine == 0 and not calc._wants_quality() \
+                        and calc.doppler_search_hz is None:
+                    members = self._measure_shared_captures(work, members, bands, n_samp, key[3])
+                    if not members:
+                        continue
                 if any(bands[n] is not None for n in members):
                     band = np.stack([np.array([-0.5, 0.5]) if bands[n] is None else bands[n] for n in members])
             stacked = np.stack([work[n][3] for n in members])
@@ -849,6 +893,33 @@ class TDoAProcessor:
                                         f"({fix.estimated_lat:.6f}, {fix.estimated_lng:.6f}) "
                                         f"±{fix.accuracy_meters:.1f}m")
         return results
+
+    def _measure_shared_captures(self, work, members, bands, n_samp: int, fs: float):
+        """share_captures: the members of one batch whose stacked windows are byte-identical to another member's -- frequency
+        groups cut from ONE capture -- and whose lag bounds (bound_lags) are identical too are correlated as one window under
+        several bands (TDoACalculator._measure_shared); their work items get their lags as the separate calls would have
+        set them.  A row with fewer bands than the widest is padded by repeating its last band, and the padded outputs
+        are dropped.  Returns the members that are left for the usual call."""
+        calc = self.tdoa_calculator
+        per = {n: calc.lag_bounds(work[n][1], self.buoy_positions, n_samp, fs) for n in members} if calc.bound_lags else {}
+        rows: Dict[Any, List[int]] = {}
+        for n in members:
+            sig = (work[n][3].tobytes(),) + ((per[n][0].tobytes(), per[n][1].tobytes()) if per else ())
+            rows.setdefault(sig, []).append(n)
+        shared = [r for r in rows.values() if len(r) > 1]
+        if not shared:
+            return members
+        full = np.array([-0.5, 0.5])
+        width = max(len(r) for r in shared)
+        band_set = np.stack([np.stack([full if bands[n] is None else bands[n] for n in r + [r[-1]] * (width - len(r))])
+                             for r in shared])
+        stacked = np.stack([work[r[0]][3] for r in shared])
+        lags = calc._measure_shared(stacked, np.stack([per[r[0]][0] for r in shared]) if per else None, band_set)
+        for g, r in enumerate(shared):
+            for m, n in enumerate(r):
+                work[n][4] = None if lags is None else ((lags[g, m], fs) + ((per[n][1],) if per else ()))
+        taken = {n for r in shared for n in r}
+        return [n for n in members if n not in taken]
 
     def triangulate_signal(self, detections: List[SignalDetection]) -> Optional[TriangulationResult]:
         """What central_processor.py:418 calls (missing in the reference): first fix or None."""

@@ -81,6 +81,8 @@ def load_library():
     lib.rmx_xcorr_batch_bounded.restype = ci
     lib.rmx_xcorr_batch_weighted.argtypes = [vp, vp, ci, vp, ci, vp, ci, cu, vp, ci, vp, vp, vp, cu]
     lib.rmx_xcorr_batch_weighted.restype = ci
+    lib.rmx_xcorr_batch_bands.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, cu, vp, ci, vp, vp, vp, cu]
+    lib.rmx_xcorr_batch_bands.restype = ci
     lib.rmx_xcorr_batch_integrated.argtypes = [vp, vp, ci, vp, ci, ci, vp, ci, cu, vp, ci, vp, vp, vp, cu]
     lib.rmx_xcorr_batch_integrated.restype = ci
     lib.rmx_xcorr_batch_refined.argtypes = [vp, vp, ci, vp, ci, ci, vp, ci, cu, vp, ci, ci, vp, vp, vp, cu]
@@ -153,6 +155,36 @@ def check_band(band, n_windows: int):
     lo, hi = a[..., 0], a[..., 1]
     if np.any(lo < -0.5) or np.any(hi > 0.5) or np.any(lo > hi):
         raise ValueError("band must satisfy -0.5 <= lo <= hi <= 0.5 (cycles per sample; no wrap across +-fs/2)")
+    return a, per_window
+
+
+MAX_BANDS = 64
+
+
+def check_bands(bands, n_windows: int):
+    """bands as correlate_bands() takes them -> (contiguous float64 array, per_window).  Shape [M][2] (one set of M bands
+    shared by every window) or [W][M][2], 1 <= M <= 64, in cycles per sample; finite, -0.5 <= lo <= hi <= 0.5.  Raises
+    ValueError before any call into the library.  Whether a band keeps a bin at all depends on the window length: the
+    library checks that (RmxError, RMX_E_INVAL)."""
+    if bands is None:
+        raise ValueError("bands must be an array [M][2] or [W][M][2], got None")
+    a = np.asarray(bands)
+    if a.dtype.kind not in "iuf":
+        raise ValueError(f"bands must be a real array, got dtype {a.dtype}")
+    if a.ndim == 2 and a.shape[1] == 2:
+        per_window = False
+    elif a.ndim == 3 and a.shape[0] == n_windows and a.shape[2] == 2:
+        per_window = True
+    else:
+        raise ValueError(f"bands must be [M][2] or [W][M][2] = [{n_windows}][M][2], got shape {a.shape}")
+    if not 1 <= a.shape[-2] <= MAX_BANDS:
+        raise ValueError(f"bands must hold 1..{MAX_BANDS} bands per window, got {a.shape[-2]}")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if not np.all(np.isfinite(a)):
+        raise ValueError("bands values must be finite")
+    lo, hi = a[..., 0], a[..., 1]
+    if np.any(lo < -0.5) or np.any(hi > 0.5) or np.any(lo > hi):
+        raise ValueError("bands must satisfy -0.5 <= lo <= hi <= 0.5 (cycles per sample; no wrap across +-fs/2)")
     return a, per_window
 
 
@@ -262,7 +294,7 @@ def doppler_estimate(doppler_cps, dop_idx, dop_frac) -> np.ndarray:
 
 
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -472,6 +504,42 @@ class XcorrEngine:
         self._xcorr(vp(iq), W, pp, P, K, bd, band_pw, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags, U,
                     vp(qual) if quality else None)
         return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
+
+    def correlate_bands(self, iq: np.ndarray, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
+                        whiten: bool = False):
+        """Every window under several bands with ONE forward transform per (window, buoy) (rmx_xcorr_batch_bands).
+        iq: as for correlate().  bands: float [M][2] (shared by every window) or [W][M][2], [lo, hi] in cycles per sample,
+        1 <= M <= 64.  lag_bounds: None, [P][2] or [W][P][2]: per (window, pair), shared by the window's bands.  whiten:
+        PHAT.  Returns (lag_int int32, lag_frac float32, peak float32), each [W][M][P]; [:, m] is bit for bit what
+        correlate(iq, band=bands[..., m, :], ...) returns."""
+        iq, flags = self._check_iq(iq)
+        W = iq.shape[0]
+        pairs, pp, P = self._pairs_arg(pairs)
+        bd, per_window_b = check_bands(bands, W)
+        M = bd.shape[-2]
+        lb, per_window = check_lag_bounds(lag_bounds, W, P)
+        lag_int = np.zeros((W, M, P), np.int32)
+        lag_frac = np.zeros((W, M, P), np.float32)
+        peak = np.zeros((W, M, P), np.float32)
+        if W and P:
+            vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
+            self._check(self._lib.rmx_xcorr_batch_bands(
+                self._ctx, vp(iq), W, pp, P, vp(bd), M, int(per_window_b), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
+                None if lb is None else vp(lb), int(per_window), vp(lag_int), vp(lag_frac), vp(peak), flags))
+        return lag_int, lag_frac, peak
+
+    def correlate_bands_device(self, iq_ptr: int, n_windows: int, bands, lag_int_ptr: int, lag_frac_ptr: int, peak_ptr: int,
+                               pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None, whiten: bool = False):
+        """correlate_bands() with device pointers in and out (the bands, the pair list and the bounds stay host arrays; the
+        library keeps its own copies); asynchronous on the ctx stream.  The outputs are [n_windows][M][P]."""
+        pairs, pp, P = self._pairs_arg(pairs)
+        bd, per_window_b = check_bands(bands, n_windows)
+        lb, per_window = check_lag_bounds(lag_bounds, n_windows, P)
+        flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
+        self._check(self._lib.rmx_xcorr_batch_bands(
+            self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P, bd.ctypes.data_as(C.c_void_p), bd.shape[-2], int(per_window_b),
+            RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
+            int(per_window), C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags))
 
     def _pairs_arg(self, pairs):
         """pairs as the entries take it -> (kept int32 array or None, its pointer or None, P)"""
