@@ -379,6 +379,37 @@ int rmx_xcorr_batch_quality(rmx_ctx* ctx, const void* iq, int n_windows, const i
                             const int32_t* lag_bounds, int bounds_per_group, int refine,
                             int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
 
+/* Refined and qualified lags of several bands per window: rmx_xcorr_batch_bands with the fine lag search of
+ * rmx_xcorr_batch_refined and the four figures of rmx_xcorr_batch_quality per (window, band, pair), still over ONE set of
+ * forward spectra per window.
+ *   band_cps, n_bands, bands_per_window, weighting, lag_bounds, bounds_per_window   exactly as in rmx_xcorr_batch_bands.
+ *   refine      U, one of 0, 2, 4, 8, 16, as in rmx_xcorr_batch_refined.
+ *   lag_int, lag_frac, peak   [n_windows][n_bands][n_pairs].
+ *   quality     float32 [n_windows][n_bands][n_pairs][4] (RMX_Q_...), or NULL; a device pointer with RMX_OUT_DEVICE.  It
+ *               must not overlap lag_int, lag_frac or peak.
+ * Definition: slot (w, m, q) is slot (w, q) of rmx_xcorr_batch_quality called with integrate = 1, band[w][m] (band[m] when
+ *   shared) and otherwise the same arguments -- all four outputs, and that entry's parity statements (tests/
+ *   bands_quality_ref.py stacks tests/refined_ref.py and tests/quality_ref.py per band).  There is no integration: the
+ *   entry has no argument for it.
+ * refine == 0 and quality == NULL IS rmx_xcorr_batch_bands: the same kernels, bit-identical outputs.
+ * n_bands == 1 IS rmx_xcorr_batch_quality with integrate = 1 and the same arguments, bit-identical.
+ * Otherwise the call runs exactly what rmx_xcorr_batch_bands runs -- one forward pass, the banded pair kernels -- and
+ *   behind each chunk's pair kernels the banded instantiations k_quality<layout, BandSet>, then k_refine<U, layout,
+ *   BandSet> (radio-mapper_amd/csrc/quality.hpp, refine.hpp): one workgroup per (virtual window, pair) reads the real
+ *   window's two unmasked spectra and skips every stored position whose bin the slot's band drops.  Those positions are
+ *   stored zeros in the weighted call and add +-0 there, so away from the four-step route with the default pair list from
+ *   6 buoys on (where the weighted call's coarse peak comes from g_rows_anchor) slot (w, m, q) is bit-identical to
+ *   rmx_xcorr_batch_quality with band[w][m].  lag_int, lag_frac and peak of a call with quality
+ *   are bit-identical to the same call without it.
+ * Refusals (RMX_E_INVAL, the text in rmx_last_error, nothing staged or written), in this order: rmx_xcorr_batch_bands' own,
+ *   in its order; refine not one of 0, 2, 4, 8, 16; quality overlapping another output, the text naming the array.
+ *   n_windows == 0 or n_pairs == 0 returns RMX_OK and writes nothing.
+ * Flags, custom pair lists, chunking and the staging of bands and bounds work as in rmx_xcorr_batch_bands. */
+int rmx_xcorr_batch_bands_quality(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                                  const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
+                                  const int32_t* lag_bounds, int bounds_per_window, int refine,
+                                  int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
+
 /* Cross-ambiguity variant of the hot path (BASELINE configs[4]): for
  * every window and pair (i, j) the later buoy's window is de-rotated by each Doppler hypothesis,
  *     c_d = correlate(x[w][j] * exp(-2*pi*i*doppler_cps[d]*n), x[w][i], 'full', 'fft'),

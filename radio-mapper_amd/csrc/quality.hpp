@@ -40,8 +40,12 @@ struct QualityArgs {
 
 constexpr int kQualSums = 5;   // A, B, C, D, F
 
-template <int LAYOUT>
-__global__ __launch_bounds__(kRefThreads) void k_quality(QualityArgs a, const float* __restrict__ peak, float* __restrict__ quality) {
+// The trailing pack is empty for the plain kernel and <BandSet> for the banded one, as k_refine's (refine.hpp): output row
+// gl is a virtual window, the spectra are real window gl / n_bands', and a position whose bin the band drops adds nothing
+// -- in the weighted call it is a stored zero, which adds +0 to each of the five sums.
+template <int LAYOUT, class... P>
+__global__ __launch_bounds__(kRefThreads) void k_quality(QualityArgs a, const float* __restrict__ peak, float* __restrict__ quality,
+                                                         P... tail) {
     __shared__ float red[kRefWaves][kQualSums];
     const int tid = threadIdx.x;
     const int gl = blockIdx.x / a.n_pairs, q = blockIdx.x % a.n_pairs;   // output row inside the chunk, pair
@@ -50,17 +54,33 @@ __global__ __launch_bounds__(kRefThreads) void k_quality(QualityArgs a, const fl
     const RefPair pr = a.pairs[q];
     const float inv_l = 1.0f / (float)L;   // a power of two
     float ee = 0.0f, sum_c = 0.0f, sum_d = 0.0f, sum_f = 0.0f;   // thread 0: over the windows, in window order
+    [[maybe_unused]] XBand bd{0, 0u};
+    [[maybe_unused]] long w_real = 0;
+    if constexpr (kBanded<P...>) {
+        const BandSet bs = band_set_of(tail...);
+        bd = band_of_virtual(bs, gl);
+        w_real = band_real_window(bs, gl);
+    }
     for (int w = 0; w < a.k; ++w) {
-        const long wl = (long)gl * a.k + w;
+        long wl = (long)gl * a.k + w;
+        if constexpr (kBanded<P...>) wl = w_real;   // (a.k == 1: a banded call is never integrated)
         const float4* xi = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.i) * L);
         const float4* xj = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.j) * L);
         float acc[kQualSums];
 #pragma unroll
         for (int u = 0; u < kQualSums; ++u) acc[u] = 0.0f;
         for (int f = tid; f < (L >> 1); f += kRefThreads) {
+            [[maybe_unused]] bool keep[2] = {true, true};
+            if constexpr (kBanded<P...>) {
+                keep[0] = xband_keeps(bd, ref_bin<LAYOUT>(2 * f, a.logL, a.row_bits), L - 1);
+                keep[1] = xband_keeps(bd, ref_bin<LAYOUT>(2 * f + 1, a.logL, a.row_bits), L - 1);
+                if (!(keep[0] || keep[1])) continue;
+            }
             const float4 vi = xi[f], vj = xj[f];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
+                if constexpr (kBanded<P...>)
+                    if (!keep[e]) continue;
                 const float2 bi = e ? make_float2(vi.z, vi.w) : make_float2(vi.x, vi.y);
                 const float2 bj = e ? make_float2(vj.z, vj.w) : make_float2(vj.x, vj.y);
                 const int k = ref_bin<LAYOUT>(2 * f + e, a.logL, a.row_bits);

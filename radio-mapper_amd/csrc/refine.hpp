@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lag_bounds.hpp"
+#include "xspec_bands.hpp"
 #include "xspec_weight.hpp"
 
 namespace rmx {
@@ -64,9 +65,36 @@ __device__ __forceinline__ int ref_bin(int pos, int logL, int row_bits) {
     }
 }
 
-template <int U, int LAYOUT>
+// The rotation steps of the banded k_refine in the form hipcc compiles the plain kernel's to.  Each component of a step
+// is a sum of two products, one of which is rounded and one fused into the multiply-add; which one is the compiler's
+// choice (-ffp-contract), it depends on the order in which the backend meets the nodes, and it fell differently in the
+// banded instantiation: last-bit differences from the single-band call.  The plain kernel's forms are stated here with the
+// contraction off (tests/test_gpu_bands_quality.py holds the two kernels together, every U on every layout):
+//   u = 1, up and dn both from c0, sharing their products:   ss * c0 rounded, sc * c0 fused
+//   u > 1:   up.x, dn.x, dn.y: the ss product rounded, the sc product fused;   up.y: sc * up.y rounded, ss * up.x fused
+__device__ __forceinline__ void ref_first_step(const float2 c0, float ss, float sc, float2& up, float2& dn) {
+#pragma clang fp contract(off)
+    const float sx = ss * c0.x, sy = ss * c0.y;
+    up = make_float2(__builtin_fmaf(sc, c0.x, -sy), __builtin_fmaf(sc, c0.y, sx));
+    dn = make_float2(__builtin_fmaf(sc, c0.x, sy), __builtin_fmaf(sc, c0.y, -sx));
+}
+__device__ __forceinline__ void ref_next_step(float ss, float sc, float2& up, float2& dn) {
+#pragma clang fp contract(off)
+    const float uy = ss * up.y, ux = sc * up.y, dy = ss * dn.y, dx = ss * dn.x;
+    up = make_float2(__builtin_fmaf(sc, up.x, -uy), __builtin_fmaf(ss, up.x, ux));
+    dn = make_float2(__builtin_fmaf(sc, dn.x, dy), __builtin_fmaf(sc, dn.y, -dx));
+}
+
+// The trailing pack is empty for the plain kernel and <BandSet> for the banded one (rmx_xcorr_batch_bands_quality,
+// xspec_bands.hpp): the output row gl is then a VIRTUAL window -- the spectra are those of real window gl / n_bands, the
+// band is band_of_virtual(gl), the outputs and the lag interval are row gl's --, a.k is 1, and a stored position whose
+// natural bin the band drops contributes nothing: a 16-byte load both of whose bins are dropped is not issued and its
+// sincospif pairs are not evaluated.  The thread-to-position map, the order of a thread's additions and the reduction
+// tree are the plain kernel's, and what is skipped is what the weighted call adds as +-0 to sums that start at +0:
+// slot (w, m, q) carries the bits of the refined call with band[w][m].
+template <int U, int LAYOUT, class... P>
 __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                                        float* __restrict__ peak) {
+                                                        float* __restrict__ peak, P... tail) {
     constexpr int T = 2 * U + 1;
     __shared__ float red[kRefWaves][2 * T];
     __shared__ float taps[T];
@@ -78,17 +106,33 @@ __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __res
     const RefPair pr = a.pairs[q];
     const float inv_n = 1.0f / (float)N, inv_un = 1.0f / ((float)N * (float)U);   // powers of two
     float fsum = 0.0f;   // thread u < T: sum over the windows of |r_w(lag0 + (u - U) / U)|^2, unscaled
+    [[maybe_unused]] XBand bd{0, 0u};
+    [[maybe_unused]] long w_real = 0;
+    if constexpr (kBanded<P...>) {
+        const BandSet bs = band_set_of(tail...);
+        bd = band_of_virtual(bs, gl);
+        w_real = band_real_window(bs, gl);
+    }
     for (int w = 0; w < a.k; ++w) {
-        const long wl = (long)gl * a.k + w;
+        long wl = (long)gl * a.k + w;
+        if constexpr (kBanded<P...>) wl = w_real;   // (a.k == 1: a banded call is never integrated)
         const float4* xi = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.i) * L);
         const float4* xj = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.j) * L);
         float2 acc[T];
 #pragma unroll
         for (int u = 0; u < T; ++u) acc[u] = make_float2(0.0f, 0.0f);
         for (int f = tid; f < (L >> 1); f += kRefThreads) {
+            [[maybe_unused]] bool keep[2] = {true, true};
+            if constexpr (kBanded<P...>) {
+                keep[0] = xband_keeps(bd, ref_bin<LAYOUT>(2 * f, a.logL, a.row_bits), L - 1);
+                keep[1] = xband_keeps(bd, ref_bin<LAYOUT>(2 * f + 1, a.logL, a.row_bits), L - 1);
+                if (!(keep[0] || keep[1])) continue;
+            }
             const float4 vi = xi[f], vj = xj[f];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
+                if constexpr (kBanded<P...>)
+                    if (!keep[e]) continue;
                 const float2 bi = e ? make_float2(vi.z, vi.w) : make_float2(vi.x, vi.y);
                 const float2 bj = e ? make_float2(vj.z, vj.w) : make_float2(vj.x, vj.y);
                 const int k = ref_bin<LAYOUT>(2 * f + e, a.logL, a.row_bits);
@@ -104,8 +148,13 @@ __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __res
                 float2 up = c0, dn = c0;
 #pragma unroll
                 for (int u = 1; u <= U; ++u) {
-                    up = make_float2(up.x * sc - up.y * ss, up.x * ss + up.y * sc);
-                    dn = make_float2(dn.x * sc + dn.y * ss, dn.y * sc - dn.x * ss);
+                    if constexpr (kBanded<P...>) {
+                        if (u == 1) ref_first_step(c0, ss, sc, up, dn);
+                        else ref_next_step(ss, sc, up, dn);
+                    } else {
+                        up = make_float2(up.x * sc - up.y * ss, up.x * ss + up.y * sc);
+                        dn = make_float2(dn.x * sc + dn.y * ss, dn.y * sc - dn.x * ss);
+                    }
                     acc[U + u].x += up.x;
                     acc[U + u].y += up.y;
                     acc[U - u].x += dn.x;

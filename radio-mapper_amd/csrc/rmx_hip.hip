@@ -425,10 +425,19 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, i
     a.row_bits = sv.row_bits;
     a.k = call.integ;
     a.scale = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the two stored forward scales 2^unit_log2
-    const unsigned grid = (unsigned)(wc / call.integ * n_pairs);
+    // banded call (never integrated): one slot per VIRTUAL window, rows and lag intervals from virtual window w0 * n_bands
+    // on, the spectra per real window; the band set's w0 is the chunk's first real window
+    const int nb = call.banded() ? call.bs.n_bands : 1;
+    a.first_out *= nb;
+    BandSet bs = call.bs;
+    bs.w0 = w0;
+    const unsigned grid = (unsigned)(wc / call.integ * nb * n_pairs);
     // k_refine<U, layout>; U was checked by the entry (16 is the last it admits), the four-step layout is the last one
     return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
         return with_one_of<2, 4, 8, 16>(call.refine, [&](auto u) {
+            if (call.banded())
+                return launch(c, kTkRefine, k_refine<decltype(u)::value, decltype(lay)::value, BandSet>, dim3(grid), dim3(kRefThreads), 0, a,
+                              d_lag, d_frac, d_peak, bs);
             return launch(c, kTkRefine, k_refine<decltype(u)::value, decltype(lay)::value>, dim3(grid), dim3(kRefThreads), 0, a, d_lag,
                           d_frac, d_peak);
         });
@@ -452,8 +461,14 @@ static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, 
     a.k = call.integ;
     a.sa = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the stored forward scale 2^unit_log2, squared
     a.sc = std::ldexp(1.0f, -logL - 4 * unit_log2);   // ... to the fourth power
-    const unsigned grid = (unsigned)(wc / call.integ * n_pairs);
+    const int nb = call.banded() ? call.bs.n_bands : 1;   // (banded call: as refine_chunk)
+    a.first_out *= nb;
+    BandSet bs = call.bs;
+    bs.w0 = w0;
+    const unsigned grid = (unsigned)(wc / call.integ * nb * n_pairs);
     return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
+        if (call.banded())
+            return launch(c, kTkQuality, k_quality<decltype(lay)::value, BandSet>, dim3(grid), dim3(kRefThreads), 0, a, d_peak, call.quality, bs);
         return launch(c, kTkQuality, k_quality<decltype(lay)::value>, dim3(grid), dim3(kRefThreads), 0, a, d_peak, call.quality);
     });
 }
@@ -1595,7 +1610,8 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
                           int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     // Quality and nothing else that needs the spectra in HBM: the three lag outputs come from the routes of the same call
     // without quality, so they are that call's bit for bit whatever kernel it takes; the figures follow in a second pass.
-    if (req.qualified() && !req.wt.band && !req.integrated() && !req.refined()) {
+    // (A banded call runs the per-transform kernels with or without quality: one pass, k_quality behind its pair kernels.)
+    if (req.qualified() && !req.wt.band && !req.banded() && !req.integrated() && !req.refined()) {
         XcorrCall lags = req;
         lags.quality = nullptr;
         const int rc_l = xcorr_dispatch(c, lags, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
@@ -1965,6 +1981,86 @@ int rmx_xcorr_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int
                             int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
     return xcorr_request(c, iq, n_windows, pairs, n_pairs, true, integrate, band_cps, band_per_window, weighting, lag_bounds,
                          bounds_per_group, refine, lag_int, lag_frac, peak, quality, flags);
+}
+
+// rmx_xcorr_batch_bands with the fine lag search and the quality figures of rmx_xcorr_batch_quality per (window, band,
+// pair): k_quality, then k_refine, behind every chunk's pair kernels in their banded instantiations (refine.hpp,
+// quality.hpp), which read the chunk's unmasked spectra under the slot's band.  No forward pass is added.  refine == 0 and
+// quality == NULL IS rmx_xcorr_batch_bands; n_bands == 1 IS rmx_xcorr_batch_quality with integrate = 1.
+int rmx_xcorr_batch_bands_quality(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                                  const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
+                                  const int32_t* lag_bounds, int bounds_per_window, int refine,
+                                  int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
+    if (refine == 0 && !quality)
+        return rmx_xcorr_batch_bands(c, iq, n_windows, pairs, n_pairs, band_cps, n_bands, bands_per_window, weighting, lag_bounds,
+                                     bounds_per_window, lag_int, lag_frac, peak, flags);
+    // rmx_xcorr_batch_bands' own checks, in its order
+    if (!c) return RMX_E_INVAL;
+    if (!iq || !lag_int || !lag_frac || !peak || !band_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
+    if (n_bands < 1 || n_bands > 64) return fail(c, RMX_E_INVAL, "n_bands %d not in 1..64", n_bands);
+    if (weighting != RMX_WEIGHT_NONE && weighting != RMX_WEIGHT_PHAT)
+        return fail(c, RMX_E_INVAL, "unknown weighting %u (RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1)", weighting);
+    int rc = check_n_windows(c, n_windows);
+    if (rc != RMX_OK) return rc;
+    const int N = c->n_samples;
+    const long band_rows = bands_per_window ? (long)n_windows : 1L;
+    std::vector<int32_t> bins((size_t)(2 + 2 * band_rows * n_bands));
+    bins[0] = -N;
+    bins[1] = N - 1;
+    for (long r = 0; r < band_rows * n_bands; ++r) {
+        const double lo = band_cps[2 * r], hi = band_cps[2 * r + 1];
+        const char* shared = bands_per_window ? "" : " (one band set shared by every window)";
+        const host::BandCheck bc = host::band_to_bins(lo, hi, N, &bins[2 + 2 * r], &bins[3 + 2 * r]);
+        if (bc == host::kBandNoInterval)
+            return fail(c, RMX_E_INVAL, "band %ld of window %ld%s: [%g, %g] is not an interval inside [-0.5, 0.5] cycles per sample",
+                        r % n_bands, r / n_bands, shared, lo, hi);
+        if (bc == host::kBandNoBin)
+            return fail(c, RMX_E_INVAL, "band %ld of window %ld%s: [%g, %g] keeps no bin of the %ld-point transform", r % n_bands,
+                        r / n_bands, shared, lo, hi, 2L * N);
+    }
+    if (n_bands == 1)   // the quality call itself, ungrouped as the banded entry's n_bands == 1 (its checks repeat the ones above)
+        return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, band_cps, bands_per_window, weighting, lag_bounds,
+                             bounds_per_window, refine, lag_int, lag_frac, peak, quality, flags);
+    if (n_windows == 0) return RMX_OK;
+    rc = check_batch(c, n_windows, pairs, &n_pairs);
+    if (rc != RMX_OK) return rc;
+    if (n_pairs == 0) return RMX_OK;
+    bool bounded = false;
+    long bound_rows = 0;
+    if (lag_bounds) {
+        rc = check_bounded(c, n_windows, n_pairs, 1, lag_bounds, bounds_per_window, &bound_rows, &bounded);
+        if (rc != RMX_OK) return rc;
+    }
+    // the refined entry's check, then the quality entry's, over the [n_windows][n_bands][n_pairs] rows of this call
+    if (refine != 0 && refine != 2 && refine != 4 && refine != 8 && refine != 16)
+        return fail(c, RMX_E_INVAL, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", refine);
+    if (quality) {
+        const size_t rows = (size_t)n_windows * n_bands * n_pairs;
+        const char *q0 = reinterpret_cast<const char*>(quality), *q1 = q0 + 4 * rows * sizeof(float);
+        const struct { const char* name; const void* p; } outs[3] = {{"lag_int", lag_int}, {"lag_frac", lag_frac}, {"peak", peak}};
+        for (const auto& o : outs) {
+            const char* p0 = static_cast<const char*>(o.p);
+            if (p0 < q1 && q0 < p0 + rows * sizeof(float))
+                return fail(c, RMX_E_INVAL, "quality overlaps %s: the %zu x 4 floats of quality need a buffer of their own", o.name, rows);
+        }
+    }
+    RMX_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> vb;   // per-window bounds once per virtual window, as rmx_xcorr_batch_bands stages them
+    if (bounded && bounds_per_window) {
+        const size_t row = 2 * (size_t)n_pairs;
+        vb.resize((size_t)n_windows * n_bands * row);
+        for (long v = 0; v < (long)n_windows * n_bands; ++v) std::memcpy(&vb[(size_t)v * row], lag_bounds + (size_t)(v / n_bands) * row, row * sizeof(int32_t));
+        lag_bounds = vb.data();
+        bound_rows *= n_bands;
+    }
+    XcorrCall call;
+    call.refine = refine;
+    call.quality = quality;
+    rc = stage_request(c, &call, true, bins, false, weighting, bounded, lag_bounds, bound_rows, bounds_per_window, n_pairs);
+    if (rc != RMX_OK) return rc;
+    call.bs = BandSet{c->band_stage.d + 2, bands_per_window ? 2L * n_bands : 0L, 0L, n_bands};
+    if (weighting != RMX_WEIGHT_PHAT) call.wt = XWeight{nullptr, 0, 0, 0, 0, 0.0f};
+    return xcorr_dispatch(c, call, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
 }
 
 // The Doppler search is rmx_caf_batch_request with nothing requested: the same kernels, the same launches

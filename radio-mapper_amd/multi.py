@@ -165,10 +165,11 @@ class MultiXcorrEngine:
         return self._run(iq.shape[0], block_call, n_out, dtypes, P, tails=tails)
 
     def correlate_bands(self, iq: np.ndarray, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
-                        whiten: bool = False):
+                        whiten: bool = False, refine: int = 0, quality: bool = False):
         """XcorrEngine.correlate_bands over the devices -> three [W][M][P] arrays.  The windows are sharded as correlate()
         shards them: bands [M][2] and lag_bounds [P][2] go to every block whole, [W][M][2] and [W][P][2] are cut into each
-        block's own windows' rows."""
+        block's own windows' rows.  refine and quality are handed to every block's call (quality: a fourth array,
+        [W][M][P][4]); with neither, every block makes exactly the call it made without them."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
@@ -176,12 +177,16 @@ class MultiXcorrEngine:
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
         bd, bands_pw = check_bands(bands, W)
         lb, per_window = check_lag_bounds(lag_bounds, W, P)
+        U = check_refine(refine)
+        more = {"refine": U, "quality": True} if quality else ({"refine": U} if U else {})
 
         def block_call(eng, s, c):
             return eng.correlate_bands(iq[s:s + c], bd[s:s + c] if bands_pw else bd, pairs,
-                                       lag_bounds=None if lb is None else (lb[s:s + c] if per_window else lb), whiten=whiten)
+                                       lag_bounds=None if lb is None else (lb[s:s + c] if per_window else lb), whiten=whiten, **more)
         # (_run's rows are [W][n_pairs] + tail: here [W][M] + (P,))
-        return self._run(W, block_call, 3, (np.int32, np.float32, np.float32), bd.shape[-2], tails=[(P,)] * 3)
+        n_out = 4 if quality else 3
+        return self._run(W, block_call, n_out, (np.int32, np.float32, np.float32, np.float32)[:n_out], bd.shape[-2],
+                         tails=[(P,), (P,), (P,), (P, 4)][:n_out])
 
     def _correlate_integrated(self, iq, pairs, lag_bounds, band, whiten, K, P, U=0, quality=False):
         W = iq.shape[0]

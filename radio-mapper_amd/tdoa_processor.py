@@ -155,7 +155,8 @@ class TDoACalculator:
     def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, min_cut_samples: int = 128,
                  bound_lags: bool = False, band_limit: bool = False, whiten: bool = False, integrate: int = 1,
                  refine: int = 0, min_psr: Optional[float] = None, correlation_confidence: bool = False,
-                 doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False):
+                 doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False,
+                 share_qualified: bool = False):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
@@ -195,7 +196,13 @@ class TDoACalculator:
         (rmx_xcorr_batch_bands: one upload and one forward transform per buoy instead of one per emitter); the lags are
         those of the separate calls.  Not for groups under integrate, refine, min_psr / correlation_confidence or
         doppler_search_hz, which go the usual way.  A plain attribute, False (off) by default: the engine is then called
-        exactly as before."""
+        exactly as before.
+        share_qualified: together with share_captures, shared captures are also correlated as one window under several
+        bands when refine > 0, min_psr or correlation_confidence is set (rmx_xcorr_batch_bands_quality: the fine lag search
+        and the quality figures per (capture, band, pair), still one forward transform per buoy); min_psr and the
+        correlation confidence are applied per (capture, band, pair), and the measurements are those of the separate
+        calls, in the same order.  Groups under integrate > 1 or doppler_search_hz still go the usual way.  A plain
+        attribute, False (off) by default: nothing changes then."""
         from .xcorr import check_refine
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
@@ -205,6 +212,7 @@ class TDoACalculator:
         self.band_limit = bool(band_limit)
         self.whiten = bool(whiten)
         self.share_captures = bool(share_captures)
+        self.share_qualified = bool(share_qualified)
         self.integrate = int(integrate)
         self.refine = check_refine(refine)
         self.min_psr = None if min_psr is None else float(min_psr)
@@ -356,6 +364,41 @@ class TDoACalculator:
             out = eng.correlate(iq, pairs)
         else:
             out = eng.correlate(iq, pairs, lag_bounds=lb)
+        if lead is not None:
+            out = tuple(a.reshape(lead + a.shape[1:]) for a in out)
+        return out
+
+    def measure_band_lags(self, iq, bands, pairs=None, lag_bounds=None, whiten=False, refine=0, quality=False):
+        """measure_lags(bands=...) with the fine lag search and the quality figures (rmx_xcorr_batch_bands_quality): iq
+        complex64 [W][B][N] (or uint8 [W][B][2N]) under bands [W][M][2] -> (lag_int, lag_frac, peak), each [W][M][P], and
+        with quality=True a fourth array [W][M][P][4]; one forward transform per (window, buoy).  A leading channel axis is
+        a batch axis, as in measure_lags: [C][W][B][N] with bands [C][W][M][2] (and lag_bounds [C][W][P][2]) -> [C][W][M][P]
+        ([C][W][M][P][4]).  refine: U in (0, 2, 4, 8, 16).  With refine=0 and quality=False it is measure_lags(bands=...)."""
+        from .xcorr import check_refine
+        refine = check_refine(refine)
+        iq = np.asarray(iq)
+        lead = None
+        if iq.ndim == 4:
+            lead = iq.shape[:2]
+            iq = iq.reshape((lead[0] * lead[1],) + iq.shape[2:])
+        if iq.ndim != 3:
+            raise ValueError(f"iq must be [W][B][N] or [C][W][B][N], got shape {iq.shape}")
+        n = iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2]
+        eng = self._engine(iq.shape[1], n, iq.shape[0])
+        lb = None
+        if lag_bounds is not None:
+            lb = np.asarray(lag_bounds)
+            if lead is not None and lb.ndim == 4:
+                lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
+        bs = np.asarray(bands)
+        if lead is not None and bs.ndim == 4:
+            bs = bs.reshape((-1,) + bs.shape[2:])
+        if bs.ndim != 3 or bs.shape[0] != iq.shape[0] or bs.shape[2] != 2:
+            raise ValueError(f"bands must be [W][M][2] or [C][W][M][2] for {iq.shape[0]} windows, got shape {np.shape(bands)}")
+        kw = {"refine": refine} if refine > 0 else {}
+        if quality:
+            kw["quality"] = True
+        out = eng.correlate_bands(iq, bs, pairs, lag_bounds=lb, whiten=bool(whiten), **kw)
         if lead is not None:
             out = tuple(a.reshape(lead + a.shape[1:]) for a in out)
         return out
@@ -546,11 +589,19 @@ class TDoACalculator:
             self.logger.error(f"Cross-correlation engine failed: {e}")   # no device, engine refused the batch
             return None
 
-    def _measure_shared(self, stacked: np.ndarray, lag_bounds, bands: np.ndarray):
+    def _measure_shared(self, stacked: np.ndarray, lag_bounds, bands: np.ndarray, with_quality: bool = False):
         """share_captures: [G][B][N] captures, each under the M bands of bands [G][M][2] -> lag [G][M][P] float64, or None
-        after logging, as _measure_groups does.  lag_bounds: None, or int [G][P][2]."""
+        after logging, as _measure_groups does.  lag_bounds: None, or int [G][P][2].  share_qualified: the calculator's
+        refine goes along, and with_quality -> (lag [G][M][P], quality [G][M][P][4]) instead."""
         try:
-            li, lf, _ = self.measure_lags(stacked, lag_bounds=lag_bounds, bands=bands, whiten=self.whiten)
+            if with_quality:
+                li, lf, _, qual = self.measure_band_lags(stacked, bands, lag_bounds=lag_bounds, whiten=self.whiten,
+                                                         refine=self.refine, quality=True)
+                return li.astype(np.float64) + lf.astype(np.float64), np.asarray(qual)
+            if self.refine > 0:
+                li, lf, _ = self.measure_band_lags(stacked, bands, lag_bounds=lag_bounds, whiten=self.whiten, refine=self.refine)
+            else:
+                li, lf, _ = self.measure_lags(stacked, lag_bounds=lag_bounds, bands=bands, whiten=self.whiten)
             return li.astype(np.float64) + lf.astype(np.float64)
         except (ImportError, OSError) as e:   # library not built / not loadable
             self.logger.error(f"Cross-correlation engine failed: {e}")
@@ -766,13 +817,15 @@ class HyperbolicPositioning:
 class TDoAProcessor:
     def __init__(self, band_limit: bool = False, whiten: bool = False, integrate: int = 1, refine: int = 0,
                  min_psr: Optional[float] = None, correlation_confidence: bool = False,
-                 doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False):
-        """band_limit, whiten, integrate, refine, min_psr, correlation_confidence, doppler_search_hz, share_captures: the
-        TDoACalculator settings of the same names (off by default)."""
+                 doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False,
+                 share_qualified: bool = False):
+        """band_limit, whiten, integrate, refine, min_psr, correlation_confidence, doppler_search_hz, share_captures,
+        share_qualified: the TDoACalculator settings of the same names (off by default)."""
         self.logger = logging.getLogger(__name__ + ".TDoAProcessor")
         self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten, integrate=integrate, refine=refine,
                                               min_psr=min_psr, correlation_confidence=correlation_confidence,
-                                              doppler_search_hz=doppler_search_hz, share_captures=share_captures)
+                                              doppler_search_hz=doppler_search_hz, share_captures=share_captures,
+                                              share_qualified=share_qualified)
         self.hyperbolic_positioner = HyperbolicPositioning()
         self.buoy_positions: Dict[str, BuoyPosition] = {}
         self.correlation_window_s = 10.0
@@ -846,8 +899,9 @@ class TDoAProcessor:
                         bands[n] = b
                 if not members:
                     continue
-                if calc.share_captures and calc.integrate == 1 and calc.refine == 0 and not calc._wants_quality() \
-                        and calc.doppler_search_hz is None:
+                # (refine, min_psr / correlation_confidence: only with share_qualified; integrate and the Doppler search never)
+                if calc.share_captures and calc.integrate == 1 and calc.doppler_search_hz is None \
+                        and (calc.share_qualified or (calc.refine == 0 and not calc._wants_quality())):
                     members = self._measure_shared_captures(work, members, bands, n_samp, key[3])
                     if not members:
                         continue
@@ -899,7 +953,8 @@ class TDoAProcessor:
         groups cut from ONE capture -- and whose lag bounds (bound_lags) are identical too are correlated as one window under
         several bands (TDoACalculator._measure_shared); their work items get their lags as the separate calls would have
         set them.  A row with fewer bands than the widest is padded by repeating its last band, and the padded outputs
-        are dropped.  Returns the members that are left for the usual call."""
+        are dropped.  share_qualified: the quality figures of every (capture, band) ride along as the work item's fourth
+        entry, as _measure_groups' do.  Returns the members that are left for the usual call."""
         calc = self.tdoa_calculator
         per = {n: calc.lag_bounds(work[n][1], self.buoy_positions, n_samp, fs) for n in members} if calc.bound_lags else {}
         rows: Dict[Any, List[int]] = {}
@@ -914,10 +969,19 @@ class TDoAProcessor:
         band_set = np.stack([np.stack([full if bands[n] is None else bands[n] for n in r + [r[-1]] * (width - len(r))])
                              for r in shared])
         stacked = np.stack([work[r[0]][3] for r in shared])
-        lags = calc._measure_shared(stacked, np.stack([per[r[0]][0] for r in shared]) if per else None, band_set)
+        more = {"with_quality": True} if calc._wants_quality() else {}
+        lags = calc._measure_shared(stacked, np.stack([per[r[0]][0] for r in shared]) if per else None, band_set, **more)
+        qual = None
+        if more and lags is not None:
+            lags, qual = lags
         for g, r in enumerate(shared):
             for m, n in enumerate(r):
-                work[n][4] = None if lags is None else ((lags[g, m], fs) + ((per[n][1],) if per else ()))
+                if lags is None:
+                    work[n][4] = None
+                elif qual is None:
+                    work[n][4] = (lags[g, m], fs) + ((per[n][1],) if per else ())
+                else:
+                    work[n][4] = (lags[g, m], fs, per[n][1] if per else None, qual[g, m])
         taken = {n for r in shared for n in r}
         return [n for n in members if n not in taken]
 
