@@ -109,7 +109,7 @@ int rmx_set_stream(rmx_ctx* ctx, void* hip_stream);
  * about 0.25 ... 0.5 windows per CU, depending on the buoy count -- run through those per-transform kernels, which spread
  * one window's spectra and pairs over the CUs: 13 us instead of 92 us for a single window of 8 buoys; 0: always the
  * fused kernel), "stag" (0..5: which waves of the fused N = 4096 kernel run the two halves
- * between barriers in the opposite order; default 1), "win8" / "pk" (two other builds of that kernel,
+ * between barriers in the opposite order; default 0, nobody: scheduling only, every value gives the same bytes), "win8" / "pk" (two other builds of that kernel,
  * tools/experiments/: present only in a -DRMX_EXPERIMENTS build, RMX_E_UNSUPPORTED otherwise), "dbg"
  * (the ablation masks of a timing-only build that was removed; the key is rejected with RMX_E_UNSUPPORTED).
  * Returns RMX_E_INVAL for an unknown key. */

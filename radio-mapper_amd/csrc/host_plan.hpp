@@ -11,6 +11,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace rmx {
@@ -33,7 +34,7 @@ struct OptionSpec {
 };
 inline const std::vector<OptionSpec>& option_specs() {
     static const std::vector<OptionSpec> s = {
-        {"stag", 0, 5, "N = 4096 fused kernel: which waves run the two halves between barriers in the opposite order (default 1)"},
+        {"stag", 0, 5, "N = 4096 fused kernel: which waves run the two halves between barriers in the opposite order (0 nobody: the default; 1 SIMDs 1 and 3, 2 odd waves, 3 the second wave of every SIMD, 4 one wave of every SIMD, 5 everybody); k_win8 of the experiments build: default 1"},
         {"ncus", 1, 4096, "persistent workgroups of the fused N = 4096 kernel (default: one per CU)"},
         {"chunk_windows", 1, 1 << 20, "windows per chunk of the unfused N = 4096 path"},
         {"small4096", 0, 1, "0: N = 4096 through the fused kernel however few the windows (default 1: few windows through the per-transform kernels)"},
@@ -194,6 +195,149 @@ inline int make_pair_plan(int n_buoys, const int32_t* pairs, int n_pairs, int pa
     out->all_pairs = is_default_list(n_buoys, pl.data(), n_pairs);
     out->pairs.swap(pl);
     return 0;
+}
+
+// ---- k_win, phase 2: the order of a window's pairs among buoys 1 .. B-1 ---------------------------------------------
+// Phase 1 of the fused kernel (anchor 0) leaves X_{B-1} in register array 1 (sb) and every X_1 .. X_{B-1} in the scratch.
+// The remaining pairs are walked so that every pair shares one buoy with the pair before it: the shared spectrum stays
+// in its register array, and each step requests ONE spectrum, into the array whose buoy the next step drops.
+struct TrailStep {
+    int i, j;       // the pair, i < j: the kernel computes X_j conj(X_i)
+    int out_idx;    // i*B - i(i+1)/2 + (j-i-1)
+    int xi_arr;     // register array (0 = sa, 1 = sb) that holds X_i; X_j is in the other one
+    int load_arr;   // array that the request issued DURING this step overwrites: the one whose buoy the next step drops
+    int load_idx;   // the spectrum that request loads (an operand of the next step); -1 behind the last step
+    int reload;     // 1: the next step shares no buoy with this one, load2 goes into the other array as well
+    int load2;      // -1 unless reload
+};
+struct PairTrail {
+    int n_buoys = 0;
+    int first_load = -1;   // requested by the last pair of phase 1 into array 0: the first step's other operand (-1: no step)
+    std::vector<TrailStep> steps;
+    int loads = 0;         // spectrum requests issued by the steps: one per step but the last, two where `reload`;
+                           // with first_load that is loads + 1 spectrum loads per window (21 at B = 8)
+    int reloads = 0, min_reloads = 0;   // steps that reload both arrays, and the fewest the order's construction needs
+    int sim_hits2 = 0, sim_hits3 = 0;   // of first_load + loads: hits in an LRU of two / three spectra (trail_sim_hits)
+};
+
+inline int trail_out_idx(int B, int i, int j) { return i * B - (i * (i + 1)) / 2 + (j - i - 1); }
+
+// One window's spectrum traffic through an LRU of `cap` spectra: the stores of X_1 .. X_{B-1} (write-allocate), then
+// first_load and every step's requests in order.  Returns the requests that hit.  (A model for the notes: two spectra are a
+// workgroup's share of its XCD's L2; LABNOTES R10.1 sets it against the measured counters.)
+inline int trail_sim_hits(const PairTrail& t, int cap) {
+    std::vector<int> lru;   // most recent first
+    auto touch = [&](int b) -> bool {
+        bool hit = false;
+        for (size_t k = 0; k < lru.size(); ++k)
+            if (lru[k] == b) { lru.erase(lru.begin() + (long)k); hit = true; break; }
+        lru.insert(lru.begin(), b);
+        if ((int)lru.size() > cap) lru.pop_back();
+        return hit;
+    };
+    int hits = 0;
+    for (int b = 1; b < t.n_buoys; ++b) touch(b);
+    if (t.first_load >= 0) hits += touch(t.first_load);
+    for (const TrailStep& s : t.steps) {
+        if (s.load_idx >= 0) hits += touch(s.load_idx);
+        if (s.reload) hits += touch(s.load2);
+    }
+    return hits;
+}
+
+// steps from a list of pairs in walking order (the first one holds B-1, resident in array 1): a pair that shares a buoy
+// with the one before it keeps that buoy where it is; one that shares none is a reload of both arrays
+inline void trail_from_pairs(int B, const std::vector<std::pair<int, int>>& pairs, PairTrail* t) {
+    t->n_buoys = B;
+    t->steps.clear();
+    t->loads = t->reloads = 0;
+    t->first_load = -1;
+    if (pairs.empty()) return;
+    t->first_load = pairs[0].first == B - 1 ? pairs[0].second : pairs[0].first;
+    int arr_of[2] = {t->first_load, B - 1};
+    for (size_t k = 0; k < pairs.size(); ++k) {
+        const int a = pairs[k].first, b = pairs[k].second;
+        TrailStep s{};
+        s.i = a < b ? a : b;
+        s.j = a < b ? b : a;
+        s.out_idx = trail_out_idx(B, s.i, s.j);
+        s.xi_arr = arr_of[0] == s.i ? 0 : 1;
+        s.load_arr = 0; s.load_idx = -1; s.reload = 0; s.load2 = -1;
+        if (k + 1 < pairs.size()) {
+            const int c = pairs[k + 1].first, d = pairs[k + 1].second;
+            const bool keep_c = c == a || c == b, keep_d = d == a || d == b;
+            if (keep_c == keep_d) {          // no shared buoy (or the same pair again, which the planner never emits)
+                s.reload = 1;
+                s.load_arr = 0; s.load_idx = c < d ? c : d; s.load2 = c < d ? d : c;
+                arr_of[0] = s.load_idx; arr_of[1] = s.load2;
+                t->loads += 2;
+                ++t->reloads;
+            } else {
+                const int keep = keep_c ? c : d;
+                s.load_arr = arr_of[0] == keep ? 1 : 0;
+                s.load_idx = keep_c ? d : c;
+                arr_of[s.load_arr] = s.load_idx;
+                ++t->loads;
+            }
+        }
+        t->steps.push_back(s);
+    }
+    t->sim_hits2 = trail_sim_hits(*t, 2);
+    t->sim_hits3 = trail_sim_hits(*t, 3);
+}
+
+// THE order k_win walks: runs that hand the anchor over.  A run (a, r1), (a, r2), ... keeps the anchor a where it is and
+// streams the r, and its last pair (a, r_last) is followed by (r_last, r'): the spectrum streamed last stays in ITS array
+// as the next anchor, and the stream moves to the array the old anchor leaves.  Every buoy becomes anchor once, with the
+// buoys that have not been one as its stream, so every pair appears once, no step reloads both arrays whatever the parity
+// of B (min_reloads = 0), and no anchor is ever loaded.  Each run streams the previous run's order backwards (less its
+// last buoy, the new anchor), so its first request is the spectrum requested second to last.  The first run is anchored
+// at B-1 (resident behind phase 1) and streams B-2 first, which phase 1 stored last but one.  Anchors alternate between
+// the highest and the lowest buoy left, streamed from the far end, which puts X_i into array 0 at every step.
+// (An Eulerian trail of the complete graph on buoys 1 .. B-1 -- one shared buoy per step, changing at every step -- was
+// built and measured first: odd B forces (B-1)/2 - 1 reloads, and no spectrum comes back before two others have passed;
+// LABNOTES R10.1 has its table and counters.)
+inline PairTrail plan_pair_trail(int B) {
+    PairTrail t;
+    t.n_buoys = B;
+    const int n = B - 1;
+    std::vector<std::pair<int, int>> pairs;
+    std::vector<int> order;
+    for (int r = n - 1; r >= 1; --r) order.push_back(r);
+    int anchor = n;
+    while (!order.empty()) {
+        for (int r : order) pairs.push_back({anchor, r});
+        anchor = order.back();
+        order.pop_back();
+        for (size_t a = 0, b = order.size(); a + 1 < b; ++a, --b) { const int x = order[a]; order[a] = order[b - 1]; order[b - 1] = x; }
+    }
+    trail_from_pairs(B, pairs, &t);
+    t.min_reloads = 0;
+    return t;
+}
+
+// what k_win's phase 2 can walk: X_i in array 0 at every step and never a reload of both arrays (it has one copy of h1
+// per request target, none per role).  rmx_create refuses a table that is anything else.
+inline bool trail_kernel_ok(const PairTrail& t) {
+    for (const TrailStep& s : t.steps)
+        if (s.xi_arr != 0 || s.reload != 0) return false;
+    return true;
+}
+
+// The kernel's copy: (pairs + 1) entries of four ints {out_idx, load_arr, load_idx, 0} (16 bytes: one scalar load).  Entry
+// 0 is the last pair of phase 1, (0, B-1), whose request is first_load into array 0; entry k + 1 is step k.  Where a step
+// requests nothing, the entry names a spectrum that exists (the kernel requests unconditionally into dead registers).
+// Empty for a table the kernel cannot walk (trail_kernel_ok).
+inline std::vector<int32_t> encode_pair_trail(const PairTrail& t) {
+    std::vector<int32_t> e;
+    if (!trail_kernel_ok(t)) return e;
+    const int B = t.n_buoys;
+    e.reserve(4 * (t.steps.size() + 1));
+    const int some = B > 1 ? B - 1 : 0;
+    e.insert(e.end(), {trail_out_idx(B, 0, B - 1), 0, t.first_load >= 0 ? t.first_load : some, 0});
+    for (const TrailStep& s : t.steps)
+        e.insert(e.end(), {s.out_idx, s.load_arr, s.load_idx >= 0 ? s.load_idx : some, 0});
+    return e;
 }
 
 // ---- chunk arithmetic of the generic path ----------------------------------------------------------------------------

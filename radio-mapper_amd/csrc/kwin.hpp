@@ -54,8 +54,8 @@ __device__ __forceinline__ void load_tw1(float2 (&tw1)[16], const float4* __rest
 // Fused window kernel: one workgroup (512 threads, <= 256 VGPRs, one per CU) per capture window.
 //   phase 1  forward spectra of all B buoys -> this window's scratch (thread-private layout: every
 //            thread later re-reads exactly the float4s it stored, so no visibility protocol is needed)
-//   phase 2  anchor runs over the pair list: X_i stays in registers for its run, X_j streams one pair
-//            ahead; conj-multiply merged into the first radix-16 pass; ONE workgroup barrier per pair.
+//   phase 2  the remaining pairs in runs that hand the anchor over: consecutive pairs share a spectrum that stays in
+//            registers, the other one streams one pair ahead; conj-multiply merged into the first radix-16 pass; ONE workgroup barrier per pair.
 // LDS: two exchange images (alternating by transform/pair, which is what makes one barrier enough:
 // a wave only writes its own half-wave regions of the image the others are not reading), the TW2
 // table, and two small double-buffered records per wave for the argmax: the wave's winner with its
@@ -141,21 +141,26 @@ __device__ __forceinline__ void resolve_batch(int lane, const float4* red, const
     }
 }
 
-// Schedule of one window (all pairs i<j of B buoys; the anchor spectrum X_i is resident in registers,
-// X_j streams one pair ahead):
-//   anchor 0      X_0 is transformed straight into the anchor registers (never stored); every further
-//                 X_e is transformed once, stored once, and used at once, from registers, for (0,e);
-//   anchor i>=1   one anchor load, then the X_j stream, walking j down for odd i and up for even i so
-//                 that each anchor starts on the spectra the previous one touched last.
-// HBM/L2 traffic per window at B = 8: 8 inputs (256 KiB) + 7 spectrum stores (448 KiB) + 27
-// spectrum loads of 64 KiB, of which ~8 are L2-hot, instead of 8 stores + 35 loads.
+// Schedule of one window (all pairs i<j of B buoys; two register arrays of one spectrum each, sa and sb):
+//   anchor 0      X_0 is transformed straight into sa (never stored); every further X_e is transformed once into sb,
+//                 stored once, and used at once, from registers, for (0,e).  X_{B-1} stays in sb behind this phase;
+//   handover runs the pairs among buoys 1 .. B-1 in the order of a host-planned table (host::plan_pair_trail, `trail`).
+//                 A run keeps its anchor in one array and streams its partners through the other, one pair ahead; the
+//                 partner streamed last stays where it is as the next run's anchor, and the stream moves to the array the
+//                 old anchor leaves.  Anchors go B-1, 1, B-2, 2, ..., each with the buoys that have not been anchor yet,
+//                 each run walking the previous run's order backwards.  Every step requests ONE spectrum; no anchor is
+//                 ever loaded and no step loads both arrays, whatever the parity or size of B.  X_i is in sa and X_j in
+//                 sb at every step, as the anchor runs had them, so every pair's arithmetic is what it was; the request
+//                 goes to sa or to sb (two copies of h1).
+// Requests per window at B = 8: 8 inputs (256 KiB) + 7 spectrum stores (448 KiB) + 21 spectrum loads of 64 KiB (one from
+// the last pair of anchor 0, 20 from the table's steps) instead of 27 (6 anchors, 21 streamed, X_7 among them again).
 template <bool U8>
 __global__ __launch_bounds__(kThreads, 2) void k_win(const void* __restrict__ iq_v, float4* __restrict__ spec,
                                                      const float4* __restrict__ tw1_g,
                                                      const float2* __restrict__ tw2_g, int n_buoys,
                                                      long first_window, float out_scale,
                                                      int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                                     float* __restrict__ peak, int n_win, int /* was dbg_rt */, int stag) {
+                                                     float* __restrict__ peak, int n_win, const int4* __restrict__ trail, int stag) {
     constexpr bool BOUNDED = false;
     constexpr LagBounds lb{nullptr, 0, 0, 0};   // (named by the bounded branches only)
 #include "kwin_body.hpp"
@@ -169,7 +174,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_win_lb(const void* __restrict__
                                                         const float2* __restrict__ tw2_g, int n_buoys,
                                                         long first_window, float out_scale,
                                                         int* __restrict__ lag_int, float* __restrict__ lag_frac,
-                                                        float* __restrict__ peak, int n_win, int /* was dbg_rt */, int stag, LagBounds lb) {
+                                                        float* __restrict__ peak, int n_win, const int4* __restrict__ trail, int stag, LagBounds lb) {
     constexpr bool BOUNDED = true;
 #include "kwin_body.hpp"
 }

@@ -374,87 +374,75 @@
         store_spec(sb, e);
         pair(sa, sb, out_of(0, e), [&](auto part) __attribute__((always_inline)) { load_x_part(sb, e + 1, part); });
     }
-    if (B > 1) {
-        cvt_x(sb);
-        fwd(sb);
-        store_spec(sb, B - 1);
-        pair(sa, sb, out_of(0, B - 1), [&](auto part) __attribute__((always_inline)) {
-            if (B > 2) {               // next anchor 1 streams downwards from B-1: X_{B-1} is L2-hot
-                load_spec_part(sa, 1, part);
-                load_spec_part(sb, B - 1, part);
-            }
-        });
-    }
-    // ---- anchors 1..B-2: the stream direction alternates (odd anchors walk j down, even ones up), so
-    // the first spectra an anchor streams are the ones the previous anchor touched last (L2 hits).
-    // Between two barriers sit h2 of pair m and h1 of pair m+1, which are independent: waves 0-3 run
-    // them in that order and waves 4-7 (the second wave of each SIMD) in the opposite order, so that
-    // one wave's LDS / barrier / DPP-chain stalls fall on the other's butterfly arithmetic instead of
-    // on the same stalls (all eight waves are otherwise barrier-aligned in lockstep).
+    // ---- the last buoy and the pairs among buoys 1..B-1, in the order of a host-planned table (host::plan_pair_trail:
+    // runs that hand the anchor over).  Entry 0 of the table is the pair (0, B-1), entry k + 1 the order's step k:
+    // {out_idx, load_arr, load_idx, 0}.  Consecutive steps share one buoy, whose spectrum stays in its register array; each
+    // step's h1 requests ONE spectrum (load_idx) into the array whose buoy the next step drops (load_arr: 0 = sa, 1 = sb).
+    // In this order X_i is in sa and X_j in sb at every step (host::trail_kernel_ok, checked where the table is built), so
+    // pair_h1 gets them as the anchor runs gave them and every pair's arithmetic is what it was.  X_{B-1} stays in sb
+    // behind phase 1: the first step is (first_load, B-1), and only first_load is requested, into sa.
     {
-        const int M2 = (B - 1) * (B - 2) / 2;            // pairs of this phase
+        const int M2 = (B - 1) * (B - 2) / 2;            // steps of the order
+        const int4* __restrict__ tab = trail;
+        int4 cur = tab[0];
+        int4 nxt = tab[M2 > 0 ? 1 : 0];
+        if (B > 1) {
+            cvt_x(sb);
+            fwd(sb);
+            store_spec(sb, B - 1);
+            const int fl = cur.z;
+            pair(sa, sb, cur.x, [&](auto part) __attribute__((always_inline)) {
+                if (M2 > 0) load_spec_part(sa, fl, part);
+            });
+        }
+        // h1 of the step in `st`, its request into sa or into sb.  Two ONE-SIDED branches, not an if / else: with an else
+        // side the compiler lays the sides out one behind the other and keeps the spectrum a side requested in registers of
+        // its own across the other side, then moves the registers behind a wait for every request, at every step.  (An
+        // opaque copy of the selector per test: left to itself the compiler folds the tests back into one two-sided branch.)
+        auto h1_step = [&](const int4& st, int tr) __attribute__((always_inline)) {
+            const int li = st.z;
+            const int var = __builtin_amdgcn_readfirstlane(st.y);
+            int v0 = var, v1 = var;
+            asm volatile("" : "+s"(v0));
+            if (v0 == 0) pair_h1(sa, sb, tr, [&](auto part) __attribute__((always_inline)) { load_spec_part(sa, li, part); });
+            asm volatile("" : "+s"(v1));
+            if (v1 != 0) pair_h1(sa, sb, tr, [&](auto part) __attribute__((always_inline)) { load_spec_part(sb, li, part); });
+        };
+        // Step m's h1 sits between the same two barriers as h2 of the pair before it (m = 0: behind h2 of (0, B-1), above).
+        // The two are independent (different images, disjoint registers): waves 0-3 of stag 1 run h2 first, the others h1
+        // first, so that one wave's LDS / barrier / DPP-chain stalls fall on the other's butterfly arithmetic instead of on
+        // the same stalls (all eight waves are otherwise barrier-aligned in lockstep).  ONE copy of h1 between two one-sided
+        // copies of h2, not two sides of h1 + h2 each.
         // SIMD pairs {a, a+2} vs {a+1, a+3} (stag 1): measured best of the splits; 0 = nobody, 5 = everybody late
         // (2: odd waves = SIMDs 1, 3; 3: the second wave of every SIMD; 4: one wave of every SIMD, alternating between SIMDs)
         const bool late_h2 = stag == 1 ? ((wave >> 1) & 1) : stag == 2 ? (wave & 1) : stag == 3 ? (wave >> 2) :
                              stag == 4 ? ((wave ^ (wave >> 2)) & 1) : (stag == 5);
-        auto j_of = [&](int i, int s) -> int { return (i & 1) ? (B - 1 - s) : (i + 1 + s); };
-        int ci = 1, cs = 0;                              // pair m     (anchor, position in its run)
-        int ni = 1, ns = 1;                              // pair m + 1
-        if (ns >= B - 1 - ni) { ++ni; ns = 0; }
-        auto h1_of = [&](int hi, int hs, int tr) __attribute__((always_inline)) {
-            // spectra for the pair after (hi, hs) are requested here
-            int pi = hi, ps = hs + 1;
-            if (ps >= B - 1 - pi) { ++pi; ps = 0; }
-            const bool valid = pi + 1 < B;
-            const bool new_anchor = valid && pi != hi;
-            // Every instruction costs the issuing wave ~2 ns whatever its kind (tools/probe/valu_forms.hip), and the two
-            // uniform branches around each of the eight requests were 45 scalar instructions per pair plus the vector
-            // instructions hipcc used to carry their conditions: the streamed spectrum is now requested unconditionally
-            // (behind the window's last pair an index that exists: the registers are dead there), and a new anchor's
-            // eight requests go out together behind ONE branch, in the first callback (6 of a window's 21 pairs).
-            const int pj = valid ? j_of(pi, ps) : B - 1;
-            pair_h1(sa, sb, tr, [&](auto part) __attribute__((always_inline)) {
-                if constexpr (decltype(part)::value == 0) {
-                    if (new_anchor) {
-                        load_spec_part(sa, pi, std::integral_constant<int, 0>{});
-                        load_spec_part(sa, pi, std::integral_constant<int, 1>{});
-                        load_spec_part(sa, pi, std::integral_constant<int, 2>{});
-                        load_spec_part(sa, pi, std::integral_constant<int, 3>{});
-                        load_spec_part(sa, pi, std::integral_constant<int, 4>{});
-                        load_spec_part(sa, pi, std::integral_constant<int, 5>{});
-                        load_spec_part(sa, pi, std::integral_constant<int, 6>{});
-                        load_spec_part(sa, pi, std::integral_constant<int, 7>{});
-                    }
+#pragma clang loop unroll(disable)
+        for (int m = 0; m <= M2; ++m) {
+            const int4 ahead = tab[m + 2 <= M2 ? m + 2 : M2];   // one step ahead of its use
+            if (m > 0) {
+                barrier_hook(false);
+                // The two waves of a SIMD share its issue slots (and the CU's LDS / vector-memory request paths), and every
+                // arbiter prefers the OLDER one: in-kernel shader-clock stamps (LABNOTES 6.2) showed waves 0-3
+                // spending 51-60 k ticks per window in the two pieces between barriers where waves 4-7 need 57-64 k, and then
+                // waiting ~950 ticks at every barrier for them (waves 4-7: ~270).  Priority outranks age, so waves 4-7 run the
+                // FIRST of their two pieces at priority 1 and the second at 0 (h2 is the piece that reacts to priority).
+                if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+                if (!late_h2) {
+                    pair_h2(seq, cur.x);
+                    if (wave >= 4) __builtin_amdgcn_s_setprio(0);
                 }
-                load_spec_part(sb, pj, part);
-            });
-        };
-        if (M2 > 0) h1_of(ci, cs, seq);
-        for (int m = 0; m < M2; ++m) {
-            barrier_hook(false);
-            const bool has_next = m + 1 < M2;
-            const int out_idx = out_of(ci, j_of(ci, cs));
-            // The two waves of a SIMD share its issue slots (and the CU's LDS / vector-memory request paths), and every
-            // arbiter prefers the OLDER one: in-kernel shader-clock stamps (LABNOTES 6.2) showed waves 0-3
-            // spending 51-60 k ticks per window in the two pieces between barriers where waves 4-7 need 57-64 k, and then
-            // waiting ~950 ticks at every barrier for them (waves 4-7: ~270).  Priority outranks age, so waves 4-7 run the
-            // FIRST of their two pieces at priority 1 and the second at 0.  It only helps the piece that is VALU-bound (h2
-            // as first piece: 63.9 -> 58.1 k ticks; h1 does not react to priority), so the launch gains 0.8-1.0 %, not the 8 %
-            // an even split would give; priority during h2 only and priority 3 measured the same or less.
-            if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-            if (late_h2) {
-                if (has_next) h1_of(ni, ns, seq + 1);
-                if (wave >= 4) __builtin_amdgcn_s_setprio(0);
-                pair_h2(seq, out_idx);
-            } else {
-                pair_h2(seq, out_idx);
-                if (wave >= 4) __builtin_amdgcn_s_setprio(0);
-                if (has_next) h1_of(ni, ns, seq + 1);
             }
-            ++seq;
-            ci = ni; cs = ns;
-            ++ns;
-            if (ns >= B - 1 - ni) { ++ni; ns = 0; }
+            if (m < M2) h1_step(nxt, m > 0 ? seq + 1 : seq);
+            if (m > 0) {
+                if (late_h2) {
+                    if (wave >= 4) __builtin_amdgcn_s_setprio(0);
+                    pair_h2(seq, cur.x);
+                }
+                ++seq;
+            }
+            cur = nxt;
+            nxt = ahead;
         }
     }
     seq = 0;   // any wave may resolve the last pairs; take wave 0

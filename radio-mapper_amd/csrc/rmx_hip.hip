@@ -93,6 +93,7 @@ struct rmx_ctx {
     int pk = 0;             // fused path: 1 = k_winp (k_win on packed fp32)
     int win8 = 0;           // fused path: 1 = k_win8 (8 points x 1024 threads, 4 waves/SIMD), 0 = k_win
     int stag = 1;           // k_win8: which waves run the two halves between barriers in the opposite order
+    int stag_kwin = 0;      // k_win / k_win_lb: the same choice; 0 (nobody) measured best since h1 stands once between two copies of h2 (LABNOTES R10.2)
     float4* d_tw1_8 = nullptr;
     float2* d_tb8 = nullptr;
     float2* d_tc8 = nullptr;
@@ -101,6 +102,7 @@ struct rmx_ctx {
     float4* d_spec = nullptr;
     float4* d_tw1 = nullptr;
     float2* d_tw2 = nullptr;
+    int4* d_trail = nullptr;   // k_win: the order of a window's pairs among buoys 1 .. B-1 (host::plan_pair_trail)
     rmx::PairItem* d_items = nullptr;
     int* d_part_begin = nullptr;
     void* d_in = nullptr;      size_t d_in_bytes = 0;
@@ -1295,8 +1297,13 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
         RMX_HIP(c, hipMalloc((void**)&c->d_tw2, tw2.size() * sizeof(float2)));
         RMX_HIP(c, hipMemcpy(c->d_tw1, tw1.data(), tw1.size() * sizeof(float4), hipMemcpyHostToDevice));
         RMX_HIP(c, hipMemcpy(c->d_tw2, tw2.data(), tw2.size() * sizeof(float2), hipMemcpyHostToDevice));
-        c->scratch_bytes = c->spec_bytes + tw1.size() * sizeof(float4) + tw2.size() * sizeof(float2);
+        const std::vector<int32_t> trail = host::encode_pair_trail(host::plan_pair_trail(n_buoys));
+        if (trail.empty()) return fail(c, RMX_E_INVAL, "k_win cannot walk the pair order planned for %d buoys", n_buoys);
+        RMX_HIP(c, hipMalloc((void**)&c->d_trail, trail.size() * sizeof(int32_t)));
+        RMX_HIP(c, hipMemcpy(c->d_trail, trail.data(), trail.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        c->scratch_bytes = c->spec_bytes + tw1.size() * sizeof(float4) + tw2.size() * sizeof(float2) + trail.size() * sizeof(int32_t);
         c->stag = (int)c->knobs.get_or("stag", 1);
+        c->stag_kwin = (int)c->knobs.get_or("stag", 0);
         c->small_batch = c->knobs.get_or("small4096", 1) != 0;
 #ifdef RMX_EXPERIMENTS
         {   // the two other builds of the fused kernel: measured slower, not in the default build
@@ -1355,6 +1362,7 @@ void rmx_destroy(rmx_ctx* c) {
     if (c->d_spec) (void)hipFree(c->d_spec);
     if (c->d_tw1) (void)hipFree(c->d_tw1);
     if (c->d_tw2) (void)hipFree(c->d_tw2);
+    if (c->d_trail) (void)hipFree(c->d_trail);
     for (void* p : {(void*)c->d_tw1_8, (void*)c->d_tb8, (void*)c->d_tc8})
         if (p) (void)hipFree(p);
     if (c->d_items) (void)hipFree(c->d_items);
@@ -1425,7 +1433,7 @@ int rmx_set_option(rmx_ctx* c, const char* key, long value) {
     }
     if (!strcmp(key, "stag")) {
         if (value < 0 || value > 5) return fail(c, RMX_E_INVAL, "stag %ld not in 0..5", value);
-        c->stag = (int)value;
+        c->stag = c->stag_kwin = (int)value;
         return RMX_OK;
     }
     if (!strcmp(key, "small4096")) {
@@ -1701,7 +1709,7 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
                 constexpr bool U8 = decltype(U)::value;
                 auto go = [&](auto kern, auto... lb) {
                     return launch(c, kTkPair4096, kern, dim3(wgrid), dim3(kThreads), kLdsWinBytes, d_iq, c->d_spec, c->d_tw1, c->d_tw2,
-                                  c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, 0, c->stag, lb...);
+                                  c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, (const int4*)c->d_trail, c->stag_kwin, lb...);
                 };
 #ifdef RMX_EXPERIMENTS
                 if (c->win8)

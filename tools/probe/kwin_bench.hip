@@ -12,8 +12,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
+#include "../../radio-mapper_amd/csrc/host_plan.hpp"
 #include "../../radio-mapper_amd/csrc/kwin.hpp"
 #if !defined(KWB_NO_KWIN2)
 #include "kwin2.hpp"
@@ -45,7 +47,7 @@ __global__ void k_gen(float2* iq, int B, int N) {
 }
 
 struct Bufs {
-    float2* iq; float4* spec; float4* tw1; float2* tw2; int* li; float* lf; float* pk;
+    float2* iq; float4* spec; float4* tw1; float2* tw2; int4* trail; int* li; float* lf; float* pk;
     int W, B; float out_scale;
 };
 
@@ -53,19 +55,11 @@ typedef void (*launch_fn)(const Bufs&, hipStream_t);
 
 static void launch_base(const Bufs& b, hipStream_t s) {
     hipLaunchKernelGGL(k_win<false>, dim3(256), dim3(kThreads), kLdsWinBytes, s, (const void*)b.iq, b.spec, b.tw1, b.tw2, b.B, 0L,
-                       b.out_scale, b.li, b.lf, b.pk, b.W, 0, 1);
+                       b.out_scale, b.li, b.lf, b.pk, b.W, (const int4*)b.trail, 1);
 }
-#define KWB_STAG(NAME, ST)                                                                                               \
-    static void NAME(const Bufs& b, hipStream_t s) {                                                                    \
-        hipLaunchKernelGGL(k_win<false>, dim3(256), dim3(kThreads), kLdsWinBytes, s, (const void*)b.iq, b.spec, b.tw1, b.tw2, \
-                           b.B, 0L, b.out_scale, b.li, b.lf, b.pk, b.W, 0, ST);                                        \
-    }
-KWB_STAG(launch_stag2, 2)
-KWB_STAG(launch_stag3, 3)
-KWB_STAG(launch_stag4, 4)
 static void launch_stag0(const Bufs& b, hipStream_t s) {
     hipLaunchKernelGGL(k_win<false>, dim3(256), dim3(kThreads), kLdsWinBytes, s, (const void*)b.iq, b.spec, b.tw1, b.tw2, b.B, 0L,
-                       b.out_scale, b.li, b.lf, b.pk, b.W, 0, 0);
+                       b.out_scale, b.li, b.lf, b.pk, b.W, (const int4*)b.trail, 0);
 }
 #ifdef KWB_HAVE_KWIN2
 #define KWB_V2(NAME, ...)                                                                                               \
@@ -111,21 +105,26 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&b.tw1, tw1.size() * 16)); CK(hipMalloc(&b.tw2, tw2.size() * 8));
     CK(hipMemcpy(b.tw1, tw1.data(), tw1.size() * 16, hipMemcpyHostToDevice));
     CK(hipMemcpy(b.tw2, tw2.data(), tw2.size() * 8, hipMemcpyHostToDevice));
+    {   // the order of a window's pairs among buoys 1 .. B-1
+        const host::PairTrail tr = host::plan_pair_trail(B);
+        const std::vector<int32_t> e = host::encode_pair_trail(tr);
+        if (e.empty()) { printf("the kernel cannot walk this pair order\n"); return 1; }
+        CK(hipMalloc(&b.trail, e.size() * 4));
+        CK(hipMemcpy(b.trail, e.data(), e.size() * 4, hipMemcpyHostToDevice));
+        printf("pair order: %d steps, %d requests + 1 from phase 1, %d reloads, simulated hits LRU2 %d LRU3 %d\n", (int)tr.steps.size(),
+               tr.loads, tr.reloads, tr.sim_hits2, tr.sim_hits3);
+    }
     hipLaunchKernelGGL(k_gen, dim3((unsigned)((long)W * B * N / 256)), dim3(256), 0, 0, b.iq, B, N);
     CK(hipDeviceSynchronize());
 
     std::vector<Variant> vars = {
-        {"k_win stag=1 (production)", launch_base, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win stag=0", launch_stag0, (const void*)k_win<false>, kLdsWinBytes},
-#ifdef KWB_ALL_STAGS
-        {"k_win stag=2 (odd waves late)", launch_stag2, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win stag=3 (waves 4-7 late)", launch_stag3, (const void*)k_win<false>, kLdsWinBytes},
-        {"k_win stag=4 (one of every SIMD, alternating)", launch_stag4, (const void*)k_win<false>, kLdsWinBytes},
-#endif
+        {"k_win stag=1", launch_base, (const void*)k_win<false>, kLdsWinBytes},
+        {"k_win stag=0 (production)", launch_stag0, (const void*)k_win<false>, kLdsWinBytes},
 #ifdef KWB_HAVE_KWIN2
         KWB_KWIN2_TABLE
 #endif
     };
+    if (argc > 6) vars = {vars.at((size_t)atoi(argv[6]))};   // argv[6]: that variant alone (counter passes: one kernel name, one order)
     for (auto& v : vars) CK(hipFuncSetAttribute(v.kfn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds));
 
     hipEvent_t e0, e1;
@@ -156,7 +155,17 @@ int main(int argc, char** argv) {
                     for (int j = i + 1; j < B; ++j, ++o)
                         if (li[(size_t)w * P + o] != delay_of(w, j) - delay_of(w, i)) ++bad_truth;
             }
-            if (vi == 0 && round == 0) { li0 = li; lf0 = lf; pk0 = pk; }
+            if (vi == 0 && round == 0) {
+                li0 = li; lf0 = lf; pk0 = pk;
+                if (argc > 5 && strcmp(argv[5], "-") != 0) {   // argv[5]: prefix of three raw files ("-": none), to set two builds of the harness against each other
+                    const char* ext[3] = {".li", ".lf", ".pk"};
+                    const void* src[3] = {li.data(), lf.data(), pk.data()};
+                    for (int k = 0; k < 3; ++k) {
+                        FILE* f = fopen((std::string(argv[5]) + ext[k]).c_str(), "wb");
+                        if (f) { fwrite(src[k], 4, li.size(), f); fclose(f); }
+                    }
+                }
+            }
             else
                 for (size_t k = 0; k < li.size(); ++k) {
                     diff_li += li[k] != li0[k];
