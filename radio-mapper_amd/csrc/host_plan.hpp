@@ -129,7 +129,7 @@ inline bool lag_interval_ok(int lo, int hi, int n_samples, bool* full) {
 
 // one band [lo, hi] in cycles per sample (rmx_xcorr_batch_weighted) -> the signed bins s in [-N, N-1] of the 2N-point
 // transform with lo <= s / 2N <= hi (exact: 2N is a power of two); hi = 0.5 is bin N, which -N stands for: clamped to N-1
-enum BandCheck { kBandOk = 0, kBandNoInterval = 1, kBandNoBin = 2 };   // not an interval inside [-0.5, 0.5] / keeps no bin
+enum BandCheck { kBandOk = 0, kBandNoInterval = 1, kBandNoBin = 2 };   // not an interval inside [-0.5, 0.5] / no bin kept
 inline BandCheck band_to_bins(double lo, double hi, int n_samples, int32_t* s_lo, int32_t* s_hi) {
     if (!std::isfinite(lo) || !std::isfinite(hi) || lo < -0.5 || hi > 0.5 || lo > hi) return kBandNoInterval;
     const long N = n_samples, L = 2L * N;

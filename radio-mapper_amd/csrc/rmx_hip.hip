@@ -24,6 +24,7 @@
 
 #include "../../include/rmx.h"
 #include "host_plan.hpp"
+#include "host_request.hpp"
 #include "lag_bounds.hpp"
 #include "xspec_weight.hpp"
 #include "xspec_bands.hpp"
@@ -1523,26 +1524,6 @@ static int ensure_quality(rmx_ctx* c, size_t elems) {
     return RMX_OK;
 }
 
-// ---- what the correlation entries share ----------------------------------------------------------------------------
-static int check_n_windows(rmx_ctx* c, int n_windows) {
-    if (n_windows < 0 || n_windows > c->max_windows)
-        return fail(c, RMX_E_INVAL, "n_windows %d not in 0..max_windows=%d", n_windows, c->max_windows);
-    return RMX_OK;
-}
-// the shape of a batch: n_windows in range; pairs == NULL is the default list, and *n_pairs becomes its length
-static int check_batch(rmx_ctx* c, int n_windows, const int32_t* pairs, int* n_pairs) {
-    const int rc = check_n_windows(c, n_windows);
-    if (rc != RMX_OK) return rc;
-    const int all_pairs = c->n_buoys * (c->n_buoys - 1) / 2;
-    if (!pairs) {
-        if (*n_pairs != 0 && *n_pairs != all_pairs)
-            return fail(c, RMX_E_INVAL, "pairs == NULL needs n_pairs == 0 or %d, got %d", all_pairs, *n_pairs);
-        *n_pairs = all_pairs;
-    }
-    if (*n_pairs < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", *n_pairs);
-    return RMX_OK;
-}
-
 // host windows: the ctx-owned device copy they go to
 static int ensure_in(rmx_ctx* c, size_t in_bytes) {
     if (c->d_in_bytes >= in_bytes) return RMX_OK;
@@ -1731,158 +1712,91 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
     return done(RMX_OK);
 }
 
-// ---- the validators, one per feature ---------------------------------------------------------------------------------
-// rmx_xcorr_batch_weighted: the weighting, the window count and the bands, one per window or one for all, converted to
-// signed bins in *bins.  *weighted stays false when there is no band (or the full one) and no weighting: the plain call.
-static int check_weighted(rmx_ctx* c, int n_windows, const double* band_cps, int band_per_window, unsigned weighting,
-                          std::vector<int32_t>* bins, bool* weighted) {
-    if (weighting != RMX_WEIGHT_NONE && weighting != RMX_WEIGHT_PHAT)
-        return fail(c, RMX_E_INVAL, "unknown weighting %u (RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1)", weighting);
-    const int rc = check_n_windows(c, n_windows);
-    if (rc != RMX_OK) return rc;
-    const int N = c->n_samples;
-    const long rows = band_cps ? (band_per_window ? (long)n_windows : 1L) : 1L;
-    bins->resize((size_t)(2 * rows));
-    bool all_full = true;
-    for (long r = 0; r < rows; ++r) {
-        const double lo = band_cps ? band_cps[2 * r] : -0.5, hi = band_cps ? band_cps[2 * r + 1] : 0.5;
-        const char* shared = band_per_window ? "" : " (one band shared by every window)";
-        int32_t* s = bins->data() + 2 * r;
-        const host::BandCheck bc = host::band_to_bins(lo, hi, N, &s[0], &s[1]);
-        if (bc == host::kBandNoInterval)
-            return fail(c, RMX_E_INVAL, "band of window %ld%s: [%g, %g] is not an interval inside [-0.5, 0.5] cycles per sample",
-                        r, shared, lo, hi);
-        if (bc == host::kBandNoBin)
-            return fail(c, RMX_E_INVAL, "band of window %ld%s: [%g, %g] keeps no bin of the %ld-point transform", r, shared, lo,
-                        hi, 2L * N);
-        all_full = all_full && s[0] == -N && s[1] == N - 1;
-    }
-    *weighted = !(all_full && weighting == RMX_WEIGHT_NONE);
-    return RMX_OK;
-}
-
-// rmx_xcorr_batch_bounded: one interval per pair, shared or per window -- per GROUP of `integrate` windows in an
-// integrated call.  *bounded stays false when every interval is the full one and nothing is integrated: that is the
-// unbounded call, whatever route it takes (the whole-window generic kernels, which a bounded call avoids, included).
-static int check_bounded(rmx_ctx* c, int n_windows, int n_pairs, int integrate, const int32_t* lag_bounds,
-                         int bounds_per_window, long* rows, bool* bounded) {
-    const int nm1 = c->n_samples - 1;
-    *rows = bounds_per_window ? (long)(n_windows / integrate) * n_pairs : (long)n_pairs;
-    bool all_full = true;
-    for (long r = 0; r < *rows; ++r) {
-        const int lo = lag_bounds[2 * r], hi = lag_bounds[2 * r + 1];
-        bool full = false;
-        if (!host::lag_interval_ok(lo, hi, c->n_samples, &full))
-            return fail(c, RMX_E_INVAL, "lag_bounds of %s %ld, pair %ld: [%d, %d] is not an interval inside [%d, %d]",
-                        integrate > 1 ? "group" : "window", bounds_per_window ? r / n_pairs : -1L, r % n_pairs, lo, hi, -nm1, nm1);
-        all_full = all_full && full;
-    }
-    *bounded = !(all_full && integrate == 1);
-    return RMX_OK;
-}
-
-// The request's small host arrays onto the device, through the ctx's own staging (the caller may reuse its arrays on
-// return), and into `call`: the bands as signed bins where the call is weighted, the lag intervals where it is bounded.
-// Both the correlation entries (xcorr_request) and the Doppler search (rmx_caf_batch_request) describe their call so.
-static int stage_request(rmx_ctx* c, XcorrCall* call, bool weighted, const std::vector<int32_t>& bins, bool band_rows_per_window,
-                         unsigned weighting, bool bounded, const int32_t* lag_bounds, long bound_rows, int bounds_per_window,
-                         int n_pairs) {
-    if (weighted) {
-        const int rc = stage_to_device(c, &c->band_stage, bins.data(), bins.size());
+// ---- the request of one call (host_request.hpp) and its way to the device ------------------------------------------
+// The checked request's small host arrays onto the device, through the ctx's own staging (the caller may reuse its arrays
+// on return), and into `call`: the bands as signed bins where the call is weighted, the lag intervals where it is
+// bounded.  Both the correlation entries (xcorr_request) and the Doppler search (rmx_caf_batch_request) describe their
+// call so.
+static int describe_call(rmx_ctx* c, const host::Request& rq, XcorrCall* call) {
+    if (rq.weighted) {
+        const int rc = stage_to_device(c, &c->band_stage, rq.bins.data(), rq.bins.size());
         if (rc != RMX_OK) return rc;
-        call->wt = XWeight{c->band_stage.d, band_rows_per_window ? 2L : 0L, 0L, c->n_buoys, weighting == RMX_WEIGHT_PHAT ? 1 : 0, 1.0f};
+        // band_stage of a banded call: [full band | band set].  PHAT keeps call->wt on the full band (every bin whitened,
+        // none dropped); without it the forward kernels are the plain ones
+        if (rq.n_bands > 1) call->bs = BandSet{c->band_stage.d + 2, rq.band_per_window ? 2L * rq.n_bands : 0L, 0L, rq.n_bands};
+        if (rq.n_bands == 1 || rq.phat)
+            call->wt = XWeight{c->band_stage.d, rq.n_bands == 1 && rq.band_per_window ? 2L : 0L, 0L, c->n_buoys, rq.phat ? 1 : 0, 1.0f};
     }
-    if (bounded) {
-        const int rc = stage_to_device(c, &c->lb_stage, lag_bounds, (size_t)(2 * bound_rows));
+    if (rq.bounded) {
+        const int rc = stage_to_device(c, &c->lb_stage, rq.bounds, (size_t)(2 * rq.bound_rows));
         if (rc != RMX_OK) return rc;
-        call->lb = LagBounds{c->lb_stage.d, bounds_per_window ? 2L * n_pairs : 0L, 0L, n_pairs};
+        call->lb = LagBounds{c->lb_stage.d, rq.bounds_per_window ? 2L * rq.n_pairs : 0L, 0L, rq.n_pairs};
     }
     return RMX_OK;
 }
 
-// What all six correlation entries do, and none of them through another: check the arguments -- the checks of the entries
-// that take `integrate` (grouped), then the weighted entry's, then the bounded entry's, so an input with several bad
-// arguments is refused for the same one whichever entry it came through --, copy the bands (as signed bins) and the lag
+// What all eight correlation entries do, and none of them through another: hand their arguments to host::check_request
+// -- every refusal, in one order whichever entry the call came through --, copy the bands (as signed bins) and the lag
 // intervals into ctx-owned device buffers, describe the call in an XcorrCall and dispatch it.  The plain call is
 // integrate = 1, no band, no weighting, no bounds.
-static int xcorr_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, bool grouped, int integrate,
-                         const double* band_cps, int band_per_window, unsigned weighting, const int32_t* lag_bounds,
-                         int bounds_per_window, int refine, int32_t* lag_int, float* lag_frac, float* peak, float* quality,
-                         unsigned flags) {
+static int xcorr_request(rmx_ctx* c, host::RequestArgs a, unsigned flags) {
     if (!c) return RMX_E_INVAL;
-    std::vector<int32_t> bins, full;
-    bool weighted = false, bounded = false;
-    long bound_rows = 0;
-    int rc;
-    if (grouped) {   // K and the group count
-        if (integrate < 1) return fail(c, RMX_E_INVAL, "integrate = %d: at least one window per group", integrate);
-        if (n_windows <= 0 || n_windows % integrate != 0)
-            return fail(c, RMX_E_INVAL, "n_windows = %d is not a positive multiple of integrate = %d", n_windows, integrate);
-        if (integrate > 1 && !lag_bounds) {   // the integrating kernels always carry bounds: the full interval per pair
-            const int np = pairs ? n_pairs : c->n_buoys * (c->n_buoys - 1) / 2;
-            if (np < 0) return fail(c, RMX_E_INVAL, "n_pairs %d < 0", n_pairs);
-            full.resize((size_t)(2 * (np > 0 ? np : 1)));   // (np == 0 is never read: a call without pairs returns before the bounds)
-            for (int q = 0; q < np; ++q) {
-                full[2 * q] = -(c->n_samples - 1);
-                full[2 * q + 1] = c->n_samples - 1;
-            }
-            lag_bounds = full.data();
-            bounds_per_window = 0;
-        }
-    }
-    if (!iq || !lag_int || !lag_frac || !peak) return fail(c, RMX_E_INVAL, "NULL buffer");
-    if (band_cps || weighting != RMX_WEIGHT_NONE) {
-        rc = check_weighted(c, n_windows, band_cps, band_per_window, weighting, &bins, &weighted);
-        if (rc != RMX_OK) return rc;
-        if (weighted && n_windows == 0) return RMX_OK;   // (the weighted entry does not look at the pairs of an empty batch)
-    }
-    rc = check_batch(c, n_windows, pairs, &n_pairs);
-    if (rc != RMX_OK) return rc;
-    if (n_windows == 0 || n_pairs == 0) return RMX_OK;
-    if (lag_bounds) {
-        rc = check_bounded(c, n_windows, n_pairs, integrate, lag_bounds, bounds_per_window, &bound_rows, &bounded);
-        if (rc != RMX_OK) return rc;
-    }
-    // rmx_xcorr_batch_refined: U, refused after the other three and before anything is staged
-    if (refine != 0 && refine != 2 && refine != 4 && refine != 8 && refine != 16)
-        return fail(c, RMX_E_INVAL, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", refine);
-    // rmx_xcorr_batch_quality: the fourth output must not lie over one of the other three (k_quality reads peak while it
-    // writes quality); refused after the other four and before anything is staged
-    if (quality) {
-        const size_t rows = (size_t)(n_windows / integrate) * n_pairs;
-        const char *q0 = reinterpret_cast<const char*>(quality), *q1 = q0 + 4 * rows * sizeof(float);
-        const struct { const char* name; const void* p; } outs[3] = {{"lag_int", lag_int}, {"lag_frac", lag_frac}, {"peak", peak}};
-        for (const auto& o : outs) {
-            const char* p0 = static_cast<const char*>(o.p);
-            if (p0 < q1 && q0 < p0 + rows * sizeof(float))
-                return fail(c, RMX_E_INVAL, "quality overlaps %s: the %zu x 4 floats of quality need a buffer of their own", o.name, rows);
-        }
-    }
+    a.n_buoys = c->n_buoys;
+    a.n_samples = c->n_samples;
+    a.max_windows = c->max_windows;
+    host::Request rq;
+    std::string why;
+    int rc = host::check_request(a, &rq, &why);
+    if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
+    if (rq.empty) return RMX_OK;
     RMX_HIP(c, hipSetDevice(c->device));
     XcorrCall call;
-    call.integ = integrate;
-    call.refine = refine;
-    call.quality = quality;
-    rc = stage_request(c, &call, weighted, bins, band_cps && band_per_window, weighting, bounded, lag_bounds, bound_rows,
-                       bounds_per_window, n_pairs);
+    call.integ = rq.integ;
+    call.refine = rq.refine;
+    call.quality = a.quality;
+    rc = describe_call(c, rq, &call);
     if (rc != RMX_OK) return rc;
-    return xcorr_dispatch(c, call, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+    return xcorr_dispatch(c, call, a.iq, a.n_windows, a.pairs, rq.n_pairs, a.lag_int, a.lag_frac, a.peak, flags);
+}
+
+// the arguments every correlation entry takes
+static host::RequestArgs batch_args(const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int32_t* lag_int, float* lag_frac,
+                                    float* peak) {
+    host::RequestArgs a;
+    a.iq = iq;
+    a.n_windows = n_windows;
+    a.pairs = pairs;
+    a.n_pairs = n_pairs;
+    a.lag_int = lag_int;
+    a.lag_frac = lag_frac;
+    a.peak = peak;
+    return a;
+}
+// ... and what the weighted entry adds, which every entry behind it takes too
+static host::RequestArgs weighted_args(host::RequestArgs a, const double* band_cps, int band_per_window, unsigned weighting,
+                                       const int32_t* lag_bounds, int bounds_per_window) {
+    a.band_cps = band_cps;
+    a.band_per_window = band_per_window;
+    a.weighting = weighting;
+    a.lag_bounds = lag_bounds;
+    a.bounds_per_window = bounds_per_window;
+    return a;
 }
 
 int rmx_xcorr_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                     int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0, 0, lag_int, lag_frac, peak,
-                         nullptr, flags);
+    return xcorr_request(c, batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), flags);
 }
 
 // rmx_xcorr_batch with a lag interval per (window, pair).  Every interval the full one IS the plain call.
 int rmx_xcorr_batch_bounded(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                             const int32_t* lag_bounds, int bounds_per_window, int32_t* lag_int, float* lag_frac, float* peak,
                             unsigned flags) {
-    if (!c) return RMX_E_INVAL;
-    if (!lag_bounds) return fail(c, RMX_E_INVAL, "NULL buffer");
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, nullptr, 0, RMX_WEIGHT_NONE, lag_bounds, bounds_per_window, 0, lag_int,
-                         lag_frac, peak, nullptr, flags);
+    host::RequestArgs a = batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak);
+    a.bounds_required = true;
+    a.lag_bounds = lag_bounds;
+    a.bounds_per_window = bounds_per_window;
+    return xcorr_request(c, a, flags);
 }
 
 // rmx_xcorr_batch(_bounded) on band-masked and / or PHAT-whitened spectra.  No band (or the full one) and no weighting IS
@@ -1891,8 +1805,8 @@ int rmx_xcorr_batch_weighted(rmx_ctx* c, const void* iq, int n_windows, const in
                              const double* band_cps, int band_per_window, unsigned weighting,
                              const int32_t* lag_bounds, int bounds_per_window,
                              int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, band_cps, band_per_window, weighting, lag_bounds,
-                         bounds_per_window, 0, lag_int, lag_frac, peak, nullptr, flags);
+    return xcorr_request(c, weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, band_per_window,
+                                          weighting, lag_bounds, bounds_per_window), flags);
 }
 
 // rmx_xcorr_batch_weighted under n_bands bands per window over ONE set of forward spectra (xspec_bands.hpp): the forward
@@ -1902,62 +1816,11 @@ int rmx_xcorr_batch_bands(rmx_ctx* c, const void* iq, int n_windows, const int32
                           const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
                           const int32_t* lag_bounds, int bounds_per_window,
                           int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    if (!c) return RMX_E_INVAL;
-    if (!iq || !lag_int || !lag_frac || !peak || !band_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
-    if (n_bands < 1 || n_bands > 64) return fail(c, RMX_E_INVAL, "n_bands %d not in 1..64", n_bands);
-    // the weighted entry's checks, per (window, band): [full band | band set] as signed bins
-    if (weighting != RMX_WEIGHT_NONE && weighting != RMX_WEIGHT_PHAT)
-        return fail(c, RMX_E_INVAL, "unknown weighting %u (RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1)", weighting);
-    int rc = check_n_windows(c, n_windows);
-    if (rc != RMX_OK) return rc;
-    const int N = c->n_samples;
-    const long band_rows = bands_per_window ? (long)n_windows : 1L;
-    std::vector<int32_t> bins((size_t)(2 + 2 * band_rows * n_bands));
-    bins[0] = -N;
-    bins[1] = N - 1;
-    for (long r = 0; r < band_rows * n_bands; ++r) {
-        const double lo = band_cps[2 * r], hi = band_cps[2 * r + 1];
-        const char* shared = bands_per_window ? "" : " (one band set shared by every window)";
-        const host::BandCheck bc = host::band_to_bins(lo, hi, N, &bins[2 + 2 * r], &bins[3 + 2 * r]);
-        if (bc == host::kBandNoInterval)
-            return fail(c, RMX_E_INVAL, "band %ld of window %ld%s: [%g, %g] is not an interval inside [-0.5, 0.5] cycles per sample",
-                        r % n_bands, r / n_bands, shared, lo, hi);
-        if (bc == host::kBandNoBin)
-            return fail(c, RMX_E_INVAL, "band %ld of window %ld%s: [%g, %g] keeps no bin of the %ld-point transform", r % n_bands,
-                        r / n_bands, shared, lo, hi, 2L * N);
-    }
-    if (n_bands == 1)   // the weighted call itself (its own checks repeat the ones above and pass)
-        return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, band_cps, bands_per_window, weighting, lag_bounds,
-                             bounds_per_window, 0, lag_int, lag_frac, peak, nullptr, flags);
-    if (n_windows == 0) return RMX_OK;   // (as the weighted entry: it does not look at the pairs of an empty batch)
-    rc = check_batch(c, n_windows, pairs, &n_pairs);
-    if (rc != RMX_OK) return rc;
-    if (n_pairs == 0) return RMX_OK;
-    bool bounded = false;
-    long bound_rows = 0;
-    if (lag_bounds) {
-        rc = check_bounded(c, n_windows, n_pairs, 1, lag_bounds, bounds_per_window, &bound_rows, &bounded);
-        if (rc != RMX_OK) return rc;
-    }
-    RMX_HIP(c, hipSetDevice(c->device));
-    // the bounds are per (window, pair) and shared by the window's bands: per-window bounds go to the device once per
-    // VIRTUAL window (window-major), so the bounded kernels index them with the virtual window as they index their outputs
-    std::vector<int32_t> vb;
-    if (bounded && bounds_per_window) {
-        const size_t row = 2 * (size_t)n_pairs;
-        vb.resize((size_t)n_windows * n_bands * row);
-        for (long v = 0; v < (long)n_windows * n_bands; ++v) std::memcpy(&vb[(size_t)v * row], lag_bounds + (size_t)(v / n_bands) * row, row * sizeof(int32_t));
-        lag_bounds = vb.data();
-        bound_rows *= n_bands;
-    }
-    XcorrCall call;
-    rc = stage_request(c, &call, true, bins, false, weighting, bounded, lag_bounds, bound_rows, bounds_per_window, n_pairs);
-    if (rc != RMX_OK) return rc;
-    // band_stage: [full band | band set].  PHAT keeps call.wt on the full band (every bin whitened, none dropped); without
-    // it the forward kernels are the plain ones
-    call.bs = BandSet{c->band_stage.d + 2, bands_per_window ? 2L * n_bands : 0L, 0L, n_bands};
-    if (weighting != RMX_WEIGHT_PHAT) call.wt = XWeight{nullptr, 0, 0, 0, 0, 0.0f};
-    return xcorr_dispatch(c, call, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+    host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, bands_per_window,
+                                        weighting, lag_bounds, bounds_per_window);
+    a.banded = true;
+    a.n_bands = n_bands;
+    return xcorr_request(c, a, flags);
 }
 
 // rmx_xcorr_batch_weighted with one peak search per group of `integrate` consecutive windows, on the lag-by-lag sum of the
@@ -1967,8 +1830,11 @@ int rmx_xcorr_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const 
                                const double* band_cps, int band_per_window, unsigned weighting,
                                const int32_t* lag_bounds, int bounds_per_group,
                                int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, true, integrate, band_cps, band_per_window, weighting, lag_bounds,
-                         bounds_per_group, 0, lag_int, lag_frac, peak, nullptr, flags);
+    host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, band_per_window,
+                                        weighting, lag_bounds, bounds_per_group);
+    a.grouped = true;
+    a.integrate = integrate;
+    return xcorr_request(c, a, flags);
 }
 
 // rmx_xcorr_batch_integrated with the fine lag search of refine.hpp behind the coarse one: refine = U in {2, 4, 8, 16}
@@ -1977,8 +1843,12 @@ int rmx_xcorr_batch_refined(rmx_ctx* c, const void* iq, int n_windows, const int
                             const double* band_cps, int band_per_window, unsigned weighting,
                             const int32_t* lag_bounds, int bounds_per_group, int refine,
                             int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, true, integrate, band_cps, band_per_window, weighting, lag_bounds,
-                         bounds_per_group, refine, lag_int, lag_frac, peak, nullptr, flags);
+    host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, band_per_window,
+                                        weighting, lag_bounds, bounds_per_group);
+    a.grouped = true;
+    a.integrate = integrate;
+    a.refine = refine;
+    return xcorr_request(c, a, flags);
 }
 
 // rmx_xcorr_batch_refined with four quality figures per output slot (quality.hpp) as a fourth output, computed from the
@@ -1987,8 +1857,13 @@ int rmx_xcorr_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int
                             const double* band_cps, int band_per_window, unsigned weighting,
                             const int32_t* lag_bounds, int bounds_per_group, int refine,
                             int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
-    return xcorr_request(c, iq, n_windows, pairs, n_pairs, true, integrate, band_cps, band_per_window, weighting, lag_bounds,
-                         bounds_per_group, refine, lag_int, lag_frac, peak, quality, flags);
+    host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, band_per_window,
+                                        weighting, lag_bounds, bounds_per_group);
+    a.grouped = true;
+    a.integrate = integrate;
+    a.refine = refine;
+    a.quality = quality;
+    return xcorr_request(c, a, flags);
 }
 
 // rmx_xcorr_batch_bands with the fine lag search and the quality figures of rmx_xcorr_batch_quality per (window, band,
@@ -1999,76 +1874,13 @@ int rmx_xcorr_batch_bands_quality(rmx_ctx* c, const void* iq, int n_windows, con
                                   const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
                                   const int32_t* lag_bounds, int bounds_per_window, int refine,
                                   int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
-    if (refine == 0 && !quality)
-        return rmx_xcorr_batch_bands(c, iq, n_windows, pairs, n_pairs, band_cps, n_bands, bands_per_window, weighting, lag_bounds,
-                                     bounds_per_window, lag_int, lag_frac, peak, flags);
-    // rmx_xcorr_batch_bands' own checks, in its order
-    if (!c) return RMX_E_INVAL;
-    if (!iq || !lag_int || !lag_frac || !peak || !band_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
-    if (n_bands < 1 || n_bands > 64) return fail(c, RMX_E_INVAL, "n_bands %d not in 1..64", n_bands);
-    if (weighting != RMX_WEIGHT_NONE && weighting != RMX_WEIGHT_PHAT)
-        return fail(c, RMX_E_INVAL, "unknown weighting %u (RMX_WEIGHT_NONE = 0, RMX_WEIGHT_PHAT = 1)", weighting);
-    int rc = check_n_windows(c, n_windows);
-    if (rc != RMX_OK) return rc;
-    const int N = c->n_samples;
-    const long band_rows = bands_per_window ? (long)n_windows : 1L;
-    std::vector<int32_t> bins((size_t)(2 + 2 * band_rows * n_bands));
-    bins[0] = -N;
-    bins[1] = N - 1;
-    for (long r = 0; r < band_rows * n_bands; ++r) {
-        const double lo = band_cps[2 * r], hi = band_cps[2 * r + 1];
-        const char* shared = bands_per_window ? "" : " (one band set shared by every window)";
-        const host::BandCheck bc = host::band_to_bins(lo, hi, N, &bins[2 + 2 * r], &bins[3 + 2 * r]);
-        if (bc == host::kBandNoInterval)
-            return fail(c, RMX_E_INVAL, "band %ld of window %ld%s: [%g, %g] is not an interval inside [-0.5, 0.5] cycles per sample",
-                        r % n_bands, r / n_bands, shared, lo, hi);
-        if (bc == host::kBandNoBin)
-            return fail(c, RMX_E_INVAL, "band %ld of window %ld%s: [%g, %g] keeps no bin of the %ld-point transform", r % n_bands,
-                        r / n_bands, shared, lo, hi, 2L * N);
-    }
-    if (n_bands == 1)   // the quality call itself, ungrouped as the banded entry's n_bands == 1 (its checks repeat the ones above)
-        return xcorr_request(c, iq, n_windows, pairs, n_pairs, false, 1, band_cps, bands_per_window, weighting, lag_bounds,
-                             bounds_per_window, refine, lag_int, lag_frac, peak, quality, flags);
-    if (n_windows == 0) return RMX_OK;
-    rc = check_batch(c, n_windows, pairs, &n_pairs);
-    if (rc != RMX_OK) return rc;
-    if (n_pairs == 0) return RMX_OK;
-    bool bounded = false;
-    long bound_rows = 0;
-    if (lag_bounds) {
-        rc = check_bounded(c, n_windows, n_pairs, 1, lag_bounds, bounds_per_window, &bound_rows, &bounded);
-        if (rc != RMX_OK) return rc;
-    }
-    // the refined entry's check, then the quality entry's, over the [n_windows][n_bands][n_pairs] rows of this call
-    if (refine != 0 && refine != 2 && refine != 4 && refine != 8 && refine != 16)
-        return fail(c, RMX_E_INVAL, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", refine);
-    if (quality) {
-        const size_t rows = (size_t)n_windows * n_bands * n_pairs;
-        const char *q0 = reinterpret_cast<const char*>(quality), *q1 = q0 + 4 * rows * sizeof(float);
-        const struct { const char* name; const void* p; } outs[3] = {{"lag_int", lag_int}, {"lag_frac", lag_frac}, {"peak", peak}};
-        for (const auto& o : outs) {
-            const char* p0 = static_cast<const char*>(o.p);
-            if (p0 < q1 && q0 < p0 + rows * sizeof(float))
-                return fail(c, RMX_E_INVAL, "quality overlaps %s: the %zu x 4 floats of quality need a buffer of their own", o.name, rows);
-        }
-    }
-    RMX_HIP(c, hipSetDevice(c->device));
-    std::vector<int32_t> vb;   // per-window bounds once per virtual window, as rmx_xcorr_batch_bands stages them
-    if (bounded && bounds_per_window) {
-        const size_t row = 2 * (size_t)n_pairs;
-        vb.resize((size_t)n_windows * n_bands * row);
-        for (long v = 0; v < (long)n_windows * n_bands; ++v) std::memcpy(&vb[(size_t)v * row], lag_bounds + (size_t)(v / n_bands) * row, row * sizeof(int32_t));
-        lag_bounds = vb.data();
-        bound_rows *= n_bands;
-    }
-    XcorrCall call;
-    call.refine = refine;
-    call.quality = quality;
-    rc = stage_request(c, &call, true, bins, false, weighting, bounded, lag_bounds, bound_rows, bounds_per_window, n_pairs);
-    if (rc != RMX_OK) return rc;
-    call.bs = BandSet{c->band_stage.d + 2, bands_per_window ? 2L * n_bands : 0L, 0L, n_bands};
-    if (weighting != RMX_WEIGHT_PHAT) call.wt = XWeight{nullptr, 0, 0, 0, 0, 0.0f};
-    return xcorr_dispatch(c, call, iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak, flags);
+    host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, bands_per_window,
+                                        weighting, lag_bounds, bounds_per_window);
+    a.banded = true;
+    a.n_bands = n_bands;
+    a.refine = refine;
+    a.quality = quality;
+    return xcorr_request(c, a, flags);
 }
 
 // The Doppler search is rmx_caf_batch_request with nothing requested: the same kernels, the same launches
@@ -2090,8 +1902,9 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
     if (!c) return RMX_E_INVAL;
     if (!iq || !dop_idx || !lag_int || !lag_frac || !peak || !doppler_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
     if (n_dopplers < 1 || n_dopplers > 4096) return fail(c, RMX_E_INVAL, "n_dopplers %d not in 1..4096", n_dopplers);
-    int rc = check_batch(c, n_windows, pairs, &n_pairs);
-    if (rc != RMX_OK) return rc;
+    std::string why;
+    int rc = host::check_batch(c->n_buoys, c->max_windows, n_windows, pairs, &n_pairs, &why);
+    if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
     if (n_windows == 0 || n_pairs == 0) return RMX_OK;
     const int B = c->n_buoys, N = c->n_samples;
     XcorrCall call;   // the plain request unless the checks below say otherwise; never integrated, refined or qualified
@@ -2110,29 +1923,15 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
     if (rc != RMX_OK) return rc;
     const size_t out_elems = (size_t)n_windows * n_pairs;
     {   // the request: the weighted entry's checks, the bounded entry's, then dop_frac; nothing is staged before the last
-        std::vector<int32_t> bins;
-        bool weighted = false, bounded = false;
-        long bound_rows = 0;
-        if (band_cps || weighting != RMX_WEIGHT_NONE) {
-            rc = check_weighted(c, n_windows, band_cps, band_per_window, weighting, &bins, &weighted);
-            if (rc != RMX_OK) return rc;
-        }
-        if (lag_bounds) {
-            rc = check_bounded(c, n_windows, n_pairs, 1, lag_bounds, bounds_per_window, &bound_rows, &bounded);
-            if (rc != RMX_OK) return rc;
-        }
-        if (dop_frac) {
-            const char *f0 = reinterpret_cast<const char*>(dop_frac), *f1 = f0 + out_elems * sizeof(float);
-            const struct { const char* name; const void* p; } outs[4] = {{"dop_idx", dop_idx}, {"lag_int", lag_int}, {"lag_frac", lag_frac},
-                                                                        {"peak", peak}};
-            for (const auto& o : outs) {
-                const char* p0 = static_cast<const char*>(o.p);
-                if (p0 < f1 && f0 < p0 + out_elems * sizeof(float))
-                    return fail(c, RMX_E_INVAL, "dop_frac overlaps %s: its %zu floats need a buffer of their own", o.name, out_elems);
-            }
-        }
-        rc = stage_request(c, &call, weighted, bins, band_cps && band_per_window, weighting, bounded, lag_bounds, bound_rows,
-                           bounds_per_window, n_pairs);
+        host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, band_per_window,
+                                            weighting, lag_bounds, bounds_per_window);
+        a.n_buoys = B;
+        a.n_samples = N;
+        a.max_windows = c->max_windows;
+        host::Request rq;
+        rc = host::check_caf_request(a, dop_idx, dop_frac, &rq, &why);
+        if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
+        rc = describe_call(c, rq, &call);
         if (rc != RMX_OK) return rc;
     }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;

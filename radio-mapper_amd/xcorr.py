@@ -135,6 +135,31 @@ def check_lag_bounds(lag_bounds, n_windows: int, n_pairs: int):
     return np.ascontiguousarray(a, dtype=np.int32), per_window
 
 
+def _check_band_rows(name: str, value, n_windows: int, sets: bool):
+    """what check_band (sets False: rows [2] or [W][2]) and check_bands (sets True: [M][2] or [W][M][2]) share"""
+    a = np.asarray(value)
+    if a.dtype.kind not in "iuf":
+        raise ValueError(f"{name} must be a real array, got dtype {a.dtype}")
+    shared = 2 if sets else 1   # dimensions of the array that every window shares
+    if a.ndim == shared and a.shape[-1] == 2:
+        per_window = False
+    elif a.ndim == shared + 1 and a.shape[0] == n_windows and a.shape[-1] == 2:
+        per_window = True
+    elif sets:
+        raise ValueError(f"bands must be [M][2] or [W][M][2] = [{n_windows}][M][2], got shape {a.shape}")
+    else:
+        raise ValueError(f"band must be [2] or [W][2] = [{n_windows}][2], got shape {a.shape}")
+    if sets and not 1 <= a.shape[-2] <= MAX_BANDS:
+        raise ValueError(f"bands must hold 1..{MAX_BANDS} bands per window, got {a.shape[-2]}")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name} values must be finite")
+    lo, hi = a[..., 0], a[..., 1]
+    if np.any(lo < -0.5) or np.any(hi > 0.5) or np.any(lo > hi):
+        raise ValueError(f"{name} must satisfy -0.5 <= lo <= hi <= 0.5 (cycles per sample; no wrap across +-fs/2)")
+    return a, per_window
+
+
 def check_band(band, n_windows: int):
     """band as correlate() takes it -> (contiguous float64 array or None, per_window).  Shape [2] (one [lo, hi] shared by
     every window) or [W][2], in cycles per sample; finite, -0.5 <= lo <= hi <= 0.5.  Raises ValueError before any call
@@ -142,22 +167,7 @@ def check_band(band, n_windows: int):
     (RmxError, RMX_E_INVAL)."""
     if band is None:
         return None, False
-    a = np.asarray(band)
-    if a.dtype.kind not in "iuf":
-        raise ValueError(f"band must be a real array, got dtype {a.dtype}")
-    if a.shape == (2,):
-        per_window = False
-    elif a.ndim == 2 and a.shape == (n_windows, 2):
-        per_window = True
-    else:
-        raise ValueError(f"band must be [2] or [W][2] = [{n_windows}][2], got shape {a.shape}")
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if not np.all(np.isfinite(a)):
-        raise ValueError("band values must be finite")
-    lo, hi = a[..., 0], a[..., 1]
-    if np.any(lo < -0.5) or np.any(hi > 0.5) or np.any(lo > hi):
-        raise ValueError("band must satisfy -0.5 <= lo <= hi <= 0.5 (cycles per sample; no wrap across +-fs/2)")
-    return a, per_window
+    return _check_band_rows("band", band, n_windows, False)
 
 
 MAX_BANDS = 64
@@ -170,24 +180,7 @@ def check_bands(bands, n_windows: int):
     library checks that (RmxError, RMX_E_INVAL)."""
     if bands is None:
         raise ValueError("bands must be an array [M][2] or [W][M][2], got None")
-    a = np.asarray(bands)
-    if a.dtype.kind not in "iuf":
-        raise ValueError(f"bands must be a real array, got dtype {a.dtype}")
-    if a.ndim == 2 and a.shape[1] == 2:
-        per_window = False
-    elif a.ndim == 3 and a.shape[0] == n_windows and a.shape[2] == 2:
-        per_window = True
-    else:
-        raise ValueError(f"bands must be [M][2] or [W][M][2] = [{n_windows}][M][2], got shape {a.shape}")
-    if not 1 <= a.shape[-2] <= MAX_BANDS:
-        raise ValueError(f"bands must hold 1..{MAX_BANDS} bands per window, got {a.shape[-2]}")
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if not np.all(np.isfinite(a)):
-        raise ValueError("bands values must be finite")
-    lo, hi = a[..., 0], a[..., 1]
-    if np.any(lo < -0.5) or np.any(hi > 0.5) or np.any(lo > hi):
-        raise ValueError("bands must satisfy -0.5 <= lo <= hi <= 0.5 (cycles per sample; no wrap across +-fs/2)")
-    return a, per_window
+    return _check_band_rows("bands", bands, n_windows, True)
 
 
 def check_integrate(integrate, n_windows: int) -> int:
@@ -487,13 +480,7 @@ class XcorrEngine:
         W = iq.shape[0]
         K = check_integrate(integrate, W)
         U = check_refine(refine)
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-            P = pairs.shape[0]
-            pp = pairs.ctypes.data_as(C.c_void_p)
-        else:
-            P = self.n_buoys * (self.n_buoys - 1) // 2
-            pp = None
+        pairs, pp, P = self._pairs_arg(pairs)
         lb, per_window = check_lag_bounds(lag_bounds, W // K, P)
         bd, band_pw = check_band(band, W)
         lag_int = np.zeros((W // K, P), np.int32)
@@ -506,6 +493,20 @@ class XcorrEngine:
         self._xcorr(vp(iq), W, pp, P, K, bd, band_pw, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags, U,
                     vp(qual) if quality else None)
         return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
+
+    def _xcorr_bands(self, iq_p, W: int, pp, P: int, bd, bands_pw: bool, whiten: bool, lb, per_window: bool,
+                     lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0, quality_p=None):
+        """One banded correlation call through the C entry its arguments name: rmx_xcorr_batch_bands_quality for U > 0 or
+        a quality pointer, else rmx_xcorr_batch_bands.  iq and the outputs are pointers (host or device, as `flags` says);
+        bd is the checked host array [M][2] or [W][M][2], lb a checked host array or None."""
+        head = (self._ctx, iq_p, W, pp, P, bd.ctypes.data_as(C.c_void_p), bd.shape[-2], int(bands_pw),
+                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
+                int(per_window))
+        if U or quality_p is not None:
+            rc = self._lib.rmx_xcorr_batch_bands_quality(*head, U, lag_int_p, lag_frac_p, peak_p, quality_p, flags)
+        else:
+            rc = self._lib.rmx_xcorr_batch_bands(*head, lag_int_p, lag_frac_p, peak_p, flags)
+        self._check(rc)
 
     def correlate_bands(self, iq: np.ndarray, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
                         whiten: bool = False, refine: int = 0, quality: bool = False):
@@ -530,13 +531,8 @@ class XcorrEngine:
         qual = np.zeros((W, M, P, 4), np.float32) if quality else None
         if W and P:
             vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
-            head = (self._ctx, vp(iq), W, pp, P, vp(bd), M, int(per_window_b), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE,
-                    None if lb is None else vp(lb), int(per_window))
-            if U or quality:
-                self._check(self._lib.rmx_xcorr_batch_bands_quality(*head, U, vp(lag_int), vp(lag_frac), vp(peak),
-                                                                    vp(qual) if quality else None, flags))
-            else:
-                self._check(self._lib.rmx_xcorr_batch_bands(*head, vp(lag_int), vp(lag_frac), vp(peak), flags))
+            self._xcorr_bands(vp(iq), W, pp, P, bd, per_window_b, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags,
+                              U, vp(qual) if quality else None)
         return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
 
     def correlate_bands_device(self, iq_ptr: int, n_windows: int, bands, lag_int_ptr: int, lag_frac_ptr: int, peak_ptr: int,
@@ -550,15 +546,9 @@ class XcorrEngine:
         bd, per_window_b = check_bands(bands, n_windows)
         lb, per_window = check_lag_bounds(lag_bounds, n_windows, P)
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
-        head = (self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P, bd.ctypes.data_as(C.c_void_p), bd.shape[-2], int(per_window_b),
-                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
-                int(per_window))
-        out = (C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr))
-        if U or quality_ptr is not None:
-            self._check(self._lib.rmx_xcorr_batch_bands_quality(
-                *head, U, *out, None if quality_ptr is None else C.c_void_p(quality_ptr), flags))
-        else:
-            self._check(self._lib.rmx_xcorr_batch_bands(*head, *out, flags))
+        self._xcorr_bands(C.c_void_p(iq_ptr), n_windows, pp, P, bd, per_window_b, whiten, lb, per_window, C.c_void_p(lag_int_ptr),
+                          C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags, U,
+                          None if quality_ptr is None else C.c_void_p(quality_ptr))
 
     def _pairs_arg(self, pairs):
         """pairs as the entries take it -> (kept int32 array or None, its pointer or None, P)"""
@@ -725,13 +715,7 @@ class XcorrEngine:
         [n_windows // K][P][4] float32 for the quality figures (rmx_xcorr_batch_quality)."""
         K = check_integrate(integrate, n_windows)
         U = check_refine(refine)
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-            P = pairs.shape[0]
-            pp = pairs.ctypes.data_as(C.c_void_p)
-        else:
-            P = self.n_buoys * (self.n_buoys - 1) // 2
-            pp = None
+        pairs, pp, P = self._pairs_arg(pairs)
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
         lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
         bd, band_pw = check_band(band, n_windows)
