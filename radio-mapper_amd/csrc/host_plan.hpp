@@ -198,7 +198,7 @@ inline int make_pair_plan(int n_buoys, const int32_t* pairs, int n_pairs, int pa
 }
 
 // ---- k_win, phase 2: the order of a window's pairs among buoys 1 .. B-1 ---------------------------------------------
-// Phase 1 of the fused kernel (anchor 0) leaves X_{B-1} in register array 1 (sb) and every X_1 .. X_{B-1} in the scratch.
+// Phase 1 of the fused kernel (anchor 0) leaves X_{B-1} in register array 1 (sb) and X_1 .. X_{B-2} in the scratch.
 // The remaining pairs are walked so that every pair shares one buoy with the pair before it: the shared spectrum stays
 // in its register array, and each step requests ONE spectrum, into the array whose buoy the next step drops.
 struct TrailStep {
@@ -222,7 +222,7 @@ struct PairTrail {
 
 inline int trail_out_idx(int B, int i, int j) { return i * B - (i * (i + 1)) / 2 + (j - i - 1); }
 
-// One window's spectrum traffic through an LRU of `cap` spectra: the stores of X_1 .. X_{B-1} (write-allocate), then
+// One window's spectrum traffic through an LRU of `cap` spectra: the stores of X_1 .. X_{B-2} (write-allocate), then
 // first_load and every step's requests in order.  Returns the requests that hit.  (A model for the notes: two spectra are a
 // workgroup's share of its XCD's L2; LABNOTES R10.1 sets it against the measured counters.)
 inline int trail_sim_hits(const PairTrail& t, int cap) {
@@ -236,7 +236,7 @@ inline int trail_sim_hits(const PairTrail& t, int cap) {
         return hit;
     };
     int hits = 0;
-    for (int b = 1; b < t.n_buoys; ++b) touch(b);
+    for (int b = 1; b + 1 < t.n_buoys; ++b) touch(b);
     if (t.first_load >= 0) hits += touch(t.first_load);
     for (const TrailStep& s : t.steps) {
         if (s.load_idx >= 0) hits += touch(s.load_idx);
@@ -318,22 +318,27 @@ inline PairTrail plan_pair_trail(int B) {
 
 // what k_win's phase 2 can walk: X_i in array 0 at every step and never a reload of both arrays (it has one copy of h1
 // per request target, none per role).  rmx_create refuses a table that is anything else.
+// And no request for X_{B-1}: it stays in array 1 behind phase 1 and is the one spectrum phase 1 does not store, so its
+// slot of the scratch holds nothing of this window.
 inline bool trail_kernel_ok(const PairTrail& t) {
+    const int last = t.n_buoys - 1;
+    if (!t.steps.empty() && t.first_load == last) return false;
     for (const TrailStep& s : t.steps)
-        if (s.xi_arr != 0 || s.reload != 0) return false;
+        if (s.xi_arr != 0 || s.reload != 0 || s.load_idx == last) return false;
     return true;
 }
 
 // The kernel's copy: (pairs + 1) entries of four ints {out_idx, load_arr, load_idx, 0} (16 bytes: one scalar load).  Entry
 // 0 is the last pair of phase 1, (0, B-1), whose request is first_load into array 0; entry k + 1 is step k.  Where a step
-// requests nothing, the entry names a spectrum that exists (the kernel requests unconditionally into dead registers).
+// requests nothing, the entry names a spectrum that phase 1 stored (the kernel requests unconditionally into dead
+// registers): buoy 1, never B-1, whose slot nobody writes.  (B = 2 stores nothing and requests nothing: entry 0 names 0.)
 // Empty for a table the kernel cannot walk (trail_kernel_ok).
 inline std::vector<int32_t> encode_pair_trail(const PairTrail& t) {
     std::vector<int32_t> e;
     if (!trail_kernel_ok(t)) return e;
     const int B = t.n_buoys;
     e.reserve(4 * (t.steps.size() + 1));
-    const int some = B > 1 ? B - 1 : 0;
+    const int some = B > 2 ? 1 : 0;
     e.insert(e.end(), {trail_out_idx(B, 0, B - 1), 0, t.first_load >= 0 ? t.first_load : some, 0});
     for (const TrailStep& s : t.steps)
         e.insert(e.end(), {s.out_idx, s.load_arr, s.load_idx >= 0 ? s.load_idx : some, 0});

@@ -143,7 +143,9 @@ __device__ __forceinline__ void resolve_batch(int lane, const float4* red, const
 
 // Schedule of one window (all pairs i<j of B buoys; two register arrays of one spectrum each, sa and sb):
 //   anchor 0      X_0 is transformed straight into sa (never stored); every further X_e is transformed once into sb,
-//                 stored once, and used at once, from registers, for (0,e).  X_{B-1} stays in sb behind this phase;
+//                 stored once, and used at once, from registers, for (0,e).  X_{B-1} stays in sb behind this phase and is
+//                 not stored either: the table never requests it (host::trail_kernel_ok) and the scratch is private to
+//                 the workgroup, so its slot of the scratch stays unwritten;
 //   handover runs the pairs among buoys 1 .. B-1 in the order of a host-planned table (host::plan_pair_trail, `trail`).
 //                 A run keeps its anchor in one array and streams its partners through the other, one pair ahead; the
 //                 partner streamed last stays where it is as the next run's anchor, and the stream moves to the array the
@@ -152,8 +154,8 @@ __device__ __forceinline__ void resolve_batch(int lane, const float4* red, const
 //                 ever loaded and no step loads both arrays, whatever the parity or size of B.  X_i is in sa and X_j in
 //                 sb at every step, as the anchor runs had them, so every pair's arithmetic is what it was; the request
 //                 goes to sa or to sb (two copies of h1).
-// Requests per window at B = 8: 8 inputs (256 KiB) + 7 spectrum stores (448 KiB) + 21 spectrum loads of 64 KiB (one from
-// the last pair of anchor 0, 20 from the table's steps) instead of 27 (6 anchors, 21 streamed, X_7 among them again).
+// Requests per window at B = 8: 8 inputs (256 KiB) + 6 spectrum stores (384 KiB: X_1 .. X_6) + 21 spectrum loads of 64 KiB
+// (one from the last pair of anchor 0, 20 from the table's steps; a 22nd, behind the last step, goes into dead registers).
 template <bool U8>
 __global__ __launch_bounds__(kThreads, 2) void k_win(const void* __restrict__ iq_v, float4* __restrict__ spec,
                                                      const float4* __restrict__ tw1_g,

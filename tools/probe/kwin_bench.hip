@@ -21,6 +21,9 @@
 #include "kwin2.hpp"
 #define KWB_HAVE_KWIN2 1
 #endif
+#if !defined(KWB_NO_P1)
+#include "kwin_p1.hpp"
+#endif
 
 using namespace rmx;
 
@@ -84,6 +87,35 @@ KWB_V2(launch_a15, 1, 15)
     {"k_win2 ABL 15: all", launch_a15, (const void*)k_win2<false, 1, 15>, kLdsWin2Bytes},
 #endif
 
+#if !defined(KWB_NO_P1)
+// the request side of phase 1 (kwin_p1.hpp, LABNOTES R12): P1 bits 1 no store of X_{B-1}, 2 stores spread over the groups of
+// h1, 4 priority for waves 4-7, 8 every store under a run-time mask that is false (timing only), 16 stores spread over four groups
+#define KWB_P1(NAME, BITS)                                                                                                  \
+    static void NAME(const Bufs& b, hipStream_t s) {                                                                         \
+        hipLaunchKernelGGL((k_win_p1<false, BITS>), dim3(256), dim3(kThreads), kLdsWinBytes, s, (const void*)b.iq, b.spec,   \
+                           b.tw1, b.tw2, b.B, 0L, b.out_scale, b.li, b.lf, b.pk, b.W, (const int4*)b.trail, 0, 0);           \
+    }
+KWB_P1(launch_p1_0, 0)
+KWB_P1(launch_p1_8, 8)
+KWB_P1(launch_p1_1, 1)
+KWB_P1(launch_p1_2, 2)
+KWB_P1(launch_p1_16, 16)
+KWB_P1(launch_p1_4, 4)
+KWB_P1(launch_p1_3, 3)
+KWB_P1(launch_p1_5, 5)
+KWB_P1(launch_p1_7, 7)
+#define KWB_P1_TABLE \
+    {"p1 0: the body before R12, stag 0", launch_p1_0, (const void*)k_win_p1<false, 0>, kLdsWinBytes}, \
+    {"p1 8: stores masked at run time (TIMING ONLY)", launch_p1_8, (const void*)k_win_p1<false, 8>, kLdsWinBytes}, \
+    {"p1 1: no store of X_{B-1}", launch_p1_1, (const void*)k_win_p1<false, 1>, kLdsWinBytes}, \
+    {"p1 2: stores spread over eight groups", launch_p1_2, (const void*)k_win_p1<false, 2>, kLdsWinBytes}, \
+    {"p1 16: stores spread over four groups", launch_p1_16, (const void*)k_win_p1<false, 16>, kLdsWinBytes}, \
+    {"p1 4: priority in phase 1", launch_p1_4, (const void*)k_win_p1<false, 4>, kLdsWinBytes}, \
+    {"p1 3: 1 + 2", launch_p1_3, (const void*)k_win_p1<false, 3>, kLdsWinBytes}, \
+    {"p1 5: 1 + 4", launch_p1_5, (const void*)k_win_p1<false, 5>, kLdsWinBytes}, \
+    {"p1 7: 1 + 2 + 4", launch_p1_7, (const void*)k_win_p1<false, 7>, kLdsWinBytes},
+#endif
+
 struct Variant { const char* name; launch_fn fn; const void* kfn; int lds; };
 
 int main(int argc, char** argv) {
@@ -123,8 +155,12 @@ int main(int argc, char** argv) {
 #ifdef KWB_HAVE_KWIN2
         KWB_KWIN2_TABLE
 #endif
+#ifdef KWB_P1_TABLE
+        KWB_P1_TABLE
+#endif
     };
-    if (argc > 6) vars = {vars.at((size_t)atoi(argv[6]))};   // argv[6]: that variant alone (counter passes: one kernel name, one order)
+    const int rounds = argc > 7 ? atoi(argv[7]) : 2;   // argv[7]: interleaved runs of every variant
+    if (argc > 6 && argv[6][0] != '-') vars = {vars.at((size_t)atoi(argv[6]))};   // argv[6]: that variant alone (counter passes: one kernel name, one order); "-": all
     for (auto& v : vars) CK(hipFuncSetAttribute(v.kfn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds));
 
     hipEvent_t e0, e1;
@@ -132,7 +168,7 @@ int main(int argc, char** argv) {
     std::vector<int> li0, li((size_t)W * P);
     std::vector<float> lf0, pk0, lf((size_t)W * P), pk((size_t)W * P);
     const double alg_bytes = (double)W * P * (16.0 * N + 12.0);
-    for (int round = 0; round < 2; ++round)
+    for (int round = 0; round < rounds; ++round)
         for (size_t vi = 0; vi < vars.size(); ++vi) {
             auto& v = vars[vi];
             CK(hipMemset(b.li, 0xff, (size_t)W * P * 4)); CK(hipMemset(b.lf, 0xff, (size_t)W * P * 4)); CK(hipMemset(b.pk, 0xff, (size_t)W * P * 4));

@@ -1,7 +1,28 @@
-// kwin_body.hpp -- the body of the fused N = 4096 kernel, included by kwin.hpp into k_win (BOUNDED = false: the unbounded
-// kernel, the same source as before) and into k_win_lb (BOUNDED = true: the caller's lag window per pair, lag_bounds.hpp).
-// Not a header of its own: it expects the kernel's parameters, BOUNDED and lb in scope.
-// A textual include, not a <U8, BOUNDED> device function: that form compiled all four kernels to other instruction bodies.
+// kwin_p1.hpp -- PROBE copy of k_win's body (radio-mapper_amd/csrc/kwin_body.hpp as it stood before LABNOTES R12) for the
+// A/B of the request side of phase 1 in tools/probe/kwin_bench.hip.  Never part of the library.  P1 = 0 compiles to the
+// instruction count of that body, P1 = 1 is what R12 shipped.  P1 is a set of bits:
+//   1   the store of X_{B-1} is dropped (it stays in sb behind phase 1 and the table never requests it)
+//   2   the eight 16-byte stores of X_e are issued from inside the h1 of (0,e), one per butterfly group, each in front of
+//       the sample request into the same registers
+//   4   waves 4-7 run the first piece of every phase-1 interval at s_setprio 1, the second at 0
+//   8   TIMING ONLY (results wrong, registers keep healthy data): every spectrum store hangs on the run-time test
+//       t < store_lanes, which the harness makes false for every lane -- the run-time mask of LABNOTES 6.2
+//   16  like 2, but two stores per group from the four groups of the role-C pass only
+#pragma once
+#include "../../radio-mapper_amd/csrc/kwin.hpp"
+
+namespace rmx {
+
+template <bool U8, int P1>
+__global__ __launch_bounds__(kThreads, 2) void k_win_p1(const void* __restrict__ iq_v, float4* __restrict__ spec,
+                                                        const float4* __restrict__ tw1_g,
+                                                        const float2* __restrict__ tw2_g, int n_buoys,
+                                                        long first_window, float out_scale,
+                                                        int* __restrict__ lag_int, float* __restrict__ lag_frac,
+                                                        float* __restrict__ peak, int n_win, const int4* __restrict__ trail, int stag,
+                                                        int store_lanes) {
+    constexpr bool BOUNDED = false;
+    constexpr LagBounds lb{nullptr, 0, 0, 0};
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* img0 = reinterpret_cast<float2*>(smem);
     float2* img1 = reinterpret_cast<float2*>(smem + kLdsWinImg);
@@ -48,8 +69,8 @@
     for (int wl = blockIdx.x; wl < n_win; wl += gridDim.x) {
     C16 sa, sb;   // anchor spectrum X_i and the streamed X_j (scalar arrays: see C16)
     // spectrum scratch is per WORKGROUP, not per window: the persistent workgroup reuses the same
-    // B x 64 KiB for every window it processes (B = 8: slots 1 .. 6 are written, 256 x 384 KiB = 98 MB live for the
-    // whole launch, resident in the 256 MB Infinity Cache, rewritten before most of it is ever evicted to HBM)
+    // B x 64 KiB for every window it processes (256 x 448 KiB = 115 MB live for the whole launch,
+    // resident in the 256 MB Infinity Cache, rewritten before most of it is ever evicted to HBM)
     const long wbase = (long)blockIdx.x * B;
     const long obase = (first_window + wl) * (long)n_pairs;
     int seq = 0;         // transform counter: selects the exchange image
@@ -163,9 +184,13 @@
             d.set(2 * j + 1, __uint_as_float(w.z), __uint_as_float(w.w));
         }
     };
-    auto store_spec = [&](const C16& d, int b) __attribute__((always_inline)) {
+    auto store_spec_range = [&](const C16& d, int b, auto j0c, auto j1c) __attribute__((always_inline)) {
+        constexpr int J0 = decltype(j0c)::value, J1 = decltype(j1c)::value;
+        if constexpr (P1 & 8) {
+            if (t >= store_lanes) return;   // run-time mask: no lane stores
+        }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = J0; j < J1; ++j) {
             // (opaque copies: hipcc otherwise widens these four scalar reads into overlapping 16-byte
             // loads of the register array, which pins half of it in scratch memory)
             float e0 = d.re[2 * j], e1 = d.im[2 * j], e2 = d.re[2 * j + 1], e3 = d.im[2 * j + 1];
@@ -184,6 +209,20 @@
             __builtin_amdgcn_raw_buffer_store_b128(w, ss, soff + (b * 8 + j) * (kThreads * 16), 0, 0);
         }
     };
+    auto store_spec = [&](const C16& d, int b) __attribute__((always_inline)) {
+        store_spec_range(d, b, std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{});
+    };
+    // the share of X_b's stores that goes in front of part G of the requests of an h1 (P1 & 2: store G; P1 & 16: stores 2G
+    // and 2G + 1 from parts 0-3).  Store j reads slots 2j, 2j + 1, which the sample requests overwrite from part j on.
+    auto store_spec_part = [&](const C16& d, int b, auto part) __attribute__((always_inline)) {
+        constexpr int G = decltype(part)::value;
+        if constexpr (P1 & 2)
+            store_spec_range(d, b, std::integral_constant<int, G>{}, std::integral_constant<int, G + 1>{});
+        else if constexpr ((P1 & 16) != 0 && G < 4)
+            store_spec_range(d, b, std::integral_constant<int, 2 * G>{}, std::integral_constant<int, 2 * G + 2>{});
+    };
+    constexpr bool kSpread = (P1 & (2 | 16)) != 0;
+    const bool prio_wave = (P1 & 4) != 0 && wave >= 4;
     // forward spectrum of the samples in x, in place (carries the 2^-6 of the TW1 table)
     auto fwd = [&](C16& xc) __attribute__((always_inline)) {
         float2* img = (seq & 1) ? img1 : img0;
@@ -195,6 +234,7 @@
         mul_tw1(x, tw1);
         xchg_a2_write(img, x, t);
         barrier_hook(false);
+        if constexpr (P1 & 4) { if (prio_wave) __builtin_amdgcn_s_setprio(1); }   // first piece of [second half of fwd, h1]
         xchg_b2_read(img, x, t);
         dft16(x);
         loc_write16(loc_m0[seq & 1], x);
@@ -203,6 +243,7 @@
         dft16_tw<true>(x, tw2r);
 #pragma unroll
         for (int q = 0; q < 16; ++q) xc.set(q, x[q].x, x[q].y);   // (scaled by 2^-6 through the TW1 table)
+        if constexpr (P1 & 4) { if (prio_wave) __builtin_amdgcn_s_setprio(0); }
         ++seq;
     };
     // One pair = two halves around its only workgroup barrier.
@@ -354,12 +395,14 @@
     auto pair = [&](const C16& a, const C16& s, int out_idx, auto prefetch) __attribute__((always_inline)) {
         pair_h1(a, s, seq, prefetch);
         barrier_hook(false);                     // the pair's only barrier
+        if constexpr (P1 & 4) { if (prio_wave) __builtin_amdgcn_s_setprio(1); }   // first piece of [h2, first half of the next fwd]
         pair_h2(seq, out_idx);
+        if constexpr (P1 & 4) { if (prio_wave) __builtin_amdgcn_s_setprio(0); }
         ++seq;
     };
     auto out_of = [&](int i, int j) -> int { return i * B - (i * (i + 1)) / 2 + (j - i - 1); };
 
-    // ---- anchor 0: X_0 goes straight into the anchor registers (never stored); every other X_e but the last is
+    // ---- anchor 0: X_0 goes straight into the anchor registers (never stored); every other X_e is
     // transformed once, stored once for the later anchors, and used at once from registers for (0,e)
     load_x(sa, 0);
     if (B > 1) load_x(sb, 1);          // sb is free: X_1's samples travel while X_0 is transformed
@@ -371,8 +414,11 @@
     for (int e = 1; e + 1 < B; ++e) {
         cvt_x(sb);
         fwd(sb);
-        store_spec(sb, e);
-        pair(sa, sb, out_of(0, e), [&](auto part) __attribute__((always_inline)) { load_x_part(sb, e + 1, part); });
+        if constexpr (!kSpread) store_spec(sb, e);
+        pair(sa, sb, out_of(0, e), [&](auto part) __attribute__((always_inline)) {
+            if constexpr (kSpread) store_spec_part(sb, e, part);
+            load_x_part(sb, e + 1, part);
+        });
     }
     // ---- the last buoy and the pairs among buoys 1..B-1, in the order of a host-planned table (host::plan_pair_trail:
     // runs that hand the anchor over).  Entry 0 of the table is the pair (0, B-1), entry k + 1 the order's step k:
@@ -380,7 +426,7 @@
     // step's h1 requests ONE spectrum (load_idx) into the array whose buoy the next step drops (load_arr: 0 = sa, 1 = sb).
     // In this order X_i is in sa and X_j in sb at every step (host::trail_kernel_ok, checked where the table is built), so
     // pair_h1 gets them as the anchor runs gave them and every pair's arithmetic is what it was.  X_{B-1} stays in sb
-    // behind phase 1 and is never stored: the first step is (first_load, B-1), and only first_load is requested, into sa.
+    // behind phase 1: the first step is (first_load, B-1), and only first_load is requested, into sa.
     {
         const int M2 = (B - 1) * (B - 2) / 2;            // steps of the order
         const int4* __restrict__ tab = trail;
@@ -389,10 +435,10 @@
         if (B > 1) {
             cvt_x(sb);
             fwd(sb);
-            // (X_{B-1} is NOT stored: no entry of the table requests it -- host::trail_kernel_ok -- and the scratch is private
-            // to this workgroup, so nobody else could read it either.  Its slot of the scratch stays allocated and unwritten.)
+            if constexpr (!(P1 & 1) && !kSpread) store_spec(sb, B - 1);
             const int fl = cur.z;
             pair(sa, sb, cur.x, [&](auto part) __attribute__((always_inline)) {
+                if constexpr (!(P1 & 1) && kSpread) store_spec_part(sb, B - 1, part);
                 if (M2 > 0) load_spec_part(sa, fl, part);
             });
         }
@@ -449,3 +495,6 @@
     seq = 0;   // any wave may resolve the last pairs; take wave 0
     barrier_hook(true);
     }   // next window of this workgroup
+}
+
+}  // namespace rmx
