@@ -50,6 +50,20 @@
  * passes; the library owns only ctx-internal device scratch.  Functions return 0 (RMX_OK) or a
  * negative code and never abort; rmx_last_error() gives the text.  A ctx is single-owner (not
  * thread safe); use one ctx per device (one process per GPU, or one host thread per ctx).
+ *
+ * The caller's buffers (tests/test_gpu_caller_memory.py holds every correlation and Doppler-search route to this):
+ *   Alignment: a DEVICE pointer must be aligned to its element and to nothing more -- `iq` to 8 bytes (one complex64
+ *     sample) or, with RMX_IN_U8, to 2 bytes (one I,Q pair; an odd address is refused), every output to 4 bytes.  The
+ *     kernels touch caller memory one element per access, so a slice of a larger buffer is as good as a fresh allocation.
+ *     A device pointer aligned to less is RMX_E_INVAL, the text naming the array, checked directly behind the NULL-buffer
+ *     check.  Host pointers only pass through the library's own copies and need no alignment beyond their C type's.
+ *   Extent: a call writes exactly [rows][n_pairs] elements of lag_int, lag_frac and peak ([n_windows][n_bands][n_pairs] in a
+ *     banded call; x 4 for quality; dop_idx and dop_frac like lag_int) and not one byte in front of or behind them, and it
+ *     never writes its input.  A refused call writes nothing.
+ *   Order: everything a call queues -- copies, kernels, the staging of pairs, bands and bounds -- is ordered on the ctx
+ *     stream, whichever stream rmx_set_stream named, one that does not synchronise with the null stream included: work
+ *     queued on that stream before the call is seen by it, work queued behind it sees its outputs.  Two asynchronous
+ *     (RMX_OUT_DEVICE) calls on one ctx may follow each other without a wait, with different pair lists, bands and bounds.
  */
 #ifndef RMX_H
 #define RMX_H

@@ -38,6 +38,7 @@ struct RequestArgs {
     int refine = 0;
     int32_t* lag_int = nullptr;
     float *lag_frac = nullptr, *peak = nullptr, *quality = nullptr;
+    unsigned flags = 0;             // RMX_IN_DEVICE, RMX_OUT_DEVICE, RMX_IN_U8: which pointers the kernels themselves touch
 };
 
 // The checked request in host form.  The plain call allocates nothing: bins and own_bounds stay empty.
@@ -161,6 +162,13 @@ struct OutArray {
 inline int check_overlap(const char* name, const void* p, size_t bytes, const OutArray* outs, int n, size_t out_bytes, const char* needs,
                          std::string* err) {
     const char *q0 = static_cast<const char*>(p), *q1 = q0 + bytes;
+    // The array that holds p's first byte is named in front of any other: quality is four times as long as an output, so
+    // a quality pointer set ON peak also runs over whatever array the caller's allocator happened to place behind peak,
+    // and the text must not depend on that.
+    for (int k = 0; k < n; ++k) {
+        const char* p0 = static_cast<const char*>(outs[k].p);
+        if (p0 <= q0 && q0 < p0 + out_bytes) return refuse(err, "%s overlaps %s: %s", name, outs[k].name, needs);
+    }
     for (int k = 0; k < n; ++k) {
         const char* p0 = static_cast<const char*>(outs[k].p);
         if (p0 < q1 && q0 < p0 + out_bytes) return refuse(err, "%s overlaps %s: %s", name, outs[k].name, needs);
@@ -168,10 +176,33 @@ inline int check_overlap(const char* name, const void* p, size_t bytes, const Ou
     return RMX_OK;
 }
 
+// The kernels read a device `iq` and write device outputs through the caller's own pointers, one element per access: a
+// complex64 sample (8 bytes), a uint8 I,Q pair (2 bytes: uchar2 indexing and 16-bit buffer loads), a 4-byte output.  A
+// device pointer aligned to less than its element is refused, the text naming the array; host pointers only pass
+// through the library's own copies and need nothing.  `outs`: the n output arrays, a NULL one (no quality) skipped.
+inline int check_alignment(unsigned flags, const void* iq, const OutArray* outs, int n, std::string* err) {
+    if (flags & RMX_IN_DEVICE) {
+        const bool u8 = (flags & RMX_IN_U8) != 0;
+        const unsigned need = u8 ? 2u : 8u, past = (unsigned)(reinterpret_cast<uintptr_t>(iq) % need);
+        if (past)
+            return refuse(err, "iq is a device pointer %u bytes past a multiple of %u: %s", past, need,
+                          u8 ? "uint8 input must be aligned to 2 bytes (one I,Q pair)" : "complex64 input must be aligned to 8 bytes (one sample)");
+    }
+    if (flags & RMX_OUT_DEVICE)
+        for (int k = 0; k < n; ++k) {
+            const unsigned past = (unsigned)(reinterpret_cast<uintptr_t>(outs[k].p) % 4u);
+            if (outs[k].p && past)
+                return refuse(err, "%s is a device pointer %u bytes past a multiple of 4: an output must be aligned to 4 bytes (one element)",
+                              outs[k].name, past);
+        }
+    return RMX_OK;
+}
+
 // Every check of the eight rmx_xcorr_batch* entries, in the order include/rmx.h promises, so an input with several bad
 // arguments is refused for the same one whichever entry it came through: the grouped entries' (integrate, the group
-// count), a NULL buffer, n_bands, the weighted entry's, the batch shape, the bounded entry's, refine, quality over
-// another output.  RMX_OK with *r filled (r->empty: nothing to do), or RMX_E_INVAL with *err.
+// count), a NULL buffer, a device pointer aligned to less than its element, n_bands, the weighted entry's, the batch
+// shape, the bounded entry's, refine, quality over another output.  RMX_OK with *r filled (r->empty: nothing to do), or
+// RMX_E_INVAL with *err.
 inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
     *r = Request{};
     if (a.bounds_required && !a.lag_bounds) return refuse(err, "NULL buffer");
@@ -184,8 +215,13 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
     }
     const int K = a.grouped ? a.integrate : 1;
     if (!a.iq || !a.lag_int || !a.lag_frac || !a.peak || (a.banded && !a.band_cps)) return refuse(err, "NULL buffer");
-    if (a.banded && (a.n_bands < 1 || a.n_bands > 64)) return refuse(err, "n_bands %d not in 1..64", a.n_bands);
     int rc;
+    {
+        const OutArray outs[4] = {{"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}, {"quality", a.quality}};
+        rc = check_alignment(a.flags, a.iq, outs, 4, err);
+        if (rc != RMX_OK) return rc;
+    }
+    if (a.banded && (a.n_bands < 1 || a.n_bands > 64)) return refuse(err, "n_bands %d not in 1..64", a.n_bands);
     if (a.banded || a.band_cps || a.weighting != RMX_WEIGHT_NONE) {
         rc = check_bands(a, r, err);
         if (rc != RMX_OK) return rc;

@@ -1744,6 +1744,7 @@ static int xcorr_request(rmx_ctx* c, host::RequestArgs a, unsigned flags) {
     a.n_buoys = c->n_buoys;
     a.n_samples = c->n_samples;
     a.max_windows = c->max_windows;
+    a.flags = flags;
     host::Request rq;
     std::string why;
     int rc = host::check_request(a, &rq, &why);
@@ -1901,8 +1902,12 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
                           int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
     if (!c) return RMX_E_INVAL;
     if (!iq || !dop_idx || !lag_int || !lag_frac || !peak || !doppler_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
-    if (n_dopplers < 1 || n_dopplers > 4096) return fail(c, RMX_E_INVAL, "n_dopplers %d not in 1..4096", n_dopplers);
     std::string why;
+    {   // a device pointer aligned to less than its element, as the correlation entries refuse it
+        const host::OutArray outs[5] = {{"dop_idx", dop_idx}, {"dop_frac", dop_frac}, {"lag_int", lag_int}, {"lag_frac", lag_frac}, {"peak", peak}};
+        if (host::check_alignment(flags, iq, outs, 5, &why) != RMX_OK) return fail(c, RMX_E_INVAL, "%s", why.c_str());
+    }
+    if (n_dopplers < 1 || n_dopplers > 4096) return fail(c, RMX_E_INVAL, "n_dopplers %d not in 1..4096", n_dopplers);
     int rc = host::check_batch(c->n_buoys, c->max_windows, n_windows, pairs, &n_pairs, &why);
     if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
     if (n_windows == 0 || n_pairs == 0) return RMX_OK;

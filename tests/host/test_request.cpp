@@ -252,10 +252,101 @@ static void test_refusal_texts() {
             REFUSED(call(block.data(), block.data(), 0), text);
             REFUSED(call(block.data(), block.data() + slots - 1, 8), text);
             REFUSED(call(block.data() + 4 * slots - 1, block.data(), 0), text);
+            // quality ON the array also runs over the three arrays' worth of memory behind it: whichever output the
+            // allocator placed there, the array that holds quality's first float is the one named
+            if (shape != 2) {
+                std::vector<float> row(4 * slots);
+                RequestArgs a = grouped(plain(o), shape == 1 ? 2 : 1, 0, row.data());
+                float* near[2] = {row.data() + slots, row.data() + 2 * slots};
+                if (k == 0) { a.lag_int = reinterpret_cast<int32_t*>(row.data()); a.lag_frac = near[0]; a.peak = near[1]; }
+                if (k == 1) { a.lag_frac = row.data(); a.lag_int = reinterpret_cast<int32_t*>(near[0]); a.peak = near[1]; }
+                if (k == 2) { a.peak = row.data(); a.lag_int = reinterpret_cast<int32_t*>(near[0]); a.lag_frac = near[1]; }
+                REFUSED(a, text);
+            }
             std::vector<float> apart(5 * slots);
             (void)ACCEPTED(call(apart.data(), apart.data() + slots, 4));      // directly behind it
             (void)ACCEPTED(call(apart.data() + 4 * slots, apart.data(), 4));  // directly in front of it
         }
+    }
+}
+
+// ---- 1b. a device pointer aligned to less than its element: refused, the array named; a host pointer is not looked at ----------
+static void test_alignment() {
+    Outs o((size_t)W * P + 1);
+    std::vector<float> iq_block(8);
+    char* const iq8 = reinterpret_cast<char*>(iq_block.data());            // a heap block: aligned to 8 or better
+    const unsigned in_dev = RMX_IN_DEVICE, out_dev = RMX_OUT_DEVICE, both = in_dev | out_dev;
+    auto call = [&](unsigned flags, const void* iq) {
+        RequestArgs a = plain(o);
+        a.flags = flags;
+        a.iq = iq;
+        return a;
+    };
+    // complex64 input: 8 bytes, one sample
+    (void)ACCEPTED(call(both, iq8));
+    (void)ACCEPTED(call(both, iq8 + 8));
+    REFUSED(call(in_dev, iq8 + 4), "iq is a device pointer 4 bytes past a multiple of 8: complex64 input must be aligned to 8 bytes (one sample)");
+    REFUSED(call(both, iq8 + 1), "iq is a device pointer 1 bytes past a multiple of 8: complex64 input must be aligned to 8 bytes (one sample)");
+    (void)ACCEPTED(call(out_dev, iq8 + 4));                                  // a host pointer goes through the library's copy
+    (void)ACCEPTED(call(0, iq8 + 1));
+    // uint8 input: 2 bytes, one I,Q pair; an odd address is refused
+    (void)ACCEPTED(call(both | RMX_IN_U8, iq8 + 2));
+    (void)ACCEPTED(call(in_dev | RMX_IN_U8, iq8 + 6));
+    REFUSED(call(both | RMX_IN_U8, iq8 + 1), "iq is a device pointer 1 bytes past a multiple of 2: uint8 input must be aligned to 2 bytes (one I,Q pair)");
+    REFUSED(call(in_dev | RMX_IN_U8, iq8 + 7), "iq is a device pointer 1 bytes past a multiple of 2: uint8 input must be aligned to 2 bytes (one I,Q pair)");
+    (void)ACCEPTED(call(out_dev | RMX_IN_U8, iq8 + 1));
+    // the outputs: 4 bytes each, the first misaligned one named; every 4-byte offset is accepted
+    for (int k = 0; k < 4; ++k) {
+        static const char* name[4] = {"lag_int", "lag_frac", "peak", "quality"};
+        for (int past = 0; past < 4; ++past) {
+            RequestArgs a = grouped(call(both, iq8), 1, 0, o.quality.data());
+            if (k == 0) a.lag_int = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(o.lag_int.data()) + past);
+            if (k == 1) a.lag_frac = reinterpret_cast<float*>(reinterpret_cast<char*>(o.lag_frac.data()) + past);
+            if (k == 2) a.peak = reinterpret_cast<float*>(reinterpret_cast<char*>(o.peak.data()) + past);
+            if (k == 3) a.quality = reinterpret_cast<float*>(reinterpret_cast<char*>(o.quality.data()) + past);
+            if (past == 0) {
+                (void)ACCEPTED(a);
+                continue;
+            }
+            char text[160];
+            std::snprintf(text, sizeof text, "%s is a device pointer %d bytes past a multiple of 4: an output must be aligned to 4 bytes (one element)",
+                          name[k], past);
+            REFUSED(a, text);
+            a.flags = in_dev;                                                // host outputs: not looked at
+            (void)ACCEPTED(a);
+        }
+    }
+    {   // lag_int one ELEMENT further (4 mod 16, 8 mod 16, ...): what a slice of a larger buffer gives
+        RequestArgs a = call(both, iq8);
+        a.lag_int = o.lag_int.data() + 1;
+        (void)ACCEPTED(a);
+    }
+    // the order: behind a NULL buffer, in front of n_bands and everything after it; iq in front of the outputs
+    const std::vector<double> set = bands_of(M);
+    Outs om((size_t)W * M * P);
+    {
+        RequestArgs a = banded(weighted(plain(om), &set, 0, 7), 0, 3);
+        a.flags = both;
+        a.iq = iq8 + 4;
+        a.peak = reinterpret_cast<float*>(reinterpret_cast<char*>(om.peak.data()) + 2);
+        REFUSED(a, "iq is a device pointer 4 bytes past a multiple of 8: complex64 input must be aligned to 8 bytes (one sample)");
+        a.iq = iq8;
+        REFUSED(a, "peak is a device pointer 2 bytes past a multiple of 4: an output must be aligned to 4 bytes (one element)");
+        a.lag_frac = nullptr;
+        REFUSED(a, kNull);
+    }
+    // the Doppler search calls the same routine with its five outputs, a NULL dop_frac skipped
+    {
+        std::vector<int32_t> dop_idx((size_t)W * P);
+        std::string err;
+        const OutArray ok[5] = {{"dop_idx", dop_idx.data()}, {"dop_frac", nullptr}, {"lag_int", o.lag_int.data()}, {"lag_frac", o.lag_frac.data()},
+                                {"peak", o.peak.data()}};
+        CHECK(check_alignment(both, iq8, ok, 5, &err) == RMX_OK);
+        const OutArray bad[5] = {{"dop_idx", reinterpret_cast<char*>(dop_idx.data()) + 3}, {"dop_frac", nullptr}, {"lag_int", o.lag_int.data()},
+                                 {"lag_frac", o.lag_frac.data()}, {"peak", o.peak.data()}};
+        CHECK(check_alignment(both, iq8, bad, 5, &err) == RMX_E_INVAL &&
+              err == "dop_idx is a device pointer 3 bytes past a multiple of 4: an output must be aligned to 4 bytes (one element)");
+        CHECK(check_alignment(in_dev, iq8, bad, 5, &err) == RMX_OK);
     }
 }
 
@@ -567,6 +658,7 @@ static void test_staged_layouts() {
 
 int main() {
     test_refusal_texts();
+    test_alignment();
     test_refusal_order();
     test_caf_tail();
     test_empty_and_identities();
