@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/rmx.h"
+#include "dev_buf.hpp"
 #include "host_plan.hpp"
 #include "host_request.hpp"
 #include "lag_bounds.hpp"
@@ -50,12 +51,52 @@
 #include "solve_path.hpp"
 #include "detect_path.hpp"
 
+namespace rmx {
+
+// dev_buf.hpp's memory calls on HIP.  A refused request becomes the ctx's error text; its code is RMX_E_HIP (RMX_MEM).
+struct HipMem {
+    const hipStream_t* stream;   // the ctx's, as it is at the moment of the wait (rmx_set_stream)
+    std::string* err;
+    hipError_t last = hipSuccess;
+    void* keep(void* p) {
+        if (last == hipSuccess) return p;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    void* alloc(size_t bytes) { void* p = nullptr; last = hipMalloc(&p, bytes); return keep(p); }
+    void free(void* p) { (void)hipFree(p); }
+    void* alloc_pinned(size_t bytes) { void* p = nullptr; last = hipHostMalloc(&p, bytes, hipHostMallocDefault); return keep(p); }
+    void free_pinned(void* p) { (void)hipHostFree(p); }
+    bool upload(void* dst, const void* src, size_t bytes) { last = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); return last == hipSuccess; }
+    void wait() { (void)hipStreamSynchronize(*stream); }
+    void refused(const char* what, size_t bytes) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "%s of %zu bytes failed: %s", what, bytes, hipGetErrorString(last));
+        *err = buf;
+    }
+};
+using Mem = mem::Arena<HipMem>;
+template <class T> using Counted = mem::Buf<T, HipMem, mem::kCounted>;       // in rmx_scratch_bytes
+template <class T> using Uncounted = mem::Buf<T, HipMem, mem::kUncounted>;   // not in it (the split is historical)
+template <class T> using Pinned = mem::Buf<T, HipMem, mem::kPinned>;
+template <class T, class Key> using Keyed = mem::Keyed<T, HipMem, Key>;      // uncounted, cached under Key
+
+}  // namespace rmx
+
 struct rmx_ctx {
+    template <class T> using Counted = rmx::Counted<T>;
+    template <class T> using Uncounted = rmx::Uncounted<T>;
     // a small host array that kernels read: staged through pinned memory into a ctx-owned device buffer (stage_to_device)
     struct DevStage {
-        int32_t* h = nullptr;  size_t h_elems = 0;
-        int* d = nullptr;      size_t d_elems = 0;
+        explicit DevStage(rmx::Mem* m) : h(m), d(m) {}
+        rmx::Pinned<int32_t> h;
+        Counted<int> d;
         hipEvent_t ev = nullptr;   // the last copy out of h: the next call waits for it before it rewrites h
+    };
+    struct PlanKey {   // what the pair plan on the device was built from
+        std::vector<int32_t> pairs;
+        int ppb = 0;
+        bool operator==(const PlanKey& o) const { return ppb == o.ppb && pairs == o.pairs; }
     };
     // The generic path's kernels as rmx::pick_generic_kernels chose them for this ctx: one typed pointer per signature
     // (the template arguments below only name the signature), null = this ctx does not have that kernel.
@@ -79,11 +120,13 @@ struct rmx_ctx {
         int ws_thr = 0, ws_upw = 0;                                             // its threads and windows per workgroup
     };
 
+    hipStream_t stream = nullptr;
+    std::string err;
+    rmx::Mem mem{{&stream, &err}};   // every buffer below allocates through it; mem.ledger is rmx_scratch_bytes
     rmx::host::Knobs knobs;   // kernel-selection options as they were at rmx_create (host_plan.hpp)
     int device = 0;
     int n_cus = 256;   // compute units of the device (persistent-grid size of the fused kernel)
     int n_buoys = 0, n_samples = 0, max_windows = 0;
-    hipStream_t stream = nullptr;
     bool own_stream = false;
     int chunk_windows = 0;
     int pairs_per_block = 7;
@@ -95,27 +138,22 @@ struct rmx_ctx {
     int win8 = 0;           // fused path: 1 = k_win8 (8 points x 1024 threads, 4 waves/SIMD), 0 = k_win
     int stag = 1;           // k_win8: which waves run the two halves between barriers in the opposite order
     int stag_kwin = 0;      // k_win / k_win_lb: the same choice; 0 (nobody) measured best since h1 stands once between two copies of h2 (LABNOTES R10.2)
-    float4* d_tw1_8 = nullptr;
-    float2* d_tb8 = nullptr;
-    float2* d_tc8 = nullptr;
+    Counted<float4> d_tw1_8{&mem};
+    Counted<float2> d_tb8{&mem}, d_tc8{&mem};
     bool fused = true;      // one kernel per chunk: forward spectra + pairs in one workgroup per window   // pair kernel variant: 1 workgroup/CU with resident tables
     // device buffers
-    float4* d_spec = nullptr;
-    float4* d_tw1 = nullptr;
-    float2* d_tw2 = nullptr;
-    int4* d_trail = nullptr;   // k_win: the order of a window's pairs among buoys 1 .. B-1 (host::plan_pair_trail)
-    rmx::PairItem* d_items = nullptr;
-    int* d_part_begin = nullptr;
-    void* d_in = nullptr;      size_t d_in_bytes = 0;
-    int* d_lag = nullptr;      float* d_frac = nullptr;  float* d_peak = nullptr;  size_t d_out_elems = 0;   // ONE block: lag | frac | peak
-    int* d_dop = nullptr;
-    float* d_quality = nullptr;  size_t d_quality_elems = 0;   // rmx_xcorr_batch_quality's fourth output of a host-pointer call
-    void* h_out = nullptr;     size_t h_out_bytes = 0;   // pinned staging of small host-pointer results (fetch_out)
-    size_t spec_bytes = 0, scratch_bytes = 0;
+    Counted<float4> d_spec{&mem}, d_tw1{&mem};
+    Counted<float2> d_tw2{&mem};
+    Counted<int32_t> d_trail{&mem};   // k_win: the order of a window's pairs among buoys 1 .. B-1 (host::plan_pair_trail), as int4
+    rmx::Keyed<rmx::PairItem, PlanKey> d_items{&mem};   // the pair plan: both hold the same key, or the plan is not there
+    rmx::Keyed<int, PlanKey> d_part_begin{&mem};
+    Uncounted<char> d_in{&mem};
+    Uncounted<float> d_out{&mem};       // ONE block of a host-pointer call's results: lag | frac | peak | dop (out_block)
+    Uncounted<float> d_quality{&mem};   // rmx_xcorr_batch_quality's fourth output of a host-pointer call
+    rmx::Pinned<char> h_out{&mem};      // pinned staging of small host-pointer results (fetch_out)
     // generic path (n_samples != 4096): see generic_path.hpp
     bool generic = false;
     int g_logL = 0, g_logL1 = 0, g_logL2 = 0, g_lo_bits = 0, g_chunk = 0;
-    size_t g_dyn_bytes = 0, g_pair_bytes = 0;   // chunk-sized buffers of generic_ensure (all of them / the pair-dependent ones)
     GenericKernels gk;
     bool g_fused = false;      // four-step: both row passes in g_rows_fused (n_buoys <= 4, plain batches)
     bool g_fused_always = false;
@@ -123,50 +161,49 @@ struct rmx_ctx {
     bool g_wscr = false;       // 512 <= L <= 16384, any buoy count: whole windows in g_win_scr (spectra in a cache-resident scratch)
     bool g_wscr_always = false;
     int g_ws_grid = 0;
-    float4* g_ws_scratch = nullptr;
-    float2* g_tw_win = nullptr;            // W_L half table of that kernel
-    float2* g_tw_l = nullptr;              // g_win_eo15 (N = 16384): W_32768^i, i < 1024
+    Counted<float4> g_ws_scratch{&mem};
+    Counted<float2> g_tw_win{&mem};        // W_L half table of that kernel
+    Counted<float2> g_tw_l{&mem};          // g_win_eo15 (N = 16384): W_32768^i, i < 1024
     bool g_k8 = false;                     // N = 8192: k_win8kl (kwin8k.hpp) instead of g_win_scr14 for batches that fill the chip
     int g_k8_kind = 1;                     // 1 = k_win8kl (LDS-resident anchor half), 2 = k_win8k (experiments build)
-    float4* g_k8_tw1 = nullptr;            // its TW1 tables (both halves)
-    float2* g_k8_tw2 = nullptr;            // k_win's TW2 table
+    Counted<float4> g_k8_tw1{&mem};        // its TW1 tables (both halves)
+    Counted<float2> g_k8_tw2{&mem};        // k_win's TW2 table
     int g_k16 = 0;                         // N = 16384: k16_fwd + k16_pairs (kwin16k.hpp); 1 = from the measured batch size on, 2 = always
-    float4* g_k16_tw1 = nullptr;           // slot factors of TW1
-    float2 *g_k16_gq = nullptr, *g_k16_tw2 = nullptr, *g_k16_tws = nullptr;   // per-quarter thread factors, k_win's TW2, W_128 rows
+    Counted<float4> g_k16_tw1{&mem};       // slot factors of TW1
+    Counted<float2> g_k16_gq{&mem}, g_k16_tw2{&mem}, g_k16_tws{&mem};   // per-quarter thread factors, k_win's TW2, W_128 rows
     int g_rows_anchor_min_b = 6;           // gk.rows_anchor from this many buoys on (option rows_anchor = n sets it, 0 = never)
-    float2 *g_tw = nullptr, *g_tw1 = nullptr, *g_tw2 = nullptr, *g_thi = nullptr, *g_tlo = nullptr;
-    float2 *g_spec = nullptr, *g_spec_r = nullptr, *g_prod = nullptr;   // spectra, de-rotated spectra (CAF), products
-    rmx::gen::GTile* g_rec = nullptr;   // per column tile: partial argmax + taps
-    float* g_halo = nullptr;            // per column tile: |r|^2 of its two edge columns
-    rmx::gen::GPair* g_pairs = nullptr;
-    long g_slots_alloc = 0;
-    int g_pairs_n = -1;
-    std::vector<int32_t> g_pairs_plan;
+    Counted<float2> g_tw{&mem}, g_tw1{&mem}, g_tw2{&mem}, g_thi{&mem}, g_tlo{&mem};
+    // the chunk-sized buffers (generic_ensure): spectra, de-rotated spectra (CAF), products
+    Counted<float2> g_spec{&mem}, g_spec_r{&mem}, g_prod{&mem};
+    Counted<rmx::gen::GTile> g_rec{&mem};   // per column tile: partial argmax + taps
+    Counted<float> g_halo{&mem};            // per column tile: |r|^2 of its two edge columns
+    rmx::Keyed<rmx::gen::GPair, std::vector<int32_t>> g_pairs{&mem};   // under the plan's pair list
     // host-pointer input of the fused path: copies pipelined against the kernels on a second stream
     hipStream_t copy_stream = nullptr;
     hipEvent_t copy_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // rmx_detect_batch: twiddle table of the last window length, dB spectra, staging
-    float2* dt_tw = nullptr;  int dt_logn = 0;  float* dt_pdb = nullptr;  size_t dt_pdb_bytes = 0;
-    void* dt_in = nullptr;  size_t dt_in_bytes = 0;  void* dt_out = nullptr;  size_t dt_out_bytes = 0;
+    rmx::Keyed<float2, int> dt_tw{&mem};   // under log2 of the window length
+    Uncounted<float> dt_pdb{&mem};
+    Uncounted<char> dt_in{&mem}, dt_out{&mem};   // (dt_out: ONE block, bin | power | snr | confidence | count | floor)
     // rmx_solve_batch work buffers
-    double* sv_buoys = nullptr;  int* sv_pairs = nullptr;  size_t sv_pairs_cap = 0;
-    void* sv_in = nullptr;  size_t sv_in_bytes = 0;  void* sv_out = nullptr;  size_t sv_out_bytes = 0;
+    Uncounted<double> sv_buoys{&mem};
+    Uncounted<int> sv_pairs{&mem};
+    Uncounted<char> sv_in{&mem}, sv_out{&mem};   // ONE block each: lag_int | lag_frac | weight, pos | cost | iters
     // CAF (rmx_caf_batch): de-rotated spectra of the N = 4096 path, phasor table, per-hypothesis results
-    float4* d_spec_r = nullptr;  size_t spec_r_bytes = 0;
-    float2* caf_rot = nullptr;  size_t caf_rot_elems = 0;
-    int* caf_lag = nullptr;  float* caf_frac = nullptr;  float* caf_peak = nullptr;  int* caf_dop = nullptr;
-    size_t caf_out_elems = 0;
-    float* caf_nb = nullptr;  size_t caf_nb_elems = 0;   // rmx_caf_batch_request with dop_frac: [3][slots] neighbour peaks of
-                                                         // k_caf_select_fd, then [slots] dop_frac of a host-pointer call
-    std::vector<double> caf_grid;
+    Uncounted<float4> d_spec_r{&mem};
+    rmx::Keyed<float2, std::vector<double>> caf_rot{&mem};   // under the Doppler grid
+    Uncounted<int> caf_lag{&mem};
+    Uncounted<float> caf_frac{&mem}, caf_peak{&mem};
+    Uncounted<float> caf_nb{&mem};   // rmx_caf_batch_request with dop_frac: [3][slots] neighbour peaks of k_caf_select_fd,
+                                     // then [slots] dop_frac of a host-pointer call
     // the caller's lag windows (rmx_xcorr_batch_bounded) and its bands as signed bins (rmx_xcorr_batch_weighted): the
     // device copies that a call's XcorrCall points into (rmx_xcorr_batch_bands: the full band, then the band set)
-    DevStage lb_stage, band_stage;
-    rmx::RefPair* rf_pairs = nullptr;          // k_refine's and k_quality's pair list (refine.hpp): the plan's pairs in output order
-    std::vector<int32_t> rf_pairs_plan;
-    // cached pair plan
+    DevStage lb_stage{&mem}, band_stage{&mem};
+    // k_refine's and k_quality's pair list (refine.hpp): the plan's pairs in output order, under that list
+    rmx::Keyed<rmx::RefPair, std::vector<int32_t>> rf_pairs{&mem};
+    // the pair plan that d_items and d_part_begin hold (build_plan)
     std::vector<int32_t> plan_pairs;
-    int plan_n_pairs = -1, plan_n_parts = 0, plan_ppb = 0;
+    int plan_n_parts = 0;
     bool plan_all_pairs = false;   // the plan is the default list: all i<j in nested-loop order
     // timing
     std::vector<hipEvent_t> ev;
@@ -174,7 +211,6 @@ struct rmx_ctx {
     size_t ev_used = 0;
     float t_fwd = 0, t_pair = 0;
     int n_fwd = 0, n_pair = 0;
-    std::string err;
 };
 
 namespace rmx {
@@ -252,6 +288,11 @@ static int fail(rmx_ctx* c, int code, const char* fmt, ...) {
         if (e_ != hipSuccess)                                                                     \
             return fail((c), RMX_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_),    \
                         __FILE__, __LINE__);                                                      \
+    } while (0)
+// a buffer request (dev_buf.hpp: reserve, assign, refill) that failed: HipMem::refused has written the ctx's error text
+#define RMX_MEM(ok)                    \
+    do {                               \
+        if (!(ok)) return RMX_E_HIP;   \
     } while (0)
 
 using host::is_pow2;
@@ -382,31 +423,21 @@ static int build_plan(rmx_ctx* c, const int32_t* pairs, int n_pairs) {
     host::PairPlan pp;
     std::string why;
     if (host::make_pair_plan(c->n_buoys, pairs, n_pairs, c->pairs_per_block, &pp, &why) != 0) return fail(c, RMX_E_INVAL, "%s", why.c_str());
-    if (c->plan_n_pairs == n_pairs && c->plan_ppb == c->pairs_per_block && pp.pairs == c->plan_pairs) return RMX_OK;
-    if (c->d_items) { (void)hipFree(c->d_items); c->d_items = nullptr; }
-    if (c->d_part_begin) { (void)hipFree(c->d_part_begin); c->d_part_begin = nullptr; }
-    RMX_HIP(c, hipMalloc((void**)&c->d_items, sizeof(PairItem) * (size_t)n_pairs));
-    RMX_HIP(c, hipMalloc((void**)&c->d_part_begin, sizeof(int) * (size_t)(pp.n_parts + 1)));
-    RMX_HIP(c, hipMemcpy(c->d_items, pp.items.data(), sizeof(PairItem) * (size_t)n_pairs, hipMemcpyHostToDevice));
-    RMX_HIP(c, hipMemcpy(c->d_part_begin, pp.part_begin.data(), sizeof(int) * (size_t)(pp.n_parts + 1), hipMemcpyHostToDevice));
+    const rmx_ctx::PlanKey key{std::move(pp.pairs), c->pairs_per_block};
+    if (c->d_items.holds(key) && c->d_part_begin.holds(key)) return RMX_OK;
+    RMX_MEM(c->d_items.refill(key, pp.items.data(), (size_t)n_pairs));
+    RMX_MEM(c->d_part_begin.refill(key, pp.part_begin.data(), (size_t)(pp.n_parts + 1)));
     c->plan_all_pairs = pp.all_pairs;
-    c->plan_pairs.swap(pp.pairs);
-    c->plan_n_pairs = n_pairs;
+    c->plan_pairs = key.pairs;
     c->plan_n_parts = pp.n_parts;
-    c->plan_ppb = c->pairs_per_block;
     return RMX_OK;
 }
 
 // the plan's pairs in output order on the device, for the kernels that take one output slot per workgroup
 static int ensure_ref_pairs(rmx_ctx* c, int n_pairs) {
-    if (c->rf_pairs_plan != c->plan_pairs || !c->rf_pairs) {
-        RMX_HIP(c, hipStreamSynchronize(c->stream));   // an earlier call's k_refine / k_quality may still read the old list
-        if (c->rf_pairs) { (void)hipFree(c->rf_pairs); c->rf_pairs = nullptr; }
-        c->rf_pairs_plan.clear();
-        RMX_HIP(c, hipMalloc((void**)&c->rf_pairs, sizeof(RefPair) * (size_t)n_pairs));
-        RMX_HIP(c, hipMemcpy(c->rf_pairs, c->plan_pairs.data(), sizeof(RefPair) * (size_t)n_pairs, hipMemcpyHostToDevice));
-        c->rf_pairs_plan = c->plan_pairs;
-    }
+    static_assert(sizeof(RefPair) == 2 * sizeof(int32_t), "a RefPair is one (i, j) of the plan's list");
+    if (!c->rf_pairs.holds(c->plan_pairs))
+        RMX_MEM(c->rf_pairs.refill(c->plan_pairs, reinterpret_cast<const RefPair*>(c->plan_pairs.data()), (size_t)n_pairs));
     return RMX_OK;
 }
 
@@ -474,13 +505,6 @@ static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, 
             return launch(c, kTkQuality, k_quality<decltype(lay)::value, BandSet>, dim3(grid), dim3(kRefThreads), 0, a, d_peak, call.quality, bs);
         return launch(c, kTkQuality, k_quality<decltype(lay)::value>, dim3(grid), dim3(kRefThreads), 0, a, d_peak, call.quality);
     });
-}
-
-static int upload(rmx_ctx* c, float2** dst, const std::vector<float2>& v) {
-    RMX_HIP(c, hipMalloc((void**)dst, v.size() * sizeof(float2)));
-    RMX_HIP(c, hipMemcpy(*dst, v.data(), v.size() * sizeof(float2), hipMemcpyHostToDevice));
-    c->scratch_bytes += v.size() * sizeof(float2);
-    return RMX_OK;
 }
 
 // windows up to this zero-padded length run with the whole transform in LDS (128 KiB of the 160)
@@ -658,8 +682,7 @@ static int generic_init(rmx_ctx* c) {
     int rc = RMX_OK;
     if (L <= kGenSmallMaxL) {
         make_row_table(t, (int)L);
-        rc = upload(c, &c->g_tw, t);
-        if (rc) return rc;
+        RMX_MEM(c->g_tw.assign(t));
         c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, 0, 0, 0, 0, 0, c->knobs);
         rc = allow_lds(c, (size_t)gen::lp(L) * 8 + 1024 * 8, g_pair_small<>, g_pair_small<LagBounds>, g_pair_small<LagBounds, Integrate>,
                        g_pair_small<BandSet>, g_pair_small<LagBounds, BandSet>, g_fwd_small<false>, g_fwd_small<true>,
@@ -678,17 +701,13 @@ static int generic_init(rmx_ctx* c) {
         c->g_logL2 = c->g_logL - c->g_logL1;
         c->g_lo_bits = (c->g_logL + 1) / 2;
         make_row_table(t, 1 << c->g_logL1);
-        rc = upload(c, &c->g_tw1, t);
-        if (rc) return rc;
+        RMX_MEM(c->g_tw1.assign(t));
         make_row_table(t, 1 << c->g_logL2);
-        rc = upload(c, &c->g_tw2, t);
-        if (rc) return rc;
+        RMX_MEM(c->g_tw2.assign(t));
         std::vector<float2> thi, tlo;
         make_big_tables(thi, tlo, L, c->g_lo_bits);
-        rc = upload(c, &c->g_thi, thi);
-        if (rc) return rc;
-        rc = upload(c, &c->g_tlo, tlo);
-        if (rc) return rc;
+        RMX_MEM(c->g_thi.assign(thi));
+        RMX_MEM(c->g_tlo.assign(tlo));
         c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, c->g_logL1, c->g_logL2, host_col_log_t(c, c->g_logL1),
                                      gen_cols_threads(c, c->g_logL1), gen_rows_tpr(c, 1 << c->g_logL2), c->knobs);
         const GenericKernels& k = c->gk;
@@ -711,14 +730,12 @@ static int generic_init(rmx_ctx* c) {
     if (c->g_wscr) {
         const GenericKernels& k = c->gk;
         make_row_table(t, c->g_logL == 15 ? 16384 : (int)L);       // (N = 16384: two 16384-point halves)
-        rc = upload(c, &c->g_tw_win, t);
-        if (rc) return rc;
+        RMX_MEM(c->g_tw_win.assign(t));
         if (c->g_logL == 15) {
             const double two_pi = 6.283185307179586476925286766559;
             std::vector<float2> wl(1024);
             for (int i = 0; i < 1024; ++i) wl[i] = make_float2((float)std::cos(two_pi * i / 32768.0), (float)-std::sin(two_pi * i / 32768.0));
-            rc = upload(c, &c->g_tw_l, wl);
-            if (rc) return rc;
+            RMX_MEM(c->g_tw_l.assign(wl));
         }
         rc = allow_lds(c, k.ws_lds, k.ws[0], k.ws[1], k.ws15[0], k.ws15[1]);
         if (rc) return rc;
@@ -732,8 +749,7 @@ static int generic_init(rmx_ctx* c) {
         if (grid > need) grid = need;
         c->g_ws_grid = (int)grid;
         const size_t sbytes = (size_t)grid * k.ws_upw * c->n_buoys * L * 8;
-        RMX_HIP(c, hipMalloc((void**)&c->g_ws_scratch, sbytes));
-        c->scratch_bytes += sbytes;
+        RMX_MEM(c->g_ws_scratch.reserve(sbytes / sizeof(float4)));
         // N = 8192: the two bin-parity halves on the fused N = 4096 kernel's network (kwin8k.hpp), same scratch size
         // (B x 2 x 64 KiB per persistent workgroup), one workgroup per CU.  Option kwin8k: 1 (default) = k_win8kl, one anchor
         // half resident in LDS -- 0.51 against g_win_scr14's 0.73 ms at 8 buoys x 512 windows, 1.00 against 1.42 at 16 x 256,
@@ -748,11 +764,8 @@ static int generic_init(rmx_ctx* c) {
             else
 #endif
             k8::build_tables8kl(t1);
-            RMX_HIP(c, hipMalloc((void**)&c->g_k8_tw1, t1.size() * sizeof(float4)));
-            RMX_HIP(c, hipMemcpy(c->g_k8_tw1, t1.data(), t1.size() * sizeof(float4), hipMemcpyHostToDevice));
-            RMX_HIP(c, hipMalloc((void**)&c->g_k8_tw2, t2.size() * sizeof(float2)));
-            RMX_HIP(c, hipMemcpy(c->g_k8_tw2, t2.data(), t2.size() * sizeof(float2), hipMemcpyHostToDevice));
-            c->scratch_bytes += t1.size() * sizeof(float4) + t2.size() * sizeof(float2);
+            RMX_MEM(c->g_k8_tw1.assign(t1));
+            RMX_MEM(c->g_k8_tw2.assign(t2));
             rc = allow_lds(c, k8::kLdsLBytes, k8::k_win8kl<false>, k8::k_win8kl<true>, k8::k_win8kl<false, LagBounds>, k8::k_win8kl<true, LagBounds>);
             if (rc) return rc;
             c->g_k8 = k.ws_upw == 1 && grid <= c->n_cus;      // (its grid is the scratch's: one window slot per workgroup)
@@ -772,15 +785,10 @@ static int generic_init(rmx_ctx* c) {
             std::vector<float2> t2, gq, tws;
             build_tables(t1_4096, t2);
             k16::build_tables16k(t1, gq, tws);
-            RMX_HIP(c, hipMalloc((void**)&c->g_k16_tw1, t1.size() * sizeof(float4)));
-            RMX_HIP(c, hipMemcpy(c->g_k16_tw1, t1.data(), t1.size() * sizeof(float4), hipMemcpyHostToDevice));
-            rc = upload(c, &c->g_k16_gq, gq);
-            if (rc) return rc;
-            rc = upload(c, &c->g_k16_tw2, t2);
-            if (rc) return rc;
-            rc = upload(c, &c->g_k16_tws, tws);
-            if (rc) return rc;
-            c->scratch_bytes += t1.size() * sizeof(float4);
+            RMX_MEM(c->g_k16_tw1.assign(t1));
+            RMX_MEM(c->g_k16_gq.assign(gq));
+            RMX_MEM(c->g_k16_tw2.assign(t2));
+            RMX_MEM(c->g_k16_tws.assign(tws));
             rc = allow_lds(c, k16::kLdsFwdBytes, k16::k16_fwd<false>, k16::k16_fwd<true>);
             if (rc == RMX_OK) rc = allow_lds(c, k16::kLdsPairBytes, k16::k16_pairs<>, k16::k16_pairs<LagBounds>);
             if (rc) return rc;
@@ -798,60 +806,36 @@ static int generic_init(rmx_ctx* c) {
 //   need_pairbufs  products / tile records / halo of the FOUR-STEP pair kernels -- not when the whole-window kernels
 //                  run (g_win_fused, g_win_scr never touch them: an 8-buoy, 4096-window engine of 8192-sample windows
 //                  would otherwise pin 15 GB it never uses)
-// A failed hipMalloc halves the chunk and retries (down to one window) instead of giving up.
+// A failed allocation halves the chunk and retries (down to one window) instead of giving up.
 // n_bands > 1 (rmx_xcorr_batch_bands): the pair-dependent buffers hold the slots host::plan_bands states for the chunk.
 static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool need_pairbufs = true, int n_bands = 1) {
     using namespace gen;
     const long L = 1L << c->g_logL;
     const bool four_step = L > kGenSmallMaxL;
-    auto release = [&]() {
-        for (void** p : {(void**)&c->g_spec, (void**)&c->g_spec_r, (void**)&c->g_prod, (void**)&c->g_rec, (void**)&c->g_halo})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        c->scratch_bytes -= c->g_dyn_bytes;
-        c->g_dyn_bytes = 0;
-        c->g_slots_alloc = 0;
+    auto release = [&]() {   // every chunk-sized buffer
+        c->g_spec.release();
+        c->g_spec_r.release();
+        c->g_prod.release();
+        c->g_rec.release();
+        c->g_halo.release();
     };
     for (;;) {
         const long parts = four_step ? (1L << c->g_logL2) >> host_col_log_t(c, c->g_logL1) : 0;   // one record per column tile
         const host::BandsPlan bp = host::plan_bands(c->g_chunk, 0, n_bands, c->n_buoys, n_pairs, L, four_step, parts, c->g_logL1, sizeof(GTile));
-        const long items = (long)c->g_chunk * c->n_buoys, slots = bp.slots;   // (n_bands = 1: g_chunk * n_pairs)
-        bool ok = true;
-        auto grab = [&](void** p, size_t bytes) {
-            if (!ok) return;
-            if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; ok = false; return; }
-            c->scratch_bytes += bytes;
-            c->g_dyn_bytes += bytes;
-        };
-        if (!c->g_spec && need_spec) grab((void**)&c->g_spec, (size_t)items * L * 8);
-        if (four_step && need_pairbufs && slots > c->g_slots_alloc) {
-            // (re)allocate the pair-dependent buffers when the pair count grows
-            for (void** p : {(void**)&c->g_prod, (void**)&c->g_rec, (void**)&c->g_halo})
-                if (*p) { (void)hipFree(*p); *p = nullptr; }
-            c->scratch_bytes -= c->g_pair_bytes;
-            c->g_dyn_bytes -= c->g_pair_bytes;
-            c->g_pair_bytes = 0;
-            c->g_slots_alloc = 0;
-            const size_t before = c->g_dyn_bytes;
-            grab((void**)&c->g_prod, bp.prod_bytes);
-            grab((void**)&c->g_rec, bp.rec_bytes);
-            grab((void**)&c->g_halo, bp.halo_bytes);
-            c->g_pair_bytes = c->g_dyn_bytes - before;
-            if (ok) c->g_slots_alloc = slots;
-        }
+        bool ok = !need_spec || c->g_spec.try_reserve((size_t)c->g_chunk * c->n_buoys * L);
+        // the pair-dependent buffers grow with the slots (n_bands = 1: g_chunk * n_pairs): each of their sizes is per slot
+        if (four_step && need_pairbufs)
+            ok = ok && c->g_prod.try_reserve(bp.prod_bytes / sizeof(float2)) && c->g_rec.try_reserve(bp.rec_bytes / sizeof(GTile)) &&
+                 c->g_halo.try_reserve(bp.halo_bytes / sizeof(float));
         if (ok) break;
-        if (c->g_chunk <= 1) { release(); return fail(c, RMX_E_NOMEM, "device allocation failed even for one window per chunk"); }
-        RMX_HIP(c, hipStreamSynchronize(c->stream));
-        release();                                    // every chunk-sized buffer goes; they come back at half the size
+        release();                                    // they come back at half the size
+        if (c->g_chunk <= 1) return fail(c, RMX_E_NOMEM, "device allocation failed even for one window per chunk");
         c->g_chunk = (c->g_chunk + 1) / 2;
     }
-    if (c->g_pairs_n == n_pairs && c->g_pairs_plan == c->plan_pairs) return RMX_OK;
-    if (c->g_pairs) { (void)hipFree(c->g_pairs); c->g_pairs = nullptr; }
+    if (c->g_pairs.holds(c->plan_pairs)) return RMX_OK;
     std::vector<GPair> gp(n_pairs);
     for (int q = 0; q < n_pairs; ++q) gp[q] = GPair{c->plan_pairs[2 * q], c->plan_pairs[2 * q + 1]};
-    RMX_HIP(c, hipMalloc((void**)&c->g_pairs, sizeof(GPair) * (size_t)n_pairs));
-    RMX_HIP(c, hipMemcpy(c->g_pairs, gp.data(), sizeof(GPair) * (size_t)n_pairs, hipMemcpyHostToDevice));
-    c->g_pairs_n = n_pairs;
-    c->g_pairs_plan = c->plan_pairs;
+    RMX_MEM(c->g_pairs.refill(c->plan_pairs, gp));
     return RMX_OK;
 }
 
@@ -865,11 +849,7 @@ static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, 
     const float fwd_scale = std::ldexp(1.0f, -(logL / 2));
     const int items = wc * B;
     const long first_item = (long)w0 * B;
-    if (rot && !c->g_spec_r) {
-        RMX_HIP(c, hipMalloc((void**)&c->g_spec_r, (size_t)c->g_chunk * B * L * 8));
-        c->scratch_bytes += (size_t)c->g_chunk * B * L * 8;
-        c->g_dyn_bytes += (size_t)c->g_chunk * B * L * 8;
-    }
+    if (rot) RMX_MEM(c->g_spec_r.reserve((size_t)c->g_chunk * B * L));   // chunk-sized: generic_ensure releases it with the others
     float2* dst = rot ? c->g_spec_r : c->g_spec;
     XWeight wt = call.wt;   // weighted call: the stored bins carry fwd_scale
     wt.unit = fwd_scale;
@@ -993,16 +973,9 @@ static int fwd4096(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, 
     if (rot) {
         const size_t nb = n_bins > 1 ? (size_t)n_items * (8 * kThreads) * sizeof(float4)
                                      : (size_t)(wc < c->chunk_windows ? c->chunk_windows : wc) * c->n_buoys * (8 * kThreads) * sizeof(float4);
-        if (c->spec_r_bytes < nb) {
-            RMX_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->d_spec_r) (void)hipFree(c->d_spec_r);
-            c->d_spec_r = nullptr;
-            c->spec_r_bytes = 0;
-            RMX_HIP(c, hipMalloc((void**)&c->d_spec_r, nb));
-            c->spec_r_bytes = nb;
-        }
+        RMX_MEM(c->d_spec_r.reserve(nb / sizeof(float4)));
     }
-    float4* dst = rot ? c->d_spec_r : c->d_spec;
+    float4* dst = rot ? c->d_spec_r.get() : c->d_spec.get();
     return with_u8(u8, [&](auto U) {
         constexpr bool U8 = decltype(U)::value;
         auto go = [&](auto kern, const float2* a_rot, int a_wrap, auto... wt) {
@@ -1023,7 +996,7 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
     const long first = (long)w0 * nb;
     wc *= n_bins * nb;
     const int xcd_map = (wc % 8 == 0) ? 1 : 0;
-    const float4* spec_j = use_rot ? c->d_spec_r : c->d_spec;
+    const float4* spec_j = use_rot ? c->d_spec_r.get() : c->d_spec.get();
     // the streaming and the resident kernel (which keeps one unused int argument), each with or without its trailing structs
     auto str = [&](auto kern, int windows, int xmap, long first, int wrap, auto... tail) {
         return launch(c, kTkPair4096, kern, dim3(windows * n_parts), dim3(kThreads), kLdsBytes, c->d_spec, spec_j, c->d_tw1, c->d_tw2,
@@ -1113,7 +1086,7 @@ static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_
                      float* d_peak, bool u8) {
     const int B = c->n_buoys;
     const float out_scale = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 15);
-    const k16::Pair2* prs = reinterpret_cast<const k16::Pair2*>(c->g_pairs);
+    const k16::Pair2* prs = reinterpret_cast<const k16::Pair2*>(c->g_pairs.get());
     for (int w0 = 0; w0 < n_windows; w0 += chunk) {
         const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
         const int items = wc * B;
@@ -1191,7 +1164,7 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps
     if (grid > c->g_ws_grid) grid = c->g_ws_grid;
     if (plan.route == kRouteKWin8) {            // N = 8192 on k_win's network (kwin8k.hpp)
         const float out_scale8 = std::ldexp(1.0f, 3 * kTw1ScaleLog2 - 14);
-        const k8::Pair2* prs = rq.all_pairs ? nullptr : reinterpret_cast<const k8::Pair2*>(c->g_pairs);
+        const k8::Pair2* prs = rq.all_pairs ? nullptr : reinterpret_cast<const k8::Pair2*>(c->g_pairs.get());
         const int stag = (int)c->knobs.get_or("stag", 1);
         rc = with_u8(u8, [&](auto U) {
             constexpr bool U8 = decltype(U)::value;
@@ -1288,21 +1261,16 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
         // per-window scratch of the unfused path (custom pair lists) is allocated on first use
         {
             const int wg = chunk < c->n_cus ? chunk : c->n_cus;
-            c->spec_bytes = (size_t)wg * n_buoys * (8 * kThreads) * sizeof(float4);
+            RMX_MEM(c->d_spec.reserve((size_t)wg * n_buoys * (8 * kThreads)));
         }
-        RMX_HIP(c, hipMalloc((void**)&c->d_spec, c->spec_bytes));
         std::vector<float4> tw1;
         std::vector<float2> tw2;
         build_tables(tw1, tw2);
-        RMX_HIP(c, hipMalloc((void**)&c->d_tw1, tw1.size() * sizeof(float4)));
-        RMX_HIP(c, hipMalloc((void**)&c->d_tw2, tw2.size() * sizeof(float2)));
-        RMX_HIP(c, hipMemcpy(c->d_tw1, tw1.data(), tw1.size() * sizeof(float4), hipMemcpyHostToDevice));
-        RMX_HIP(c, hipMemcpy(c->d_tw2, tw2.data(), tw2.size() * sizeof(float2), hipMemcpyHostToDevice));
+        RMX_MEM(c->d_tw1.assign(tw1));
+        RMX_MEM(c->d_tw2.assign(tw2));
         const std::vector<int32_t> trail = host::encode_pair_trail(host::plan_pair_trail(n_buoys));
         if (trail.empty()) return fail(c, RMX_E_INVAL, "k_win cannot walk the pair order planned for %d buoys", n_buoys);
-        RMX_HIP(c, hipMalloc((void**)&c->d_trail, trail.size() * sizeof(int32_t)));
-        RMX_HIP(c, hipMemcpy(c->d_trail, trail.data(), trail.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        c->scratch_bytes = c->spec_bytes + tw1.size() * sizeof(float4) + tw2.size() * sizeof(float2) + trail.size() * sizeof(int32_t);
+        RMX_MEM(c->d_trail.assign(trail));
         c->stag = (int)c->knobs.get_or("stag", 1);
         c->stag_kwin = (int)c->knobs.get_or("stag", 0);
         c->small_batch = c->knobs.get_or("small4096", 1) != 0;
@@ -1311,13 +1279,9 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
             std::vector<float4> t1;
             std::vector<float2> tb, tc;
             build_tables8(t1, tb, tc);
-            RMX_HIP(c, hipMalloc((void**)&c->d_tw1_8, t1.size() * sizeof(float4)));
-            RMX_HIP(c, hipMalloc((void**)&c->d_tb8, tb.size() * sizeof(float2)));
-            RMX_HIP(c, hipMalloc((void**)&c->d_tc8, tc.size() * sizeof(float2)));
-            RMX_HIP(c, hipMemcpy(c->d_tw1_8, t1.data(), t1.size() * sizeof(float4), hipMemcpyHostToDevice));
-            RMX_HIP(c, hipMemcpy(c->d_tb8, tb.data(), tb.size() * sizeof(float2), hipMemcpyHostToDevice));
-            RMX_HIP(c, hipMemcpy(c->d_tc8, tc.data(), tc.size() * sizeof(float2), hipMemcpyHostToDevice));
-            c->scratch_bytes += t1.size() * sizeof(float4) + (tb.size() + tc.size()) * sizeof(float2);
+            RMX_MEM(c->d_tw1_8.assign(t1));
+            RMX_MEM(c->d_tb8.assign(tb));
+            RMX_MEM(c->d_tc8.assign(tc));
             int rc_x = allow_lds(c, w8::kLdsWin8Bytes, w8::k_win8<false>, w8::k_win8<true>);
             if (rc_x == RMX_OK) rc_x = allow_lds(c, pk::kLdsWinpBytes, k_winp<false>, k_winp<true>);
             if (rc_x != RMX_OK) return rc_x;
@@ -1345,41 +1309,13 @@ void rmx_destroy(rmx_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-    for (void* p : {(void*)c->g_tw, (void*)c->g_tw1, (void*)c->g_tw2, (void*)c->g_thi, (void*)c->g_tlo, (void*)c->g_spec,
-                    (void*)c->g_spec_r, (void*)c->g_prod, (void*)c->g_rec, (void*)c->g_halo, (void*)c->g_pairs,
-                    (void*)c->g_ws_scratch, (void*)c->g_tw_win, (void*)c->g_tw_l, (void*)c->g_k8_tw1, (void*)c->g_k8_tw2,
-                    (void*)c->g_k16_tw1, (void*)c->g_k16_gq, (void*)c->g_k16_tw2, (void*)c->g_k16_tws})
-        if (p) (void)hipFree(p);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t e : c->copy_ev)
         if (e) (void)hipEventDestroy(e);
-    for (void* p : {(void*)c->dt_tw, (void*)c->dt_pdb, c->dt_in, c->dt_out})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)c->sv_buoys, (void*)c->sv_pairs, c->sv_in, c->sv_out})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)c->d_spec_r, (void*)c->caf_rot, (void*)c->caf_lag, (void*)c->caf_frac, (void*)c->caf_peak,
-                    (void*)c->caf_dop, (void*)c->caf_nb})
-        if (p) (void)hipFree(p);
-    if (c->d_spec) (void)hipFree(c->d_spec);
-    if (c->d_tw1) (void)hipFree(c->d_tw1);
-    if (c->d_tw2) (void)hipFree(c->d_tw2);
-    if (c->d_trail) (void)hipFree(c->d_trail);
-    for (void* p : {(void*)c->d_tw1_8, (void*)c->d_tb8, (void*)c->d_tc8})
-        if (p) (void)hipFree(p);
-    if (c->d_items) (void)hipFree(c->d_items);
-    if (c->d_part_begin) (void)hipFree(c->d_part_begin);
-    if (c->d_in) (void)hipFree(c->d_in);
-    if (c->d_lag) (void)hipFree(c->d_lag);            // (d_frac / d_peak point into the same block)
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->rf_pairs) (void)hipFree(c->rf_pairs);
-    if (c->d_quality) (void)hipFree(c->d_quality);
-    for (DevStage* s : {&c->lb_stage, &c->band_stage}) {
-        if (s->d) (void)hipFree(s->d);
-        if (s->h) (void)hipHostFree(s->h);
+    for (DevStage* s : {&c->lb_stage, &c->band_stage})
         if (s->ev) (void)hipEventDestroy(s->ev);
-    }
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // every buffer frees itself (dev_buf.hpp); nothing of this ctx runs any more
 }
 
 int rmx_set_stream(rmx_ctx* c, void* hip_stream) {
@@ -1458,15 +1394,7 @@ int rmx_set_option(rmx_ctx* c, const char* key, long value) {
 
 // spectrum scratch of at least `windows` window slots (B * 64 KiB each)
 static int ensure_spec(rmx_ctx* c, long windows) {
-    const size_t nb = (size_t)windows * c->n_buoys * (8 * kThreads) * sizeof(float4);
-    if (nb <= c->spec_bytes) return RMX_OK;
-    RMX_HIP(c, hipStreamSynchronize(c->stream));
-    float4* nspec = nullptr;
-    RMX_HIP(c, hipMalloc((void**)&nspec, nb));
-    (void)hipFree(c->d_spec);
-    c->d_spec = nspec;
-    c->scratch_bytes += nb - c->spec_bytes;
-    c->spec_bytes = nb;
+    RMX_MEM(c->d_spec.reserve((size_t)windows * c->n_buoys * (8 * kThreads)));
     return RMX_OK;
 }
 
@@ -1474,64 +1402,41 @@ static int ensure_spec(rmx_ctx* c, long windows) {
 // call) come back as ONE copy into pinned memory + three memcpys instead of three pageable copies (each of which the
 // runtime stages and synchronises on its own); large ones keep the three direct copies.
 static constexpr size_t kPackedOutMax = 256 * 1024;   // bytes of all three arrays
+struct OutBlock {   // views into d_out: four sub-arrays a quarter of its capacity apart
+    int* lag;  float* frac;  float* peak;  int* dop;   // (dop: rmx_caf_batch's fourth array)
+};
+static OutBlock out_block(const rmx_ctx* c) {
+    float* base = c->d_out;
+    const size_t stride = c->d_out.capacity() / 4;
+    return {reinterpret_cast<int*>(base), base + stride, base + 2 * stride, reinterpret_cast<int*>(base + 3 * stride)};
+}
 static int ensure_out(rmx_ctx* c, size_t out_elems) {
-    if (c->d_out_elems >= out_elems) return RMX_OK;
-    if (c->d_lag) (void)hipFree(c->d_lag);
-    c->d_lag = nullptr; c->d_frac = nullptr; c->d_peak = nullptr; c->d_out_elems = 0;
     const size_t stride = (out_elems + 63) & ~(size_t)63;           // 256-byte aligned sub-arrays
-    RMX_HIP(c, hipMalloc((void**)&c->d_lag, 4 * stride * sizeof(float)));
-    c->d_frac = reinterpret_cast<float*>(c->d_lag) + stride;
-    c->d_peak = c->d_frac + stride;
-    c->d_dop = reinterpret_cast<int*>(c->d_peak + stride);     // (rmx_caf_batch's fourth array)
-    c->d_out_elems = out_elems;
+    RMX_MEM(c->d_out.reserve(4 * stride));
     return RMX_OK;
 }
 static int fetch_out(rmx_ctx* c, size_t out_elems, int32_t* lag_int, float* lag_frac, float* peak, int32_t* dop = nullptr) {
     const size_t nb = out_elems * sizeof(float);
-    const char* last = reinterpret_cast<char*>(dop ? (void*)c->d_dop : (void*)c->d_peak);
-    const size_t span = (size_t)(last - reinterpret_cast<char*>(c->d_lag)) + nb;
+    const OutBlock o = out_block(c);
+    const char* first = reinterpret_cast<const char*>(o.lag);
+    const char* last = reinterpret_cast<const char*>(dop ? (void*)o.dop : (void*)o.peak);
+    const size_t span = (size_t)(last - first) + nb;
     if (span <= kPackedOutMax) {
-        if (c->h_out_bytes < span) {
-            if (c->h_out) (void)hipHostFree(c->h_out);
-            c->h_out = nullptr; c->h_out_bytes = 0;
-            RMX_HIP(c, hipHostMalloc(&c->h_out, kPackedOutMax, hipHostMallocDefault));
-            c->h_out_bytes = kPackedOutMax;
-        }
-        RMX_HIP(c, hipMemcpyAsync(c->h_out, c->d_lag, span, hipMemcpyDeviceToHost, c->stream));
+        RMX_MEM(c->h_out.reserve(kPackedOutMax));
+        RMX_HIP(c, hipMemcpyAsync(c->h_out, o.lag, span, hipMemcpyDeviceToHost, c->stream));
         RMX_HIP(c, hipStreamSynchronize(c->stream));
-        const char* h = static_cast<const char*>(c->h_out);
+        const char* h = c->h_out;
         std::memcpy(lag_int, h, nb);
-        std::memcpy(lag_frac, h + (reinterpret_cast<char*>(c->d_frac) - reinterpret_cast<char*>(c->d_lag)), nb);
-        std::memcpy(peak, h + (reinterpret_cast<char*>(c->d_peak) - reinterpret_cast<char*>(c->d_lag)), nb);
-        if (dop) std::memcpy(dop, h + (reinterpret_cast<char*>(c->d_dop) - reinterpret_cast<char*>(c->d_lag)), nb);
+        std::memcpy(lag_frac, h + (reinterpret_cast<const char*>(o.frac) - first), nb);
+        std::memcpy(peak, h + (reinterpret_cast<const char*>(o.peak) - first), nb);
+        if (dop) std::memcpy(dop, h + (reinterpret_cast<const char*>(o.dop) - first), nb);
         return RMX_OK;
     }
-    if (dop) RMX_HIP(c, hipMemcpyAsync(dop, c->d_dop, nb, hipMemcpyDeviceToHost, c->stream));
-    RMX_HIP(c, hipMemcpyAsync(lag_int, c->d_lag, nb, hipMemcpyDeviceToHost, c->stream));
-    RMX_HIP(c, hipMemcpyAsync(lag_frac, c->d_frac, nb, hipMemcpyDeviceToHost, c->stream));
-    RMX_HIP(c, hipMemcpyAsync(peak, c->d_peak, nb, hipMemcpyDeviceToHost, c->stream));
+    if (dop) RMX_HIP(c, hipMemcpyAsync(dop, o.dop, nb, hipMemcpyDeviceToHost, c->stream));
+    RMX_HIP(c, hipMemcpyAsync(lag_int, o.lag, nb, hipMemcpyDeviceToHost, c->stream));
+    RMX_HIP(c, hipMemcpyAsync(lag_frac, o.frac, nb, hipMemcpyDeviceToHost, c->stream));
+    RMX_HIP(c, hipMemcpyAsync(peak, o.peak, nb, hipMemcpyDeviceToHost, c->stream));
     RMX_HIP(c, hipStreamSynchronize(c->stream));
-    return RMX_OK;
-}
-
-// the device block a host-pointer quality call writes its fourth output to (rmx_xcorr_batch_quality)
-static int ensure_quality(rmx_ctx* c, size_t elems) {
-    if (c->d_quality_elems >= elems) return RMX_OK;
-    if (c->d_quality) (void)hipFree(c->d_quality);
-    c->d_quality = nullptr; c->d_quality_elems = 0;
-    RMX_HIP(c, hipMalloc((void**)&c->d_quality, elems * sizeof(float)));
-    c->d_quality_elems = elems;
-    return RMX_OK;
-}
-
-// host windows: the ctx-owned device copy they go to
-static int ensure_in(rmx_ctx* c, size_t in_bytes) {
-    if (c->d_in_bytes >= in_bytes) return RMX_OK;
-    if (c->d_in) (void)hipFree(c->d_in);
-    c->d_in = nullptr;
-    c->d_in_bytes = 0;
-    RMX_HIP(c, hipMalloc(&c->d_in, in_bytes));
-    c->d_in_bytes = in_bytes;
     return RMX_OK;
 }
 
@@ -1541,21 +1446,8 @@ static int ensure_in(rmx_ctx* c, size_t in_bytes) {
 static int stage_to_device(rmx_ctx* c, DevStage* s, const int32_t* src, size_t elems) {
     if (!s->ev) RMX_HIP(c, hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
     RMX_HIP(c, hipEventSynchronize(s->ev));   // the previous call's copy out of the pinned buffer has finished
-    if (s->h_elems < elems) {
-        if (s->h) (void)hipHostFree(s->h);
-        s->h = nullptr; s->h_elems = 0;
-        RMX_HIP(c, hipHostMalloc((void**)&s->h, elems * sizeof(int32_t), hipHostMallocDefault));
-        s->h_elems = elems;
-    }
-    if (s->d_elems < elems) {
-        RMX_HIP(c, hipStreamSynchronize(c->stream));   // earlier kernels of this ctx may still read the old buffer
-        if (s->d) (void)hipFree(s->d);
-        c->scratch_bytes -= s->d_elems * sizeof(int32_t);
-        s->d = nullptr; s->d_elems = 0;
-        RMX_HIP(c, hipMalloc((void**)&s->d, elems * sizeof(int32_t)));
-        s->d_elems = elems;
-        c->scratch_bytes += elems * sizeof(int32_t);
-    }
+    RMX_MEM(s->h.reserve(elems));
+    RMX_MEM(s->d.reserve(elems));
     std::memcpy(s->h, src, elems * sizeof(int32_t));
     RMX_HIP(c, hipMemcpyAsync(s->d, s->h, elems * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     RMX_HIP(c, hipEventRecord(s->ev, c->stream));
@@ -1569,13 +1461,12 @@ static int stage_to_device(rmx_ctx* c, DevStage* s, const int32_t* src, size_t e
 // and the peaks.  The input is on the device (the caller's, or the ctx's copy the first pass made).
 static int quality_pass(rmx_ctx* c, const XcorrCall& req, const void* iq, int n_windows, int n_pairs, float* peak, unsigned flags) {
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
-    const void* d_iq = in_dev ? iq : c->d_in;
-    float* d_peak = out_dev ? peak : c->d_peak;
+    const void* d_iq = in_dev ? iq : c->d_in.get();
+    float* d_peak = out_dev ? peak : out_block(c).peak;
     const size_t out_elems = (size_t)n_windows * n_pairs;
     XcorrCall call = req;
     if (!out_dev) {
-        const int rc_q = ensure_quality(c, 4 * out_elems);
-        if (rc_q != RMX_OK) return rc_q;
+        RMX_MEM(c->d_quality.reserve(4 * out_elems));
         call.quality = c->d_quality;
     }
     int rc = c->generic ? rmx::generic_ensure(c, n_pairs, true, true)
@@ -1624,8 +1515,7 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
     const size_t in_bytes = (size_t)n_windows * c->n_buoys * c->n_samples * samp_bytes;
     const void* d_iq = iq;
     if (!in_dev) {
-        rc = ensure_in(c, in_bytes);
-        if (rc != RMX_OK) return rc;
+        RMX_MEM(c->d_in.reserve(in_bytes));
         // k_win: the copy is cut into sub-chunks issued on a second stream, each followed by its
         // kernel launch, so that copy k+1 travels while kernel k runs (below); otherwise one copy up front
         if (plan.pipelined) {
@@ -1646,9 +1536,10 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
     const size_t out_elems = (size_t)(n_windows / call.integ) * n_pairs * (size_t)rq.n_bands;
     if (!out_dev) {
         rc = ensure_out(c, out_elems);
-        if (rc == RMX_OK && call.qualified()) rc = ensure_quality(c, 4 * out_elems);
         if (rc != RMX_OK) return rc;
-        d_lag = c->d_lag; d_frac = c->d_frac; d_peak = c->d_peak;
+        if (call.qualified()) RMX_MEM(c->d_quality.reserve(4 * out_elems));
+        const OutBlock o = out_block(c);
+        d_lag = o.lag; d_frac = o.frac; d_peak = o.peak;
         if (call.qualified()) call.quality = c->d_quality;
     }
     // host-pointer results: the fourth array is queued in front of fetch_out, which waits for the stream
@@ -1690,7 +1581,7 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
                 constexpr bool U8 = decltype(U)::value;
                 auto go = [&](auto kern, auto... lb) {
                     return launch(c, kTkPair4096, kern, dim3(wgrid), dim3(kThreads), kLdsWinBytes, d_iq, c->d_spec, c->d_tw1, c->d_tw2,
-                                  c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, (const int4*)c->d_trail, c->stag_kwin, lb...);
+                                  c->n_buoys, wfirst, out_scale, d_lag, d_frac, d_peak, sc, reinterpret_cast<const int4*>(c->d_trail.get()), c->stag_kwin, lb...);
                 };
 #ifdef RMX_EXPERIMENTS
                 if (c->win8)
@@ -1943,38 +1834,25 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
     const size_t in_bytes = (size_t)n_windows * B * N * (u8 ? 2 : 8);
     const void* d_iq = iq;
     if (!in_dev) {
-        rc = ensure_in(c, in_bytes);
-        if (rc != RMX_OK) return rc;
+        RMX_MEM(c->d_in.reserve(in_bytes));
         RMX_HIP(c, hipMemcpyAsync(c->d_in, iq, in_bytes, hipMemcpyHostToDevice, c->stream));
         d_iq = c->d_in;
     }
     // phasor table [D][N]: exp(-2 pi i nu n) in double, rounded once to float
     std::vector<double> grid(doppler_cps, doppler_cps + n_dopplers);
-    if (grid != c->caf_grid || c->caf_rot_elems < (size_t)n_dopplers * N) {
+    if (!c->caf_rot.holds(grid)) {
         std::vector<float2> rot((size_t)n_dopplers * N);
         for (int d = 0; d < n_dopplers; ++d)
             for (int n = 0; n < N; ++n) {
                 const double a = -6.283185307179586476925286766559 * grid[d] * (double)n;
                 rot[(size_t)d * N + n] = make_float2((float)std::cos(a), (float)std::sin(a));
             }
-        RMX_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->caf_rot) (void)hipFree(c->caf_rot);
-        c->caf_rot = nullptr; c->caf_rot_elems = 0;
-        RMX_HIP(c, hipMalloc((void**)&c->caf_rot, rot.size() * sizeof(float2)));
-        RMX_HIP(c, hipMemcpy(c->caf_rot, rot.data(), rot.size() * sizeof(float2), hipMemcpyHostToDevice));
-        c->caf_rot_elems = rot.size();
-        c->caf_grid = grid;
+        RMX_MEM(c->caf_rot.refill(grid, rot));
     }
     const size_t caf_elems = batch_bins ? out_elems * (size_t)n_dopplers : out_elems;   // per-hypothesis results: [d][w][pair]
-    if (c->caf_out_elems < caf_elems) {
-        for (void* p : {(void*)c->caf_lag, (void*)c->caf_frac, (void*)c->caf_peak, (void*)c->caf_dop})
-            if (p) (void)hipFree(p);
-        c->caf_lag = nullptr; c->caf_frac = nullptr; c->caf_peak = nullptr; c->caf_dop = nullptr; c->caf_out_elems = 0;
-        RMX_HIP(c, hipMalloc((void**)&c->caf_lag, caf_elems * sizeof(int)));
-        RMX_HIP(c, hipMalloc((void**)&c->caf_frac, caf_elems * sizeof(float)));
-        RMX_HIP(c, hipMalloc((void**)&c->caf_peak, caf_elems * sizeof(float)));
-        c->caf_out_elems = caf_elems;
-    }
+    RMX_MEM(c->caf_lag.reserve(caf_elems));
+    RMX_MEM(c->caf_frac.reserve(caf_elems));
+    RMX_MEM(c->caf_peak.reserve(caf_elems));
     int *b_dop = dop_idx, *b_lag = lag_int;
     float *b_frac = lag_frac, *b_peak = peak;
     if (!out_dev) {
@@ -1982,17 +1860,12 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
             const int rc_out = ensure_out(c, out_elems);
             if (rc_out != RMX_OK) return rc_out;
         }
-        b_dop = c->d_dop; b_lag = c->d_lag; b_frac = c->d_frac; b_peak = c->d_peak;
+        const OutBlock o = out_block(c);
+        b_dop = o.dop; b_lag = o.lag; b_frac = o.frac; b_peak = o.peak;
     }
     float* b_dfrac = dop_frac;
     if (dop_frac && (!batch_bins || !out_dev)) {   // k_caf_select_fd's three neighbour rows, and dop_frac of a host-pointer call
-        if (c->caf_nb_elems < 4 * out_elems) {
-            RMX_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->caf_nb) (void)hipFree(c->caf_nb);
-            c->caf_nb = nullptr; c->caf_nb_elems = 0;
-            RMX_HIP(c, hipMalloc((void**)&c->caf_nb, 4 * out_elems * sizeof(float)));
-            c->caf_nb_elems = 4 * out_elems;
-        }
+        RMX_MEM(c->caf_nb.reserve(4 * out_elems));
         if (!out_dev) b_dfrac = c->caf_nb + 3 * out_elems;
     }
     // Per chunk of windows: the un-rotated spectra once, then per hypothesis the de-rotated spectra (the rotation
@@ -2075,13 +1948,8 @@ int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32
     }
     if (n_windows == 0) return RMX_OK;
     RMX_HIP(c, hipSetDevice(c->device));
-    if (!c->sv_buoys) RMX_HIP(c, hipMalloc((void**)&c->sv_buoys, rmx::kSolveMaxBuoys * 3 * sizeof(double)));
-    if (c->sv_pairs_cap < pl.size()) {
-        if (c->sv_pairs) (void)hipFree(c->sv_pairs);
-        c->sv_pairs = nullptr; c->sv_pairs_cap = 0;
-        RMX_HIP(c, hipMalloc((void**)&c->sv_pairs, pl.size() * sizeof(int)));
-        c->sv_pairs_cap = pl.size();
-    }
+    RMX_MEM(c->sv_buoys.reserve(rmx::kSolveMaxBuoys * 3));
+    RMX_MEM(c->sv_pairs.reserve(pl.size()));
     // (pageable host sources: these copies are synchronous with respect to the host buffers)
     RMX_HIP(c, hipMemcpyAsync(c->sv_buoys, buoy_xyz, (size_t)n_buoys * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     RMX_HIP(c, hipMemcpyAsync(c->sv_pairs, pl.data(), pl.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -2092,14 +1960,8 @@ int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32
     const float* d_lf = lag_frac;
     const float* d_wg = weight;
     if (!in_dev) {
-        const size_t need = ne * 4 * 3;
-        if (c->sv_in_bytes < need) {
-            if (c->sv_in) (void)hipFree(c->sv_in);
-            c->sv_in = nullptr; c->sv_in_bytes = 0;
-            RMX_HIP(c, hipMalloc(&c->sv_in, need));
-            c->sv_in_bytes = need;
-        }
-        char* base = (char*)c->sv_in;
+        RMX_MEM(c->sv_in.reserve(ne * 4 * 3));
+        char* base = c->sv_in;
         RMX_HIP(c, hipMemcpyAsync(base, lag_int, ne * 4, hipMemcpyHostToDevice, c->stream));
         RMX_HIP(c, hipMemcpyAsync(base + ne * 4, lag_frac, ne * 4, hipMemcpyHostToDevice, c->stream));
         if (weight) RMX_HIP(c, hipMemcpyAsync(base + ne * 8, weight, ne * 4, hipMemcpyHostToDevice, c->stream));
@@ -2110,14 +1972,8 @@ int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32
     double *d_pos = pos, *d_cost = cost;
     int* d_it = iters;
     if (!out_dev) {
-        const size_t need = (size_t)n_windows * (3 * 8 + 8 + 4);
-        if (c->sv_out_bytes < need) {
-            if (c->sv_out) (void)hipFree(c->sv_out);
-            c->sv_out = nullptr; c->sv_out_bytes = 0;
-            RMX_HIP(c, hipMalloc(&c->sv_out, need));
-            c->sv_out_bytes = need;
-        }
-        d_pos = (double*)c->sv_out;
+        RMX_MEM(c->sv_out.reserve((size_t)n_windows * (3 * 8 + 8 + 4)));
+        d_pos = reinterpret_cast<double*>(c->sv_out.get());
         d_cost = d_pos + (size_t)n_windows * 3;
         d_it = (int*)(d_cost + n_windows);
     }
@@ -2148,34 +2004,21 @@ int rmx_detect_batch(rmx_ctx* c, const void* iq, int n_windows, int n_samples, f
     if (n_windows == 0) return RMX_OK;
     RMX_HIP(c, hipSetDevice(c->device));
     const int N = n_samples;
-    if (c->dt_logn != logn) {
+    if (!c->dt_tw.holds(logn)) {
         std::vector<float2> t;
         rmx::gen::make_row_table(t, N);
-        if (c->dt_tw) { RMX_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->dt_tw); c->dt_tw = nullptr; }
-        RMX_HIP(c, hipMalloc((void**)&c->dt_tw, t.size() * sizeof(float2)));
-        RMX_HIP(c, hipMemcpy(c->dt_tw, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
-        c->dt_logn = logn;
+        RMX_MEM(c->dt_tw.refill(logn, t));
         int rc_l = allow_lds(c, (size_t)rmx::gen::lp(16384) * 8, det::d_fft_db<false>, det::d_fft_db<true>);
         if (rc_l == RMX_OK) rc_l = allow_lds(c, 16384 * 6 + 8192, det::d_peaks);
         if (rc_l != RMX_OK) return rc_l;
     }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
-    auto grow = [&](void** p, size_t* have, size_t need) -> int {
-        if (*have >= need) return RMX_OK;
-        RMX_HIP(c, hipStreamSynchronize(c->stream));
-        if (*p) (void)hipFree(*p);
-        *p = nullptr; *have = 0;
-        RMX_HIP(c, hipMalloc(p, need));
-        *have = need;
-        return RMX_OK;
-    };
-    int rc = grow((void**)&c->dt_pdb, &c->dt_pdb_bytes, (size_t)n_windows * N * sizeof(float));
-    if (rc != RMX_OK) return rc;
+    RMX_MEM(c->dt_pdb.reserve((size_t)n_windows * N));
+    int rc = RMX_OK;
     const void* d_iq = iq;
     if (!in_dev) {
         const size_t nb = (size_t)n_windows * N * (u8 ? 2 : 8);
-        rc = grow(&c->dt_in, &c->dt_in_bytes, nb);
-        if (rc != RMX_OK) return rc;
+        RMX_MEM(c->dt_in.reserve(nb));
         RMX_HIP(c, hipMemcpyAsync(c->dt_in, iq, nb, hipMemcpyHostToDevice, c->stream));
         d_iq = c->dt_in;
     }
@@ -2183,9 +2026,8 @@ int rmx_detect_batch(rmx_ctx* c, const void* iq, int n_windows, int n_samples, f
     float *d_pw = power_db, *d_snr = snr_db, *d_conf = confidence, *d_floor = noise_floor_db;
     const size_t per = (size_t)n_windows * max_peaks;
     if (!out_dev) {
-        rc = grow(&c->dt_out, &c->dt_out_bytes, per * 16 + (size_t)n_windows * 8);
-        if (rc != RMX_OK) return rc;
-        char* b = (char*)c->dt_out;
+        RMX_MEM(c->dt_out.reserve(per * 16 + (size_t)n_windows * 8));
+        char* b = c->dt_out;
         d_bin = (int*)b; d_pw = (float*)(b + per * 4); d_snr = (float*)(b + per * 8); d_conf = (float*)(b + per * 12);
         d_count = (int*)(b + per * 16); d_floor = (float*)(b + per * 16 + (size_t)n_windows * 4);
     }
@@ -2267,6 +2109,6 @@ int rmx_last_timing_kind(rmx_ctx* c, int kind, const char** name, float* ms, int
 // (the marker in front of the digest lets __graft_entry__._stale() read it out of the file without loading the library)
 const char* rmx_build_info(void) { return "RMX_BUILD_INFO source_digest=" RMX_SOURCE_DIGEST " arch=gfx950"; }
 
-size_t rmx_scratch_bytes(const rmx_ctx* c) { return c ? c->scratch_bytes : 0; }
+size_t rmx_scratch_bytes(const rmx_ctx* c) { return c ? c->mem.ledger : 0; }
 
 }  // extern "C"
