@@ -403,8 +403,8 @@ int rmx_xcorr_batch_quality(rmx_ctx* ctx, const void* iq, int n_windows, const i
  *               must not overlap lag_int, lag_frac or peak.
  * Definition: slot (w, m, q) is slot (w, q) of rmx_xcorr_batch_quality called with integrate = 1, band[w][m] (band[m] when
  *   shared) and otherwise the same arguments -- all four outputs, and that entry's parity statements (tests/
- *   bands_quality_ref.py stacks tests/refined_ref.py and tests/quality_ref.py per band).  There is no integration: the
- *   entry has no argument for it.
+ *   bands_quality_ref.py stacks tests/refined_ref.py and tests/quality_ref.py per band).  There is no integration here:
+ *   rmx_xcorr_batch_bands_integrated is this entry with `integrate`.
  * refine == 0 and quality == NULL IS rmx_xcorr_batch_bands: the same kernels, bit-identical outputs.
  * n_bands == 1 IS rmx_xcorr_batch_quality with integrate = 1 and the same arguments, bit-identical.
  * Otherwise the call runs exactly what rmx_xcorr_batch_bands runs -- one forward pass, the banded pair kernels -- and
@@ -423,6 +423,46 @@ int rmx_xcorr_batch_bands_quality(rmx_ctx* ctx, const void* iq, int n_windows, c
                                   const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
                                   const int32_t* lag_bounds, int bounds_per_window, int refine,
                                   int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
+
+/* Noncoherent integration under several bands per window: rmx_xcorr_batch_bands_quality plus `integrate`, for captures
+ * that hold several emitters AND come from free-running receivers or weak emitters.  ONE set of forward spectra per window
+ * serves every band and every group.
+ *   integrate   K >= 1; n_windows must be a positive multiple of K: G = n_windows / K groups of consecutive windows, as in
+ *               rmx_xcorr_batch_integrated.
+ *   band_cps    stays per WINDOW: float64 [n_windows][n_bands][2], or [n_bands][2] shared (bands_per_window == 0).  The
+ *               windows of one group may carry different bands in column m.
+ *   lag_bounds  NULL, int32 [n_pairs][2] (bounds_per_group == 0), or [G][n_pairs][2] per group; shared by the group's bands.
+ *   lag_int, lag_frac, peak   [G][n_bands][n_pairs].
+ *   quality     float32 [G][n_bands][n_pairs][4] (RMX_Q_...), or NULL.  It must not overlap lag_int, lag_frac or peak.
+ * Definition: slot (g, m, q) is slot (g, q) of rmx_xcorr_batch_quality called with the same integrate, weighting, lag_bounds
+ *   and refine, band_per_window = 1 and band[w] = band_cps[w][m] (band_cps[m] when shared) -- all four outputs, that entry's
+ *   parity statements unchanged, and its (K - 1) 2^-24 note on the in-order sum (tests/bands_integrated_ref.py stacks
+ *   tests/integrated_ref.py, refined_ref.py and quality_ref.py per band).
+ * integrate == 1 IS rmx_xcorr_batch_bands_quality; n_bands == 1 IS rmx_xcorr_batch_quality; refine == 0, quality == NULL and
+ *   integrate == 1 IS rmx_xcorr_batch_bands: each the same kernels, bit-identical outputs.  lag_int, lag_frac and peak of a
+ *   call with quality are bit-identical to the same call without it.
+ * Otherwise the forward kernels run once per (window, buoy) on all windows -- unmasked, or under PHAT whitened with the
+ *   full band -- and the pair kernels run in their banded integrating instantiations, pack <LagBounds, Integrate, BandSet>
+ *   (radio-mapper_amd/csrc/xspec_bands.hpp): a work item is (group, band, pair); it walks the group's real windows, masks
+ *   each window's product with band (window, m) and adds |r|^2 into per-thread accumulators in window order, then searches
+ *   the peak once.  k_quality and k_refine follow in the same pack.  A dropped bin is a stored +0 in the single-band call and
+ *   a skipped +0 here, and the K terms of a lag are added by one thread in window order on both sides, so away from the
+ *   four-step route with the default pair list from 6 buoys on (where the single-band integrated call's coarse peak comes
+ *   from g_rows_anchor, which the banded call never takes) slot (g, m, q) is bit-identical to rmx_xcorr_batch_quality with
+ *   band m; there the slot is held to the reference's bars.
+ * Refusals (RMX_E_INVAL, the text in rmx_last_error, nothing staged or written), in this order: integrate < 1, or n_windows
+ *   not a positive multiple of it; a NULL buffer (band_cps included); a misaligned device pointer; n_bands outside 1..64;
+ *   the weighting and the bands, the text naming band m of the REAL window w; the batch shape; the bounds, the text saying
+ *   "group" when integrate > 1; refine; quality overlapping another output.  Then the route: a chunk holds whole groups AND
+ *   at most the virtual windows and bytes the bands allow -- a K that no such chunk holds is refused, the text naming K,
+ *   n_bands and the chunk the bands left; never a silent split of a group.  RMX_E_UNSUPPORTED for the column tile of
+ *   rmx_xcorr_batch_integrated.
+ * Flags, custom pair lists and the staging of bands and bounds work as in rmx_xcorr_batch_bands. */
+int rmx_xcorr_batch_bands_integrated(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                                     int integrate,
+                                     const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
+                                     const int32_t* lag_bounds, int bounds_per_group, int refine,
+                                     int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
 
 /* Cross-ambiguity variant of the hot path (BASELINE configs[4]): for
  * every window and pair (i, j) the later buoy's window is de-rotated by each Doppler hypothesis,

@@ -491,10 +491,15 @@ struct GPair {
 // lags m = tid + e nthr, e < 16 (L <= 16 nthr for every L this kernel runs), in every window of the group; their |r|^2
 // are added in window order into acc[e], and the scan, the workgroup argmax and the parabola run once on the sums.
 // The three taps live in their owners' registers: the owners publish them (as the N = 4096 pair kernel does).
+// BS: empty, or one BandSet (the banded integrating instantiation, xspec_bands.hpp): gl is then an output ROW, group
+// gl / n_bands under band gl % n_bands, and first_group the chunk's first row; every window's product is formed on load
+// under the band of THAT window, a dropped bin loading nothing (+0), as the banded g_pair_small does.
+template <class... BS>
 __device__ __forceinline__ void pair_small_integ(const float2* __restrict__ spec, const float2* __restrict__ tw,
                                                  const GPair* __restrict__ pairs, int n_pairs, int n_buoys, int N, int logL,
                                                  long first_group, float out_scale, int* __restrict__ lag_int,
-                                                 float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K) {
+                                                 float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K,
+                                                 BS... bs_pack) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     float2* x = reinterpret_cast<float2*>(gsm);
     const int L = 1 << logL, tid = threadIdx.x, nthr = blockDim.x;
@@ -502,13 +507,30 @@ __device__ __forceinline__ void pair_small_integ(const float2* __restrict__ spec
     int* sk = reinterpret_cast<int*>(sv + nthr);
     const int gl = blockIdx.x / n_pairs, q = blockIdx.x % n_pairs;
     const GPair pr = pairs[q];
+    int gr = gl;
+    [[maybe_unused]] int band_m = 0;
+    if constexpr (sizeof...(BS) > 0) {
+        const BandSet bs = band_set_of(bs_pack...);
+        gr = gl / bs.n_bands;
+        band_m = gl - gr * bs.n_bands;
+    }
     float acc[kIntegMaxPerThread];
 #pragma unroll
     for (int e = 0; e < kIntegMaxPerThread; ++e) acc[e] = 0.0f;
     for (int kw = 0; kw < K; ++kw) {
-        const long wl = (long)gl * K + kw;
+        const long wl = (long)gr * K + kw;
         const float2* xi = spec + (wl * n_buoys + pr.i) * L;
         const float2* xj = spec + (wl * n_buoys + pr.j) * L;
+        if constexpr (sizeof...(BS) > 0) {
+            const XBand bd = band_of_window(band_set_of(bs_pack...), wl, band_m);
+            batched<4>(tid, L, nthr,
+                       [&](int n) -> float4 {
+                           if (!xband_keeps(bd, xbin_small(n, logL), L - 1)) return make_float4(0.f, 0.f, 0.f, 0.f);
+                           const float2 a = xj[n], b = xi[n];
+                           return make_float4(a.x, a.y, b.x, b.y);
+                       },
+                       [&](int n, float4 v) { x[lp(n)] = g_cmulc(make_float2(v.x, v.y), make_float2(v.z, v.w)); });
+        } else
         batched<4>(tid, L, nthr, [&](int n) -> float4 { const float2 a = xj[n], b = xi[n]; return make_float4(a.x, a.y, b.x, b.y); },
                    [&](int n, float4 v) { x[lp(n)] = g_cmulc(make_float2(v.x, v.y), make_float2(v.z, v.w)); });   // X_j conj(X_i)
         __syncthreads();
@@ -574,7 +596,11 @@ __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ 
                                                           float out_scale, int* __restrict__ lag_int,
                                                           float* __restrict__ lag_frac, float* __restrict__ peak,
                                                           LB... lb_pack) {
-    if constexpr (kIntegrating<LB...>) {   // (first_window: the chunk's first GROUP; spec_j == spec)
+    if constexpr (kIntegrating<LB...> && kBanded<LB...>) {   // (first_window: the chunk's first ROW, group * n_bands + band)
+        pair_small_integ(spec, tw, pairs, n_pairs, n_buoys, N, logL, first_window, out_scale, lag_int, lag_frac, peak,
+                         integ_bounds(lb_pack...), integ_windows(lb_pack...), band_set_of(lb_pack...));
+        return;
+    } else if constexpr (kIntegrating<LB...>) {   // (first_window: the chunk's first GROUP; spec_j == spec)
         pair_small_integ(spec, tw, pairs, n_pairs, n_buoys, N, logL, first_window, out_scale, lag_int, lag_frac, peak,
                          integ_bounds(lb_pack...), integ_windows(lb_pack...));
         return;
@@ -1847,10 +1873,10 @@ struct GTile {
 // adds the elements tid + e nthr (e < 16: a tile has at most 16 elements per thread at the thread counts the host
 // launches this instantiation with) into acc[e], and after the last window the sums go back into the image.  The
 // candidate scan, the halo, the tile record and g_final then see the summed |r|^2 where the plain kernel sees one
-// window's.
-template <int kColLogT, int L1C>
+// window's.  BANDED: behind the banded inverse rows, nb bands per window (else nb is not read).
+template <int kColLogT, int L1C, bool BANDED>
 __device__ __forceinline__ void cols_inv_integ(const float2* __restrict__ in, const float2* __restrict__ tw, int l1_arg, int l2,
-                                               GTile* __restrict__ rec, float* __restrict__ halo, LagBounds lb, int K) {
+                                               GTile* __restrict__ rec, float* __restrict__ halo, LagBounds lb, int K, int nb) {
     constexpr int kColT = 1 << kColLogT;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     float2* x = reinterpret_cast<float2*>(gsm);
@@ -1866,12 +1892,21 @@ __device__ __forceinline__ void cols_inv_integ(const float2* __restrict__ in, co
     __syncthreads();
     const int elems = L1 << kColLogT;
     const long gs = blockIdx.y;
-    const long slot0 = (gs / lb.n_pairs) * K * lb.n_pairs + gs % lb.n_pairs;   // the group's first window, this pair
+    long slot0 = (gs / lb.n_pairs) * K * lb.n_pairs + gs % lb.n_pairs;   // the group's first window, this pair
+    long wstep = lb.n_pairs;
+    if constexpr (BANDED) {
+        // gs / P is the row g nb + m, and the banded inverse rows left one product per VIRTUAL window, window-major:
+        // window g K + w under band m is slot ((g K + w) nb + m) P + q  (32-bit: a grid has at most 65535 rows of slots;
+        // uniform over the workgroup: kept in scalar registers)
+        const int orow = (int)blockIdx.y / lb.n_pairs, og = orow / nb;
+        slot0 = __builtin_amdgcn_readfirstlane((og * K * nb + (orow - og * nb)) * lb.n_pairs + (int)blockIdx.y % lb.n_pairs);
+        wstep = __builtin_amdgcn_readfirstlane(nb * lb.n_pairs);
+    }
     float acc[kIntegMaxPerThread];
 #pragma unroll
     for (int e = 0; e < kIntegMaxPerThread; ++e) acc[e] = 0.0f;
     for (int kw = 0; kw < K; ++kw) {
-        const float2* src = in + (slot0 + (long)kw * lb.n_pairs) * L;
+        const float2* src = in + (slot0 + (long)kw * wstep) * L;
         fft_dit_inv<kColLogT>(
             x, l1, twl, tid, nthr,
             make_src([&](int E) -> float2 { return src[((E >> kColLogT) << l2) + c0 + (E & (kColT - 1))]; }),
@@ -1922,12 +1957,14 @@ __device__ __forceinline__ void cols_inv_integ(const float2* __restrict__ in, co
 }
 
 // LB: empty, or one LagBounds (the bounded instantiation: candidates outside the slot's lag window are skipped; the LDS
-// image keeps every |r|^2, so the taps and the halo are those of the unbounded kernel), or <LagBounds, Integrate>
+// image keeps every |r|^2, so the taps and the halo are those of the unbounded kernel), or <LagBounds, Integrate>, or
+// <LagBounds, Integrate, BandSet> (the integrating one behind the banded inverse rows: only n_bands is read)
 template <int kColLogT, int L1C = 0, class... LB>
 __global__ __launch_bounds__(1024) void g_cols_inv(const float2* __restrict__ in, const float2* __restrict__ tw, int l1_arg,
                                                    int l2, GTile* __restrict__ rec, float* __restrict__ halo, LB... lb_pack) {
     if constexpr (kIntegrating<LB...>) {
-        cols_inv_integ<kColLogT, L1C>(in, tw, l1_arg, l2, rec, halo, integ_bounds(lb_pack...), integ_windows(lb_pack...));
+        cols_inv_integ<kColLogT, L1C, kBanded<LB...>>(in, tw, l1_arg, l2, rec, halo, integ_bounds(lb_pack...), integ_windows(lb_pack...),
+                                      integ_bands(lb_pack...));
         return;
     }
     constexpr bool BOUNDED = sizeof...(LB) > 0;

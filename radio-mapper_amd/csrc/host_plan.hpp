@@ -448,7 +448,8 @@ enum Route {
     kRouteSmallL,      // L <= small_maxl: g_fwd_small + g_pair_small per chunk
     kRouteFourStep     // longer: the column and row passes per chunk (route_rows_fused: g_rows_fused does both row passes)
 };
-enum RouteRefusal { kRouteOk = 0, kRefuseIntegChunk, kRefuseIntegTile };   // integrate > a chunk / column tile too large per thread
+enum RouteRefusal { kRouteOk = 0, kRefuseIntegChunk, kRefuseIntegTile };   // integrate > a chunk (RoutePlan::bands_chunk > 0: after
+                                                                             // the bands shrank it) / column tile too large per thread
 
 // what rmx_create / generic_init (and rmx_set_option) fixed for the ctx
 struct RouteCaps {
@@ -480,6 +481,8 @@ struct RoutePlan {
     int tail = 0;                // k_win: the largest partial round of any chunk that pays (the gate of route_wtail4096), or 0
     bool pipelined = false;      // k_win, host windows: the copy is cut into sub-chunks on a second stream
     RouteRefusal refused = kRouteOk;
+    int bands_chunk = 0;         // banded integrated call: the chunk plan_bands allows, before it is rounded down to whole groups
+                                 // (kRefuseIntegChunk with bands_chunk > 0: the bands shrank the chunk below one group)
 };
 
 constexpr int kHostSubChunk = 512;   // windows per copy/kernel step of the pipelined host-pointer path
@@ -610,10 +613,13 @@ inline RoutePlan plan_route(const RouteCaps& k, const RouteCall& a) {
     if (!a.weighted && k.wfused && !a.bounded) { p.route = kRouteWinFused; return p; }
     p.route = (1L << k.logL) <= k.small_maxl ? kRouteSmallL : kRouteFourStep;
     p.chunk = k.g_chunk / a.integ * a.integ;
-    // banded call (never integrated): the chunk whose virtual windows the per-slot buffers hold (plan_bands: the sizes)
+    // banded call: the chunk whose virtual windows the per-slot buffers hold (plan_bands: the sizes); banded AND integrated:
+    // that chunk first, then rounded down to whole groups -- both caps hold, and no group is ever split
     if (a.n_bands > 1) {
         const bool four_step = p.route == kRouteFourStep;
-        p.chunk = (int)plan_bands(k.g_chunk, W, a.n_bands, k.n_buoys, a.n_pairs, 1L << k.logL, four_step, 0, 0, 0).chunk;
+        const int bc = (int)plan_bands(k.g_chunk, W, a.n_bands, k.n_buoys, a.n_pairs, 1L << k.logL, four_step, 0, 0, 0).chunk;
+        p.chunk = bc / a.integ * a.integ;
+        if (a.integ > 1 && k.g_chunk >= a.integ) p.bands_chunk = bc;
     }   // (integrated call: a chunk holds whole groups -- never a silent split of a group)
     if (p.chunk == 0) p.refused = kRefuseIntegChunk;
     else if (a.integ > 1 && p.route == kRouteFourStep && k.col_tile > (long)k.integ_max_per_thread * k.cols_threads)

@@ -22,7 +22,7 @@ namespace host {
 struct RequestArgs {
     int n_buoys = 0, n_samples = 0, max_windows = 0;   // of the ctx
     bool grouped = false;           // the entries that take `integrate` (_integrated, _refined, _quality)
-    bool banded = false;            // rmx_xcorr_batch_bands(_quality): band_cps is [..][n_bands][2] and never NULL
+    bool banded = false;            // rmx_xcorr_batch_bands(_quality, _integrated): band_cps is [..][n_bands][2] and never NULL
     int n_bands = 0;                // as passed to a banded entry (0 from the single-band entries)
     bool bounds_required = false;   // rmx_xcorr_batch_bounded: lag_bounds is never NULL
     const void* iq = nullptr;
@@ -57,7 +57,7 @@ struct Request {
     long bound_rows = 0;
     bool bounds_per_window = false;    // one row of n_pairs intervals per window (group, virtual window), else one for all
     std::vector<int32_t> own_bounds;   // the full interval per pair (integrated call without bounds); each window's row
-                                       // n_bands times, window-major (banded call with per-window bounds)
+                                       // (group's) row n_bands times, window-major (banded call with per-window bounds)
 };
 
 // *err = the text; returns RMX_E_INVAL.  (512 bytes: what rmx_last_error has always kept of a text)
@@ -198,7 +198,7 @@ inline int check_alignment(unsigned flags, const void* iq, const OutArray* outs,
     return RMX_OK;
 }
 
-// Every check of the eight rmx_xcorr_batch* entries, in the order include/rmx.h promises, so an input with several bad
+// Every check of the nine rmx_xcorr_batch* entries, in the order include/rmx.h promises, so an input with several bad
 // arguments is refused for the same one whichever entry it came through: the grouped entries' (integrate, the group
 // count), a NULL buffer, a device pointer aligned to less than its element, n_bands, the weighted entry's, the batch
 // shape, the bounded entry's, refine, quality over another output.  RMX_OK with *r filled (r->empty: nothing to do), or
@@ -266,11 +266,14 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
         r->bound_rows = r->n_pairs;
         r->bounded = true;
     }
-    // the bounds are per (window, pair) and shared by the window's bands: per-window bounds go to the device once per
-    // VIRTUAL window (window-major), so the bounded kernels index them with the virtual window as they index their outputs
+    // the bounds are per (window, pair) -- per (group, pair) of an integrated call -- and shared by the bands: per-window
+    // bounds go to the device once per VIRTUAL window (window-major; per row group * n_bands + band, group-major), so the
+    // bounded kernels index them with the virtual window (the row) as they index their outputs.  (The full intervals made
+    // above are the shared form, one row for every group and band: nothing to replicate.)
     if (r->n_bands > 1 && r->bounded && r->bounds_per_window) {
-        r->own_bounds.resize((size_t)a.n_windows * r->n_bands * row);
-        for (long v = 0; v < (long)a.n_windows * r->n_bands; ++v)
+        const long out_rows = (long)(a.n_windows / K) * r->n_bands;
+        r->own_bounds.resize((size_t)out_rows * row);
+        for (long v = 0; v < out_rows; ++v)
             std::memcpy(&r->own_bounds[(size_t)v * row], a.lag_bounds + (size_t)(v / r->n_bands) * row, row * sizeof(int32_t));
         r->bounds = r->own_bounds.data();
         r->bound_rows *= r->n_bands;

@@ -17,6 +17,9 @@
 //                                   into the tile image and the tile record, the halo and g_final run as they are
 // The lag windows of an integrating kernel are indexed by GROUP (lag_bounds.hpp: w is the group, wstride the int32
 // elements per group).
+// A banded call may be integrated too (rmx_xcorr_batch_bands_integrated): xspec_bands.hpp adds the pack
+// <LagBounds, Integrate, BandSet>, whose work item is (group, band, pair) and whose lag windows and outputs are indexed by
+// the row group * n_bands + band.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -298,11 +298,18 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
 // TW1 in registers as that kernel does.  One more barrier per window than pair_body has per pair: the A<->B image of window w is read across
 // waves, and window w + 1 writes the exchange buffer again without the argmax's barriers in between.
 //   out arrays and lag windows are indexed [(first_group + gl) * n_pairs + item.out].
+// BS: empty, or one BandSet (the banded integrating instantiation, xspec_bands.hpp): gl is then an output ROW, group
+// gl / n_bands under band gl % n_bands, and first_group the chunk's first row; the spectra are the group's real windows',
+// and pair_body's 16-bit keep word zeroes the product -- built once when the band set is shared, rebuilt in front of
+// every window's product when the bands are per window.
+template <class... BS>
 __device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec, const float4* __restrict__ tw1_g,
                                                 const float2* __restrict__ tw2_g, const PairItem* __restrict__ items,
                                                 const int* __restrict__ part_begin, int n_parts, int n_buoys, int n_pairs,
                                                 int xcd_map, long first_group, float out_scale, int* __restrict__ lag_int,
-                                                float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K) {
+                                                float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K,
+                                                BS... bs_pack) {
+    constexpr bool BANDED = sizeof...(BS) > 0;
     extern __shared__ __attribute__((aligned(16))) char smem_ig[];   // (pair_body's carve)
     float2* xl = reinterpret_cast<float2*>(smem_ig);
     float2* tw2_lds = reinterpret_cast<float2*>(smem_ig + kLdsXchg);
@@ -334,7 +341,32 @@ __device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec,
     const int kbase = p ? (u - 1) : (u + kM - 1);
     const int it_begin = part_begin[part];
     const int it_end = part_begin[part + 1];
-    const long gbase = (long)gl * K * n_buoys;   // item of the group's first window, buoy 0 (chunk-local)
+    // banded: gl is a row (group gl / n_bands, band gl % n_bands); bit s of `keep` says whether this thread's slot s
+    // lies in the band of the window about to be multiplied (role C: xspec_weight.hpp's k_fwd map)
+    int gr = gl;
+    [[maybe_unused]] int band_m = 0;
+    [[maybe_unused]] unsigned keep = 0xffffu;
+    [[maybe_unused]] auto keep_of = [&](int kw) -> unsigned {
+        unsigned kp = 0xffffu;
+        if constexpr (BANDED) {
+            const BandSet bs = band_set_of(bs_pack...);
+            const XBand bd = band_of_window(bs, (long)gr * K + kw, band_m);
+            const int kb = RMX_XBIN_KFWD(p, u);
+            kp = 0u;
+#pragma unroll
+            for (int s = 0; s < 16; ++s) kp |= (xband_keeps(bd, kb + kXbinKfwdSlot * s, kL - 1) ? 1u : 0u) << s;
+        }
+        return kp;
+    };
+    [[maybe_unused]] bool band_per_window = false;
+    if constexpr (BANDED) {
+        const BandSet bs = band_set_of(bs_pack...);
+        gr = gl / bs.n_bands;
+        band_m = gl - gr * bs.n_bands;
+        band_per_window = bs.wstride != 0;
+        keep = keep_of(0);
+    }
+    const long gbase = (long)gr * K * n_buoys;   // item of the group's first window, buoy 0 (chunk-local)
     float4 sa[8], sb[8];   // X_i and X_j of the window about to be processed
     PairItem pi = items[it_begin < it_end ? it_begin : 0];
     auto request = [&](const PairItem& pr, int kw) {
@@ -360,6 +392,12 @@ __device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec,
                 const float4 b = sb[j];
                 v[2 * j] = make_float2(b.y * a.x - b.x * a.y, b.x * a.x + b.y * a.y);
                 v[2 * j + 1] = make_float2(b.w * a.z - b.z * a.w, b.z * a.z + b.w * a.w);
+            }
+            if constexpr (BANDED) {       // the band of THIS window: a dropped bin's product is +0
+                if (band_per_window) keep = keep_of(kw);
+#pragma unroll
+                for (int s = 0; s < 16; ++s)
+                    if (!((keep >> s) & 1u)) v[s] = make_float2(0.0f, 0.0f);
             }
             dft16(v);                     // k2 -> n0   (role C)
             mul_tw2(v, tw2_lds, u & 15);  // W_256^(k1*n0)
@@ -663,11 +701,15 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
         lag_int, lag_frac, peak, i_wrap
 
 // LB: empty, one LagBounds (the bounded instantiation), <LagBounds, Integrate> (the integrating one, integrate.hpp:
-// first_window is then the chunk's first GROUP; spec_j and i_wrap are not used), or <BandSet> / <LagBounds, BandSet> (the
-// banded ones, xspec_bands.hpp: first_window is then the chunk's first VIRTUAL window)
+// first_window is then the chunk's first GROUP; spec_j and i_wrap are not used), <BandSet> / <LagBounds, BandSet> (the
+// banded ones, xspec_bands.hpp: first_window is then the chunk's first VIRTUAL window), or <LagBounds, Integrate, BandSet>
+// (the banded integrating one: first_window is the chunk's first ROW, group * n_bands + band)
 template <class... LB>
 __global__ __launch_bounds__(kThreads, kIntegrating<LB...> ? 2 : 4) void k_pair_str(RMX_PAIR_ARGS, LB... lb) {
-    if constexpr (kIntegrating<LB...>) {
+    if constexpr (kIntegrating<LB...> && kBanded<LB...>) {
+        pair_body_integ(spec, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
+                        lag_int, lag_frac, peak, integ_bounds(lb...), integ_windows(lb...), band_set_of(lb...));
+    } else if constexpr (kIntegrating<LB...>) {
         pair_body_integ(spec, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
                         lag_int, lag_frac, peak, integ_bounds(lb...), integ_windows(lb...));
     } else if constexpr (kBanded<LB...>) {

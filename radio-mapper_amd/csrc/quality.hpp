@@ -42,7 +42,9 @@ constexpr int kQualSums = 5;   // A, B, C, D, F
 
 // The trailing pack is empty for the plain kernel and <BandSet> for the banded one, as k_refine's (refine.hpp): output row
 // gl is a virtual window, the spectra are real window gl / n_bands', and a position whose bin the band drops adds nothing
-// -- in the weighted call it is a stored zero, which adds +0 to each of the five sums.
+// -- in the weighted call it is a stored zero, which adds +0 to each of the five sums.  <LagBounds, Integrate, BandSet>:
+// the banded pack of an integrated call, as k_refine's: row gl = group * n_bands + m walks its group's a.k windows, each
+// under band (window, m), and thread 0 adds the per-window terms in window order as the plain kernel does.
 template <int LAYOUT, class... P>
 __global__ __launch_bounds__(kRefThreads) void k_quality(QualityArgs a, const float* __restrict__ peak, float* __restrict__ quality,
                                                          P... tail) {
@@ -56,14 +58,21 @@ __global__ __launch_bounds__(kRefThreads) void k_quality(QualityArgs a, const fl
     float ee = 0.0f, sum_c = 0.0f, sum_d = 0.0f, sum_f = 0.0f;   // thread 0: over the windows, in window order
     [[maybe_unused]] XBand bd{0, 0u};
     [[maybe_unused]] long w_real = 0;
-    if constexpr (kBanded<P...>) {
+    if constexpr (kBanded<P...> && !kIntegrating<P...>) {
         const BandSet bs = band_set_of(tail...);
         bd = band_of_virtual(bs, gl);
         w_real = band_real_window(bs, gl);
     }
     for (int w = 0; w < a.k; ++w) {
         long wl = (long)gl * a.k + w;
-        if constexpr (kBanded<P...>) wl = w_real;   // (a.k == 1: a banded call is never integrated)
+        if constexpr (kBanded<P...> && kIntegrating<P...>) {   // row gl = group * n_bands + m: the group's window w under ITS band m
+            const BandSet bs = band_set_of(tail...);
+            const int g = gl / bs.n_bands;
+            wl = (long)g * a.k + w;
+            bd = band_of_window(bs, wl, gl - g * bs.n_bands);
+        } else if constexpr (kBanded<P...>) {
+            wl = w_real;   // (the banded pack of a call that is not integrated: a.k == 1)
+        }
         const float4* xi = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.i) * L);
         const float4* xj = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.j) * L);
         float acc[kQualSums];

@@ -92,6 +92,10 @@ __device__ __forceinline__ void ref_next_step(float ss, float sc, float2& up, fl
 // sincospif pairs are not evaluated.  The thread-to-position map, the order of a thread's additions and the reduction
 // tree are the plain kernel's, and what is skipped is what the weighted call adds as +-0 to sums that start at +0:
 // slot (w, m, q) carries the bits of the refined call with band[w][m].
+// <LagBounds, Integrate, BandSet> is the banded pack of an integrated call (rmx_xcorr_batch_bands_integrated): output row
+// gl = group * n_bands + m walks the a.k real windows of its group in window order, each under band (window, m); the sums,
+// the fixed tree and the tap rule are those of the plain kernel with a.k > 1.  Of that pack only
+// the band set is read: the lag intervals and K are a.lb and a.k.
 template <int U, int LAYOUT, class... P>
 __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __restrict__ lag_int, float* __restrict__ lag_frac,
                                                         float* __restrict__ peak, P... tail) {
@@ -108,14 +112,21 @@ __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __res
     float fsum = 0.0f;   // thread u < T: sum over the windows of |r_w(lag0 + (u - U) / U)|^2, unscaled
     [[maybe_unused]] XBand bd{0, 0u};
     [[maybe_unused]] long w_real = 0;
-    if constexpr (kBanded<P...>) {
+    if constexpr (kBanded<P...> && !kIntegrating<P...>) {
         const BandSet bs = band_set_of(tail...);
         bd = band_of_virtual(bs, gl);
         w_real = band_real_window(bs, gl);
     }
     for (int w = 0; w < a.k; ++w) {
         long wl = (long)gl * a.k + w;
-        if constexpr (kBanded<P...>) wl = w_real;   // (a.k == 1: a banded call is never integrated)
+        if constexpr (kBanded<P...> && kIntegrating<P...>) {   // row gl = group * n_bands + m: the group's window w under ITS band m
+            const BandSet bs = band_set_of(tail...);
+            const int g = gl / bs.n_bands;
+            wl = (long)g * a.k + w;
+            bd = band_of_window(bs, wl, gl - g * bs.n_bands);
+        } else if constexpr (kBanded<P...>) {
+            wl = w_real;   // (the banded pack of a call that is not integrated: a.k == 1)
+        }
         const float4* xi = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.i) * L);
         const float4* xj = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.j) * L);
         float2 acc[T];

@@ -104,6 +104,7 @@ struct rmx_ctx {
         decltype(&rmx::gen::g_cols_inv<4>) cols_inv = nullptr;
         decltype(&rmx::gen::g_cols_inv<4, 0, rmx::LagBounds>) cols_inv_lb = nullptr;                    // its bounded instantiation (rmx_xcorr_batch_bounded)
         decltype(&rmx::gen::g_cols_inv<4, 0, rmx::LagBounds, rmx::Integrate>) cols_inv_int = nullptr;   // its integrating one (integrate.hpp)
+        decltype(&rmx::gen::g_cols_inv<4, 0, rmx::LagBounds, rmx::Integrate, rmx::BandSet>) cols_inv_int_bs = nullptr;   // ... behind the banded inverse rows
         decltype(&rmx::gen::g_cols_fwd<false, 4>) cols_fwd[2] = {nullptr, nullptr};                     // [u8]
         decltype(&rmx::gen::g_rows<true, false>) rows_fwd = nullptr;   // g_rows compiled for this row length (or the run-time one)
         decltype(&rmx::gen::g_rows<true, false, false, 0, rmx::XWeight>) rows_fwd_wt = nullptr;         // its weighted instantiation
@@ -230,7 +231,8 @@ struct XcorrCall {
                                              // then walk n_bands virtual windows per window, lb and the outputs are per virtual
                                              // window, and wt is the full band (PHAT) or none
     int integ = 1;                           // windows per group (rmx_xcorr_batch_integrated): the bounds and the outputs
-                                             // are then per GROUP, the bands stay per window, a chunk holds whole groups
+                                             // are then per GROUP, the bands stay per window, a chunk holds whole groups;
+                                             // with bs (rmx_xcorr_batch_bands_integrated) per row group * n_bands + band
     int refine = 0;                          // U of rmx_xcorr_batch_refined: k_refine behind every chunk's pair kernels, or 0
     bool bounded() const { return lb.b != nullptr; }         // the bounded instantiations of the peak-searching kernels
     bool integrated() const { return integ > 1; }            // the integrating instantiations of the pair kernels
@@ -459,8 +461,9 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, i
     a.row_bits = sv.row_bits;
     a.k = call.integ;
     a.scale = std::ldexp(1.0f, -logL - 2 * unit_log2);   // (1 / L) over the two stored forward scales 2^unit_log2
-    // banded call (never integrated): one slot per VIRTUAL window, rows and lag intervals from virtual window w0 * n_bands
-    // on, the spectra per real window; the band set's w0 is the chunk's first real window
+    // banded call: one slot per VIRTUAL window, rows and lag intervals from virtual window w0 * n_bands on, the spectra per
+    // real window; the band set's w0 is the chunk's first real window.  Banded and integrated: one slot per row
+    // group * n_bands + band, from row (w0 / K) * n_bands on, the kernel walking the group's real windows
     const int nb = call.banded() ? call.bs.n_bands : 1;
     a.first_out *= nb;
     BandSet bs = call.bs;
@@ -469,6 +472,9 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, i
     // k_refine<U, layout>; U was checked by the entry (16 is the last it admits), the four-step layout is the last one
     return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
         return with_one_of<2, 4, 8, 16>(call.refine, [&](auto u) {
+            if (call.banded() && call.integrated())
+                return launch(c, kTkRefine, k_refine<decltype(u)::value, decltype(lay)::value, LagBounds, Integrate, BandSet>, dim3(grid),
+                              dim3(kRefThreads), 0, a, d_lag, d_frac, d_peak, call.lb, Integrate{call.integ}, bs);
             if (call.banded())
                 return launch(c, kTkRefine, k_refine<decltype(u)::value, decltype(lay)::value, BandSet>, dim3(grid), dim3(kRefThreads), 0, a,
                               d_lag, d_frac, d_peak, bs);
@@ -501,6 +507,9 @@ static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, 
     bs.w0 = w0;
     const unsigned grid = (unsigned)(wc / call.integ * nb * n_pairs);
     return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
+        if (call.banded() && call.integrated())
+            return launch(c, kTkQuality, k_quality<decltype(lay)::value, LagBounds, Integrate, BandSet>, dim3(grid), dim3(kRefThreads), 0, a,
+                          d_peak, call.quality, call.lb, Integrate{call.integ}, bs);
         if (call.banded())
             return launch(c, kTkQuality, k_quality<decltype(lay)::value, BandSet>, dim3(grid), dim3(kRefThreads), 0, a, d_peak, call.quality, bs);
         return launch(c, kTkQuality, k_quality<decltype(lay)::value>, dim3(grid), dim3(kRefThreads), 0, a, d_peak, call.quality);
@@ -531,7 +540,8 @@ static size_t gen_rows_lds(const rmx_ctx* c, int R) {   // rows + per-row twiddl
 // ---- the selection tables: a run-time length -> the instantiation compiled for it (with_one_of: a length outside a
 // list gets the list's last entry; 0 stands for the run-time-length instantiation) -----------------------------------
 // column kernels with the column length compiled in (16-column tiles, the default thread count), else the run-time ones
-// (LB: empty, or LagBounds / LagBounds, Integrate for the bounded / integrating instantiations of the same set)
+// (LB: empty, or LagBounds / LagBounds, Integrate / LagBounds, Integrate, BandSet for the bounded / integrating / banded
+// integrating instantiations of the same set)
 template <class... LB>
 static auto cols_inv_fn(int l1, int lt, int thr) {
     using namespace gen;
@@ -632,6 +642,7 @@ static GenericKernels pick_generic_kernels(int n_buoys, int logL, int logL1, int
         k.cols_inv = cols_inv_fn<>(logL1, col_log_t, cols_threads);
         k.cols_inv_lb = cols_inv_fn<LagBounds>(logL1, col_log_t, cols_threads);
         k.cols_inv_int = cols_inv_fn<LagBounds, Integrate>(logL1, col_log_t, cols_threads);
+        k.cols_inv_int_bs = cols_inv_fn<LagBounds, Integrate, BandSet>(logL1, col_log_t, cols_threads);
         k.cols_fwd[0] = cols_fwd_fn<false>(logL1, col_log_t, cols_threads);
         k.cols_fwd[1] = cols_fwd_fn<true>(logL1, col_log_t, cols_threads);
         k.rows_fwd = rows_fwd_fn<>(logL2, rows_tpr);
@@ -685,7 +696,7 @@ static int generic_init(rmx_ctx* c) {
         RMX_MEM(c->g_tw.assign(t));
         c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, 0, 0, 0, 0, 0, c->knobs);
         rc = allow_lds(c, (size_t)gen::lp(L) * 8 + 1024 * 8, g_pair_small<>, g_pair_small<LagBounds>, g_pair_small<LagBounds, Integrate>,
-                       g_pair_small<BandSet>, g_pair_small<LagBounds, BandSet>, g_fwd_small<false>, g_fwd_small<true>,
+                       g_pair_small<LagBounds, Integrate, BandSet>, g_pair_small<BandSet>, g_pair_small<LagBounds, BandSet>, g_fwd_small<false>, g_fwd_small<true>,
                        g_fwd_small<false, XWeight>, g_fwd_small<true, XWeight>);
         for (int d = 0; d < 2 && rc == RMX_OK; ++d) rc = allow_lds(c, c->gk.wf_lds[d], c->gk.wf[d][0], c->gk.wf[d][1]);
         if (rc) return rc;
@@ -712,7 +723,7 @@ static int generic_init(rmx_ctx* c) {
                                      gen_cols_threads(c, c->g_logL1), gen_rows_tpr(c, 1 << c->g_logL2), c->knobs);
         const GenericKernels& k = c->gk;
         const size_t rows_lds = gen_rows_lds(c, 1 << c->g_logL2);
-        rc = allow_lds(c, gen_cols_lds(c, c->g_logL1), k.cols_inv, k.cols_inv_lb, k.cols_inv_int, k.cols_fwd[0], k.cols_fwd[1]);
+        rc = allow_lds(c, gen_cols_lds(c, c->g_logL1), k.cols_inv, k.cols_inv_lb, k.cols_inv_int, k.cols_inv_int_bs, k.cols_fwd[0], k.cols_fwd[1]);
         // (the run-time-length row kernels too, whichever the tables chose)
         if (rc == RMX_OK)
             rc = allow_lds(c, rows_lds, g_rows<true, false, false>, g_rows<false, true, true>, k.rows_fwd, k.rows_fwd_wt, k.rows_inv, k.rows_inv_bs,
@@ -905,6 +916,8 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
             return launch(c, kTkPairSmall, kern, dim3(grid), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, c->g_spec, spec_j, c->g_tw,
                           c->g_pairs, n_pairs, B, N, logL, first, out_scale, d_lag, d_frac, d_peak, tail...);
         };
+        if (call.integrated() && call.banded())   // one workgroup per (group, band, pair); the bounds per row group * n_bands + band
+            return go(g_pair_small<LagBounds, Integrate, BandSet>, slots / call.integ, v0 / call.integ, call.lb, Integrate{call.integ}, bs);
         if (call.integrated())   // one workgroup per (group, pair); w0 and wc are whole groups, the bounds per group
             return go(g_pair_small<LagBounds, Integrate>, slots / call.integ, (long)(w0 / call.integ), call.lb, Integrate{call.integ});
         if (call.banded()) return call.bounded() ? go(g_pair_small<LagBounds, BandSet>, slots, v0, call.lb, bs) : go(g_pair_small<BandSet>, slots, v0, bs);
@@ -947,15 +960,20 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     if (rc != RMX_OK) return rc;
     // integrated call: the column pass sums the |r|^2 of a group's K product slots tile by tile and leaves one tile record
     // and halo per (group, pair) slot; g_final then reduces those slots as it reduces a window's (the bounds are per group:
-    // slot -> group w0 / K + slot / P).  Otherwise K = 1: slot -> window w0 + slot / P, pair slot % P.
+    // slot -> group w0 / K + slot / P).  Otherwise K = 1: slot -> window w0 + slot / P, pair slot % P.  Banded and integrated:
+    // the banded rows above left one product per virtual window, and the column pass sums the K products of (group, band)
+    // where they lie, n_bands * P slots apart; a slot is then (row w0 / K * n_bands + slot / P, pair).
     const int oslots = slots / call.integ;
     LagBounds lb = call.lb;
-    lb.w0 = v0 / call.integ;   // (banded: the bounds are per virtual window)
+    lb.w0 = v0 / call.integ;   // (banded: the bounds are per virtual window; w0 is a multiple of K)
     lb.n_pairs = n_pairs;
     auto cols = [&](auto kern, auto... tail) {
         return launch(c, kTkColsInv, kern, dim3(ntiles, oslots), dim3(cthr), clds, c->g_prod, c->g_tw1, l1, l2, c->g_rec, c->g_halo, tail...);
     };
-    rc = call.integrated() ? cols(k.cols_inv_int, lb, Integrate{call.integ}) : call.bounded() ? cols(k.cols_inv_lb, lb) : cols(k.cols_inv);
+    rc = call.integrated() && call.banded() ? cols(k.cols_inv_int_bs, lb, Integrate{call.integ}, bs)
+         : call.integrated()                ? cols(k.cols_inv_int, lb, Integrate{call.integ})
+         : call.bounded()                   ? cols(k.cols_inv_lb, lb)
+                                            : cols(k.cols_inv);
     if (rc != RMX_OK) return rc;
     auto reduce = [&](auto kern, auto... tail) {
         return launch(c, kTkFinal, kern, dim3(oslots), dim3(64), 0, N, l1, l2, lt, c->g_rec, c->g_halo, ntiles, oslots, lb.w0 * n_pairs,
@@ -1007,6 +1025,15 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
                       c->d_items, c->d_part_begin, n_parts, c->n_buoys, n_pairs, xcd_map, first, out_scale, d_lag, d_frac, d_peak, 0, i_wrap,
                       lb...);
     };
+    if (call.integrated() && call.banded()) {
+        // the banded integrating instantiation: one work item per (group, band, pair), rows group-major from
+        // (w0 / K) * n_bands on (wc counts the chunk's virtual windows here: whole groups times n_bands)
+        const int rows = wc / call.integ;
+        BandSet bs = call.bs;
+        bs.w0 = w0;
+        return str(k_pair_str<LagBounds, Integrate, BandSet>, rows, (rows % 8 == 0) ? 1 : 0, first / call.integ, 0, call.lb,
+                   Integrate{call.integ}, bs);
+    }
     if (call.integrated()) {
         // always the streaming kernel's integrating instantiation, one work item per (group, pair); w0 and wc are whole
         // groups, the bounds per group
@@ -1122,8 +1149,11 @@ static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_
 }
 
 // a refusal of the planner as the caller reads it
-static int route_refusal(rmx_ctx* c, const host::RoutePlan& plan, const host::RouteCaps& k, int integ) {
+static int route_refusal(rmx_ctx* c, const host::RoutePlan& plan, const host::RouteCaps& k, int integ, int n_bands) {
     if (plan.refused == host::kRouteOk) return RMX_OK;
+    if (plan.refused == host::kRefuseIntegChunk && plan.bands_chunk > 0)
+        return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the chunk of %d windows that n_bands = %d bands shrank this "
+                    "ctx's chunk of %d windows to: a group is never split", integ, plan.bands_chunk, n_bands, k.g_chunk);
     if (plan.refused == host::kRefuseIntegChunk)
         return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
                     integ, k.generic ? k.g_chunk : k.chunk_windows);
@@ -1147,7 +1177,7 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps
     // the whole-window kernels and k16 keep no per-window state in HBM
     const bool per_transform = plan.route == kRouteSmallL || plan.route == kRouteFourStep;
     int rc = ensure(per_transform, per_transform);
-    if (rc == RMX_OK) rc = route_refusal(c, plan, caps, call.integ);
+    if (rc == RMX_OK) rc = route_refusal(c, plan, caps, call.integ, rq.n_bands);
     if (rc != RMX_OK) return rc;
     if (per_transform) return run_chunks(c, call, caps, d_iq, 0, rq.n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
     if (plan.route == kRouteK16) return k16_batch(c, call, d_iq, rq.n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
@@ -1292,7 +1322,8 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
         // every instantiation of the N = 4096 kernels: plain, weighted (rmx_xcorr_batch_weighted: k_fwd) and bounded
         // (rmx_xcorr_batch_bounded: the peak-searching ones)
         int rc_l = allow_lds(c, kLdsBytes, k_fwd<false>, k_fwd<true>, k_fwd<false, XWeight>, k_fwd<true, XWeight>, k_pair_str<>,
-                             k_pair_str<LagBounds>, k_pair_str<BandSet>, k_pair_str<LagBounds, BandSet>);
+                             k_pair_str<LagBounds>, k_pair_str<BandSet>, k_pair_str<LagBounds, BandSet>,
+                             k_pair_str<LagBounds, Integrate, BandSet>);
         if (rc_l == RMX_OK)
             rc_l = allow_lds(c, kLdsResBytes, k_pair_res<>, k_pair_res<LagBounds>, k_pair_res<BandSet>, k_pair_res<LagBounds, BandSet>);
         if (rc_l == RMX_OK) rc_l = allow_lds(c, kLdsWinBytes, k_win<false>, k_win<true>, k_win_lb<false>, k_win_lb<true>);
@@ -1508,7 +1539,7 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
     const host::RoutePlan plan = host::plan_route(caps, rq);
     if (!c->generic) c->pairs_per_block = plan.ppb;
     int rc = build_plan(c, pairs, n_pairs);
-    if (rc == RMX_OK && !c->generic) rc = route_refusal(c, plan, caps, call.integ);
+    if (rc == RMX_OK && !c->generic) rc = route_refusal(c, plan, caps, call.integ, rq.n_bands);
     if (rc != RMX_OK) return rc;
 
     const size_t samp_bytes = u8 ? 2 : 8;
@@ -1626,7 +1657,7 @@ static int describe_call(rmx_ctx* c, const host::Request& rq, XcorrCall* call) {
     return RMX_OK;
 }
 
-// What all eight correlation entries do, and none of them through another: hand their arguments to host::check_request
+// What all nine correlation entries do, and none of them through another: hand their arguments to host::check_request
 // -- every refusal, in one order whichever entry the call came through --, copy the bands (as signed bins) and the lag
 // intervals into ctx-owned device buffers, describe the call in an XcorrCall and dispatch it.  The plain call is
 // integrate = 1, no band, no weighting, no bounds.
@@ -1768,6 +1799,25 @@ int rmx_xcorr_batch_bands_quality(rmx_ctx* c, const void* iq, int n_windows, con
                                   int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
     host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, bands_per_window,
                                         weighting, lag_bounds, bounds_per_window);
+    a.banded = true;
+    a.n_bands = n_bands;
+    a.refine = refine;
+    a.quality = quality;
+    return xcorr_request(c, a, flags);
+}
+
+// rmx_xcorr_batch_bands_quality with one peak search per (group of `integrate` consecutive windows, band): the banded
+// integrating instantiations of the pair kernels, of k_quality and of k_refine (xspec_bands.hpp) walk each group's real
+// windows under the band of each window.  integrate == 1 IS rmx_xcorr_batch_bands_quality; n_bands == 1 IS
+// rmx_xcorr_batch_quality.
+int rmx_xcorr_batch_bands_integrated(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs, int integrate,
+                                     const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
+                                     const int32_t* lag_bounds, int bounds_per_group, int refine,
+                                     int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
+    host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, bands_per_window,
+                                        weighting, lag_bounds, bounds_per_group);
+    a.grouped = true;
+    a.integrate = integrate;
     a.banded = true;
     a.n_bands = n_bands;
     a.refine = refine;

@@ -15,12 +15,21 @@
 // for each of its bands), so the bounded code of a kernel indexes them with v as it indexes everything else.
 // A dropped bin is exactly +0, which is what the product of two masked spectra is, and a kept bin is the product of the
 // same two stored values: slot (w, m, q) carries the bits of the weighted call with band[w][m].
+//
+// Banded AND integrated (rmx_xcorr_batch_bands_integrated): the third pack, <LagBounds, Integrate, BandSet>, on the
+// integrating pair kernels (integrate.hpp) and on k_refine / k_quality.  A work item is an output ROW r = g n_bands + m
+// -- group g, band m -- and a pair: it walks the real windows g K ... g K + K - 1 of the chunk, masks each window's
+// product with band (window, m) -- looked up per WINDOW: the windows of a group may carry different bands in column m --
+// and adds |r|^2 in window order into the accumulators of the integrating kernel.  The lag interval and the outputs are
+// row r's.  A skipped +0 here is a stored +0 in the single-band integrated call with band[.][m], and the K terms of a lag
+// are added by one thread in window order on both sides: slot (g, m, q) carries that call's bits.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
+#include "integrate.hpp"
 #include "lag_bounds.hpp"
 #include "xspec_weight.hpp"
 
@@ -39,8 +48,16 @@ template <>
 struct band_pack<BandSet> : std::true_type {};
 template <>
 struct band_pack<LagBounds, BandSet> : std::true_type {};
+template <>
+struct band_pack<LagBounds, Integrate, BandSet> : std::true_type {};
 template <class... P>
 inline constexpr bool kBanded = band_pack<P...>::value;
+
+// the banded integrating pack is an integrating pack (integrate.hpp)
+template <>
+struct integ_pack<LagBounds, Integrate, BandSet> : std::true_type {};
+__device__ __forceinline__ LagBounds integ_bounds(LagBounds lb, Integrate, BandSet) { return lb; }
+__device__ __forceinline__ int integ_windows(LagBounds, Integrate ig, BandSet) { return ig.k; }
 
 // does the pack start with a LagBounds (the bounded, the integrating and the bounded banded instantiations)?
 template <class... P>
@@ -53,11 +70,21 @@ inline constexpr bool kHasBounds = bounds_pack<P...>::value;
 __device__ __forceinline__ LagBounds lag_bounds_of(BandSet) { return LagBounds{nullptr, 0, 0, 0}; }
 __device__ __forceinline__ BandSet band_set_of(BandSet bs) { return bs; }
 __device__ __forceinline__ BandSet band_set_of(LagBounds, BandSet bs) { return bs; }
+__device__ __forceinline__ BandSet band_set_of(LagBounds, Integrate, BandSet bs) { return bs; }
+// bands per window of an integrating pack: the row stride of its work items (1 without a band set)
+__device__ __forceinline__ int integ_bands(LagBounds, Integrate) { return 1; }
+__device__ __forceinline__ int integ_bands(LagBounds, Integrate, BandSet bs) { return bs.n_bands; }
 
 // virtual window v of the launch -> the real window (chunk-local) whose spectra it correlates / its band
 __device__ __forceinline__ int band_real_window(const BandSet& bs, int v) { return v / bs.n_bands; }
 __device__ __forceinline__ XBand band_of_virtual(const BandSet& bs, int v) {
     const int wr = v / bs.n_bands, m = v - wr * bs.n_bands;
+    const int* p = bs.bins + (bs.w0 + wr) * bs.wstride + 2 * m;
+    return XBand{p[0], (unsigned)(p[1] - p[0])};
+}
+
+// banded integrating kernels: band m of real window wr (chunk-local) -- per window, whatever the group
+__device__ __forceinline__ XBand band_of_window(const BandSet& bs, long wr, int m) {
     const int* p = bs.bins + (bs.w0 + wr) * bs.wstride + 2 * m;
     return XBand{p[0], (unsigned)(p[1] - p[0])};
 }

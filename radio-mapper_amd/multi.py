@@ -165,26 +165,45 @@ class MultiXcorrEngine:
         return self._run(iq.shape[0], block_call, n_out, dtypes, P, tails=tails)
 
     def correlate_bands(self, iq: np.ndarray, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
-                        whiten: bool = False, refine: int = 0, quality: bool = False):
+                        whiten: bool = False, refine: int = 0, quality: bool = False, integrate: int = 1):
         """XcorrEngine.correlate_bands over the devices -> three [W][M][P] arrays.  The windows are sharded as correlate()
         shards them: bands [M][2] and lag_bounds [P][2] go to every block whole, [W][M][2] and [W][P][2] are cut into each
         block's own windows' rows.  refine and quality are handed to every block's call (quality: a fourth array,
-        [W][M][P][4]); with neither, every block makes exactly the call it made without them."""
+        [W][M][P][4]); with neither, every block makes exactly the call it made without them.
+        integrate: K windows per group (XcorrEngine.correlate_bands): whole groups are sharded over the devices, as
+        correlate() shards them; the results and per-group lag_bounds are [W // K][.], the bands stay per window."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
         W = iq.shape[0]
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
+        K = check_integrate(integrate, W)
         bd, bands_pw = check_bands(bands, W)
-        lb, per_window = check_lag_bounds(lag_bounds, W, P)
+        lb, per_window = check_lag_bounds(lag_bounds, W // K, P)
         U = check_refine(refine)
         more = {"refine": U, "quality": True} if quality else ({"refine": U} if U else {})
+        n_out = 4 if quality else 3
+        if K > 1:
+            def group_call(eng, gs, gc):
+                # (as _correlate_integrated: a block of whole groups may be a little larger than its engine)
+                step = getattr(eng, "max_windows", gc * K) // K
+                if step < 1:
+                    raise ValueError(f"integrate = {K} windows per group is more than one device's engine holds "
+                                     f"({eng.max_windows} windows)")
+                parts = []
+                for g0 in range(gs, gs + gc, step):
+                    g1 = min(g0 + step, gs + gc)
+                    parts.append(eng.correlate_bands(iq[g0 * K:g1 * K], bd[g0 * K:g1 * K] if bands_pw else bd, pairs,
+                                                     lag_bounds=None if lb is None else (lb[g0:g1] if per_window else lb),
+                                                     whiten=whiten, integrate=K, **more))
+                return tuple(np.concatenate([p[k] for p in parts]) for k in range(n_out))
+            return self._run(W, group_call, n_out, (np.int32, np.float32, np.float32, np.float32)[:n_out], bd.shape[-2],
+                             n_rows=W // K, tails=[(P,), (P,), (P,), (P, 4)][:n_out])
 
         def block_call(eng, s, c):
             return eng.correlate_bands(iq[s:s + c], bd[s:s + c] if bands_pw else bd, pairs,
                                        lag_bounds=None if lb is None else (lb[s:s + c] if per_window else lb), whiten=whiten, **more)
         # (_run's rows are [W][n_pairs] + tail: here [W][M] + (P,))
-        n_out = 4 if quality else 3
         return self._run(W, block_call, n_out, (np.int32, np.float32, np.float32, np.float32)[:n_out], bd.shape[-2],
                          tails=[(P,), (P,), (P,), (P, 4)][:n_out])
 

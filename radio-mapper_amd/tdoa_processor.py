@@ -156,7 +156,7 @@ class TDoACalculator:
                  bound_lags: bool = False, band_limit: bool = False, whiten: bool = False, integrate: int = 1,
                  refine: int = 0, min_psr: Optional[float] = None, correlation_confidence: bool = False,
                  doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False,
-                 share_qualified: bool = False):
+                 share_qualified: bool = False, share_integrated: bool = False):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
@@ -202,7 +202,13 @@ class TDoACalculator:
         and the quality figures per (capture, band, pair), still one forward transform per buoy); min_psr and the
         correlation confidence are applied per (capture, band, pair), and the measurements are those of the separate
         calls, in the same order.  Groups under integrate > 1 or doppler_search_hz still go the usual way.  A plain
-        attribute, False (off) by default: nothing changes then."""
+        attribute, False (off) by default: nothing changes then.
+        share_integrated: together with share_captures, shared captures are correlated as one window under several bands
+        under integrate > 1 too (rmx_xcorr_batch_bands_integrated): the capture is cut ONCE into its K segments, exactly as
+        the separate calls cut it, each member's band is repeated over its K segments, and lag bounds and the
+        segment_length checks are as without sharing.  With refine > 0, min_psr or correlation_confidence it needs
+        share_qualified as well.  The Doppler search stays out.  A plain attribute, False (off) by default: share_captures
+        and share_qualified alone still stand back for integration."""
         from .xcorr import check_refine
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
@@ -213,6 +219,7 @@ class TDoACalculator:
         self.whiten = bool(whiten)
         self.share_captures = bool(share_captures)
         self.share_qualified = bool(share_qualified)
+        self.share_integrated = bool(share_integrated)
         self.integrate = int(integrate)
         self.refine = check_refine(refine)
         self.min_psr = None if min_psr is None else float(min_psr)
@@ -368,13 +375,16 @@ class TDoACalculator:
             out = tuple(a.reshape(lead + a.shape[1:]) for a in out)
         return out
 
-    def measure_band_lags(self, iq, bands, pairs=None, lag_bounds=None, whiten=False, refine=0, quality=False):
+    def measure_band_lags(self, iq, bands, pairs=None, lag_bounds=None, whiten=False, refine=0, quality=False, integrate=1):
         """measure_lags(bands=...) with the fine lag search and the quality figures (rmx_xcorr_batch_bands_quality): iq
         complex64 [W][B][N] (or uint8 [W][B][2N]) under bands [W][M][2] -> (lag_int, lag_frac, peak), each [W][M][P], and
         with quality=True a fourth array [W][M][P][4]; one forward transform per (window, buoy).  A leading channel axis is
         a batch axis, as in measure_lags: [C][W][B][N] with bands [C][W][M][2] (and lag_bounds [C][W][P][2]) -> [C][W][M][P]
-        ([C][W][M][P][4]).  refine: U in (0, 2, 4, 8, 16).  With refine=0 and quality=False it is measure_lags(bands=...)."""
-        from .xcorr import check_refine
+        ([C][W][M][P][4]).  refine: U in (0, 2, 4, 8, 16).  With refine=0 and quality=False it is measure_lags(bands=...).
+        integrate: K >= 1 consecutive windows per group, one lag per (group, band, pair) (rmx_xcorr_batch_bands_integrated):
+        W must be a multiple of K -- with a channel axis, every channel's W --, the results and per-group lag_bounds are
+        [W // K][.], the bands stay per window."""
+        from .xcorr import check_integrate, check_refine
         refine = check_refine(refine)
         iq = np.asarray(iq)
         lead = None
@@ -383,6 +393,11 @@ class TDoACalculator:
             iq = iq.reshape((lead[0] * lead[1],) + iq.shape[2:])
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N] or [C][W][B][N], got shape {iq.shape}")
+        if lead is not None:   # (groups never straddle two channels)
+            integrate = check_integrate(integrate, lead[1])
+            lead = (lead[0], lead[1] // integrate)
+        else:
+            integrate = check_integrate(integrate, iq.shape[0])
         n = iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2]
         eng = self._engine(iq.shape[1], n, iq.shape[0])
         lb = None
@@ -398,6 +413,8 @@ class TDoACalculator:
         kw = {"refine": refine} if refine > 0 else {}
         if quality:
             kw["quality"] = True
+        if integrate > 1:
+            kw["integrate"] = integrate
         out = eng.correlate_bands(iq, bs, pairs, lag_bounds=lb, whiten=bool(whiten), **kw)
         if lead is not None:
             out = tuple(a.reshape(lead + a.shape[1:]) for a in out)
@@ -592,14 +609,24 @@ class TDoACalculator:
     def _measure_shared(self, stacked: np.ndarray, lag_bounds, bands: np.ndarray, with_quality: bool = False):
         """share_captures: [G][B][N] captures, each under the M bands of bands [G][M][2] -> lag [G][M][P] float64, or None
         after logging, as _measure_groups does.  lag_bounds: None, or int [G][P][2].  share_qualified: the calculator's
-        refine goes along, and with_quality -> (lag [G][M][P], quality [G][M][P][4]) instead."""
+        refine goes along, and with_quality -> (lag [G][M][P], quality [G][M][P][4]) instead.  share_integrated: under
+        integrate = K > 1 every capture is cut into its K segments as _measure_groups cuts it and every band is repeated
+        over its capture's segments (the callers checked segment_length and derived lag_bounds and bands for N // K)."""
+        more = {}
+        if self.integrate > 1:
+            k = self.integrate
+            g, b, nn = stacked.shape
+            stacked = np.ascontiguousarray(stacked.reshape(g, b, k, nn // k).transpose(0, 2, 1, 3)).reshape(g * k, b, nn // k)
+            bands = np.repeat(np.asarray(bands), k, axis=0)
+            more["integrate"] = k
         try:
             if with_quality:
                 li, lf, _, qual = self.measure_band_lags(stacked, bands, lag_bounds=lag_bounds, whiten=self.whiten,
-                                                         refine=self.refine, quality=True)
+                                                         refine=self.refine, quality=True, **more)
                 return li.astype(np.float64) + lf.astype(np.float64), np.asarray(qual)
-            if self.refine > 0:
-                li, lf, _ = self.measure_band_lags(stacked, bands, lag_bounds=lag_bounds, whiten=self.whiten, refine=self.refine)
+            if self.refine > 0 or more:
+                li, lf, _ = self.measure_band_lags(stacked, bands, lag_bounds=lag_bounds, whiten=self.whiten, refine=self.refine,
+                                                   **more)
             else:
                 li, lf, _ = self.measure_lags(stacked, lag_bounds=lag_bounds, bands=bands, whiten=self.whiten)
             return li.astype(np.float64) + lf.astype(np.float64)
@@ -818,14 +845,14 @@ class TDoAProcessor:
     def __init__(self, band_limit: bool = False, whiten: bool = False, integrate: int = 1, refine: int = 0,
                  min_psr: Optional[float] = None, correlation_confidence: bool = False,
                  doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False,
-                 share_qualified: bool = False):
+                 share_qualified: bool = False, share_integrated: bool = False):
         """band_limit, whiten, integrate, refine, min_psr, correlation_confidence, doppler_search_hz, share_captures,
-        share_qualified: the TDoACalculator settings of the same names (off by default)."""
+        share_qualified, share_integrated: the TDoACalculator settings of the same names (off by default)."""
         self.logger = logging.getLogger(__name__ + ".TDoAProcessor")
         self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten, integrate=integrate, refine=refine,
                                               min_psr=min_psr, correlation_confidence=correlation_confidence,
                                               doppler_search_hz=doppler_search_hz, share_captures=share_captures,
-                                              share_qualified=share_qualified)
+                                              share_qualified=share_qualified, share_integrated=share_integrated)
         self.hyperbolic_positioner = HyperbolicPositioning()
         self.buoy_positions: Dict[str, BuoyPosition] = {}
         self.correlation_window_s = 10.0
@@ -899,8 +926,9 @@ class TDoAProcessor:
                         bands[n] = b
                 if not members:
                     continue
-                # (refine, min_psr / correlation_confidence: only with share_qualified; integrate and the Doppler search never)
-                if calc.share_captures and calc.integrate == 1 and calc.doppler_search_hz is None \
+                # (refine, min_psr / correlation_confidence: only with share_qualified; integrate: only with share_integrated;
+                # the Doppler search never)
+                if calc.share_captures and (calc.integrate == 1 or calc.share_integrated) and calc.doppler_search_hz is None \
                         and (calc.share_qualified or (calc.refine == 0 and not calc._wants_quality())):
                     members = self._measure_shared_captures(work, members, bands, n_samp, key[3])
                     if not members:

@@ -91,6 +91,8 @@ def load_library():
     lib.rmx_xcorr_batch_quality.restype = ci
     lib.rmx_xcorr_batch_bands_quality.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, cu, vp, ci, ci, vp, vp, vp, vp, cu]
     lib.rmx_xcorr_batch_bands_quality.restype = ci
+    lib.rmx_xcorr_batch_bands_integrated.argtypes = [vp, vp, ci, vp, ci, ci, vp, ci, ci, cu, vp, ci, ci, vp, vp, vp, vp, cu]
+    lib.rmx_xcorr_batch_bands_integrated.restype = ci
     lib.rmx_caf_batch.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, cu]
     lib.rmx_caf_batch.restype = ci
     lib.rmx_caf_batch_request.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, cu, vp, ci, vp, vp, vp, vp, vp, cu]
@@ -289,7 +291,7 @@ def doppler_estimate(doppler_cps, dop_idx, dop_frac) -> np.ndarray:
 
 
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_xcorr_batch_bands_quality", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_xcorr_batch_bands_quality", "rmx_xcorr_batch_bands_integrated", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -495,21 +497,26 @@ class XcorrEngine:
         return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
 
     def _xcorr_bands(self, iq_p, W: int, pp, P: int, bd, bands_pw: bool, whiten: bool, lb, per_window: bool,
-                     lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0, quality_p=None):
-        """One banded correlation call through the C entry its arguments name: rmx_xcorr_batch_bands_quality for U > 0 or
+                     lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0, quality_p=None, K: int = 1):
+        """One banded correlation call through the C entry its arguments name: rmx_xcorr_batch_bands_integrated for K > 1,
+        else rmx_xcorr_batch_bands_quality for U > 0 or
         a quality pointer, else rmx_xcorr_batch_bands.  iq and the outputs are pointers (host or device, as `flags` says);
         bd is the checked host array [M][2] or [W][M][2], lb a checked host array or None."""
-        head = (self._ctx, iq_p, W, pp, P, bd.ctypes.data_as(C.c_void_p), bd.shape[-2], int(bands_pw),
-                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
-                int(per_window))
-        if U or quality_p is not None:
+        band_args = (bd.ctypes.data_as(C.c_void_p), bd.shape[-2], int(bands_pw),
+                     RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
+                     int(per_window))
+        head = (self._ctx, iq_p, W, pp, P) + band_args
+        if K > 1:
+            rc = self._lib.rmx_xcorr_batch_bands_integrated(self._ctx, iq_p, W, pp, P, K, *band_args, U, lag_int_p, lag_frac_p,
+                                                            peak_p, quality_p, flags)
+        elif U or quality_p is not None:
             rc = self._lib.rmx_xcorr_batch_bands_quality(*head, U, lag_int_p, lag_frac_p, peak_p, quality_p, flags)
         else:
             rc = self._lib.rmx_xcorr_batch_bands(*head, lag_int_p, lag_frac_p, peak_p, flags)
         self._check(rc)
 
     def correlate_bands(self, iq: np.ndarray, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
-                        whiten: bool = False, refine: int = 0, quality: bool = False):
+                        whiten: bool = False, refine: int = 0, quality: bool = False, integrate: int = 1):
         """Every window under several bands with ONE forward transform per (window, buoy) (rmx_xcorr_batch_bands).
         iq: as for correlate().  bands: float [M][2] (shared by every window) or [W][M][2], [lo, hi] in cycles per sample,
         1 <= M <= 64.  lag_bounds: None, [P][2] or [W][P][2]: per (window, pair), shared by the window's bands.  whiten:
@@ -517,38 +524,45 @@ class XcorrEngine:
         correlate(iq, band=bands[..., m, :], ...) returns.
         refine: U in (0, 2, 4, 8, 16), the fine lag search of correlate(refine=U) per (window, band, pair); quality: True
         returns a fourth array, float32 [W][M][P][4] indexed by RMX_Q_* (rmx_xcorr_batch_bands_quality; still one forward
-        transform per (window, buoy)).  With neither, the call is rmx_xcorr_batch_bands."""
+        transform per (window, buoy)).  With neither, the call is rmx_xcorr_batch_bands.
+        integrate: K >= 1, as for correlate(): every K consecutive windows form a group with ONE peak search per (group,
+        band, pair) on the sum of the windows' squared magnitudes (rmx_xcorr_batch_bands_integrated).  W must be a multiple
+        of K; the results are [W // K][M][P] ([...][4]), lag_bounds [P][2] or [W // K][P][2]; bands stay [M][2] or
+        [W][M][2], and [:, m] is what correlate(iq, band=bands[..., m, :], integrate=K, ...) returns."""
         iq, flags = self._check_iq(iq)
         W = iq.shape[0]
+        K = check_integrate(integrate, W)
         U = check_refine(refine)
         pairs, pp, P = self._pairs_arg(pairs)
         bd, per_window_b = check_bands(bands, W)
         M = bd.shape[-2]
-        lb, per_window = check_lag_bounds(lag_bounds, W, P)
-        lag_int = np.zeros((W, M, P), np.int32)
-        lag_frac = np.zeros((W, M, P), np.float32)
-        peak = np.zeros((W, M, P), np.float32)
-        qual = np.zeros((W, M, P, 4), np.float32) if quality else None
+        lb, per_window = check_lag_bounds(lag_bounds, W // K, P)
+        lag_int = np.zeros((W // K, M, P), np.int32)
+        lag_frac = np.zeros((W // K, M, P), np.float32)
+        peak = np.zeros((W // K, M, P), np.float32)
+        qual = np.zeros((W // K, M, P, 4), np.float32) if quality else None
         if W and P:
             vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
             self._xcorr_bands(vp(iq), W, pp, P, bd, per_window_b, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags,
-                              U, vp(qual) if quality else None)
+                              U, vp(qual) if quality else None, K)
         return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
 
     def correlate_bands_device(self, iq_ptr: int, n_windows: int, bands, lag_int_ptr: int, lag_frac_ptr: int, peak_ptr: int,
                                pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None, whiten: bool = False,
-                               refine: int = 0, quality_ptr: Optional[int] = None):
+                               refine: int = 0, quality_ptr: Optional[int] = None, integrate: int = 1):
         """correlate_bands() with device pointers in and out (the bands, the pair list and the bounds stay host arrays; the
-        library keeps its own copies); asynchronous on the ctx stream.  The outputs are [n_windows][M][P]; quality_ptr, if
-        given, [n_windows][M][P][4] float32 on the device (rmx_xcorr_batch_bands_quality)."""
+        library keeps its own copies); asynchronous on the ctx stream.  The outputs are [n_windows // K][M][P]; quality_ptr,
+        if given, [n_windows // K][M][P][4] float32 on the device (rmx_xcorr_batch_bands_quality; with integrate = K > 1
+        rmx_xcorr_batch_bands_integrated)."""
+        K = check_integrate(integrate, n_windows)
         U = check_refine(refine)
         pairs, pp, P = self._pairs_arg(pairs)
         bd, per_window_b = check_bands(bands, n_windows)
-        lb, per_window = check_lag_bounds(lag_bounds, n_windows, P)
+        lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
         self._xcorr_bands(C.c_void_p(iq_ptr), n_windows, pp, P, bd, per_window_b, whiten, lb, per_window, C.c_void_p(lag_int_ptr),
                           C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags, U,
-                          None if quality_ptr is None else C.c_void_p(quality_ptr))
+                          None if quality_ptr is None else C.c_void_p(quality_ptr), K)
 
     def _pairs_arg(self, pairs):
         """pairs as the entries take it -> (kept int32 array or None, its pointer or None, P)"""
