@@ -331,7 +331,7 @@ int rmx_xcorr_batch_integrated(rmx_ctx* ctx, const void* iq, int n_windows, cons
  *   as a weighted call does (a full band and no whitening when the caller gave none), and one more kernel, k_refine
  *   (radio-mapper_amd/csrc/refine.hpp), runs behind each chunk's pair kernels: it reads lag0 from the outputs, sums the
  *   cross-spectrum in storage order with exact rational phases, reduces in a fixed tree (two identical calls give
- *   bit-identical outputs) and overwrites the three outputs in place.  rmx_caf_batch is not refined. */
+ *   bit-identical outputs) and overwrites the three outputs in place.  (The Doppler search: rmx_caf_batch_quality.) */
 int rmx_xcorr_batch_refined(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                             int integrate,
                             const double* band_cps, int band_per_window, unsigned weighting,
@@ -386,7 +386,7 @@ enum { RMX_Q_COHERENCE = 0, RMX_Q_PSR = 1, RMX_Q_RMS_BW = 2, RMX_Q_NEFF = 3 };
  *     k_win8kl, k16_*, g_win_*, g_rows_fused included, which keep their spectra to themselves and round lag_frac and
  *     peak differently in the last bits than the per-transform kernels), then, chunk by chunk, the per-transform
  *     forward kernels and k_quality: one more forward pass, and the outputs stay those of the call without quality.
- *   rmx_caf_batch reports no quality. */
+ *   (The Doppler search: rmx_caf_batch_quality.) */
 int rmx_xcorr_batch_quality(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                             int integrate,
                             const double* band_cps, int band_per_window, unsigned weighting,
@@ -506,13 +506,57 @@ int rmx_caf_batch(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pa
  * The routes are rmx_caf_batch's: every weighted or bounded instantiation runs where the plain one runs, with the same
  *   launch counts (the N = 4096 one-launch path included); a non-NULL dop_frac swaps k_caf_select(_all) for
  *   k_caf_select(_all)_fd (radio-mapper_amd/csrc/caf_select.hpp).
- * There is no integration, refinement or quality here: rmx_caf_batch_request is not refined and reports no quality. */
+ * There is no integration here.  Refinement and quality: rmx_caf_batch_quality, which this entry is with neither. */
 int rmx_caf_batch_request(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                           const double* doppler_cps, int n_dopplers,
                           const double* band_cps, int band_per_window, unsigned weighting,
                           const int32_t* lag_bounds, int bounds_per_window,
                           int32_t* dop_idx, float* dop_frac,
                           int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
+
+/* Refined and qualified lags of the Doppler search: rmx_caf_batch_request with the fine lag search of
+ * rmx_xcorr_batch_refined and the four figures of rmx_xcorr_batch_quality on each slot's WINNING hypothesis.  Receivers
+ * whose oscillators differ by hundreds of hertz are the ones whose lags most need a threshold (quality[RMX_Q_PSR] against
+ * xcorr.psr_threshold) and a weight for rmx_solve_batch (xcorr.lag_sigma).
+ *   refine      U, one of 0, 2, 4, 8, 16, as in rmx_xcorr_batch_refined.
+ *   quality     float32 [n_windows][n_pairs][4] (RMX_Q_...), or NULL; a device pointer with RMX_OUT_DEVICE.  It must not
+ *               overlap one of the five other outputs.
+ *   every other argument means exactly what it means for rmx_caf_batch_request.
+ * Definition, for window w, pair (i, j) and the winner d* = dop_idx[w][q]:
+ *   The winner is chosen exactly as in rmx_caf_batch_request, on the coarse per-hypothesis peaks, and is never revisited:
+ *   dop_idx and dop_frac do not move when refine or quality is set, and dop_frac stays the parabola through the COARSE peaks.
+ *   lag_int, lag_frac, peak and quality of the slot are those of rmx_xcorr_batch_quality for the pair of windows
+ *   (x_i, x_j * rot_d*) with integrate = 1 and this call's band, weighting, lag bounds and refine:
+ *     Y_i and Y_j,d* are the weighted un-rotated and de-rotated spectra exactly as rmx_caf_batch_request defines them (the
+ *       weight applied to the stored spectrum after the rotation);
+ *     lag0 and p0 are the winner's coarse lag and coarse peak (lag_d*, peak_d*);
+ *     quality is computed with p0, before any refinement;
+ *     refine then overwrites lag_int, lag_frac and peak by the rule of rmx_xcorr_batch_refined.
+ *   Parity against a float64 restatement (tests/caf_quality_ref.py stacks tests/caf_request_ref.py, refined_ref.py and
+ *   quality_ref.py on the winner's rotated pair): the bars of rmx_xcorr_batch_refined and rmx_xcorr_batch_quality.
+ * refine == 0 and quality == NULL IS rmx_caf_batch_request: the same kernels, the same launches, bit-identical outputs.
+ *   With refine == 0, lag_int, lag_frac and peak are bit-identical to the call without quality.
+ * Otherwise the search itself runs exactly what rmx_caf_batch_request runs, and behind the selection k_quality<layout,
+ *   CafWinner>, then k_refine<U, layout, CafWinner> (radio-mapper_amd/csrc/caf_select.hpp, quality.hpp, refine.hpp) read
+ *   operand i from the un-rotated spectra and operand j from the winner's de-rotated ones.  Under a band the spectra are
+ *   stored masked, so these are the plain kernel bodies.
+ *   - The one-launch path of N = 4096 holds every hypothesis' spectra when the selection has run: one launch of each
+ *     kernel, slot (w, q) reading operand j at virtual window dop_idx * n_windows + w; no transform is added.
+ *   - Every other route overwrites hypothesis d's spectra with d + 1's and knows the winner only after the last one:
+ *     behind the last hypothesis of each chunk the hypotheses are swept a second time, each forward pass followed by the
+ *     two kernels, whose workgroups return at once unless dop_idx[slot] == d.  n_dopplers more forward launches and
+ *     n_dopplers launches of each kernel per chunk; no scratch.
+ * Refusals (RMX_E_INVAL, the text in rmx_last_error, nothing staged or written), in this order: rmx_caf_batch_request's own,
+ *   in its order; refine not one of 0, 2, 4, 8, 16, with the value; quality overlapping one of the five other outputs, the
+ *   text naming the array; a device quality not aligned to 4 bytes.  n_windows == 0 or n_pairs == 0 returns RMX_OK and
+ *   writes nothing.
+ * There is no integration here. */
+int rmx_caf_batch_quality(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                          const double* doppler_cps, int n_dopplers,
+                          const double* band_cps, int band_per_window, unsigned weighting,
+                          const int32_t* lag_bounds, int bounds_per_window, int refine,
+                          int32_t* dop_idx, float* dop_frac,
+                          int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
 
 /* Batched hyperbolic position solve: the consumer of the lags.  One
  * independent 3-unknown least-squares problem per window with the reference's objective

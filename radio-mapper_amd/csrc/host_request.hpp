@@ -282,7 +282,8 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
 }
 
 // The tail of rmx_caf_batch_request, behind its own head (NULL buffer, n_dopplers, the batch shape, the pair list):
-// `a` with n_pairs resolved; the weighted entry's checks, the bounded entry's, then dop_frac over another output.
+// `a` with n_pairs resolved; the weighted entry's checks, the bounded entry's, then dop_frac over another output, and what
+// rmx_caf_batch_quality adds behind them (a.refine, a.quality, a.flags).
 inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const float* dop_frac, Request* r, std::string* err) {
     *r = Request{};
     r->n_pairs = a.n_pairs;
@@ -303,6 +304,22 @@ inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const
         rc = check_overlap("dop_frac", dop_frac, slots * sizeof(float), outs, 4, slots * sizeof(float), needs, err);
         if (rc != RMX_OK) return rc;
     }
+    // rmx_caf_batch_quality: refine, then quality over one of the five other outputs (k_quality reads peak and dop_idx
+    // while it writes quality), then a device quality aligned to less than its element
+    if (a.refine != 0 && a.refine != 2 && a.refine != 4 && a.refine != 8 && a.refine != 16)
+        return refuse(err, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", a.refine);
+    if (a.quality) {
+        const size_t slots = (size_t)a.n_windows * a.n_pairs;
+        OutArray outs[5] = {{"dop_idx", dop_idx}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}, {"dop_frac", dop_frac}};
+        char needs[96];
+        std::snprintf(needs, sizeof needs, "the %zu x 4 floats of quality need a buffer of their own", slots);
+        rc = check_overlap("quality", a.quality, 4 * slots * sizeof(float), outs, dop_frac ? 5 : 4, slots * sizeof(float), needs, err);
+        if (rc != RMX_OK) return rc;
+        const OutArray q[1] = {{"quality", a.quality}};
+        rc = check_alignment(a.flags & RMX_OUT_DEVICE, nullptr, q, 1, err);
+        if (rc != RMX_OK) return rc;
+    }
+    r->refine = a.refine;
     return RMX_OK;
 }
 

@@ -45,6 +45,8 @@ constexpr int kQualSums = 5;   // A, B, C, D, F
 // -- in the weighted call it is a stored zero, which adds +0 to each of the five sums.  <LagBounds, Integrate, BandSet>:
 // the banded pack of an integrated call, as k_refine's: row gl = group * n_bands + m walks its group's a.k windows, each
 // under band (window, m), and thread 0 adds the per-window terms in window order as the plain kernel does.
+// <CafWinner> (rmx_caf_batch_quality, caf_select.hpp): the plain body with operand j read from the de-rotated set of the
+// slot's winning hypothesis; p0 is the winner's coarse peak, which the selection wrote.
 template <int LAYOUT, class... P>
 __global__ __launch_bounds__(kRefThreads) void k_quality(QualityArgs a, const float* __restrict__ peak, float* __restrict__ quality,
                                                          P... tail) {
@@ -53,6 +55,13 @@ __global__ __launch_bounds__(kRefThreads) void k_quality(QualityArgs a, const fl
     const int gl = blockIdx.x / a.n_pairs, q = blockIdx.x % a.n_pairs;   // output row inside the chunk, pair
     const long o = (a.first_out + gl) * (long)a.n_pairs + q;
     const int L = 1 << a.logL, N = L >> 1;
+    [[maybe_unused]] const float2* spec_j = a.spec;
+    if constexpr (kCafWinner<P...>) {
+        const CafWinner cw = caf_winner_of(tail...);
+        const int dw = cw.dop[o];
+        if (cw.d >= 0 && dw != cw.d) return;   // (the whole workgroup: o is its slot)
+        spec_j = cw.spec_j + (cw.d >= 0 ? 0L : dw * cw.hyp_items) * L;
+    }
     const RefPair pr = a.pairs[q];
     const float inv_l = 1.0f / (float)L;   // a power of two
     float ee = 0.0f, sum_c = 0.0f, sum_d = 0.0f, sum_f = 0.0f;   // thread 0: over the windows, in window order
@@ -75,6 +84,7 @@ __global__ __launch_bounds__(kRefThreads) void k_quality(QualityArgs a, const fl
         }
         const float4* xi = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.i) * L);
         const float4* xj = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.j) * L);
+        if constexpr (kCafWinner<P...>) xj = reinterpret_cast<const float4*>(spec_j + (wl * a.n_buoys + pr.j) * L);
         float acc[kQualSums];
 #pragma unroll
         for (int u = 0; u < kQualSums; ++u) acc[u] = 0.0f;

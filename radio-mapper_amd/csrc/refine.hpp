@@ -23,6 +23,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "caf_select.hpp"
 #include "lag_bounds.hpp"
 #include "xspec_bands.hpp"
 #include "xspec_weight.hpp"
@@ -69,7 +70,9 @@ __device__ __forceinline__ int ref_bin(int pos, int logL, int row_bits) {
 // is a sum of two products, one of which is rounded and one fused into the multiply-add; which one is the compiler's
 // choice (-ffp-contract), it depends on the order in which the backend meets the nodes, and it fell differently in the
 // banded instantiation: last-bit differences from the single-band call.  The plain kernel's forms are stated here with the
-// contraction off (tests/test_gpu_bands_quality.py holds the two kernels together, every U on every layout):
+// contraction off (tests/test_gpu_bands_quality.py holds the two kernels together, every U on every layout).  The
+// <CafWinner> instantiation takes them too: left to the backend, its first step rounded sc * c0.x and fused ss * c0.y
+// (tests/test_gpu_caf_quality.py holds it to the plain kernel bit for bit):
 //   u = 1, up and dn both from c0, sharing their products:   ss * c0 rounded, sc * c0 fused
 //   u > 1:   up.x, dn.x, dn.y: the ss product rounded, the sc product fused;   up.y: sc * up.y rounded, ss * up.x fused
 __device__ __forceinline__ void ref_first_step(const float2 c0, float ss, float sc, float2& up, float2& dn) {
@@ -96,6 +99,8 @@ __device__ __forceinline__ void ref_next_step(float ss, float sc, float2& up, fl
 // gl = group * n_bands + m walks the a.k real windows of its group in window order, each under band (window, m); the sums,
 // the fixed tree and the tap rule are those of the plain kernel with a.k > 1.  Of that pack only
 // the band set is read: the lag intervals and K are a.lb and a.k.
+// <CafWinner> (rmx_caf_batch_quality, caf_select.hpp): the plain body -- a band is stored masked --, with operand j read
+// from the de-rotated set of the slot's winning hypothesis; lag0 is the winner's coarse lag, which the selection wrote.
 template <int U, int LAYOUT, class... P>
 __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __restrict__ lag_int, float* __restrict__ lag_frac,
                                                         float* __restrict__ peak, P... tail) {
@@ -106,6 +111,13 @@ __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __res
     const int gl = blockIdx.x / a.n_pairs, q = blockIdx.x % a.n_pairs;   // output row inside the chunk, pair
     const long o = (a.first_out + gl) * (long)a.n_pairs + q;
     const int L = 1 << a.logL, N = L >> 1;
+    [[maybe_unused]] const float2* spec_j = a.spec;
+    if constexpr (kCafWinner<P...>) {
+        const CafWinner cw = caf_winner_of(tail...);
+        const int dw = cw.dop[o];
+        if (cw.d >= 0 && dw != cw.d) return;   // (the whole workgroup: o is its slot)
+        spec_j = cw.spec_j + (cw.d >= 0 ? 0L : dw * cw.hyp_items) * L;
+    }
     const int lag0 = lag_int[o];
     const RefPair pr = a.pairs[q];
     const float inv_n = 1.0f / (float)N, inv_un = 1.0f / ((float)N * (float)U);   // powers of two
@@ -129,6 +141,7 @@ __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __res
         }
         const float4* xi = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.i) * L);
         const float4* xj = reinterpret_cast<const float4*>(a.spec + (wl * a.n_buoys + pr.j) * L);
+        if constexpr (kCafWinner<P...>) xj = reinterpret_cast<const float4*>(spec_j + (wl * a.n_buoys + pr.j) * L);
         float2 acc[T];
 #pragma unroll
         for (int u = 0; u < T; ++u) acc[u] = make_float2(0.0f, 0.0f);
@@ -159,7 +172,7 @@ __global__ __launch_bounds__(kRefThreads) void k_refine(RefineArgs a, int* __res
                 float2 up = c0, dn = c0;
 #pragma unroll
                 for (int u = 1; u <= U; ++u) {
-                    if constexpr (kBanded<P...>) {
+                    if constexpr (kBanded<P...> || kCafWinner<P...>) {
                         if (u == 1) ref_first_step(c0, ss, sc, up, dn);
                         else ref_next_step(ss, sc, up, dn);
                     } else {

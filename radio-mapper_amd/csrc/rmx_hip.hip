@@ -447,7 +447,7 @@ static int ensure_ref_pairs(rmx_ctx* c, int n_pairs) {
 // [w0, w0 + wc), whose spectra `spec` still holds in the order `layout` names.  One workgroup per output slot of the
 // chunk; lag_int is read (the coarse lag0) and all three outputs are overwritten in place.
 static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, int w0, int wc, int n_pairs, int* d_lag, float* d_frac,
-                        float* d_peak) {
+                        float* d_peak, const CafWinner* cw = nullptr) {
     const int rc_p = ensure_ref_pairs(c, n_pairs), logL = sv.logL, unit_log2 = sv.unit_log2;
     if (rc_p != RMX_OK) return rc_p;
     RefineArgs a;
@@ -472,6 +472,9 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, i
     // k_refine<U, layout>; U was checked by the entry (16 is the last it admits), the four-step layout is the last one
     return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
         return with_one_of<2, 4, 8, 16>(call.refine, [&](auto u) {
+            if (cw)   // rmx_caf_batch_quality: operand j from the winner's de-rotated set (never banded or integrated)
+                return launch(c, kTkRefine, k_refine<decltype(u)::value, decltype(lay)::value, CafWinner>, dim3(grid), dim3(kRefThreads), 0,
+                              a, d_lag, d_frac, d_peak, *cw);
             if (call.banded() && call.integrated())
                 return launch(c, kTkRefine, k_refine<decltype(u)::value, decltype(lay)::value, LagBounds, Integrate, BandSet>, dim3(grid),
                               dim3(kRefThreads), 0, a, d_lag, d_frac, d_peak, call.lb, Integrate{call.integ}, bs);
@@ -487,7 +490,8 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, i
 // The quality figures of a quality call (quality.hpp) on the chunk the pair kernels have just finished, in front of
 // refine_chunk: d_peak still holds the coarse peaks.  One workgroup per output slot of the chunk; nothing but
 // call.quality is written.
-static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, int w0, int wc, int n_pairs, const float* d_peak) {
+static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, int w0, int wc, int n_pairs, const float* d_peak,
+                         const CafWinner* cw = nullptr) {
     const int rc_p = ensure_ref_pairs(c, n_pairs), logL = sv.logL, unit_log2 = sv.unit_log2;
     if (rc_p != RMX_OK) return rc_p;
     QualityArgs a;
@@ -507,6 +511,9 @@ static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, 
     bs.w0 = w0;
     const unsigned grid = (unsigned)(wc / call.integ * nb * n_pairs);
     return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
+        if (cw)   // rmx_caf_batch_quality, as refine_chunk
+            return launch(c, kTkQuality, k_quality<decltype(lay)::value, CafWinner>, dim3(grid), dim3(kRefThreads), 0, a, d_peak, call.quality,
+                          *cw);
         if (call.banded() && call.integrated())
             return launch(c, kTkQuality, k_quality<decltype(lay)::value, LagBounds, Integrate, BandSet>, dim3(grid), dim3(kRefThreads), 0, a,
                           d_peak, call.quality, call.lb, Integrate{call.integ}, bs);
@@ -1835,12 +1842,28 @@ int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pair
 
 // The Doppler search under a request: a band and PHAT on every stored spectrum, the rotated ones included, lag intervals
 // in every hypothesis' peak search, and (dop_frac) the parabola through the winner's and its two neighbours' peaks.
+// It is rmx_caf_batch_quality with nothing refined or qualified: the same kernels, the same launches
 int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                           const double* doppler_cps, int n_dopplers,
                           const double* band_cps, int band_per_window, unsigned weighting,
                           const int32_t* lag_bounds, int bounds_per_window,
                           int32_t* dop_idx, float* dop_frac,
                           int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    return rmx_caf_batch_quality(c, iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, band_cps, band_per_window, weighting, lag_bounds,
+                                 bounds_per_window, 0, dop_idx, dop_frac, lag_int, lag_frac, peak, nullptr, flags);
+}
+
+// rmx_caf_batch_request with the fine lag search and the quality figures of rmx_xcorr_batch_quality on each slot's WINNING
+// hypothesis: behind the selection, k_quality and then k_refine in their <CafWinner> instantiations (caf_select.hpp) read
+// operand i from the un-rotated spectra and operand j from the winner's de-rotated ones.  Where every hypothesis' set is
+// resident (the one-launch path of N = 4096) that is one launch of each; elsewhere the hypotheses of a chunk are swept a
+// second time, each forward pass followed by the two kernels, whose workgroups return unless their slot's winner is resident.
+int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                          const double* doppler_cps, int n_dopplers,
+                          const double* band_cps, int band_per_window, unsigned weighting,
+                          const int32_t* lag_bounds, int bounds_per_window, int refine,
+                          int32_t* dop_idx, float* dop_frac,
+                          int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
     if (!c) return RMX_E_INVAL;
     if (!iq || !dop_idx || !lag_int || !lag_frac || !peak || !doppler_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
     std::string why;
@@ -1853,7 +1876,7 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
     if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
     if (n_windows == 0 || n_pairs == 0) return RMX_OK;
     const int B = c->n_buoys, N = c->n_samples;
-    XcorrCall call;   // the plain request unless the checks below say otherwise; never integrated, refined or qualified
+    XcorrCall call;   // the plain request unless the checks below say otherwise; never integrated
     RMX_HIP(c, hipSetDevice(c->device));
     // N = 4096, one chunk: all hypotheses in ONE forward launch and ONE pair launch (virtual window = hypothesis x
     // window) instead of three launches per hypothesis -- 21 hypotheses on one frequency group: 431 -> ~60 us
@@ -1874,12 +1897,21 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
         a.n_buoys = B;
         a.n_samples = N;
         a.max_windows = c->max_windows;
+        a.refine = refine;
+        a.quality = quality;
+        a.flags = flags;
         host::Request rq;
         rc = host::check_caf_request(a, dop_idx, dop_frac, &rq, &why);
         if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
         rc = describe_call(c, rq, &call);
         if (rc != RMX_OK) return rc;
     }
+    // What follows the selection.  `call` itself stays unrefined and unqualified: the forward and the pair kernels of the
+    // search are those of rmx_caf_batch_request whatever is asked here.
+    XcorrCall tail = call;
+    tail.refine = refine;
+    tail.quality = quality;
+    const bool with_tail = tail.refined() || tail.qualified();
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
     const size_t in_bytes = (size_t)n_windows * B * N * (u8 ? 2 : 8);
     const void* d_iq = iq;
@@ -1918,6 +1950,10 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
         RMX_MEM(c->caf_nb.reserve(4 * out_elems));
         if (!out_dev) b_dfrac = c->caf_nb + 3 * out_elems;
     }
+    if (quality && !out_dev) {
+        RMX_MEM(c->d_quality.reserve(4 * out_elems));
+        tail.quality = c->d_quality;
+    }
     // Per chunk of windows: the un-rotated spectra once, then per hypothesis the de-rotated spectra (the rotation
     // is applied as the window is loaded), the pair kernels with X_i un-rotated and X_j de-rotated, and the
     // running d-major first maximum.  No augmented copy of the windows, no second engine.
@@ -1945,6 +1981,10 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
         if (rc == RMX_OK && dop_frac)
             rc = launch(c, kTkCafSelect, k_caf_select_all_fd, sgrid, dim3(256), 0, n_dopplers, (long)out_elems, c->caf_lag, c->caf_frac,
                         c->caf_peak, b_dop, b_lag, b_frac, b_peak, b_dfrac);
+        // every de-rotated set is resident: slot (w, q) reads operand j at virtual window dop_idx * W + w
+        const CafWinner cw{b_dop, reinterpret_cast<const float2*>(c->d_spec_r.get()), (long)n_windows * B, -1};
+        if (rc == RMX_OK && tail.qualified()) rc = quality_chunk(c, tail, sv, 0, n_windows, n_pairs, b_peak, &cw);
+        if (rc == RMX_OK && tail.refined()) rc = refine_chunk(c, tail, sv, 0, n_windows, n_pairs, b_lag, b_frac, b_peak, &cw);
     }
     for (int w0 = 0; !batch_bins && w0 < n_windows && rc == RMX_OK; w0 += chunk) {
         const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
@@ -1964,11 +2004,20 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
                 rc = launch(c, kTkCafSelect, k_caf_select, sgrid, dim3(256), 0, d, first, cnt, c->caf_lag, c->caf_frac, c->caf_peak, b_dop,
                             b_lag, b_frac, b_peak);
         }
+        // The chunk's winners are known now and only the last hypothesis' de-rotated set is left: the hypotheses once
+        // more, each followed by k_quality and k_refine on the slots it won (k_quality in front: k_refine overwrites peak)
+        for (int d = 0; with_tail && d < n_dopplers && rc == RMX_OK; ++d) {
+            rc = sv.forward(c, call, d_iq, w0, wc, u8, c->caf_rot + (size_t)d * N, false);
+            const CafWinner cw{b_dop, c->generic ? c->g_spec_r.get() : reinterpret_cast<const float2*>(c->d_spec_r.get()), 0L, d};
+            if (rc == RMX_OK && tail.qualified()) rc = quality_chunk(c, tail, sv, w0, wc, n_pairs, b_peak, &cw);
+            if (rc == RMX_OK && tail.refined()) rc = refine_chunk(c, tail, sv, w0, wc, n_pairs, b_lag, b_frac, b_peak, &cw);
+        }
     }
     if (rc != RMX_OK) return rc;
     if (out_dev) return RMX_OK;
     // host-pointer results: dop_frac is queued in front of fetch_out, which waits for the stream
     if (dop_frac) RMX_HIP(c, hipMemcpyAsync(dop_frac, b_dfrac, out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (quality) RMX_HIP(c, hipMemcpyAsync(quality, tail.quality, 4 * out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return fetch_out(c, out_elems, lag_int, lag_frac, peak, dop_idx);
 }
 

@@ -236,24 +236,30 @@ class MultiXcorrEngine:
                          tails=[(), (), (), (4,)][:n_out])
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
-            whiten: bool = False, fine: bool = False):
+            whiten: bool = False, fine: bool = False, refine: int = 0, quality: bool = False):
         """Cross-ambiguity search -> (doppler_idx, lag_int, lag_frac, peak), each [W][P]; with fine=True (doppler_idx,
         dop_frac, lag_int, lag_frac, peak) (XcorrEngine.caf).  lag_bounds [P][2] and band [2] go to every block whole,
-        [W][P][2] and [W][2] are cut into each block's own windows' rows, as correlate() cuts them."""
+        [W][P][2] and [W][2] are cut into each block's own windows' rows, as correlate() cuts them.  refine and quality
+        are handed to every block's call (quality: the blocks' figures [W][P][4] as the last array); with neither, every
+        block makes exactly the call it made without them."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
         lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
         bd, band_pw = check_band(band, iq.shape[0])
-        if lb is None and bd is None and not whiten and not fine:
+        U = check_refine(refine)
+        more = {"refine": U, "quality": True} if quality else ({"refine": U} if U else {})
+        if lb is None and bd is None and not whiten and not fine and not more:
             return self._run(iq.shape[0], lambda eng, s, c: eng.caf(iq[s:s + c], doppler_cps, pairs), 4,
                              (np.int32, np.int32, np.float32, np.float32), P)
 
         def block_call(eng, s, c):
             return eng.caf(iq[s:s + c], doppler_cps, pairs,
                            lag_bounds=None if lb is None else (lb[s:s + c] if per_window else lb),
-                           band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, fine=fine)
-        if fine:
-            return self._run(iq.shape[0], block_call, 5, (np.int32, np.float32, np.int32, np.float32, np.float32), P)
-        return self._run(iq.shape[0], block_call, 4, (np.int32, np.int32, np.float32, np.float32), P)
+                           band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, fine=fine, **more)
+        dtypes = (np.int32, np.float32, np.int32, np.float32, np.float32) if fine else (np.int32, np.int32, np.float32, np.float32)
+        tails = [()] * len(dtypes)
+        if quality:
+            dtypes, tails = dtypes + (np.float32,), tails + [(4,)]
+        return self._run(iq.shape[0], block_call, len(dtypes), dtypes, P, tails=tails)

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""GPU box: the Doppler search (rmx_caf_batch / rmx_caf_batch_request) at one shape, device arrays in and out.
-usage: bench_caf.py B N W D [--whiten] [--band LO HI] [--bounds HALF] [--fine] [--host] [--reps R] [--rounds K]
+"""GPU box: the Doppler search (rmx_caf_batch / rmx_caf_batch_request / rmx_caf_batch_quality) at one shape, device arrays
+in and out.
+usage: bench_caf.py B N W D [--whiten] [--band LO HI] [--bounds HALF] [--fine] [--refine U] [--quality] [--host] [--reps R]
+                    [--rounds K]
 
   --whiten       PHAT                                      --band LO HI   keep [LO, HI] cycles per sample
   --bounds HALF  per-window lag intervals of +-HALF samples around the true lags
   --fine         with the sub-grid Doppler estimate (dop_frac)
+  --refine U     the fine lag search on each slot's winning hypothesis       --quality   with the four quality figures
   --host         host arrays in and out (XcorrEngine.caf: the copies and the synchronisation are part of every call)
 
 Each round times R back-to-back calls between two stream synchronisations and reports the time per call; the line gives
@@ -28,6 +31,8 @@ ap.add_argument("--whiten", action="store_true")
 ap.add_argument("--band", type=float, nargs=2, metavar=("LO", "HI"))
 ap.add_argument("--bounds", type=int, metavar="HALF")
 ap.add_argument("--fine", action="store_true")
+ap.add_argument("--refine", type=int, default=0)
+ap.add_argument("--quality", action="store_true")
 ap.add_argument("--host", action="store_true")
 ap.add_argument("--reps", type=int, default=0, help="calls per round (default: enough for about 0.3 s)")
 ap.add_argument("--rounds", type=int, default=7)
@@ -56,6 +61,11 @@ x = torch.from_numpy(np.ascontiguousarray(iq).view(np.float32).reshape(W, B, N, 
 out = [torch.zeros((W, P), dtype=t, device=dev) for t in (torch.int32, torch.int32, torch.float32, torch.float32, torch.float32)]
 if args.fine:
     kw["fine" if args.host else "dop_frac_ptr"] = True if args.host else out[4].data_ptr()
+if args.refine:
+    kw["refine"] = args.refine
+qual = torch.zeros((W, P, 4), dtype=torch.float32, device=dev)
+if args.quality:
+    kw["quality" if args.host else "quality_ptr"] = True if args.host else qual.data_ptr()
 eng = xcorr.XcorrEngine(B, N, W)
 eng.set_stream(torch.cuda.current_stream().cuda_stream)
 
@@ -63,6 +73,7 @@ eng.set_stream(torch.cuda.current_stream().cuda_stream)
 def call():
     if args.host:
         res = eng.caf(iq, grid, **kw)
+        res = res[:-1] if args.quality else res
         out[1], out[2] = torch.from_numpy(res[-3]), torch.from_numpy(res[-2])
         return
     eng.caf_device(x.data_ptr(), W, grid, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), **kw)
@@ -85,7 +96,8 @@ for _ in range(args.rounds):
 li, lf = out[1].cpu().numpy(), out[2].cpu().numpy()
 ok = np.mean(np.abs(li + lf - true) < 1.0)
 med, lo, hi = np.median(per_call), min(per_call), max(per_call)
-what = " ".join([k for k in ("whiten", "band", "lag_bounds", "dop_frac_ptr", "fine") if k in kw] + ["host"] * args.host) or "plain"
+what = " ".join([k for k in ("whiten", "band", "lag_bounds", "dop_frac_ptr", "fine", "quality_ptr", "quality") if k in kw]
+                + ["refine=%d" % args.refine] * bool(args.refine) + ["host"] * args.host) or "plain"
 print(f"caf B={B} N={N} W={W} D={D} [{what}] {xcorr.build_info().get('source_digest')}: {med * 1e6:.1f} us per call "
       f"(median of {args.rounds} rounds of {reps}, {lo * 1e6:.1f} .. {hi * 1e6:.1f}) = {W * P * D * N / med / 1e9:.2f} Gsample-bins/s; "
       f"lags within 1 sample of the truth: {ok * 100:.1f}%  scratch {eng.scratch_bytes() / 2**30:.2f} GiB", flush=True)
