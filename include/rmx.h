@@ -506,7 +506,8 @@ int rmx_caf_batch(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pa
  * The routes are rmx_caf_batch's: every weighted or bounded instantiation runs where the plain one runs, with the same
  *   launch counts (the N = 4096 one-launch path included); a non-NULL dop_frac swaps k_caf_select(_all) for
  *   k_caf_select(_all)_fd (radio-mapper_amd/csrc/caf_select.hpp).
- * There is no integration here.  Refinement and quality: rmx_caf_batch_quality, which this entry is with neither. */
+ * There is no integration here.  Refinement and quality: rmx_caf_batch_quality, which this entry is with neither; the
+ * search integrated over groups of windows: rmx_caf_batch_integrated. */
 int rmx_caf_batch_request(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                           const double* doppler_cps, int n_dopplers,
                           const double* band_cps, int band_per_window, unsigned weighting,
@@ -550,13 +551,76 @@ int rmx_caf_batch_request(rmx_ctx* ctx, const void* iq, int n_windows, const int
  *   in its order; refine not one of 0, 2, 4, 8, 16, with the value; quality overlapping one of the five other outputs, the
  *   text naming the array; a device quality not aligned to 4 bytes.  n_windows == 0 or n_pairs == 0 returns RMX_OK and
  *   writes nothing.
- * There is no integration here. */
+ * There is no integration here.  rmx_caf_batch_integrated is this entry with `integrate`. */
 int rmx_caf_batch_quality(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                           const double* doppler_cps, int n_dopplers,
                           const double* band_cps, int band_per_window, unsigned weighting,
                           const int32_t* lag_bounds, int bounds_per_window, int refine,
                           int32_t* dop_idx, float* dop_frac,
                           int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
+
+/* The Doppler search integrated noncoherently over consecutive windows: coherent inside each window under a frequency
+ * hypothesis, noncoherent across the K windows of a group -- the weak-signal form for receivers with free-running
+ * oscillators.  rmx_xcorr_batch_integrated alone fails once the offset reaches one cycle per window (every term of its
+ * sum then sits on the null of the window's own sinc); rmx_caf_batch_quality alone has no processing gain beyond one
+ * window.  Here every hypothesis is de-rotated per window and |r|^2 is summed over the group before ONE peak search.
+ *   integrate   K >= 1; n_windows must be a positive multiple of K: G = n_windows / K groups of K consecutive windows, as
+ *               in rmx_xcorr_batch_integrated.
+ *   band_cps, band_per_window, weighting   stay per WINDOW ([n_windows][2] or [2]), shared by all hypotheses.
+ *   lag_bounds  NULL, host int32 [n_pairs][2] (bounds_per_group == 0), or [G][n_pairs][2] per group; the interval of a
+ *               (group, pair) is shared by all its hypotheses.
+ *   dop_idx, dop_frac (or NULL), lag_int, lag_frac, peak   [G][n_pairs];  quality  float32 [G][n_pairs][4], or NULL.
+ *   every other argument means exactly what it means for rmx_caf_batch_quality.
+ * Definition, for group g, pair (i, j) and hypothesis d:
+ *     r_{w,d}  = the per-window correlation of rmx_caf_batch_request, exactly: the same phasor table rot_d, indexed
+ *                n = 0 .. N-1 in EVERY window (the phase origin of a window is immaterial under |.|^2), the band mask and
+ *                PHAT of window w on each stored spectrum after the rotation;
+ *     s_d[k]   = sum over the group's windows, in window order, of |r_{w,d}[k]|^2, in float32, by one thread;
+ *     m_d[k]   = sqrt(s_d[k]);
+ *   per hypothesis S4-S6 of rmx_xcorr_batch on m_d -- the sliced rule of rmx_xcorr_batch_bounded on the group's interval --
+ *   give (lag_d, frac_d, peak_d); dop_idx = d* is the d-major first maximum of peak_d (strict >: ties keep the lowest d);
+ *   dop_frac is rmx_caf_batch_request's parabola through the integrated peak_d of d* - 1, d*, d* + 1.  The winner is never
+ *   revisited.
+ *   refine and quality are those of rmx_xcorr_batch_quality with the same `integrate`, computed on the window sequences
+ *   (x_{i,w}, x_{j,w} * rot_d*) of the group: quality uses the coarse integrated peak p0 = peak_d*; refine then
+ *   overwrites lag_int, lag_frac and peak by the rule of rmx_xcorr_batch_refined (f[u] summed over the group's windows).
+ *   Parity against a float restatement (tests/caf_integrated_ref.py stacks tests/caf_request_ref.py, integrated_ref.py,
+ *   refined_ref.py and quality_ref.py): the bars of rmx_caf_batch_quality and rmx_xcorr_batch_integrated, with that
+ *   entry's (K - 1) 2^-24 note on the in-order sum; dop_idx and lag_int exact where the restatement's hypothesis margin
+ *   and top-two lag margin, both taken on the integrated vectors, exceed 1e-5.
+ * Range: the sum of K windows' |r|^2 is K times as large as one window's: divide the |sample| bound of rmx_xcorr_batch by
+ *   K^(1/4), as for rmx_xcorr_batch_integrated.
+ * integrate == 1 IS rmx_caf_batch_quality with the same arguments (that entry forwards here): the same kernels, the same
+ *   launches, bit-identical outputs.  With refine == 0 and quality == NULL nothing is launched behind the selection;
+ *   lag_int, lag_frac and peak of a call with quality are bit-identical to the same call without it.  A call whose
+ *   hypotheses are applied to buoy j's windows on the host (the same float32 phasors) and that goes through
+ *   rmx_xcorr_batch_quality with the same integrate and request gives, at the coarse first maximum, the same bits.
+ * Otherwise the forward kernels are those of the search, on all windows, and every route of rmx_caf_batch_quality takes
+ *   the call with its integrating pair kernels reading operand j from the de-rotated set: the pack <LagBounds, Integrate,
+ *   CafOperand> of k_pair_str and g_pair_small (radio-mapper_amd/csrc/integrate.hpp); the four-step row kernels take the
+ *   second operand set as they are and g_cols_inv's integrating instantiation sums their products (never g_rows_fused).
+ *   - N = 4096, every hypothesis in one launch (the condition is rmx_caf_batch's, on n_windows): two forward launches, ONE
+ *     integrating pair launch over n_dopplers * G virtual groups gv = d * G + g (operand j at virtual windows gv * K + kw,
+ *     operand i and the lag interval at real group g), the selection over [n_dopplers][G][n_pairs], then at most one
+ *     k_quality and one k_refine launch.
+ *   - N = 4096 in chunks, the small route, the four-step route: chunks are rounded down to whole groups; per hypothesis
+ *     forward, the integrating pair kernels, k_caf_select(_fd) on the chunk's G' * n_pairs slots; then, with refine or
+ *     quality, the second sweep of rmx_caf_batch_quality, whose workgroups walk their group's K windows.
+ * Refusals (RMX_E_INVAL, the text in rmx_last_error, nothing staged or written), in this order: rmx_caf_batch_quality's
+ *   head (a NULL buffer, a misaligned device pointer, n_dopplers); integrate < 1, or n_windows not a positive multiple of
+ *   it (the values in the text; integrate == 1 takes an empty batch as rmx_caf_batch_quality does); the batch shape and
+ *   the pair list; the weighting and the bands, the text naming the real window; the bounds, the text saying "group" when
+ *   integrate > 1; dop_frac overlapping another output; refine; quality overlapping another output or misaligned -- every
+ *   extent G * n_pairs slots; then the route: a chunk holds whole groups, and a K that no chunk of the ctx holds (option
+ *   "chunk_windows" at N = 4096, the scratch budget elsewhere) is refused with a text that says so, never a silent
+ *   split.  RMX_E_UNSUPPORTED for the column tile of rmx_xcorr_batch_integrated.
+ * Several bands under the search (rmx_xcorr_batch_bands) are not offered. */
+int rmx_caf_batch_integrated(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                             const double* doppler_cps, int n_dopplers, int integrate,
+                             const double* band_cps, int band_per_window, unsigned weighting,
+                             const int32_t* lag_bounds, int bounds_per_group, int refine,
+                             int32_t* dop_idx, float* dop_frac,
+                             int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
 
 /* Batched hyperbolic position solve: the consumer of the lags.  One
  * independent 3-unknown least-squares problem per window with the reference's objective

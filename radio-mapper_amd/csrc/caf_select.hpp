@@ -12,13 +12,15 @@ namespace rmx {
 // The tail of k_refine's and k_quality's parameter pack under rmx_caf_batch_quality (refine.hpp, quality.hpp): output slot
 // o = (window, pair) correlates operand i from the kernel's own spectra (the un-rotated set) at (window, i) and operand j
 // from the de-rotated set of ITS winner dop[o] -- chosen by the selection kernels below, which have run.
+// rmx_caf_batch_integrated: a slot is a (group, pair) and the kernels walk the group's a.k windows, window g K + kw of
+// either set; dop is indexed by the group's slot and hyp_items stays W * B, so virtual window dop[o] * W + g K + kw.
 //   every hypothesis resident (the one-launch path of N = 4096): d < 0; the set of hypothesis h starts hyp_items items
 //       into spec_j, and slot o reads item dop[o] * hyp_items + window * n_buoys + j (virtual window dop[o] * W + window);
 //   one hypothesis resident (the second sweep of the per-hypothesis routes): d >= 0 is the hypothesis whose de-rotated
 //       set spec_j holds, laid out as the kernel's own; a workgroup whose slot was won by another hypothesis returns at
 //       once, in front of its first barrier, and touches nothing.
 struct CafWinner {
-    const int* dop;          // device dop_idx, [n_windows][n_pairs]: indexed by the global output slot
+    const int* dop;          // device dop_idx, [n_windows][n_pairs] ([G][n_pairs] integrated): indexed by the global output slot
     const float2* spec_j;    // the de-rotated spectra, [item][L] in the layout's order
     long hyp_items;          // items (window, buoy) per resident hypothesis, or 0
     int d;                   // the one resident hypothesis, or -1: all are

@@ -494,8 +494,10 @@ struct GPair {
 // BS: empty, or one BandSet (the banded integrating instantiation, xspec_bands.hpp): gl is then an output ROW, group
 // gl / n_bands under band gl % n_bands, and first_group the chunk's first row; every window's product is formed on load
 // under the band of THAT window, a dropped bin loading nothing (+0), as the banded g_pair_small does.
+// spec_j: where operand j is read -- spec itself, or the de-rotated set of one hypothesis, laid out as spec (the pack
+// <LagBounds, Integrate, CafOperand> of the integrated Doppler search).
 template <class... BS>
-__device__ __forceinline__ void pair_small_integ(const float2* __restrict__ spec, const float2* __restrict__ tw,
+__device__ __forceinline__ void pair_small_integ(const float2* __restrict__ spec, const float2* spec_j, const float2* __restrict__ tw,
                                                  const GPair* __restrict__ pairs, int n_pairs, int n_buoys, int N, int logL,
                                                  long first_group, float out_scale, int* __restrict__ lag_int,
                                                  float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K,
@@ -520,7 +522,7 @@ __device__ __forceinline__ void pair_small_integ(const float2* __restrict__ spec
     for (int kw = 0; kw < K; ++kw) {
         const long wl = (long)gr * K + kw;
         const float2* xi = spec + (wl * n_buoys + pr.i) * L;
-        const float2* xj = spec + (wl * n_buoys + pr.j) * L;
+        const float2* xj = spec_j + (wl * n_buoys + pr.j) * L;
         if constexpr (sizeof...(BS) > 0) {
             const XBand bd = band_of_window(band_set_of(bs_pack...), wl, band_m);
             batched<4>(tid, L, nthr,
@@ -597,11 +599,15 @@ __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ 
                                                           float* __restrict__ lag_frac, float* __restrict__ peak,
                                                           LB... lb_pack) {
     if constexpr (kIntegrating<LB...> && kBanded<LB...>) {   // (first_window: the chunk's first ROW, group * n_bands + band)
-        pair_small_integ(spec, tw, pairs, n_pairs, n_buoys, N, logL, first_window, out_scale, lag_int, lag_frac, peak,
+        pair_small_integ(spec, spec, tw, pairs, n_pairs, n_buoys, N, logL, first_window, out_scale, lag_int, lag_frac, peak,
                          integ_bounds(lb_pack...), integ_windows(lb_pack...), band_set_of(lb_pack...));
         return;
+    } else if constexpr (kCafOperand<LB...>) {   // (the integrated Doppler search: operand j from the de-rotated set)
+        pair_small_integ(spec, spec_j, tw, pairs, n_pairs, n_buoys, N, logL, first_window, out_scale, lag_int, lag_frac, peak,
+                         integ_bounds(lb_pack...), integ_windows(lb_pack...));
+        return;
     } else if constexpr (kIntegrating<LB...>) {   // (first_window: the chunk's first GROUP; spec_j == spec)
-        pair_small_integ(spec, tw, pairs, n_pairs, n_buoys, N, logL, first_window, out_scale, lag_int, lag_frac, peak,
+        pair_small_integ(spec, spec, tw, pairs, n_pairs, n_buoys, N, logL, first_window, out_scale, lag_int, lag_frac, peak,
                          integ_bounds(lb_pack...), integ_windows(lb_pack...));
         return;
     }

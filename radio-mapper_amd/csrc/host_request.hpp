@@ -198,6 +198,14 @@ inline int check_alignment(unsigned flags, const void* iq, const OutArray* outs,
     return RMX_OK;
 }
 
+// K and the group count of the grouped entries (integrate, rmx_caf_batch_integrated): the text carries the values
+inline int check_groups(int integrate, int n_windows, std::string* err) {
+    if (integrate < 1) return refuse(err, "integrate = %d: at least one window per group", integrate);
+    if (n_windows <= 0 || n_windows % integrate != 0)
+        return refuse(err, "n_windows = %d is not a positive multiple of integrate = %d", n_windows, integrate);
+    return RMX_OK;
+}
+
 // Every check of the nine rmx_xcorr_batch* entries, in the order include/rmx.h promises, so an input with several bad
 // arguments is refused for the same one whichever entry it came through: the grouped entries' (integrate, the group
 // count), a NULL buffer, a device pointer aligned to less than its element, n_bands, the weighted entry's, the batch
@@ -207,9 +215,8 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
     *r = Request{};
     if (a.bounds_required && !a.lag_bounds) return refuse(err, "NULL buffer");
     if (a.grouped) {   // K and the group count
-        if (a.integrate < 1) return refuse(err, "integrate = %d: at least one window per group", a.integrate);
-        if (a.n_windows <= 0 || a.n_windows % a.integrate != 0)
-            return refuse(err, "n_windows = %d is not a positive multiple of integrate = %d", a.n_windows, a.integrate);
+        const int rc_g = check_groups(a.integrate, a.n_windows, err);
+        if (rc_g != RMX_OK) return rc_g;
         // (the full intervals an integrated call without bounds carries are sized by the pair count, so that is looked at here)
         if (a.integrate > 1 && !a.lag_bounds && a.pairs && a.n_pairs < 0) return refuse(err, "n_pairs %d < 0", a.n_pairs);
     }
@@ -283,21 +290,24 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
 
 // The tail of rmx_caf_batch_request, behind its own head (NULL buffer, n_dopplers, the batch shape, the pair list):
 // `a` with n_pairs resolved; the weighted entry's checks, the bounded entry's, then dop_frac over another output, and what
-// rmx_caf_batch_quality adds behind them (a.refine, a.quality, a.flags).
+// rmx_caf_batch_quality adds behind them (a.refine, a.quality, a.flags).  rmx_caf_batch_integrated (a.grouped, with
+// a.integrate = K checked by check_groups): the bands stay per window, the bounds are per GROUP and every output extent
+// is G * n_pairs slots, G = n_windows / K; K > 1 without bounds carries the full interval per pair, as check_request's.
 inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const float* dop_frac, Request* r, std::string* err) {
     *r = Request{};
     r->n_pairs = a.n_pairs;
+    const int K = a.grouped ? a.integrate : 1;
+    const size_t slots = (size_t)(a.n_windows / K) * a.n_pairs;
     int rc;
     if (a.band_cps || a.weighting != RMX_WEIGHT_NONE) {
         rc = check_bands(a, r, err);
         if (rc != RMX_OK) return rc;
     }
     if (a.lag_bounds) {
-        rc = check_bounds(a, 1, r, err);
+        rc = check_bounds(a, K, r, err);
         if (rc != RMX_OK) return rc;
     }
     if (dop_frac) {
-        const size_t slots = (size_t)a.n_windows * a.n_pairs;
         const OutArray outs[4] = {{"dop_idx", dop_idx}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}};
         char needs[96];
         std::snprintf(needs, sizeof needs, "its %zu floats need a buffer of their own", slots);
@@ -309,7 +319,6 @@ inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const
     if (a.refine != 0 && a.refine != 2 && a.refine != 4 && a.refine != 8 && a.refine != 16)
         return refuse(err, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", a.refine);
     if (a.quality) {
-        const size_t slots = (size_t)a.n_windows * a.n_pairs;
         OutArray outs[5] = {{"dop_idx", dop_idx}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}, {"dop_frac", dop_frac}};
         char needs[96];
         std::snprintf(needs, sizeof needs, "the %zu x 4 floats of quality need a buffer of their own", slots);
@@ -319,7 +328,18 @@ inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const
         rc = check_alignment(a.flags & RMX_OUT_DEVICE, nullptr, q, 1, err);
         if (rc != RMX_OK) return rc;
     }
+    r->integ = K;
     r->refine = a.refine;
+    if (K > 1 && !a.lag_bounds) {   // the integrating kernels always carry bounds: the full interval per pair, one row for all
+        r->own_bounds.resize(2 * (size_t)r->n_pairs);
+        for (int q = 0; q < r->n_pairs; ++q) {
+            r->own_bounds[2 * q] = -(a.n_samples - 1);
+            r->own_bounds[2 * q + 1] = a.n_samples - 1;
+        }
+        r->bounds = r->own_bounds.data();
+        r->bound_rows = r->n_pairs;
+        r->bounded = true;
+    }
     return RMX_OK;
 }
 

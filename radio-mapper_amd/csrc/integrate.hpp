@@ -17,6 +17,9 @@
 //                                   into the tile image and the tile record, the halo and g_final run as they are
 // The lag windows of an integrating kernel are indexed by GROUP (lag_bounds.hpp: w is the group, wstride the int32
 // elements per group).
+// The Doppler search may be integrated too (rmx_caf_batch_integrated): the pack <LagBounds, Integrate, CafOperand> below
+// gives k_pair_str and g_pair_small their operand j from the de-rotated spectra; the four-step row kernels take that set
+// as they are (spec_j) and cols_inv_integ sums whatever products they made.
 // A banded call may be integrated too (rmx_xcorr_batch_bands_integrated): xspec_bands.hpp adds the pack
 // <LagBounds, Integrate, BandSet>, whose work item is (group, band, pair) and whose lag windows and outputs are indexed by
 // the row group * n_bands + band.
@@ -45,5 +48,26 @@ inline constexpr bool kIntegrating = integ_pack<P...>::value;
 
 __device__ __forceinline__ LagBounds integ_bounds(LagBounds lb, Integrate) { return lb; }
 __device__ __forceinline__ int integ_windows(LagBounds, Integrate ig) { return ig.k; }
+
+// The integrated Doppler search (rmx_caf_batch_integrated): the pack <LagBounds, Integrate, CafOperand> of k_pair_str and
+// g_pair_small reads operand j from the kernel's second spectrum set, spec_j -- the de-rotated spectra -- instead of the
+// first.  Where one launch holds every hypothesis (N = 4096) a work item is a VIRTUAL group gv = d * groups + g: its K
+// de-rotated windows are virtual windows gv * K + kw of spec_j (d * W + g * K + kw, contiguous), operand i and the lag
+// interval are those of the REAL group gv % groups, the output slot stays virtual.  groups == 0: spec_j holds one
+// hypothesis, laid out as spec, and the group is the real one.
+struct CafOperand {
+    int groups;   // real groups per hypothesis of a launch over every hypothesis, or 0
+};
+template <>
+struct integ_pack<LagBounds, Integrate, CafOperand> : std::true_type {};
+template <class... P>
+struct caf_operand_pack : std::false_type {};
+template <>
+struct caf_operand_pack<LagBounds, Integrate, CafOperand> : std::true_type {};
+template <class... P>
+inline constexpr bool kCafOperand = caf_operand_pack<P...>::value;
+__device__ __forceinline__ LagBounds integ_bounds(LagBounds lb, Integrate, CafOperand) { return lb; }
+__device__ __forceinline__ int integ_windows(LagBounds, Integrate ig, CafOperand) { return ig.k; }
+__device__ __forceinline__ int caf_groups(LagBounds, Integrate, CafOperand co) { return co.groups; }
 
 }  // namespace rmx

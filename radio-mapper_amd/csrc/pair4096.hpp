@@ -302,8 +302,13 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
 // gl / n_bands under band gl % n_bands, and first_group the chunk's first row; the spectra are the group's real windows',
 // and pair_body's 16-bit keep word zeroes the product -- built once when the band set is shared, rebuilt in front of
 // every window's product when the bands are per window.
-template <class... BS>
-__device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec, const float4* __restrict__ tw1_g,
+// CAF (the pack <LagBounds, Integrate, CafOperand>, integrate.hpp): operand j comes from spec_j, the de-rotated set; with
+// caf_groups > 0 the launch holds every hypothesis and gl is a VIRTUAL group d * caf_groups + g -- operand j at virtual
+// windows gl * K + kw, operand i and the lag interval at real group gl % caf_groups, the output slot virtual.  Otherwise
+// spec_j and caf_groups are not read.
+template <bool CAF = false, class... BS>
+__device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec, const float4* spec_j, int caf_groups,
+                                                const float4* __restrict__ tw1_g,
                                                 const float2* __restrict__ tw2_g, const PairItem* __restrict__ items,
                                                 const int* __restrict__ part_begin, int n_parts, int n_buoys, int n_pairs,
                                                 int xcd_map, long first_group, float out_scale, int* __restrict__ lag_int,
@@ -366,12 +371,17 @@ __device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec,
         band_per_window = bs.wstride != 0;
         keep = keep_of(0);
     }
+    if constexpr (CAF) {   // the real group: operand i and the lag interval (gl stays the virtual one)
+        if (caf_groups > 0) gr = gl % caf_groups;
+    }
     const long gbase = (long)gr * K * n_buoys;   // item of the group's first window, buoy 0 (chunk-local)
     float4 sa[8], sb[8];   // X_i and X_j of the window about to be processed
     PairItem pi = items[it_begin < it_end ? it_begin : 0];
     auto request = [&](const PairItem& pr, int kw) {
         const float4* xi = spec + (gbase + (long)kw * n_buoys + pr.i) * (8 * kThreads);
         const float4* xj = spec + (gbase + (long)kw * n_buoys + pr.j) * (8 * kThreads);
+        if constexpr (CAF)   // the (virtual) group's window kw in the de-rotated set
+            xj = spec_j + (((long)gl * K + kw) * n_buoys + pr.j) * (8 * kThreads);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             sa[j] = xi[j * kThreads + t];
@@ -430,7 +440,7 @@ __device__ __forceinline__ void pair_body_integ(const float4* __restrict__ spec,
         }
         if (p && u == 0) acc[0] = -1.0f;   // lag -M is not part of 'full'
         int klo, khi;
-        lag_window(lb, first_group + gl, out_idx, kM - 1, klo, khi);
+        lag_window(lb, first_group + (CAF ? gr : gl), out_idx, kM - 1, klo, khi);
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[q] = lag_mask(acc[q], kbase + q * 256, klo, khi);
         float tmax = acc[0];
@@ -701,16 +711,20 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
         lag_int, lag_frac, peak, i_wrap
 
 // LB: empty, one LagBounds (the bounded instantiation), <LagBounds, Integrate> (the integrating one, integrate.hpp:
-// first_window is then the chunk's first GROUP; spec_j and i_wrap are not used), <BandSet> / <LagBounds, BandSet> (the
+// first_window is then the chunk's first GROUP; spec_j and i_wrap are not used), <LagBounds, Integrate, CafOperand> (the
+// integrated Doppler search's: operand j from spec_j), <BandSet> / <LagBounds, BandSet> (the
 // banded ones, xspec_bands.hpp: first_window is then the chunk's first VIRTUAL window), or <LagBounds, Integrate, BandSet>
 // (the banded integrating one: first_window is the chunk's first ROW, group * n_bands + band)
 template <class... LB>
 __global__ __launch_bounds__(kThreads, kIntegrating<LB...> ? 2 : 4) void k_pair_str(RMX_PAIR_ARGS, LB... lb) {
     if constexpr (kIntegrating<LB...> && kBanded<LB...>) {
-        pair_body_integ(spec, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
+        pair_body_integ(spec, spec, 0, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
                         lag_int, lag_frac, peak, integ_bounds(lb...), integ_windows(lb...), band_set_of(lb...));
+    } else if constexpr (kCafOperand<LB...>) {   // (first_window: the chunk's first GROUP; i_wrap is not used)
+        pair_body_integ<true>(spec, spec_j, caf_groups(lb...), tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map,
+                              first_window, out_scale, lag_int, lag_frac, peak, integ_bounds(lb...), integ_windows(lb...));
     } else if constexpr (kIntegrating<LB...>) {
-        pair_body_integ(spec, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
+        pair_body_integ(spec, spec, 0, tw1_g, tw2_g, items, part_begin, n_parts, n_buoys, n_pairs, xcd_map, first_window, out_scale,
                         lag_int, lag_frac, peak, integ_bounds(lb...), integ_windows(lb...));
     } else if constexpr (kBanded<LB...>) {
         pair_body<kHasBounds<LB...>>(RMX_PAIR_PASS, lag_bounds_of(lb...), band_set_of(lb...));

@@ -472,7 +472,7 @@ static int refine_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, i
     // k_refine<U, layout>; U was checked by the entry (16 is the last it admits), the four-step layout is the last one
     return with_one_of<kRefKfwd, kRefSmall, kRefRows>(sv.layout, [&](auto lay) {
         return with_one_of<2, 4, 8, 16>(call.refine, [&](auto u) {
-            if (cw)   // rmx_caf_batch_quality: operand j from the winner's de-rotated set (never banded or integrated)
+            if (cw)   // rmx_caf_batch_quality / _integrated: operand j from the winner's de-rotated set (never banded; a.k windows per slot)
                 return launch(c, kTkRefine, k_refine<decltype(u)::value, decltype(lay)::value, CafWinner>, dim3(grid), dim3(kRefThreads), 0,
                               a, d_lag, d_frac, d_peak, *cw);
             if (call.banded() && call.integrated())
@@ -703,7 +703,7 @@ static int generic_init(rmx_ctx* c) {
         RMX_MEM(c->g_tw.assign(t));
         c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, 0, 0, 0, 0, 0, c->knobs);
         rc = allow_lds(c, (size_t)gen::lp(L) * 8 + 1024 * 8, g_pair_small<>, g_pair_small<LagBounds>, g_pair_small<LagBounds, Integrate>,
-                       g_pair_small<LagBounds, Integrate, BandSet>, g_pair_small<BandSet>, g_pair_small<LagBounds, BandSet>, g_fwd_small<false>, g_fwd_small<true>,
+                       g_pair_small<LagBounds, Integrate, CafOperand>, g_pair_small<LagBounds, Integrate, BandSet>, g_pair_small<BandSet>, g_pair_small<LagBounds, BandSet>, g_fwd_small<false>, g_fwd_small<true>,
                        g_fwd_small<false, XWeight>, g_fwd_small<true, XWeight>);
         for (int d = 0; d < 2 && rc == RMX_OK; ++d) rc = allow_lds(c, c->gk.wf_lds[d], c->gk.wf[d][0], c->gk.wf[d][1]);
         if (rc) return rc;
@@ -925,6 +925,9 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
         };
         if (call.integrated() && call.banded())   // one workgroup per (group, band, pair); the bounds per row group * n_bands + band
             return go(g_pair_small<LagBounds, Integrate, BandSet>, slots / call.integ, v0 / call.integ, call.lb, Integrate{call.integ}, bs);
+        if (call.integrated() && use_rot)   // rmx_caf_batch_integrated: operand j from the de-rotated set of one hypothesis
+            return go(g_pair_small<LagBounds, Integrate, CafOperand>, slots / call.integ, (long)(w0 / call.integ), call.lb,
+                      Integrate{call.integ}, CafOperand{0});
         if (call.integrated())   // one workgroup per (group, pair); w0 and wc are whole groups, the bounds per group
             return go(g_pair_small<LagBounds, Integrate>, slots / call.integ, (long)(w0 / call.integ), call.lb, Integrate{call.integ});
         if (call.banded()) return call.bounded() ? go(g_pair_small<LagBounds, BandSet>, slots, v0, call.lb, bs) : go(g_pair_small<BandSet>, slots, v0, bs);
@@ -1040,6 +1043,14 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
         bs.w0 = w0;
         return str(k_pair_str<LagBounds, Integrate, BandSet>, rows, (rows % 8 == 0) ? 1 : 0, first / call.integ, 0, call.lb,
                    Integrate{call.integ}, bs);
+    }
+    if (call.integrated() && use_rot) {
+        // rmx_caf_batch_integrated: operand j from the de-rotated set.  One hypothesis (n_bins == 1): the chunk's groups, as
+        // below.  All hypotheses in one launch: virtual group = hypothesis * groups + group (wc counts virtual windows here),
+        // operand i and the bounds at the real group, the output slot virtual
+        const int gc = wc / call.integ;
+        return str(k_pair_str<LagBounds, Integrate, CafOperand>, gc, (gc % 8 == 0) ? 1 : 0, (long)(w0 / call.integ), 0, call.lb,
+                   Integrate{call.integ}, CafOperand{i_wrap / call.integ});
     }
     if (call.integrated()) {
         // always the streaming kernel's integrating instantiation, one work item per (group, pair); w0 and wc are whole
@@ -1330,7 +1341,7 @@ int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max
         // (rmx_xcorr_batch_bounded: the peak-searching ones)
         int rc_l = allow_lds(c, kLdsBytes, k_fwd<false>, k_fwd<true>, k_fwd<false, XWeight>, k_fwd<true, XWeight>, k_pair_str<>,
                              k_pair_str<LagBounds>, k_pair_str<BandSet>, k_pair_str<LagBounds, BandSet>,
-                             k_pair_str<LagBounds, Integrate, BandSet>);
+                             k_pair_str<LagBounds, Integrate, BandSet>, k_pair_str<LagBounds, Integrate, CafOperand>);
         if (rc_l == RMX_OK)
             rc_l = allow_lds(c, kLdsResBytes, k_pair_res<>, k_pair_res<LagBounds>, k_pair_res<BandSet>, k_pair_res<LagBounds, BandSet>);
         if (rc_l == RMX_OK) rc_l = allow_lds(c, kLdsWinBytes, k_win<false>, k_win<true>, k_win_lb<false>, k_win_lb<true>);
@@ -1858,12 +1869,30 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
 // operand i from the un-rotated spectra and operand j from the winner's de-rotated ones.  Where every hypothesis' set is
 // resident (the one-launch path of N = 4096) that is one launch of each; elsewhere the hypotheses of a chunk are swept a
 // second time, each forward pass followed by the two kernels, whose workgroups return unless their slot's winner is resident.
+// It is rmx_caf_batch_integrated with one window per group: the same kernels, the same launches
 int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                           const double* doppler_cps, int n_dopplers,
                           const double* band_cps, int band_per_window, unsigned weighting,
                           const int32_t* lag_bounds, int bounds_per_window, int refine,
                           int32_t* dop_idx, float* dop_frac,
                           int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
+    return rmx_caf_batch_integrated(c, iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, 1, band_cps, band_per_window, weighting,
+                                    lag_bounds, bounds_per_window, refine, dop_idx, dop_frac, lag_int, lag_frac, peak, quality, flags);
+}
+
+// The Doppler search integrated noncoherently over groups of K = `integrate` consecutive windows: coherent per window
+// under each hypothesis, |r|^2 summed over the group's windows, ONE peak search per (group, pair, hypothesis).  The
+// forward kernels are the search's; the pair kernels are the integrating instantiations with operand j from the
+// de-rotated set (pack <LagBounds, Integrate, CafOperand>, integrate.hpp; the four-step row kernels take spec_j as they
+// are and g_cols_inv's integrating instantiation sums their products); the selection runs on G * n_pairs slots; k_quality
+// and k_refine <CafWinner> walk the group's windows.  K = 1 is rmx_caf_batch_quality itself: none of the above is reached.
+int rmx_caf_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                             const double* doppler_cps, int n_dopplers, int integrate,
+                             const double* band_cps, int band_per_window, unsigned weighting,
+                             const int32_t* lag_bounds, int bounds_per_group, int refine,
+                             int32_t* dop_idx, float* dop_frac,
+                             int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
+    const int bounds_per_window = bounds_per_group;   // (per output row: the window, or the group)
     if (!c) return RMX_E_INVAL;
     if (!iq || !dop_idx || !lag_int || !lag_frac || !peak || !doppler_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
     std::string why;
@@ -1872,11 +1901,14 @@ int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32
         if (host::check_alignment(flags, iq, outs, 5, &why) != RMX_OK) return fail(c, RMX_E_INVAL, "%s", why.c_str());
     }
     if (n_dopplers < 1 || n_dopplers > 4096) return fail(c, RMX_E_INVAL, "n_dopplers %d not in 1..4096", n_dopplers);
+    // (one window per group is rmx_caf_batch_quality, which takes an empty batch)
+    if (integrate != 1 && host::check_groups(integrate, n_windows, &why) != RMX_OK) return fail(c, RMX_E_INVAL, "%s", why.c_str());
+    const int K = integrate;
     int rc = host::check_batch(c->n_buoys, c->max_windows, n_windows, pairs, &n_pairs, &why);
     if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
     if (n_windows == 0 || n_pairs == 0) return RMX_OK;
     const int B = c->n_buoys, N = c->n_samples;
-    XcorrCall call;   // the plain request unless the checks below say otherwise; never integrated
+    XcorrCall call;   // the plain request unless the checks below say otherwise
     RMX_HIP(c, hipSetDevice(c->device));
     // N = 4096, one chunk: all hypotheses in ONE forward launch and ONE pair launch (virtual window = hypothesis x
     // window) instead of three launches per hypothesis -- 21 hypotheses on one frequency group: 431 -> ~60 us
@@ -1885,12 +1917,12 @@ int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32
                             (long)n_dopplers * n_windows < (1L << 20);
     if (!c->generic && !c->ppb_user) {               // (N = 4096: blocks sized to this batch, not to the previous call's)
         int q = 7;
-        (void)host::split_cost4096(c->n_cus, c->n_buoys, n_pairs, batch_bins ? n_windows * n_dopplers : n_windows, 0, &q);
+        (void)host::split_cost4096(c->n_cus, c->n_buoys, n_pairs, (batch_bins ? n_windows * n_dopplers : n_windows) / K, 0, &q);
         c->pairs_per_block = q;
     }
     rc = build_plan(c, pairs, n_pairs);              // validates the pair list
     if (rc != RMX_OK) return rc;
-    const size_t out_elems = (size_t)n_windows * n_pairs;
+    const size_t out_elems = (size_t)(n_windows / K) * n_pairs;   // one slot per (group, pair)
     {   // the request: the weighted entry's checks, the bounded entry's, then dop_frac; nothing is staged before the last
         host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, band_per_window,
                                             weighting, lag_bounds, bounds_per_window);
@@ -1900,9 +1932,21 @@ int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32
         a.refine = refine;
         a.quality = quality;
         a.flags = flags;
+        a.grouped = true;
+        a.integrate = K;
         host::Request rq;
         rc = host::check_caf_request(a, dop_idx, dop_frac, &rq, &why);
         if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
+        if (K > 1) {   // the route: a chunk holds whole groups (the ctx's chunk as it stands; generic_ensure may still halve it)
+            const host::RouteCaps caps = route_caps(c);
+            host::RoutePlan rp;
+            if ((c->generic ? caps.g_chunk : caps.chunk_windows) < K) rp.refused = host::kRefuseIntegChunk;
+            else if (c->generic && (1L << caps.logL) > caps.small_maxl && caps.col_tile > (long)caps.integ_max_per_thread * caps.cols_threads)
+                rp.refused = host::kRefuseIntegTile;
+            rc = route_refusal(c, rp, caps, K, 1);
+            if (rc != RMX_OK) return rc;
+        }
+        call.integ = rq.integ;
         rc = describe_call(c, rq, &call);
         if (rc != RMX_OK) return rc;
     }
@@ -1968,6 +2012,14 @@ int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32
         rc = ensure_spec(c, n_windows < chunk ? n_windows : chunk);
         if (rc != RMX_OK) return rc;
     }
+    if (K > 1) {   // whole groups per chunk, never a silent split (a failed allocation may have halved the generic chunk)
+        chunk = chunk / K * K;
+        if (chunk == 0) {
+            host::RoutePlan rp;
+            rp.refused = host::kRefuseIntegChunk;
+            return route_refusal(c, rp, route_caps(c), K, 1);
+        }
+    }
     const float osc = out_scale4096();
     const SpecView sv = spec_view(c);
     if (batch_bins) {
@@ -1981,7 +2033,8 @@ int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32
         if (rc == RMX_OK && dop_frac)
             rc = launch(c, kTkCafSelect, k_caf_select_all_fd, sgrid, dim3(256), 0, n_dopplers, (long)out_elems, c->caf_lag, c->caf_frac,
                         c->caf_peak, b_dop, b_lag, b_frac, b_peak, b_dfrac);
-        // every de-rotated set is resident: slot (w, q) reads operand j at virtual window dop_idx * W + w
+        // every de-rotated set is resident: slot (w, q) reads operand j at virtual window dop_idx * W + w (a group's slot
+        // (g, q): at dop_idx * W + g K + kw, its K windows in order)
         const CafWinner cw{b_dop, reinterpret_cast<const float2*>(c->d_spec_r.get()), (long)n_windows * B, -1};
         if (rc == RMX_OK && tail.qualified()) rc = quality_chunk(c, tail, sv, 0, n_windows, n_pairs, b_peak, &cw);
         if (rc == RMX_OK && tail.refined()) rc = refine_chunk(c, tail, sv, 0, n_windows, n_pairs, b_lag, b_frac, b_peak, &cw);
@@ -1995,7 +2048,7 @@ int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32
             if (rc != RMX_OK) break;
             rc = sv.pairs(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true, false);
             if (rc != RMX_OK) break;
-            const long first = (long)w0 * n_pairs, cnt = (long)wc * n_pairs;
+            const long first = (long)(w0 / K) * n_pairs, cnt = (long)(wc / K) * n_pairs;   // the chunk's output rows
             const dim3 sgrid((unsigned)((cnt + 255) / 256));
             if (dop_frac)
                 rc = launch(c, kTkCafSelect, k_caf_select_fd, sgrid, dim3(256), 0, d, n_dopplers, first, cnt, (long)out_elems, c->caf_lag,

@@ -236,20 +236,25 @@ class MultiXcorrEngine:
                          tails=[(), (), (), (4,)][:n_out])
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
-            whiten: bool = False, fine: bool = False, refine: int = 0, quality: bool = False):
+            whiten: bool = False, fine: bool = False, refine: int = 0, quality: bool = False, integrate=None):
         """Cross-ambiguity search -> (doppler_idx, lag_int, lag_frac, peak), each [W][P]; with fine=True (doppler_idx,
         dop_frac, lag_int, lag_frac, peak) (XcorrEngine.caf).  lag_bounds [P][2] and band [2] go to every block whole,
         [W][P][2] and [W][2] are cut into each block's own windows' rows, as correlate() cuts them.  refine and quality
         are handed to every block's call (quality: the blocks' figures [W][P][4] as the last array); with neither, every
-        block makes exactly the call it made without them."""
+        block makes exactly the call it made without them.
+        integrate: K windows per group (XcorrEngine.caf): whole groups are sharded over the devices, as correlate() shards
+        them; the results and per-group lag_bounds are [W // K][.], the band stays per window."""
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
         P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
-        lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
-        bd, band_pw = check_band(band, iq.shape[0])
+        K = 1 if integrate is None else check_integrate(integrate, iq.shape[0])
         U = check_refine(refine)
         more = {"refine": U, "quality": True} if quality else ({"refine": U} if U else {})
+        if K > 1:
+            return self._caf_integrated(iq, doppler_cps, pairs, lag_bounds, band, whiten, fine, more, K, P)
+        lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
+        bd, band_pw = check_band(band, iq.shape[0])
         if lb is None and bd is None and not whiten and not fine and not more:
             return self._run(iq.shape[0], lambda eng, s, c: eng.caf(iq[s:s + c], doppler_cps, pairs), 4,
                              (np.int32, np.int32, np.float32, np.float32), P)
@@ -263,3 +268,30 @@ class MultiXcorrEngine:
         if quality:
             dtypes, tails = dtypes + (np.float32,), tails + [(4,)]
         return self._run(iq.shape[0], block_call, len(dtypes), dtypes, P, tails=tails)
+
+    def _caf_integrated(self, iq, doppler_cps, pairs, lag_bounds, band, whiten, fine, more, K, P):
+        """caf(integrate=K > 1): whole groups per device, as _correlate_integrated"""
+        W = iq.shape[0]
+        G = W // K
+        lb, per_group = check_lag_bounds(lag_bounds, G, P)
+        bd, band_pw = check_band(band, W)
+        dtypes = (np.int32, np.float32, np.int32, np.float32, np.float32) if fine else (np.int32, np.int32, np.float32, np.float32)
+        tails = [()] * len(dtypes)
+        if more.get("quality"):
+            dtypes, tails = dtypes + (np.float32,), tails + [(4,)]
+
+        def block_call(eng, gs, gc):
+            # the engines are sized for an even split of the WINDOWS; a block of whole groups may be a little larger
+            step = getattr(eng, "max_windows", gc * K) // K
+            if step < 1:
+                raise ValueError(f"integrate = {K} windows per group is more than one device's engine holds "
+                                 f"({eng.max_windows} windows)")
+            parts = []
+            for g0 in range(gs, gs + gc, step):
+                g1 = min(g0 + step, gs + gc)
+                parts.append(eng.caf(iq[g0 * K:g1 * K], doppler_cps, pairs,
+                                     lag_bounds=None if lb is None else (lb[g0:g1] if per_group else lb),
+                                     band=None if bd is None else (bd[g0 * K:g1 * K] if band_pw else bd),
+                                     whiten=whiten, fine=fine, integrate=K, **more))
+            return tuple(np.concatenate([p[k] for p in parts]) for k in range(len(dtypes)))
+        return self._run(W, block_call, len(dtypes), dtypes, P, n_rows=G, tails=tails)

@@ -99,6 +99,8 @@ def load_library():
     lib.rmx_caf_batch_request.restype = ci
     lib.rmx_caf_batch_quality.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, cu, vp, ci, ci, vp, vp, vp, vp, vp, vp, cu]
     lib.rmx_caf_batch_quality.restype = ci
+    lib.rmx_caf_batch_integrated.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, ci, cu, vp, ci, ci, vp, vp, vp, vp, vp, vp, cu]
+    lib.rmx_caf_batch_integrated.restype = ci
     lib.rmx_solve_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, ci, ci, vp, vp, vp, cu]
     lib.rmx_solve_batch.restype = ci
     lib.rmx_detect_batch.argtypes = [vp, vp, ci, ci, C.c_float, ci, C.c_double, C.c_float, ci, vp, vp, vp, vp, vp, vp, cu]
@@ -293,7 +295,7 @@ def doppler_estimate(doppler_cps, dop_idx, dop_frac) -> np.ndarray:
 
 
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_xcorr_batch_bands_quality", "rmx_xcorr_batch_bands_integrated", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_caf_batch_quality", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_xcorr_batch_bands_quality", "rmx_xcorr_batch_bands_integrated", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_caf_batch_quality", "rmx_caf_batch_integrated", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -574,12 +576,17 @@ class XcorrEngine:
         return pairs, pairs.ctypes.data_as(C.c_void_p), pairs.shape[0]
 
     def _caf(self, iq_p, W: int, pp, P: int, dc, bd, band_pw: bool, whiten: bool, lb, per_window: bool, dop_p, dop_frac_p,
-             lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0, quality_p=None):
+             lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0, quality_p=None, K: int = 1):
         """One Doppler search through the C entry its arguments name: rmx_caf_batch when nothing is requested,
-        rmx_caf_batch_quality for U > 0 or a quality pointer, else rmx_caf_batch_request.  dop_frac_p: a pointer, or None
-        (not computed)."""
+        rmx_caf_batch_integrated for K > 1 windows per group, rmx_caf_batch_quality for U > 0 or a quality pointer, else
+        rmx_caf_batch_request.  dop_frac_p: a pointer, or None (not computed)."""
         grid = (dc.ctypes.data_as(C.c_void_p), dc.shape[0])
-        if U or quality_p is not None:
+        if K > 1:
+            rc = self._lib.rmx_caf_batch_integrated(
+                self._ctx, iq_p, W, pp, P, *grid, K, None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
+                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
+                int(per_window), U, dop_p, dop_frac_p, lag_int_p, lag_frac_p, peak_p, quality_p, flags)
+        elif U or quality_p is not None:
             rc = self._lib.rmx_caf_batch_quality(
                 self._ctx, iq_p, W, pp, P, *grid, None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
                 RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
@@ -594,7 +601,7 @@ class XcorrEngine:
         self._check(rc)
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
-            whiten: bool = False, fine: bool = False, refine: int = 0, quality: bool = False):
+            whiten: bool = False, fine: bool = False, refine: int = 0, quality: bool = False, integrate=None):
         """Cross-ambiguity search (rmx_caf_batch, rmx_caf_batch_request, rmx_caf_batch_quality): host arrays in and out.
         doppler_cps: hypotheses in cycles/sample.  lag_bounds, band, whiten: as for correlate(), shared by all hypotheses
         of a (window, pair).
@@ -603,24 +610,29 @@ class XcorrEngine:
         indices (doppler_estimate turns it into cycles per sample); the other four are bit for bit those without it.
         refine: U in (0, 2, 4, 8, 16), the fine lag search of correlate(refine=U) on each slot's winning hypothesis; the
         winner and dop_frac do not move.  quality: True appends float32 [W][P][4] = (coherence, psr, rms_bw, n_eff) of the
-        winner's pair, indexed by RMX_Q_*, as the last element (psr_threshold and lag_sigma read it)."""
+        winner's pair, indexed by RMX_Q_*, as the last element (psr_threshold and lag_sigma read it).
+        integrate: K windows per group (rmx_caf_batch_integrated): every hypothesis' |r|^2 is summed over the K consecutive
+        windows of a group before ONE peak search; every output is then [W // K][P] (quality [W // K][P][4]), lag_bounds
+        [P][2] or [W // K][P][2] per group, the band stays per window.  None (or 1): the search per window."""
         iq, flags = self._check_iq(iq)
         W = iq.shape[0]
+        K = 1 if integrate is None else check_integrate(integrate, W)   # (the search without it pays for no check)
+        G = W // K
         U = check_refine(refine)
         pairs, pp, P = self._pairs_arg(pairs)
         dc = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
-        lb, per_window = check_lag_bounds(lag_bounds, W, P)
+        lb, per_window = check_lag_bounds(lag_bounds, G, P)
         bd, band_pw = check_band(band, W)
-        dop = np.zeros((W, P), np.int32)
-        dfrac = np.zeros((W, P), np.float32) if fine else None
-        lag_int = np.zeros((W, P), np.int32)
-        lag_frac = np.zeros((W, P), np.float32)
-        peak = np.zeros((W, P), np.float32)
-        qual = np.zeros((W, P, 4), np.float32) if quality else None
+        dop = np.zeros((G, P), np.int32)
+        dfrac = np.zeros((G, P), np.float32) if fine else None
+        lag_int = np.zeros((G, P), np.int32)
+        lag_frac = np.zeros((G, P), np.float32)
+        peak = np.zeros((G, P), np.float32)
+        qual = np.zeros((G, P, 4), np.float32) if quality else None
         if W and P:
             vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
             self._caf(vp(iq), W, pp, P, dc, bd, band_pw, bool(whiten), lb, per_window, vp(dop), vp(dfrac) if fine else None,
-                      vp(lag_int), vp(lag_frac), vp(peak), flags, U, vp(qual) if quality else None)
+                      vp(lag_int), vp(lag_frac), vp(peak), flags, U, vp(qual) if quality else None, K)
         out = (dop, dfrac, lag_int, lag_frac, peak) if fine else (dop, lag_int, lag_frac, peak)
         return out + (qual,) if quality else out
 
@@ -716,26 +728,29 @@ class XcorrEngine:
 
     def caf_device(self, iq_ptr: int, n_windows: int, doppler_cps, dop_ptr: int, lag_int_ptr: int,
                    lag_frac_ptr: int, peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
-                   band=None, whiten: bool = False, dop_frac_ptr: int = 0, refine: int = 0, quality_ptr: int = 0):
+                   band=None, whiten: bool = False, dop_frac_ptr: int = 0, refine: int = 0, quality_ptr: int = 0, integrate=None):
         """rmx_caf_batch / rmx_caf_batch_request / rmx_caf_batch_quality with device pointers in and out (the Doppler grid,
         the pair list, the bounds and the bands stay host arrays; the library keeps its own copies); asynchronous on the
         ctx stream.  dop_frac_ptr: 0, or a device buffer of [n_windows][P] float32 for the sub-grid Doppler estimate.
-        refine: as for caf(); quality_ptr: 0, or a device buffer of [n_windows][P][4] float32 for the quality figures."""
+        refine: as for caf(); quality_ptr: 0, or a device buffer of [n_windows][P][4] float32 for the quality figures.
+        integrate: as for caf() (rmx_caf_batch_integrated): every output buffer is then [n_windows // K][P] (quality
+        [n_windows // K][P][4]) and per-group lag_bounds are [n_windows // K][P][2]."""
         U = check_refine(refine) if refine else 0   # (the search without it pays for no check)
+        K = 1 if integrate is None else check_integrate(integrate, n_windows)
         pairs, pp, P = self._pairs_arg(pairs)
         dc = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
         flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
-        if lag_bounds is None and band is None and not whiten and not dop_frac_ptr and not U and not quality_ptr:   # the plain call, as ever
+        if lag_bounds is None and band is None and not whiten and not dop_frac_ptr and not U and not quality_ptr and K == 1:   # the plain call, as ever
             self._check(self._lib.rmx_caf_batch(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
                                                 dc.ctypes.data_as(C.c_void_p), dc.shape[0], C.c_void_p(dop_ptr),
                                                 C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr),
                                                 flags))
             return
-        lb, per_window = check_lag_bounds(lag_bounds, n_windows, P)
+        lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
         bd, band_pw = check_band(band, n_windows)
         self._caf(C.c_void_p(iq_ptr), n_windows, pp, P, dc, bd, band_pw, bool(whiten), lb, per_window, C.c_void_p(dop_ptr),
                   C.c_void_p(dop_frac_ptr) if dop_frac_ptr else None, C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
-                  C.c_void_p(peak_ptr), flags, U, C.c_void_p(quality_ptr) if quality_ptr else None)
+                  C.c_void_p(peak_ptr), flags, U, C.c_void_p(quality_ptr) if quality_ptr else None, K)
 
     def correlate_device(self, iq_ptr: int, n_windows: int, lag_int_ptr: int, lag_frac_ptr: int,
                          peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
