@@ -590,7 +590,7 @@ int rmx_caf_batch_quality(rmx_ctx* ctx, const void* iq, int n_windows, const int
  *   and top-two lag margin, both taken on the integrated vectors, exceed 1e-5.
  * Range: the sum of K windows' |r|^2 is K times as large as one window's: divide the |sample| bound of rmx_xcorr_batch by
  *   K^(1/4), as for rmx_xcorr_batch_integrated.
- * integrate == 1 IS rmx_caf_batch_quality with the same arguments (that entry forwards here): the same kernels, the same
+ * integrate == 1 IS rmx_caf_batch_quality with the same arguments (one checked request behind both): the same kernels, the same
  *   launches, bit-identical outputs.  With refine == 0 and quality == NULL nothing is launched behind the selection;
  *   lag_int, lag_frac and peak of a call with quality are bit-identical to the same call without it.  A call whose
  *   hypotheses are applied to buoy j's windows on the host (the same float32 phasors) and that goes through

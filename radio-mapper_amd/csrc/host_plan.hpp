@@ -161,11 +161,26 @@ inline bool is_default_list(int n_buoys, const int32_t* pairs, int n_pairs) {
     return true;
 }
 
+// every index of a caller's list names a buoy (pairs == nullptr: the default list, nothing to look at).  0, or -1 with *err.
+inline int check_pair_list(int n_buoys, const int32_t* pairs, int n_pairs, std::string* err) {
+    for (int q = 0; pairs && q < n_pairs; ++q) {
+        const int i = pairs[2 * q], j = pairs[2 * q + 1];
+        if (i < 0 || j < 0 || i >= n_buoys || j >= n_buoys) {
+            char b[200];
+            std::snprintf(b, sizeof b, "pair %d = (%d,%d) out of range for %d buoys", q, i, j, n_buoys);
+            *err = b;
+            return -1;
+        }
+    }
+    return 0;
+}
+
 // pairs == nullptr: the default list (n_pairs must then be P = B(B-1)/2).  0, or -1 with *err.
 inline int make_pair_plan(int n_buoys, const int32_t* pairs, int n_pairs, int pairs_per_block, PairPlan* out, std::string* err) {
     char b[200];
     const long all = (long)n_buoys * (n_buoys - 1) / 2;
     if (n_pairs < 0) { std::snprintf(b, sizeof b, "n_pairs %d < 0", n_pairs); *err = b; return -1; }
+    if (check_pair_list(n_buoys, pairs, n_pairs, err) != 0) return -1;
     std::vector<int32_t> pl;
     if (pairs) {
         pl.assign(pairs, pairs + 2 * (size_t)n_pairs);
@@ -174,14 +189,6 @@ inline int make_pair_plan(int n_buoys, const int32_t* pairs, int n_pairs, int pa
         pl.reserve(2 * (size_t)all);
         for (int i = 0; i < n_buoys; ++i)
             for (int j = i + 1; j < n_buoys; ++j) { pl.push_back(i); pl.push_back(j); }
-    }
-    for (int q = 0; q < n_pairs; ++q) {
-        const int i = pl[2 * q], j = pl[2 * q + 1];
-        if (i < 0 || j < 0 || i >= n_buoys || j >= n_buoys) {
-            std::snprintf(b, sizeof b, "pair %d = (%d,%d) out of range for %d buoys", q, i, j, n_buoys);
-            *err = b;
-            return -1;
-        }
     }
     out->items.resize(n_pairs);
     for (int q = 0; q < n_pairs; ++q) out->items[q] = PairItem{pl[2 * q], pl[2 * q + 1], q, 1};
@@ -508,6 +515,15 @@ inline bool route_rows_fused(const RouteCaps& k, bool weighted, int wc) {
     return fused_blocks >= 2L * k.n_cus || k.g_fused_always;
 }
 
+// An integrated call's chunk (plan_route and plan_caf): `chunk` windows rounded down to whole groups -- never a silent
+// split of a group --, refused when that leaves none, or when the four-step column kernel would sum more per thread than it holds
+inline RouteRefusal integ_chunk(const RouteCaps& k, int chunk, int integ, bool four_step, int* whole_groups) {
+    *whole_groups = chunk / integ * integ;
+    if (*whole_groups == 0) return kRefuseIntegChunk;
+    if (integ > 1 && four_step && k.col_tile > (long)k.integ_max_per_thread * k.cols_threads) return kRefuseIntegTile;
+    return kRouteOk;
+}
+
 inline RoutePlan plan_route4096(const RouteCaps& k, const RouteCall& a) {
     RoutePlan p;
     const int all_pairs = k.n_buoys * (k.n_buoys - 1) / 2, W = a.n_windows;
@@ -553,8 +569,7 @@ inline RoutePlan plan_route4096(const RouteCaps& k, const RouteCall& a) {
     // fused path: the host copy is cut into sub-chunks issued on a second stream, each followed by its kernel launch, so
     // that copy k+1 travels while kernel k runs; otherwise one copy up front
     p.pipelined = !a.in_dev && fused_now && W > kHostSubChunk;
-    p.chunk = k.chunk_windows / a.integ * a.integ;   // (integrated call: a chunk holds whole groups -- never a silent split of a group)
-    if (p.chunk == 0) p.refused = kRefuseIntegChunk;
+    p.refused = integ_chunk(k, k.chunk_windows, a.integ, false, &p.chunk);
     return p;
 }
 
@@ -612,18 +627,55 @@ inline RoutePlan plan_route(const RouteCaps& k, const RouteCall& a) {
     }
     if (!a.weighted && k.wfused && !a.bounded) { p.route = kRouteWinFused; return p; }
     p.route = (1L << k.logL) <= k.small_maxl ? kRouteSmallL : kRouteFourStep;
-    p.chunk = k.g_chunk / a.integ * a.integ;
     // banded call: the chunk whose virtual windows the per-slot buffers hold (plan_bands: the sizes); banded AND integrated:
     // that chunk first, then rounded down to whole groups -- both caps hold, and no group is ever split
+    const bool four_step = p.route == kRouteFourStep;
+    int chunk = k.g_chunk;
     if (a.n_bands > 1) {
-        const bool four_step = p.route == kRouteFourStep;
-        const int bc = (int)plan_bands(k.g_chunk, W, a.n_bands, k.n_buoys, a.n_pairs, 1L << k.logL, four_step, 0, 0, 0).chunk;
-        p.chunk = bc / a.integ * a.integ;
-        if (a.integ > 1 && k.g_chunk >= a.integ) p.bands_chunk = bc;
-    }   // (integrated call: a chunk holds whole groups -- never a silent split of a group)
-    if (p.chunk == 0) p.refused = kRefuseIntegChunk;
-    else if (a.integ > 1 && p.route == kRouteFourStep && k.col_tile > (long)k.integ_max_per_thread * k.cols_threads)
-        p.refused = kRefuseIntegTile;
+        chunk = (int)plan_bands(k.g_chunk, W, a.n_bands, k.n_buoys, a.n_pairs, 1L << k.logL, four_step, 0, 0, 0).chunk;
+        if (a.integ > 1 && k.g_chunk >= a.integ) p.bands_chunk = chunk;
+    }
+    p.refused = integ_chunk(k, chunk, a.integ, four_step, &p.chunk);
+    return p;
+}
+
+// ---- the shape of one Doppler search ----------------------------------------------------------------------------------
+// plan_caf is the ONE place where it is decided; caf_request in rmx_hip.hip executes the plan.
+constexpr size_t kSpecBytes4096 = 64 * 1024;   // one stored N = 4096 spectrum: 8192 bins of 8 bytes
+struct CafCall {
+    int n_windows = 0, n_pairs = 0, n_dopplers = 1;
+    int integ = 1;            // K windows per group
+    bool fine = false;        // dop_frac is asked for
+    bool refined = false, qualified = false;
+    bool out_dev = false;     // RMX_OUT_DEVICE
+};
+struct CafPlan {
+    bool one_launch = false;       // N = 4096: every hypothesis in ONE forward and ONE pair launch (virtual window = hypothesis x window)
+    int ppb = 7;                   // pairs per workgroup of the N = 4096 pair kernels (unused elsewhere)
+    int chunk = 0;                 // windows per chunk of the per-hypothesis sweep, a multiple of integ
+    RouteRefusal refused = kRouteOk;
+    size_t out_elems = 0;          // elements of each output: one slot per (group, pair)
+    size_t hyp_elems = 0;          // elements of each per-hypothesis result array: [d][group][pair] in one launch, else one hypothesis'
+    bool need_nb = false;          // caf_nb: k_caf_select_fd's three neighbour rows, and dop_frac of a host-pointer call behind them
+    bool stage_dfrac = false;      // dop_frac is written to the ctx's block (the fourth row of caf_nb) and copied to the caller
+    bool second_sweep = false;     // the hypotheses of each chunk once more, each followed by k_quality / k_refine on the slots it won
+};
+inline CafPlan plan_caf(const RouteCaps& k, const CafCall& a) {
+    CafPlan p;
+    const long W = a.n_windows, D = a.n_dopplers;
+    // 21 hypotheses on one frequency group: 431 -> ~60 us against three launches per hypothesis.  One chunk, at most 1 GiB
+    // of de-rotated spectra, and virtual windows that the pair kernels' grids hold
+    p.one_launch = !k.generic && D > 1 && W <= k.chunk_windows && (size_t)D * W * k.n_buoys * kSpecBytes4096 <= ((size_t)1 << 30) &&
+                   D * W < (1L << 20);
+    p.ppb = k.ppb_user ? k.ppb_user : 7;
+    if (!k.generic && !k.ppb_user)   // (N = 4096: blocks sized to this batch's work items)
+        (void)split_cost4096(k.n_cus, k.n_buoys, a.n_pairs, (p.one_launch ? W * D : W) / a.integ, 0, &p.ppb);
+    p.refused = integ_chunk(k, k.generic ? k.g_chunk : k.chunk_windows, a.integ, k.generic && (1L << k.logL) > k.small_maxl, &p.chunk);
+    p.out_elems = (size_t)(W / a.integ) * a.n_pairs;
+    p.hyp_elems = p.one_launch ? p.out_elems * (size_t)D : p.out_elems;
+    p.need_nb = a.fine && (!p.one_launch || !a.out_dev);
+    p.stage_dfrac = a.fine && !a.out_dev;
+    p.second_sweep = (a.refined || a.qualified) && !p.one_launch;
     return p;
 }
 

@@ -39,6 +39,11 @@ struct RequestArgs {
     int32_t* lag_int = nullptr;
     float *lag_frac = nullptr, *peak = nullptr, *quality = nullptr;
     unsigned flags = 0;             // RMX_IN_DEVICE, RMX_OUT_DEVICE, RMX_IN_U8: which pointers the kernels themselves touch
+    // the Doppler search (check_caf_request): the grid, and its two outputs in front of the three above
+    const double* doppler_cps = nullptr;
+    int n_dopplers = 0;
+    int32_t* dop_idx = nullptr;
+    float* dop_frac = nullptr;      // or NULL: not computed
 };
 
 // The checked request in host form.  The plain call allocates nothing: bins and own_bounds stay empty.
@@ -206,6 +211,30 @@ inline int check_groups(int integrate, int n_windows, std::string* err) {
     return RMX_OK;
 }
 
+// What check_request and check_caf_request share behind their bounds: refine with its value; quality over one of the n
+// other outputs of `slots` elements each (k_quality reads them while it writes quality); the full interval per pair, one
+// row for every group, which an integrated call without bounds carries (the integrating kernels always take bounds).
+inline int check_refine(int refine, std::string* err) {
+    if (refine != 0 && refine != 2 && refine != 4 && refine != 8 && refine != 16)
+        return refuse(err, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", refine);
+    return RMX_OK;
+}
+inline int check_quality_overlap(const float* quality, size_t slots, const OutArray* outs, int n, std::string* err) {
+    char needs[96];
+    std::snprintf(needs, sizeof needs, "the %zu x 4 floats of quality need a buffer of their own", slots);
+    return check_overlap("quality", quality, 4 * slots * sizeof(float), outs, n, slots * sizeof(float), needs, err);
+}
+inline void full_bounds(int n_samples, Request* r) {
+    r->own_bounds.resize(2 * (size_t)r->n_pairs);
+    for (int q = 0; q < r->n_pairs; ++q) {
+        r->own_bounds[2 * q] = -(n_samples - 1);
+        r->own_bounds[2 * q + 1] = n_samples - 1;
+    }
+    r->bounds = r->own_bounds.data();
+    r->bound_rows = r->n_pairs;
+    r->bounded = true;
+}
+
 // Every check of the nine rmx_xcorr_batch* entries, in the order include/rmx.h promises, so an input with several bad
 // arguments is refused for the same one whichever entry it came through: the grouped entries' (integrate, the group
 // count), a NULL buffer, a device pointer aligned to less than its element, n_bands, the weighted entry's, the batch
@@ -249,30 +278,17 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
         rc = check_bounds(a, K, r, err);
         if (rc != RMX_OK) return rc;
     }
-    if (a.refine != 0 && a.refine != 2 && a.refine != 4 && a.refine != 8 && a.refine != 16)
-        return refuse(err, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", a.refine);
-    // k_quality reads peak while it writes quality
+    rc = check_refine(a.refine, err);
+    if (rc != RMX_OK) return rc;
     if (a.quality) {
-        const size_t slots = (size_t)(a.n_windows / K) * r->n_bands * r->n_pairs;
         const OutArray outs[3] = {{"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}};
-        char needs[96];
-        std::snprintf(needs, sizeof needs, "the %zu x 4 floats of quality need a buffer of their own", slots);
-        rc = check_overlap("quality", a.quality, 4 * slots * sizeof(float), outs, 3, slots * sizeof(float), needs, err);
+        rc = check_quality_overlap(a.quality, (size_t)(a.n_windows / K) * r->n_bands * r->n_pairs, outs, 3, err);
         if (rc != RMX_OK) return rc;
     }
     r->integ = K;
     r->refine = a.refine;
     const size_t row = 2 * (size_t)r->n_pairs;
-    if (K > 1 && !a.lag_bounds) {   // the integrating kernels always carry bounds: the full interval per pair
-        r->own_bounds.resize(row);
-        for (int q = 0; q < r->n_pairs; ++q) {
-            r->own_bounds[2 * q] = -(a.n_samples - 1);
-            r->own_bounds[2 * q + 1] = a.n_samples - 1;
-        }
-        r->bounds = r->own_bounds.data();
-        r->bound_rows = r->n_pairs;
-        r->bounded = true;
-    }
+    if (K > 1 && !a.lag_bounds) full_bounds(a.n_samples, r);
     // the bounds are per (window, pair) -- per (group, pair) of an integrated call -- and shared by the bands: per-window
     // bounds go to the device once per VIRTUAL window (window-major; per row group * n_bands + band, group-major), so the
     // bounded kernels index them with the virtual window (the row) as they index their outputs.  (The full intervals made
@@ -288,16 +304,17 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
     return RMX_OK;
 }
 
-// The tail of rmx_caf_batch_request, behind its own head (NULL buffer, n_dopplers, the batch shape, the pair list):
-// `a` with n_pairs resolved; the weighted entry's checks, the bounded entry's, then dop_frac over another output, and what
-// rmx_caf_batch_quality adds behind them (a.refine, a.quality, a.flags).  rmx_caf_batch_integrated (a.grouped, with
-// a.integrate = K checked by check_groups): the bands stay per window, the bounds are per GROUP and every output extent
-// is G * n_pairs slots, G = n_windows / K; K > 1 without bounds carries the full interval per pair, as check_request's.
+// The tail of a Doppler call's check, behind its head (below): `a` with n_pairs resolved; the weighted entry's checks, the
+// bounded entry's, dop_frac over another output, refine, quality over one of the five other outputs (k_quality reads
+// peak and dop_idx while it writes quality), a device quality aligned to less than its element.  The bands stay per
+// window, the bounds are per GROUP and every output extent is G * n_pairs slots, G = n_windows / K; K > 1 without bounds
+// carries the full interval per pair, as check_request's.
 inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const float* dop_frac, Request* r, std::string* err) {
     *r = Request{};
     r->n_pairs = a.n_pairs;
     const int K = a.grouped ? a.integrate : 1;
     const size_t slots = (size_t)(a.n_windows / K) * a.n_pairs;
+    const OutArray outs[5] = {{"dop_idx", dop_idx}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}, {"dop_frac", dop_frac}};
     int rc;
     if (a.band_cps || a.weighting != RMX_WEIGHT_NONE) {
         rc = check_bands(a, r, err);
@@ -308,21 +325,15 @@ inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const
         if (rc != RMX_OK) return rc;
     }
     if (dop_frac) {
-        const OutArray outs[4] = {{"dop_idx", dop_idx}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}};
         char needs[96];
         std::snprintf(needs, sizeof needs, "its %zu floats need a buffer of their own", slots);
         rc = check_overlap("dop_frac", dop_frac, slots * sizeof(float), outs, 4, slots * sizeof(float), needs, err);
         if (rc != RMX_OK) return rc;
     }
-    // rmx_caf_batch_quality: refine, then quality over one of the five other outputs (k_quality reads peak and dop_idx
-    // while it writes quality), then a device quality aligned to less than its element
-    if (a.refine != 0 && a.refine != 2 && a.refine != 4 && a.refine != 8 && a.refine != 16)
-        return refuse(err, "refine = %d: the fine grid is 1 / U samples with U one of 0 (none), 2, 4, 8, 16", a.refine);
+    rc = check_refine(a.refine, err);
+    if (rc != RMX_OK) return rc;
     if (a.quality) {
-        OutArray outs[5] = {{"dop_idx", dop_idx}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}, {"dop_frac", dop_frac}};
-        char needs[96];
-        std::snprintf(needs, sizeof needs, "the %zu x 4 floats of quality need a buffer of their own", slots);
-        rc = check_overlap("quality", a.quality, 4 * slots * sizeof(float), outs, dop_frac ? 5 : 4, slots * sizeof(float), needs, err);
+        rc = check_quality_overlap(a.quality, slots, outs, dop_frac ? 5 : 4, err);
         if (rc != RMX_OK) return rc;
         const OutArray q[1] = {{"quality", a.quality}};
         rc = check_alignment(a.flags & RMX_OUT_DEVICE, nullptr, q, 1, err);
@@ -330,17 +341,36 @@ inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const
     }
     r->integ = K;
     r->refine = a.refine;
-    if (K > 1 && !a.lag_bounds) {   // the integrating kernels always carry bounds: the full interval per pair, one row for all
-        r->own_bounds.resize(2 * (size_t)r->n_pairs);
-        for (int q = 0; q < r->n_pairs; ++q) {
-            r->own_bounds[2 * q] = -(a.n_samples - 1);
-            r->own_bounds[2 * q + 1] = a.n_samples - 1;
-        }
-        r->bounds = r->own_bounds.data();
-        r->bound_rows = r->n_pairs;
-        r->bounded = true;
-    }
+    if (K > 1 && !a.lag_bounds) full_bounds(a.n_samples, r);
     return RMX_OK;
+}
+
+// Every check of the four rmx_caf_batch* entries, in the order include/rmx.h promises, as check_request is every check of
+// a correlation call.  The head: a NULL buffer, a device pointer aligned to less than its element (the five arrays),
+// n_dopplers, the group count (a.grouped with a.integrate != 1 only: one window per group takes an empty batch), the
+// batch shape, the empty batch, the pair list; then the tail above on the resolved pair count.  RMX_OK with *r filled
+// (r->empty: nothing to do), or RMX_E_INVAL with *err.
+inline int check_caf_request(const RequestArgs& a, Request* r, std::string* err) {
+    *r = Request{};
+    if (!a.iq || !a.dop_idx || !a.lag_int || !a.lag_frac || !a.peak || !a.doppler_cps) return refuse(err, "NULL buffer");
+    const OutArray outs[5] = {{"dop_idx", a.dop_idx}, {"dop_frac", a.dop_frac}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}};
+    int rc = check_alignment(a.flags, a.iq, outs, 5, err);
+    if (rc != RMX_OK) return rc;
+    if (a.n_dopplers < 1 || a.n_dopplers > 4096) return refuse(err, "n_dopplers %d not in 1..4096", a.n_dopplers);
+    if (a.grouped && a.integrate != 1) {
+        rc = check_groups(a.integrate, a.n_windows, err);
+        if (rc != RMX_OK) return rc;
+    }
+    RequestArgs resolved = a;
+    rc = check_batch(a.n_buoys, a.max_windows, a.n_windows, a.pairs, &resolved.n_pairs, err);
+    if (rc != RMX_OK) return rc;
+    if (a.n_windows == 0 || resolved.n_pairs == 0) {
+        r->n_pairs = resolved.n_pairs;
+        r->empty = true;
+        return RMX_OK;
+    }
+    if (check_pair_list(a.n_buoys, a.pairs, resolved.n_pairs, err) != 0) return RMX_E_INVAL;
+    return check_caf_request(resolved, a.dop_idx, a.dop_frac, r, err);
 }
 
 }  // namespace host

@@ -1167,12 +1167,12 @@ static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_
 }
 
 // a refusal of the planner as the caller reads it
-static int route_refusal(rmx_ctx* c, const host::RoutePlan& plan, const host::RouteCaps& k, int integ, int n_bands) {
-    if (plan.refused == host::kRouteOk) return RMX_OK;
-    if (plan.refused == host::kRefuseIntegChunk && plan.bands_chunk > 0)
+static int route_refusal(rmx_ctx* c, host::RouteRefusal refused, int bands_chunk, const host::RouteCaps& k, int integ, int n_bands) {
+    if (refused == host::kRouteOk) return RMX_OK;
+    if (refused == host::kRefuseIntegChunk && bands_chunk > 0)
         return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the chunk of %d windows that n_bands = %d bands shrank this "
-                    "ctx's chunk of %d windows to: a group is never split", integ, plan.bands_chunk, n_bands, k.g_chunk);
-    if (plan.refused == host::kRefuseIntegChunk)
+                    "ctx's chunk of %d windows to: a group is never split", integ, bands_chunk, n_bands, k.g_chunk);
+    if (refused == host::kRefuseIntegChunk)
         return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the largest chunk this ctx can hold, %d windows",
                     integ, k.generic ? k.g_chunk : k.chunk_windows);
     return fail(c, RMX_E_UNSUPPORTED, "integrated call: a column tile of %ld elements on %d threads is more than %d per thread",
@@ -1195,7 +1195,7 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps
     // the whole-window kernels and k16 keep no per-window state in HBM
     const bool per_transform = plan.route == kRouteSmallL || plan.route == kRouteFourStep;
     int rc = ensure(per_transform, per_transform);
-    if (rc == RMX_OK) rc = route_refusal(c, plan, caps, call.integ, rq.n_bands);
+    if (rc == RMX_OK) rc = route_refusal(c, plan.refused, plan.bands_chunk, caps, call.integ, rq.n_bands);
     if (rc != RMX_OK) return rc;
     if (per_transform) return run_chunks(c, call, caps, d_iq, 0, rq.n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
     if (plan.route == kRouteK16) return k16_batch(c, call, d_iq, rq.n_windows, plan.chunk, n_pairs, d_lag, d_frac, d_peak, u8);
@@ -1442,8 +1442,20 @@ int rmx_set_option(rmx_ctx* c, const char* key, long value) {
 }
 
 // spectrum scratch of at least `windows` window slots (B * 64 KiB each)
+static_assert(host::kSpecBytes4096 == 8 * kThreads * sizeof(float4), "host::plan_caf counts a stored N = 4096 spectrum as 64 KiB");
 static int ensure_spec(rmx_ctx* c, long windows) {
     RMX_MEM(c->d_spec.reserve((size_t)windows * c->n_buoys * (8 * kThreads)));
+    return RMX_OK;
+}
+
+// The call's windows on the device: a device pointer as it is; host windows in the ctx's d_in, with (copy_now) one copy
+// up front on the ctx stream
+static int host_input(rmx_ctx* c, const void* iq, size_t bytes, bool in_dev, bool copy_now, const void** d_iq) {
+    *d_iq = iq;
+    if (in_dev) return RMX_OK;
+    RMX_MEM(c->d_in.reserve(bytes));
+    if (copy_now) RMX_HIP(c, hipMemcpyAsync(c->d_in, iq, bytes, hipMemcpyHostToDevice, c->stream));
+    *d_iq = c->d_in;
     return RMX_OK;
 }
 
@@ -1557,27 +1569,23 @@ static int xcorr_dispatch(rmx_ctx* c, const XcorrCall& req, const void* iq, int 
     const host::RoutePlan plan = host::plan_route(caps, rq);
     if (!c->generic) c->pairs_per_block = plan.ppb;
     int rc = build_plan(c, pairs, n_pairs);
-    if (rc == RMX_OK && !c->generic) rc = route_refusal(c, plan, caps, call.integ, rq.n_bands);
+    if (rc == RMX_OK && !c->generic) rc = route_refusal(c, plan.refused, plan.bands_chunk, caps, call.integ, rq.n_bands);
     if (rc != RMX_OK) return rc;
 
     const size_t samp_bytes = u8 ? 2 : 8;
     const size_t in_bytes = (size_t)n_windows * c->n_buoys * c->n_samples * samp_bytes;
-    const void* d_iq = iq;
-    if (!in_dev) {
-        RMX_MEM(c->d_in.reserve(in_bytes));
-        // k_win: the copy is cut into sub-chunks issued on a second stream, each followed by its
-        // kernel launch, so that copy k+1 travels while kernel k runs (below); otherwise one copy up front
-        if (plan.pipelined) {
-            if (!c->copy_stream) RMX_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-            for (hipEvent_t& e : c->copy_ev)
-                if (!e) RMX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            // earlier work of this ctx may still read the staging buffer
-            RMX_HIP(c, hipEventRecord(c->copy_ev[3], c->stream));
-            RMX_HIP(c, hipStreamWaitEvent(c->copy_stream, c->copy_ev[3], 0));
-        } else {
-            RMX_HIP(c, hipMemcpyAsync(c->d_in, iq, in_bytes, hipMemcpyHostToDevice, c->stream));
-        }
-        d_iq = c->d_in;
+    // k_win: the copy is cut into sub-chunks issued on a second stream, each followed by its
+    // kernel launch, so that copy k+1 travels while kernel k runs (below); otherwise one copy up front
+    const void* d_iq = nullptr;
+    rc = host_input(c, iq, in_bytes, in_dev, !plan.pipelined, &d_iq);
+    if (rc != RMX_OK) return rc;
+    if (!in_dev && plan.pipelined) {
+        if (!c->copy_stream) RMX_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+        for (hipEvent_t& e : c->copy_ev)
+            if (!e) RMX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        // earlier work of this ctx may still read the staging buffer
+        RMX_HIP(c, hipEventRecord(c->copy_ev[3], c->stream));
+        RMX_HIP(c, hipStreamWaitEvent(c->copy_stream, c->copy_ev[3], 0));
     }
     int* d_lag = lag_int;
     float *d_frac = lag_frac, *d_peak = peak;
@@ -1843,25 +1851,199 @@ int rmx_xcorr_batch_bands_integrated(rmx_ctx* c, const void* iq, int n_windows, 
     return xcorr_request(c, a, flags);
 }
 
-// The Doppler search is rmx_caf_batch_request with nothing requested: the same kernels, the same launches
+// ---- the Doppler search (host_plan.hpp: plan_caf decides its shape; this executes it) -----------------------------------------
+// One search on its way to the device.  `call` describes the search's own forward and pair kernels and is never refined
+// or qualified: they are those of rmx_caf_batch_request whatever else is asked.  `tail` is what follows the selection:
+// call + refine + quality, the quality pointer the ctx's block for a host-pointer call.  The five outputs as the kernels
+// write them: the caller's device arrays, or the ctx's blocks.
+struct CafRun {
+    XcorrCall call, tail;
+    const void* d_iq = nullptr;
+    int n_windows = 0, n_pairs = 0, n_dopplers = 0;
+    bool u8 = false;
+    int *dop = nullptr, *lag = nullptr;
+    float *frac = nullptr, *peak = nullptr, *dfrac = nullptr;   // (dfrac: NULL unless dop_frac is asked for)
+};
+
+// phasor table [D][N] under the grid: exp(-2 pi i nu n) in double, rounded once to float
+static int caf_phasors(rmx_ctx* c, const double* doppler_cps, int n_dopplers) {
+    const int N = c->n_samples;
+    std::vector<double> grid(doppler_cps, doppler_cps + n_dopplers);
+    if (c->caf_rot.holds(grid)) return RMX_OK;
+    std::vector<float2> rot((size_t)n_dopplers * N);
+    for (int d = 0; d < n_dopplers; ++d)
+        for (int n = 0; n < N; ++n) {
+            const double a = -6.283185307179586476925286766559 * grid[d] * (double)n;
+            rot[(size_t)d * N + n] = make_float2((float)std::cos(a), (float)std::sin(a));
+        }
+    RMX_MEM(c->caf_rot.refill(grid, rot));
+    return RMX_OK;
+}
+
+// The buffers the plan sizes -- the per-hypothesis results, the outputs of a host-pointer call, k_caf_select_fd's
+// neighbour rows with the staged dop_frac behind them, the staged quality -- and where `r` writes its outputs
+static int caf_buffers(rmx_ctx* c, const host::RequestArgs& a, const host::CafPlan& plan, bool out_dev, CafRun* r) {
+    RMX_MEM(c->caf_lag.reserve(plan.hyp_elems));
+    RMX_MEM(c->caf_frac.reserve(plan.hyp_elems));
+    RMX_MEM(c->caf_peak.reserve(plan.hyp_elems));
+    r->dop = a.dop_idx; r->lag = a.lag_int; r->frac = a.lag_frac; r->peak = a.peak; r->dfrac = a.dop_frac;
+    if (!out_dev) {
+        const int rc = ensure_out(c, plan.out_elems);
+        if (rc != RMX_OK) return rc;
+        const OutBlock o = out_block(c);
+        r->dop = o.dop; r->lag = o.lag; r->frac = o.frac; r->peak = o.peak;
+    }
+    if (plan.need_nb) RMX_MEM(c->caf_nb.reserve(4 * plan.out_elems));
+    if (plan.stage_dfrac) r->dfrac = c->caf_nb + 3 * plan.out_elems;
+    if (a.quality && !out_dev) {
+        RMX_MEM(c->d_quality.reserve(4 * plan.out_elems));
+        r->tail.quality = c->d_quality;
+    }
+    return RMX_OK;
+}
+
+// N = 4096, one chunk: all hypotheses in ONE forward launch and ONE pair launch (virtual window = hypothesis x window)
+// instead of three launches per hypothesis, ONE selection over the resident per-hypothesis results, and the tail once
+static int caf_one_launch(rmx_ctx* c, const CafRun& r, const host::CafPlan& plan) {
+    const int W = r.n_windows, D = r.n_dopplers;
+    const SpecView sv = spec_view(c);
+    int rc = fwd4096(c, r.call, r.d_iq, 0, W, r.u8, nullptr);
+    if (rc == RMX_OK) rc = fwd4096(c, r.call, r.d_iq, 0, W, r.u8, c->caf_rot, D);
+    if (rc == RMX_OK) rc = pairs4096(c, r.call, 0, W, r.n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, out_scale4096(), true, D);
+    const dim3 sgrid((unsigned)((plan.out_elems + 255) / 256));
+    if (rc == RMX_OK && !r.dfrac)
+        rc = launch(c, kTkCafSelect, k_caf_select_all, sgrid, dim3(256), 0, D, (long)plan.out_elems, c->caf_lag, c->caf_frac, c->caf_peak,
+                    r.dop, r.lag, r.frac, r.peak);
+    if (rc == RMX_OK && r.dfrac)
+        rc = launch(c, kTkCafSelect, k_caf_select_all_fd, sgrid, dim3(256), 0, D, (long)plan.out_elems, c->caf_lag, c->caf_frac, c->caf_peak,
+                    r.dop, r.lag, r.frac, r.peak, r.dfrac);
+    // every de-rotated set is resident: slot (w, q) reads operand j at virtual window dop_idx * W + w (a group's slot
+    // (g, q): at dop_idx * W + g K + kw, its K windows in order)
+    const CafWinner cw{r.dop, reinterpret_cast<const float2*>(c->d_spec_r.get()), (long)W * c->n_buoys, -1};
+    if (rc == RMX_OK && r.tail.qualified()) rc = quality_chunk(c, r.tail, sv, 0, W, r.n_pairs, r.peak, &cw);
+    if (rc == RMX_OK && r.tail.refined()) rc = refine_chunk(c, r.tail, sv, 0, W, r.n_pairs, r.lag, r.frac, r.peak, &cw);
+    return rc;
+}
+
+// Per chunk of windows: the un-rotated spectra once, then per hypothesis the de-rotated spectra (the rotation is applied
+// as the window is loaded), the pair kernels with X_i un-rotated and X_j de-rotated, and the running d-major first
+// maximum.  No augmented copy of the windows, no second engine.
+static int caf_sweep(rmx_ctx* c, const CafRun& r, const host::CafPlan& plan) {
+    const int K = r.call.integ, N = c->n_samples, D = r.n_dopplers;
+    const SpecView sv = spec_view(c);
+    int rc = RMX_OK;
+    for (int w0 = 0; w0 < r.n_windows && rc == RMX_OK; w0 += plan.chunk) {
+        const int wc = r.n_windows - w0 < plan.chunk ? r.n_windows - w0 : plan.chunk;
+        rc = sv.forward(c, r.call, r.d_iq, w0, wc, r.u8, nullptr, false);
+        for (int d = 0; d < D && rc == RMX_OK; ++d) {
+            rc = sv.forward(c, r.call, r.d_iq, w0, wc, r.u8, c->caf_rot + (size_t)d * N, false);
+            if (rc != RMX_OK) break;
+            rc = sv.pairs(c, r.call, w0, wc, r.n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true, false);
+            if (rc != RMX_OK) break;
+            const long first = (long)(w0 / K) * r.n_pairs, cnt = (long)(wc / K) * r.n_pairs;   // the chunk's output rows
+            const dim3 sgrid((unsigned)((cnt + 255) / 256));
+            if (r.dfrac)
+                rc = launch(c, kTkCafSelect, k_caf_select_fd, sgrid, dim3(256), 0, d, D, first, cnt, (long)plan.out_elems, c->caf_lag,
+                            c->caf_frac, c->caf_peak, r.dop, r.lag, r.frac, r.peak, c->caf_nb, r.dfrac);
+            else
+                rc = launch(c, kTkCafSelect, k_caf_select, sgrid, dim3(256), 0, d, first, cnt, c->caf_lag, c->caf_frac, c->caf_peak, r.dop,
+                            r.lag, r.frac, r.peak);
+        }
+        // The chunk's winners are known now and only the last hypothesis' de-rotated set is left: the hypotheses once
+        // more, each followed by k_quality and k_refine on the slots it won (k_quality in front: k_refine overwrites peak)
+        for (int d = 0; plan.second_sweep && d < D && rc == RMX_OK; ++d) {
+            rc = sv.forward(c, r.call, r.d_iq, w0, wc, r.u8, c->caf_rot + (size_t)d * N, false);
+            const CafWinner cw{r.dop, c->generic ? c->g_spec_r.get() : reinterpret_cast<const float2*>(c->d_spec_r.get()), 0L, d};
+            if (rc == RMX_OK && r.tail.qualified()) rc = quality_chunk(c, r.tail, sv, w0, wc, r.n_pairs, r.peak, &cw);
+            if (rc == RMX_OK && r.tail.refined()) rc = refine_chunk(c, r.tail, sv, w0, wc, r.n_pairs, r.lag, r.frac, r.peak, &cw);
+        }
+    }
+    return rc;
+}
+
+// What all four Doppler entries do, and none of them through another: hand their arguments to host::check_caf_request --
+// every refusal, in one order whichever entry the call came through --, describe the search in an XcorrCall (the staged
+// bands and lag intervals), let host::plan_caf decide its shape and run that.  The plain search is one window per group,
+// no band, no weighting, no bounds, dop_frac == NULL, nothing refined or qualified.
+static int caf_request(rmx_ctx* c, host::RequestArgs a, unsigned flags) {
+    if (!c) return RMX_E_INVAL;
+    a.n_buoys = c->n_buoys;
+    a.n_samples = c->n_samples;
+    a.max_windows = c->max_windows;
+    a.flags = flags;
+    a.grouped = true;
+    host::Request rq;
+    std::string why;
+    int rc = host::check_caf_request(a, &rq, &why);
+    if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
+    if (rq.empty) return RMX_OK;
+    RMX_HIP(c, hipSetDevice(c->device));
+    const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE;
+    CafRun r;
+    r.n_windows = a.n_windows;  r.n_pairs = rq.n_pairs;  r.n_dopplers = a.n_dopplers;  r.u8 = flags & RMX_IN_U8;
+    r.call.integ = rq.integ;
+    rc = describe_call(c, rq, &r.call);
+    if (rc != RMX_OK) return rc;
+    r.tail = r.call;
+    r.tail.refine = rq.refine;
+    r.tail.quality = a.quality;
+    const host::CafCall cq{a.n_windows, rq.n_pairs, a.n_dopplers, rq.integ, a.dop_frac != nullptr, r.tail.refined(), r.tail.qualified(), out_dev};
+    host::RouteCaps caps = route_caps(c);
+    host::CafPlan plan = host::plan_caf(caps, cq);
+    if (!c->generic) c->pairs_per_block = plan.ppb;   // (N = 4096: blocks sized to this batch, not to the previous call's)
+    rc = build_plan(c, a.pairs, rq.n_pairs);
+    if (rc == RMX_OK) rc = route_refusal(c, plan.refused, 0, caps, rq.integ, 1);
+    if (rc == RMX_OK) rc = host_input(c, a.iq, (size_t)a.n_windows * c->n_buoys * c->n_samples * (r.u8 ? 2 : 8), in_dev, true, &r.d_iq);
+    if (rc == RMX_OK) rc = caf_phasors(c, a.doppler_cps, a.n_dopplers);
+    if (rc == RMX_OK) rc = caf_buffers(c, a, plan, out_dev, &r);
+    if (rc != RMX_OK) return rc;
+    tm_reset(c);
+    if (c->generic) {   // a failed allocation halves g_chunk, and the plan follows: whole groups per chunk, or the refusal
+        rc = rmx::generic_ensure(c, rq.n_pairs);
+        if (rc == RMX_OK && c->g_chunk != caps.g_chunk) {
+            caps.g_chunk = c->g_chunk;
+            plan = host::plan_caf(caps, cq);
+            rc = route_refusal(c, plan.refused, 0, caps, rq.integ, 1);
+        }
+    } else {
+        rc = ensure_spec(c, a.n_windows < c->chunk_windows ? a.n_windows : c->chunk_windows);
+    }
+    if (rc == RMX_OK) rc = plan.one_launch ? caf_one_launch(c, r, plan) : caf_sweep(c, r, plan);
+    if (rc != RMX_OK || out_dev) return rc;
+    // host-pointer results: dop_frac and quality are queued in front of fetch_out, which waits for the stream
+    if (a.dop_frac) RMX_HIP(c, hipMemcpyAsync(a.dop_frac, r.dfrac, plan.out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (a.quality) RMX_HIP(c, hipMemcpyAsync(a.quality, r.tail.quality, 4 * plan.out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return fetch_out(c, plan.out_elems, a.lag_int, a.lag_frac, a.peak, a.dop_idx);
+}
+
+// the arguments every Doppler entry takes: batch_args, the grid and the search's own two outputs
+static host::RequestArgs caf_args(const void* iq, int n_windows, const int32_t* pairs, int n_pairs, const double* doppler_cps, int n_dopplers,
+                                  int32_t* dop_idx, float* dop_frac, int32_t* lag_int, float* lag_frac, float* peak) {
+    host::RequestArgs a = batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak);
+    a.doppler_cps = doppler_cps;
+    a.n_dopplers = n_dopplers;
+    a.dop_idx = dop_idx;
+    a.dop_frac = dop_frac;
+    return a;
+}
+
 int rmx_caf_batch(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                   const double* doppler_cps, int n_dopplers, int32_t* dop_idx, int32_t* lag_int, float* lag_frac,
                   float* peak, unsigned flags) {
-    return rmx_caf_batch_request(c, iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, nullptr, 0, RMX_WEIGHT_NONE, nullptr, 0,
-                                 dop_idx, nullptr, lag_int, lag_frac, peak, flags);
+    return caf_request(c, caf_args(iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, dop_idx, nullptr, lag_int, lag_frac, peak), flags);
 }
 
 // The Doppler search under a request: a band and PHAT on every stored spectrum, the rotated ones included, lag intervals
 // in every hypothesis' peak search, and (dop_frac) the parabola through the winner's and its two neighbours' peaks.
-// It is rmx_caf_batch_quality with nothing refined or qualified: the same kernels, the same launches
+// Nothing requested IS rmx_caf_batch.
 int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                           const double* doppler_cps, int n_dopplers,
                           const double* band_cps, int band_per_window, unsigned weighting,
                           const int32_t* lag_bounds, int bounds_per_window,
                           int32_t* dop_idx, float* dop_frac,
                           int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
-    return rmx_caf_batch_quality(c, iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, band_cps, band_per_window, weighting, lag_bounds,
-                                 bounds_per_window, 0, dop_idx, dop_frac, lag_int, lag_frac, peak, nullptr, flags);
+    return caf_request(c, weighted_args(caf_args(iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, dop_idx, dop_frac, lag_int, lag_frac, peak),
+                                        band_cps, band_per_window, weighting, lag_bounds, bounds_per_window), flags);
 }
 
 // rmx_caf_batch_request with the fine lag search and the quality figures of rmx_xcorr_batch_quality on each slot's WINNING
@@ -1869,15 +2051,18 @@ int rmx_caf_batch_request(rmx_ctx* c, const void* iq, int n_windows, const int32
 // operand i from the un-rotated spectra and operand j from the winner's de-rotated ones.  Where every hypothesis' set is
 // resident (the one-launch path of N = 4096) that is one launch of each; elsewhere the hypotheses of a chunk are swept a
 // second time, each forward pass followed by the two kernels, whose workgroups return unless their slot's winner is resident.
-// It is rmx_caf_batch_integrated with one window per group: the same kernels, the same launches
+// refine == 0 and quality == NULL IS rmx_caf_batch_request.
 int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                           const double* doppler_cps, int n_dopplers,
                           const double* band_cps, int band_per_window, unsigned weighting,
                           const int32_t* lag_bounds, int bounds_per_window, int refine,
                           int32_t* dop_idx, float* dop_frac,
                           int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
-    return rmx_caf_batch_integrated(c, iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, 1, band_cps, band_per_window, weighting,
-                                    lag_bounds, bounds_per_window, refine, dop_idx, dop_frac, lag_int, lag_frac, peak, quality, flags);
+    host::RequestArgs a = weighted_args(caf_args(iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, dop_idx, dop_frac, lag_int, lag_frac, peak),
+                                        band_cps, band_per_window, weighting, lag_bounds, bounds_per_window);
+    a.refine = refine;
+    a.quality = quality;
+    return caf_request(c, a, flags);
 }
 
 // The Doppler search integrated noncoherently over groups of K = `integrate` consecutive windows: coherent per window
@@ -1885,193 +2070,19 @@ int rmx_caf_batch_quality(rmx_ctx* c, const void* iq, int n_windows, const int32
 // forward kernels are the search's; the pair kernels are the integrating instantiations with operand j from the
 // de-rotated set (pack <LagBounds, Integrate, CafOperand>, integrate.hpp; the four-step row kernels take spec_j as they
 // are and g_cols_inv's integrating instantiation sums their products); the selection runs on G * n_pairs slots; k_quality
-// and k_refine <CafWinner> walk the group's windows.  K = 1 is rmx_caf_batch_quality itself: none of the above is reached.
+// and k_refine <CafWinner> walk the group's windows.  integrate == 1 IS rmx_caf_batch_quality: none of the above is reached.
 int rmx_caf_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                              const double* doppler_cps, int n_dopplers, int integrate,
                              const double* band_cps, int band_per_window, unsigned weighting,
                              const int32_t* lag_bounds, int bounds_per_group, int refine,
                              int32_t* dop_idx, float* dop_frac,
                              int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags) {
-    const int bounds_per_window = bounds_per_group;   // (per output row: the window, or the group)
-    if (!c) return RMX_E_INVAL;
-    if (!iq || !dop_idx || !lag_int || !lag_frac || !peak || !doppler_cps) return fail(c, RMX_E_INVAL, "NULL buffer");
-    std::string why;
-    {   // a device pointer aligned to less than its element, as the correlation entries refuse it
-        const host::OutArray outs[5] = {{"dop_idx", dop_idx}, {"dop_frac", dop_frac}, {"lag_int", lag_int}, {"lag_frac", lag_frac}, {"peak", peak}};
-        if (host::check_alignment(flags, iq, outs, 5, &why) != RMX_OK) return fail(c, RMX_E_INVAL, "%s", why.c_str());
-    }
-    if (n_dopplers < 1 || n_dopplers > 4096) return fail(c, RMX_E_INVAL, "n_dopplers %d not in 1..4096", n_dopplers);
-    // (one window per group is rmx_caf_batch_quality, which takes an empty batch)
-    if (integrate != 1 && host::check_groups(integrate, n_windows, &why) != RMX_OK) return fail(c, RMX_E_INVAL, "%s", why.c_str());
-    const int K = integrate;
-    int rc = host::check_batch(c->n_buoys, c->max_windows, n_windows, pairs, &n_pairs, &why);
-    if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
-    if (n_windows == 0 || n_pairs == 0) return RMX_OK;
-    const int B = c->n_buoys, N = c->n_samples;
-    XcorrCall call;   // the plain request unless the checks below say otherwise
-    RMX_HIP(c, hipSetDevice(c->device));
-    // N = 4096, one chunk: all hypotheses in ONE forward launch and ONE pair launch (virtual window = hypothesis x
-    // window) instead of three launches per hypothesis -- 21 hypotheses on one frequency group: 431 -> ~60 us
-    const bool batch_bins = !c->generic && n_dopplers > 1 && n_windows <= c->chunk_windows &&
-                            (size_t)n_dopplers * n_windows * B * (8 * kThreads) * sizeof(float4) <= ((size_t)1 << 30) &&
-                            (long)n_dopplers * n_windows < (1L << 20);
-    if (!c->generic && !c->ppb_user) {               // (N = 4096: blocks sized to this batch, not to the previous call's)
-        int q = 7;
-        (void)host::split_cost4096(c->n_cus, c->n_buoys, n_pairs, (batch_bins ? n_windows * n_dopplers : n_windows) / K, 0, &q);
-        c->pairs_per_block = q;
-    }
-    rc = build_plan(c, pairs, n_pairs);              // validates the pair list
-    if (rc != RMX_OK) return rc;
-    const size_t out_elems = (size_t)(n_windows / K) * n_pairs;   // one slot per (group, pair)
-    {   // the request: the weighted entry's checks, the bounded entry's, then dop_frac; nothing is staged before the last
-        host::RequestArgs a = weighted_args(batch_args(iq, n_windows, pairs, n_pairs, lag_int, lag_frac, peak), band_cps, band_per_window,
-                                            weighting, lag_bounds, bounds_per_window);
-        a.n_buoys = B;
-        a.n_samples = N;
-        a.max_windows = c->max_windows;
-        a.refine = refine;
-        a.quality = quality;
-        a.flags = flags;
-        a.grouped = true;
-        a.integrate = K;
-        host::Request rq;
-        rc = host::check_caf_request(a, dop_idx, dop_frac, &rq, &why);
-        if (rc != RMX_OK) return fail(c, rc, "%s", why.c_str());
-        if (K > 1) {   // the route: a chunk holds whole groups (the ctx's chunk as it stands; generic_ensure may still halve it)
-            const host::RouteCaps caps = route_caps(c);
-            host::RoutePlan rp;
-            if ((c->generic ? caps.g_chunk : caps.chunk_windows) < K) rp.refused = host::kRefuseIntegChunk;
-            else if (c->generic && (1L << caps.logL) > caps.small_maxl && caps.col_tile > (long)caps.integ_max_per_thread * caps.cols_threads)
-                rp.refused = host::kRefuseIntegTile;
-            rc = route_refusal(c, rp, caps, K, 1);
-            if (rc != RMX_OK) return rc;
-        }
-        call.integ = rq.integ;
-        rc = describe_call(c, rq, &call);
-        if (rc != RMX_OK) return rc;
-    }
-    // What follows the selection.  `call` itself stays unrefined and unqualified: the forward and the pair kernels of the
-    // search are those of rmx_caf_batch_request whatever is asked here.
-    XcorrCall tail = call;
-    tail.refine = refine;
-    tail.quality = quality;
-    const bool with_tail = tail.refined() || tail.qualified();
-    const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
-    const size_t in_bytes = (size_t)n_windows * B * N * (u8 ? 2 : 8);
-    const void* d_iq = iq;
-    if (!in_dev) {
-        RMX_MEM(c->d_in.reserve(in_bytes));
-        RMX_HIP(c, hipMemcpyAsync(c->d_in, iq, in_bytes, hipMemcpyHostToDevice, c->stream));
-        d_iq = c->d_in;
-    }
-    // phasor table [D][N]: exp(-2 pi i nu n) in double, rounded once to float
-    std::vector<double> grid(doppler_cps, doppler_cps + n_dopplers);
-    if (!c->caf_rot.holds(grid)) {
-        std::vector<float2> rot((size_t)n_dopplers * N);
-        for (int d = 0; d < n_dopplers; ++d)
-            for (int n = 0; n < N; ++n) {
-                const double a = -6.283185307179586476925286766559 * grid[d] * (double)n;
-                rot[(size_t)d * N + n] = make_float2((float)std::cos(a), (float)std::sin(a));
-            }
-        RMX_MEM(c->caf_rot.refill(grid, rot));
-    }
-    const size_t caf_elems = batch_bins ? out_elems * (size_t)n_dopplers : out_elems;   // per-hypothesis results: [d][w][pair]
-    RMX_MEM(c->caf_lag.reserve(caf_elems));
-    RMX_MEM(c->caf_frac.reserve(caf_elems));
-    RMX_MEM(c->caf_peak.reserve(caf_elems));
-    int *b_dop = dop_idx, *b_lag = lag_int;
-    float *b_frac = lag_frac, *b_peak = peak;
-    if (!out_dev) {
-        {
-            const int rc_out = ensure_out(c, out_elems);
-            if (rc_out != RMX_OK) return rc_out;
-        }
-        const OutBlock o = out_block(c);
-        b_dop = o.dop; b_lag = o.lag; b_frac = o.frac; b_peak = o.peak;
-    }
-    float* b_dfrac = dop_frac;
-    if (dop_frac && (!batch_bins || !out_dev)) {   // k_caf_select_fd's three neighbour rows, and dop_frac of a host-pointer call
-        RMX_MEM(c->caf_nb.reserve(4 * out_elems));
-        if (!out_dev) b_dfrac = c->caf_nb + 3 * out_elems;
-    }
-    if (quality && !out_dev) {
-        RMX_MEM(c->d_quality.reserve(4 * out_elems));
-        tail.quality = c->d_quality;
-    }
-    // Per chunk of windows: the un-rotated spectra once, then per hypothesis the de-rotated spectra (the rotation
-    // is applied as the window is loaded), the pair kernels with X_i un-rotated and X_j de-rotated, and the
-    // running d-major first maximum.  No augmented copy of the windows, no second engine.
-    tm_reset(c);
-    int chunk;
-    if (c->generic) {
-        rc = rmx::generic_ensure(c, n_pairs);
-        if (rc != RMX_OK) return rc;
-        chunk = c->g_chunk;
-    } else {
-        chunk = c->chunk_windows;
-        rc = ensure_spec(c, n_windows < chunk ? n_windows : chunk);
-        if (rc != RMX_OK) return rc;
-    }
-    if (K > 1) {   // whole groups per chunk, never a silent split (a failed allocation may have halved the generic chunk)
-        chunk = chunk / K * K;
-        if (chunk == 0) {
-            host::RoutePlan rp;
-            rp.refused = host::kRefuseIntegChunk;
-            return route_refusal(c, rp, route_caps(c), K, 1);
-        }
-    }
-    const float osc = out_scale4096();
-    const SpecView sv = spec_view(c);
-    if (batch_bins) {
-        rc = fwd4096(c, call, d_iq, 0, n_windows, u8, nullptr);
-        if (rc == RMX_OK) rc = fwd4096(c, call, d_iq, 0, n_windows, u8, c->caf_rot, n_dopplers);
-        if (rc == RMX_OK) rc = pairs4096(c, call, 0, n_windows, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, osc, true, n_dopplers);
-        const dim3 sgrid((unsigned)((out_elems + 255) / 256));
-        if (rc == RMX_OK && !dop_frac)
-            rc = launch(c, kTkCafSelect, k_caf_select_all, sgrid, dim3(256), 0, n_dopplers, (long)out_elems, c->caf_lag, c->caf_frac,
-                        c->caf_peak, b_dop, b_lag, b_frac, b_peak);
-        if (rc == RMX_OK && dop_frac)
-            rc = launch(c, kTkCafSelect, k_caf_select_all_fd, sgrid, dim3(256), 0, n_dopplers, (long)out_elems, c->caf_lag, c->caf_frac,
-                        c->caf_peak, b_dop, b_lag, b_frac, b_peak, b_dfrac);
-        // every de-rotated set is resident: slot (w, q) reads operand j at virtual window dop_idx * W + w (a group's slot
-        // (g, q): at dop_idx * W + g K + kw, its K windows in order)
-        const CafWinner cw{b_dop, reinterpret_cast<const float2*>(c->d_spec_r.get()), (long)n_windows * B, -1};
-        if (rc == RMX_OK && tail.qualified()) rc = quality_chunk(c, tail, sv, 0, n_windows, n_pairs, b_peak, &cw);
-        if (rc == RMX_OK && tail.refined()) rc = refine_chunk(c, tail, sv, 0, n_windows, n_pairs, b_lag, b_frac, b_peak, &cw);
-    }
-    for (int w0 = 0; !batch_bins && w0 < n_windows && rc == RMX_OK; w0 += chunk) {
-        const int wc = n_windows - w0 < chunk ? n_windows - w0 : chunk;
-        rc = sv.forward(c, call, d_iq, w0, wc, u8, nullptr, false);
-        for (int d = 0; d < n_dopplers && rc == RMX_OK; ++d) {
-            const float2* rot = c->caf_rot + (size_t)d * N;
-            rc = sv.forward(c, call, d_iq, w0, wc, u8, rot, false);
-            if (rc != RMX_OK) break;
-            rc = sv.pairs(c, call, w0, wc, n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true, false);
-            if (rc != RMX_OK) break;
-            const long first = (long)(w0 / K) * n_pairs, cnt = (long)(wc / K) * n_pairs;   // the chunk's output rows
-            const dim3 sgrid((unsigned)((cnt + 255) / 256));
-            if (dop_frac)
-                rc = launch(c, kTkCafSelect, k_caf_select_fd, sgrid, dim3(256), 0, d, n_dopplers, first, cnt, (long)out_elems, c->caf_lag,
-                            c->caf_frac, c->caf_peak, b_dop, b_lag, b_frac, b_peak, c->caf_nb, b_dfrac);
-            else
-                rc = launch(c, kTkCafSelect, k_caf_select, sgrid, dim3(256), 0, d, first, cnt, c->caf_lag, c->caf_frac, c->caf_peak, b_dop,
-                            b_lag, b_frac, b_peak);
-        }
-        // The chunk's winners are known now and only the last hypothesis' de-rotated set is left: the hypotheses once
-        // more, each followed by k_quality and k_refine on the slots it won (k_quality in front: k_refine overwrites peak)
-        for (int d = 0; with_tail && d < n_dopplers && rc == RMX_OK; ++d) {
-            rc = sv.forward(c, call, d_iq, w0, wc, u8, c->caf_rot + (size_t)d * N, false);
-            const CafWinner cw{b_dop, c->generic ? c->g_spec_r.get() : reinterpret_cast<const float2*>(c->d_spec_r.get()), 0L, d};
-            if (rc == RMX_OK && tail.qualified()) rc = quality_chunk(c, tail, sv, w0, wc, n_pairs, b_peak, &cw);
-            if (rc == RMX_OK && tail.refined()) rc = refine_chunk(c, tail, sv, w0, wc, n_pairs, b_lag, b_frac, b_peak, &cw);
-        }
-    }
-    if (rc != RMX_OK) return rc;
-    if (out_dev) return RMX_OK;
-    // host-pointer results: dop_frac is queued in front of fetch_out, which waits for the stream
-    if (dop_frac) RMX_HIP(c, hipMemcpyAsync(dop_frac, b_dfrac, out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (quality) RMX_HIP(c, hipMemcpyAsync(quality, tail.quality, 4 * out_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    return fetch_out(c, out_elems, lag_int, lag_frac, peak, dop_idx);
+    host::RequestArgs a = weighted_args(caf_args(iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, dop_idx, dop_frac, lag_int, lag_frac, peak),
+                                        band_cps, band_per_window, weighting, lag_bounds, bounds_per_group);
+    a.integrate = integrate;
+    a.refine = refine;
+    a.quality = quality;
+    return caf_request(c, a, flags);
 }
 
 int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32_t* pairs, int n_pairs,

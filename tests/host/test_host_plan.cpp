@@ -420,9 +420,167 @@ static void test_route_invariants() {
           !is_default_list(3, d3, 2));
 }
 
+// ---- the Doppler search: plan_caf ----------------------------------------------------------------------------------------
+// The rows of tests/golden/caf_route_table.json, transcribed (three hypotheses unless D says otherwise; ncus = 8): the launch
+// counts are the RECORDING's (the library of the commit before plan_caf, on an MI355X), the plan must imply exactly them.
+// chunk: chunk_windows as rmx_create derives it (caps4096), or g_chunk of a generic ctx (gen_chunk, else max_windows = W).
+// fwd: launches of each forward family (k_fwd; g_fwd_small; g_cols_fwd and g_rows_fwd each); pair: of each pair family
+// (k_win|k_pair; g_pair_small; g_cols_inv, g_rows_inv and g_final each); then k_caf_select, k_quality, k_refine.
+struct RecordedCaf {
+    const char* name;
+    int B, W, D, K, logL;       // logL = 0: N = 4096 on its own kernels
+    int chunk_opt, ppb_user;
+    bool fine, refined, qualified, out_dev;
+    int fwd, pair, select, quality, refine;
+    RouteRefusal refused;
+};
+static const RecordedCaf kRecordedCaf[] = {
+    {"caf_n256_fine", 3, 4, 3, 1, 9, 0, 0, true, false, false, false, 4, 3, 3, 0, 0, kRouteOk},
+    {"caf_n256_bounded_band_phat", 3, 4, 3, 1, 9, 0, 0, false, false, false, false, 4, 3, 3, 0, 0, kRouteOk},
+    {"caf_n256_integ2", 3, 4, 3, 2, 9, 0, 0, false, false, false, false, 4, 3, 3, 0, 0, kRouteOk},
+    {"caf_n256_refine4_quality", 3, 4, 3, 1, 9, 0, 0, false, true, true, false, 7, 3, 3, 3, 3, kRouteOk},
+    {"caf_n256_all", 3, 4, 3, 2, 9, 0, 0, true, true, true, false, 7, 3, 3, 3, 3, kRouteOk},
+    {"caf_n256_all_two_chunks", 3, 8, 3, 2, 9, 4, 0, true, true, true, false, 14, 6, 6, 6, 6, kRouteOk},
+    {"caf_n4096_one_fine", 3, 4, 3, 1, 0, 4096, 0, true, false, false, false, 2, 1, 1, 0, 0, kRouteOk},
+    {"caf_n4096_one_bounded_band_phat", 3, 4, 3, 1, 0, 4096, 0, false, false, false, false, 2, 1, 1, 0, 0, kRouteOk},
+    {"caf_n4096_one_integ2", 3, 4, 3, 2, 0, 4096, 0, false, false, false, false, 2, 1, 1, 0, 0, kRouteOk},
+    {"caf_n4096_one_refine4_quality", 3, 4, 3, 1, 0, 4096, 0, false, true, true, false, 2, 1, 1, 1, 1, kRouteOk},
+    {"caf_n4096_one_all", 3, 4, 3, 2, 0, 4096, 0, true, true, true, false, 2, 1, 1, 1, 1, kRouteOk},
+    {"caf_n4096_per_fine", 3, 12, 3, 1, 0, 8, 0, true, false, false, false, 8, 6, 6, 0, 0, kRouteOk},
+    {"caf_n4096_per_bounded_band_phat", 3, 12, 3, 1, 0, 8, 0, false, false, false, false, 8, 6, 6, 0, 0, kRouteOk},
+    {"caf_n4096_per_integ2", 3, 12, 3, 2, 0, 8, 0, false, false, false, false, 8, 6, 6, 0, 0, kRouteOk},
+    {"caf_n4096_per_refine4_quality", 3, 12, 3, 1, 0, 8, 0, false, true, true, false, 14, 6, 6, 6, 6, kRouteOk},
+    {"caf_n4096_per_all", 3, 12, 3, 2, 0, 8, 0, true, true, true, false, 14, 6, 6, 6, 6, kRouteOk},
+    {"caf_n4096_per_all_two_chunks", 3, 16, 3, 2, 0, 8, 0, true, true, true, false, 14, 6, 6, 6, 6, kRouteOk},
+    {"caf_n8192_fine", 3, 4, 3, 1, 14, 0, 0, true, false, false, false, 4, 3, 3, 0, 0, kRouteOk},
+    {"caf_n8192_bounded_band_phat", 3, 4, 3, 1, 14, 0, 0, false, false, false, false, 4, 3, 3, 0, 0, kRouteOk},
+    {"caf_n8192_integ2", 3, 4, 3, 2, 14, 0, 0, false, false, false, false, 4, 3, 3, 0, 0, kRouteOk},
+    {"caf_n8192_refine4_quality", 3, 4, 3, 1, 14, 0, 0, false, true, true, false, 7, 3, 3, 3, 3, kRouteOk},
+    {"caf_n8192_all", 3, 4, 3, 2, 14, 0, 0, true, true, true, false, 7, 3, 3, 3, 3, kRouteOk},
+    {"caf_n8192_all_two_chunks", 3, 8, 3, 2, 14, 4, 0, true, true, true, false, 14, 6, 6, 6, 6, kRouteOk},
+    {"caf_n4096_single", 3, 4, 1, 1, 0, 4096, 0, false, false, false, false, 2, 1, 1, 0, 0, kRouteOk},
+    {"caf_n4096_one_fine_device", 3, 4, 3, 1, 0, 4096, 0, true, false, false, true, 2, 1, 1, 0, 0, kRouteOk},
+    {"caf_n4096_per_fine_device", 3, 12, 3, 1, 0, 8, 0, true, false, false, true, 8, 6, 6, 0, 0, kRouteOk},
+    {"caf_n4096_u8", 3, 4, 3, 1, 0, 4096, 0, false, false, false, false, 2, 1, 1, 0, 0, kRouteOk},
+    {"caf_n4096_generic", 3, 4, 3, 1, 13, 0, 0, false, false, false, false, 4, 3, 3, 0, 0, kRouteOk},
+    {"caf_n4096_rev", 3, 4, 3, 1, 0, 4096, 0, false, false, false, false, 2, 1, 1, 0, 0, kRouteOk},
+    {"caf_n4096_b8_ppb3_integ2", 8, 4, 3, 2, 0, 4096, 3, false, false, false, false, 2, 1, 1, 0, 0, kRouteOk},
+    {"caf_n4096_integ16_chunk8", 3, 16, 3, 16, 0, 8, 0, false, false, false, false, 0, 0, 0, 0, 0, kRefuseIntegChunk},
+    {"caf_n8192_integ2_chunk1", 3, 4, 3, 2, 14, 1, 0, false, false, false, false, 0, 0, 0, 0, 0, kRefuseIntegChunk},
+    {"caf_n65536_integ2_cols64", 3, 4, 3, 2, 17, 0, 0, false, false, false, false, 0, 0, 0, 0, 0, kRefuseIntegTile},
+};
+
+static bool same_caf_plan(const CafPlan& a, const CafPlan& b) {
+    return a.one_launch == b.one_launch && a.ppb == b.ppb && a.chunk == b.chunk && a.refused == b.refused && a.out_elems == b.out_elems &&
+           a.hyp_elems == b.hyp_elems && a.need_nb == b.need_nb && a.stage_dfrac == b.stage_dfrac && a.second_sweep == b.second_sweep;
+}
+
+static void test_recorded_caf_rows() {
+    int n = 0, n_one = 0;
+    for (const RecordedCaf& r : kRecordedCaf) {
+        RouteCaps k = caps4096(r.B, r.W, 8, r.chunk_opt);
+        k.ppb_user = r.ppb_user;
+        if (r.logL) {
+            k.generic = true;
+            k.logL = r.logL;
+            k.g_chunk = r.chunk_opt ? r.chunk_opt : r.W;
+            if (r.logL == 17) { k.col_tile = 2048; k.cols_threads = 64; }   // (the recorded text: 2048 elements on 64 threads)
+        }
+        const CafCall a{r.W, r.B * (r.B - 1) / 2, r.D, r.K, r.fine, r.refined, r.qualified, r.out_dev};
+        const CafPlan p = plan_caf(k, a);
+        CHECK(p.refused == r.refused);
+        ++n;
+        if (p.refused != kRouteOk) continue;
+        int fwd = 2, pair = 1, select = 1, quality = r.qualified, refine = r.refined;
+        if (!p.one_launch) {
+            const int chunks = (r.W + p.chunk - 1) / p.chunk, tail = p.second_sweep ? chunks * r.D : 0;
+            fwd = chunks * (1 + r.D) + tail;
+            pair = select = chunks * r.D;
+            quality = r.qualified ? tail : 0;
+            refine = r.refined ? tail : 0;
+        }
+        if (fwd != r.fwd || pair != r.pair || select != r.select || quality != r.quality || refine != r.refine) {
+            std::fprintf(stderr, "%s: the plan implies %d forward, %d pair, %d select, %d quality, %d refine launches, recorded %d %d %d %d %d\n",
+                         r.name, fwd, pair, select, quality, refine, r.fwd, r.pair, r.select, r.quality, r.refine);
+            std::exit(1);
+        }
+        if (r.ppb_user) CHECK(p.ppb == r.ppb_user);
+        CHECK(p.need_nb == (r.fine && !(p.one_launch && r.out_dev)));   // the two sides of the caf_nb rule: the two _device rows
+        n_one += p.one_launch;
+    }
+    CHECK(n == 33 && n_one == 9);
+}
+
+static void test_caf_thresholds() {
+    // at most 1 GiB of de-rotated spectra: 3 buoys x 8 windows x 64 KiB x D
+    RouteCaps k = caps4096(3, 8, 8);
+    CafCall a;
+    a.n_windows = 8;  a.n_pairs = 3;
+    a.n_dopplers = 682;
+    CHECK(plan_caf(k, a).one_launch && plan_caf(k, a).hyp_elems == (size_t)8 * 3 * 682);
+    a.n_dopplers = 683;
+    CHECK(!plan_caf(k, a).one_launch && plan_caf(k, a).hyp_elems == (size_t)8 * 3);
+    // D > 1, and one chunk
+    a.n_dopplers = 1;
+    CHECK(!plan_caf(k, a).one_launch);
+    a.n_dopplers = 2;
+    CHECK(plan_caf(k, a).one_launch);
+    k = caps4096(3, 16, 8, 8);
+    a.n_windows = 9;
+    CHECK(!plan_caf(k, a).one_launch);
+    a.n_windows = 8;
+    CHECK(plan_caf(k, a).one_launch);
+    k.generic = true;
+    CHECK(!plan_caf(k, a).one_launch);
+    // D * W < 2^20 virtual windows: with two or more buoys the 1 GiB above is reached first (D * W * B <= 2^14), so from
+    // either side of 2^20 the answer is the same -- the bound only guards the launch arithmetic should the other ever move
+    k = caps4096(3, 1024, 8);
+    a.n_windows = 1023;  a.n_dopplers = 1025;   // 2^20 - 1
+    CHECK((long)a.n_windows * a.n_dopplers == (1L << 20) - 1 && !plan_caf(k, a).one_launch);
+    a.n_windows = 1024;  a.n_dopplers = 1024;   // 2^20
+    CHECK(!plan_caf(k, a).one_launch);
+}
+
+static void test_caf_invariants() {
+    long n_plans = 0;
+    for (int B : {2, 3, 8})
+        for (int generic = 0; generic < 3; ++generic)                                  // N = 4096 / small L / four-step
+            for (int chunk : {1, 3, 8, 64})
+                for (int ppb_user : {0, 9})
+                    for (int W = 1; W <= 20; ++W)
+                        for (int D : {1, 2, 3, 21, 683, 4096})
+                            for (int K : {1, 2, 5})
+                                for (int flags = 0; flags < 16; ++flags) {
+                                    if (W % K != 0) continue;                           // (refused by the entry)
+                                    RouteCaps k;
+                                    k.n_cus = 8;  k.n_buoys = B;  k.generic = generic != 0;  k.logL = generic == 2 ? 14 : 13;
+                                    k.chunk_windows = k.g_chunk = chunk;  k.ppb_user = ppb_user;
+                                    k.col_tile = 512;  k.cols_threads = flags & 1 ? 64 : 16;   // 16 threads: 32 per thread, refused
+                                    const int P = B * (B - 1) / 2;
+                                    const CafCall a{W, P, D, K, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (flags & 8) != 0};
+                                    const CafPlan p = plan_caf(k, a);
+                                    ++n_plans;
+                                    CHECK(same_caf_plan(p, plan_caf(k, a)));            // a pure function
+                                    CHECK(p.refused != kRouteOk || (p.chunk > 0 && p.chunk % K == 0 && p.chunk <= chunk));
+                                    if (p.refused != kRouteOk) CHECK(K > 1);
+                                    CHECK((p.refused == kRefuseIntegChunk) == (K > chunk));
+                                    if (p.refused == kRefuseIntegTile) CHECK(generic == 2 && k.cols_threads == 16);
+                                    CHECK(p.second_sweep == ((a.refined || a.qualified) && !p.one_launch));
+                                    CHECK(p.need_nb == (a.fine && (!p.one_launch || !a.out_dev)));
+                                    CHECK(p.stage_dfrac == (a.fine && !a.out_dev) && (!p.stage_dfrac || p.need_nb));
+                                    CHECK(ppb_user ? p.ppb == ppb_user : (p.ppb >= 1 && p.ppb <= 7));
+                                    if (p.one_launch) CHECK(!k.generic && D > 1 && W <= chunk && (long)D * W * B <= (1L << 14));
+                                    CHECK(p.out_elems == (size_t)(W / K) * P && p.hyp_elems == p.out_elems * (p.one_launch ? D : 1));
+                                }
+    CHECK(n_plans > 100000);
+}
+
 int main() {
     test_route_invariants();
     test_recorded_rows();
+    test_recorded_caf_rows();
+    test_caf_thresholds();
+    test_caf_invariants();
     test_options();
     test_create_args();
     test_request_conversions();

@@ -489,6 +489,114 @@ static void test_caf_tail() {
     CHECK(caf(weighted(plain(o), &full, 0, 0, &full_lb, 0), dop_idx, dop_frac.data(), &r, &err) == RMX_OK && !r.weighted && !r.bounded);
 }
 
+// ---- the head of the Doppler entries, in front of that tail: NULL buffer, alignment of the five arrays, n_dopplers, the group
+// count (integrate != 1 only), the batch shape, the empty batch, the pair list ------------------------------------------------------
+// The WHOLE check, as caf_request in rmx_hip.hip calls it: the arguments as an entry fills them (the grid and the search's own
+// two outputs in RequestArgs)
+static const double kGrid[3] = {-1e-4, 0.0, 1e-4};
+static int check_caf(RequestArgs a, const int32_t* dop_idx, const float* dop_frac, Request* r, std::string* err) {
+    if (!a.doppler_cps && a.n_dopplers == 0) {
+        a.doppler_cps = kGrid;
+        a.n_dopplers = 3;
+    }
+    a.dop_idx = const_cast<int32_t*>(dop_idx);
+    a.dop_frac = const_cast<float*>(dop_frac);
+    return check_caf_request(a, r, err);
+}
+static void test_caf_head() {
+    Outs o((size_t)W * P);
+    std::vector<int32_t> dop_idx((size_t)W * P);
+    std::vector<float> dop_frac((size_t)W * P);
+    const std::vector<double> band1 = bands_of(1);
+    std::vector<double> bad_band = band1;
+    bad_band[0] = 0.3; bad_band[1] = -0.2;
+    std::vector<int32_t> bad_lb = bounds_of(P);
+    bad_lb[2] = 4; bad_lb[3] = 3;
+    const std::vector<int32_t> bad_pairs = {0, 1, 0, 3, 1, 2}, rev = {1, 2, 0, 2, 0, 1};
+    Request r;
+    std::string err;
+    auto refused_caf = [&](const RequestArgs& a, const int32_t* di, const float* df, const char* text) {
+        const int rc = check_caf(a, di, df, &r, &err);
+        if (rc != RMX_E_INVAL || err != text) std::fprintf(stderr, "rc %d, text \"%s\"\n  wanted \"%s\"\n", rc, err.c_str(), text);
+        return rc == RMX_E_INVAL && err == text;
+    };
+    const int32_t* di = dop_idx.data();
+    const float* df = dop_frac.data();
+    const char* past2 = reinterpret_cast<const char*>(df) + 2;
+    // everything at once that the tail refuses: a bad weighting, a bad band, bad bounds, refine = 3, quality over peak
+    const RequestArgs bad_tail = grouped(weighted(plain(o), &bad_band, 0, 7, &bad_lb, 0), 1, 3, o.peak.data());
+    // a NULL buffer: each of the six the plain search takes (dop_frac and quality may be NULL), in front of everything else
+    for (int k = 0; k < 6; ++k) {
+        RequestArgs a = bad_tail;
+        a.n_dopplers = k == 5 ? 3 : 9999;   // (k == 5: doppler_cps stays NULL)
+        a.doppler_cps = k == 5 ? nullptr : kGrid;
+        a.flags = RMX_OUT_DEVICE;
+        if (k == 0) a.iq = nullptr;
+        if (k == 2) a.lag_int = nullptr;
+        if (k == 3) a.lag_frac = nullptr;
+        if (k == 4) a.peak = nullptr;
+        CHECK(refused_caf(a, k == 1 ? nullptr : di, reinterpret_cast<const float*>(past2), kNull));
+    }
+    // a misaligned device pointer: in the order dop_idx, dop_frac, lag_int, lag_frac, peak, in front of n_dopplers
+    {
+        RequestArgs a = bad_tail;
+        a.doppler_cps = kGrid;
+        a.n_dopplers = 0;
+        a.flags = RMX_OUT_DEVICE;
+        a.lag_int = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(o.lag_int.data()) + 1);
+        CHECK(refused_caf(a, di, reinterpret_cast<const float*>(past2),
+                          "dop_frac is a device pointer 2 bytes past a multiple of 4: an output must be aligned to 4 bytes (one element)"));
+        CHECK(refused_caf(a, di, df, "lag_int is a device pointer 1 bytes past a multiple of 4: an output must be aligned to 4 bytes (one element)"));
+        CHECK(refused_caf(a, reinterpret_cast<const int32_t*>(past2), reinterpret_cast<const float*>(past2),
+                          "dop_idx is a device pointer 2 bytes past a multiple of 4: an output must be aligned to 4 bytes (one element)"));
+        a.flags = RMX_IN_DEVICE;   // host outputs need nothing; a device iq does
+        a.iq = reinterpret_cast<const char*>(g_iq.data()) + 4;
+        CHECK(refused_caf(a, di, df, "iq is a device pointer 4 bytes past a multiple of 8: complex64 input must be aligned to 8 bytes (one sample)"));
+        a.flags = 0;
+        CHECK(refused_caf(a, di, reinterpret_cast<const float*>(past2), "n_dopplers 0 not in 1..4096"));
+    }
+    // n_dopplers in front of the group count, the batch shape, the pair list and the whole tail
+    for (int d : {0, -1, 4097}) {
+        RequestArgs a = grouped(weighted(plain(o, W + 1, bad_pairs.data(), P), &bad_band, 0, 7, &bad_lb, 0), 3, 3, o.peak.data());
+        a.doppler_cps = kGrid;
+        a.n_dopplers = d;
+        char want[48];
+        std::snprintf(want, sizeof want, "n_dopplers %d not in 1..4096", d);
+        CHECK(refused_caf(a, di, o.peak.data(), want));
+    }
+    // the group count (integrate != 1 only) in front of the batch shape; one window per group looks at the batch shape alone
+    CHECK(refused_caf(grouped(weighted(plain(o, W + 1, bad_pairs.data(), P), &bad_band, 0, 7), 3), di, df,
+                      "n_windows = 5 is not a positive multiple of integrate = 3"));
+    CHECK(refused_caf(grouped(plain(o, W, bad_pairs.data(), P), 0), di, df, "integrate = 0: at least one window per group"));
+    CHECK(refused_caf(grouped(plain(o, 0), 2), di, df, "n_windows = 0 is not a positive multiple of integrate = 2"));
+    CHECK(refused_caf(grouped(weighted(plain(o, W + 1, bad_pairs.data(), P), &bad_band, 0, 7), 1), di, df, "n_windows 5 not in 0..max_windows=4"));
+    // the batch shape in front of the pair list and the tail
+    CHECK(refused_caf(weighted(plain(o, W, nullptr, 2), &bad_band, 0, 7, &bad_lb, 0), di, df, "pairs == NULL needs n_pairs == 0 or 3, got 2"));
+    CHECK(refused_caf(weighted(plain(o, W, bad_pairs.data(), -1), &bad_band, 0, 7), di, df, "n_pairs -1 < 0"));
+    // the empty batch is OK before its pairs, its bands and its refine are looked at (one window per group only)
+    CHECK(check_caf(grouped(weighted(plain(o, 0, bad_pairs.data(), P), &bad_band, 0, 7, &bad_lb, 0), 1, 3, o.peak.data()), di, o.peak.data(), &r, &err) == RMX_OK && r.empty);
+    CHECK(check_caf(weighted(plain(o, W, bad_pairs.data(), 0), &bad_band, 0, 7), di, df, &r, &err) == RMX_OK && r.empty && r.n_pairs == 0);
+    // the pair list in front of the weighting, the band, the bounds and everything behind them
+    const char* pair_text = "pair 1 = (0,3) out of range for 3 buoys";
+    CHECK(refused_caf(weighted(plain(o, W, bad_pairs.data(), P), &bad_band, 0, 7, &bad_lb, 0), di, o.peak.data(), pair_text));
+    CHECK(refused_caf(weighted(plain(o, W, bad_pairs.data(), P), &bad_band, 0, 0), di, df, pair_text));
+    CHECK(refused_caf(grouped(plain(o, W, bad_pairs.data(), P), 2, 3, o.peak.data()), di, df, pair_text));
+    const std::vector<int32_t> neg = {0, 1, -1, 2};
+    CHECK(refused_caf(plain(o, W, neg.data(), 2), di, df, "pair 1 = (-1,2) out of range for 3 buoys"));
+    // ... and a good list hands the tail its first refusal
+    CHECK(refused_caf(weighted(plain(o, W, rev.data(), P), &bad_band, 0, 7, &bad_lb, 0), di, o.peak.data(), kWeighting));
+    // accepted: a custom list, its length resolved; the default one by its count
+    CHECK(check_caf(plain(o, W, rev.data(), P), di, df, &r, &err) == RMX_OK && !r.empty && r.n_pairs == P);
+    CHECK(check_caf(plain(o, W, rev.data(), 2), di, df, &r, &err) == RMX_OK && r.n_pairs == 2);
+    CHECK(check_caf(plain(o, W, nullptr, 0), di, df, &r, &err) == RMX_OK && r.n_pairs == P);
+    for (int d : {1, 4096}) {
+        RequestArgs a = plain(o);
+        a.doppler_cps = kGrid;   // (only counted by the check, never read)
+        a.n_dopplers = d;
+        CHECK(check_caf(a, di, nullptr, &r, &err) == RMX_OK);
+    }
+}
+
 // ---- 3. the empty batches and the identities --------------------------------------------------------------------------------
 static void test_empty_and_identities() {
     Outs o((size_t)W * P), om((size_t)W * M * P);
@@ -660,6 +768,7 @@ int main() {
     test_refusal_texts();
     test_alignment();
     test_refusal_order();
+    test_caf_head();
     test_caf_tail();
     test_empty_and_identities();
     test_staged_layouts();

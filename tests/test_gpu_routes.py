@@ -1,8 +1,9 @@
-"""Replay of tests/golden/route_table.json (tools/record_routes.py): every case must launch the kernel families the
-recorded library launched, as often, and produce the same bytes in every output array (or refuse with the same text).
-The table was recorded with the library of the commit in front of the route planner (host_plan.hpp: plan_route), so this
-pins "the planner chooses what the scattered rules chose".  A case recorded as not reproducible (digest null) carries its
-arrays and is compared with the bars of test_gpu_parity: integer outputs exact, 1e-5 on the lag, rtol 1e-5 on the rest."""
+"""Replay of tests/golden/route_table.json and tests/golden/caf_route_table.json (tools/record_routes.py): every case must
+launch the kernel families the recorded library launched, as often, and produce the same bytes in every output array (or
+refuse with the same text).  Each table was recorded with the library of the commit in front of its planner (host_plan.hpp:
+plan_route for the correlation, plan_caf for the Doppler search), so this pins "the planner chooses what the scattered rules
+chose".  A case recorded as not reproducible (digest null) carries its arrays and is compared with the bars of
+test_gpu_parity: integer outputs exact, 1e-5 on the lag (and on dop_frac), rtol 1e-5 on the rest."""
 import json
 import os
 import sys
@@ -16,8 +17,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import record_routes  # noqa: E402
 
-with open(record_routes.TABLE) as _f:
-    TABLE = json.load(_f)["cases"]
+TABLES = []
+for _path in (record_routes.TABLE, record_routes.CAF_TABLE):
+    with open(_path) as _f:
+        TABLES.append(json.load(_f)["cases"])
+TABLE = TABLES[0] + TABLES[1]
 
 
 @pytest.fixture(scope="module")
@@ -29,8 +33,9 @@ def built():
 
 
 def test_table_is_mostly_reproducible():
-    nulls = [r["name"] for r in TABLE if "error" not in r and r["digest"] is None]
-    assert 10 * len(nulls) <= len(TABLE), nulls
+    for table in TABLES:   # each on its own
+        nulls = [r["name"] for r in table if "error" not in r and r["digest"] is None]
+        assert 10 * len(nulls) <= len(table), nulls
 
 
 @pytest.mark.parametrize("row", TABLE, ids=[r["name"] for r in TABLE])
@@ -49,11 +54,14 @@ def test_route(built, row):
     caf = row["kind"] == "caf"
     if caf:
         assert np.array_equal(got["arrays"][0], ref[0])
-    li, lf, pk = got["arrays"][1 if caf else 0:][:3]
-    ri, rf, rp = ref[1 if caf else 0:][:3]
+    first = (2 if row.get("fine") else 1) if caf else 0   # behind dop_idx (and dop_frac)
+    if first == 2:
+        assert np.all(np.abs(got["arrays"][1] - ref[1]) <= 1e-5)
+    li, lf, pk = got["arrays"][first:][:3]
+    ri, rf, rp = ref[first:][:3]
     assert np.array_equal(li, ri)
     lag, rlag = li + lf.astype(np.float64), ri + rf.astype(np.float64)
     assert np.all(np.abs(lag - rlag) <= 1e-5 * np.maximum(np.abs(rlag), 1.0))
     assert np.allclose(pk, rp, rtol=1e-5, atol=0)
     if row["quality"]:
-        assert np.allclose(got["arrays"][3], ref[3], rtol=1e-5, atol=0)
+        assert np.allclose(got["arrays"][first + 3], ref[first + 3], rtol=1e-5, atol=0)

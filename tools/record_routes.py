@@ -4,9 +4,11 @@ option timing = 1 and writes, per case, the parameters, last_timing_by_kernel() 
 SHA-256 over the bytes of every output array.  Each case runs twice; a case whose two digests differ gets digest null
 and its first run's arrays instead (tests/test_gpu_routes.py then compares it by value; only small cases can be kept so).
 
-usage: RMX_LIBRARY=<library of the commit the table pins> python tools/record_routes.py OUT.json
+usage: RMX_LIBRARY=<library of the commit the table pins> python tools/record_routes.py [--caf] OUT.json
        Record with the library of the commit BEFORE a change to the planner, never with the changed one; an existing
-       OUT.json is not overwritten.  tests/test_gpu_routes.py replays tests/golden/route_table.json on the tree's library."""
+       OUT.json is not overwritten.  tests/test_gpu_routes.py replays tests/golden/route_table.json on the tree's library.
+       --caf records caf_cases() instead of cases(): tests/golden/caf_route_table.json, the pin of the Doppler search's plan
+       (host_plan.hpp: plan_caf), recorded with the library of the commit in front of it and replayed by the same test."""
 import hashlib
 import json
 import os
@@ -16,6 +18,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = os.path.join(ROOT, "tests", "golden", "route_table.json")
+CAF_TABLE = os.path.join(ROOT, "tests", "golden", "caf_route_table.json")
 FS = 10e6
 MAX_KEPT = 4096   # elements of a not reproducible case's outputs that the table may carry
 
@@ -119,6 +122,47 @@ def cases():
     return out
 
 
+def caf_case(name, B, N, W, fine=False, **kw):
+    c = case(name, B, N, W, kind="caf", **{"dopplers": [-1e-4, 0.0, 1e-4], "defaults": {"ncus": 8}, **kw})
+    c["fine"] = fine
+    return c
+
+
+def caf_cases():
+    """the Doppler search: every branch of the request on every route, 3 buoys and three hypotheses unless stated"""
+    out = []
+    band = [-0.2, 0.3]
+    every = dict(fine=True, bounded=True, band=band, whiten=True, integrate=2, refine=4, quality=True)
+    # small-L kernels / N = 4096 in one launch / N = 4096 per hypothesis, chunks of 8 + 4 / four-step
+    for tag, N, W, d in (("n256", 256, 4, {}), ("n4096_one", 4096, 4, {}), ("n4096_per", 4096, 12, {"chunk_windows": 8}),
+                         ("n8192", 8192, 4, {})):
+        f = lambda t, W=W, d=d, **kw: out.append(caf_case(f"caf_{tag}_{t}", 3, N, W, defaults={"ncus": 8, **d}, **kw))   # noqa: E731
+        f("fine", fine=True)
+        f("bounded_band_phat", bounded=True, band=band, whiten=True)
+        f("integ2", integrate=2)
+        f("refine4_quality", refine=4, quality=True)
+        f("all", **every)
+        # two chunks: the second sweep over the hypotheses crosses a seam (N = 4096: more windows than a chunk is never
+        # one launch, so the two N = 4096 rows are one)
+        if tag != "n4096_one":
+            two = {"chunk_windows": 8} if N == 4096 else {"gen_chunk": 4}
+            f("all_two_chunks", W=16 if N == 4096 else 8, d=two, **every)
+    f = lambda t, B=3, N=4096, W=4, **kw: out.append(caf_case(f"caf_{t}", B, N, W, **kw))   # noqa: E731
+    f("n4096_single", dopplers=[1e-4])                              # one hypothesis: never one launch
+    f("n4096_one_fine_device", fine=True, device=True)              # the two sides of the caf_nb rule
+    f("n4096_per_fine_device", W=12, defaults={"ncus": 8, "chunk_windows": 8}, fine=True, device=True)
+    f("n4096_u8", u8=True)
+    f("n4096_generic", defaults={"ncus": 8, "generic4096": 1})
+    f("n4096_rev", pairs="rev")
+    f("n4096_b8_ppb3_integ2", B=8, options={"pairs_per_block": 3}, integrate=2)
+    f("n4096_integ16_chunk8", W=16, defaults={"ncus": 8, "chunk_windows": 8}, integrate=16)
+    f("n8192_integ2_chunk1", N=8192, defaults={"ncus": 8, "gen_chunk": 1}, integrate=2)
+    f("n65536_integ2_cols64", N=65536, defaults={"ncus": 8, "cols_threads": 64}, integrate=2)
+    names = [c["name"] for c in out]
+    assert len(set(names)) == len(names)
+    return out
+
+
 def _pairs(kind, B):
     from radio_mapper_amd import xcorr
     pl = xcorr.pair_list(B)
@@ -163,12 +207,17 @@ def run_case(c):
                 eng.set_option(k, v)
             eng.set_option("timing", 1)
             try:
+                kw = dict(pairs=pairs, band=c["band"], whiten=c["whiten"], integrate=c["integrate"], refine=c["refine"])
+                if c["bounded"]:
+                    kw["lag_bounds"] = np.tile(np.array([[-64, 64]], np.int32), (P, 1))
                 if c["kind"] == "caf":
-                    arrays = eng.caf(iq, c["dopplers"], pairs=pairs)
+                    if c["integrate"] == 1:
+                        kw["integrate"] = None                   # (the search per window, as the rows without the key)
+                    if c["device"]:
+                        arrays = _caf_device(eng, iq, P, c, kw)
+                    else:
+                        arrays = eng.caf(iq, c["dopplers"], fine=c.get("fine", False), quality=c["quality"], **kw)
                 else:
-                    kw = dict(pairs=pairs, band=c["band"], whiten=c["whiten"], integrate=c["integrate"], refine=c["refine"])
-                    if c["bounded"]:
-                        kw["lag_bounds"] = np.tile(np.array([[-64, 64]], np.int32), (P, 1))
                     if c["device"]:
                         arrays = _correlate_device(eng, iq, P, c, kw)
                     else:
@@ -193,6 +242,24 @@ def _correlate_device(eng, iq, P, c, kw):
     eng.correlate_device(t_iq.data_ptr(), W, li.data_ptr(), lf.data_ptr(), pk.data_ptr(), u8=c["u8"], **kw)
     eng.synchronize()
     return li.cpu().numpy(), lf.cpu().numpy(), pk.cpu().numpy()
+
+
+def _caf_device(eng, iq, P, c, kw):
+    """caf_device with every output buffer [W // K][P] (quality [W // K][P][4]), in the order caf() returns them"""
+    import torch
+    W, G = c["W"], c["W"] // c["integrate"]
+    dev = torch.device("cuda", 0)
+    t_iq = torch.from_numpy(iq).to(dev)
+    i32 = lambda: torch.zeros((G, P), dtype=torch.int32, device=dev)      # noqa: E731
+    f32 = lambda *s: torch.zeros((G, P) + s, dtype=torch.float32, device=dev)   # noqa: E731
+    dop, li, lf, pk = i32(), i32(), f32(), f32()
+    df = f32() if c.get("fine", False) else None
+    q = f32(4) if c["quality"] else None
+    torch.cuda.synchronize()
+    eng.caf_device(t_iq.data_ptr(), W, c["dopplers"], dop.data_ptr(), li.data_ptr(), lf.data_ptr(), pk.data_ptr(), u8=c["u8"],
+                   dop_frac_ptr=df.data_ptr() if df is not None else 0, quality_ptr=q.data_ptr() if q is not None else 0, **kw)
+    eng.synchronize()
+    return tuple(t.cpu().numpy() for t in (dop, df, li, lf, pk, q) if t is not None)
 
 
 def digest(arrays):
@@ -220,13 +287,13 @@ def record(c):
     return row
 
 
-def main(out_path):
+def main(out_path, caf=False):
     if os.path.exists(out_path):
         sys.exit(f"{out_path} exists: a recorded table is not overwritten (move it away first)")
     sys.path.insert(0, ROOT)
     from radio_mapper_amd import xcorr
     rows = []
-    for c in cases():
+    for c in (caf_cases() if caf else cases()):
         row = record(c)
         rows.append(row)
         print("%-36s %s %s" % (c["name"], row.get("error") or row["launches"],
@@ -241,6 +308,7 @@ def main(out_path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 2:
+    args = [a for a in sys.argv[1:] if a != "--caf"]
+    if len(args) != 1:
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1]))
+    sys.exit(main(args[0], caf=len(args) < len(sys.argv) - 1))
