@@ -21,7 +21,18 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .shard import window_shard
-from .xcorr import check_band, check_bands, check_integrate, check_lag_bounds, check_refine
+from .xcorr import LagRequest, check_refine, lag_request
+
+
+def _more(req: LagRequest, name_refine: bool) -> dict:
+    """The keywords a block's call names beyond its arrays: an option at its default is left out, so that an engine that
+    does not know it still serves (name_refine: refine = 0 is named all the same)."""
+    more = {"refine": req.U} if req.U or name_refine else {}
+    if req.quality:
+        more["quality"] = True
+    if req.K > 1:
+        more["integrate"] = req.K
+    return more
 
 
 class MultiXcorrEngine:
@@ -94,26 +105,38 @@ class MultiXcorrEngine:
         """(start, count) of every device's block, in device order (empty blocks included)."""
         return [window_shard(n_windows, r, len(self.devices)) for r in range(len(self.devices))]
 
-    def _run(self, n_windows: int, call: Callable, n_out: int, dtypes, n_pairs: int, n_rows: Optional[int] = None,
-             tails=None):
-        """n_rows: the items that are sharded and the rows of the results (the groups of an integrated call); default: the
-        windows.  tails: per output, the trailing shape behind [rows][P] (the 4 of the quality array); default: none"""
-        if n_windows > self.max_windows:
-            raise ValueError(f"n_windows {n_windows} > max_windows {self.max_windows}")
-        n_windows = n_windows if n_rows is None else n_rows
-        tails = tails or [()] * len(dtypes)
-        outs = [np.zeros((n_windows, n_pairs) + tuple(t), dt) for dt, t in zip(dtypes, tails)]
+    def _n_pairs(self, pairs) -> int:
+        return self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
+
+    def _shard(self, req: LagRequest, iq: np.ndarray, call: Callable):
+        """The one sharding routine.  The request's rows -- the windows, or whole groups of K -- are block-sharded over the
+        devices; every block walks steps of whole groups that its engine holds and makes call(eng, the step's windows, its
+        lag bounds, its band(s)) (LagRequest.cut); the parts are gathered into outputs of the request's shapes and dtypes."""
+        if req.n_windows > self.max_windows:
+            raise ValueError(f"n_windows {req.n_windows} > max_windows {self.max_windows}")
+        K = req.K
+        outs = [np.zeros(shape, dt) for _, dt, shape in req.outputs()]
+
+        def block(eng, gs, gc):
+            # the engines are sized for an even split of the WINDOWS; a block of whole groups may be a little larger
+            step = gc if K == 1 else getattr(eng, "max_windows", gc * K) // K
+            if step < 1:
+                raise ValueError(f"integrate = {K} windows per group is more than one device's engine holds "
+                                 f"({eng.max_windows} windows)")
+            parts = [call(eng, iq[g0 * K:g1 * K], *req.cut(g0, g1))
+                     for g0, g1 in ((g, min(g + step, gs + gc)) for g in range(gs, gs + gc, step))]
+            return parts[0] if len(parts) == 1 else [np.concatenate([p[k] for p in parts]) for k in range(len(outs))]
         with self._lock:
             futs = []
-            for r, (s, c) in enumerate(self.blocks(n_windows)):
+            for r, (s, c) in enumerate(self.blocks(req.rows)):
                 if c:
-                    futs.append((s, c, self._pools[r].submit(call, self._engines[r], s, c)))
+                    futs.append((s, c, self._pools[r].submit(block, self._engines[r], s, c)))
             err = None
             for s, c, f in futs:                 # wait for ALL workers before raising: no engine is left mid-call
                 try:
                     res = f.result()
-                    for k in range(n_out):
-                        outs[k][s:s + c] = res[k]
+                    for k, out in enumerate(outs):
+                        out[s:s + c] = res[k]
                 except Exception as e:           # noqa: BLE001  (re-raised below)
                     err = err or e
             if err is not None:
@@ -133,36 +156,15 @@ class MultiXcorrEngine:
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
-        P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
-        K = check_integrate(integrate, iq.shape[0])
-        U = check_refine(refine)
-        n_out = 4 if quality else 3
-        dtypes = (np.int32, np.float32, np.float32, np.float32)[:n_out]
-        tails = [(), (), (), (4,)][:n_out]
-        if K > 1:
-            return self._correlate_integrated(iq, pairs, lag_bounds, band, whiten, K, P, U, bool(quality))
-        lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
+        req = lag_request("xcorr", self.n_buoys, iq.shape[0], None, lag_bounds, band, whiten, integrate, refine, quality,
+                          n_pairs=self._n_pairs(pairs))
+        more = _more(req, req.quality and req.K == 1)   # (a quality call names refine = 0 too, but not under integration)
 
-        bd, band_pw = check_band(band, iq.shape[0])
-
-        def block_bounds(s, c):
-            return lb[s:s + c] if per_window else lb
-
-        def block_call(eng, s, c):
-            if quality:
-                return eng.correlate(iq[s:s + c], pairs, None if lb is None else block_bounds(s, c),
-                                     band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, refine=U,
-                                     quality=True)
-            if U > 0:
-                return eng.correlate(iq[s:s + c], pairs, None if lb is None else block_bounds(s, c),
-                                     band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, refine=U)
-            if bd is not None or whiten:
-                return eng.correlate(iq[s:s + c], pairs, None if lb is None else block_bounds(s, c),
-                                     band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten)
-            if lb is not None:
-                return eng.correlate(iq[s:s + c], pairs, block_bounds(s, c))
-            return eng.correlate(iq[s:s + c], pairs)
-        return self._run(iq.shape[0], block_call, n_out, dtypes, P, tails=tails)
+        def call(eng, x, lb, bd):
+            if more or bd is not None or whiten:
+                return eng.correlate(x, pairs, lb, band=bd, whiten=whiten, **more)
+            return eng.correlate(x, pairs) if lb is None else eng.correlate(x, pairs, lb)
+        return self._shard(req, iq, call)
 
     def correlate_bands(self, iq: np.ndarray, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
                         whiten: bool = False, refine: int = 0, quality: bool = False, integrate: int = 1):
@@ -175,65 +177,11 @@ class MultiXcorrEngine:
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
-        W = iq.shape[0]
-        P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
-        K = check_integrate(integrate, W)
-        bd, bands_pw = check_bands(bands, W)
-        lb, per_window = check_lag_bounds(lag_bounds, W // K, P)
-        U = check_refine(refine)
-        more = {"refine": U, "quality": True} if quality else ({"refine": U} if U else {})
-        n_out = 4 if quality else 3
-        if K > 1:
-            def group_call(eng, gs, gc):
-                # (as _correlate_integrated: a block of whole groups may be a little larger than its engine)
-                step = getattr(eng, "max_windows", gc * K) // K
-                if step < 1:
-                    raise ValueError(f"integrate = {K} windows per group is more than one device's engine holds "
-                                     f"({eng.max_windows} windows)")
-                parts = []
-                for g0 in range(gs, gs + gc, step):
-                    g1 = min(g0 + step, gs + gc)
-                    parts.append(eng.correlate_bands(iq[g0 * K:g1 * K], bd[g0 * K:g1 * K] if bands_pw else bd, pairs,
-                                                     lag_bounds=None if lb is None else (lb[g0:g1] if per_window else lb),
-                                                     whiten=whiten, integrate=K, **more))
-                return tuple(np.concatenate([p[k] for p in parts]) for k in range(n_out))
-            return self._run(W, group_call, n_out, (np.int32, np.float32, np.float32, np.float32)[:n_out], bd.shape[-2],
-                             n_rows=W // K, tails=[(P,), (P,), (P,), (P, 4)][:n_out])
-
-        def block_call(eng, s, c):
-            return eng.correlate_bands(iq[s:s + c], bd[s:s + c] if bands_pw else bd, pairs,
-                                       lag_bounds=None if lb is None else (lb[s:s + c] if per_window else lb), whiten=whiten, **more)
-        # (_run's rows are [W][n_pairs] + tail: here [W][M] + (P,))
-        return self._run(W, block_call, n_out, (np.int32, np.float32, np.float32, np.float32)[:n_out], bd.shape[-2],
-                         tails=[(P,), (P,), (P,), (P, 4)][:n_out])
-
-    def _correlate_integrated(self, iq, pairs, lag_bounds, band, whiten, K, P, U=0, quality=False):
-        W = iq.shape[0]
-        G = W // K
-        lb, per_group = check_lag_bounds(lag_bounds, G, P)
-        bd, band_pw = check_band(band, W)
-
-        kw = {"refine": U} if U > 0 else {}
-        if quality:
-            kw["quality"] = True
-        n_out = 4 if quality else 3
-
-        def block_call(eng, gs, gc):
-            # the engines are sized for an even split of the WINDOWS; a block of whole groups may be a little larger
-            step = getattr(eng, "max_windows", gc * K) // K
-            if step < 1:
-                raise ValueError(f"integrate = {K} windows per group is more than one device's engine holds "
-                                 f"({eng.max_windows} windows)")
-            parts = []
-            for g0 in range(gs, gs + gc, step):
-                g1 = min(g0 + step, gs + gc)
-                parts.append(eng.correlate(iq[g0 * K:g1 * K], pairs,
-                                           None if lb is None else (lb[g0:g1] if per_group else lb),
-                                           band=None if bd is None else (bd[g0 * K:g1 * K] if band_pw else bd),
-                                           whiten=whiten, integrate=K, **kw))
-            return tuple(np.concatenate([p[k] for p in parts]) for k in range(n_out))
-        return self._run(W, block_call, n_out, (np.int32, np.float32, np.float32, np.float32)[:n_out], P, n_rows=G,
-                         tails=[(), (), (), (4,)][:n_out])
+        # (the bands and the bounds are checked in front of refine here)
+        req = lag_request("bands", self.n_buoys, iq.shape[0], None, lag_bounds, bands, whiten, integrate, 0, quality,
+                          n_pairs=self._n_pairs(pairs))._replace(U=check_refine(refine))
+        more = _more(req, req.quality)
+        return self._shard(req, iq, lambda eng, x, lb, bd: eng.correlate_bands(x, bd, pairs, lag_bounds=lb, whiten=whiten, **more))
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
             whiten: bool = False, fine: bool = False, refine: int = 0, quality: bool = False, integrate=None):
@@ -247,51 +195,13 @@ class MultiXcorrEngine:
         iq = np.asarray(iq)
         if iq.ndim != 3:
             raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
-        P = self.n_buoys * (self.n_buoys - 1) // 2 if pairs is None else np.asarray(pairs).reshape(-1, 2).shape[0]
-        K = 1 if integrate is None else check_integrate(integrate, iq.shape[0])
-        U = check_refine(refine)
-        more = {"refine": U, "quality": True} if quality else ({"refine": U} if U else {})
-        if K > 1:
-            return self._caf_integrated(iq, doppler_cps, pairs, lag_bounds, band, whiten, fine, more, K, P)
-        lb, per_window = check_lag_bounds(lag_bounds, iq.shape[0], P)
-        bd, band_pw = check_band(band, iq.shape[0])
-        if lb is None and bd is None and not whiten and not fine and not more:
-            return self._run(iq.shape[0], lambda eng, s, c: eng.caf(iq[s:s + c], doppler_cps, pairs), 4,
-                             (np.int32, np.int32, np.float32, np.float32), P)
+        # (the engines see the caller's own grid and check it themselves, as they do the pairs)
+        req = lag_request("caf", self.n_buoys, iq.shape[0], None, lag_bounds, band, whiten, integrate, refine, quality, (), fine,
+                          n_pairs=self._n_pairs(pairs))
+        more = _more(req, req.quality)
 
-        def block_call(eng, s, c):
-            return eng.caf(iq[s:s + c], doppler_cps, pairs,
-                           lag_bounds=None if lb is None else (lb[s:s + c] if per_window else lb),
-                           band=None if bd is None else (bd[s:s + c] if band_pw else bd), whiten=whiten, fine=fine, **more)
-        dtypes = (np.int32, np.float32, np.int32, np.float32, np.float32) if fine else (np.int32, np.int32, np.float32, np.float32)
-        tails = [()] * len(dtypes)
-        if quality:
-            dtypes, tails = dtypes + (np.float32,), tails + [(4,)]
-        return self._run(iq.shape[0], block_call, len(dtypes), dtypes, P, tails=tails)
-
-    def _caf_integrated(self, iq, doppler_cps, pairs, lag_bounds, band, whiten, fine, more, K, P):
-        """caf(integrate=K > 1): whole groups per device, as _correlate_integrated"""
-        W = iq.shape[0]
-        G = W // K
-        lb, per_group = check_lag_bounds(lag_bounds, G, P)
-        bd, band_pw = check_band(band, W)
-        dtypes = (np.int32, np.float32, np.int32, np.float32, np.float32) if fine else (np.int32, np.int32, np.float32, np.float32)
-        tails = [()] * len(dtypes)
-        if more.get("quality"):
-            dtypes, tails = dtypes + (np.float32,), tails + [(4,)]
-
-        def block_call(eng, gs, gc):
-            # the engines are sized for an even split of the WINDOWS; a block of whole groups may be a little larger
-            step = getattr(eng, "max_windows", gc * K) // K
-            if step < 1:
-                raise ValueError(f"integrate = {K} windows per group is more than one device's engine holds "
-                                 f"({eng.max_windows} windows)")
-            parts = []
-            for g0 in range(gs, gs + gc, step):
-                g1 = min(g0 + step, gs + gc)
-                parts.append(eng.caf(iq[g0 * K:g1 * K], doppler_cps, pairs,
-                                     lag_bounds=None if lb is None else (lb[g0:g1] if per_group else lb),
-                                     band=None if bd is None else (bd[g0 * K:g1 * K] if band_pw else bd),
-                                     whiten=whiten, fine=fine, integrate=K, **more))
-            return tuple(np.concatenate([p[k] for p in parts]) for k in range(len(dtypes)))
-        return self._run(W, block_call, len(dtypes), dtypes, P, n_rows=G, tails=tails)
+        def call(eng, x, lb, bd):
+            if more or lb is not None or bd is not None or whiten or fine:
+                return eng.caf(x, doppler_cps, pairs, lag_bounds=lb, band=bd, whiten=whiten, fine=fine, **more)
+            return eng.caf(x, doppler_cps, pairs)
+        return self._shard(req, iq, call)

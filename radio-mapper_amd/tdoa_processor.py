@@ -142,6 +142,15 @@ class GeodeticCalculator:
         return (math.degrees(brg) + 360) % 360, dist
 
 
+_DEFAULTS = {"lag_bounds": None, "band": None, "whiten": False, "integrate": 1, "refine": 0, "quality": False}
+
+
+def _named(**options) -> dict:
+    """Only the options that are not at their defaults, as keywords: an engine (or measure_lags, or a stub of either) that
+    does not know an option still serves every call that does not ask for it."""
+    return {k: v for k, v in options.items() if v is not None and (isinstance(v, np.ndarray) or v != _DEFAULTS[k])}
+
+
 # --------------------------------------------------------------------------------------------------
 # the seam: pairwise TDoA
 # --------------------------------------------------------------------------------------------------
@@ -308,7 +317,7 @@ class TDoACalculator:
         bands: None, or float [W][M][2] (with a channel axis: [C][W][M][2]): every window under M bands with one forward
         transform per buoy (rmx_xcorr_batch_bands); the three results are then [W][M][P] ([C][W][M][P]), lag_bounds stay
         per (window, pair).  Not together with band, integrate > 1, refine > 0, quality or doppler_cps (ValueError)."""
-        from .xcorr import check_integrate, check_refine
+        from .xcorr import check_refine
         refine = check_refine(refine)
         if bands is not None:
             for name, on in (("band", band is not None), ("integrate", integrate != 1), ("refine", refine > 0),
@@ -316,64 +325,23 @@ class TDoACalculator:
                 if on:
                     raise ValueError(f"bands and {name} cannot be combined: the multi-band correlation takes one band set "
                                      f"and has no integration, refinement, quality or Doppler search")
+            return self.measure_band_lags(iq, bands, pairs, lag_bounds, whiten, integrate=integrate)
         if doppler_cps is not None:
             for name, on in (("integrate", integrate != 1), ("refine", refine > 0), ("quality", bool(quality))):
                 if on:
                     raise ValueError(f"doppler_cps and {name} cannot be combined: the Doppler search has no integration, "
                                      f"refinement or quality")
-        iq = np.asarray(iq)
-        lead = None
-        if iq.ndim == 4:
-            lead = iq.shape[:2]
-            iq = iq.reshape((lead[0] * lead[1],) + iq.shape[2:])
-            integrate = check_integrate(integrate, lead[1])
-            lead = (lead[0], lead[1] // integrate)
-        elif iq.ndim == 3:
-            integrate = check_integrate(integrate, iq.shape[0])
-        if iq.ndim != 3:
-            raise ValueError(f"iq must be [W][B][N] or [C][W][B][N], got shape {iq.shape}")
-        n = iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2]
-        eng = self._engine(iq.shape[1], n, iq.shape[0])
-        lb = None
-        if lag_bounds is not None:
-            lb = np.asarray(lag_bounds)
-            if lead is not None and lb.ndim == 4:
-                lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
-        if bands is not None:
-            bs = np.asarray(bands)
-            if lead is not None and bs.ndim == 4:
-                bs = bs.reshape((-1,) + bs.shape[2:])
-            if bs.ndim != 3 or bs.shape[0] != iq.shape[0] or bs.shape[2] != 2:
-                raise ValueError(f"bands must be [W][M][2] or [C][W][M][2] for {iq.shape[0]} windows, got shape {np.shape(bands)}")
-            out = eng.correlate_bands(iq, bs, pairs, lag_bounds=lb, whiten=bool(whiten))
-        elif doppler_cps is not None:
+        iq, integrate, fold, unfold = self._channels(iq, integrate)
+        eng = self._engine(iq.shape[1], iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2], iq.shape[0])
+        lb, bd = fold(lag_bounds, 4, True), fold(band, 3)
+        if doppler_cps is not None:
             from .xcorr import doppler_estimate
-            bd = None
-            if band is not None:
-                bd = np.asarray(band)
-                if lead is not None and bd.ndim == 3:
-                    bd = bd.reshape((-1,) + bd.shape[2:])
             dop, dfrac, li, lf, pk = eng.caf(iq, doppler_cps, pairs, lag_bounds=lb, band=bd, whiten=bool(whiten), fine=True)
-            out = (li, lf, pk, dop, doppler_estimate(doppler_cps, dop, dfrac))
-        elif band is not None or whiten or integrate > 1 or refine > 0 or quality:
-            bd = None
-            if band is not None:
-                bd = np.asarray(band)
-                if lead is not None and bd.ndim == 3:
-                    bd = bd.reshape((-1,) + bd.shape[2:])
-            kw = {"integrate": integrate} if integrate > 1 else {}
-            if refine > 0:
-                kw["refine"] = refine
-            if quality:
-                kw["quality"] = True
-            out = eng.correlate(iq, pairs, lag_bounds=lb, band=bd, whiten=bool(whiten), **kw)
-        elif lb is None:
-            out = eng.correlate(iq, pairs)
-        else:
-            out = eng.correlate(iq, pairs, lag_bounds=lb)
-        if lead is not None:
-            out = tuple(a.reshape(lead + a.shape[1:]) for a in out)
-        return out
+            return unfold((li, lf, pk, dop, doppler_estimate(doppler_cps, dop, dfrac)))
+        if band is not None or whiten or integrate > 1 or refine > 0 or quality:
+            return unfold(eng.correlate(iq, pairs, lag_bounds=lb, band=bd, whiten=bool(whiten),
+                                        **_named(integrate=integrate, refine=refine, quality=bool(quality))))
+        return unfold(eng.correlate(iq, pairs, **_named(lag_bounds=lb)))
 
     def measure_band_lags(self, iq, bands, pairs=None, lag_bounds=None, whiten=False, refine=0, quality=False, integrate=1):
         """measure_lags(bands=...) with the fine lag search and the quality figures (rmx_xcorr_batch_bands_quality): iq
@@ -384,41 +352,42 @@ class TDoACalculator:
         integrate: K >= 1 consecutive windows per group, one lag per (group, band, pair) (rmx_xcorr_batch_bands_integrated):
         W must be a multiple of K -- with a channel axis, every channel's W --, the results and per-group lag_bounds are
         [W // K][.], the bands stay per window."""
-        from .xcorr import check_integrate, check_refine
+        from .xcorr import check_refine
         refine = check_refine(refine)
-        iq = np.asarray(iq)
-        lead = None
-        if iq.ndim == 4:
-            lead = iq.shape[:2]
-            iq = iq.reshape((lead[0] * lead[1],) + iq.shape[2:])
-        if iq.ndim != 3:
-            raise ValueError(f"iq must be [W][B][N] or [C][W][B][N], got shape {iq.shape}")
-        if lead is not None:   # (groups never straddle two channels)
-            integrate = check_integrate(integrate, lead[1])
-            lead = (lead[0], lead[1] // integrate)
-        else:
-            integrate = check_integrate(integrate, iq.shape[0])
-        n = iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2]
-        eng = self._engine(iq.shape[1], n, iq.shape[0])
-        lb = None
-        if lag_bounds is not None:
-            lb = np.asarray(lag_bounds)
-            if lead is not None and lb.ndim == 4:
-                lb = lb.reshape((lead[0] * lead[1],) + lb.shape[2:])
-        bs = np.asarray(bands)
-        if lead is not None and bs.ndim == 4:
-            bs = bs.reshape((-1,) + bs.shape[2:])
+        iq, integrate, fold, unfold = self._channels(iq, integrate)
+        eng = self._engine(iq.shape[1], iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2], iq.shape[0])
+        lb, bs = fold(lag_bounds, 4, True), fold(np.asarray(bands), 4)
         if bs.ndim != 3 or bs.shape[0] != iq.shape[0] or bs.shape[2] != 2:
             raise ValueError(f"bands must be [W][M][2] or [C][W][M][2] for {iq.shape[0]} windows, got shape {np.shape(bands)}")
-        kw = {"refine": refine} if refine > 0 else {}
-        if quality:
-            kw["quality"] = True
-        if integrate > 1:
-            kw["integrate"] = integrate
-        out = eng.correlate_bands(iq, bs, pairs, lag_bounds=lb, whiten=bool(whiten), **kw)
-        if lead is not None:
-            out = tuple(a.reshape(lead + a.shape[1:]) for a in out)
-        return out
+        return unfold(eng.correlate_bands(iq, bs, pairs, lag_bounds=lb, whiten=bool(whiten),
+                                          **_named(refine=refine, quality=bool(quality), integrate=integrate)))
+
+    @staticmethod
+    def _channels(iq, integrate):
+        """The channel axis of measure_lags and measure_band_lags as a batch axis: iq [W][B][N] or [C][W][B][N] ->
+        (iq [W][B][N] or [C W][B][N], K = integrate checked against one channel's W -- groups never straddle two channels --,
+        fold, unfold).  fold(value, ndim, exact=False): a per-row option with the channel axis in front (`ndim` dimensions)
+        -> [C W]... (exact: [C (W // K)]..., the rows of the results), anything else as an array, None as None.
+        unfold(out): every [C (W // K)]... array of a result -> [C][W // K]...; without a channel axis, out itself."""
+        from .xcorr import check_integrate
+        iq = np.asarray(iq)
+        chan = iq.shape[:2] if iq.ndim == 4 else None
+        if chan is not None:
+            iq = iq.reshape((chan[0] * chan[1],) + iq.shape[2:])
+        if iq.ndim != 3:
+            raise ValueError(f"iq must be [W][B][N] or [C][W][B][N], got shape {iq.shape}")
+        k = check_integrate(integrate, iq.shape[0] if chan is None else chan[1])
+        lead = None if chan is None else (chan[0], chan[1] // k)
+
+        def fold(value, ndim, exact=False):
+            if value is None:
+                return None
+            a = np.asarray(value)
+            return a.reshape((lead[0] * lead[1] if exact else -1,) + a.shape[2:]) if lead is not None and a.ndim == ndim else a
+
+        def unfold(out):
+            return out if lead is None else tuple(a.reshape(lead + a.shape[1:]) for a in out)
+        return iq, k, fold, unfold
 
     @staticmethod
     def _iq_of(det: SignalDetection):
@@ -569,25 +538,10 @@ class TDoACalculator:
         int [G][P][2] (bound_lags); band: None, or float [G][2] (band_limit); whiten applies to every group.
         with_quality: -> (lag [G][P], quality [G][P][4]) instead (min_psr / correlation_confidence), None all the same.
         doppler_search_hz (fs, the groups' sample rate, must be given): -> (lag [G][P], offset in hertz [G][P]) instead."""
-        kw = {}
-        if lag_bounds is not None:
-            kw["lag_bounds"] = lag_bounds
-        if self.integrate > 1:
-            # [G][B][N] -> [G K][B][N // K]: window g K + s is segment s of group g (the callers checked segment_length and
-            # derived lag_bounds and band for N // K); one lag per pair and group comes back, as without integration
-            k = self.integrate
-            g, b, nn = stacked.shape
-            stacked = np.ascontiguousarray(stacked.reshape(g, b, k, nn // k).transpose(0, 2, 1, 3)).reshape(g * k, b, nn // k)
-            if band is not None:
-                band = np.repeat(np.asarray(band), k, axis=0)
-            kw["integrate"] = k
-        if band is not None:
-            kw["band"] = band
-        if self.whiten:
-            kw["whiten"] = True
-        if self.refine > 0:
-            kw["refine"] = self.refine
-        try:
+        stacked, band, k = self._segments(stacked, band)
+        kw = _named(lag_bounds=lag_bounds, integrate=k, band=band, whiten=bool(self.whiten), refine=self.refine)
+
+        def measure():
             if self.doppler_search_hz is not None:
                 li, lf, _, _, dop = self.measure_lags(stacked, doppler_cps=self.doppler_grid(fs), **kw)
                 return li.astype(np.float64) + lf.astype(np.float64), np.asarray(dop, np.float64) * float(fs)
@@ -596,15 +550,7 @@ class TDoACalculator:
                 return li.astype(np.float64) + lf.astype(np.float64), np.asarray(qual)
             li, lf, _ = self.measure_lags(stacked, **kw)
             return li.astype(np.float64) + lf.astype(np.float64)
-        except (ImportError, OSError) as e:   # library not built / not loadable
-            self.logger.error(f"Cross-correlation engine failed: {e}")
-            return None
-        except Exception as e:
-            from . import xcorr
-            if not isinstance(e, xcorr.RmxError):    # programming errors (shapes, types) surface
-                raise
-            self.logger.error(f"Cross-correlation engine failed: {e}")   # no device, engine refused the batch
-            return None
+        return self._logged(measure)
 
     def _measure_shared(self, stacked: np.ndarray, lag_bounds, bands: np.ndarray, with_quality: bool = False):
         """share_captures: [G][B][N] captures, each under the M bands of bands [G][M][2] -> lag [G][M][P] float64, or None
@@ -612,14 +558,10 @@ class TDoACalculator:
         refine goes along, and with_quality -> (lag [G][M][P], quality [G][M][P][4]) instead.  share_integrated: under
         integrate = K > 1 every capture is cut into its K segments as _measure_groups cuts it and every band is repeated
         over its capture's segments (the callers checked segment_length and derived lag_bounds and bands for N // K)."""
-        more = {}
-        if self.integrate > 1:
-            k = self.integrate
-            g, b, nn = stacked.shape
-            stacked = np.ascontiguousarray(stacked.reshape(g, b, k, nn // k).transpose(0, 2, 1, 3)).reshape(g * k, b, nn // k)
-            bands = np.repeat(np.asarray(bands), k, axis=0)
-            more["integrate"] = k
-        try:
+        stacked, bands, k = self._segments(stacked, bands)
+        more = _named(integrate=k)
+
+        def measure():
             if with_quality:
                 li, lf, _, qual = self.measure_band_lags(stacked, bands, lag_bounds=lag_bounds, whiten=self.whiten,
                                                          refine=self.refine, quality=True, **more)
@@ -630,13 +572,27 @@ class TDoACalculator:
             else:
                 li, lf, _ = self.measure_lags(stacked, lag_bounds=lag_bounds, bands=bands, whiten=self.whiten)
             return li.astype(np.float64) + lf.astype(np.float64)
-        except (ImportError, OSError) as e:   # library not built / not loadable
-            self.logger.error(f"Cross-correlation engine failed: {e}")
-            return None
-        except Exception as e:
-            from . import xcorr
-            if not isinstance(e, xcorr.RmxError):    # programming errors (shapes, types) surface
-                raise
+        return self._logged(measure)
+
+    def _segments(self, stacked: np.ndarray, band):
+        """integrate = K > 1: [G][B][N] -> [G K][B][N // K], window g K + s segment s of group g, and the band(s) [G]... repeated
+        over each group's K segments (the callers checked segment_length and derived lag_bounds and band(s) for N // K; one
+        lag per pair and group comes back, as without integration) -> (stacked, band(s), K); K = 1: as they are."""
+        k = self.integrate
+        if k <= 1:
+            return stacked, band, 1
+        g, b, nn = stacked.shape
+        stacked = np.ascontiguousarray(stacked.reshape(g, b, k, nn // k).transpose(0, 2, 1, 3)).reshape(g * k, b, nn // k)
+        return stacked, None if band is None else np.repeat(np.asarray(band), k, axis=0), k
+
+    def _logged(self, measure):
+        """measure(), or None after logging when the library is not built or not loadable (ImportError, OSError) or the
+        engine refused the batch or found no device (RmxError): the reference's seam never raises (tdoa_processor.py:151-153).
+        Everything else -- programming errors: shapes, types -- surfaces."""
+        from .xcorr import RmxError
+        try:
+            return measure()
+        except (ImportError, OSError, RmxError) as e:
             self.logger.error(f"Cross-correlation engine failed: {e}")
             return None
 

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", LIB_NAME)
 RMX_IN_DEVICE = 1
 RMX_OUT_DEVICE = 2
 RMX_IN_U8 = 4
+_DEVICE = RMX_IN_DEVICE | RMX_OUT_DEVICE
 
 RMX_WEIGHT_NONE = 0
 RMX_WEIGHT_PHAT = 1
@@ -214,6 +215,110 @@ def check_refine(refine) -> int:
     if u not in REFINE_VALUES:
         raise ValueError(f"refine must be one of {REFINE_VALUES}, got {u}")
     return u
+
+
+OUTPUTS = ("dop_idx", "dop_frac", "lag_int", "lag_frac", "peak", "quality")   # in the order every method returns them
+
+
+class LagRequest(NamedTuple):
+    """One checked correlation or Doppler-search call: what lag_request() made of the options of correlate(),
+    correlate_bands(), caf() and their device-pointer twins.  It holds the normalised host arrays themselves, so whoever holds
+    the request keeps alive what the C entry reads; it is a tuple, so nothing changes it after the checks (MultiXcorrEngine
+    hands one to several worker threads, and cut() returns views)."""
+    family: str                    # "xcorr", "bands" or "caf"
+    n_windows: int
+    K: int                         # windows per group
+    U: int                         # fine lag grid, 0 for none
+    P: int
+    M: int                         # bands per window ("bands"), else 0
+    pairs: Optional[np.ndarray]    # int32 [P][2], None: every i < j
+    bounds: Optional[np.ndarray]   # int32 [P][2] or [rows][P][2]
+    bounds_per_row: bool
+    band: Optional[np.ndarray]     # float64 [2] or [W][2]; "bands": [M][2] or [W][M][2]
+    band_per_window: bool
+    grid: Optional[np.ndarray]     # float64 [D] ("caf")
+    whiten: bool
+    fine: bool                     # a dop_frac output ("caf")
+    quality: bool                  # a quality output
+
+    @property
+    def rows(self) -> int:
+        """the rows of every output: the windows, or the groups of K"""
+        return self.n_windows // self.K
+
+    def outputs(self, rows: Optional[int] = None):
+        """(name, dtype, shape) of every output of the call (or of `rows` of its rows), in the order the methods return them"""
+        shape = (self.rows if rows is None else rows,) + ((self.M,) if self.family == "bands" else ()) + (self.P,)
+        have = {"dop_idx": self.family == "caf", "dop_frac": self.fine, "quality": self.quality}
+        return [(n, np.int32 if n in ("dop_idx", "lag_int") else np.float32, shape + ((4,) if n == "quality" else ()))
+                for n in OUTPUTS if have.get(n, True)]
+
+    def cut(self, g0: int, g1: int):
+        """(lag_bounds, band(s)) of rows g0 .. g1 - 1: an array every row shares goes whole, per-row bounds are cut by row,
+        per-window band(s) by the rows' windows"""
+        return (self.bounds[g0:g1] if self.bounds_per_row else self.bounds,
+                self.band[g0 * self.K:g1 * self.K] if self.band_per_window else self.band)
+
+
+def lag_request(family: str, n_buoys: int, n_windows: int, pairs=None, lag_bounds=None, band=None, whiten=False, integrate=1,
+                refine=0, quality=False, doppler_cps=None, fine=False, n_pairs: Optional[int] = None) -> LagRequest:
+    """The one place where the options of a call are checked: ValueError before any call into the library, in the order
+    integrate, refine, pairs, then lag_bounds, band ("xcorr"), bands, lag_bounds ("bands": `band` is the band set) or grid,
+    lag_bounds, band ("caf", where integrate = None is 1 without a check).  n_pairs: the pair count of a caller that leaves the
+    pair list to somebody else's check (MultiXcorrEngine: its engines see the caller's own list)."""
+    K = 1 if integrate is None and family == "caf" else check_integrate(integrate, n_windows)
+    U = check_refine(refine)
+    if n_pairs is not None:
+        pairs, P = None, n_pairs
+    elif pairs is None:
+        P = n_buoys * (n_buoys - 1) // 2
+    else:
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        P = pairs.shape[0]
+    grid, M = None, 0
+    if family == "bands":
+        bd, band_pw = check_bands(band, n_windows)
+        M = bd.shape[-2]
+        lb, per_row = check_lag_bounds(lag_bounds, n_windows // K, P)
+    else:
+        if family == "caf":
+            grid = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
+        lb, per_row = check_lag_bounds(lag_bounds, n_windows // K, P)
+        bd, band_pw = check_band(band, n_windows)
+    return LagRequest._make((family, n_windows, K, U, P, M, pairs, lb, per_row, bd, band_pw, grid, bool(whiten), bool(fine),
+                             bool(quality)))
+
+
+# what each entry takes between (ctx, iq, n_windows, pairs, n_pairs[, grid, n_dopplers]) and (lag_int, lag_frac, peak, flags), in
+# this order: K integrate; W band(s)[, n_bands], per window, weighting; B lag bounds, per row; U refine; (dop_idx: every
+# caf entry); F dop_frac; (the three outputs); Q quality
+_ENTRY_ARGS = {"rmx_xcorr_batch": "", "rmx_xcorr_batch_bounded": "B", "rmx_xcorr_batch_weighted": "WB",
+               "rmx_xcorr_batch_integrated": "KWB", "rmx_xcorr_batch_refined": "KWBU", "rmx_xcorr_batch_quality": "KWBUQ",
+               "rmx_xcorr_batch_bands": "WB", "rmx_xcorr_batch_bands_quality": "WBUQ", "rmx_xcorr_batch_bands_integrated": "KWBUQ",
+               "rmx_caf_batch": "", "rmx_caf_batch_request": "WBF", "rmx_caf_batch_quality": "WBUFQ",
+               "rmx_caf_batch_integrated": "KWBUFQ"}
+
+
+def entry_name(req: LagRequest) -> str:
+    """The C entry a request goes through: the smallest one that takes what it asks for."""
+    if req.family == "xcorr":
+        if req.quality:
+            return "rmx_xcorr_batch_quality"
+        if req.U > 0:
+            return "rmx_xcorr_batch_refined"
+        if req.K > 1:
+            return "rmx_xcorr_batch_integrated"
+        if req.band is not None or req.whiten:
+            return "rmx_xcorr_batch_weighted"
+        return "rmx_xcorr_batch" if req.bounds is None else "rmx_xcorr_batch_bounded"
+    stem = "rmx_xcorr_batch_bands" if req.family == "bands" else "rmx_caf_batch"
+    if req.K > 1:
+        return stem + "_integrated"
+    if req.U > 0 or req.quality:
+        return stem + "_quality"
+    if req.family == "bands" or (req.band is None and not req.whiten and req.bounds is None and not req.fine):
+        return stem
+    return "rmx_caf_batch_request"
 
 
 def psr_threshold(n_lags: int, pfa: float, integrate: int = 1) -> float:
@@ -439,30 +544,58 @@ class XcorrEngine:
         return np.ascontiguousarray(iq), flags
 
     # -- the hot path ----------------------------------------------------------------------------
+    def _call(self, req: LagRequest, iq_p, out_p, flags: int):
+        """The one call into the library: the request through the entry entry_name() names.  iq_p and out_p, the pointers of
+        OUTPUTS with None for an output the call does not have, are host or device pointers, as `flags` says; the host
+        arrays are the request's own."""
+        name = entry_name(req)
+        args, vp = _ENTRY_ARGS[name], C.c_void_p
+        family, W, K, U, P, M, pairs, bounds, per_row, band, band_pw, grid, whiten, _, _ = req
+        dop_p, dop_frac_p, lag_int_p, lag_frac_p, peak_p, quality_p = out_p
+        a = [self._ctx, iq_p, W, None if pairs is None else pairs.ctypes.data_as(vp), P]
+        if family == "caf":
+            a += (grid.ctypes.data_as(vp), grid.shape[0])
+        if "K" in args:
+            a.append(K)
+        if "W" in args:
+            a.append(None if band is None else band.ctypes.data_as(vp))
+            if family == "bands":
+                a.append(M)
+            a += (int(band_pw), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE)
+        if "B" in args:
+            a += (None if bounds is None else bounds.ctypes.data_as(vp), int(per_row))
+        if "U" in args:
+            a.append(U)
+        if family == "caf":
+            a.append(dop_p)
+        if "F" in args:
+            a.append(dop_frac_p)
+        a += (lag_int_p, lag_frac_p, peak_p)
+        if "Q" in args:
+            a.append(quality_p)
+        self._check(getattr(self._lib, name)(*a, flags))
+
+    def _host_call(self, req: LagRequest, iq: np.ndarray, flags: int):
+        """the outputs of a host-array call as zeroed arrays, filled by _call unless the batch is empty (no call then)"""
+        out = {n: np.zeros(shape, dt) for n, dt, shape in req.outputs()}
+        if req.n_windows and req.P:
+            vp = C.c_void_p
+            self._call(req, iq.ctypes.data_as(vp), [out[n].ctypes.data_as(vp) if n in out else None for n in OUTPUTS], flags)
+        return tuple(out.values())
+
     def _xcorr(self, iq_p, W: int, pp, P: int, K: int, bd, band_pw: bool, whiten: bool, lb, per_window: bool,
                lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0, quality_p=None):
-        """One correlation call through the C entry its arguments name: the quality one for a quality pointer, else
-        the refined one for U > 0, else the integrated
-        one for K > 1, else the weighted
-        one for a band or whitening, else the plain one without lag bounds and the bounded one with them.  iq and the
-        outputs are pointers (host or device, as `flags` says); bd and lb are checked host arrays or None."""
-        lib, head, out = self._lib, (self._ctx, iq_p, W, pp, P), (lag_int_p, lag_frac_p, peak_p, flags)
-        bounds = (None if lb is None else lb.ctypes.data_as(C.c_void_p), int(per_window))
-        weight = (None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
-                  RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE)
-        if quality_p is not None:
-            rc = lib.rmx_xcorr_batch_quality(*head, K, *weight, *bounds, U, lag_int_p, lag_frac_p, peak_p, quality_p, flags)
-        elif U > 0:
-            rc = lib.rmx_xcorr_batch_refined(*head, K, *weight, *bounds, U, *out)
-        elif K > 1:
-            rc = lib.rmx_xcorr_batch_integrated(*head, K, *weight, *bounds, *out)
-        elif bd is not None or whiten:
-            rc = lib.rmx_xcorr_batch_weighted(*head, *weight, *bounds, *out)
-        elif lb is None:
-            rc = lib.rmx_xcorr_batch(*head, *out)
-        else:
-            rc = lib.rmx_xcorr_batch_bounded(*head, *bounds, *out)
-        self._check(rc)
+        """(for callers that hold checked parts and pointers of their own: one correlation call, as _call makes it)"""
+        pairs = None if pp is None else np.ctypeslib.as_array(C.cast(pp, C.POINTER(C.c_int32)), (P, 2))
+        self._call(LagRequest("xcorr", W, K, U, P, 0, pairs, lb, bool(per_window), bd, bool(band_pw), None, bool(whiten), False,
+                              quality_p is not None), iq_p, (None, None, lag_int_p, lag_frac_p, peak_p, quality_p), flags)
+
+    def _pairs_arg(self, pairs):
+        """(as _xcorr) pairs as the entries take it -> (kept int32 array or None, its pointer or None, P)"""
+        if pairs is None:
+            return None, None, self.n_buoys * (self.n_buoys - 1) // 2
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        return pairs, pairs.ctypes.data_as(C.c_void_p), pairs.shape[0]
 
     def correlate(self, iq: np.ndarray, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
                   whiten: bool = False, integrate: int = 1, refine: int = 0, quality: bool = False):
@@ -483,41 +616,8 @@ class XcorrEngine:
         by RMX_Q_* (rmx_xcorr_batch_quality; psr_threshold and lag_sigma read them); the first three arrays are bit for bit
         those of the same call without it."""
         iq, flags = self._check_iq(iq)
-        W = iq.shape[0]
-        K = check_integrate(integrate, W)
-        U = check_refine(refine)
-        pairs, pp, P = self._pairs_arg(pairs)
-        lb, per_window = check_lag_bounds(lag_bounds, W // K, P)
-        bd, band_pw = check_band(band, W)
-        lag_int = np.zeros((W // K, P), np.int32)
-        lag_frac = np.zeros((W // K, P), np.float32)
-        peak = np.zeros((W // K, P), np.float32)
-        qual = np.zeros((W // K, P, 4), np.float32) if quality else None
-        if W == 0 or P == 0:
-            return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
-        vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
-        self._xcorr(vp(iq), W, pp, P, K, bd, band_pw, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags, U,
-                    vp(qual) if quality else None)
-        return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
-
-    def _xcorr_bands(self, iq_p, W: int, pp, P: int, bd, bands_pw: bool, whiten: bool, lb, per_window: bool,
-                     lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0, quality_p=None, K: int = 1):
-        """One banded correlation call through the C entry its arguments name: rmx_xcorr_batch_bands_integrated for K > 1,
-        else rmx_xcorr_batch_bands_quality for U > 0 or
-        a quality pointer, else rmx_xcorr_batch_bands.  iq and the outputs are pointers (host or device, as `flags` says);
-        bd is the checked host array [M][2] or [W][M][2], lb a checked host array or None."""
-        band_args = (bd.ctypes.data_as(C.c_void_p), bd.shape[-2], int(bands_pw),
-                     RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
-                     int(per_window))
-        head = (self._ctx, iq_p, W, pp, P) + band_args
-        if K > 1:
-            rc = self._lib.rmx_xcorr_batch_bands_integrated(self._ctx, iq_p, W, pp, P, K, *band_args, U, lag_int_p, lag_frac_p,
-                                                            peak_p, quality_p, flags)
-        elif U or quality_p is not None:
-            rc = self._lib.rmx_xcorr_batch_bands_quality(*head, U, lag_int_p, lag_frac_p, peak_p, quality_p, flags)
-        else:
-            rc = self._lib.rmx_xcorr_batch_bands(*head, lag_int_p, lag_frac_p, peak_p, flags)
-        self._check(rc)
+        return self._host_call(lag_request("xcorr", self.n_buoys, iq.shape[0], pairs, lag_bounds, band, whiten, integrate, refine,
+                                           quality), iq, flags)
 
     def correlate_bands(self, iq: np.ndarray, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
                         whiten: bool = False, refine: int = 0, quality: bool = False, integrate: int = 1):
@@ -534,22 +634,8 @@ class XcorrEngine:
         of K; the results are [W // K][M][P] ([...][4]), lag_bounds [P][2] or [W // K][P][2]; bands stay [M][2] or
         [W][M][2], and [:, m] is what correlate(iq, band=bands[..., m, :], integrate=K, ...) returns."""
         iq, flags = self._check_iq(iq)
-        W = iq.shape[0]
-        K = check_integrate(integrate, W)
-        U = check_refine(refine)
-        pairs, pp, P = self._pairs_arg(pairs)
-        bd, per_window_b = check_bands(bands, W)
-        M = bd.shape[-2]
-        lb, per_window = check_lag_bounds(lag_bounds, W // K, P)
-        lag_int = np.zeros((W // K, M, P), np.int32)
-        lag_frac = np.zeros((W // K, M, P), np.float32)
-        peak = np.zeros((W // K, M, P), np.float32)
-        qual = np.zeros((W // K, M, P, 4), np.float32) if quality else None
-        if W and P:
-            vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
-            self._xcorr_bands(vp(iq), W, pp, P, bd, per_window_b, whiten, lb, per_window, vp(lag_int), vp(lag_frac), vp(peak), flags,
-                              U, vp(qual) if quality else None, K)
-        return (lag_int, lag_frac, peak, qual) if quality else (lag_int, lag_frac, peak)
+        return self._host_call(lag_request("bands", self.n_buoys, iq.shape[0], pairs, lag_bounds, bands, whiten, integrate, refine,
+                                           quality), iq, flags)
 
     def correlate_bands_device(self, iq_ptr: int, n_windows: int, bands, lag_int_ptr: int, lag_frac_ptr: int, peak_ptr: int,
                                pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None, whiten: bool = False,
@@ -558,47 +644,11 @@ class XcorrEngine:
         library keeps its own copies); asynchronous on the ctx stream.  The outputs are [n_windows // K][M][P]; quality_ptr,
         if given, [n_windows // K][M][P][4] float32 on the device (rmx_xcorr_batch_bands_quality; with integrate = K > 1
         rmx_xcorr_batch_bands_integrated)."""
-        K = check_integrate(integrate, n_windows)
-        U = check_refine(refine)
-        pairs, pp, P = self._pairs_arg(pairs)
-        bd, per_window_b = check_bands(bands, n_windows)
-        lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
-        flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
-        self._xcorr_bands(C.c_void_p(iq_ptr), n_windows, pp, P, bd, per_window_b, whiten, lb, per_window, C.c_void_p(lag_int_ptr),
-                          C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags, U,
-                          None if quality_ptr is None else C.c_void_p(quality_ptr), K)
-
-    def _pairs_arg(self, pairs):
-        """pairs as the entries take it -> (kept int32 array or None, its pointer or None, P)"""
-        if pairs is None:
-            return None, None, self.n_buoys * (self.n_buoys - 1) // 2
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        return pairs, pairs.ctypes.data_as(C.c_void_p), pairs.shape[0]
-
-    def _caf(self, iq_p, W: int, pp, P: int, dc, bd, band_pw: bool, whiten: bool, lb, per_window: bool, dop_p, dop_frac_p,
-             lag_int_p, lag_frac_p, peak_p, flags: int, U: int = 0, quality_p=None, K: int = 1):
-        """One Doppler search through the C entry its arguments name: rmx_caf_batch when nothing is requested,
-        rmx_caf_batch_integrated for K > 1 windows per group, rmx_caf_batch_quality for U > 0 or a quality pointer, else
-        rmx_caf_batch_request.  dop_frac_p: a pointer, or None (not computed)."""
-        grid = (dc.ctypes.data_as(C.c_void_p), dc.shape[0])
-        if K > 1:
-            rc = self._lib.rmx_caf_batch_integrated(
-                self._ctx, iq_p, W, pp, P, *grid, K, None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
-                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
-                int(per_window), U, dop_p, dop_frac_p, lag_int_p, lag_frac_p, peak_p, quality_p, flags)
-        elif U or quality_p is not None:
-            rc = self._lib.rmx_caf_batch_quality(
-                self._ctx, iq_p, W, pp, P, *grid, None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
-                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
-                int(per_window), U, dop_p, dop_frac_p, lag_int_p, lag_frac_p, peak_p, quality_p, flags)
-        elif bd is None and not whiten and lb is None and dop_frac_p is None:
-            rc = self._lib.rmx_caf_batch(self._ctx, iq_p, W, pp, P, *grid, dop_p, lag_int_p, lag_frac_p, peak_p, flags)
-        else:
-            rc = self._lib.rmx_caf_batch_request(
-                self._ctx, iq_p, W, pp, P, *grid, None if bd is None else bd.ctypes.data_as(C.c_void_p), int(band_pw),
-                RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE, None if lb is None else lb.ctypes.data_as(C.c_void_p),
-                int(per_window), dop_p, dop_frac_p, lag_int_p, lag_frac_p, peak_p, flags)
-        self._check(rc)
+        req = lag_request("bands", self.n_buoys, n_windows, pairs, lag_bounds, bands, whiten, integrate, refine,
+                          quality_ptr is not None)
+        vp = C.c_void_p
+        self._call(req, vp(iq_ptr), (None, None, vp(lag_int_ptr), vp(lag_frac_ptr), vp(peak_ptr),
+                                     None if quality_ptr is None else vp(quality_ptr)), _DEVICE | (RMX_IN_U8 if u8 else 0))
 
     def caf(self, iq: np.ndarray, doppler_cps, pairs: Optional[np.ndarray] = None, lag_bounds=None, band=None,
             whiten: bool = False, fine: bool = False, refine: int = 0, quality: bool = False, integrate=None):
@@ -615,26 +665,8 @@ class XcorrEngine:
         windows of a group before ONE peak search; every output is then [W // K][P] (quality [W // K][P][4]), lag_bounds
         [P][2] or [W // K][P][2] per group, the band stays per window.  None (or 1): the search per window."""
         iq, flags = self._check_iq(iq)
-        W = iq.shape[0]
-        K = 1 if integrate is None else check_integrate(integrate, W)   # (the search without it pays for no check)
-        G = W // K
-        U = check_refine(refine)
-        pairs, pp, P = self._pairs_arg(pairs)
-        dc = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
-        lb, per_window = check_lag_bounds(lag_bounds, G, P)
-        bd, band_pw = check_band(band, W)
-        dop = np.zeros((G, P), np.int32)
-        dfrac = np.zeros((G, P), np.float32) if fine else None
-        lag_int = np.zeros((G, P), np.int32)
-        lag_frac = np.zeros((G, P), np.float32)
-        peak = np.zeros((G, P), np.float32)
-        qual = np.zeros((G, P, 4), np.float32) if quality else None
-        if W and P:
-            vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
-            self._caf(vp(iq), W, pp, P, dc, bd, band_pw, bool(whiten), lb, per_window, vp(dop), vp(dfrac) if fine else None,
-                      vp(lag_int), vp(lag_frac), vp(peak), flags, U, vp(qual) if quality else None, K)
-        out = (dop, dfrac, lag_int, lag_frac, peak) if fine else (dop, lag_int, lag_frac, peak)
-        return out + (qual,) if quality else out
+        return self._host_call(lag_request("caf", self.n_buoys, iq.shape[0], pairs, lag_bounds, band, whiten, integrate, refine,
+                                           quality, doppler_cps, fine), iq, flags)
 
     def solve(self, buoy_xyz, lag_int, lag_frac, sample_rate_hz: float, weight=None,
               pairs: Optional[np.ndarray] = None, max_iter: int = 60):
@@ -735,22 +767,19 @@ class XcorrEngine:
         refine: as for caf(); quality_ptr: 0, or a device buffer of [n_windows][P][4] float32 for the quality figures.
         integrate: as for caf() (rmx_caf_batch_integrated): every output buffer is then [n_windows // K][P] (quality
         [n_windows // K][P][4]) and per-group lag_bounds are [n_windows // K][P][2]."""
-        U = check_refine(refine) if refine else 0   # (the search without it pays for no check)
-        K = 1 if integrate is None else check_integrate(integrate, n_windows)
-        pairs, pp, P = self._pairs_arg(pairs)
-        dc = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
-        flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
-        if lag_bounds is None and band is None and not whiten and not dop_frac_ptr and not U and not quality_ptr and K == 1:   # the plain call, as ever
-            self._check(self._lib.rmx_caf_batch(self._ctx, C.c_void_p(iq_ptr), n_windows, pp, P,
-                                                dc.ctypes.data_as(C.c_void_p), dc.shape[0], C.c_void_p(dop_ptr),
-                                                C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr),
-                                                flags))
+        U = check_refine(refine) if refine else 0   # (in front of integrate here; the search without it pays for no check)
+        vp, flags = C.c_void_p, _DEVICE | (RMX_IN_U8 if u8 else 0)
+        if integrate is None and not U and lag_bounds is None and band is None and not whiten and not dop_frac_ptr \
+                and not quality_ptr:   # the plain call, as ever, pays for no request: bench.py times it on a 13 us kernel
+            pairs, pp, P = self._pairs_arg(pairs)
+            dc = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
+            self._check(self._lib.rmx_caf_batch(self._ctx, vp(iq_ptr), n_windows, pp, P, dc.ctypes.data_as(vp), dc.shape[0],
+                                                vp(dop_ptr), vp(lag_int_ptr), vp(lag_frac_ptr), vp(peak_ptr), flags))
             return
-        lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
-        bd, band_pw = check_band(band, n_windows)
-        self._caf(C.c_void_p(iq_ptr), n_windows, pp, P, dc, bd, band_pw, bool(whiten), lb, per_window, C.c_void_p(dop_ptr),
-                  C.c_void_p(dop_frac_ptr) if dop_frac_ptr else None, C.c_void_p(lag_int_ptr), C.c_void_p(lag_frac_ptr),
-                  C.c_void_p(peak_ptr), flags, U, C.c_void_p(quality_ptr) if quality_ptr else None, K)
+        req = lag_request("caf", self.n_buoys, n_windows, pairs, lag_bounds, band, whiten, integrate, U, bool(quality_ptr),
+                          doppler_cps, bool(dop_frac_ptr))
+        self._call(req, vp(iq_ptr), (vp(dop_ptr), vp(dop_frac_ptr) if dop_frac_ptr else None, vp(lag_int_ptr), vp(lag_frac_ptr),
+                                     vp(peak_ptr), vp(quality_ptr) if quality_ptr else None), flags)
 
     def correlate_device(self, iq_ptr: int, n_windows: int, lag_int_ptr: int, lag_frac_ptr: int,
                          peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
@@ -759,11 +788,13 @@ class XcorrEngine:
         stream.  lag_bounds, band, whiten, integrate, refine: as for correlate() (host arrays; the library keeps its own
         copies; with integrate = K the three outputs are [n_windows // K][P]).  quality_ptr: 0, or a device buffer of
         [n_windows // K][P][4] float32 for the quality figures (rmx_xcorr_batch_quality)."""
-        K = check_integrate(integrate, n_windows)
-        U = check_refine(refine)
-        pairs, pp, P = self._pairs_arg(pairs)
-        flags = RMX_IN_DEVICE | RMX_OUT_DEVICE | (RMX_IN_U8 if u8 else 0)
-        lb, per_window = check_lag_bounds(lag_bounds, n_windows // K, P)
-        bd, band_pw = check_band(band, n_windows)
-        self._xcorr(C.c_void_p(iq_ptr), n_windows, pp, P, K, bd, band_pw, whiten, lb, per_window, C.c_void_p(lag_int_ptr),
-                    C.c_void_p(lag_frac_ptr), C.c_void_p(peak_ptr), flags, U, C.c_void_p(quality_ptr) if quality_ptr else None)
+        vp, flags = C.c_void_p, _DEVICE | (RMX_IN_U8 if u8 else 0)
+        if pairs is None and lag_bounds is None and band is None and not whiten and not quality_ptr \
+                and integrate.__class__ is int and integrate == 1 and refine.__class__ is int and refine == 0:
+            # the plain call pays for no request either (an int 1 and an int 0 pass their checks for any batch)
+            self._check(self._lib.rmx_xcorr_batch(self._ctx, vp(iq_ptr), n_windows, None, self.n_buoys * (self.n_buoys - 1) // 2,
+                                                  vp(lag_int_ptr), vp(lag_frac_ptr), vp(peak_ptr), flags))
+            return
+        req = lag_request("xcorr", self.n_buoys, n_windows, pairs, lag_bounds, band, whiten, integrate, refine, bool(quality_ptr))
+        self._call(req, vp(iq_ptr), (None, None, vp(lag_int_ptr), vp(lag_frac_ptr), vp(peak_ptr),
+                                     vp(quality_ptr) if quality_ptr else None), flags)
