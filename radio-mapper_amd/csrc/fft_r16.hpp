@@ -365,7 +365,8 @@ __device__ __forceinline__ void xchg_bc_read_b(const float2* lds, float2 (&v)[16
 // of bits 4 and 5, which is why ONE lane map per role serves both directions.
 // The barrier image becomes [k0][n1][p][n0] (complex): role B reads / writes 16 consecutive complex per 16-lane
 // group and (n0, p) = 32 consecutive per half wave; role A reads conflict free (its lane pairs sit 128 bytes
-// apart); only role A's stores of the FORWARD transform are 2-way conflicted (8 of 36 transforms).
+// apart); only role A's stores of the FORWARD transform would be 2-way conflicted in it (8 of 36 transforms), which is
+// why k_win's fwd exchanges through an image of its own (xa2f_base below).
 constexpr int kLocRow = 272;                   // bytes between rows of the wave-local planar image
 constexpr int kLocPlane = 16 * kLocRow;        // re plane, then im plane
 constexpr int kLocWave = 2 * kLocPlane;        // 8704 bytes per wave = the wave's two k0 rows of the barrier image
@@ -431,6 +432,48 @@ __device__ __forceinline__ void xchg_b2_read(const float2* lds, float2 (&v)[16],
     const float2* b = lds + xb2_base(t);
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) v[n1] = b[n1 * 32];
+}
+// FORWARD-ONLY barrier image [k0][n1][n0 >> 3][p][n0 & 7] (k_win's fwd): the forward transform writes its image in role A
+// and reads it in role B between its own barrier, so the inverse transforms never see its layout.  Here each 16-lane
+// group of role A's ds_write_b64 (eight n0, both p) covers 16 consecutive complex = all 32 store banks, and each half wave
+// of role B's ds_read_b64 the 32 consecutive complex of one (k0, n1) = all 64 banks: no conflict on either side
+// (tools/model_kwin_lds.py), where [k0][n1][p][n0] costs role A's stores 2 ways.  Same k0 rows, so role B's wave still
+// reads nothing but its own region.  Bases as xa2_base / xb2_base: slot k0 adds k0 * kBcHalf, slot n1 adds 32 * n1.
+__device__ __forceinline__ int xa2f_base(int t) { const int p = t & 1, u = t >> 1; return 32 * (u >> 4) + 16 * ((u >> 3) & 1) + 8 * p + (u & 7); }
+__device__ __forceinline__ int xb2f_base(int t) { return (t >> 5) * kBcHalf + 16 * ((t >> 3) & 1) + 8 * ((t >> 4) & 1) + (t & 7); }
+__device__ __forceinline__ void xchg_a2f_write(float2* lds, const float2 (&v)[16], int t) {
+    float2* b = lds + xa2f_base(t);
+#pragma unroll
+    for (int k0 = 0; k0 < 16; ++k0) b[k0 * kBcHalf] = make_float2(v[k0].x, v[k0].y);
+}
+// Role B's sixteen slots of that image as sixteen ds_read_b64 in ONE asm statement (lds_byte = the image's byte address in
+// LDS + 8 * xb2f_base(t); the kernel's dynamic LDS starts at address 0, as loc_write4's M0 assumes).  Written in C++, the
+// compiler pairs these reads, 256 bytes apart, into eight ds_read2_b64, which cost 8 LDS-array cycles each against 2 x 2
+// and bank by 32 (2 ways on this image); a volatile pointer keeps them apart but spills.  Issue order = layer-1 consumption
+// order.  The statement waits for its own reads: the compiler does not count LDS instructions it cannot see, so nothing may
+// leave the statement in flight.  (The values come back as register PAIRS, which lets the compiler form v_pk_add_f32 from
+// the plain butterflies of the pass behind the reads: the same sums, bit for bit.)
+__device__ __forceinline__ void xchg_b2f_read(int lds_byte, float2 (&v)[16]) {
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    f2v r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15;
+    asm volatile(
+        "ds_read_b64 %0, %16\n\tds_read_b64 %4, %16 offset:1024\n\t"
+        "ds_read_b64 %8, %16 offset:2048\n\tds_read_b64 %12, %16 offset:3072\n\t"
+        "ds_read_b64 %1, %16 offset:256\n\tds_read_b64 %5, %16 offset:1280\n\t"
+        "ds_read_b64 %9, %16 offset:2304\n\tds_read_b64 %13, %16 offset:3328\n\t"
+        "ds_read_b64 %2, %16 offset:512\n\tds_read_b64 %6, %16 offset:1536\n\t"
+        "ds_read_b64 %10, %16 offset:2560\n\tds_read_b64 %14, %16 offset:3584\n\t"
+        "ds_read_b64 %3, %16 offset:768\n\tds_read_b64 %7, %16 offset:1792\n\t"
+        "ds_read_b64 %11, %16 offset:2816\n\tds_read_b64 %15, %16 offset:3840\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7), "=&v"(r8), "=&v"(r9),
+          "=&v"(r10), "=&v"(r11), "=&v"(r12), "=&v"(r13), "=&v"(r14), "=&v"(r15)
+        : "v"(lds_byte)
+        : "memory");
+#define RMX_XB2F(q) v[q] = make_float2(r##q.x, r##q.y);
+    RMX_XB2F(0) RMX_XB2F(1) RMX_XB2F(2) RMX_XB2F(3) RMX_XB2F(4) RMX_XB2F(5) RMX_XB2F(6) RMX_XB2F(7)
+    RMX_XB2F(8) RMX_XB2F(9) RMX_XB2F(10) RMX_XB2F(11) RMX_XB2F(12) RMX_XB2F(13) RMX_XB2F(14) RMX_XB2F(15)
+#undef RMX_XB2F
 }
 
 // TW2[a][b] = W_256^(a*b) lives in LDS as 16 rows of 16 complex padded to 18 (144-B rows: the 16

@@ -40,6 +40,18 @@ def xb2(t, n1):                       # complex index of role B's slot n1
     return k0 * K_BC_HALF + 32 * n1 + 16 * p + n0
 
 
+# forward-only barrier image [k0][n1][n0 >> 3][p][n0 & 7] (fwd writes it in role A and reads it in role B between its own
+# barrier; the inverse transforms never see it)
+def xa2f(t, k0):
+    n1, n0, p = role_a(t)
+    return k0 * K_BC_HALF + 32 * n1 + 16 * (n0 >> 3) + 8 * p + (n0 & 7)
+
+
+def xb2f(t, n1):
+    k0, n0, p = role_b(t)
+    return k0 * K_BC_HALF + 32 * n1 + 16 * (n0 >> 3) + 8 * p + (n0 & 7)
+
+
 def loc_write_addr(t, slot, plane):   # byte address (addtid: M0 = wave region, offset = row, + 4 * lane)
     lane, wave = t & 63, t >> 6
     return wave * LOC_WAVE + plane * LOC_PLANE + loc_pos(slot) * LOC_ROW + 4 * lane
@@ -144,6 +156,37 @@ def check_banks():
     assert res["A write (b64, forward only)"] == 2
 
 
+def check_forward_image():
+    """the forward-only image: role A's sixteen stores reach role B's sixteen reads of the same k0 row, inside the row's own
+    region (role B's wave overwrites that region with its wave-local image right behind the reads), and both sides are
+    conflict free under the same lane-group rules as check_banks.  Returns {side: worst ways}."""
+    T = range(512)
+    img = {}
+    for t in T:
+        n1, n0, p = role_a(t)
+        for k0 in range(16):
+            a = xa2f(t, k0)
+            assert a not in img and k0 * K_BC_HALF <= a < (k0 + 1) * K_BC_HALF
+            img[a] = (n1, n0, p, k0)
+    for t in T:
+        k0, n0, p = role_b(t)
+        lo, hi = (t >> 6) * LOC_WAVE, ((t >> 6) + 1) * LOC_WAVE
+        for n1 in range(16):
+            assert img[xb2f(t, n1)] == (n1, n0, p, k0), ("A->B forward", t, n1)
+            assert lo <= 8 * xb2f(t, n1) < hi
+    res = {"A write (b64, forward image)": 0, "B read  (b64, forward image)": 0}
+    rd_groups = [list(range(0, 32)), list(range(32, 64))]
+    wr_groups = [list(range(16 * g, 16 * g + 16)) for g in range(4)]
+    for wave in range(8):
+        lanes = [wave * 64 + l for l in range(64)]
+        for s in range(16):
+            res["A write (b64, forward image)"] = max(res["A write (b64, forward image)"],
+                                                      worst([8 * xa2f(t, s) for t in lanes], wr_groups, 8, 32))
+            res["B read  (b64, forward image)"] = max(res["B read  (b64, forward image)"],
+                                                      worst([8 * xb2f(t, s) for t in lanes], rd_groups, 8, 64))
+    return res
+
+
 def brute_force_local():
     """the search behind the local layout: row pad in bank quads, S / S^c row interleave, reader group permutation"""
     best = []
@@ -171,5 +214,8 @@ def brute_force_local():
 if __name__ == "__main__":
     check_dataflow()
     check_banks()
+    for k, v in check_forward_image().items():
+        print("%-30s %d-way%s" % (k, v, "" if v == 1 else "   <-- conflict"))
+        assert v == 1
     brute_force_local()
     print("model ok")

@@ -24,6 +24,9 @@
 #if !defined(KWB_NO_P1)
 #include "kwin_p1.hpp"
 #endif
+#if !defined(KWB_NO_FX)
+#include "kwin_fx.hpp"
+#endif
 
 using namespace rmx;
 
@@ -116,6 +119,38 @@ KWB_P1(launch_p1_7, 7)
     {"p1 7: 1 + 2 + 4", launch_p1_7, (const void*)k_win_p1<false, 7>, kLdsWinBytes},
 #endif
 
+#if !defined(KWB_NO_FX)
+// the forward transform's barrier exchange (kwin_fx.hpp, LABNOTES R17): FX bits 1 sixteen plain ds_read_b64 in fwd, 2 the
+// forward-only image without the store conflict, 4 sixteen plain ds_write_b64 for role B's stores in h1, 8 / 16 / 32 see
+// kwin_fx.hpp.  (k_win itself is what shipped, FX = 3; `fx 0` is the body before R17.)
+#define KWB_FX(NAME, BITS)                                                                                                  \
+    static void NAME(const Bufs& b, hipStream_t s) {                                                                         \
+        hipLaunchKernelGGL((k_win_fx<false, BITS>), dim3(256), dim3(kThreads), kLdsWinBytes, s, (const void*)b.iq, b.spec,   \
+                           b.tw1, b.tw2, b.B, 0L, b.out_scale, b.li, b.lf, b.pk, b.W, (const int4*)b.trail, 0);              \
+    }
+KWB_FX(launch_fx_0, 0)
+KWB_FX(launch_fx_1, 1)
+KWB_FX(launch_fx_2, 2)
+KWB_FX(launch_fx_3, 3)
+KWB_FX(launch_fx_4, 4)
+KWB_FX(launch_fx_7, 7)
+KWB_FX(launch_fx_9, 9)
+KWB_FX(launch_fx_11, 11)
+KWB_FX(launch_fx_19, 19)
+KWB_FX(launch_fx_35, 35)
+#define KWB_FX_TABLE \
+    {"fx 0: the body before R17, stag 0", launch_fx_0, (const void*)k_win_fx<false, 0>, kLdsWinBytes}, \
+    {"fx 1: A, plain reads in fwd", launch_fx_1, (const void*)k_win_fx<false, 1>, kLdsWinBytes}, \
+    {"fx 2: B, forward-only image", launch_fx_2, (const void*)k_win_fx<false, 2>, kLdsWinBytes}, \
+    {"fx 3: A + B", launch_fx_3, (const void*)k_win_fx<false, 3>, kLdsWinBytes}, \
+    {"fx 4: plain role-B stores in h1", launch_fx_4, (const void*)k_win_fx<false, 4>, kLdsWinBytes}, \
+    {"fx 7: A + B + plain stores", launch_fx_7, (const void*)k_win_fx<false, 7>, kLdsWinBytes}, \
+    {"fx 9: A, values as opaque scalars", launch_fx_9, (const void*)k_win_fx<false, 9>, kLdsWinBytes}, \
+    {"fx 11: A + B, values as opaque scalars", launch_fx_11, (const void*)k_win_fx<false, 11>, kLdsWinBytes}, \
+    {"fx 19: A + B, bases computed per transform", launch_fx_19, (const void*)k_win_fx<false, 19>, kLdsWinBytes}, \
+    {"fx 35: A + B, bases from the inverse's per transform", launch_fx_35, (const void*)k_win_fx<false, 35>, kLdsWinBytes},
+#endif
+
 struct Variant { const char* name; launch_fn fn; const void* kfn; int lds; };
 
 int main(int argc, char** argv) {
@@ -157,6 +192,9 @@ int main(int argc, char** argv) {
 #endif
 #ifdef KWB_P1_TABLE
         KWB_P1_TABLE
+#endif
+#ifdef KWB_FX_TABLE
+        KWB_FX_TABLE
 #endif
     };
     const int rounds = argc > 7 ? atoi(argv[7]) : 2;   // argv[7]: interleaved runs of every variant

@@ -1,7 +1,5 @@
-// kwin_body.hpp -- the body of the fused N = 4096 kernel, included by kwin.hpp into k_win (BOUNDED = false: the unbounded
-// kernel, the same source as before) and into k_win_lb (BOUNDED = true: the caller's lag window per pair, lag_bounds.hpp).
-// Not a header of its own: it expects the kernel's parameters, BOUNDED and lb in scope.
-// A textual include, not a <U8, BOUNDED> device function: that form compiled all four kernels to other instruction bodies.
+// kwin_fx_body.hpp -- PROBE copy of radio-mapper_amd/csrc/kwin_body.hpp as it stood before LABNOTES R17, included by
+// kwin_fx.hpp into k_win_fx; the levers of the forward exchange hang on the bits of FX (see there).
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* img0 = reinterpret_cast<float2*>(smem);
     float2* img1 = reinterpret_cast<float2*>(smem + kLdsWinImg);
@@ -57,6 +55,7 @@
     int npend = 0;       // pairs whose records await a resolve
 
     auto barrier_hook = [&](bool flush) __attribute__((always_inline)) {
+        if constexpr (FX & 4) __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the asm stores are not counted by the compiler
         __syncthreads();
         if (npend == kResBatch || (flush && npend > 0)) {
             if (wave == (seq & kResWaveMask)) {
@@ -193,12 +192,33 @@
         mul_w32_odd(x);            // odd sub-transform input x*W32^q (W_L^u is folded into tw1)
         dft16(x);
         mul_tw1(x, tw1);
-        // the forward-only image: role A's stores without the 2-way conflict, role B's reads as sixteen plain ds_read_b64
-        // (fft_r16.hpp; LDS array time is not hidden in this kernel, and every wave waits for exactly these reads behind
-        // the transform's only barrier)
-        xchg_a2f_write(img, x, t);
+        if constexpr (FX & 2) {
+            int tf = t;   // FX & 16: the base is computed here, at every transform, not held in a register across the launch
+            if constexpr (FX & (16 | 32)) asm volatile("" : "+v"(tf));
+            // FX & 32: the same index from the inverse's base, which is live anyway: bits 3 and 4 of the index change places
+            float2* b = img + ((FX & 32) ? xa2_base(t) + 8 * (((tf >> 4) & 1) - (tf & 1)) : xa2f_base(tf));
+#pragma unroll
+            for (int k0 = 0; k0 < 16; ++k0) b[k0 * kBcHalf] = make_float2(x[k0].x, x[k0].y);
+        } else {
+            xchg_a2_write(img, x, t);
+        }
         barrier_hook(false);
-        xchg_b2f_read((seq & 1) * kLdsWinImg + 8 * xb2f_base(t), x);
+        int tg = t;
+        if constexpr (FX & (16 | 32)) asm volatile("" : "+v"(tg));
+        const int xbf = (FX & 32) ? xb2_base(t) + 8 * (((tg >> 3) & 1) - ((tg >> 4) & 1)) : xb2f_base(tg);
+        if constexpr (FX & 1) {
+            xchg_b2_read_plain((seq & 1) * kLdsWinImg + 8 * ((FX & 2) ? xbf : xb2_base(t)), x);
+            if constexpr (FX & 8) {   // opaque scalars: the pairs the reads land in otherwise draw v_pk_add_f32 into layer 1
+#pragma unroll
+                for (int q = 0; q < 16; ++q) asm volatile("" : "+v"(x[q].x), "+v"(x[q].y));
+            }
+        } else if constexpr (FX & 2) {
+            const float2* b = img + xbf;
+#pragma unroll
+            for (int n1 = 0; n1 < 16; ++n1) x[n1] = b[n1 * 32];
+        } else {
+            xchg_b2_read(img, x, t);
+        }
         dft16(x);
         loc_write16(loc_m0[seq & 1], x);
         wave_lds_order();
@@ -247,10 +267,14 @@
             dft16_layer2_emit(v, [&](auto kac, const float2& x0, const float2& x1, const float2& x2, const float2& x3)
                                      __attribute__((always_inline)) {
                 constexpr int ka = decltype(kac)::value;
-                xb[ka * 32] = make_float2(x0.x, x0.y);
-                xb[(ka + 4) * 32] = make_float2(x1.x, x1.y);
-                xb[(ka + 8) * 32] = make_float2(x2.x, x2.y);
-                xb[(ka + 12) * 32] = make_float2(x3.x, x3.y);
+                if constexpr (FX & 4) {
+                    xchg_b2_write4_plain<ka>((tr & 1) * kLdsWinImg + 8 * xb2_base(t), x0, x1, x2, x3);
+                } else {
+                    xb[ka * 32] = make_float2(x0.x, x0.y);
+                    xb[(ka + 4) * 32] = make_float2(x1.x, x1.y);
+                    xb[(ka + 8) * 32] = make_float2(x2.x, x2.y);
+                    xb[(ka + 12) * 32] = make_float2(x3.x, x3.y);
+                }
                 prefetch(std::integral_constant<int, ka + 4>{});
             });
         }
