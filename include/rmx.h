@@ -614,13 +614,59 @@ int rmx_caf_batch_quality(rmx_ctx* ctx, const void* iq, int n_windows, const int
  *   extent G * n_pairs slots; then the route: a chunk holds whole groups, and a K that no chunk of the ctx holds (option
  *   "chunk_windows" at N = 4096, the scratch budget elsewhere) is refused with a text that says so, never a silent
  *   split.  RMX_E_UNSUPPORTED for the column tile of rmx_xcorr_batch_integrated.
- * Several bands under the search (rmx_xcorr_batch_bands) are not offered. */
+ * Several bands under the search: rmx_caf_batch_bands, which has no integration. */
 int rmx_caf_batch_integrated(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
                              const double* doppler_cps, int n_dopplers, int integrate,
                              const double* band_cps, int band_per_window, unsigned weighting,
                              const int32_t* lag_bounds, int bounds_per_group, int refine,
                              int32_t* dop_idx, float* dop_frac,
                              int32_t* lag_int, float* lag_frac, float* peak, float* quality, unsigned flags);
+
+/* The Doppler search under several bands per window over ONE set of forward passes: rmx_caf_batch_request for a capture
+ * that holds several emitters, each in its own band, heard by receivers with free-running oscillators.  The forward
+ * transforms do not depend on the band: (1 + n_dopplers) * n_buoys of them per window serve all n_bands bands, where
+ * n_bands calls of rmx_caf_batch_request run n_bands times as many, and the windows are uploaded once.
+ *   band_cps, n_bands (1 .. 64), bands_per_window   exactly as in rmx_xcorr_batch_bands ([n_windows][n_bands][2] or
+ *               [n_bands][2]; never NULL); the bands of a window are shared by all its hypotheses.
+ *   doppler_cps, n_dopplers, weighting, lag_bounds, bounds_per_window, dop_frac (or NULL), flags
+ *               exactly as in rmx_caf_batch_request.  The bounds are per (window, pair), shared by the window's bands and
+ *               hypotheses.
+ *   dop_idx, dop_frac, lag_int, lag_frac, peak   [n_windows][n_bands][n_pairs].
+ * Definition: slot (w, m, q) is slot (w, q) of rmx_caf_batch_request called with band[w][m] (band[m] when shared) and
+ *   otherwise the same arguments; all five outputs follow that entry's parity statement.  Each (window, band, pair)
+ *   chooses its own winner, the d-major first maximum with strict >, and dop_frac is the parabola through that slot's own
+ *   three coarse peaks.
+ * n_bands == 1 IS rmx_caf_batch_request with the same arguments (one checked request behind both): the same kernels, the
+ *   same launches, bit-identical outputs.
+ * Otherwise the forward kernels run unmasked -- plain, or under RMX_WEIGHT_PHAT whitened with the full band --, once per
+ *   (window, buoy) un-rotated and once per (window, buoy, hypothesis) de-rotated, and the banded pair kernels
+ *   (radio-mapper_amd/csrc/xspec_bands.hpp) mask the product, operand j from the de-rotated set.  A dropped bin is a stored
+ *   +0 in the single-band search and a zeroed product here, and a kept bin is the product of the same two stored values:
+ *   slot (w, m, q) carries the bits of the single-band call with band m.  The exception is rmx_xcorr_batch_bands': on the
+ *   four-step route with the default pair list from 6 buoys on, the single-band call's peaks come from g_rows_anchor,
+ *   which the banded call never takes; there the slot is held to the reference's bars.
+ *   - N = 4096, every hypothesis in one launch (rmx_caf_batch's condition with n_dopplers * n_windows * n_bands virtual
+ *     windows under 2^20; the spectra bound is unchanged): two forward launches, ONE banded pair launch over virtual
+ *     windows v = (d * n_windows + w) * n_bands + m -- operand j at window v / n_bands of the de-rotated set, operand i,
+ *     the band and the lag interval at virtual window v mod (n_windows * n_bands), the output slot v --, and the
+ *     selection over [n_dopplers][n_windows * n_bands * n_pairs].
+ *   - N = 4096 in chunks, the small route, the four-step route: per chunk one un-rotated forward pass, then per hypothesis
+ *     one de-rotated forward pass, the banded pair kernels and k_caf_select(_fd) on the chunk's windows * n_bands *
+ *     n_pairs slots.  The chunk is that of rmx_xcorr_batch_bands for n_bands bands.
+ * Refusals (RMX_E_INVAL, the text in rmx_last_error, nothing staged or written), in this order: the search's head (a NULL
+ *   buffer, band_cps included; a misaligned device pointer; n_dopplers); n_bands outside 1 .. 64; the batch shape and the
+ *   pair list; the weighting and the bands, the text naming the window and the band index; the bounds; dop_frac
+ *   overlapping another output -- every extent n_windows * n_bands * n_pairs elements; then the route: n_bands * n_pairs
+ *   slots per window that no chunk of the ctx holds are refused with a text naming n_bands, never split silently.
+ *   n_windows == 0 or n_pairs == 0 returns RMX_OK and writes nothing.
+ * There is no integration here, and no refinement or quality: rmx_caf_batch_integrated and rmx_caf_batch_quality take one
+ * band per window. */
+int rmx_caf_batch_bands(rmx_ctx* ctx, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                        const double* doppler_cps, int n_dopplers,
+                        const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
+                        const int32_t* lag_bounds, int bounds_per_window,
+                        int32_t* dop_idx, float* dop_frac,
+                        int32_t* lag_int, float* lag_frac, float* peak, unsigned flags);
 
 /* Batched hyperbolic position solve: the consumer of the lags.  One
  * independent 3-unknown least-squares problem per window with the reference's objective

@@ -455,8 +455,9 @@ enum Route {
     kRouteSmallL,      // L <= small_maxl: g_fwd_small + g_pair_small per chunk
     kRouteFourStep     // longer: the column and row passes per chunk (route_rows_fused: g_rows_fused does both row passes)
 };
-enum RouteRefusal { kRouteOk = 0, kRefuseIntegChunk, kRefuseIntegTile };   // integrate > a chunk (RoutePlan::bands_chunk > 0: after
-                                                                             // the bands shrank it) / column tile too large per thread
+enum RouteRefusal { kRouteOk = 0, kRefuseIntegChunk, kRefuseIntegTile, kRefuseBandsChunk };   // integrate > a chunk (RoutePlan::bands_chunk > 0: after
+                                                                             // the bands shrank it) / column tile too large per thread /
+                                                                             // plan_caf: one window's n_bands * n_pairs slots are more than any chunk holds
 
 // what rmx_create / generic_init (and rmx_set_option) fixed for the ctx
 struct RouteCaps {
@@ -648,30 +649,48 @@ struct CafCall {
     bool fine = false;        // dop_frac is asked for
     bool refined = false, qualified = false;
     bool out_dev = false;     // RMX_OUT_DEVICE
+    int n_bands = 1;          // rmx_caf_batch_bands: the pair kernels see n_bands virtual windows per (hypothesis, window)
 };
 struct CafPlan {
-    bool one_launch = false;       // N = 4096: every hypothesis in ONE forward and ONE pair launch (virtual window = hypothesis x window)
+    bool one_launch = false;       // N = 4096: every hypothesis in ONE forward and ONE pair launch (virtual window = hypothesis x window;
+                                   // n_bands > 1: (hypothesis x window) x band)
     int ppb = 7;                   // pairs per workgroup of the N = 4096 pair kernels (unused elsewhere)
     int chunk = 0;                 // windows per chunk of the per-hypothesis sweep, a multiple of integ
     RouteRefusal refused = kRouteOk;
-    size_t out_elems = 0;          // elements of each output: one slot per (group, pair)
+    size_t out_elems = 0;          // elements of each output: one slot per (group, pair); n_bands > 1: per (window, band, pair)
     size_t hyp_elems = 0;          // elements of each per-hypothesis result array: [d][group][pair] in one launch, else one hypothesis'
     bool need_nb = false;          // caf_nb: k_caf_select_fd's three neighbour rows, and dop_frac of a host-pointer call behind them
     bool stage_dfrac = false;      // dop_frac is written to the ctx's block (the fourth row of caf_nb) and copied to the caller
     bool second_sweep = false;     // the hypotheses of each chunk once more, each followed by k_quality / k_refine on the slots it won
 };
+constexpr long kCafMaxVirtualWindows = 1L << 20;   // virtual windows of one pair launch of the Doppler search
 inline CafPlan plan_caf(const RouteCaps& k, const CafCall& a) {
     CafPlan p;
-    const long W = a.n_windows, D = a.n_dopplers;
+    const long W = a.n_windows, D = a.n_dopplers, M = a.n_bands > 1 ? a.n_bands : 1;
     // 21 hypotheses on one frequency group: 431 -> ~60 us against three launches per hypothesis.  One chunk, at most 1 GiB
-    // of de-rotated spectra, and virtual windows that the pair kernels' grids hold
+    // of de-rotated spectra (D * W * B of them whatever the bands), and virtual windows (D * W * M) that the pair kernels' grids hold
     p.one_launch = !k.generic && D > 1 && W <= k.chunk_windows && (size_t)D * W * k.n_buoys * kSpecBytes4096 <= ((size_t)1 << 30) &&
-                   D * W < (1L << 20);
+                   D * W * M < kCafMaxVirtualWindows;
     p.ppb = k.ppb_user ? k.ppb_user : 7;
     if (!k.generic && !k.ppb_user)   // (N = 4096: blocks sized to this batch's work items)
-        (void)split_cost4096(k.n_cus, k.n_buoys, a.n_pairs, (p.one_launch ? W * D : W) / a.integ, 0, &p.ppb);
-    p.refused = integ_chunk(k, k.generic ? k.g_chunk : k.chunk_windows, a.integ, k.generic && (1L << k.logL) > k.small_maxl, &p.chunk);
-    p.out_elems = (size_t)(W / a.integ) * a.n_pairs;
+        (void)split_cost4096(k.n_cus, k.n_buoys, a.n_pairs, (p.one_launch ? W * D : W) * M / a.integ, 0, &p.ppb);
+    // The chunk of the per-hypothesis sweep.  Banded: on the generic routes plan_bands' chunk for M bands -- the cap of the
+    // per-slot buffers, as plan_route takes it --; at N = 4096 chunk_windows, cut so that a chunk's virtual windows stay
+    // below the pair grid's bound.  A window whose own M * P slots no chunk holds (the four-step column pass has one grid
+    // row per slot, and its products lie under the budget) is refused, never split.
+    const bool four_step = k.generic && (1L << k.logL) > k.small_maxl;
+    long chunk = k.generic ? k.g_chunk : k.chunk_windows;
+    if (M > 1) {
+        if (k.generic) {
+            chunk = plan_bands(k.g_chunk, W, (int)M, k.n_buoys, a.n_pairs, 1L << k.logL, four_step, 0, 0, 0).chunk;
+            const long per_win = ((long)k.n_buoys + M * a.n_pairs) * (1L << k.logL) * 8;
+            if (four_step && (M * a.n_pairs > kMaxGridY || per_win > kGenericBudgetBytes)) p.refused = kRefuseBandsChunk;
+        } else if (chunk * M >= kCafMaxVirtualWindows) {
+            chunk = (kCafMaxVirtualWindows - 1) / M;
+        }
+    }
+    if (p.refused == kRouteOk) p.refused = integ_chunk(k, (int)chunk, a.integ, four_step, &p.chunk);
+    p.out_elems = (size_t)(W / a.integ) * (size_t)M * a.n_pairs;
     p.hyp_elems = p.one_launch ? p.out_elems * (size_t)D : p.out_elems;
     p.need_nb = a.fine && (!p.one_launch || !a.out_dev);
     p.stage_dfrac = a.fine && !a.out_dev;

@@ -22,7 +22,7 @@ namespace host {
 struct RequestArgs {
     int n_buoys = 0, n_samples = 0, max_windows = 0;   // of the ctx
     bool grouped = false;           // the entries that take `integrate` (_integrated, _refined, _quality)
-    bool banded = false;            // rmx_xcorr_batch_bands(_quality, _integrated): band_cps is [..][n_bands][2] and never NULL
+    bool banded = false;            // rmx_xcorr_batch_bands(_quality, _integrated), rmx_caf_batch_bands: band_cps is [..][n_bands][2] and never NULL
     int n_bands = 0;                // as passed to a banded entry (0 from the single-band entries)
     bool bounds_required = false;   // rmx_xcorr_batch_bounded: lag_bounds is never NULL
     const void* iq = nullptr;
@@ -235,6 +235,17 @@ inline void full_bounds(int n_samples, Request* r) {
     r->bounded = true;
 }
 
+// a banded call's per-window (per-group) bounds once per VIRTUAL window: row group * n_bands + band holds the group's row
+inline void replicate_bounds(const RequestArgs& a, int K, Request* r) {
+    const size_t row = 2 * (size_t)r->n_pairs;
+    const long out_rows = (long)(a.n_windows / K) * r->n_bands;
+    r->own_bounds.resize((size_t)out_rows * row);
+    for (long v = 0; v < out_rows; ++v)
+        std::memcpy(&r->own_bounds[(size_t)v * row], a.lag_bounds + (size_t)(v / r->n_bands) * row, row * sizeof(int32_t));
+    r->bounds = r->own_bounds.data();
+    r->bound_rows *= r->n_bands;
+}
+
 // Every check of the nine rmx_xcorr_batch* entries, in the order include/rmx.h promises, so an input with several bad
 // arguments is refused for the same one whichever entry it came through: the grouped entries' (integrate, the group
 // count), a NULL buffer, a device pointer aligned to less than its element, n_bands, the weighted entry's, the batch
@@ -287,20 +298,12 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
     }
     r->integ = K;
     r->refine = a.refine;
-    const size_t row = 2 * (size_t)r->n_pairs;
     if (K > 1 && !a.lag_bounds) full_bounds(a.n_samples, r);
     // the bounds are per (window, pair) -- per (group, pair) of an integrated call -- and shared by the bands: per-window
     // bounds go to the device once per VIRTUAL window (window-major; per row group * n_bands + band, group-major), so the
     // bounded kernels index them with the virtual window (the row) as they index their outputs.  (The full intervals made
     // above are the shared form, one row for every group and band: nothing to replicate.)
-    if (r->n_bands > 1 && r->bounded && r->bounds_per_window) {
-        const long out_rows = (long)(a.n_windows / K) * r->n_bands;
-        r->own_bounds.resize((size_t)out_rows * row);
-        for (long v = 0; v < out_rows; ++v)
-            std::memcpy(&r->own_bounds[(size_t)v * row], a.lag_bounds + (size_t)(v / r->n_bands) * row, row * sizeof(int32_t));
-        r->bounds = r->own_bounds.data();
-        r->bound_rows *= r->n_bands;
-    }
+    if (r->n_bands > 1 && r->bounded && r->bounds_per_window) replicate_bounds(a, K, r);
     return RMX_OK;
 }
 
@@ -308,15 +311,17 @@ inline int check_request(const RequestArgs& a, Request* r, std::string* err) {
 // bounded entry's, dop_frac over another output, refine, quality over one of the five other outputs (k_quality reads
 // peak and dop_idx while it writes quality), a device quality aligned to less than its element.  The bands stay per
 // window, the bounds are per GROUP and every output extent is G * n_pairs slots, G = n_windows / K; K > 1 without bounds
-// carries the full interval per pair, as check_request's.
+// carries the full interval per pair, as check_request's.  The banded search (rmx_caf_batch_bands, a.banded): n_bands band
+// rows per window, every extent n_windows * n_bands * n_pairs slots, and per-window bounds replicated per virtual window
+// as check_request replicates them.
 inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const float* dop_frac, Request* r, std::string* err) {
     *r = Request{};
     r->n_pairs = a.n_pairs;
     const int K = a.grouped ? a.integrate : 1;
-    const size_t slots = (size_t)(a.n_windows / K) * a.n_pairs;
+    const size_t slots = (size_t)(a.n_windows / K) * (size_t)(a.banded ? a.n_bands : 1) * a.n_pairs;
     const OutArray outs[5] = {{"dop_idx", dop_idx}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}, {"dop_frac", dop_frac}};
     int rc;
-    if (a.band_cps || a.weighting != RMX_WEIGHT_NONE) {
+    if (a.banded || a.band_cps || a.weighting != RMX_WEIGHT_NONE) {
         rc = check_bands(a, r, err);
         if (rc != RMX_OK) return rc;
     }
@@ -342,21 +347,25 @@ inline int check_caf_request(const RequestArgs& a, const int32_t* dop_idx, const
     r->integ = K;
     r->refine = a.refine;
     if (K > 1 && !a.lag_bounds) full_bounds(a.n_samples, r);
+    if (r->n_bands > 1 && r->bounded && r->bounds_per_window) replicate_bounds(a, K, r);
     return RMX_OK;
 }
 
-// Every check of the four rmx_caf_batch* entries, in the order include/rmx.h promises, as check_request is every check of
-// a correlation call.  The head: a NULL buffer, a device pointer aligned to less than its element (the five arrays),
-// n_dopplers, the group count (a.grouped with a.integrate != 1 only: one window per group takes an empty batch), the
-// batch shape, the empty batch, the pair list; then the tail above on the resolved pair count.  RMX_OK with *r filled
+// Every check of the five rmx_caf_batch* entries, in the order include/rmx.h promises, as check_request is every check of
+// a correlation call.  The head: a NULL buffer (rmx_caf_batch_bands: band_cps too), a device pointer aligned to less than
+// its element (the five arrays), n_dopplers, n_bands (rmx_caf_batch_bands), the group count (a.grouped with
+// a.integrate != 1 only: one window per group takes an empty batch), the batch shape, the empty batch, the pair list; then
+// the tail above on the resolved pair count.  RMX_OK with *r filled
 // (r->empty: nothing to do), or RMX_E_INVAL with *err.
 inline int check_caf_request(const RequestArgs& a, Request* r, std::string* err) {
     *r = Request{};
-    if (!a.iq || !a.dop_idx || !a.lag_int || !a.lag_frac || !a.peak || !a.doppler_cps) return refuse(err, "NULL buffer");
+    if (!a.iq || !a.dop_idx || !a.lag_int || !a.lag_frac || !a.peak || !a.doppler_cps || (a.banded && !a.band_cps))
+        return refuse(err, "NULL buffer");
     const OutArray outs[5] = {{"dop_idx", a.dop_idx}, {"dop_frac", a.dop_frac}, {"lag_int", a.lag_int}, {"lag_frac", a.lag_frac}, {"peak", a.peak}};
     int rc = check_alignment(a.flags, a.iq, outs, 5, err);
     if (rc != RMX_OK) return rc;
     if (a.n_dopplers < 1 || a.n_dopplers > 4096) return refuse(err, "n_dopplers %d not in 1..4096", a.n_dopplers);
+    if (a.banded && (a.n_bands < 1 || a.n_bands > 64)) return refuse(err, "n_bands %d not in 1..64", a.n_bands);
     if (a.grouped && a.integrate != 1) {
         rc = check_groups(a.integrate, a.n_windows, err);
         if (rc != RMX_OK) return rc;

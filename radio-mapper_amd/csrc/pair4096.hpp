@@ -137,19 +137,27 @@ __device__ __forceinline__ void pair_body(const float4* __restrict__ spec, const
     const int it_end = part_begin[part + 1];
     // banded: wl is a VIRTUAL window (real window wl / n_bands, band wl % n_bands); both spectra are the real window's,
     // and bit s of `keep` says whether this thread's slot s lies in the band (role C: xspec_weight.hpp's k_fwd map)
+    // rmx_caf_batch_bands, all hypotheses in one launch (i_wrap > 0, in virtual windows): wl = (hypothesis * windows +
+    // window) * n_bands + band; operand j is at wl / n_bands in the de-rotated set, operand i and the band are those of
+    // virtual window wl % i_wrap = window * n_bands + band.  All of it scalar, once per workgroup.
     int wr = wl;
+    [[maybe_unused]] int wr_i = wl;
     [[maybe_unused]] unsigned keep = 0xffffu;
     if constexpr (BANDED) {
         const BandSet bs = band_set_of(bs_pack...);
+        const int vi = i_wrap > 0 ? wl % i_wrap : wl;
         wr = band_real_window(bs, wl);
-        const XBand bd = band_of_virtual(bs, wl);
+        wr_i = band_real_window(bs, vi);
+        const XBand bd = band_of_virtual(bs, vi);
         const int kb = RMX_XBIN_KFWD(p, u);
         keep = 0u;
 #pragma unroll
         for (int s = 0; s < 16; ++s) keep |= (xband_keeps(bd, kb + kXbinKfwdSlot * s, kL - 1) ? 1u : 0u) << s;
     }
     const long wbase = (long)wr * n_buoys;
-    const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wr) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
+    long wbase_i;
+    if constexpr (BANDED) wbase_i = (long)wr_i * n_buoys;
+    else wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wr) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
     float4 sa[8], sb[8];   // X_i (anchor) and X_j of the pair about to be processed
     PairItem pi = items[it_begin < it_end ? it_begin : 0];
     if (it_begin < it_end) {
@@ -587,19 +595,25 @@ __global__ __launch_bounds__(kThreads, 2) void k_pair_res(
     if (it_begin >= it_end) return;
     // banded: wl is a VIRTUAL window (real window wl / n_bands, band wl % n_bands); both spectra are the real window's,
     // and bit s of `keep` says whether this thread's slot s lies in the band (role C: xspec_weight.hpp's k_fwd map)
+    // (rmx_caf_batch_bands, all hypotheses in one launch: i_wrap in virtual windows, as pair_body)
     int wr = wl;
+    [[maybe_unused]] int wr_i = wl;
     [[maybe_unused]] unsigned keep = 0xffffu;
     if constexpr (BANDED) {
         const BandSet bs = band_set_of(lb_pack...);
+        const int vi = i_wrap > 0 ? wl % i_wrap : wl;
         wr = band_real_window(bs, wl);
-        const XBand bd = band_of_virtual(bs, wl);
+        wr_i = band_real_window(bs, vi);
+        const XBand bd = band_of_virtual(bs, vi);
         const int kb = RMX_XBIN_KFWD(p, u);
         keep = 0u;
 #pragma unroll
         for (int s = 0; s < 16; ++s) keep |= (xband_keeps(bd, kb + kXbinKfwdSlot * s, kL - 1) ? 1u : 0u) << s;
     }
     const long wbase = (long)wr * n_buoys;
-    const long wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wr) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
+    long wbase_i;
+    if constexpr (BANDED) wbase_i = (long)wr_i * n_buoys;
+    else wbase_i = (long)(i_wrap > 0 ? wl % i_wrap : wr) * n_buoys;   // (rmx_caf_batch: wl = hypothesis * windows + window)
     const long obase = (first_window + wl) * (long)n_pairs;
     // the window whose lag bounds apply (one launch for all hypotheses: the REAL window; the output slot stays virtual)
     [[maybe_unused]] const long lbw = first_window + (i_wrap > 0 ? wl % i_wrap : wl);

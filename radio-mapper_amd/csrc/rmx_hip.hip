@@ -1019,8 +1019,10 @@ static int fwd4096(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, 
 static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, float out_scale,
                      bool use_rot, int n_bins = 1) {
     const int n_parts = c->plan_n_parts;
-    const int i_wrap = n_bins > 1 ? wc : 0;     // (all hypotheses in one launch: virtual window = hypothesis * wc + window)
     const int nb = call.banded() ? call.bs.n_bands : 1;   // (banded call: virtual window = window * n_bands + band)
+    // all hypotheses in one launch: virtual window = hypothesis * wc + window; banded (rmx_caf_batch_bands): that times
+    // n_bands, plus the band, and the wrap counts virtual windows
+    const int i_wrap = n_bins > 1 ? wc * nb : 0;
     const long first = (long)w0 * nb;
     wc *= n_bins * nb;
     const int xcd_map = (wc % 8 == 0) ? 1 : 0;
@@ -1062,7 +1064,8 @@ static int pairs4096(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pa
         BandSet bs = call.bs;
         bs.w0 = w0;
         if (c->resident) return call.bounded() ? res(k_pair_res<LagBounds, BandSet>, call.lb, bs) : res(k_pair_res<BandSet>, bs);
-        return call.bounded() ? str(k_pair_str<LagBounds, BandSet>, wc, xcd_map, first, 0, call.lb, bs) : str(k_pair_str<BandSet>, wc, xcd_map, first, 0, bs);
+        return call.bounded() ? str(k_pair_str<LagBounds, BandSet>, wc, xcd_map, first, i_wrap, call.lb, bs)
+                              : str(k_pair_str<BandSet>, wc, xcd_map, first, i_wrap, bs);
     }
     if (c->resident) return call.bounded() ? res(k_pair_res<LagBounds>, call.lb) : res(k_pair_res<>);
     return call.bounded() ? str(k_pair_str<LagBounds>, wc, xcd_map, (long)w0, i_wrap, call.lb) : str(k_pair_str<>, wc, xcd_map, (long)w0, i_wrap);
@@ -1167,8 +1170,13 @@ static int k16_batch(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int n_
 }
 
 // a refusal of the planner as the caller reads it
-static int route_refusal(rmx_ctx* c, host::RouteRefusal refused, int bands_chunk, const host::RouteCaps& k, int integ, int n_bands) {
+static int route_refusal(rmx_ctx* c, host::RouteRefusal refused, int bands_chunk, const host::RouteCaps& k, int integ, int n_bands,
+                         int n_pairs = 0) {
     if (refused == host::kRouteOk) return RMX_OK;
+    if (refused == host::kRefuseBandsChunk)
+        return fail(c, RMX_E_INVAL, "n_bands = %d bands x %d pairs are more slots per window than any chunk of this ctx holds (at most %ld, "
+                    "their products under %ld bytes): a window's bands are never split", n_bands, n_pairs, host::kMaxGridY,
+                    host::kGenericBudgetBytes);
     if (refused == host::kRefuseIntegChunk && bands_chunk > 0)
         return fail(c, RMX_E_INVAL, "integrate = %d windows per group is more than the chunk of %d windows that n_bands = %d bands shrank this "
                     "ctx's chunk of %d windows to: a group is never split", integ, bands_chunk, n_bands, k.g_chunk);
@@ -1940,7 +1948,9 @@ static int caf_sweep(rmx_ctx* c, const CafRun& r, const host::CafPlan& plan) {
             if (rc != RMX_OK) break;
             rc = sv.pairs(c, r.call, w0, wc, r.n_pairs, c->caf_lag, c->caf_frac, c->caf_peak, true, false);
             if (rc != RMX_OK) break;
-            const long first = (long)(w0 / K) * r.n_pairs, cnt = (long)(wc / K) * r.n_pairs;   // the chunk's output rows
+            // the chunk's output rows (banded: n_bands virtual windows per window, never integrated)
+            const long nb = r.call.banded() ? r.call.bs.n_bands : 1;
+            const long first = (long)(w0 / K) * nb * r.n_pairs, cnt = (long)(wc / K) * nb * r.n_pairs;
             const dim3 sgrid((unsigned)((cnt + 255) / 256));
             if (r.dfrac)
                 rc = launch(c, kTkCafSelect, k_caf_select_fd, sgrid, dim3(256), 0, d, D, first, cnt, (long)plan.out_elems, c->caf_lag,
@@ -1961,7 +1971,7 @@ static int caf_sweep(rmx_ctx* c, const CafRun& r, const host::CafPlan& plan) {
     return rc;
 }
 
-// What all four Doppler entries do, and none of them through another: hand their arguments to host::check_caf_request --
+// What all five Doppler entries do, and none of them through another: hand their arguments to host::check_caf_request --
 // every refusal, in one order whichever entry the call came through --, describe the search in an XcorrCall (the staged
 // bands and lag intervals), let host::plan_caf decide its shape and run that.  The plain search is one window per group,
 // no band, no weighting, no bounds, dop_frac == NULL, nothing refined or qualified.
@@ -1987,23 +1997,24 @@ static int caf_request(rmx_ctx* c, host::RequestArgs a, unsigned flags) {
     r.tail = r.call;
     r.tail.refine = rq.refine;
     r.tail.quality = a.quality;
-    const host::CafCall cq{a.n_windows, rq.n_pairs, a.n_dopplers, rq.integ, a.dop_frac != nullptr, r.tail.refined(), r.tail.qualified(), out_dev};
+    const host::CafCall cq{a.n_windows, rq.n_pairs, a.n_dopplers, rq.integ, a.dop_frac != nullptr, r.tail.refined(), r.tail.qualified(),
+                           out_dev, rq.n_bands};
     host::RouteCaps caps = route_caps(c);
     host::CafPlan plan = host::plan_caf(caps, cq);
     if (!c->generic) c->pairs_per_block = plan.ppb;   // (N = 4096: blocks sized to this batch, not to the previous call's)
     rc = build_plan(c, a.pairs, rq.n_pairs);
-    if (rc == RMX_OK) rc = route_refusal(c, plan.refused, 0, caps, rq.integ, 1);
+    if (rc == RMX_OK) rc = route_refusal(c, plan.refused, 0, caps, rq.integ, rq.n_bands, rq.n_pairs);
     if (rc == RMX_OK) rc = host_input(c, a.iq, (size_t)a.n_windows * c->n_buoys * c->n_samples * (r.u8 ? 2 : 8), in_dev, true, &r.d_iq);
     if (rc == RMX_OK) rc = caf_phasors(c, a.doppler_cps, a.n_dopplers);
     if (rc == RMX_OK) rc = caf_buffers(c, a, plan, out_dev, &r);
     if (rc != RMX_OK) return rc;
     tm_reset(c);
     if (c->generic) {   // a failed allocation halves g_chunk, and the plan follows: whole groups per chunk, or the refusal
-        rc = rmx::generic_ensure(c, rq.n_pairs);
+        rc = rmx::generic_ensure(c, rq.n_pairs, true, true, rq.n_bands);
         if (rc == RMX_OK && c->g_chunk != caps.g_chunk) {
             caps.g_chunk = c->g_chunk;
             plan = host::plan_caf(caps, cq);
-            rc = route_refusal(c, plan.refused, 0, caps, rq.integ, 1);
+            rc = route_refusal(c, plan.refused, 0, caps, rq.integ, rq.n_bands, rq.n_pairs);
         }
     } else {
         rc = ensure_spec(c, a.n_windows < c->chunk_windows ? a.n_windows : c->chunk_windows);
@@ -2082,6 +2093,24 @@ int rmx_caf_batch_integrated(rmx_ctx* c, const void* iq, int n_windows, const in
     a.integrate = integrate;
     a.refine = refine;
     a.quality = quality;
+    return caf_request(c, a, flags);
+}
+
+// rmx_caf_batch_request under n_bands bands per window over ONE set of forward passes (xspec_bands.hpp): the forward
+// kernels run unmasked -- plain, or under PHAT weighted with the full band --, once un-rotated and once per hypothesis
+// de-rotated; the banded pair kernels mask the product with operand j from the de-rotated set and see n_bands virtual
+// windows per (hypothesis, window); the selection runs over n_windows * n_bands * n_pairs slots.  n_bands == 1 IS
+// rmx_caf_batch_request.
+int rmx_caf_batch_bands(rmx_ctx* c, const void* iq, int n_windows, const int32_t* pairs, int n_pairs,
+                        const double* doppler_cps, int n_dopplers,
+                        const double* band_cps, int n_bands, int bands_per_window, unsigned weighting,
+                        const int32_t* lag_bounds, int bounds_per_window,
+                        int32_t* dop_idx, float* dop_frac,
+                        int32_t* lag_int, float* lag_frac, float* peak, unsigned flags) {
+    host::RequestArgs a = weighted_args(caf_args(iq, n_windows, pairs, n_pairs, doppler_cps, n_dopplers, dop_idx, dop_frac, lag_int, lag_frac, peak),
+                                        band_cps, bands_per_window, weighting, lag_bounds, bounds_per_window);
+    a.banded = true;
+    a.n_bands = n_bands;
     return caf_request(c, a, flags);
 }
 

@@ -16,6 +16,12 @@
 // A dropped bin is exactly +0, which is what the product of two masked spectra is, and a kept bin is the product of the
 // same two stored values: slot (w, m, q) carries the bits of the weighted call with band[w][m].
 //
+// The Doppler search under several bands (rmx_caf_batch_bands): the same banded pair kernels with operand j from the
+// de-rotated set.  Per hypothesis nothing changes.  With every hypothesis in ONE launch of N = 4096 the virtual window is
+// v = (d W + w) n_bands + m and the kernels get i_wrap = W n_bands: operand j at window v / n_bands of the de-rotated set,
+// operand i, the band and the lag interval those of virtual window v mod i_wrap, the output row v.  i_wrap = 0 is the
+// correlation above.
+//
 // Banded AND integrated (rmx_xcorr_batch_bands_integrated): the third pack, <LagBounds, Integrate, BandSet>, on the
 // integrating pair kernels (integrate.hpp) and on k_refine / k_quality.  A work item is an output ROW r = g n_bands + m
 // -- group g, band m -- and a pair: it walks the real windows g K ... g K + K - 1 of the chunk, masks each window's

@@ -36,7 +36,7 @@ def _more(req: LagRequest, name_refine: bool) -> dict:
 
 
 class MultiXcorrEngine:
-    """`XcorrEngine.correlate` / `.caf` over several devices.
+    """`XcorrEngine.correlate` / `.correlate_bands` / `.caf` / `.caf_bands` over several devices.
 
     devices=None -> every visible device (`rmx_device_count`).  A device may be listed more than once (two
     contexts on one GPU: the rehearsal mode of the tests).  `engine_factory(n_buoys, n_samples, max_windows,
@@ -205,3 +205,18 @@ class MultiXcorrEngine:
                 return eng.caf(x, doppler_cps, pairs, lag_bounds=lb, band=bd, whiten=whiten, fine=fine, **more)
             return eng.caf(x, doppler_cps, pairs)
         return self._shard(req, iq, call)
+
+    def caf_bands(self, iq: np.ndarray, doppler_cps, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
+                  whiten: bool = False, fine: bool = False):
+        """XcorrEngine.caf_bands over the devices -> (doppler_idx, lag_int, lag_frac, peak), each [W][M][P]; with fine=True
+        (doppler_idx, dop_frac, lag_int, lag_frac, peak).  The windows are sharded as caf() shards them: bands [M][2] and
+        lag_bounds [P][2] go to every block whole, [W][M][2] and [W][P][2] are cut into each block's own windows' rows; the
+        grid goes to every block whole."""
+        iq = np.asarray(iq)
+        if iq.ndim != 3:
+            raise ValueError(f"iq must be [W][B][N], got shape {iq.shape}")
+        # (the engines see the caller's own grid and check it themselves, as they do the pairs)
+        req = lag_request("caf_bands", self.n_buoys, iq.shape[0], None, lag_bounds, bands, whiten, doppler_cps=(), fine=fine,
+                          n_pairs=self._n_pairs(pairs))
+        return self._shard(req, iq, lambda eng, x, lb, bd: eng.caf_bands(x, doppler_cps, bd, pairs, lag_bounds=lb, whiten=whiten,
+                                                                          fine=fine))

@@ -165,7 +165,7 @@ class TDoACalculator:
                  bound_lags: bool = False, band_limit: bool = False, whiten: bool = False, integrate: int = 1,
                  refine: int = 0, min_psr: Optional[float] = None, correlation_confidence: bool = False,
                  doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False,
-                 share_qualified: bool = False, share_integrated: bool = False):
+                 share_qualified: bool = False, share_integrated: bool = False, share_doppler: bool = False):
         """device: the GPU of a single-device calculator (the default).  devices: a list of GPUs, or "all" for every
         visible one -- with more than one entry a batch of windows / frequency groups is block-sharded over them by
         `multi.MultiXcorrEngine` (one rmx_ctx and one host thread per device, no collective).  min_cut_samples: the
@@ -204,7 +204,7 @@ class TDoACalculator:
         that were cut from ONE capture (byte-identical windows, identical lag bounds) as one window under several bands
         (rmx_xcorr_batch_bands: one upload and one forward transform per buoy instead of one per emitter); the lags are
         those of the separate calls.  Not for groups under integrate, refine, min_psr / correlation_confidence or
-        doppler_search_hz, which go the usual way.  A plain attribute, False (off) by default: the engine is then called
+        doppler_search_hz, which go the usual way (share_qualified, share_integrated and share_doppler, below, admit them).  A plain attribute, False (off) by default: the engine is then called
         exactly as before.
         share_qualified: together with share_captures, shared captures are also correlated as one window under several
         bands when refine > 0, min_psr or correlation_confidence is set (rmx_xcorr_batch_bands_quality: the fine lag search
@@ -217,7 +217,12 @@ class TDoACalculator:
         the separate calls cut it, each member's band is repeated over its K segments, and lag bounds and the
         segment_length checks are as without sharing.  With refine > 0, min_psr or correlation_confidence it needs
         share_qualified as well.  The Doppler search stays out.  A plain attribute, False (off) by default: share_captures
-        and share_qualified alone still stand back for integration."""
+        and share_qualified alone still stand back for integration.
+        share_doppler: together with band_limit, share_captures and doppler_search_hz, shared captures go through ONE Doppler
+        search under several bands (rmx_caf_batch_bands: one upload, and the forward transforms of every hypothesis once
+        per buoy instead of once per emitter); the measurements, frequency_offset_hz included, are those of the separate
+        searches, in the same order.  A plain attribute, False (off) by default: groups under doppler_search_hz then go
+        the usual way, one full search per emitter."""
         from .xcorr import check_refine
         self.logger = logging.getLogger(__name__ + ".TDoACalculator")
         self.device = device
@@ -229,6 +234,7 @@ class TDoACalculator:
         self.share_captures = bool(share_captures)
         self.share_qualified = bool(share_qualified)
         self.share_integrated = bool(share_integrated)
+        self.share_doppler = bool(share_doppler)
         self.integrate = int(integrate)
         self.refine = check_refine(refine)
         self.min_psr = None if min_psr is None else float(min_psr)
@@ -343,7 +349,8 @@ class TDoACalculator:
                                         **_named(integrate=integrate, refine=refine, quality=bool(quality))))
         return unfold(eng.correlate(iq, pairs, **_named(lag_bounds=lb)))
 
-    def measure_band_lags(self, iq, bands, pairs=None, lag_bounds=None, whiten=False, refine=0, quality=False, integrate=1):
+    def measure_band_lags(self, iq, bands, pairs=None, lag_bounds=None, whiten=False, refine=0, quality=False, integrate=1,
+                          doppler_cps=None):
         """measure_lags(bands=...) with the fine lag search and the quality figures (rmx_xcorr_batch_bands_quality): iq
         complex64 [W][B][N] (or uint8 [W][B][2N]) under bands [W][M][2] -> (lag_int, lag_frac, peak), each [W][M][P], and
         with quality=True a fourth array [W][M][P][4]; one forward transform per (window, buoy).  A leading channel axis is
@@ -351,14 +358,27 @@ class TDoACalculator:
         ([C][W][M][P][4]).  refine: U in (0, 2, 4, 8, 16).  With refine=0 and quality=False it is measure_lags(bands=...).
         integrate: K >= 1 consecutive windows per group, one lag per (group, band, pair) (rmx_xcorr_batch_bands_integrated):
         W must be a multiple of K -- with a channel axis, every channel's W --, the results and per-group lag_bounds are
-        [W // K][.], the bands stay per window."""
+        [W // K][.], the bands stay per window.
+        doppler_cps: None, or the hypotheses of a Doppler search in cycles per sample (a uniformly spaced grid): the call
+        goes to caf_bands() (rmx_caf_batch_bands) with the same lag_bounds and whiten, and returns (lag_int, lag_frac, peak,
+        dop_idx int32, doppler float64 in cycles per sample), each [W][M][P], as measure_lags(doppler_cps=...) returns them
+        per band.  Not together with integrate > 1, refine > 0 or quality (ValueError)."""
         from .xcorr import check_refine
         refine = check_refine(refine)
+        if doppler_cps is not None:
+            for name, on in (("integrate", integrate != 1), ("refine", refine > 0), ("quality", bool(quality))):
+                if on:
+                    raise ValueError(f"doppler_cps and {name} cannot be combined: the Doppler search under several bands has "
+                                     f"no integration, refinement or quality")
         iq, integrate, fold, unfold = self._channels(iq, integrate)
         eng = self._engine(iq.shape[1], iq.shape[2] // 2 if iq.dtype == np.uint8 else iq.shape[2], iq.shape[0])
         lb, bs = fold(lag_bounds, 4, True), fold(np.asarray(bands), 4)
         if bs.ndim != 3 or bs.shape[0] != iq.shape[0] or bs.shape[2] != 2:
             raise ValueError(f"bands must be [W][M][2] or [C][W][M][2] for {iq.shape[0]} windows, got shape {np.shape(bands)}")
+        if doppler_cps is not None:
+            from .xcorr import doppler_estimate
+            dop, dfrac, li, lf, pk = eng.caf_bands(iq, doppler_cps, bs, pairs, lag_bounds=lb, whiten=bool(whiten), fine=True)
+            return unfold((li, lf, pk, dop, doppler_estimate(doppler_cps, dop, dfrac)))
         return unfold(eng.correlate_bands(iq, bs, pairs, lag_bounds=lb, whiten=bool(whiten),
                                           **_named(refine=refine, quality=bool(quality), integrate=integrate)))
 
@@ -552,16 +572,22 @@ class TDoACalculator:
             return li.astype(np.float64) + lf.astype(np.float64)
         return self._logged(measure)
 
-    def _measure_shared(self, stacked: np.ndarray, lag_bounds, bands: np.ndarray, with_quality: bool = False):
+    def _measure_shared(self, stacked: np.ndarray, lag_bounds, bands: np.ndarray, with_quality: bool = False, fs=None):
         """share_captures: [G][B][N] captures, each under the M bands of bands [G][M][2] -> lag [G][M][P] float64, or None
         after logging, as _measure_groups does.  lag_bounds: None, or int [G][P][2].  share_qualified: the calculator's
         refine goes along, and with_quality -> (lag [G][M][P], quality [G][M][P][4]) instead.  share_integrated: under
         integrate = K > 1 every capture is cut into its K segments as _measure_groups cuts it and every band is repeated
-        over its capture's segments (the callers checked segment_length and derived lag_bounds and bands for N // K)."""
+        over its capture's segments (the callers checked segment_length and derived lag_bounds and bands for N // K).
+        share_doppler (doppler_search_hz; fs, the captures' sample rate, must be given): -> (lag [G][M][P], offset in hertz
+        [G][M][P]) instead, from one Doppler search under the M bands."""
         stacked, bands, k = self._segments(stacked, bands)
         more = _named(integrate=k)
 
         def measure():
+            if self.doppler_search_hz is not None:
+                li, lf, _, _, dop = self.measure_band_lags(stacked, bands, lag_bounds=lag_bounds, whiten=self.whiten,
+                                                           doppler_cps=self.doppler_grid(fs))
+                return li.astype(np.float64) + lf.astype(np.float64), np.asarray(dop, np.float64) * float(fs)
             if with_quality:
                 li, lf, _, qual = self.measure_band_lags(stacked, bands, lag_bounds=lag_bounds, whiten=self.whiten,
                                                          refine=self.refine, quality=True, **more)
@@ -801,14 +827,15 @@ class TDoAProcessor:
     def __init__(self, band_limit: bool = False, whiten: bool = False, integrate: int = 1, refine: int = 0,
                  min_psr: Optional[float] = None, correlation_confidence: bool = False,
                  doppler_search_hz: Optional[Tuple[float, float]] = None, share_captures: bool = False,
-                 share_qualified: bool = False, share_integrated: bool = False):
+                 share_qualified: bool = False, share_integrated: bool = False, share_doppler: bool = False):
         """band_limit, whiten, integrate, refine, min_psr, correlation_confidence, doppler_search_hz, share_captures,
-        share_qualified, share_integrated: the TDoACalculator settings of the same names (off by default)."""
+        share_qualified, share_integrated, share_doppler: the TDoACalculator settings of the same names (off by default)."""
         self.logger = logging.getLogger(__name__ + ".TDoAProcessor")
         self.tdoa_calculator = TDoACalculator(band_limit=band_limit, whiten=whiten, integrate=integrate, refine=refine,
                                               min_psr=min_psr, correlation_confidence=correlation_confidence,
                                               doppler_search_hz=doppler_search_hz, share_captures=share_captures,
-                                              share_qualified=share_qualified, share_integrated=share_integrated)
+                                              share_qualified=share_qualified, share_integrated=share_integrated,
+                                              share_doppler=share_doppler)
         self.hyperbolic_positioner = HyperbolicPositioning()
         self.buoy_positions: Dict[str, BuoyPosition] = {}
         self.correlation_window_s = 10.0
@@ -883,8 +910,9 @@ class TDoAProcessor:
                 if not members:
                     continue
                 # (refine, min_psr / correlation_confidence: only with share_qualified; integrate: only with share_integrated;
-                # the Doppler search never)
-                if calc.share_captures and (calc.integrate == 1 or calc.share_integrated) and calc.doppler_search_hz is None \
+                # the Doppler search only with share_doppler -- it has none of the three)
+                if calc.share_captures and (calc.integrate == 1 or calc.share_integrated) \
+                        and (calc.doppler_search_hz is None or calc.share_doppler) \
                         and (calc.share_qualified or (calc.refine == 0 and not calc._wants_quality())):
                     members = self._measure_shared_captures(work, members, bands, n_samp, key[3])
                     if not members:
@@ -938,7 +966,8 @@ class TDoAProcessor:
         several bands (TDoACalculator._measure_shared); their work items get their lags as the separate calls would have
         set them.  A row with fewer bands than the widest is padded by repeating its last band, and the padded outputs
         are dropped.  share_qualified: the quality figures of every (capture, band) ride along as the work item's fourth
-        entry, as _measure_groups' do.  Returns the members that are left for the usual call."""
+        entry, as _measure_groups' do.  share_doppler: one Doppler search under the bands; every member's work item is the
+        search's own (lag, fs, window starts, None, offsets in hertz).  Returns the members that are left for the usual call."""
         calc = self.tdoa_calculator
         per = {n: calc.lag_bounds(work[n][1], self.buoy_positions, n_samp, fs) for n in members} if calc.bound_lags else {}
         rows: Dict[Any, List[int]] = {}
@@ -954,14 +983,21 @@ class TDoAProcessor:
                              for r in shared])
         stacked = np.stack([work[r[0]][3] for r in shared])
         more = {"with_quality": True} if calc._wants_quality() else {}
+        doppler = calc.doppler_search_hz is not None
+        if doppler:
+            more = {"fs": fs}
         lags = calc._measure_shared(stacked, np.stack([per[r[0]][0] for r in shared]) if per else None, band_set, **more)
-        qual = None
-        if more and lags is not None:
+        qual = dop = None
+        if doppler and lags is not None:
+            lags, dop = lags
+        elif more and lags is not None:
             lags, qual = lags
         for g, r in enumerate(shared):
             for m, n in enumerate(r):
                 if lags is None:
                     work[n][4] = None
+                elif doppler:
+                    work[n][4] = (lags[g, m], fs, per[n][1] if per else None, None, dop[g, m])
                 elif qual is None:
                     work[n][4] = (lags[g, m], fs) + ((per[n][1],) if per else ())
                 else:

@@ -102,6 +102,8 @@ def load_library():
     lib.rmx_caf_batch_quality.restype = ci
     lib.rmx_caf_batch_integrated.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, ci, cu, vp, ci, ci, vp, vp, vp, vp, vp, vp, cu]
     lib.rmx_caf_batch_integrated.restype = ci
+    lib.rmx_caf_batch_bands.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, ci, cu, vp, ci, vp, vp, vp, vp, vp, cu]
+    lib.rmx_caf_batch_bands.restype = ci
     lib.rmx_solve_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, ci, ci, vp, vp, vp, cu]
     lib.rmx_solve_batch.restype = ci
     lib.rmx_detect_batch.argtypes = [vp, vp, ci, ci, C.c_float, ci, C.c_double, C.c_float, ci, vp, vp, vp, vp, vp, vp, cu]
@@ -220,25 +222,29 @@ def check_refine(refine) -> int:
 OUTPUTS = ("dop_idx", "dop_frac", "lag_int", "lag_frac", "peak", "quality")   # in the order every method returns them
 
 
+_BANDED = ("bands", "caf_bands")   # the families whose outputs carry a band axis
+_SEARCH = ("caf", "caf_bands")     # the families with a Doppler grid and a dop_idx output
+
+
 class LagRequest(NamedTuple):
     """One checked correlation or Doppler-search call: what lag_request() made of the options of correlate(),
-    correlate_bands(), caf() and their device-pointer twins.  It holds the normalised host arrays themselves, so whoever holds
+    correlate_bands(), caf(), caf_bands() and their device-pointer twins.  It holds the normalised host arrays themselves, so whoever holds
     the request keeps alive what the C entry reads; it is a tuple, so nothing changes it after the checks (MultiXcorrEngine
     hands one to several worker threads, and cut() returns views)."""
-    family: str                    # "xcorr", "bands" or "caf"
+    family: str                    # "xcorr", "bands", "caf" or "caf_bands"
     n_windows: int
     K: int                         # windows per group
     U: int                         # fine lag grid, 0 for none
     P: int
-    M: int                         # bands per window ("bands"), else 0
+    M: int                         # bands per window ("bands", "caf_bands"), else 0
     pairs: Optional[np.ndarray]    # int32 [P][2], None: every i < j
     bounds: Optional[np.ndarray]   # int32 [P][2] or [rows][P][2]
     bounds_per_row: bool
-    band: Optional[np.ndarray]     # float64 [2] or [W][2]; "bands": [M][2] or [W][M][2]
+    band: Optional[np.ndarray]     # float64 [2] or [W][2]; "bands", "caf_bands": [M][2] or [W][M][2]
     band_per_window: bool
-    grid: Optional[np.ndarray]     # float64 [D] ("caf")
+    grid: Optional[np.ndarray]     # float64 [D] ("caf", "caf_bands")
     whiten: bool
-    fine: bool                     # a dop_frac output ("caf")
+    fine: bool                     # a dop_frac output ("caf", "caf_bands")
     quality: bool                  # a quality output
 
     @property
@@ -248,8 +254,8 @@ class LagRequest(NamedTuple):
 
     def outputs(self, rows: Optional[int] = None):
         """(name, dtype, shape) of every output of the call (or of `rows` of its rows), in the order the methods return them"""
-        shape = (self.rows if rows is None else rows,) + ((self.M,) if self.family == "bands" else ()) + (self.P,)
-        have = {"dop_idx": self.family == "caf", "dop_frac": self.fine, "quality": self.quality}
+        shape = (self.rows if rows is None else rows,) + ((self.M,) if self.family in _BANDED else ()) + (self.P,)
+        have = {"dop_idx": self.family in _SEARCH, "dop_frac": self.fine, "quality": self.quality}
         return [(n, np.int32 if n in ("dop_idx", "lag_int") else np.float32, shape + ((4,) if n == "quality" else ()))
                 for n in OUTPUTS if have.get(n, True)]
 
@@ -264,9 +270,15 @@ def lag_request(family: str, n_buoys: int, n_windows: int, pairs=None, lag_bound
                 refine=0, quality=False, doppler_cps=None, fine=False, n_pairs: Optional[int] = None) -> LagRequest:
     """The one place where the options of a call are checked: ValueError before any call into the library, in the order
     integrate, refine, pairs, then lag_bounds, band ("xcorr"), bands, lag_bounds ("bands": `band` is the band set) or grid,
-    lag_bounds, band ("caf", where integrate = None is 1 without a check).  n_pairs: the pair count of a caller that leaves the
+    lag_bounds, band ("caf", where integrate = None is 1 without a check) or grid, bands, lag_bounds ("caf_bands", which has no
+    integration, refinement or quality and says so).  n_pairs: the pair count of a caller that leaves the
     pair list to somebody else's check (MultiXcorrEngine: its engines see the caller's own list)."""
-    K = 1 if integrate is None and family == "caf" else check_integrate(integrate, n_windows)
+    if family == "caf_bands":
+        for what, asked in (("integration", integrate is not None and integrate != 1), ("refinement", refine != 0),
+                            ("quality", bool(quality))):
+            if asked:
+                raise ValueError(f"rmx_caf_batch_bands has no {what}: caf() takes integrate, refine and quality, one band per window")
+    K = 1 if integrate is None and family in _SEARCH else check_integrate(integrate, n_windows)
     U = check_refine(refine)
     if n_pairs is not None:
         pairs, P = None, n_pairs
@@ -276,7 +288,9 @@ def lag_request(family: str, n_buoys: int, n_windows: int, pairs=None, lag_bound
         pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         P = pairs.shape[0]
     grid, M = None, 0
-    if family == "bands":
+    if family in _BANDED:
+        if family == "caf_bands":
+            grid = np.ascontiguousarray(doppler_cps, dtype=np.float64).reshape(-1)
         bd, band_pw = check_bands(band, n_windows)
         M = bd.shape[-2]
         lb, per_row = check_lag_bounds(lag_bounds, n_windows // K, P)
@@ -296,7 +310,7 @@ _ENTRY_ARGS = {"rmx_xcorr_batch": "", "rmx_xcorr_batch_bounded": "B", "rmx_xcorr
                "rmx_xcorr_batch_integrated": "KWB", "rmx_xcorr_batch_refined": "KWBU", "rmx_xcorr_batch_quality": "KWBUQ",
                "rmx_xcorr_batch_bands": "WB", "rmx_xcorr_batch_bands_quality": "WBUQ", "rmx_xcorr_batch_bands_integrated": "KWBUQ",
                "rmx_caf_batch": "", "rmx_caf_batch_request": "WBF", "rmx_caf_batch_quality": "WBUFQ",
-               "rmx_caf_batch_integrated": "KWBUFQ"}
+               "rmx_caf_batch_integrated": "KWBUFQ", "rmx_caf_batch_bands": "WBF"}
 
 
 def entry_name(req: LagRequest) -> str:
@@ -311,6 +325,8 @@ def entry_name(req: LagRequest) -> str:
         if req.band is not None or req.whiten:
             return "rmx_xcorr_batch_weighted"
         return "rmx_xcorr_batch" if req.bounds is None else "rmx_xcorr_batch_bounded"
+    if req.family == "caf_bands":
+        return "rmx_caf_batch_bands"
     stem = "rmx_xcorr_batch_bands" if req.family == "bands" else "rmx_caf_batch"
     if req.K > 1:
         return stem + "_integrated"
@@ -400,7 +416,7 @@ def doppler_estimate(doppler_cps, dop_idx, dop_frac) -> np.ndarray:
 
 
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_xcorr_batch_bands_quality", "rmx_xcorr_batch_bands_integrated", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_caf_batch_quality", "rmx_caf_batch_integrated", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_xcorr_batch_bands_quality", "rmx_xcorr_batch_bands_integrated", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_caf_batch_quality", "rmx_caf_batch_integrated", "rmx_caf_batch_bands", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -553,20 +569,20 @@ class XcorrEngine:
         family, W, K, U, P, M, pairs, bounds, per_row, band, band_pw, grid, whiten, _, _ = req
         dop_p, dop_frac_p, lag_int_p, lag_frac_p, peak_p, quality_p = out_p
         a = [self._ctx, iq_p, W, None if pairs is None else pairs.ctypes.data_as(vp), P]
-        if family == "caf":
+        if family in _SEARCH:
             a += (grid.ctypes.data_as(vp), grid.shape[0])
         if "K" in args:
             a.append(K)
         if "W" in args:
             a.append(None if band is None else band.ctypes.data_as(vp))
-            if family == "bands":
+            if family in _BANDED:
                 a.append(M)
             a += (int(band_pw), RMX_WEIGHT_PHAT if whiten else RMX_WEIGHT_NONE)
         if "B" in args:
             a += (None if bounds is None else bounds.ctypes.data_as(vp), int(per_row))
         if "U" in args:
             a.append(U)
-        if family == "caf":
+        if family in _SEARCH:
             a.append(dop_p)
         if "F" in args:
             a.append(dop_frac_p)
@@ -667,6 +683,20 @@ class XcorrEngine:
         iq, flags = self._check_iq(iq)
         return self._host_call(lag_request("caf", self.n_buoys, iq.shape[0], pairs, lag_bounds, band, whiten, integrate, refine,
                                            quality, doppler_cps, fine), iq, flags)
+
+    def caf_bands(self, iq: np.ndarray, doppler_cps, bands, pairs: Optional[np.ndarray] = None, lag_bounds=None,
+                  whiten: bool = False, fine: bool = False):
+        """The cross-ambiguity search under several bands per window with ONE set of forward transforms
+        (rmx_caf_batch_bands): host arrays in and out.  iq, doppler_cps, lag_bounds, whiten, fine: as for caf(); bands: float
+        [M][2] (shared by every window) or [W][M][2], as for correlate_bands().  The bounds are per (window, pair), shared by
+        the window's bands and hypotheses.
+        Returns (doppler_idx int32, lag_int int32, lag_frac float32, peak float32), each [W][M][P]; with fine=True
+        (doppler_idx, dop_frac float32, lag_int, lag_frac, peak).  [:, m] is what caf(iq, doppler_cps,
+        band=bands[..., m, :], ...) returns; every (window, band, pair) chooses its own hypothesis.
+        The entry has no integration, refinement or quality: caf() takes those, one band per window."""
+        iq, flags = self._check_iq(iq)
+        return self._host_call(lag_request("caf_bands", self.n_buoys, iq.shape[0], pairs, lag_bounds, bands, whiten,
+                                           doppler_cps=doppler_cps, fine=fine), iq, flags)
 
     def solve(self, buoy_xyz, lag_int, lag_frac, sample_rate_hz: float, weight=None,
               pairs: Optional[np.ndarray] = None, max_iter: int = 60):
@@ -780,6 +810,18 @@ class XcorrEngine:
                           doppler_cps, bool(dop_frac_ptr))
         self._call(req, vp(iq_ptr), (vp(dop_ptr), vp(dop_frac_ptr) if dop_frac_ptr else None, vp(lag_int_ptr), vp(lag_frac_ptr),
                                      vp(peak_ptr), vp(quality_ptr) if quality_ptr else None), flags)
+
+    def caf_bands_device(self, iq_ptr: int, n_windows: int, doppler_cps, bands, dop_ptr: int, lag_int_ptr: int, lag_frac_ptr: int,
+                         peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
+                         whiten: bool = False, dop_frac_ptr: int = 0):
+        """caf_bands() with device pointers in and out (the Doppler grid, the bands, the pair list and the bounds stay host
+        arrays; the library keeps its own copies); asynchronous on the ctx stream.  Every output buffer is
+        [n_windows][M][P]; dop_frac_ptr: 0, or a device buffer of that many float32 for the sub-grid Doppler estimate."""
+        req = lag_request("caf_bands", self.n_buoys, n_windows, pairs, lag_bounds, bands, whiten, doppler_cps=doppler_cps,
+                          fine=bool(dop_frac_ptr))
+        vp = C.c_void_p
+        self._call(req, vp(iq_ptr), (vp(dop_ptr), vp(dop_frac_ptr) if dop_frac_ptr else None, vp(lag_int_ptr), vp(lag_frac_ptr),
+                                     vp(peak_ptr), None), _DEVICE | (RMX_IN_U8 if u8 else 0))
 
     def correlate_device(self, iq_ptr: int, n_windows: int, lag_int_ptr: int, lag_frac_ptr: int,
                          peak_ptr: int, pairs: Optional[np.ndarray] = None, u8: bool = False, lag_bounds=None,
