@@ -104,6 +104,11 @@ int rmx_device_count(void);
 
 /* Create an engine for windows of `n_samples` complex64 samples from `n_buoys` buoys.
  * n_samples: power of two, 16 .. 4194304.  max_windows: largest n_windows a later call may pass.
+ * n_windows of every batch entry below is bounded by max_windows and by the device's memory alone: the library cuts a
+ * batch into chunks of its own (the four-step route so that its column pass has at most 65535 grid rows, one per
+ * (window, pair) slot), and every offset into the caller's arrays and into its scratch is 64-bit.  Inputs beyond 4 GiB
+ * (host and device pointers, complex64 and uint8 -- sample index 2^31 --), scratch beyond 4 GiB inside one chunk and calls
+ * of more than 65535 (window, pair) slots are tested on every route (tests/test_gpu_large_batches.py).
  * flags: reserved, pass 0. */
 int rmx_create(rmx_ctx** out, int device_id, int n_buoys, int n_samples, int max_windows,
                unsigned flags);

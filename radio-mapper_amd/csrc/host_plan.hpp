@@ -377,7 +377,27 @@ inline long generic_chunk_windows(int n_buoys, long L, int max_windows, long bud
 // n_bands = 1 leaves the chunk as it is.
 constexpr long kGenericBudgetBytes = 32L << 30;   // spectra + products of a chunk (generic_chunk_windows)
 constexpr long kGenericMaxChunk = 4096;
-constexpr long kMaxGridY = 65535;                 // the largest second grid dimension of a launch
+// The most grid rows (second grid dimension) the library gives a launch.  Not a limit of the runtime: HIP on gfx950 took
+// g_cols_inv with 67 200 rows (16 buoys x 560 windows of 8192 samples, PHAT) and every slot came out right (LABNOTES R19);
+// it is the bound the library states for itself, so that no grid is larger than the ones tests/test_gpu_large_batches.py
+// runs on both sides of it, and every planner below cuts its chunks to it.
+constexpr long kMaxGridY = 65535;
+// grid rows of a chunk's g_cols_inv launch: one per output slot -- (window, band, pair), or (group, band, pair) of an
+// integrated call, whose chunk holds whole groups of `integ` windows.  generic_pairs launches exactly this many.
+inline long cols_inv_grid_rows(long chunk, int n_bands, int n_pairs, int integ) {
+    const long nb = n_bands > 1 ? n_bands : 1, np = n_pairs > 0 ? n_pairs : 0, K = integ > 1 ? integ : 1;
+    return chunk * nb * np / K;
+}
+// `chunk` windows cut, in whole groups of `integ`, until that launch has at most kMaxGridY rows.  One group stays one
+// chunk even where its own n_bands * n_pairs slots are more (a pair list beyond 65535 pairs): nothing smaller can be
+// launched, and a group is never split.
+inline long cap_chunk_grid_rows(long chunk, int n_bands, int n_pairs, int integ) {
+    const long K = integ > 1 ? integ : 1;
+    const long per_group = cols_inv_grid_rows(K, n_bands, n_pairs, (int)K);
+    if (per_group <= 0 || cols_inv_grid_rows(chunk, n_bands, n_pairs, integ) <= kMaxGridY) return chunk;
+    const long groups = kMaxGridY / per_group > 1 ? kMaxGridY / per_group : 1;
+    return groups * K < chunk ? groups * K : chunk;
+}
 struct BandsPlan {
     long chunk = 0;          // real windows per chunk, >= 1
     long vwindows = 0;       // virtual windows of a full chunk: chunk * n_bands
@@ -397,7 +417,7 @@ inline BandsPlan plan_bands(long chunk, long n_windows, int n_bands, int n_buoys
         if (four_step) {
             const long per_win = ((long)n_buoys + nb * np) * L * 8;
             if (per_win > 0 && chunk > budget_bytes / per_win) chunk = budget_bytes / per_win;
-            if (np > 0 && chunk * nb * np > kMaxGridY) chunk = kMaxGridY / (nb * np);   // g_cols_inv: one grid row per slot
+            chunk = cap_chunk_grid_rows(chunk, (int)nb, (int)np, 1);   // g_cols_inv: one grid row per slot
         }
         if (chunk < 1) chunk = 1;
     }
@@ -624,6 +644,7 @@ inline RoutePlan plan_route(const RouteCaps& k, const RouteCall& a) {
         if (p.route == kRouteWinEo15 && k.ws_upw == 1) partial_round(12.6, 60.0, 0.14, 11, 0.85);
         p.n_head = W - p.n_tail;
         p.chunk = k.g_chunk;   // (of the partial round: plain or bounded calls only, integ = 1)
+        if ((1L << k.logL) > k.small_maxl) p.chunk = (int)cap_chunk_grid_rows(p.chunk, 1, a.n_pairs, 1);   // (it runs four-step)
         return p;
     }
     if (!a.weighted && k.wfused && !a.bounded) { p.route = kRouteWinFused; return p; }
@@ -635,6 +656,9 @@ inline RoutePlan plan_route(const RouteCaps& k, const RouteCall& a) {
     if (a.n_bands > 1) {
         chunk = (int)plan_bands(k.g_chunk, W, a.n_bands, k.n_buoys, a.n_pairs, 1L << k.logL, four_step, 0, 0, 0).chunk;
         if (a.integ > 1 && k.g_chunk >= a.integ) p.bands_chunk = chunk;
+    } else if (four_step) {
+        // one band: the same cap on g_cols_inv's grid rows that plan_bands puts on a banded chunk, in whole groups
+        chunk = (int)cap_chunk_grid_rows(chunk, 1, a.n_pairs, a.integ);
     }
     p.refused = integ_chunk(k, chunk, a.integ, four_step, &p.chunk);
     return p;
@@ -688,6 +712,8 @@ inline CafPlan plan_caf(const RouteCaps& k, const CafCall& a) {
         } else if (chunk * M >= kCafMaxVirtualWindows) {
             chunk = (kCafMaxVirtualWindows - 1) / M;
         }
+    } else if (four_step) {
+        chunk = cap_chunk_grid_rows(chunk, 1, a.n_pairs, a.integ);   // as plan_route: g_cols_inv's grid rows, whole groups
     }
     if (p.refused == kRouteOk) p.refused = integ_chunk(k, (int)chunk, a.integ, four_step, &p.chunk);
     p.out_elems = (size_t)(W / a.integ) * (size_t)M * a.n_pairs;

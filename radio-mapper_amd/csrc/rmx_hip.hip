@@ -973,7 +973,7 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     // slot -> group w0 / K + slot / P).  Otherwise K = 1: slot -> window w0 + slot / P, pair slot % P.  Banded and integrated:
     // the banded rows above left one product per virtual window, and the column pass sums the K products of (group, band)
     // where they lie, n_bands * P slots apart; a slot is then (row w0 / K * n_bands + slot / P, pair).
-    const int oslots = slots / call.integ;
+    const int oslots = (int)host::cols_inv_grid_rows(wc, nb, n_pairs, call.integ);   // the planner's count: it cut the chunk by it
     LagBounds lb = call.lb;
     lb.w0 = v0 / call.integ;   // (banded: the bounds are per virtual window; w0 is a multiple of K)
     lb.n_pairs = n_pairs;

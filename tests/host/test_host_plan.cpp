@@ -575,7 +575,68 @@ static void test_caf_invariants() {
     CHECK(n_plans > 100000);
 }
 
+// No planned four-step chunk launches g_cols_inv with more than kMaxGridY rows, or holds more spectra and products than
+// generic_chunk_windows' budget: plan_route and plan_caf, 2 ... 32 buoys, every four-step length, the default pair list
+// and custom ones, 1 ... 8 bands, groups of 1 ... 8 windows.  The cut is also the tightest: one more group would pass
+// the limit (or the ctx's chunk).
+static void test_grid_rows() {
+    CHECK(cols_inv_grid_rows(560, 1, 120, 1) == 67200 && cols_inv_grid_rows(4800, 1, 28, 2) == 67200);
+    CHECK(cols_inv_grid_rows(10, 3, 28, 2) == 420 && cols_inv_grid_rows(10, 0, 28, 0) == 280);
+    CHECK(cap_chunk_grid_rows(560, 1, 120, 1) == 546 && cap_chunk_grid_rows(546, 1, 120, 1) == 546);   // 16 buoys: 546 windows
+    CHECK(cap_chunk_grid_rows(4096, 1, 28, 1) == 2340 && cap_chunk_grid_rows(4096, 1, 28, 2) == 4096);   // 8 buoys: 2340
+    CHECK(cap_chunk_grid_rows(4800, 1, 28, 2) == 4680 && cap_chunk_grid_rows(4800, 1, 28, 7) == 4800);
+    CHECK(cap_chunk_grid_rows(64, 1, 70000, 1) == 1 && cap_chunk_grid_rows(64, 1, 70000, 4) == 4);       // one group is never split
+    CHECK(cap_chunk_grid_rows(3, 1, 70000, 4) == 3 && cap_chunk_grid_rows(64, 1, 0, 1) == 64);
+    long n_plans = 0, n_cut = 0;
+    for (int B = 2; B <= 32; ++B)
+        for (int logL = 9; logL <= 23; ++logL)
+            for (int custom : {0, 1, 2, 3})
+                for (int nb = 1; nb <= 8; ++nb)
+                    for (int K = 1; K <= 8; ++K) {
+                        const long L = 1L << logL, all = (long)B * (B - 1) / 2;
+                        const int P = custom == 0 ? (int)all : custom == 1 ? 1 : custom == 2 ? (int)(2 * all + 1) : 2000;
+                        RouteCaps k;
+                        k.n_cus = 256;  k.n_buoys = B;  k.generic = true;  k.logL = logL;
+                        k.small_maxl = logL <= 13 ? 256 : 8192;            // (option small_maxl lowered: the short lengths run four-step)
+                        k.g_chunk = (int)generic_chunk_windows(B, L, 1 << 20, kGenericBudgetBytes, 0);
+                        RouteCall a;
+                        a.n_windows = 8 * 3 * 5 * 7 * 64;  a.n_pairs = P;  a.all_pairs = custom == 0;  a.pairs_given = custom != 0;
+                        a.weighted = true;  a.bounded = true;  a.integ = K;  a.n_bands = nb;
+                        const RoutePlan p = plan_route(k, a);
+                        CafCall ca;
+                        ca.n_windows = a.n_windows;  ca.n_pairs = P;  ca.n_dopplers = 5;  ca.integ = K;  ca.n_bands = nb;
+                        const CafPlan cp = plan_caf(k, ca);
+                        CHECK(p.route == kRouteFourStep);
+                        for (int which = 0; which < 2; ++which) {
+                            const RouteRefusal refused = which ? cp.refused : p.refused;
+                            const long chunk = which ? cp.chunk : p.chunk;
+                            ++n_plans;
+                            if (refused != kRouteOk) { CHECK(K > 1 || (which && nb > 1)); continue; }
+                            CHECK(chunk >= K && chunk % K == 0 && chunk <= k.g_chunk);
+                            CHECK(cols_inv_grid_rows(chunk, nb, P, K) <= kMaxGridY);
+                            // (a list longer than the default one is not what the ctx's chunk was sized for, and one window
+                            // that is over the budget by itself still runs, alone)
+                            const long per_win = ((long)B + (nb > 1 ? (long)nb * P : all)) * L * 8;
+                            if ((P <= all || nb > 1) && per_win <= kGenericBudgetBytes) CHECK(per_win * chunk <= kGenericBudgetBytes);
+                            if (nb == 1) {
+                                const long more = chunk + K;
+                                CHECK(more > k.g_chunk || cols_inv_grid_rows(more, 1, P, K) > kMaxGridY);
+                                n_cut += chunk < k.g_chunk / K * K;
+                            }
+                        }
+                    }
+    CHECK(n_plans > 200000 && n_cut > 1000);
+    // the whole-window routes' partial round runs four-step too: 255 windows of a 640-pair list
+    RouteCaps k;
+    k.n_cus = 256;  k.n_buoys = 8;  k.generic = true;  k.logL = 14;  k.g_chunk = 4096;  k.wscr = true;  k.k8 = true;  k.ws_upw = 1;  k.ws_grid = 256;
+    RouteCall a;
+    a.n_windows = 256 + 40;  a.n_pairs = 640;  a.all_pairs = false;  a.pairs_given = true;
+    const RoutePlan p = plan_route(k, a);
+    CHECK(p.route == kRouteKWin8 && cols_inv_grid_rows(p.chunk, 1, 640, 1) <= kMaxGridY && p.chunk == 102);
+}
+
 int main() {
+    test_grid_rows();
     test_route_invariants();
     test_recorded_rows();
     test_recorded_caf_rows();
