@@ -33,8 +33,8 @@ template <bool U8>
 __global__ __launch_bounds__(1024) void d_fft_db(const void* __restrict__ iq, float* __restrict__ pdb,
                                                  const float2* __restrict__ tw, int logN) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
-    float2* x = reinterpret_cast<float2*>(dsm);
     const int N = 1 << logN, tid = threadIdx.x, nthr = blockDim.x;
+    float2* x = reinterpret_cast<float2*>(dsm + gen::DetFftLds::x_off);
     const long w = blockIdx.x;
     for (int n = tid; n < N; n += nthr) {
         if constexpr (U8) {
@@ -113,12 +113,13 @@ __global__ __launch_bounds__(1024) void d_peaks(const float* __restrict__ pdb, i
                                                float* __restrict__ confidence, float* __restrict__ floor_db) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
     const int N = 1 << logN, tid = threadIdx.x, nthr = blockDim.x;
-    float* p = reinterpret_cast<float*>(dsm);                                   // [N]
-    unsigned char* st = reinterpret_cast<unsigned char*>(p + N);                // [N] 0 none 1 undecided 2 kept 3 removed 4 new
-    unsigned short* cand = reinterpret_cast<unsigned short*>(st + N);           // [N/2] candidate positions
-    unsigned* hist = reinterpret_cast<unsigned*>(cand + N / 2);                 // [256]
-    unsigned* bc = hist + 256;                                                  // [8] scalars
-    unsigned* scan = bc + 8;                                                    // [nthr]
+    using Lay = gen::DetPeaksLds;                                               // the regions, one behind the other
+    float* p = reinterpret_cast<float*>(dsm + Lay::p_off);                      // [N]
+    unsigned char* st = reinterpret_cast<unsigned char*>(p + Lay::p_words(N));  // [N] 0 none 1 undecided 2 kept 3 removed 4 new
+    unsigned short* cand = reinterpret_cast<unsigned short*>(st + Lay::st_bytes(N));    // [N/2] candidate positions
+    unsigned* hist = reinterpret_cast<unsigned*>(cand + Lay::cand_halfwords(N));        // [256]
+    unsigned* bc = hist + Lay::kHistWords;                                      // [8] scalars
+    unsigned* scan = bc + Lay::kBcWords;                                        // [nthr]
     const long w = blockIdx.x;
     const float* src = pdb + w * N;
     for (int i = tid; i < N; i += nthr) { p[i] = src[i]; st[i] = 0; }

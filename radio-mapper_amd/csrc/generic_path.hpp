@@ -29,8 +29,14 @@
 //                    minimum SURVEY.md section 8d quotes.
 // Twiddles: W_R^k tables per row length computed in double on the host; the large W_L^(a*b) factor of
 // the four-step is the product of two table entries (a*b mod L split into high and low digits).
+// Dynamic LDS: no kernel here carves it with numbers of its own.  gen_geometry.hpp (HIP-free, shared with the launch
+// code and compiled by a CPU test) names every kernel family's regions -- SmallLds, RowsLds, ColsLds, FusedLds,
+// WFusedLds, WinPlan, Win14Lds -- and each kernel walks from region to region with the lengths stated there.  The thread
+// counts and pass plans (kGThreads, lp, rows_tpr, col_log_t, cols_threads, fused_*, FusedPlan, WinPlan) live there too.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "gen_geometry.hpp"
 
 #include <cmath>
 #include <type_traits>
@@ -41,10 +47,6 @@ namespace rmx {
 namespace gen {
 
 constexpr int kProdBatch = 4;      // spectrum-product loads in flight per thread (g_rows_inv)
-constexpr int kGThreads = 256;
-// threads per row of the row kernels: two threads per radix-16 group (the passes leave half of them idle, the
-// streaming loops use all: measured better than one thread per group on the 2048-point rows of cfg2)
-__host__ __device__ constexpr int rows_tpr(int R) { return (R >> 3) < kGThreads ? ((R >> 3) > 0 ? (R >> 3) : 1) : kGThreads; }
 
 __device__ __forceinline__ float2 g_cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -102,10 +104,6 @@ __device__ __forceinline__ void batched(int start, int end, int stride, LoadFn&&
     }
 }
 
-// LDS element index -> padded position: one complex of padding per 16 keeps the stride-16 accesses of the last
-// fused passes (each thread walks 16 neighbouring elements) on distinct banks: lane i's element 16 i + m sits at
-// 17 i + m, and 17 is odd.  Every access to a transform buffer goes through lp().
-__host__ __device__ constexpr long lp(long e) { return e + (e >> 4); }
 template <int M>
 __device__ __forceinline__ constexpr int brev_m(int k) {
     int r = 0;
@@ -130,9 +128,9 @@ __device__ __forceinline__ float2 tw_full(const float2* __restrict__ tw, int e, 
 }
 // Where a pass reads its group from and writes it to.  A group's first element has the (unpadded) index
 // E0 = (j << LOGT) | c, its m-th element sits o = m * (q << LOGT) further on.
-struct LdsIO {      // the transform buffer in LDS, padded by lp()
+struct LdsIO {      // the transform buffer in LDS, padded by lp() (gen_geometry.hpp)
     float2* x;
-    static __host__ __device__ constexpr int pos(int e) { return e + (e >> 4); }
+    static __host__ __device__ constexpr int pos(int e) { return lds_pos(e); }
     struct H {
         float2* p;
         // lp(E0 + o) = lp(E0) + o + (o >> 4): E0's 16-block has fewer than the stride's worth of elements in front
@@ -172,7 +170,7 @@ using TileInv = LdsIOFor<4, kTileFlatInv>;
 template <int BM>
 struct LdsIOA {
     float2* x;
-    static __host__ __device__ constexpr int pos(int e) { return e + ((e >> BM) << 4); }
+    static __host__ __device__ constexpr int pos(int e) { return lds_pos_a(e, BM); }
     struct H {
         float2* p;
         __device__ __forceinline__ float2 ld(int o) const { return p[o + ((o >> BM) << 4)]; }     // o: below 2^BM or a multiple of it
@@ -367,7 +365,7 @@ __device__ __forceinline__ void fft_dit_inv(float2* x, int logR, const float2* _
     dit_pass_m<LOGT>(logR - b, logR, logR, tw, tid, nthr, mid, last);
 }
 __device__ __forceinline__ void build_tw16(float2* t, const float2* __restrict__ tw, int logR, int tid, int nthr) {
-    for (int e = tid; e < 240; e += nthr) t[e] = tw_full(tw, ((e & 15) << (logR - 8)) * ((e >> 4) + 1), 1 << (logR - 1));
+    for (int e = tid; e < RowsLds::kTw16Entries; e += nthr) t[e] = tw_full(tw, ((e & 15) << (logR - 8)) * ((e >> 4) + 1), 1 << (logR - 1));
 }
 // in place in LDS, barrier behind the last pass too
 template <int LOGT = 0>
@@ -451,8 +449,8 @@ __global__ __launch_bounds__(1024) void g_fwd_small(const void* __restrict__ iq,
                                                          long first_item, float scale,
                                                          const float2* __restrict__ rot = nullptr, WT... wt_pack) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
-    float2* x = reinterpret_cast<float2*>(gsm);
     const int L = 1 << logL, tid = threadIdx.x, nthr = blockDim.x;
+    float2* x = reinterpret_cast<float2*>(gsm + SmallLds::x_off);
     const long item = first_item + blockIdx.x;
     for (int n = N + tid; n < L; n += nthr) x[lp(n)] = make_float2(0.f, 0.f);   // the zero-padded half
     batched<8>(tid, N, nthr,
@@ -503,10 +501,10 @@ __device__ __forceinline__ void pair_small_integ(const float2* __restrict__ spec
                                                  float* __restrict__ lag_frac, float* __restrict__ peak, LagBounds lb, int K,
                                                  BS... bs_pack) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
-    float2* x = reinterpret_cast<float2*>(gsm);
     const int L = 1 << logL, tid = threadIdx.x, nthr = blockDim.x;
-    float* sv = reinterpret_cast<float*>(gsm + (size_t)lp(L) * 8);
-    int* sk = reinterpret_cast<int*>(sv + nthr);
+    float2* x = reinterpret_cast<float2*>(gsm + SmallLds::x_off);
+    float* sv = reinterpret_cast<float*>(gsm + SmallLds::x_bytes(L));
+    int* sk = reinterpret_cast<int*>(sv + SmallLds::sv_words(nthr));
     const int gl = blockIdx.x / n_pairs, q = blockIdx.x % n_pairs;
     const GPair pr = pairs[q];
     int gr = gl;
@@ -613,10 +611,10 @@ __global__ __launch_bounds__(1024) void g_pair_small(const float2* __restrict__ 
     }
     constexpr bool BOUNDED = kHasBounds<LB...>, BANDED = kBanded<LB...>;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
-    float2* x = reinterpret_cast<float2*>(gsm);
     const int L = 1 << logL, tid = threadIdx.x, nthr = blockDim.x;
-    float* sv = reinterpret_cast<float*>(gsm + (size_t)lp(L) * 8);
-    int* sk = reinterpret_cast<int*>(sv + nthr);
+    float2* x = reinterpret_cast<float2*>(gsm + SmallLds::x_off);
+    float* sv = reinterpret_cast<float*>(gsm + SmallLds::x_bytes(L));
+    int* sk = reinterpret_cast<int*>(sv + SmallLds::sv_words(nthr));
     const int wl = blockIdx.x / n_pairs, q = blockIdx.x % n_pairs;
     const GPair pr = pairs[q];
     if constexpr (BANDED) {   // both spectra are the real window's; a bin outside the band loads nothing: its product is +0
@@ -712,14 +710,16 @@ __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, c
     const int tpr = LOGR > 0 ? rows_tpr(1 << LOGR) : (tpr_arg > 0 ? tpr_arg : rows_tpr(R));   // threads per row
     const int rpw = kGThreads / tpr;                                                   // rows per workgroup
     const int g = threadIdx.x / tpr, tid = threadIdx.x % tpr;
-    float2* x = reinterpret_cast<float2*>(gsm) + (long)g * lp(R);
+    static_assert(TW == !FWD, "rows_layout: the inverse rows carry the per-row tables");
+    if constexpr (LOGR > 0) static_assert(rows_layout(LOGR, rows_tpr(1 << LOGR), FWD).ok(), "g_rows' LDS");
+    float2* x = reinterpret_cast<float2*>(gsm + RowsLds::x_off) + (long)g * RowsLds::row_entries(R);
     // the W_R table goes to LDS (butterflies would otherwise fetch their twiddles
     // through the vector memory path, a dependent cache-latency access in the inner loop)
-    float2* twl = reinterpret_cast<float2*>(gsm) + (long)rpw * lp(R) + (TW ? (long)rpw * ((1 << (logR >> 1)) + (R >> (logR >> 1))) : 0);
+    float2* twl = reinterpret_cast<float2*>(gsm + RowsLds::x_off) + RowsLds::x_entries(R, rpw) + RowsLds::t_entries<TW>(logR, R, rpw);
     for (int k = threadIdx.x; k < (R >> 1); k += kGThreads) twl[k] = tw[k];
-    float2* tw16 = twl + (R >> 1);                // [15][16]: the inverse's q = 16 pass (fft_dit_inv)
+    float2* tw16 = twl + RowsLds::twl_entries(R);   // [15][16]: the inverse's q = 16 pass (fft_dit_inv)
     // (rows of 4096 go without: three workgroups of 52 KiB share a CU, and 2 KiB more make it two -- 5.46 -> 5.88 ms)
-    const bool own16 = !FWD && logR > 8 && logR < 12;
+    const bool own16 = !FWD && logR > RowsLds::kOwn16Above && logR < RowsLds::kOwn16Below;
     if (own16) build_tw16(tw16, tw, logR, threadIdx.x, kGThreads);
     static_assert((FWD && !TW && !PROD) || (!FWD && TW && PROD), "the two row passes of the four-step");
     const LdsIO lds{x};
@@ -758,7 +758,7 @@ __global__ __launch_bounds__(kGThreads) void g_rows(float2* __restrict__ data, c
     } else {
         // inverse rows: X_j conj(X_i) formed on load (the product never exists in HBM)
         const int a = logR >> 1, n1 = 1 << a, n2 = R >> a;
-        float2* t1 = reinterpret_cast<float2*>(gsm) + (long)(kGThreads / tpr) * lp(R) + (long)g * (n1 + n2);
+        float2* t1 = reinterpret_cast<float2*>(gsm + RowsLds::x_off) + RowsLds::x_entries(R, kGThreads / tpr) + (long)g * RowsLds::t_row_entries(logR, R);
         float2* t2 = t1 + n1;
         {   // W_L^(c*e) for this row's multiplier c and every exponent e < R = T1[e & (2^a - 1)] * T2[e >> a]
             const long c = (long)brev(rib, row_bits);
@@ -823,14 +823,15 @@ __global__ __launch_bounds__(kGThreads) void g_rows_anchor(float2* __restrict__ 
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     constexpr int logR = LOGR, R = 1 << LOGR, tpr = rows_tpr(R), rpw = kGThreads / tpr, EPT = R / tpr;   // elements per thread
     const int g = threadIdx.x / tpr, tid = threadIdx.x % tpr;
-    float2* x = reinterpret_cast<float2*>(gsm) + (long)g * lp(R);
+    static_assert(rows_layout(LOGR, tpr, false).ok(), "g_rows_anchor's LDS");   // the inverse rows' layout
+    float2* x = reinterpret_cast<float2*>(gsm + RowsLds::x_off) + (long)g * RowsLds::row_entries(R);
     constexpr int a = logR >> 1, n1 = 1 << a, n2 = R >> a;
-    float2* t1 = reinterpret_cast<float2*>(gsm) + (long)rpw * lp(R) + (long)g * (n1 + n2);
+    float2* t1 = reinterpret_cast<float2*>(gsm + RowsLds::x_off) + RowsLds::x_entries(R, rpw) + (long)g * RowsLds::t_row_entries(logR, R);
     float2* t2 = t1 + n1;
-    float2* twl = reinterpret_cast<float2*>(gsm) + (long)rpw * lp(R) + (long)rpw * (n1 + n2);
+    float2* twl = reinterpret_cast<float2*>(gsm + RowsLds::x_off) + RowsLds::x_entries(R, rpw) + RowsLds::t_entries<true>(logR, R, rpw);
     for (int k = threadIdx.x; k < (R >> 1); k += kGThreads) twl[k] = tw[k];
-    float2* tw16 = twl + (R >> 1);
-    constexpr bool own16 = logR > 8 && logR < 12;
+    float2* tw16 = twl + RowsLds::twl_entries(R);
+    constexpr bool own16 = RowsLds::own16(false, logR);
     if constexpr (own16) build_tw16(tw16, tw, logR, threadIdx.x, kGThreads);
     // (the 256-block pass's twiddles in registers instead of this table: 8 buoys x 16384 1.36 -> 1.43 ms, cfg5 +-0: not used)
     const int nrb = n_rows / rpw, na = n_buoys - 1, bid = blockIdx.x;
@@ -915,23 +916,7 @@ __global__ __launch_bounds__(kGThreads) void g_rows_anchor(float2* __restrict__ 
 // stages in a first radix-8 / 4 / 2 pass (8 then 4 for five stages).
 // The kernel is compiled per row length (LOGR = 9..12): block sizes, strides and trip counts are constants, LDS
 // offsets immediates.
-__host__ __device__ constexpr int fused_pass_m(int left) {
-    return (left & 3) == 0 ? 4 : ((left & 3) == 1 && left > 1 ? 3 : (left & 3));
-}
-// Twiddles: every pass (block size 2^B, M stages) has its own table [k = 1 .. 2^M - 1][l < 2^(B-M)] =
-// W_R^(l k 2^(LOGR-B)) in LDS, one behind the other from the first pass (B = LOGR) down; the inverse's passes are
-// the forward's in reverse order and use the same tables conjugated.  Lanes read consecutive entries (the
-// strided reads of a shared W_R table were 2..16-way bank conflicts: half of this kernel's LDS cycles).
-__host__ __device__ constexpr int fused_tab_off(int logR, int B) {      // offset of pass B's table, in entries
-    int cur = logR, acc = 0;
-    while (cur > B) {
-        const int M = fused_pass_m(cur - 4);
-        acc += ((1 << M) - 1) << (cur - M);
-        cur -= M;
-    }
-    return acc;
-}
-__host__ __device__ constexpr int fused_tab_total(int logR) { return fused_tab_off(logR, 4); }
+// (fused_pass_m, fused_tab_off / fused_tab_total: the passes and their twiddle tables, gen_geometry.hpp)
 template <int LOGR, int B>
 __device__ __forceinline__ void fused_tab_build(float2* tab, const float2* __restrict__ tw) {
     if constexpr (B > 4) {
@@ -949,13 +934,12 @@ __device__ __forceinline__ void fused_tab_build(float2* tab, const float2* __res
 // once, one HBM latency per unit instead of one per row, in the registers that later hold the spectra.
 // LDS layouts (LdsIOA above): the first forward pass writes, the one middle pass (q = 16, blocks of 2^BM) reads
 // layout A; the middle pass writes and the 16-neighbour butterfly reads lp(); the inverse the other way round.
+// FusedPlan<LOGR> (gen_geometry.hpp) with the layout-A accessor: the unit-stride layout where its blocks line up with
+// lp()'s (LdsIOA); rows of 512 keep lp() throughout
 template <int LOGR>
-struct FusedPlan {
-    static constexpr int M0 = fused_pass_m(LOGR - 4), BM = LOGR - M0, MM = BM - 4;      // first pass, middle pass
-    static_assert(MM >= 1 && MM <= 4 && fused_pass_m(BM - 4) == MM, "rows of 2^9 .. 2^12: first pass, one middle pass, 16-point blocks");
-    // the unit-stride layout where its blocks line up with lp()'s (LdsIOA); rows of 512 keep lp() throughout
-    using IOA = std::conditional_t<BM == 8, LdsIOA<8>, LdsIO>;
-    static constexpr int buf = LdsIO::pos(1 << LOGR) > IOA::pos(1 << LOGR) ? LdsIO::pos(1 << LOGR) : IOA::pos(1 << LOGR);
+struct FusedIO : FusedPlan<LOGR> {
+    using IOA = std::conditional_t<FusedPlan<LOGR>::kLayoutA, LdsIOA<8>, LdsIO>;
+    static_assert(FusedPlan<LOGR>::buf >= LdsIO::pos(1 << LOGR) && FusedPlan<LOGR>::buf >= IOA::pos(1 << LOGR), "the buffer holds both layouts");
 };
 // Twiddle providers of the helpers below: a pointer to the passes' LDS tables (fused_tab_build), or FusedTw -- the
 // thread's own twiddles of the first / last pass (a) and of the middle pass (m) in registers (rows of 4096: one
@@ -966,7 +950,7 @@ struct FusedTw {
 };
 template <int LOGR, class TW>
 __device__ __forceinline__ void dif_first_from_regs(float2* x, const TW& tab, int tid, const float2 (&raw)[16]) {
-    using P = FusedPlan<LOGR>;
+    using P = FusedIO<LOGR>;
     constexpr int M = P::M0, RAD = 1 << M, NIT = 16 / RAD, q = 1 << (LOGR - M), nthr = 1 << (LOGR - 4);
     const typename P::IOA io{x};
 #pragma unroll
@@ -990,7 +974,7 @@ __device__ __forceinline__ void dif_first_from_regs(float2* x, const TW& tab, in
 // the middle pass and the 16-point blocks, whose butterfly ends in registers
 template <int LOGR, class TW>
 __device__ __forceinline__ void fft_dif_rest_to_regs(float2* x, const TW& tab, int tid, float2 (&out)[16]) {
-    using P = FusedPlan<LOGR>;
+    using P = FusedIO<LOGR>;
     const LdsIO nb{x};
     if constexpr (std::is_same_v<TW, FusedTw>)
         dif_pass<P::MM, 0, 3>(LOGR, P::BM, tab.m, tid, 1 << (LOGR - 4), typename P::IOA{x}, nb);
@@ -1007,7 +991,7 @@ __device__ __forceinline__ void fft_dif_rest_to_regs(float2* x, const TW& tab, i
 // `last`: where the last pass writes (default: the buffer, layout A)
 template <int LOGR, class TW, class Last>
 __device__ __forceinline__ void fft_dit_inv_from_regs(float2* x, const TW& tab, int tid, float2 (&v)[16], const Last& last) {
-    using P = FusedPlan<LOGR>;
+    using P = FusedIO<LOGR>;
     const LdsIO nb{x};
     const typename P::IOA io{x};
 #pragma unroll
@@ -1030,17 +1014,13 @@ __device__ __forceinline__ void fft_dit_inv_from_regs(float2* x, const TW& tab, 
 }
 template <int LOGR, class TW>
 __device__ __forceinline__ void fft_dit_inv_from_regs(float2* x, const TW& tab, int tid, float2 (&v)[16]) {
-    fft_dit_inv_from_regs<LOGR>(x, tab, tid, v, typename FusedPlan<LOGR>::IOA{x});
+    fft_dit_inv_from_regs<LOGR>(x, tab, tid, v, typename FusedIO<LOGR>::IOA{x});
 }
 template <int NB>
 __device__ __forceinline__ void constexpr_pair(int ij, const float2 (&S)[NB][16], float2 (&v)[16]) {
     const int i = ij / NB, j = ij % NB;       // constant after unrolling
 #pragma unroll
     for (int k = 0; k < 16; ++k) v[k] = g_cmulc(S[j][k], S[i][k]);
-}
-// rows of 4096, default plan, at most 3 buoys: the passes' twiddles live in registers (FusedTw)
-__host__ __device__ constexpr bool fused_tw_regs(int nb, int logR, bool def) {
-    return def && logR == 12 && nb <= 3;
 }
 template <int NB, int LOGR, bool DEF = false>      // DEF: the default plan (all pairs i < j in order), pair loop unrolled
 __global__ __launch_bounds__(kGThreads, 2) void g_rows_fused(const float2* __restrict__ cols, float2* __restrict__ prod,
@@ -1051,14 +1031,15 @@ __global__ __launch_bounds__(kGThreads, 2) void g_rows_fused(const float2* __res
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     constexpr int R = 1 << LOGR, tpr = R >> 4, upw = kGThreads / tpr;   // threads per row, (window, rib) units per workgroup
     constexpr bool one_wave = tpr <= 64;                                // a row's threads sit in one wave: no workgroup barriers (xsync)
-    using P = FusedPlan<LOGR>;
+    using P = FusedIO<LOGR>;
     constexpr int M0 = P::M0;                                           // stages of the forward rows' first pass
     constexpr int a = LOGR >> 1, n1 = 1 << a, n2 = R >> a;
     const int g = threadIdx.x / tpr, tid = threadIdx.x % tpr;
-    float2* x = reinterpret_cast<float2*>(gsm) + g * P::buf;
-    float2* t1 = reinterpret_cast<float2*>(gsm) + upw * P::buf + g * (n1 + n2);
-    float2* t2 = t1 + n1;
     constexpr bool TWREG = fused_tw_regs(NB, LOGR, DEF);
+    static_assert(fused_layout(LOGR, TWREG).ok() && FusedLds::upw(LOGR) == upw && FusedLds::buf_entries(LOGR) == P::buf, "g_rows_fused's LDS");
+    float2* x = reinterpret_cast<float2*>(gsm + FusedLds::x_off) + g * FusedLds::buf_entries(LOGR);
+    float2* t1 = reinterpret_cast<float2*>(gsm + FusedLds::x_off) + FusedLds::x_entries(LOGR) + g * FusedLds::t_row_entries(LOGR);
+    float2* t2 = t1 + n1;
     using TwSrc = std::conditional_t<TWREG, FusedTw, const float2*>;
     TwSrc twl;
     if constexpr (TWREG) {
@@ -1069,7 +1050,7 @@ __global__ __launch_bounds__(kGThreads, 2) void g_rows_fused(const float2* __res
             twl.m.w[k - 1] = tw_full(tw, ((tid & 15) << (LOGR - P::BM)) * k, R >> 1);        // middle pass: l = tid & 15
         }
     } else {
-        float2* tl_ = reinterpret_cast<float2*>(gsm) + upw * (P::buf + n1 + n2);
+        float2* tl_ = reinterpret_cast<float2*>(gsm + FusedLds::x_off) + (FusedLds::x_entries(LOGR) + FusedLds::t_entries(LOGR));
         fused_tab_build<LOGR, LOGR>(tl_, tw);
         twl = tl_;
     }
@@ -1214,28 +1195,27 @@ __global__ __launch_bounds__(kGThreads, 2) void g_win_fused(const void* __restri
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     constexpr int R = 1 << LOGR, N = R >> 1, tpr = R >> 4, upw = kGThreads / tpr;   // threads per window, windows per workgroup
     constexpr bool one_wave = tpr <= 64;                                            // a window's threads sit in one wave
-    using P = FusedPlan<LOGR>;
+    using P = FusedIO<LOGR>;
     constexpr int M0 = P::M0;
     const int g = threadIdx.x / tpr, tid = threadIdx.x % tpr;
-    float2* x = reinterpret_cast<float2*>(gsm) + g * P::buf;
     constexpr bool TWREG = fused_tw_regs(NB, LOGR, DEF);
+    static_assert(wfused_layout(LOGR, TWREG).ok() && WFusedLds::buf_entries(LOGR) == P::buf, "g_win_fused's LDS");
+    float2* x = reinterpret_cast<float2*>(gsm + WFusedLds::x_off) + g * WFusedLds::buf_entries(LOGR);
     using TwSrc = std::conditional_t<TWREG, FusedTw, const float2*>;
     TwSrc twl;
-    float* sv;
+    float2* tl_ = reinterpret_cast<float2*>(gsm + WFusedLds::x_off) + WFusedLds::x_entries(LOGR);   // the tables' region (empty under TWREG)
+    float* sv = reinterpret_cast<float*>(tl_ + WFusedLds::tab_entries(LOGR, TWREG));
     if constexpr (TWREG) {
 #pragma unroll
         for (int k = 1; k < 16; ++k) {
             twl.a.w[k - 1] = tw_full(tw, tid * k, R >> 1);
             twl.m.w[k - 1] = tw_full(tw, ((tid & 15) << (LOGR - P::BM)) * k, R >> 1);
         }
-        sv = reinterpret_cast<float*>(reinterpret_cast<float2*>(gsm) + upw * P::buf);
     } else {
-        float2* tl_ = reinterpret_cast<float2*>(gsm) + upw * P::buf;
         fused_tab_build<LOGR, LOGR>(tl_, tw);
         twl = tl_;
-        sv = reinterpret_cast<float*>(tl_ + fused_tab_total(LOGR));
     }
-    int* sk = reinterpret_cast<int*>(sv + 8);
+    int* sk = reinterpret_cast<int*>(sv + WFusedLds::kSvWords);
     __syncthreads();
     const long w = (long)blockIdx.x * upw + g;
     const bool live = w < n_windows;
@@ -1341,25 +1321,7 @@ __global__ __launch_bounds__(kGThreads, 2) void g_win_fused(const void* __restri
 // (kTwGlobalFrom = 99), the second pass's not in registers.
 // Pass order: radix 16 from the whole window down (DIF) while more than four stages remain, the left-over 1..4
 // stages last, on the thread's 16 neighbouring elements: they end in registers, and the inverse starts there.
-template <int LOGR>
-struct WinPlan {
-    static constexpr int R = 1 << LOGR, tpr = R >> 4;
-    static constexpr int ML = ((LOGR - 1) & 3) + 1, RADL = 1 << ML, NITL = 16 / RADL;   // the neighbour pass
-    static constexpr int NP = (LOGR - ML) / 4;                                            // radix-16 passes, blocks LOGR, LOGR - 4, ..
-    static constexpr int kTwRegFrom = 9, kTwGlobalFrom = 99;
-    static constexpr bool TW1REG = LOGR >= kTwRegFrom && LOGR < kTwGlobalFrom;                  // first pass's twiddles in registers
-    static constexpr bool TW1GLOBAL = LOGR >= kTwGlobalFrom;                            // ... or read from the global table
-    static constexpr bool TW2REG = false;                                                 // the second pass's too: settled off
-    static constexpr int thr = tpr < kGThreads ? kGThreads : tpr, upw = thr / tpr;         // threads, windows per workgroup
-    static constexpr int tab_off(int b) {                                                 // entries in front of pass b's LDS table
-        int acc = 0;
-        for (int c = LOGR; c > b; c -= 4)
-            if (!(c == LOGR && (TW1REG || TW1GLOBAL)) && !(c == LOGR - 4 && TW2REG)) acc += 15 << (c - 4);
-        return acc;
-    }
-    static constexpr int tab_total = tab_off(ML);
-    static constexpr size_t lds_bytes = ((size_t)upw * lp(R) + tab_total + 16) * 8;
-};
+// (WinPlan<LOGR>: gen_geometry.hpp)
 // The transforms of those kernels: one window's R / 16 threads, buffer x (lp() layout), the passes' twiddles
 template <int LOGR>
 struct WinXf {
@@ -1484,10 +1446,10 @@ __global__ __launch_bounds__(WinPlan<LOGR>::thr) void g_win_scr(const void* __re
     constexpr int R = P::R, N = R >> 1, tpr = P::tpr, upw = P::upw;
     constexpr bool one_wave = tpr <= 64;
     const int g = threadIdx.x / tpr, tid = threadIdx.x % tpr;
-    float2* x = reinterpret_cast<float2*>(gsm) + g * lp(R);
-    float2* tab = reinterpret_cast<float2*>(gsm) + upw * lp(R);
-    float* sv = reinterpret_cast<float*>(tab + P::tab_total);
-    int* sk = reinterpret_cast<int*>(sv + 16);
+    float2* x = reinterpret_cast<float2*>(gsm + P::x.off + g * P::x_stride);
+    float2* tab = reinterpret_cast<float2*>(gsm + P::tab.off);
+    float* sv = reinterpret_cast<float*>(gsm + P::sv.off);
+    int* sk = reinterpret_cast<int*>(gsm + P::sk.off);
     WinXf<LOGR> xf{x, tab, tw, {}, {}, tid};
     xf.setup();
     __syncthreads();
@@ -1595,12 +1557,13 @@ __global__ __launch_bounds__(512, 2) void g_win_scr14(const void* __restrict__ i
                                                    float* __restrict__ peak) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     constexpr int LOGR = 14, R = 1 << LOGR, N = R >> 1, NT = 512, Q = R >> 4;      // Q = 1024 butterflies per radix-16 pass
-    constexpr int off10 = 0, off6 = 15 * 64, tab_total = 15 * 64 + 15 * 4;          // LDS tables of the passes over blocks of 2^10, 2^6
+    using Lay = Win14Lds;
+    constexpr int off10 = Lay::off10, off6 = Lay::off6;                             // LDS tables of the passes over blocks of 2^10, 2^6
     const int tid = threadIdx.x;
-    float2* x = reinterpret_cast<float2*>(gsm);
-    float2* tab = x + lp(R);
-    float* sv = reinterpret_cast<float*>(tab + tab_total);
-    int* sk = reinterpret_cast<int*>(sv + 16);
+    float2* x = reinterpret_cast<float2*>(gsm + Lay::x.off);
+    float2* tab = reinterpret_cast<float2*>(gsm + Lay::tab.off);
+    float* sv = reinterpret_cast<float*>(gsm + Lay::sv.off);
+    int* sk = reinterpret_cast<int*>(gsm + Lay::sk.off);
     for (int e = tid; e < 15 * 64; e += NT) tab[off10 + e] = tw_full(tw, ((e & 63) << 4) * ((e >> 6) + 1), R >> 1);
     for (int e = tid; e < 15 * 4; e += NT) tab[off6 + e] = tw_full(tw, ((e & 3) << 8) * ((e >> 2) + 1), R >> 1);
     TwRegs tw1[2];
@@ -1762,7 +1725,7 @@ __global__ __launch_bounds__(512, 2) void g_win_scr14(const void* __restrict__ i
 // back in place of a transpose + row pass + transpose.
 // columns per tile: 16 (128-byte row segments), or 8 when L1 = 1024 so that two 64 KiB tiles share a CU and
 // one workgroup's loads and stores overlap the other's butterflies (measured: cfg2 8.7 -> 8.1 ms)
-__host__ __device__ constexpr int col_log_t(int l1) { return l1 >= 10 ? 3 : 4; }
+// (col_log_t: gen_geometry.hpp)
 // forward: zero-padded window -> out[k1'][n2] = W_L^(n2*k1) * sum_n1 x[n1][n2] W_L1^(n1*k1)
 //   (k1' = bit-reversed k1).  grid (L2/T, items); only the rows n1 < L1/2 are non-zero and read.
 // Workgroup -> tile: the dispatcher deals consecutive workgroups round-robin to the 8 XCDs, so with tile =
@@ -1771,10 +1734,6 @@ __host__ __device__ constexpr int col_log_t(int l1) { return l1 >= 10 ? 3 : 4; }
 // adjacent segments of the same rows together.
 __device__ __forceinline__ int xcd_tile(int bid, int n) {
     return (n & 7) == 0 ? (bid & 7) * (n >> 3) + (bid >> 3) : bid;
-}
-// threads of a column kernel: one radix-16 work item per thread and pass, 64 .. 1024
-__host__ __device__ constexpr int cols_threads(int l1, int log_t) {
-    return ((1 << l1) << log_t) / 16 >= 1024 ? 1024 : (((1 << l1) << log_t) / 16 < 64 ? 64 : ((1 << l1) << log_t) / 16);
 }
 // L1C > 0: the column length (and with it the thread count) as compile-time constants
 template <bool U8, int kColLogT, int L1C = 0>
@@ -1785,17 +1744,18 @@ __global__ __launch_bounds__(1024) void g_cols_fwd(const void* __restrict__ iq, 
                                                    const float2* __restrict__ rot = nullptr) {
     constexpr int kColT = 1 << kColLogT;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
-    float2* x = reinterpret_cast<float2*>(gsm);
     const int l1 = L1C > 0 ? L1C : l1_arg;
+    if constexpr (L1C > 0) static_assert(cols_layout(L1C, kColLogT).ok(), "the column kernels' LDS");
+    float2* x = reinterpret_cast<float2*>(gsm + ColsLds::x_off);
     const int L1 = 1 << l1, L2 = 1 << l2, tid = threadIdx.x, nthr = L1C > 0 ? cols_threads(L1C, kColLogT) : (int)blockDim.x;
     const long L = (long)L1 << l2, N = L >> 1;
     const int tile = xcd_tile(blockIdx.x, gridDim.x), c0 = tile * kColT;
     const long item = first_item + blockIdx.y;
     // per-column twiddle tables W_L^(n2*e) = T1[e & (2^a-1)] * T2[e >> a] (n2*e < L: no reduction) and the W_L1 table
     const int a = l1 >> 1, na = 1 << a, nb = L1 >> a;
-    float2* tab = x + lp((long)L1 << kColLogT);                 // [T][na + nb + 1]: an odd stride, or the 16 columns' reads of one
-    constexpr int kTabPad = 1;                                //   entry sit on two banks (8-way conflict)
-    float2* twl = tab + (long)kColT * (na + nb + kTabPad);
+    float2* tab = x + ColsLds::x_entries(L1, kColLogT);          // [T][na + nb + 1]: an odd stride, or the 16 columns' reads of one
+    constexpr int kTabPad = kColTabPad;                          //   entry sit on two banks (8-way conflict)
+    float2* twl = tab + ColsLds::tab_entries(l1, L1, kColLogT);
     for (int k = tid; k < (L1 >> 1); k += nthr) twl[k] = tw[k];
     for (int idx = tid; idx < kColT * (na + nb); idx += nthr) {
         const int c = idx / (na + nb), e = idx % (na + nb);
@@ -1885,15 +1845,16 @@ __device__ __forceinline__ void cols_inv_integ(const float2* __restrict__ in, co
                                                GTile* __restrict__ rec, float* __restrict__ halo, LagBounds lb, int K, int nb) {
     constexpr int kColT = 1 << kColLogT;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
-    float2* x = reinterpret_cast<float2*>(gsm);
     const int l1 = L1C > 0 ? L1C : l1_arg;
+    if constexpr (L1C > 0) static_assert(cols_layout(L1C, kColLogT).ok(), "the column kernels' LDS");
+    float2* x = reinterpret_cast<float2*>(gsm + ColsLds::x_off);
     const int L1 = 1 << l1, L2 = 1 << l2, tid = threadIdx.x, nthr = L1C > 0 ? cols_threads(L1C, kColLogT) : (int)blockDim.x;
     const long L = (long)L1 << l2;
     const int N = (int)(L >> 1);
     const int tile = xcd_tile(blockIdx.x, gridDim.x), c0 = tile * kColT;
-    float2* twl = x + lp((long)L1 << kColLogT) + (long)kColT * ((1 << (l1 >> 1)) + (L1 >> (l1 >> 1)) + 1);
-    float* sv = reinterpret_cast<float*>(x + lp((long)L1 << kColLogT));
-    int* sk = reinterpret_cast<int*>(sv + 16);
+    float2* twl = x + ColsLds::x_entries(L1, kColLogT) + ColsLds::tab_entries(l1, L1, kColLogT);
+    float* sv = reinterpret_cast<float*>(x + ColsLds::x_entries(L1, kColLogT));
+    int* sk = reinterpret_cast<int*>(sv + ColsLds::kSvWords);
     for (int k = tid; k < (L1 >> 1); k += nthr) twl[k] = tw[k];
     __syncthreads();
     const int elems = L1 << kColLogT;
@@ -1976,15 +1937,16 @@ __global__ __launch_bounds__(1024) void g_cols_inv(const float2* __restrict__ in
     constexpr bool BOUNDED = sizeof...(LB) > 0;
     constexpr int kColT = 1 << kColLogT;
     extern __shared__ __attribute__((aligned(16))) char gsm[];
-    float2* x = reinterpret_cast<float2*>(gsm);
     const int l1 = L1C > 0 ? L1C : l1_arg;
+    if constexpr (L1C > 0) static_assert(cols_layout(L1C, kColLogT).ok(), "the column kernels' LDS");
+    float2* x = reinterpret_cast<float2*>(gsm + ColsLds::x_off);
     const int L1 = 1 << l1, L2 = 1 << l2, tid = threadIdx.x, nthr = L1C > 0 ? cols_threads(L1C, kColLogT) : (int)blockDim.x;
     const long L = (long)L1 << l2;
     const int N = (int)(L >> 1);
     const int tile = xcd_tile(blockIdx.x, gridDim.x), c0 = tile * kColT;
-    float2* twl = x + lp((long)L1 << kColLogT) + (long)kColT * ((1 << (l1 >> 1)) + (L1 >> (l1 >> 1)) + 1);
-    float* sv = reinterpret_cast<float*>(x + lp((long)L1 << kColLogT));   // 16 + 16 words in the (unused here) table region
-    int* sk = reinterpret_cast<int*>(sv + 16);
+    float2* twl = x + ColsLds::x_entries(L1, kColLogT) + ColsLds::tab_entries(l1, L1, kColLogT);
+    float* sv = reinterpret_cast<float*>(x + ColsLds::x_entries(L1, kColLogT));   // 16 + 16 words in the (unused here) table region
+    int* sk = reinterpret_cast<int*>(sv + ColsLds::kSvWords);
     for (int k = tid; k < (L1 >> 1); k += nthr) twl[k] = tw[k];
     const float2* src = in + (long)blockIdx.y * L;
     float best = -1.0f;

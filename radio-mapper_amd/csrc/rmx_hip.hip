@@ -7,7 +7,9 @@
 // N = 4096 runs the fused kernel k_win (kwin.hpp) or, per chunk of windows on one stream, the two families of
 // pair4096.hpp: k_fwd (forward spectra -> HBM/L2 scratch) and k_pair_* (product, inverse transform, peak search).  The
 // other lengths run generic_path.hpp / win_eo.hpp / kwin8k.hpp / kwin16k.hpp.  host_plan.hpp chooses among them per
-// call; every launch goes through rmx::launch below.
+// call; every launch goes through rmx::launch below.  The generic path's thread counts, its four-step split and the
+// dynamic-LDS bytes of its launches are not computed here: generic_init asks gen::make_geometry (gen_geometry.hpp, the
+// header the kernels take their LDS layouts from) once and keeps the answer in rmx_ctx::geo.
 // No MFMA (not a contraction), no library FFT: every kernel is hand written for wave64 / LDS.
 #include <hip/hip_runtime.h>
 
@@ -114,7 +116,6 @@ struct rmx_ctx {
         decltype(&rmx::gen::g_rows_fused<2, 9>) fused = nullptr;       // four-step: both row passes in one kernel (n_buoys <= 4)
         decltype(&rmx::gen::g_rows_fused<2, 9>) fused_def = nullptr;   // the same for the default plan (pair loop unrolled)
         decltype(&rmx::gen::g_win_fused<2, 9, false, false>) wf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [default plan][u8]
-        size_t wf_lds[2] = {0, 0};                                                                      // [default plan]
         decltype(&rmx::gen::g_win_scr<9, false>) ws[2] = {nullptr, nullptr};    // [u8]: g_win_scr<log2 L> or g_win_scr14
         decltype(&rmx::gen::g_win_eo15<false>) ws15[2] = {nullptr, nullptr};    // [u8]: N = 16384 (one more table)
         size_t ws_lds = 0;                                                      // of ws or ws15, whichever is there
@@ -154,7 +155,8 @@ struct rmx_ctx {
     rmx::Pinned<char> h_out{&mem};      // pinned staging of small host-pointer results (fetch_out)
     // generic path (n_samples != 4096): see generic_path.hpp
     bool generic = false;
-    int g_logL = 0, g_logL1 = 0, g_logL2 = 0, g_lo_bits = 0, g_chunk = 0;
+    rmx::gen::Geometry geo;    // lengths, split, thread counts and LDS bytes of every launch (gen_geometry.hpp), fixed by generic_init
+    int g_chunk = 0;
     GenericKernels gk;
     bool g_fused = false;      // four-step: both row passes in g_rows_fused (n_buoys <= 4, plain batches)
     bool g_fused_always = false;
@@ -523,27 +525,6 @@ static int quality_chunk(rmx_ctx* c, const XcorrCall& call, const SpecView& sv, 
     });
 }
 
-// windows up to this zero-padded length run with the whole transform in LDS (128 KiB of the 160)
-// (L = 16384 -- N = 8192, the reference's iq_stream_client capture length -- is better off in the four-step path: one
-// 128 KiB transform per CU leaves nothing to overlap with; 0.77 -> 0.60 ms for 3 buoys x 1024 windows)
-static long gen_small_max_l(const rmx_ctx* c) { return c->knobs.get_or("small_maxl", 8192L); }
-#define kGenSmallMaxL gen_small_max_l(c)
-static int gen_small_threads(long L) { const long t = L >> 4; return t >= 1024 ? 1024 : (t < 64 ? 64 : (int)t); }   // one radix-16 group per thread and pass
-// dynamic LDS of the four-step kernels
-static int gen_rows_tpr(const rmx_ctx* c, int R) {
-    int t = gen::rows_tpr(R);
-    long v;
-    if (c->knobs.get("rows_tpr", &v) && v >= 1 && v <= gen::kGThreads && (v & (v - 1)) == 0 && v <= R) t = (int)v;
-    return t;
-}
-static size_t gen_rows_lds(const rmx_ctx* c, int R) {   // rows + per-row twiddle tables (TW passes)
-    const int tpr = gen_rows_tpr(c, R);
-    int logR = 0;
-    while ((1 << logR) < R) ++logR;
-    const int a = logR >> 1;
-    return ((size_t)(gen::kGThreads / tpr) * ((size_t)gen::lp(R) + (1 << a) + (R >> a)) + (size_t)(R >> 1) + (R < 4096 ? 240 : 0)) * 8;   // + W_R table + the q = 16 pass's own
-}
-
 // ---- the selection tables: a run-time length -> the instantiation compiled for it (with_one_of: a length outside a
 // list gets the list's last entry; 0 stands for the run-time-length instantiation) -----------------------------------
 // column kernels with the column length compiled in (16-column tiles, the default thread count), else the run-time ones
@@ -591,13 +572,6 @@ static auto wfused_fn(int nb, int logR) {                   // g_win_fused<n_buo
         return with_one_of<9, 10, 11, 12>(logR, [](auto R) { return &gen::g_win_fused<decltype(NB)::value, decltype(R)::value, DEF, U8>; });
     });
 }
-static int fused_plan_buf(int logR) {
-    return with_one_of<9, 10, 11, 12>(logR, [](auto R) { return (int)gen::FusedPlan<decltype(R)::value>::buf; });
-}
-static size_t gen_wfused_lds(int logR, bool tw_regs) {     // transform buffers + the passes' twiddle tables + argmax words
-    const int tpr = (1 << logR) >> 4, upw = gen::kGThreads / tpr;
-    return ((size_t)upw * fused_plan_buf(logR) + (size_t)(tw_regs ? 0 : gen::fused_tab_total(logR)) + 8) * 8;
-}
 template <bool U8>
 static auto wscr_fn(int logR) {                             // g_win_scr<log2 L, uint8 input>
     return with_one_of<9, 10, 11, 12, 13, 14>(logR, [](auto R) { return &gen::g_win_scr<decltype(R)::value, U8>; });
@@ -608,33 +582,14 @@ static void wscr_shape(int logR, int* thr, int* upw, size_t* lds) {
         *thr = Plan::thr;  *upw = Plan::upw;  *lds = Plan::lds_bytes;
     });
 }
-static size_t gen_fused_lds(int R, bool tw_regs = false) {   // g_rows_fused: R/16 threads per row (tw_regs: no twiddle tables)
-    int logR = 0;
-    while ((1 << logR) < R) ++logR;
-    const int a = logR >> 1, tpr = R >> 4, upw = gen::kGThreads / (tpr > 0 ? tpr : 1);
-    return ((size_t)upw * ((size_t)fused_plan_buf(logR) + (1 << a) + (R >> a)) + (size_t)(tw_regs ? 0 : gen::fused_tab_total(logR))) * 8;   // + the passes' twiddle tables
-}
-static int host_col_log_t(const rmx_ctx* c, int l1) {   // gen::col_log_t, or the "col_logt" option (3 | 4) for experiments
-    return (int)c->knobs.get_or("col_logt", gen::col_log_t(l1));
-}
-static size_t gen_cols_lds(const rmx_ctx* c, int l1) {  // [L1][T] tile + T per-column twiddle tables
-    const int a = l1 >> 1, T = 1 << host_col_log_t(c, l1);
-    return ((size_t)gen::lp((long)(1 << l1) * T) + (size_t)T * ((1 << a) + ((1 << l1) >> a) + 1) + (size_t)((1 << l1) >> 1)) * 8;   // + W_L1 table
-}
-static int gen_cols_threads(const rmx_ctx* c, int l1) { // one radix-16 work item per thread and pass, <= 1024
-    const long work = (((long)1 << l1) << host_col_log_t(c, l1)) / 16;
-    long v;
-    if (c->knobs.get("cols_threads", &v)) return (int)v;
-    return work >= 1024 ? 1024 : (work < 64 ? 64 : (int)work);
-}
-
-// Every kernel choice of the generic path, from the lengths and the options alone (no HIP call).  logL1 = 0: the
+// Every kernel choice of the generic path, from the ctx's geometry and the options alone (no HIP call).  g.small: the
 // LDS-resident lengths (g_fwd_small / g_pair_small need no choice), else the four-step split L = L1 x L2 with its
 // column tile, column threads and threads per row.
-static GenericKernels pick_generic_kernels(int n_buoys, int logL, int logL1, int logL2, int col_log_t, int cols_threads, int rows_tpr,
-                                           const host::Knobs& knobs) {
+static GenericKernels pick_generic_kernels(const gen::Geometry& g, const host::Knobs& knobs) {
+    const int n_buoys = g.n_buoys, logL = g.logL, logL1 = g.logL1, logL2 = g.logL2;
+    const int col_log_t = g.col_log_t, cols_threads = g.cols_threads, rows_tpr = g.rows_tpr;
     GenericKernels k;
-    if (logL1 == 0) {
+    if (g.small) {
         // at most four buoys, 512 <= L <= 4096: whole windows in one kernel, spectra in registers (option wfused = 0: the
         // two per-transform kernels, as for custom Doppler searches)
         if (n_buoys >= 2 && n_buoys <= 4 && logL >= 9 && logL <= 12 && knobs.get_or("wfused", 1) != 0) {
@@ -642,8 +597,6 @@ static GenericKernels pick_generic_kernels(int n_buoys, int logL, int logL1, int
             k.wf[0][1] = wfused_fn<false, true>(n_buoys, logL);
             k.wf[1][0] = wfused_fn<true, false>(n_buoys, logL);
             k.wf[1][1] = wfused_fn<true, true>(n_buoys, logL);
-            k.wf_lds[0] = gen_wfused_lds(logL, false);
-            k.wf_lds[1] = gen_wfused_lds(logL, gen::fused_tw_regs(n_buoys, logL, true));
         }
     } else {
         k.cols_inv = cols_inv_fn<>(logL1, col_log_t, cols_threads);
@@ -674,13 +627,13 @@ static GenericKernels pick_generic_kernels(int n_buoys, int logL, int logL1, int
             k.ws15[1] = gen::g_win_eo15<true>;
             k.ws_thr = 512;
             k.ws_upw = 1;
-            k.ws_lds = gen::kWinEoLds;
+            k.ws_lds = gen::Win14Lds::bytes;
         } else if (logL == 14 && knobs.get_or("wscr14", 1) != 0) {
             // L = 16384: 512 threads x two butterflies (g_win_scr14) unless wscr14 = 0 (1024 threads x one: g_win_scr<14>)
             k.ws[0] = gen::g_win_scr14<false>;
             k.ws[1] = gen::g_win_scr14<true>;
             k.ws_thr = 512;
-            k.ws_lds = ((size_t)gen::lp(16384) + 15 * 64 + 15 * 4 + 16) * 8;
+            k.ws_lds = gen::Win14Lds::bytes;
         } else {
             k.ws[0] = wscr_fn<false>(logL);
             k.ws[1] = wscr_fn<true>(logL);
@@ -692,51 +645,39 @@ static GenericKernels pick_generic_kernels(int n_buoys, int logL, int logL1, int
 static int generic_init(rmx_ctx* c) {
     using namespace gen;
     c->generic = true;
-    int logn = 0;
-    while ((1 << logn) < c->n_samples) ++logn;
-    c->g_logL = logn + 1;
-    const long L = 1L << c->g_logL;
+    c->geo = make_geometry(c->n_buoys, c->n_samples, c->knobs);
+    const Geometry& g = c->geo;
+    if (!g.layouts_ok) return fail(c, RMX_E_INVAL, "generic path: an LDS layout of this length and these options overruns its launch bytes");
+    const long L = 1L << g.logL;
     std::vector<float2> t;
     int rc = RMX_OK;
-    if (L <= kGenSmallMaxL) {
+    c->gk = pick_generic_kernels(g, c->knobs);
+    if (g.small) {
         make_row_table(t, (int)L);
         RMX_MEM(c->g_tw.assign(t));
-        c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, 0, 0, 0, 0, 0, c->knobs);
-        rc = allow_lds(c, (size_t)gen::lp(L) * 8 + 1024 * 8, g_pair_small<>, g_pair_small<LagBounds>, g_pair_small<LagBounds, Integrate>,
+        rc = allow_lds(c, g.small_allow_lds, g_pair_small<>, g_pair_small<LagBounds>, g_pair_small<LagBounds, Integrate>,
                        g_pair_small<LagBounds, Integrate, CafOperand>, g_pair_small<LagBounds, Integrate, BandSet>, g_pair_small<BandSet>, g_pair_small<LagBounds, BandSet>, g_fwd_small<false>, g_fwd_small<true>,
                        g_fwd_small<false, XWeight>, g_fwd_small<true, XWeight>);
-        for (int d = 0; d < 2 && rc == RMX_OK; ++d) rc = allow_lds(c, c->gk.wf_lds[d], c->gk.wf[d][0], c->gk.wf[d][1]);
+        for (int d = 0; d < 2 && rc == RMX_OK; ++d) rc = allow_lds(c, g.wfused_lds[d], c->gk.wf[d][0], c->gk.wf[d][1]);
         if (rc) return rc;
     } else {
-        // columns of length L1 <= 1024 (a tile of 16 columns is L1*128 bytes of LDS), rows of L2 = L/L1 <= 8192
-        // columns a little shorter than rows (measured: 512 x 4096 beats 1024 x 2048 at L = 2^21, 256 x 2048 beats
-        // 512 x 1024 at 2^19), rows at most 8192 (64 KiB of LDS)
-        c->g_logL1 = (c->g_logL - 3) / 2;
-        if (c->g_logL == 18) c->g_logL1 = 8;   // (measured with this round's kernels: 256 x 1024 beats 128 x 2048 by 5 %)
-        if (c->g_logL1 < c->g_logL - 13) c->g_logL1 = c->g_logL - 13;
-        if (c->g_logL1 > 10) c->g_logL1 = 10;
-        { long v; if (c->knobs.get("logl1", &v) && v >= 4 && v <= 10 && c->g_logL - v <= 13 && c->g_logL - v >= 4) c->g_logL1 = (int)v; }
-        c->g_logL2 = c->g_logL - c->g_logL1;
-        c->g_lo_bits = (c->g_logL + 1) / 2;
-        make_row_table(t, 1 << c->g_logL1);
+        // the split L = L1 x L2, the column tile and the thread counts: make_geometry (gen_geometry.hpp)
+        make_row_table(t, 1 << g.logL1);
         RMX_MEM(c->g_tw1.assign(t));
-        make_row_table(t, 1 << c->g_logL2);
+        make_row_table(t, 1 << g.logL2);
         RMX_MEM(c->g_tw2.assign(t));
         std::vector<float2> thi, tlo;
-        make_big_tables(thi, tlo, L, c->g_lo_bits);
+        make_big_tables(thi, tlo, L, g.lo_bits);
         RMX_MEM(c->g_thi.assign(thi));
         RMX_MEM(c->g_tlo.assign(tlo));
-        c->gk = pick_generic_kernels(c->n_buoys, c->g_logL, c->g_logL1, c->g_logL2, host_col_log_t(c, c->g_logL1),
-                                     gen_cols_threads(c, c->g_logL1), gen_rows_tpr(c, 1 << c->g_logL2), c->knobs);
         const GenericKernels& k = c->gk;
-        const size_t rows_lds = gen_rows_lds(c, 1 << c->g_logL2);
-        rc = allow_lds(c, gen_cols_lds(c, c->g_logL1), k.cols_inv, k.cols_inv_lb, k.cols_inv_int, k.cols_inv_int_bs, k.cols_fwd[0], k.cols_fwd[1]);
+        rc = allow_lds(c, g.cols_lds, k.cols_inv, k.cols_inv_lb, k.cols_inv_int, k.cols_inv_int_bs, k.cols_fwd[0], k.cols_fwd[1]);
         // (the run-time-length row kernels too, whichever the tables chose)
         if (rc == RMX_OK)
-            rc = allow_lds(c, rows_lds, g_rows<true, false, false>, g_rows<false, true, true>, k.rows_fwd, k.rows_fwd_wt, k.rows_inv, k.rows_inv_bs,
+            rc = allow_lds(c, g.rows_lds, g_rows<true, false, false>, g_rows<false, true, true>, k.rows_fwd, k.rows_fwd_wt, k.rows_inv, k.rows_inv_bs,
                            k.rows_anchor);
-        if (rc == RMX_OK) rc = allow_lds(c, gen_fused_lds(1 << c->g_logL2), k.fused);
-        if (rc == RMX_OK) rc = allow_lds(c, gen_fused_lds(1 << c->g_logL2, gen::fused_tw_regs(c->n_buoys, c->g_logL2, true)), k.fused_def);
+        if (rc == RMX_OK) rc = allow_lds(c, g.fused_lds[0], k.fused);
+        if (rc == RMX_OK) rc = allow_lds(c, g.fused_lds[1], k.fused_def);
         if (rc) return rc;
         { long v; if (c->knobs.get("rows_anchor", &v) && v >= 2) c->g_rows_anchor_min_b = (int)v; }
         c->g_fused = k.fused != nullptr;
@@ -747,9 +688,9 @@ static int generic_init(rmx_ctx* c) {
     c->g_wscr_always = c->knobs.get_or("wscr", 1) == 2;         // 2: also for batches that do not fill the chip (tests)
     if (c->g_wscr) {
         const GenericKernels& k = c->gk;
-        make_row_table(t, c->g_logL == 15 ? 16384 : (int)L);       // (N = 16384: two 16384-point halves)
+        make_row_table(t, c->geo.logL == 15 ? 16384 : (int)L);       // (N = 16384: two 16384-point halves)
         RMX_MEM(c->g_tw_win.assign(t));
-        if (c->g_logL == 15) {
+        if (c->geo.logL == 15) {
             const double two_pi = 6.283185307179586476925286766559;
             std::vector<float2> wl(1024);
             for (int i = 0; i < 1024; ++i) wl[i] = make_float2((float)std::cos(two_pi * i / 32768.0), (float)-std::sin(two_pi * i / 32768.0));
@@ -772,7 +713,7 @@ static int generic_init(rmx_ctx* c) {
         // (B x 2 x 64 KiB per persistent workgroup), one workgroup per CU.  Option kwin8k: 1 (default) = k_win8kl, one anchor
         // half resident in LDS -- 0.51 against g_win_scr14's 0.73 ms at 8 buoys x 512 windows, 1.00 against 1.42 at 16 x 256,
         // 0.19 against 0.285 at 3 x 1024 --; 0 = g_win_scr14; 2 = k_win8k (no resident anchor: -DRMX_EXPERIMENTS builds only)
-        if (c->g_logL == 14 && c->knobs.get_or("kwin8k", 1) != 0) {
+        if (c->geo.logL == 14 && c->knobs.get_or("kwin8k", 1) != 0) {
             std::vector<float4> t1;
             std::vector<float4> t1_4096;
             std::vector<float2> t2;
@@ -798,7 +739,7 @@ static int generic_init(rmx_ctx* c) {
         // N = 16384: four quarter transforms on the same network, forward and pair kernels per chunk of g_ws_grid windows
         // (kwin16k.hpp; the spectra of a chunk take the SAME B x 256 KiB per window as g_win_eo15's per-workgroup scratch, so
         // the buffer is shared).  Option kwin16k: 1 (default) = from the measured batch size on, 2 = every batch, 0 = g_win_eo15.
-        if (c->g_logL == 15 && c->knobs.get_or("kwin16k", 1) != 0 && k.ws_upw == 1) {
+        if (c->geo.logL == 15 && c->knobs.get_or("kwin16k", 1) != 0 && k.ws_upw == 1) {
             std::vector<float4> t1, t1_4096;
             std::vector<float2> t2, gq, tws;
             build_tables(t1_4096, t2);
@@ -828,8 +769,8 @@ static int generic_init(rmx_ctx* c) {
 // n_bands > 1 (rmx_xcorr_batch_bands): the pair-dependent buffers hold the slots host::plan_bands states for the chunk.
 static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool need_pairbufs = true, int n_bands = 1) {
     using namespace gen;
-    const long L = 1L << c->g_logL;
-    const bool four_step = L > kGenSmallMaxL;
+    const long L = 1L << c->geo.logL;
+    const bool four_step = !c->geo.small;
     auto release = [&]() {   // every chunk-sized buffer
         c->g_spec.release();
         c->g_spec_r.release();
@@ -838,8 +779,8 @@ static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool n
         c->g_halo.release();
     };
     for (;;) {
-        const long parts = four_step ? (1L << c->g_logL2) >> host_col_log_t(c, c->g_logL1) : 0;   // one record per column tile
-        const host::BandsPlan bp = host::plan_bands(c->g_chunk, 0, n_bands, c->n_buoys, n_pairs, L, four_step, parts, c->g_logL1, sizeof(GTile));
+        const long parts = c->geo.col_tiles;   // one record per column tile (four-step; else 0)
+        const host::BandsPlan bp = host::plan_bands(c->g_chunk, 0, n_bands, c->n_buoys, n_pairs, L, four_step, parts, c->geo.logL1, sizeof(GTile));
         bool ok = !need_spec || c->g_spec.try_reserve((size_t)c->g_chunk * c->n_buoys * L);
         // the pair-dependent buffers grow with the slots (n_bands = 1: g_chunk * n_pairs): each of their sizes is per slot
         if (four_step && need_pairbufs)
@@ -862,7 +803,7 @@ static int generic_ensure(rmx_ctx* c, int n_pairs, bool need_spec = true, bool n
 static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, int w0, int wc, bool u8, const float2* rot,
                            bool cols_only) {
     using namespace gen;
-    const int N = c->n_samples, logL = c->g_logL, B = c->n_buoys;
+    const int N = c->n_samples, logL = c->geo.logL, B = c->n_buoys;
     const long L = 1L << logL;
     const float fwd_scale = std::ldexp(1.0f, -(logL / 2));
     const int items = wc * B;
@@ -871,30 +812,30 @@ static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, 
     float2* dst = rot ? c->g_spec_r : c->g_spec;
     XWeight wt = call.wt;   // weighted call: the stored bins carry fwd_scale
     wt.unit = fwd_scale;
-    if (L <= kGenSmallMaxL) {
-        const int sthr = gen_small_threads(L);
+    const Geometry& g = c->geo;
+    if (g.small) {
+        const int sthr = g.small_threads;
         return with_u8(u8, [&](auto U) {
             constexpr bool U8 = decltype(U)::value;
             auto go = [&](auto kern, const float2* a_rot, auto... a_wt) {
-                return launch(c, kTkFwdSmall, kern, dim3(items), dim3(sthr), (size_t)gen::lp(L) * 8, d_iq, dst, c->g_tw, N, logL, first_item,
+                return launch(c, kTkFwdSmall, kern, dim3(items), dim3(sthr), g.small_fwd_lds, d_iq, dst, c->g_tw, N, logL, first_item,
                               fwd_scale, a_rot, a_wt...);
             };
             return call.wt.band ? go(g_fwd_small<U8, XWeight>, rot, wt) : go(g_fwd_small<U8>, rot);
         });
     }
-    const int l1 = c->g_logL1, l2 = c->g_logL2, L1 = 1 << l1, L2 = 1 << l2;
-    const int cthr = gen_cols_threads(c, l1), tpr = gen_rows_tpr(c, L2);
-    const int ntiles = L2 >> host_col_log_t(c, l1);
+    const int l1 = c->geo.logL1, l2 = c->geo.logL2, L1 = 1 << l1, L2 = 1 << l2;
+    const int cthr = g.cols_threads, tpr = g.rows_tpr, ntiles = g.col_tiles;
     // column pass (zero-padded window -> [k1'][n2] * W_L^(n2 k1)), row pass in place (-> [k1'][k2'])
-    int rc = launch(c, kTkColsFwd, c->gk.cols_fwd[u8 ? 1 : 0], dim3(ntiles, items), dim3(cthr), gen_cols_lds(c, l1), d_iq, dst, c->g_tw1,
-                    l1, l2, first_item, c->g_lo_bits, c->g_thi, c->g_tlo, rot);
+    int rc = launch(c, kTkColsFwd, c->gk.cols_fwd[u8 ? 1 : 0], dim3(ntiles, items), dim3(cthr), g.cols_lds, d_iq, dst, c->g_tw1,
+                    l1, l2, first_item, c->geo.lo_bits, c->g_thi, c->g_tlo, rot);
     if (rc != RMX_OK || cols_only) return rc;   // (cols_only: g_rows_fused does the rows)
     const long rows = (long)items * L1;
     const int rpw = kGThreads / tpr;
     // forward rows read no second operand: no spectra, no pair list; a weighted call's chunk starts at window w0
     auto go = [&](auto kern, auto... a_wt) {
-        return launch(c, kTkRowsFwd, kern, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), gen_rows_lds(c, L2), dst, c->g_tw2, l2,
-                      L1, l1, L, c->g_lo_bits, c->g_thi, c->g_tlo, fwd_scale, rows, /* spec */ nullptr, /* spec_j */ nullptr,
+        return launch(c, kTkRowsFwd, kern, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), g.rows_lds, dst, c->g_tw2, l2,
+                      L1, l1, L, c->geo.lo_bits, c->g_thi, c->g_tlo, fwd_scale, rows, /* spec */ nullptr, /* spec_j */ nullptr,
                       /* pairs */ nullptr, /* n_pairs */ 0, /* n_buoys */ 0, tpr, a_wt...);
     };
     wt.w0 = w0;
@@ -906,7 +847,7 @@ static int generic_forward(rmx_ctx* c, const XcorrCall& call, const void* d_iq, 
 static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak,
                          bool use_rot, bool fused) {
     using namespace gen;
-    const int N = c->n_samples, logL = c->g_logL, B = c->n_buoys;
+    const int N = c->n_samples, logL = c->geo.logL, B = c->n_buoys;
     const long L = 1L << logL;
     const int hs = logL / 2;
     const float out_scale = std::ldexp(1.0f, -(logL - 2 * hs));
@@ -917,10 +858,10 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     bs.w0 = w0;
     const int slots = wc * nb * n_pairs;
     const float2* spec_j = use_rot ? c->g_spec_r : c->g_spec;
-    if (L <= kGenSmallMaxL) {
-        const int sthr = gen_small_threads(L);
+    const Geometry& g = c->geo;
+    if (g.small) {
         auto go = [&](auto kern, int grid, long first, auto... tail) {
-            return launch(c, kTkPairSmall, kern, dim3(grid), dim3(sthr), (size_t)gen::lp(L) * 8 + (size_t)sthr * 8, c->g_spec, spec_j, c->g_tw,
+            return launch(c, kTkPairSmall, kern, dim3(grid), dim3(g.small_threads), g.small_pair_lds, c->g_spec, spec_j, c->g_tw,
                           c->g_pairs, n_pairs, B, N, logL, first, out_scale, d_lag, d_frac, d_peak, tail...);
         };
         if (call.integrated() && call.banded())   // one workgroup per (group, band, pair); the bounds per row group * n_bands + band
@@ -935,10 +876,9 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
         return go(g_pair_small<>, slots, (long)w0);
     }
     const GenericKernels& k = c->gk;
-    const int l1 = c->g_logL1, l2 = c->g_logL2, L1 = 1 << l1, L2 = 1 << l2;
-    const int cthr = gen_cols_threads(c, l1), tpr = gen_rows_tpr(c, L2);
-    const size_t clds = gen_cols_lds(c, l1), rlds = gen_rows_lds(c, L2);
-    const int lt = host_col_log_t(c, l1), ntiles = L2 >> lt;
+    const int l1 = c->geo.logL1, l2 = c->geo.logL2, L1 = 1 << l1, L2 = 1 << l2;
+    const int cthr = g.cols_threads, tpr = g.rows_tpr, lt = g.col_log_t, ntiles = g.col_tiles;
+    const size_t clds = g.cols_lds, rlds = g.rows_lds;
     const long rows = (long)slots * L1;
     const int rpw = kGThreads / tpr;
     const bool all_pairs = c->plan_all_pairs && n_pairs == B * (B - 1) / 2;
@@ -947,7 +887,7 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
     if (call.banded()) {
         // always the product-on-load rows: their banded instantiation masks the product (never g_rows_anchor / g_rows_fused)
         rc = launch(c, kTkRowsInv, k.rows_inv_bs, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), rlds, c->g_prod, c->g_tw2, l2, L1,
-                    l1, L, c->g_lo_bits, c->g_thi, c->g_tlo, 1.0f, rows, c->g_spec, spec_j, c->g_pairs, n_pairs, B, tpr, bs);
+                    l1, L, c->geo.lo_bits, c->g_thi, c->g_tlo, 1.0f, rows, c->g_spec, spec_j, c->g_pairs, n_pairs, B, tpr, bs);
     } else if (fused) {
         // g_spec holds the column pass's output: forward rows, products and inverse rows in one kernel
         const long units = (long)wc * L1;
@@ -955,17 +895,17 @@ static int generic_pairs(rmx_ctx* c, const XcorrCall& call, int w0, int wc, int 
         const bool def_plan = k.fused_def && all_pairs;
         const float fs = std::ldexp(1.0f, -(logL / 2));
         rc = launch(c, kTkRowsFused, def_plan ? k.fused_def : k.fused, dim3((unsigned)((units + upw - 1) / upw)), dim3(kGThreads),
-                    gen_fused_lds(L2, def_plan && gen::fused_tw_regs(B, l2, true)), c->g_spec, c->g_prod, c->g_tw2, L1, l1, L, c->g_lo_bits,
+                    g.fused_lds[def_plan ? 1 : 0], c->g_spec, c->g_prod, c->g_tw2, L1, l1, L, c->geo.lo_bits,
                     c->g_thi, c->g_tlo, fs * fs, units, c->g_pairs, n_pairs);
     } else if (k.rows_anchor && all_pairs && B >= c->g_rows_anchor_min_b) {
         // default pair list: the anchor's row stays in registers over its run of pairs (from 6 buoys on: with 5 the runs are
         // too short for the per-workgroup set-up, 0.649 -> 0.692 ms at N = 16384; with 6 / 7 / 8 buoys 0.89 -> 0.84, 1.16 -> 1.10,
         // 1.54 -> 1.39 ms, cfg5 250 -> 203 ms)
         rc = launch(c, kTkRowsAnchor, k.rows_anchor, dim3((unsigned)((L1 / rpw) * (B - 1)), (unsigned)wc), dim3(kGThreads), rlds, c->g_prod,
-                    c->g_tw2, L1, l1, L, c->g_lo_bits, c->g_thi, c->g_tlo, 1.0f, c->g_spec, spec_j, n_pairs, B);
+                    c->g_tw2, L1, l1, L, c->geo.lo_bits, c->g_thi, c->g_tlo, 1.0f, c->g_spec, spec_j, n_pairs, B);
     } else {
         rc = launch(c, kTkRowsInv, k.rows_inv, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(kGThreads), rlds, c->g_prod, c->g_tw2, l2, L1,
-                    l1, L, c->g_lo_bits, c->g_thi, c->g_tlo, 1.0f, rows, c->g_spec, spec_j, c->g_pairs, n_pairs, B, tpr);
+                    l1, L, c->geo.lo_bits, c->g_thi, c->g_tlo, 1.0f, rows, c->g_spec, spec_j, c->g_pairs, n_pairs, B, tpr);
     }
     if (rc != RMX_OK) return rc;
     // integrated call: the column pass sums the |r|^2 of a group's K product slots tile by tile and leaves one tile record
@@ -1086,8 +1026,8 @@ static SpecView spec_view(const rmx_ctx* c) {
                 [](rmx_ctx* c, const XcorrCall& call, int w0, int wc, int n_pairs, int* d_lag, float* d_frac, float* d_peak, bool use_rot, bool) {
                     return pairs4096(c, call, w0, wc, n_pairs, d_lag, d_frac, d_peak, out_scale4096(), use_rot);
                 }};
-    const bool small_l = (1L << c->g_logL) <= kGenSmallMaxL;
-    return {small_l ? kRefSmall : kRefRows, c->g_spec, c->g_logL, small_l ? 0 : c->g_logL1, -(c->g_logL / 2), generic_forward, generic_pairs};
+    const bool small_l = c->geo.small;
+    return {small_l ? kRefSmall : kRefRows, c->g_spec, c->geo.logL, small_l ? 0 : c->geo.logL1, -(c->geo.logL / 2), generic_forward, generic_pairs};
 }
 
 // what the planner (host_plan.hpp: plan_route) needs to know of this ctx
@@ -1098,13 +1038,13 @@ static host::RouteCaps route_caps(const rmx_ctx* c) {
     k.fused = c->fused;  k.small_batch = c->small_batch;  k.chunk_windows = c->chunk_windows;
     k.ppb_user = c->ppb_user ? c->pairs_per_block : 0;
     if (!c->generic) return k;
-    k.logL = c->g_logL;  k.logL1 = c->g_logL1;  k.logL2 = c->g_logL2;  k.small_maxl = kGenSmallMaxL;
+    k.logL = c->geo.logL;  k.logL1 = c->geo.logL1;  k.logL2 = c->geo.logL2;  k.small_maxl = c->geo.small_maxl;
     k.g_chunk = c->g_chunk;  k.wfused = c->g_wfused;  k.wscr = c->g_wscr;  k.wscr_always = c->g_wscr_always;
     k.ws_upw = c->gk.ws_upw;  k.ws_grid = c->g_ws_grid;  k.k8 = c->g_k8;  k.k16 = c->g_k16;
     if (c->g_k16 == 1) k.k16_min_windows = c->knobs.get_or("k16_min_windows", 0);
     k.g_fused = c->g_fused;  k.g_fused_always = c->g_fused_always;
     k.max_pairs8 = k8::kMaxPairs8;  k.max_pairs16 = k16::kMaxPairs16;  k.integ_max_per_thread = kIntegMaxPerThread;
-    k.col_tile = (1L << c->g_logL1) << host_col_log_t(c, c->g_logL1);  k.cols_threads = gen_cols_threads(c, c->g_logL1);   // (four-step)
+    if (!c->geo.small) { k.col_tile = c->geo.col_tile;  k.cols_threads = c->geo.cols_threads; }   // (read for the four-step route only)
     return k;
 }
 
@@ -1193,7 +1133,7 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps
                          const void* d_iq, int* d_lag, float* d_frac, float* d_peak, bool u8) {
     using namespace host;
     const GenericKernels& k = c->gk;
-    const int n_pairs = rq.n_pairs, logL = c->g_logL, hs = logL / 2;
+    const int n_pairs = rq.n_pairs, logL = c->geo.logL, hs = logL / 2;
     // device buffers on first need; a failed allocation halves g_chunk, and the plan follows (the route does not depend on it)
     auto ensure = [&](bool need_spec, bool need_pairbufs) -> int {
         const int rc_e = generic_ensure(c, n_pairs, need_spec, need_pairbufs, rq.n_bands);
@@ -1211,7 +1151,7 @@ static int generic_batch(rmx_ctx* c, const XcorrCall& call, host::RouteCaps caps
     const float fwd_scale = std::ldexp(1.0f, -hs), out_scale = std::ldexp(1.0f, -(logL - 2 * hs));
     if (plan.route == kRouteWinFused) {
         const int upw = gen::kGThreads / ((1 << logL) >> 4), def = rq.all_pairs ? 1 : 0;
-        return launch(c, kTkWindow, k.wf[def][u8 ? 1 : 0], dim3((unsigned)((rq.n_windows + upw - 1) / upw)), dim3(gen::kGThreads), k.wf_lds[def],
+        return launch(c, kTkWindow, k.wf[def][u8 ? 1 : 0], dim3((unsigned)((rq.n_windows + upw - 1) / upw)), dim3(gen::kGThreads), c->geo.wfused_lds[def],
                       d_iq, c->g_tw, n_head, 0L, fwd_scale, out_scale, c->g_pairs, n_pairs, d_lag, d_frac, d_peak);
     }
     // g_win_scr*, g_win_eo15, k_win8kl: persistent workgroups over the ctx's scratch; the full rounds here, the planned
@@ -2200,8 +2140,8 @@ int rmx_detect_batch(rmx_ctx* c, const void* iq, int n_windows, int n_samples, f
         std::vector<float2> t;
         rmx::gen::make_row_table(t, N);
         RMX_MEM(c->dt_tw.refill(logn, t));
-        int rc_l = allow_lds(c, (size_t)rmx::gen::lp(16384) * 8, det::d_fft_db<false>, det::d_fft_db<true>);
-        if (rc_l == RMX_OK) rc_l = allow_lds(c, 16384 * 6 + 8192, det::d_peaks);
+        int rc_l = allow_lds(c, rmx::gen::kDetFftAllowBytes, det::d_fft_db<false>, det::d_fft_db<true>);
+        if (rc_l == RMX_OK) rc_l = allow_lds(c, rmx::gen::kDetPeaksAllowBytes, det::d_peaks);
         if (rc_l != RMX_OK) return rc_l;
     }
     const bool in_dev = flags & RMX_IN_DEVICE, out_dev = flags & RMX_OUT_DEVICE, u8 = flags & RMX_IN_U8;
@@ -2223,14 +2163,14 @@ int rmx_detect_batch(rmx_ctx* c, const void* iq, int n_windows, int n_samples, f
         d_bin = (int*)b; d_pw = (float*)(b + per * 4); d_snr = (float*)(b + per * 8); d_conf = (float*)(b + per * 12);
         d_count = (int*)(b + per * 16); d_floor = (float*)(b + per * 16 + (size_t)n_windows * 4);
     }
-    const int fthr = N >= 4096 ? 1024 : (N >= 1024 ? 256 : 64);
+    const int fthr = rmx::gen::det_fft_threads(N);
     rc = with_u8(u8, [&](auto U) {
-        return launch(c, kTkNone, det::d_fft_db<decltype(U)::value>, dim3(n_windows), dim3(fthr), (size_t)rmx::gen::lp(N) * 8, d_iq, c->dt_pdb,
+        return launch(c, kTkNone, det::d_fft_db<decltype(U)::value>, dim3(n_windows), dim3(fthr), (size_t)rmx::gen::det_fft_layout(N).bytes, d_iq, c->dt_pdb,
                       c->dt_tw, logn);
     });
     if (rc != RMX_OK) return rc;
-    const int pthr = N >= 4096 ? 1024 : 256;
-    const size_t plds = (size_t)N * 4 + N + (size_t)N + 256 * 4 + 8 * 4 + (size_t)pthr * 4;
+    const int pthr = rmx::gen::det_peaks_threads(N);
+    const size_t plds = (size_t)rmx::gen::det_peaks_layout(N, pthr).bytes;
     // a distance >= N keeps the single highest candidate, as N does: clamped, so that the kernel's neighbour span
     // 2 (distance - 1) + 1 stays in int range and each candidate scans at most 2 N - 1 bins
     const int dist = distance < N ? distance : N;

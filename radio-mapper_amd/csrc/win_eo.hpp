@@ -21,8 +21,6 @@
 namespace rmx {
 namespace gen {
 
-constexpr size_t kWinEoLds = ((size_t)lp(16384) + 15 * 64 + 15 * 4 + 16) * 8;   // as g_win_scr14
-
 template <bool U8>
 __global__ __launch_bounds__(512, 2) void g_win_eo15(const void* __restrict__ iq, float4* __restrict__ scratch,
                                                   const float2* __restrict__ tw, const float2* __restrict__ twl,
@@ -32,12 +30,13 @@ __global__ __launch_bounds__(512, 2) void g_win_eo15(const void* __restrict__ iq
                                                   float* __restrict__ peak) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     constexpr int LOGR = 14, R = 1 << LOGR, N = R, NT = 512, Q = R >> 4;          // half transforms of R = N points
-    constexpr int off10 = 0, off6 = 15 * 64, tab_total = 15 * 64 + 15 * 4;
+    using Lay = Win14Lds;                                                         // the LDS image of g_win_scr14
+    constexpr int off10 = Lay::off10, off6 = Lay::off6;
     const int tid = threadIdx.x;
-    float2* x = reinterpret_cast<float2*>(gsm);
-    float2* tab = x + lp(R);
-    float* sv = reinterpret_cast<float*>(tab + tab_total);
-    int* sk = reinterpret_cast<int*>(sv + 16);
+    float2* x = reinterpret_cast<float2*>(gsm + Lay::x.off);
+    float2* tab = reinterpret_cast<float2*>(gsm + Lay::tab.off);
+    float* sv = reinterpret_cast<float*>(gsm + Lay::sv.off);
+    int* sk = reinterpret_cast<int*>(gsm + Lay::sk.off);
     for (int e = tid; e < 15 * 64; e += NT) tab[off10 + e] = tw_full(tw, ((e & 63) << 4) * ((e >> 6) + 1), R >> 1);
     for (int e = tid; e < 15 * 4; e += NT) tab[off6 + e] = tw_full(tw, ((e & 3) << 8) * ((e >> 2) + 1), R >> 1);
     // First-pass twiddles W_R^(i k), k = 1..15, of butterfly i: g_win_scr14 keeps all 2 x 15 of them in registers; here the
