@@ -710,6 +710,47 @@ int rmx_solve_batch(rmx_ctx* ctx, const double* buoy_xyz, int n_buoys, const int
                     double sample_rate_hz, int n_windows, int max_iter, double* pos, double* cost,
                     int32_t* iters, unsigned flags);
 
+/* rmx_solve_batch with a surface constraint and with the figures that say how far the fix can be trusted: the
+ * information matrix at the fix, its inverse and the residual of every pair.  Every argument of rmx_solve_batch means
+ * what it means there; RMX_IN_DEVICE and RMX_OUT_DEVICE act as there, and info, cov and resid follow RMX_OUT_DEVICE with
+ * pos, cost and iters, so the call chains on the ctx stream.
+ *   plane      host double [9] = origin o, then two orthonormal directions e1, e2, all ECEF (for stations on the sea:
+ *              GeodeticCalculator.tangent_plane at the fleet's centroid), or NULL = three unknowns.
+ *   plane == NULL: pos, cost and iters are those of rmx_solve_batch with the same arguments bit for bit (the same kernel).
+ *   plane given: two unknowns u = (u1, u2), p(u) = o + u1 e1 + u2 e2.  The objective f is rmx_solve_batch's; the start is
+ *              the centroid of the buoys projected onto the plane; the Jacobian row of a pair is (j . e1, j . e2) with the
+ *              j of the three-unknown solve; the Levenberg-Marquardt rule is rmx_solve_batch's written out for 2 x 2
+ *              (lambda_0 = 1e-3 on diag(J^T W J); a Cholesky step; a failed factorisation or a NaN trial cost is a
+ *              rejection; accept: lambda /= 3, floor 1e-12; reject: lambda *= 4; stop at an accepted step < 1e-4 m,
+ *              lambda > 1e12, or max_iter).  pos = p(u) in ECEF, cost = f there.
+ * At the returned pos, in both modes:
+ *   info       double, the undamped J^T W J.  plane == NULL: [n_windows][6] = xx xy xz yy yz zz in ECEF; plane given:
+ *              [n_windows][3] = 11 12 22 in plane coordinates.  In m^-2 where weight is in m^-2.
+ *   cov        double, its inverse through Cholesky, in the same layout.
+ *   resid      double [n_windows][n_pairs] = |p - b_j| - |p - b_i| - d in metres, or NULL: not computed.
+ * Singular rule: the information is singular when a Cholesky pivot is <= 1e-12 * its own diagonal entry of info, or is
+ *   not finite.  Then cov is +inf on its diagonal and 0 off it.  1e-12 sits four decades above float64 rounding and six
+ *   below the weakest geometry that still carries information (five sea-level stations about 10 km apart solved for
+ *   three unknowns: the last pivot is a few 1e-7 of its diagonal entry at the emitter, not singular; three such stations:
+ *   1e-16 or an exact 0, singular).  If any entry of info
+ *   is not finite (pos exactly on a buoy, which the give-up of rmx_solve_batch with the centroid on a buoy returns),
+ *   info is written as zeros and cov as singular.  No output is ever NaN.
+ * What the outputs mean:
+ *   with weight = 1 / sigma_d^2 (sigma_d = the standard deviation of a pair's range difference in metres,
+ *   xcorr.lag_weight) cov is the covariance of the fix under INDEPENDENT pair errors, and cost is a chi-square with
+ *   (pairs of weight > 0) - (2 or 3) degrees of freedom;
+ *   with weight == NULL cov is the cofactor matrix: the dilution of precision, squared.
+ *   All pairs of B stations carry only B - 1 independent lags: their errors share receivers, they are NOT independent,
+ *   and cov is then optimistic.  The entry does not correct for that.
+ * Parity: every output is bit-identical to tests/solve_fix_ref.py, the kernel-order float64 restatement.
+ * Refusals (RMX_E_INVAL, rmx_last_error set, no output written, the ctx stays usable): every refusal of rmx_solve_batch;
+ *   info or cov NULL; a plane entry that is not finite; | |e1| - 1 | or | |e2| - 1 | above 1e-9; |e1 . e2| above 1e-9.
+ *   n_windows == 0 returns RMX_OK and writes nothing. */
+int rmx_solve_batch_fix(rmx_ctx* ctx, const double* buoy_xyz, int n_buoys, const int32_t* pairs, int n_pairs,
+                        const int32_t* lag_int, const float* lag_frac, const float* weight,
+                        double sample_rate_hz, const double* plane, int n_windows, int max_iter, double* pos,
+                        double* cost, int32_t* iters, double* info, double* cov, double* resid, unsigned flags);
+
 /* Spectral detection: the reference's per-capture detector
  * (buoy_node.py:401-433, iq_stream_client.py:186-217) batched over windows.  Per window of n_samples
  * (power of two, 16..16384; independent of the ctx's n_samples) complex samples:

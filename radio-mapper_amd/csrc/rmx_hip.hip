@@ -2054,11 +2054,20 @@ int rmx_caf_batch_bands(rmx_ctx* c, const void* iq, int n_windows, const int32_t
     return caf_request(c, a, flags);
 }
 
-int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32_t* pairs, int n_pairs,
-                    const int32_t* lag_int, const float* lag_frac, const float* weight, double sample_rate_hz,
-                    int n_windows, int max_iter, double* pos, double* cost, int32_t* iters, unsigned flags) {
+// What rmx_solve_batch_fix asks beyond rmx_solve_batch: the plane (or NULL: three unknowns) and the outputs at the fix.
+struct SolveFixArgs {
+    const double* plane;
+    double *info, *cov, *resid;
+};
+
+// The body of both solve entries.  fx == nullptr IS rmx_solve_batch: the same checks, copies and the one k_solve launch.
+static int solve_request(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32_t* pairs, int n_pairs,
+                         const int32_t* lag_int, const float* lag_frac, const float* weight, double sample_rate_hz,
+                         int n_windows, int max_iter, double* pos, double* cost, int32_t* iters, unsigned flags,
+                         const SolveFixArgs* fx) {
     if (!c) return RMX_E_INVAL;
     if (!buoy_xyz || !lag_int || !lag_frac || !pos || !cost || !iters) return fail(c, RMX_E_INVAL, "NULL buffer");
+    if (fx && (!fx->info || !fx->cov)) return fail(c, RMX_E_INVAL, "NULL buffer (info, cov)");
     if (n_buoys < 2 || n_buoys > rmx::kSolveMaxBuoys)
         return fail(c, RMX_E_INVAL, "n_buoys %d not in 2..%d", n_buoys, rmx::kSolveMaxBuoys);
     if (!(sample_rate_hz > 0.0)) return fail(c, RMX_E_INVAL, "sample_rate_hz must be positive");
@@ -2077,6 +2086,20 @@ int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32
             if (pairs[q] < 0 || pairs[q] >= n_buoys) return fail(c, RMX_E_INVAL, "pair %d out of range", q / 2);
             pl.push_back(pairs[q]);
         }
+    }
+    // the new entry's own refusals come behind rmx_solve_batch's, so a call that is wrong in both ways reads the same there
+    rmx::SolvePlane spl{};
+    if (fx && fx->plane) {
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(fx->plane[k])) return fail(c, RMX_E_INVAL, "plane[%d] is not finite", k);
+        const double *e1 = fx->plane + 3, *e2 = fx->plane + 6;
+        const double n1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+        const double n2 = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+        const double dot = e1[0] * e2[0] + e1[1] * e2[1] + e1[2] * e2[2];
+        if (!(std::fabs(n1 - 1.0) <= 1e-9) || !(std::fabs(n2 - 1.0) <= 1e-9))
+            return fail(c, RMX_E_INVAL, "plane: |e1| = %.12g, |e2| = %.12g, both must be 1 to 1e-9", n1, n2);
+        if (!(std::fabs(dot) <= 1e-9)) return fail(c, RMX_E_INVAL, "plane: e1 . e2 = %.3g, must be 0 to 1e-9", dot);
+        for (int k = 0; k < 3; ++k) { spl.o[k] = fx->plane[k]; spl.e1[k] = e1[k]; spl.e2[k] = e2[k]; }
     }
     if (n_windows == 0) return RMX_OK;
     RMX_HIP(c, hipSetDevice(c->device));
@@ -2103,22 +2126,69 @@ int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32
     }
     double *d_pos = pos, *d_cost = cost;
     int* d_it = iters;
+    // the outputs at the fix: n_sym doubles a window for info and for cov, n_pairs for resid where it is asked for
+    const bool plane = fx && fx->plane;
+    const size_t n_sym = !fx ? 0 : plane ? 3 : 6, n_res = fx && fx->resid ? (size_t)n_pairs : 0;
+    double *d_info = fx ? fx->info : nullptr, *d_cov = fx ? fx->cov : nullptr, *d_res = fx ? fx->resid : nullptr;
     if (!out_dev) {
-        RMX_MEM(c->sv_out.reserve((size_t)n_windows * (3 * 8 + 8 + 4)));
+        RMX_MEM(c->sv_out.reserve((size_t)n_windows * ((3 + 1 + 2 * n_sym + n_res) * 8 + 4)));
         d_pos = reinterpret_cast<double*>(c->sv_out.get());
         d_cost = d_pos + (size_t)n_windows * 3;
-        d_it = (int*)(d_cost + n_windows);
+        double* end = d_cost + n_windows;
+        if (fx) {
+            d_info = end;
+            d_cov = d_info + (size_t)n_windows * n_sym;
+            end = d_cov + (size_t)n_windows * n_sym;
+            if (n_res) { d_res = end; end += (size_t)n_windows * n_res; }
+        }
+        d_it = (int*)end;
     }
-    const int rc_k = launch(c, kTkNone, k_solve, dim3((n_windows + 63) / 64), dim3(64), 0, c->sv_buoys, n_buoys, c->sv_pairs, n_pairs, d_li, d_lf,
-                            d_wg, 299792458.0 / sample_rate_hz, n_windows, max_iter, d_pos, d_cost, d_it);
+    const dim3 grid((n_windows + 63) / 64), block(64);
+    const double mps = 299792458.0 / sample_rate_hz;
+    int rc_k;
+    if (plane)
+        rc_k = launch(c, kTkNone, k_solve_plane, grid, block, 0, c->sv_buoys, n_buoys, c->sv_pairs, n_pairs, d_li, d_lf, d_wg, mps, spl,
+                      n_windows, max_iter, d_pos, d_cost, d_it);
+    else
+        rc_k = launch(c, kTkNone, k_solve, grid, block, 0, c->sv_buoys, n_buoys, c->sv_pairs, n_pairs, d_li, d_lf,
+                      d_wg, mps, n_windows, max_iter, d_pos, d_cost, d_it);
     if (rc_k != RMX_OK) return rc_k;
+    if (fx) {
+        auto* const k_fix = plane ? &k_solve_fix<true> : &k_solve_fix<false>;
+        rc_k = launch(c, kTkNone, k_fix, grid, block, 0, c->sv_buoys, n_buoys, c->sv_pairs, n_pairs, d_li, d_lf, d_wg, mps, spl, n_windows,
+                      d_pos, d_info, d_cov, d_res);
+        if (rc_k != RMX_OK) return rc_k;
+    }
     if (!out_dev) {
         RMX_HIP(c, hipMemcpyAsync(pos, d_pos, (size_t)n_windows * 3 * 8, hipMemcpyDeviceToHost, c->stream));
         RMX_HIP(c, hipMemcpyAsync(cost, d_cost, (size_t)n_windows * 8, hipMemcpyDeviceToHost, c->stream));
         RMX_HIP(c, hipMemcpyAsync(iters, d_it, (size_t)n_windows * 4, hipMemcpyDeviceToHost, c->stream));
+        if (fx) {
+            RMX_HIP(c, hipMemcpyAsync(fx->info, d_info, (size_t)n_windows * n_sym * 8, hipMemcpyDeviceToHost, c->stream));
+            RMX_HIP(c, hipMemcpyAsync(fx->cov, d_cov, (size_t)n_windows * n_sym * 8, hipMemcpyDeviceToHost, c->stream));
+            if (n_res) RMX_HIP(c, hipMemcpyAsync(fx->resid, d_res, (size_t)n_windows * n_res * 8, hipMemcpyDeviceToHost, c->stream));
+        }
         RMX_HIP(c, hipStreamSynchronize(c->stream));
     }
     return RMX_OK;
+}
+
+int rmx_solve_batch(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32_t* pairs, int n_pairs,
+                    const int32_t* lag_int, const float* lag_frac, const float* weight, double sample_rate_hz,
+                    int n_windows, int max_iter, double* pos, double* cost, int32_t* iters, unsigned flags) {
+    return solve_request(c, buoy_xyz, n_buoys, pairs, n_pairs, lag_int, lag_frac, weight, sample_rate_hz, n_windows, max_iter, pos, cost,
+                         iters, flags, nullptr);
+}
+
+// rmx_solve_batch with the plane and the outputs at the fix: k_solve itself (plane == NULL) or k_solve_plane, then k_solve_fix
+// at the position either wrote, on the ctx stream.
+int rmx_solve_batch_fix(rmx_ctx* c, const double* buoy_xyz, int n_buoys, const int32_t* pairs, int n_pairs,
+                        const int32_t* lag_int, const float* lag_frac, const float* weight, double sample_rate_hz,
+                        const double* plane, int n_windows, int max_iter, double* pos, double* cost, int32_t* iters,
+                        double* info, double* cov, double* resid, unsigned flags) {
+    const SolveFixArgs fx{plane, info, cov, resid};
+    return solve_request(c, buoy_xyz, n_buoys, pairs, n_pairs, lag_int, lag_frac, weight, sample_rate_hz, n_windows, max_iter, pos, cost,
+                         iters, flags, &fx);
 }
 
 int rmx_detect_batch(rmx_ctx* c, const void* iq, int n_windows, int n_samples, float threshold_db, int distance,

@@ -126,6 +126,20 @@ class GeodeticCalculator:
                 math.sqrt(x * x + y * y + z * z) - GeodeticCalculator.EARTH_RADIUS_M)
 
     @staticmethod
+    def tangent_plane(lat: float, lng: float, alt: float = 0.0):
+        """(origin, east, north) in ECEF of the plane that touches this class's sphere, lifted to `alt`, at (lat, lng):
+        three 3-tuples, east and north unit vectors.  origin + east + north, flattened, is the `plane` of
+        XcorrEngine.solve_fix, with u1 metres east and u2 metres north of the origin.
+        The sphere sags below the plane by d^2 / 2R at distance d from the origin: 0.7 m at 3 km, 7.8 m at 10 km, 80 m at
+        32 km.  A fix held to the plane is that much too high there.  For stations near the surface that is harmless: a
+        range difference between two of them barely moves when the emitter's altitude does (the lines of sight are nearly
+        horizontal, so the altitude column of the Jacobian is nearly zero), which is the same fact that makes altitude
+        unobservable for such a fleet and the reason to hold it fixed at all."""
+        phi, lam = math.radians(lat), math.radians(lng)
+        sp, cp, sl, cl = math.sin(phi), math.cos(phi), math.sin(lam), math.cos(lam)
+        return (GeodeticCalculator.lat_lng_to_xyz(lat, lng, alt), (-sl, cl, 0.0), (-sp * cl, -sp * sl, cp))
+
+    @staticmethod
     def distance_3d(lat1, lng1, alt1, lat2, lng2, alt2) -> float:
         a = GeodeticCalculator.lat_lng_to_xyz(lat1, lng1, alt1)
         b = GeodeticCalculator.lat_lng_to_xyz(lat2, lng2, alt2)
@@ -805,19 +819,77 @@ class HyperbolicPositioning:
 
 
     def triangulate_batch(self, engine, buoys: List[BuoyPosition], lag_int, lag_frac, sample_rate_hz: float,
-                          confidence=None, max_iter: int = 60):
+                          confidence=None, max_iter: int = 60, lag_sigma=None, sigma_floor=None, altitude_m=None):
         """Batched form of triangulate_position on the GPU (rmx_solve_batch): one solve per window
         from the lag arrays XcorrEngine.correlate returned for `buoys` (detection-list order, all
         pairs i<j).  Same objective, start point and accuracy formula as the reference
         (tdoa_processor.py:249-300).  confidence: None (every measurement counts 1), [W][P] as the lag arrays, or
         1-D of length P = one confidence row for all windows (XcorrEngine.solve broadcasts the weight row to [W][P]);
-        any other shape is a ValueError.  Returns a list of (lat, lng, altitude, accuracy_meters)."""
+        any other shape is a ValueError.  Returns a list of (lat, lng, altitude, accuracy_meters).
+
+        lag_sigma, sigma_floor, altitude_m: with none of them given the call is the one above.  With any of them the
+        solve is XcorrEngine.solve_fix (rmx_solve_batch_fix) and every tuple gains a fifth element (below).
+        lag_sigma (samples, [W][P] or [P], xcorr.lag_sigma of the lags' quality) with sigma_floor (samples, the stations'
+        clock-sync uncertainty, > 0) weights every pair by xcorr.lag_weight = 1 / sigma_d^2 instead of by confidence: the
+        two go together, and lag_sigma with confidence is a ValueError.
+        altitude_m holds the fix to the tangent plane at the fleet's centroid, lifted to that altitude
+        (GeodeticCalculator.tangent_plane): two unknowns, for stations that float on one surface, whose lags do not
+        observe altitude.
+        The fifth element is a dict: ellipse_m = (semi-major, semi-minor in metres at 95 %, azimuth of the major axis in
+        degrees from north through east, in [0, 180)), or None with three unknowns; drms_m = sqrt of the trace of the
+        horizontal 2 x 2 covariance (with three unknowns: the east/north block of cov at the fix); chi2 = the cost, a
+        chi-square where the weights are 1 / sigma_d^2; dof = the pairs of weight > 0 less the unknowns.
+        accuracy_meters is then drms_m (inf where the information is singular), not sqrt(cost / P)."""
         xyz = np.array([GeodeticCalculator.lat_lng_to_xyz(b.lat, b.lng, b.altitude) for b in buoys])
-        weight = None if confidence is None else 1.0 / (np.asarray(confidence, np.float64) + 0.1)
-        pos, cost, _ = engine.solve(xyz, lag_int, lag_frac, sample_rate_hz, weight=weight, max_iter=max_iter)
-        n_meas = np.asarray(lag_int).shape[1]
-        return [GeodeticCalculator.xyz_to_lat_lng(*p) + (math.sqrt(max(c, 0.0) / n_meas),)
-                for p, c in zip(pos, cost)]
+        if lag_sigma is None and sigma_floor is None and altitude_m is None:
+            weight = None if confidence is None else 1.0 / (np.asarray(confidence, np.float64) + 0.1)
+            pos, cost, _ = engine.solve(xyz, lag_int, lag_frac, sample_rate_hz, weight=weight, max_iter=max_iter)
+            n_meas = np.asarray(lag_int).shape[1]
+            return [GeodeticCalculator.xyz_to_lat_lng(*p) + (math.sqrt(max(c, 0.0) / n_meas),)
+                    for p, c in zip(pos, cost)]
+        from .xcorr import error_ellipse, lag_weight
+        if (lag_sigma is None) != (sigma_floor is None):
+            raise ValueError("lag_sigma and sigma_floor go together: give both or neither")
+        if lag_sigma is not None and confidence is not None:
+            raise ValueError("lag_sigma and confidence both weight the pairs: give one of them")
+        if lag_sigma is not None:
+            weight = lag_weight(lag_sigma, sample_rate_hz, sigma_floor)
+        else:
+            weight = None if confidence is None else 1.0 / (np.asarray(confidence, np.float64) + 0.1)
+        plane = None
+        if altitude_m is not None:
+            c = xyz.mean(axis=0)
+            lat0, lng0, _ = GeodeticCalculator.xyz_to_lat_lng(*c)
+            plane = np.array(GeodeticCalculator.tangent_plane(lat0, lng0, float(altitude_m))).reshape(-1)
+        fix = engine.solve_fix(xyz, lag_int, lag_frac, sample_rate_hz, weight=weight, max_iter=max_iter, plane=plane)
+        W, P = np.asarray(lag_int).shape
+        n_unknowns = 3 if plane is None else 2
+        if weight is None:
+            used = np.full(W, P)
+        else:
+            used = np.count_nonzero(np.broadcast_to(np.asarray(weight, np.float32), (W, P)) > 0, axis=1)
+        out = []
+        for w in range(W):
+            lat, lng, alt = GeodeticCalculator.xyz_to_lat_lng(*fix.pos[w])
+            if plane is not None:
+                c2 = fix.cov[w]
+                major, minor, ang = error_ellipse(c2)
+                ellipse = (float(major), float(minor), (90.0 - math.degrees(float(ang))) % 180.0)
+            else:
+                xx, xy, xz, yy, yz, zz = fix.cov[w]
+                if math.isfinite(xx) and math.isfinite(yy) and math.isfinite(zz):
+                    _, e, n = GeodeticCalculator.tangent_plane(lat, lng)
+                    full = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
+                    en = np.array([e, n])
+                    h = en @ full @ en.T
+                    c2 = (h[0, 0], h[0, 1], h[1, 1])
+                else:
+                    c2 = (math.inf, 0.0, math.inf)
+                ellipse = None
+            drms = math.sqrt(c2[0] + c2[2])
+            out.append((lat, lng, alt, drms, dict(ellipse_m=ellipse, drms_m=drms, chi2=float(fix.cost[w]),
+                                                  dof=int(used[w]) - n_unknowns)))
+        return out
 
 
 # --------------------------------------------------------------------------------------------------

@@ -106,6 +106,8 @@ def load_library():
     lib.rmx_caf_batch_bands.restype = ci
     lib.rmx_solve_batch.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, ci, ci, vp, vp, vp, cu]
     lib.rmx_solve_batch.restype = ci
+    lib.rmx_solve_batch_fix.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, C.c_double, vp, ci, ci, vp, vp, vp, vp, vp, vp, cu]
+    lib.rmx_solve_batch_fix.restype = ci
     lib.rmx_detect_batch.argtypes = [vp, vp, ci, ci, C.c_float, ci, C.c_double, C.c_float, ci, vp, vp, vp, vp, vp, vp, cu]
     lib.rmx_detect_batch.restype = ci
     lib.rmx_synchronize.argtypes = [vp]
@@ -387,6 +389,64 @@ def lag_sigma(quality) -> np.ndarray:
     return np.where(ok, sig, np.inf)
 
 
+SPEED_OF_LIGHT = 299792458.0
+
+
+def lag_weight(sigma_samples, sample_rate_hz: float, sigma_floor_samples: float) -> np.ndarray:
+    """The weight of a lag in the position solve (solve_fix), float32 in m^-2, from its standard deviation in samples
+    (lag_sigma):
+        1 / ((sigma^2 + floor^2) * mps^2),   mps = 299792458 / sample_rate_hz metres per sample.
+    sigma_floor_samples is the stations' clock-synchronisation uncertainty in samples, added in quadrature.  It must be
+    finite and > 0: lag_sigma is 0 at coherence 1, which would otherwise be an infinite weight.  sigma = inf (a dead
+    receiver) gives weight 0: the solve ignores the pair.  A negative or NaN sigma is a ValueError.  numpy only."""
+    floor = float(sigma_floor_samples)
+    if not (math.isfinite(floor) and floor > 0.0):
+        raise ValueError(f"sigma_floor_samples must be finite and > 0, got {sigma_floor_samples}")
+    fs = float(sample_rate_hz)
+    if not (math.isfinite(fs) and fs > 0.0):
+        raise ValueError(f"sample_rate_hz must be finite and positive, got {sample_rate_hz}")
+    sig = np.asarray(sigma_samples, np.float64)
+    if np.any(np.isnan(sig)) or np.any(sig < 0.0):
+        raise ValueError("sigma_samples must be >= 0 (inf allowed) and not NaN")
+    mps = SPEED_OF_LIGHT / fs
+    with np.errstate(over="ignore"):
+        return (1.0 / ((sig * sig + floor * floor) * (mps * mps))).astype(np.float32)
+
+
+def error_ellipse(cov2, confidence: float = 0.95):
+    """The error ellipse of a plane-mode fix from its covariance cov2 [...][3] = 11 12 22 (solve_fix(plane=...).cov).
+    Returns (semi_major, semi_minor, angle): the semi-axes in the covariance's length unit, scaled by
+    sqrt(-2 ln(1 - confidence)) (2.4477 at 0.95: the fix lies inside with that probability under Gaussian errors), and the
+    angle of the major axis in radians from e1 towards e2, in (-pi/2, pi/2].  A singular covariance (inf on its diagonal)
+    gives inf axes and angle 0.  numpy only."""
+    c = np.asarray(cov2, np.float64)
+    if c.shape[-1] != 3:
+        raise ValueError(f"cov2 must be [...][3] (11 12 22), got shape {c.shape}")
+    if not 0.0 < float(confidence) < 1.0:
+        raise ValueError(f"confidence must lie strictly between 0 and 1, got {confidence}")
+    k = math.sqrt(-2.0 * math.log(1.0 - float(confidence)))
+    c11, c12, c22 = c[..., 0], c[..., 1], c[..., 2]
+    ok = np.isfinite(c11) & np.isfinite(c12) & np.isfinite(c22)
+    a, b, d = np.where(ok, c11, 1.0), np.where(ok, c12, 0.0), np.where(ok, c22, 1.0)
+    mean, half = 0.5 * (a + d), 0.5 * (a - d)
+    root = np.sqrt(half * half + b * b)
+    major = np.sqrt(np.maximum(mean + root, 0.0))
+    minor = np.sqrt(np.maximum(mean - root, 0.0))
+    angle = 0.5 * np.arctan2(2.0 * b, a - d)
+    angle = np.where(angle <= -0.5 * math.pi, angle + math.pi, angle)
+    return np.where(ok, k * major, np.inf), np.where(ok, k * minor, np.inf), np.where(ok, angle, 0.0)
+
+
+class SolveFix(NamedTuple):
+    """XcorrEngine.solve_fix: the fix, and what says how far it can be trusted (rmx_solve_batch_fix)"""
+    pos: np.ndarray      # float64 [W][3] ECEF metres
+    cost: np.ndarray     # float64 [W]: f at pos; a chi-square where weight = 1 / sigma_d^2
+    iters: np.ndarray    # int32 [W]
+    info: np.ndarray     # float64 [W][6] xx xy xz yy yz zz (ECEF), or [W][3] 11 12 22 in plane coordinates
+    cov: np.ndarray      # float64, info's inverse in the same layout; inf on the diagonal and 0 off it where singular
+    resid: Optional[np.ndarray]   # float64 [W][P] metres, or None
+
+
 def doppler_estimate(doppler_cps, dop_idx, dop_frac) -> np.ndarray:
     """The frequency offset, float64 in cycles per sample, that caf(..., fine=True) found:
         doppler_cps[dop_idx] + dop_frac * step,   step = the grid's spacing.
@@ -416,7 +476,7 @@ def doppler_estimate(doppler_cps, dop_idx, dop_frac) -> np.ndarray:
 
 
 EXPORTS = ["rmx_version", "rmx_device_count", "rmx_create", "rmx_destroy", "rmx_last_error",
-           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_xcorr_batch_bands_quality", "rmx_xcorr_batch_bands_integrated", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_caf_batch_quality", "rmx_caf_batch_integrated", "rmx_caf_batch_bands", "rmx_solve_batch", "rmx_detect_batch", "rmx_synchronize",
+           "rmx_set_stream", "rmx_set_option", "rmx_set_default_option", "rmx_clear_default_options", "rmx_xcorr_batch", "rmx_xcorr_batch_bounded", "rmx_xcorr_batch_weighted", "rmx_xcorr_batch_bands", "rmx_xcorr_batch_integrated", "rmx_xcorr_batch_refined", "rmx_xcorr_batch_quality", "rmx_xcorr_batch_bands_quality", "rmx_xcorr_batch_bands_integrated", "rmx_caf_batch", "rmx_caf_batch_request", "rmx_caf_batch_quality", "rmx_caf_batch_integrated", "rmx_caf_batch_bands", "rmx_solve_batch", "rmx_solve_batch_fix", "rmx_detect_batch", "rmx_synchronize",
            "rmx_last_timing", "rmx_last_timing_kind", "rmx_build_info", "rmx_scratch_bytes"]
 
 
@@ -698,15 +758,10 @@ class XcorrEngine:
         return self._host_call(lag_request("caf_bands", self.n_buoys, iq.shape[0], pairs, lag_bounds, bands, whiten,
                                            doppler_cps=doppler_cps, fine=fine), iq, flags)
 
-    def solve(self, buoy_xyz, lag_int, lag_frac, sample_rate_hz: float, weight=None,
-              pairs: Optional[np.ndarray] = None, max_iter: int = 60):
-        """Batched hyperbolic position solve (rmx_solve_batch), host arrays in and out.
-        buoy_xyz [B][3] ECEF metres; lag_int/lag_frac [W][P] as returned by correlate().
-        weight: None (every measurement counts 1), float [W][P], or 1-D of length P = one row for all windows, broadcast
-        to [W][P].  pairs: None (all i < j in nested-loop order, P = B (B - 1) / 2) or int [P][2].
-        Returns (pos float64 [W][3], cost float64 [W], iters int32 [W]).
-        The C entry reads W * P elements from each of lag_int, lag_frac and weight, so every shape is checked here first:
-        a ValueError that names the argument, before any C call."""
+    @staticmethod
+    def _solve_request(buoy_xyz, lag_int, lag_frac, sample_rate_hz, weight, pairs, max_iter):
+        """the checks of solve() and solve_fix(): the arrays as the C entry reads them, (bx, li, lf, wgt or None, pairs or
+        None), or a ValueError that names the argument"""
         bx = np.ascontiguousarray(buoy_xyz, dtype=np.float64)
         if bx.size % 3 != 0 or not 2 <= bx.size // 3 <= 64:
             raise ValueError(f"buoy_xyz must reshape to [B][3] with 2 <= B <= 64, got shape {bx.shape}")
@@ -719,7 +774,7 @@ class XcorrEngine:
         if lf.shape != li.shape:
             raise ValueError(f"lag_frac must have lag_int's shape {li.shape}, got {lf.shape}")
         W, P = li.shape
-        wp = None
+        wgt = None
         if weight is not None:
             wgt = np.asarray(weight, dtype=np.float32)
             if wgt.shape == (P,):
@@ -727,30 +782,77 @@ class XcorrEngine:
             elif wgt.shape != (W, P):
                 raise ValueError(f"weight must be None, [{W}][{P}] or [{P}], got shape {wgt.shape}")
             wgt = np.ascontiguousarray(wgt)
-            wp = wgt.ctypes.data_as(C.c_void_p)
-        pp = None
         if pairs is not None:
             pairs = np.ascontiguousarray(pairs, dtype=np.int32)
             if pairs.size != 2 * P:
                 raise ValueError(f"pairs must be [{P}][2] for lag arrays of {P} columns, got shape {pairs.shape}")
             pairs = pairs.reshape(-1, 2)
-            pp = pairs.ctypes.data_as(C.c_void_p)
         elif P != B * (B - 1) // 2:
             raise ValueError(f"pairs is None: lag_int needs {B * (B - 1) // 2} columns for {B} buoys, got {P}")
         if not int(max_iter) >= 1:
             raise ValueError(f"max_iter must be >= 1, got {max_iter}")
         if not float(sample_rate_hz) > 0.0:
             raise ValueError(f"sample_rate_hz must be positive, got {sample_rate_hz}")
+        return bx, li, lf, wgt, pairs
+
+    def solve(self, buoy_xyz, lag_int, lag_frac, sample_rate_hz: float, weight=None,
+              pairs: Optional[np.ndarray] = None, max_iter: int = 60):
+        """Batched hyperbolic position solve (rmx_solve_batch), host arrays in and out.
+        buoy_xyz [B][3] ECEF metres; lag_int/lag_frac [W][P] as returned by correlate().
+        weight: None (every measurement counts 1), float [W][P], or 1-D of length P = one row for all windows, broadcast
+        to [W][P].  pairs: None (all i < j in nested-loop order, P = B (B - 1) / 2) or int [P][2].
+        Returns (pos float64 [W][3], cost float64 [W], iters int32 [W]).
+        The C entry reads W * P elements from each of lag_int, lag_frac and weight, so every shape is checked here first:
+        a ValueError that names the argument, before any C call."""
+        bx, li, lf, wgt, pairs = self._solve_request(buoy_xyz, lag_int, lag_frac, sample_rate_hz, weight, pairs, max_iter)
+        W, P = li.shape
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
         pos = np.zeros((W, 3), np.float64)
         cost = np.zeros(W, np.float64)
         iters = np.zeros(W, np.int32)
         if W == 0:
             return pos, cost, iters
         self._check(self._lib.rmx_solve_batch(
-            self._ctx, bx.ctypes.data_as(C.c_void_p), bx.shape[0], pp, P, li.ctypes.data_as(C.c_void_p),
-            lf.ctypes.data_as(C.c_void_p), wp, float(sample_rate_hz), W, int(max_iter),
-            pos.ctypes.data_as(C.c_void_p), cost.ctypes.data_as(C.c_void_p), iters.ctypes.data_as(C.c_void_p), 0))
+            self._ctx, vp(bx), bx.shape[0], vp(pairs), P, vp(li), vp(lf), vp(wgt), float(sample_rate_hz), W, int(max_iter),
+            vp(pos), vp(cost), vp(iters), 0))
         return pos, cost, iters
+
+    def solve_fix(self, buoy_xyz, lag_int, lag_frac, sample_rate_hz: float, weight=None,
+                  pairs: Optional[np.ndarray] = None, max_iter: int = 60, plane=None, residuals: bool = False) -> SolveFix:
+        """solve() with a surface constraint and the information at the fix (rmx_solve_batch_fix), host arrays in and out.
+        buoy_xyz, lag_int, lag_frac, weight, pairs, max_iter: as for solve(); with plane=None pos, cost and iters are
+        solve()'s bit for bit.  plane: None (three unknowns) or 9 floats = origin, e1, e2 in ECEF, e1 and e2 orthonormal to
+        1e-9 (GeodeticCalculator.tangent_plane): the fix is held to that plane, two unknowns.  residuals=True also returns
+        every pair's residual in metres.
+        Returns SolveFix(pos [W][3], cost [W], iters [W], info, cov [W][6] (xx xy xz yy yz zz, ECEF) or, with a plane,
+        [W][3] (11 12 22, plane coordinates), resid [W][P] or None).  Where the information is singular cov is inf on its
+        diagonal and 0 off it.  With weight = lag_weight(lag_sigma(quality), ...) cov is the covariance of the fix under
+        independent pair errors (error_ellipse draws it) and cost a chi-square; all pairs of B stations share receivers, so
+        that covariance is optimistic.  Every shape is checked here first, as in solve(): a ValueError that names the
+        argument, before any C call."""
+        bx, li, lf, wgt, pairs = self._solve_request(buoy_xyz, lag_int, lag_frac, sample_rate_hz, weight, pairs, max_iter)
+        W, P = li.shape
+        pl = None
+        if plane is not None:
+            pl = np.ascontiguousarray(plane, dtype=np.float64).reshape(-1)
+            if pl.size != 9:
+                raise ValueError(f"plane must be None or 9 values (origin, e1, e2), got shape {np.shape(plane)}")
+            if not np.all(np.isfinite(pl)):
+                raise ValueError("plane must be finite")
+            e1, e2 = pl[3:6], pl[6:9]
+            if abs(math.sqrt(e1 @ e1) - 1.0) > 1e-9 or abs(math.sqrt(e2 @ e2) - 1.0) > 1e-9 or abs(e1 @ e2) > 1e-9:
+                raise ValueError("plane: e1 and e2 must be orthonormal to 1e-9")
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        n_sym = 6 if pl is None else 3
+        out = SolveFix(np.zeros((W, 3), np.float64), np.zeros(W, np.float64), np.zeros(W, np.int32),
+                       np.zeros((W, n_sym), np.float64), np.zeros((W, n_sym), np.float64),
+                       np.zeros((W, P), np.float64) if residuals else None)
+        if W == 0:
+            return out
+        self._check(self._lib.rmx_solve_batch_fix(
+            self._ctx, vp(bx), bx.shape[0], vp(pairs), P, vp(li), vp(lf), vp(wgt), float(sample_rate_hz), vp(pl), W,
+            int(max_iter), vp(out.pos), vp(out.cost), vp(out.iters), vp(out.info), vp(out.cov), vp(out.resid), 0))
+        return out
 
     def detect(self, iq: np.ndarray, threshold_db: float = -70.0, distance: int = 10, dc_exclude_bins: float = 0.0,
                min_confidence: float = 0.3, max_peaks: int = 2048):
